@@ -15,9 +15,9 @@ Envs shard over GPUs by env id with no data-path collective (scaling "weak"); th
 configs 4/5 name is timed separately and reported under "allgather", never mixed into `value`.
 
 ONE clock: `value`, `ms_per_step` and `roofline.achieved / frac / read_frac` all come from the same host wall-clock
-interval (barrier + synchronize on both sides, max over ranks).  The interval holds R back-to-back blocks of EXACTLY K
-steps (R chosen so that R*K >= --min-timed-steps): a 20-step interval is shorter than the synchronisation that closes it
-(~30 us), so the per-step time is only meaningful over a few thousand steps.  Beside it, under their own names: the
+interval (barrier + synchronize on both sides, max over ranks).  The interval holds EXACTLY K = --steps steps after W =
+--warmup untimed ones; the synchronisation that closes it costs ~30 us, so the per-step time is only meaningful over a few
+thousand steps (a 20-step interval is shorter than that synchronisation).  Beside it, under their own names: the
 HIP-event time of the same launches (`roofline.gpu_timeline_*`), the in-kernel s_memrealtime timeline of the same chain
 from the committed stamped-build run (`roofline.stamp_*`) and the rocprofv3 kernel average of the committed profile
 (`roofline.rocprof_*`, computed from the launch shape that profile was TAKEN with -- its sidecar json).
@@ -28,9 +28,18 @@ outputs of a step consumable after the roll-out (qs_sync, or the stream-ordered 
 between two steps.  The rate a per-step `obs -> policy -> env.step` loop gets is `hip_stream_mode` (every launch releases)
 and `policy_between_steps`; `config.mode` / `config.outputs_consumable` say so in the line.
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline", "parity" (fixtures g4 / g5 / g7 / g1 = outputs of the NumPy
-reference replayed through the C ABI), "cpu_baseline" (the C oracle on the host cores + what the reference itself would
-reach there), "config1", "hip_stream_mode", "policy_between_steps", "rollout_stepwise", "step_api_131072_envs", ...
+Prints ONE JSON line (rank 0) with the headline and its "roofline" (derived from the same clock and the committed profiles;
+no run of its own).  A plain run does nothing else: it sets up, picks and settles the launch path, warms up, times the K
+steps, writes the last step's outputs if --dump-outputs DIR is given, and prints the line.  --full adds every other leg:
+"parity" (fixtures g4 / g5 / g7 / g1 = outputs of the NumPy reference replayed through the C ABI), "cpu_baseline" (the C
+oracle on the host cores + what the reference itself would reach there), "config1", "hip_stream_mode",
+"actions_cache_resident", "policy_between_steps", "rollout_stepwise", "step_api_131072_envs", ...; its side legs time R =
+ceil(--min-timed-steps / K) blocks of K steps each.
+
+--dump-outputs DIR: what the timed path handed its caller in its last timed step (qs_step's observation, reward, done, flags
+and terminal observation) as float32 DIR/<name>.npy, at most 64 MB in all (above that, a fixed seeded sample of env rows,
+their ids in env_index.npy).  The timed steps start from the env's state right after its reset, restored after the
+launch-path probes and the settling steps, so the same arguments give the same outputs in every run.
 """
 import argparse
 import json
@@ -84,13 +93,17 @@ def parse():
                         "step); hip: ordinary launches on the HIP stream; auto: private if it opens AND reproduces the HIP-stream "
                         "chain bit for bit on this machine, else hip")
     p.add_argument("--min-timed-steps", type=int, default=2000,
-                   help="the timed interval holds R = ceil(this / K) back-to-back blocks of K steps")
+                   help="--full side legs: their timed interval holds R = ceil(this / K) back-to-back blocks of K steps")
     p.add_argument("--rollout-T", type=int, default=64, help="steps per launch of the fused roll-out leg")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extras", action="store_true", help="skip every leg but the headline (and parity / cpu_baseline)")
-    p.add_argument("--no-parity", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="run every leg beside the headline too (parity, CPU baseline, other modes / sizes / precisions)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step to DIR/<name>.npy (float32, at most 64 MB)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline / config1")
+    p.add_argument("--no-extras", action="store_true", help="with --full: skip every leg but the headline (and parity / cpu_baseline)")
+    p.add_argument("--no-parity", action="store_true", help="with --full: skip the parity leg")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
-    p.add_argument("--repeats", type=int, default=3, help="timed intervals; the median one is reported")
+    p.add_argument("--repeats", type=int, default=1, help="timed intervals of K steps each; the median one is reported")
     p.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                    help="nccl (= RCCL over xGMI, the real thing) or gloo (rehearsal of the multi-rank control flow, "
                         "e.g. several ranks sharing one GPU; skips the all-gather leg)")
@@ -109,6 +122,7 @@ def parse():
 
 
 DEFAULT_GROUPS = 1   # measured on MI355X (profiles/r02/groups_sweep.txt): more chains in flight do not raise the rate
+SETTLE_STEPS = 2000  # untimed steps on the chosen launch path before the headline's own warm-up (see settle_and_restart)
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -427,6 +441,40 @@ def rocprof_kernel_average(kernel_substr, fname):
     return None
 
 
+DUMP_BYTES = 64 * 1000 * 1000 - 4096      # --dump-outputs: all files of one run together, .npy headers included
+DUMP_SEED = 20251015                       # the env-row sample above that size: the same rows in every run
+
+
+def dump_outputs(path, env, rank, world, lo):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step -- qs_step's observation, reward, done,
+    flags and terminal observation (rows of envs that did not finish zeroed: a caller only reads it where done) -- as float32
+    .npy files.  Above the budget, a fixed seeded sample of env rows, sorted, with their global env ids in env_index.npy.
+    Several ranks: each writes its own shard as rank<r>_<name>.npy within its share of the budget.  Called after the timed
+    interval has been drained and synchronised (time_steps)."""
+    import numpy as np
+    n = env.num_envs
+    done = env._done.cpu().numpy().astype(bool)
+    arrays = {"obs": env._obs.cpu().numpy(),
+              "reward": env._rew.cpu().numpy(),
+              "done": done.astype(np.float32),
+              "flags": env._flags.cpu().numpy().astype(np.float32),
+              "terminal_obs": np.where(done[:, None], env._term.cpu().numpy(), np.float32(0.0)).astype(np.float32)}
+    row_bytes = sum(a.nbytes for a in arrays.values()) // n
+    budget = DUMP_BYTES // world - 1024 * (len(arrays) + 1)
+    idx = np.arange(n)
+    if n * row_bytes > budget:
+        m = budget // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["env_index"] = (lo + idx).astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    prefix = "" if world == 1 else "rank%d_" % rank
+    for k, v in arrays.items():
+        np.save(os.path.join(path, prefix + k + ".npy"), np.ascontiguousarray(v))
+    return {"dir": path, "files": sorted(prefix + k + ".npy" for k in arrays), "envs": int(len(idx)),
+            "sampled": bool(len(idx) < n), "step": "last timed step"}
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -585,16 +633,33 @@ def main():
         return ("private" if queues else "hip"), queues, "; ".join(notes)
 
     K, W = args.steps, args.warmup
-    R = max(1, -(-args.min_timed_steps // K))
+    if K < 1 or W < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    R = max(1, -(-args.min_timed_steps // K))          # the --full side legs' blocks of K steps; the headline times K steps
     env = make_env(args.integrator)
     env.reset()
     if groups > 1:
         groups = env.set_groups(groups, threads=bool(args.group_threads))
-    P = max(1, min(args.action_pool, K * R, (1 << 29) // (n * 16)))      # at most 512 MiB of action batches
+    P = max(1, min(args.action_pool, (1 << 29) // (n * 16)))      # at most 512 MiB of action batches
     pool = env.random_actions(P, step0=0)               # [P,N,4] U(-1,1), resident in HBM before timing
+    # the state right after the reset, restored before the timed steps: they start from it in every run of the same arguments,
+    # whatever the probes and the settling steps did (q_des persists over resets, so a second reset would not bring it back)
+    start = env.get_state(as_numpy=False)
+    start_par = env.get_params() if args.randomise >= 2 else None
     queue_mode, queues, queue_note = pick_launch_path(env, lambda: make_env(args.integrator), pool, 1000)
+
+    def settle_and_restart():
+        """the first ~2 000 steps of a newly opened launch path run a few per cent slower than the rest: they are stepped here,
+        untimed, then the env is put back to its post-reset state and step counter 0"""
+        time_steps(env, SETTLE_STEPS, 1, 0, pool, groups)
+        env.set_state(**start)
+        if start_par is not None:
+            env.set_params(*start_par)
+        env.step_counter = 0
+
     try:
-        runs = [time_steps(env, K, R, W, pool, groups) for _ in range(max(1, args.repeats))]
+        settle_and_restart()
+        runs = [time_steps(env, K, 1, W, pool, groups) for _ in range(max(1, args.repeats))]
         guard = None
     except qa.QuadsimError as ex:
         # the private queue's placement guard fired while timing (seen when several processes share one GPU: another process's
@@ -611,11 +676,14 @@ def main():
             env.set_queue_mode(False)
         except qa.QuadsimError:
             env.set_queue_mode(False)                       # the first call reports the pending error, the second switches
-        env.reset()
-        runs = [time_steps(env, K, R, W, pool, groups) for _ in range(max(1, args.repeats))]
+        settle_and_restart()
+        runs = [time_steps(env, K, 1, W, pool, groups) for _ in range(max(1, args.repeats))]
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, env, rank, world, lo)
     order = sorted(range(len(runs)), key=lambda i: runs[i][0])
     wall, ev_ms = runs[order[len(order) // 2]]
-    steps_timed = K * R
+    steps_timed = K
+    steps_side = K * R
     value = total_envs * steps_timed / wall
     bpe = BYTES_PER_ENV_STEP_DR if args.randomise >= 2 else BYTES_PER_ENV_STEP
     rbpe = 176 if bpe == 392 else 192
@@ -652,10 +720,10 @@ def main():
         "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W,
         "ms_per_step": wall * 1e3 / steps_timed, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
-        "timed_region": {"blocks_of_K_steps": R, "steps_timed": steps_timed, "wall_s": wall,
-                         "policy": "median of %d intervals; each = %d untimed + %d x %d timed steps between barrier + "
+        "timed_region": {"steps_timed": steps_timed, "wall_s": wall,
+                         "policy": "median of %d interval(s); each = %d untimed + %d timed steps between barrier + "
                                    "synchronize; value, ms_per_step and roofline.frac all derive from this one wall clock"
-                                   % (len(runs), W, R, K),
+                                   % (len(runs), W, K),
                          "env_steps_per_s_all_intervals": [total_envs * steps_timed / r[0] for r in runs]},
         "config": {"workload": workload, "baseline_config": tag,
                    "envs_per_gpu": n, "total_envs": total_envs, "env": args.env, "integrator": args.integrator,
@@ -730,7 +798,11 @@ def main():
 
     if queue_note:
         out["config"]["queue_note"] = queue_note
-    if queue_mode == "private" and not args.no_extras:
+    if args.dump_outputs:
+        out["outputs"] = dumped
+    # everything below the headline runs with --full only: a plain run is set-up, warm-up, the K timed steps and the line
+    side_legs = args.full and not args.no_extras
+    if queue_mode == "private" and side_legs:
         # the headline cycles several hundred distinct action batches (every step reads actions the caches have never seen);
         # straight behind a policy kernel the actions are cache-resident instead: the same chain with a 16-batch pool
         best = None
@@ -740,40 +812,40 @@ def main():
                 wq, _ = time_steps(env, K, R, min(W, 50), pool[:16])
                 if best is None or wq < best[0]:
                     best = (wq, q)
-            out["actions_cache_resident"] = {"value": total_envs * steps_timed / best[0], "unit": "env-steps/s", "private_queues": best[1],
-                                             "step_period_us": best[0] * 1e6 / steps_timed,
-                                             "frac": frac_of(best[0] * 1e6 / steps_timed),
+            out["actions_cache_resident"] = {"value": total_envs * steps_side / best[0], "unit": "env-steps/s", "private_queues": best[1],
+                                             "step_period_us": best[0] * 1e6 / steps_side,
+                                             "frac": frac_of(best[0] * 1e6 / steps_side),
                                              "what": "16-batch action pool (%d MB) instead of the headline's %d batches (%.0f MB)"
                                                      % (16 * n * 16 // 1000000, P, P * n * 16 / 1e6)}
             env.set_queue_mode(True, queues, ordering="host")
         except qa.QuadsimError as ex:
             out["actions_cache_resident"] = {"invalid": "the placement guard fired during this leg: %s" % ex}
             env.reset()
-    if queue_mode == "private" and args.no_extras:
+    if queue_mode == "private" and not side_legs:
         env.set_queue_mode(False)                          # nothing below steps this env again (profiling runs: no HIP-stream twin)
     elif queue_mode == "private":
         # the same chain as ordinary HIP launches: every kernel ends with the agent-scope release, i.e. every step's outputs are
         # consumable by the next kernel on the stream -- the rate of a per-step `obs -> policy -> env.step` loop's env side
         env.set_queue_mode(False)
         wh, msh = time_steps(env, K, R, min(W, 50), pool, 1)
-        out["hip_stream_mode"] = {"value": total_envs * steps_timed / wh, "unit": "env-steps/s", "step_period_us": wh * 1e6 / steps_timed,
-                                  "frac": frac_of(wh * 1e6 / steps_timed), "read_frac": frac_of(wh * 1e6 / steps_timed, rbpe),
-                                  "gpu_timeline_us_per_step": msh * 1e3 / steps_timed,
+        out["hip_stream_mode"] = {"value": total_envs * steps_side / wh, "unit": "env-steps/s", "step_period_us": wh * 1e6 / steps_side,
+                                  "frac": frac_of(wh * 1e6 / steps_side), "read_frac": frac_of(wh * 1e6 / steps_side, rbpe),
+                                  "gpu_timeline_us_per_step": msh * 1e3 / steps_side,
                                   "what": "identical launches through hipLaunchKernel on the HIP stream (agent-scope release after every "
                                           "kernel: outputs consumable per step, in stream order)"}
-    if not args.no_parity and rank == 0:
+    if args.full and not args.no_parity and rank == 0:
         out["parity"] = parity_vs_reference(qa, local_rank)
 
-    if not args.no_extras:
+    if side_legs:
         extras(args, out, env, pool, make_env, time_steps, verify_private_queue, barrier, max_over_ranks, queue_mode, queues,
                dict(n=n, world=world, rank=rank, local_rank=local_rank, total_envs=total_envs, K=K, R=R, W=W, P=P, bpe=bpe, rbpe=rbpe,
-                    groups=groups, steps_timed=steps_timed, distributed=distributed))
+                    groups=groups, steps_timed=steps_side, distributed=distributed))
 
     # the CPU legs run on rank 0 whatever the world size (they are CPU-only; the other ranks wait in the barrier below)
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(kind, args.cpu_seconds)
         out["config1"] = config1_cpu()
-    elif rank == 0:
+    elif rank == 0 and args.full:
         out["cpu_baseline"] = None
     env.close()
     if distributed:

@@ -309,3 +309,65 @@ def test_bench_maps_gpu_count_to_baseline_configs(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--env", "docking-v0"])
     a = bench.parse()
     assert a.env == "docking-v0" and a.envs_per_gpu == 131072 and a.config_tag is None
+
+
+def test_bench_plain_and_full_options(monkeypatch):
+    """a plain `bench.py --gpus 1 --steps K --warmup W` times exactly K steps once and runs no side leg; --full and
+    --dump-outputs are opt-in"""
+    import importlib
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.repeats, a.full, a.dump_outputs) == (20, 5, 1, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+class _FakeEnv:
+    """what dump_outputs reads of a VecDockingEnv: the buffers qs_step writes"""
+
+    def __init__(self, n, seed=0):
+        import torch
+        g = torch.Generator().manual_seed(seed)
+        self.num_envs = n
+        self._obs = torch.randn((n, 12), generator=g)
+        self._rew = torch.randn((n,), generator=g)
+        self._done = (torch.rand((n,), generator=g) < 0.1).to(torch.uint8)
+        self._flags = torch.randint(0, 32, (n,), generator=g, dtype=torch.uint8)
+        self._term = torch.randn((n, 12), generator=g)
+
+
+def test_bench_dump_outputs_small_is_complete(tmp_path):
+    import importlib
+    bench = importlib.import_module("bench")
+    env = _FakeEnv(1000)
+    info = bench.dump_outputs(str(tmp_path), env, 0, 1, 0)
+    assert not info["sampled"] and info["envs"] == 1000
+    assert sorted(os.listdir(tmp_path)) == ["done.npy", "flags.npy", "obs.npy", "reward.npy", "terminal_obs.npy"]
+    for name in os.listdir(tmp_path):
+        assert np.load(tmp_path / name).dtype in (np.float32, np.float64), name
+    np.testing.assert_array_equal(np.load(tmp_path / "obs.npy"), env._obs.numpy())
+    done = env._done.numpy().astype(bool)
+    np.testing.assert_array_equal(np.load(tmp_path / "done.npy"), done.astype(np.float32))
+    term = np.load(tmp_path / "terminal_obs.npy")
+    np.testing.assert_array_equal(term[done], env._term.numpy()[done])
+    assert not term[~done].any()
+
+
+def test_bench_dump_outputs_large_is_a_fixed_sample_within_64mb(tmp_path):
+    """above 64 MB: the same seeded, sorted sample of env rows in every run, with its env ids"""
+    import importlib
+    bench = importlib.import_module("bench")
+    n = 1 << 20                                              # 108 B per env row -> 113 MB unsampled
+    env = _FakeEnv(n)
+    a, b = tmp_path / "a", tmp_path / "b"
+    info = bench.dump_outputs(str(a), env, 0, 1, 0)
+    bench.dump_outputs(str(b), _FakeEnv(n), 0, 1, 0)
+    assert info["sampled"] and 0 < info["envs"] < n
+    assert sum(os.path.getsize(a / f) for f in os.listdir(a)) <= 64 * 1000 * 1000
+    idx = np.load(a / "env_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and len(idx) == info["envs"]
+    for f in os.listdir(a):
+        np.testing.assert_array_equal(np.load(a / f), np.load(b / f))
+    np.testing.assert_array_equal(np.load(a / "reward.npy"), env._rew.numpy()[idx.astype(np.int64)])

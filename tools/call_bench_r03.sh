@@ -3,9 +3,9 @@
 # config for N, non-null roofline and cpu_baseline, RCCL initialised and used where the backend is nccl.
 set -o pipefail
 R=$(pwd); OUT=$R/gpurun_out/r03; mkdir -p $OUT
-timeout -k 10 500 python3 bench.py --gpus 2 --backend gloo > $OUT/bench_gloo2.json 2> $OUT/bench_gloo2.err; echo "gloo2 rc=$?"
-timeout -k 10 400 python3 bench.py --gpus 4 --backend gloo --no-extras --cpu-seconds 6 > $OUT/bench_gloo4.json 2> $OUT/bench_gloo4.err; echo "gloo4 rc=$?"
-QS_BENCH_FORCE_DIST=1 timeout -k 10 500 python3 bench.py > $OUT/bench_rccl_world1.json 2> $OUT/bench_rccl_world1.err; echo "rccl world 1 rc=$?"
+timeout -k 10 500 python3 bench.py --full --gpus 2 --backend gloo > $OUT/bench_gloo2.json 2> $OUT/bench_gloo2.err; echo "gloo2 rc=$?"
+timeout -k 10 400 python3 bench.py --full --gpus 4 --backend gloo --no-extras --cpu-seconds 6 > $OUT/bench_gloo4.json 2> $OUT/bench_gloo4.err; echo "gloo4 rc=$?"
+QS_BENCH_FORCE_DIST=1 timeout -k 10 500 python3 bench.py --full > $OUT/bench_rccl_world1.json 2> $OUT/bench_rccl_world1.err; echo "rccl world 1 rc=$?"
 for f in bench_gloo2 bench_gloo4 bench_rccl_world1; do python3 - <<PY
 import json
 try:
