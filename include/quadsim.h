@@ -386,6 +386,41 @@ int qs_runner_rollout_fast(QsEnv *env, int64_t T, const void *packed_weights, co
                            float *last_values, uint8_t *last_dones);
 int qs_runner_rollout_fast_blob_bytes(void);
 
+/* The Runner of qs_runner_rollout(_fast) for either actor-critic layout the reference trains, both ReLU, 12 -> 4 actions:
+ *   QS_NET_SHARED_TRUNK  net_arch [128, dict(pi=[128], vf=[128])] (trained_model/best_model_v0.zip): the network of
+ *                        qs_runner_rollout, same kernels and bits;
+ *   QS_NET_TOWERS        net_arch [dict(pi=[128, 128], vf=[128, 128])] (every ppo2_docking*.zip, run_docking_gail.py:56):
+ *                        separate policy and value towers, each with its own first layer on the observation.
+ * All weights are device pointers, transposed to (out, in) as in QsActorCritic.  quadsim_amd.load_sb2_model reads
+ * either layout from a stable-baselines PPO2 archive. */
+enum { QS_NET_SHARED_TRUNK = 0, QS_NET_TOWERS = 1 };
+typedef struct QsActorCriticNet {
+    uint32_t struct_size;       /* sizeof(QsActorCriticNet) */
+    int32_t squash;
+    int32_t layout;             /* QS_NET_* */
+    int32_t reserved;           /* 0 */
+    const float *wt1, *b1;      /* shared: shared_fc0 [128,12];  towers: pi_fc0 [128,12] */
+    const float *wt2, *b2;      /* shared: pi_fc0 [128,128];     towers: pi_fc1 [128,128] */
+    const float *wt3, *b3;      /* pi [4,128], [4] */
+    const float *wtv1, *bv1;    /* towers: vf_fc0 [128,12], [128];  shared: unused (NULL) */
+    const float *wtv2, *bv2;    /* shared: vf_fc0 [128,128];     towers: vf_fc1 [128,128] */
+    const float *wtv3, *bv3;    /* vf [1,128], [1] */
+    float logstd[4];            /* pi/logstd (host values) */
+} QsActorCriticNet;
+/* exact-float32 heads; arguments after `policy` as qs_runner_rollout */
+int qs_runner_rollout_net(QsEnv *env, int64_t T, const QsActorCriticNet *policy, const float *noise, const uint8_t *dones_in,
+                          float *mb_obs, float *mb_actions, float *mb_values, float *mb_neglogp, uint8_t *mb_dones,
+                          float *mb_rewards, uint8_t *mb_flags, float *last_obs, float *last_values, uint8_t *last_dones);
+/* split-bf16 heads as qs_runner_rollout_fast; packed_weights: device image of qs_runner_rollout_net_fast_blob_bytes(layout)
+ * bytes, 16-byte aligned.  QS_NET_TOWERS: the shared-trunk image built from pi_fc0 / pi_fc1 / pi / vf_fc1 / vf, followed by
+ * vf_fc0^T as float32 [128][13] (column 12 zero) and its bias [128] (quadsim_amd.runner.pack_fast_actor_critic). */
+int qs_runner_rollout_net_fast(QsEnv *env, int64_t T, int32_t layout, const void *packed_weights, const float *logstd,
+                               int squash, const float *noise, const uint8_t *dones_in, float *mb_obs, float *mb_actions,
+                               float *mb_values, float *mb_neglogp, uint8_t *mb_dones, float *mb_rewards, uint8_t *mb_flags,
+                               float *last_obs, float *last_values, uint8_t *last_dones);
+/* bytes of the packed image for `layout`, or QS_ERR_INVALID */
+int qs_runner_rollout_net_fast_blob_bytes(int32_t layout);
+
 /* PID expert of run_expert_policy.py:49-69 / run_expert_record.py:121-136 for all N docking envs: from the handle's
  * current chaser / target states, des_vel = kp (p_target + (-0.2,0,0) - p_chaser) + kd (-v_chaser), vel_controller on
  * the chaser, action = (inv(rotor2control) u - action_mean) / action_std (not clipped).  state_des [N,13] in/out is

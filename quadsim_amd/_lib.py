@@ -30,6 +30,7 @@ EXPORTS = [
     "qs_drone_step", "qs_ctrl", "qs_rel_obs", "qs_transform", "qs_gae", "qs_swap_and_flatten", "qs_expert_action", "qs_policy_rollout", "qs_policy_rollout_fast", "qs_policy_rollout_fast_blob_bytes",
     "qs_policy_forward", "qs_policy_forward_fast",
     "qs_runner_rollout", "qs_runner_rollout_fast", "qs_runner_rollout_fast_blob_bytes",
+    "qs_runner_rollout_net", "qs_runner_rollout_net_fast", "qs_runner_rollout_net_fast_blob_bytes",
     "qs_step_ex", "qs_set_groups", "qs_group_count", "qs_group_range", "qs_group_stream", "qs_group_set_stream",
     "qs_step_group", "qs_step_groups", "qs_groups_fork", "qs_groups_join",
     "qs_swap_and_flatten_u8", "qs_gae_flatten", "qs_episode_stats", "qs_set_rollout_layout",
@@ -54,6 +55,18 @@ class QsActorCritic(C.Structure):
         ("wt1", C.c_void_p), ("b1", C.c_void_p), ("wt2", C.c_void_p), ("b2", C.c_void_p),
         ("wt3", C.c_void_p), ("b3", C.c_void_p), ("wtv2", C.c_void_p), ("bv2", C.c_void_p),
         ("wtv3", C.c_void_p), ("bv3", C.c_void_p), ("logstd", C.c_float * 4),
+    ]
+
+
+NET_SHARED_TRUNK, NET_TOWERS = 0, 1
+
+
+class QsActorCriticNet(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("squash", C.c_int32), ("layout", C.c_int32), ("reserved", C.c_int32),
+        ("wt1", C.c_void_p), ("b1", C.c_void_p), ("wt2", C.c_void_p), ("b2", C.c_void_p),
+        ("wt3", C.c_void_p), ("b3", C.c_void_p), ("wtv1", C.c_void_p), ("bv1", C.c_void_p),
+        ("wtv2", C.c_void_p), ("bv2", C.c_void_p), ("wtv3", C.c_void_p), ("bv3", C.c_void_p), ("logstd", C.c_float * 4),
     ]
 
 
@@ -144,6 +157,9 @@ def load():
         "qs_runner_rollout": [vp, i64, C.POINTER(QsActorCritic)] + [vp] * 12,
         "qs_runner_rollout_fast": [vp, i64, vp, C.POINTER(C.c_float), i32] + [vp] * 12,
         "qs_runner_rollout_fast_blob_bytes": [],
+        "qs_runner_rollout_net": [vp, i64, C.POINTER(QsActorCriticNet)] + [vp] * 12,
+        "qs_runner_rollout_net_fast": [vp, i64, i32, vp, C.POINTER(C.c_float), i32] + [vp] * 12,
+        "qs_runner_rollout_net_fast_blob_bytes": [i32],
         "qs_step_ex": [vp] * 8,
         "qs_set_groups": [vp, i32, i32],
         "qs_group_count": [vp, C.POINTER(i32)],

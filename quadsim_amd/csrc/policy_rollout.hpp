@@ -589,13 +589,15 @@ __device__ __forceinline__ int lds_opaque(int off)
     return off;
 }
 
+// W1OFF / B1OFF: byte offsets of the layer's f32 W1^T (128 x 13) and bias in the image (the tower layout's value branch has its own)
+template <int W1OFF = kAcFastW1, int B1OFF = kAcFastB>
 __device__ __forceinline__ void ac_fast_layer1(const char *blob, const float *stage, int lane, u32x4 (&bh)[4][4], u32x4 (&bl)[4][4])
 {
     lane = lds_opaque(lane);       // lane-derived addresses are re-derived here every step instead of living across the step loop
     const int c = lane & 15, g = lane >> 4;
     // one base register per array, the (row tile, k-step, env tile) part in the offset fields (see lds_opaque)
-    const float *w1 = reinterpret_cast<const float *>(blob + lds_opaque(kAcFastW1 + (c * kLdW1 + g) * 4));   // + 16 rt kLdW1 + 4 s
-    const float *b1 = reinterpret_cast<const float *>(blob + lds_opaque(kAcFastB + 16 * g));                  // + 16 rt
+    const float *w1 = reinterpret_cast<const float *>(blob + lds_opaque(W1OFF + (c * kLdW1 + g) * 4));        // + 16 rt kLdW1 + 4 s
+    const float *b1 = reinterpret_cast<const float *>(blob + lds_opaque(B1OFF + 16 * g));                     // + 16 rt
     const float *xs = stage + lds_opaque(g * 64 + c);                                                         // + 256 s + 16 et
     float xb[3][4];
 #pragma unroll
@@ -702,14 +704,15 @@ __device__ __forceinline__ void ac_exact_layer1(const AcLds &L, const float *sta
     }
 }
 
-template <int BR>
+// LDW2: row stride (floats) of W2p^T / W2v^T (the tower image interleaves the two: kLdW2T)
+template <int BR, int LDW2 = kLdW>
 __device__ __forceinline__ void ac_exact_branch(const AcLds &L, const f32x4 (&h1)[8][4], int lane, f32x4 (&a3)[4])
 {
     const int c = lane & 15, g = lane >> 4;
     const f32x4 bias3 = *reinterpret_cast<const f32x4 *>(L.B3 + 4 * g);
 #pragma unroll
     for (int et = 0; et < 4; ++et) a3[et] = bias3;
-    const float *W2 = (BR ? L.W2v : L.W2p) + c * kLdW + 4 * g;          // + 16 nt kLdW + 16 rt
+    const float *W2 = (BR ? L.W2v : L.W2p) + c * LDW2 + 4 * g;          // + 16 nt LDW2 + 16 rt
     const float *B2 = (BR ? L.B2v : L.B2p) + 4 * g;                     // + 16 nt
     // output-layer A operand: row c of the 16-row tile; only rows 0..3 (policy) / row 4 (value) are non-zero -- every other
     // row reads 16 zero bytes (slots 8..11 of the padded b3): an address select, no branch in the MFMA stream
@@ -728,7 +731,7 @@ __device__ __forceinline__ void ac_exact_branch(const AcLds &L, const f32x4 (&h1
 #pragma unroll
         for (int rt = 0; rt < 8; ++rt) {
             const int G = 8 * nt + rt;
-            if (G + 1 < 64) wbuf[(G + 1) & 1] = *reinterpret_cast<const f32x4 *>(W2 + 16 * ((G + 1) >> 3) * kLdW + 16 * ((G + 1) & 7));
+            if (G + 1 < 64) wbuf[(G + 1) & 1] = *reinterpret_cast<const f32x4 *>(W2 + 16 * ((G + 1) >> 3) * LDW2 + 16 * ((G + 1) & 7));
             const f32x4 w = wbuf[G & 1];
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -746,6 +749,117 @@ __device__ __forceinline__ void ac_exact_branch(const AcLds &L, const f32x4 (&h1
             for (int et = 0; et < 4; ++et) a3[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(w3[i], r[et][i], a3[et], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Tower actor-critic: the OTHER layout the reference trains and ships (every ppo2_docking*.zip; run_docking_gail.py:56),
+// net_arch [dict(pi=[128, 128], vf=[128, 128])], ReLU -- no shared layer: pi_fc0 12->128 -> pi_fc1 128->128 -> pi 128->4 and
+// vf_fc0 12->128 -> vf_fc1 128->128 -> vf 128->1 (rl_baselines/common/policies.py:35-92 with an empty shared part).
+// Both Runner kernels evaluate it as the same four pieces of the shared-trunk heads: layer 1 (pi_fc0) -> policy branch ->
+// layer 1 (vf_fc0) -> value branch, the second layer 1 written into the registers of the first (a role-split matrix wave
+// holds ONE set of layer-1 B operands: 128 registers).  Per wave and step: 2 x 96 more f32 MFMAs than the shared trunk.
+// Exact-f32 LDS image (floats): W2^T 128 x 260 (row r = pi_fc1^T row r | vf_fc1^T row r | 4 pad: a 1040-byte row meets the
+// banks as the shared image's 528-byte row does, and pads 1 KiB where two 132-float images pad 4 KiB -- the room for the
+// second layer 1) | W3pi^T 4x132 | W3vf 132 | W1pi^T 128x13 | W1vf^T 128x13 | b1pi 128 | b2pi 128 | b2vf 128 | b1vf 128 |
+// b3 16 | per-wave stage 4 x 768  = 163 472 B.
+// Split-bf16 image (bytes): the shared-trunk blob with pi_fc0 as its layer 1 (141 888) | W1vf^T f32 128x13 6656 | b1vf 512 |
+// per-wave stage 4 x 3072  = 161 344 B, + 2 KiB of zeros for the dead output rows (ac_fast_branch) = 163 392 B.
+// Neither leaves room for the role-split kernel's 1 KiB value buffer: its matrix waves hand the values over by ds_bpermute.
+enum : int { kNetShared = 0, kNetTowers = 1 };
+
+// a wave's layer-1 result: FAST the split B operands of the 128 x 128 layer (bh / bl), else the f32 accumulators (h1)
+template <bool FAST> using TowB = u32x4[FAST ? 4 : 1][4];
+template <bool FAST> using TowH = f32x4[FAST ? 1 : 8][4];
+
+constexpr int kLdW2T = 2 * kHid + 4;
+
+constexpr size_t tow_lds_floats()
+{
+    return (size_t)kHid * kLdW2T + 4 * kLdW + kLdW + 2 * kHid * kLdW1 + 4 * kHid + 16 + 4 * (12 * 64);
+}
+
+constexpr int kAcTowFastW1v = kAcFastBlobBytes;
+constexpr int kAcTowFastB1v = kAcTowFastW1v + kHid * kLdW1 * 4;
+constexpr int kAcTowFastBlobBytes = kAcTowFastB1v + kHid * 4;
+constexpr int kAcTowFastLdsBytes = kAcTowFastBlobBytes + 4 * (12 * 64) * 4;
+static_assert(tow_lds_floats() * 4 == 163472 && kAcTowFastLdsBytes == 161344, "tower LDS images as documented");
+
+// layer 1 of the policy tower + policy branch -> a3p (rows 0..3), then layer 1 of the value tower + value branch -> a3v (row 4).
+// Lp: the exact image with W1 = pi_fc0; Lv: the same with W1 = vf_fc0.  FAST: split-bf16 image at `blob`, zeros at `zeros`.
+template <bool FAST>
+__device__ __forceinline__ void tow_policy_part(const char *blob, int zeros, const AcLds &Lp, const float *stage, int lane,
+                                                TowB<FAST> &bh, TowB<FAST> &bl, TowH<FAST> &h1, f32x4 (&a3p)[4])
+{
+    if constexpr (FAST) {
+        ac_fast_layer1(blob, stage, lane, bh, bl);
+        ac_fast_branch<0>(blob, zeros, bh, bl, lane, a3p);
+    } else {
+        ac_exact_layer1(Lp, stage, lane, h1);
+        ac_exact_branch<0, kLdW2T>(Lp, h1, lane, a3p);
+    }
+}
+
+template <bool FAST>
+__device__ __forceinline__ void tow_value_layer1(const char *blob, const AcLds &Lv, const float *stage, int lane,
+                                                 TowB<FAST> &bh, TowB<FAST> &bl, TowH<FAST> &h1)
+{
+    if constexpr (FAST) ac_fast_layer1<kAcTowFastW1v, kAcTowFastB1v>(blob, stage, lane, bh, bl);
+    else ac_exact_layer1(Lv, stage, lane, h1);
+}
+
+template <bool FAST>
+__device__ __forceinline__ void tow_value_branch(const char *blob, int zeros, const AcLds &Lv, const TowB<FAST> &bh,
+                                                 const TowB<FAST> &bl, const TowH<FAST> &h1, int lane, f32x4 (&a3v)[4])
+{
+    if constexpr (FAST) ac_fast_branch<1>(blob, zeros, bh, bl, lane, a3v);
+    else ac_exact_branch<1, kLdW2T>(Lv, h1, lane, a3v);
+}
+
+// One wave per tile: obs (per owning lane) -> out[0..3] = action mean, out[4] = value (per owning lane), as mlp_actor_critic.
+template <bool FAST>
+__device__ __forceinline__ void mlp_towers(const float obs[12], float out[5], const char *blob, int zeros, const AcLds &Lp,
+                                           const AcLds &Lv, float *stage, int lane)
+{
+    const int c = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) stage[k * 64 + lane] = obs[k];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    TowB<FAST> bh, bl;
+    TowH<FAST> h1;
+    f32x4 a3p[4], a3v[4];
+    tow_policy_part<FAST>(blob, zeros, Lp, stage, lane, bh, bl, h1, a3p);
+    tow_value_layer1<FAST>(blob, Lv, stage, lane, bh, bl, h1);
+    tow_value_branch<FAST>(blob, zeros, Lv, bh, bl, h1, lane, a3v);
+    // every lane read its layer-1 operands before the branches: the stage is free for the hand-over
+    if (g == 0) {
+#pragma unroll
+        for (int et = 0; et < 4; ++et) *reinterpret_cast<f32x4 *>(stage + (16 * et + c) * 8) = a3p[et];
+    } else if (g == 1) {
+#pragma unroll
+        for (int et = 0; et < 4; ++et) stage[(16 * et + c) * 8 + 4] = a3v[et][0];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const f32x4 av = *reinterpret_cast<const f32x4 *>(stage + lane * 8);
+    out[0] = av[0]; out[1] = av[1]; out[2] = av[2]; out[3] = av[3];
+    out[4] = stage[lane * 8 + 4];
+    __builtin_amdgcn_wave_barrier();
+}
+
+// value of the env of this lane from row 4 of the value tile (register 0 of lanes 16..31) without LDS memory: lane l reads
+// a3v[l >> 4][0] of lane 16 + (l & 15)
+__device__ __forceinline__ float value_to_owner(const f32x4 (&a3v)[4], int lane)
+{
+    const int src = (16 + (lane & 15)) * 4;
+    float v = 0.0f;
+#pragma unroll
+    for (int et = 0; et < 4; ++et) {
+        const float y = a3v[et][0];
+        const float x = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src, __builtin_bit_cast(int, y)));
+        if ((lane >> 4) == et) v = x;
+    }
+    return v;
 }
 
 }  // namespace qs

@@ -1269,10 +1269,15 @@ static std::atomic<int> &runner_serial_flag()
     return flag;
 }
 
+extern "C++" template <int NET>
+static void runner_dispatch(QsEnv *e, const StepArgs &A, const RunnerArgs &R, bool fast);
+
+// layout: QS_NET_SHARED_TRUNK / QS_NET_TOWERS; wtv1 / bv1: the towers' vf_fc0 (exact f32 only)
 static int runner_launch(QsEnv *e, const char *who, int64_t T, const float logstd[4], int squash, const AcArgs *net,
                          const void *blob, const float *noise, const uint8_t *dones_in, float *mb_obs, float *mb_actions,
                          float *mb_values, float *mb_neglogp, uint8_t *mb_dones, float *mb_rewards, uint8_t *mb_flags,
-                         float *last_obs, float *last_values, uint8_t *last_dones)
+                         float *last_obs, float *last_values, uint8_t *last_dones, int layout = QS_NET_SHARED_TRUNK,
+                         const float *wtv1 = nullptr, const float *bv1 = nullptr)
 {
     Range rg_(who);
     if (T < 1 || !mb_obs || !mb_actions || !mb_values || !mb_neglogp || !mb_dones || !mb_rewards || !last_values || !last_dones)
@@ -1299,11 +1304,22 @@ static int runner_launch(QsEnv *e, const char *who, int64_t T, const float logst
     R.actions = mb_actions; R.values = mb_values; R.neglogp = mb_neglogp;
     R.last_obs = last_obs; R.last_values = last_values; R.last_dones = last_dones;
     R.env_major = e->runner_env_major ? 1 : 0;
+    R.wtv1 = wtv1; R.bv1 = bv1;
+    if (layout == QS_NET_TOWERS) runner_dispatch<kNetTowers>(e, A, R, blob != nullptr);
+    else runner_dispatch<kNetShared>(e, A, R, blob != nullptr);
+    HIP_TRY(hipGetLastError());
+    return QS_OK;
+}
+
+extern "C++" template <int NET>
+static void runner_dispatch(QsEnv *e, const StepArgs &A, const RunnerArgs &R, bool fast)
+{
+    const void *blob = fast ? R.blob : nullptr;
     const unsigned grid = grid_tiles(e->n);
     const bool fr = e->cfg.integrator == QS_INTEG_FROZEN;
     const int rm = e->cfg.randomise;
     const bool params = e->per_env_params || rm == 2;
-#define QS_RUNNER_GO(I, RM, PA, FAST) hipLaunchKernelGGL((k_runner_rollout<I, RM, PA, FAST>), dim3(grid), dim3(kBlock), 0, e->stream, A, R)
+#define QS_RUNNER_GO(I, RM, PA, FAST) hipLaunchKernelGGL((k_runner_rollout<I, RM, PA, FAST, NET>), dim3(grid), dim3(kBlock), 0, e->stream, A, R)
 #define QS_RUNNER_INTEG(I, FAST)                                  \
     do {                                                          \
         if (rm == 2) QS_RUNNER_GO(I, 2, true, FAST);              \
@@ -1315,7 +1331,7 @@ static int runner_launch(QsEnv *e, const char *who, int64_t T, const float logst
     // the role-split kernel (matrix waves + env waves); QUADSIM_RUNNER_SERIAL=1 keeps the one-wave-per-tile kernel for A/B
     // runs (same results bit for bit: the same instruction sequences on the same operands)
     const bool serial_fast = runner_serial_flag().load(std::memory_order_relaxed) != 0;
-#define QS_RUNNER_SPLIT_GO(I, RM, PA, FAST) hipLaunchKernelGGL((k_runner_split<I, RM, PA, FAST>), dim3(grid), dim3(2 * kBlock), 0, e->stream, A, R)
+#define QS_RUNNER_SPLIT_GO(I, RM, PA, FAST) hipLaunchKernelGGL((k_runner_split<I, RM, PA, FAST, NET>), dim3(grid), dim3(2 * kBlock), 0, e->stream, A, R)
 #define QS_RUNNER_SPLIT(I, FAST)                                        \
     do {                                                                \
         if (rm == 2) QS_RUNNER_SPLIT_GO(I, 2, true, FAST);              \
@@ -1334,8 +1350,6 @@ static int runner_launch(QsEnv *e, const char *who, int64_t T, const float logst
 #undef QS_RUNNER_SPLIT_GO
 #undef QS_RUNNER_INTEG
 #undef QS_RUNNER_GO
-    HIP_TRY(hipGetLastError());
-    return QS_OK;
 }
 
 int qs_runner_rollout(QsEnv *e, int64_t T, const QsActorCritic *pol, const float *noise, const uint8_t *dones_in,
@@ -1365,6 +1379,46 @@ int qs_runner_rollout_fast(QsEnv *e, int64_t T, const void *packed_weights, cons
 }
 
 int qs_runner_rollout_fast_blob_bytes(void) { return kAcFastBlobBytes; }
+
+int qs_runner_rollout_net(QsEnv *e, int64_t T, const QsActorCriticNet *pol, const float *noise, const uint8_t *dones_in,
+                          float *mb_obs, float *mb_actions, float *mb_values, float *mb_neglogp, uint8_t *mb_dones,
+                          float *mb_rewards, uint8_t *mb_flags, float *last_obs, float *last_values, uint8_t *last_dones)
+{
+    CHECK_ENV(e);
+    if (!pol) return fail(QS_ERR_INVALID, "qs_runner_rollout_net: bad arguments");
+    if (pol->struct_size != sizeof(QsActorCriticNet)) return fail(QS_ERR_INVALID, "qs_runner_rollout_net: QsActorCriticNet.struct_size mismatch");
+    if (pol->layout != QS_NET_SHARED_TRUNK && pol->layout != QS_NET_TOWERS)
+        return fail(QS_ERR_INVALID, "qs_runner_rollout_net: layout must be QS_NET_SHARED_TRUNK or QS_NET_TOWERS");
+    const bool tow = pol->layout == QS_NET_TOWERS;
+    if (!pol->wt1 || !pol->b1 || !pol->wt2 || !pol->b2 || !pol->wt3 || !pol->b3 || !pol->wtv2 || !pol->bv2 || !pol->wtv3 || !pol->bv3
+        || (tow && (!pol->wtv1 || !pol->bv1)))
+        return fail(QS_ERR_INVALID, "qs_runner_rollout_net: null weight pointer");
+    const AcArgs net{pol->wt1, pol->b1, pol->wt2, pol->b2, pol->wt3, pol->b3, pol->wtv2, pol->bv2, pol->wtv3, pol->bv3};
+    return runner_launch(e, "qs_runner_rollout_net", T, pol->logstd, pol->squash, &net, nullptr, noise, dones_in, mb_obs, mb_actions,
+                         mb_values, mb_neglogp, mb_dones, mb_rewards, mb_flags, last_obs, last_values, last_dones, pol->layout,
+                         tow ? pol->wtv1 : nullptr, tow ? pol->bv1 : nullptr);
+}
+
+int qs_runner_rollout_net_fast(QsEnv *e, int64_t T, int32_t layout, const void *packed_weights, const float *logstd, int squash,
+                               const float *noise, const uint8_t *dones_in, float *mb_obs, float *mb_actions, float *mb_values,
+                               float *mb_neglogp, uint8_t *mb_dones, float *mb_rewards, uint8_t *mb_flags, float *last_obs,
+                               float *last_values, uint8_t *last_dones)
+{
+    CHECK_ENV(e);
+    if (layout != QS_NET_SHARED_TRUNK && layout != QS_NET_TOWERS)
+        return fail(QS_ERR_INVALID, "qs_runner_rollout_net_fast: layout must be QS_NET_SHARED_TRUNK or QS_NET_TOWERS");
+    if (!packed_weights || !logstd) return fail(QS_ERR_INVALID, "qs_runner_rollout_net_fast: bad arguments");
+    if (((uintptr_t)packed_weights & 15) != 0) return fail(QS_ERR_INVALID, "qs_runner_rollout_net_fast: packed weights must be 16-byte aligned");
+    return runner_launch(e, "qs_runner_rollout_net_fast", T, logstd, squash, nullptr, packed_weights, noise, dones_in, mb_obs,
+                         mb_actions, mb_values, mb_neglogp, mb_dones, mb_rewards, mb_flags, last_obs, last_values, last_dones, layout);
+}
+
+int qs_runner_rollout_net_fast_blob_bytes(int32_t layout)
+{
+    if (layout == QS_NET_SHARED_TRUNK) return kAcFastBlobBytes;
+    if (layout == QS_NET_TOWERS) return kAcTowFastBlobBytes;
+    return fail(QS_ERR_INVALID, "qs_runner_rollout_net_fast_blob_bytes: unknown layout %d", (int)layout);
+}
 
 // Diagnostic (not in quadsim.h; tests and A/B tools only): Runner kernel flavour for every later qs_runner_rollout* call of
 // the process -- 1 one wave per tile, 0 role-split (matrix waves + env waves).  Returns the previous setting.

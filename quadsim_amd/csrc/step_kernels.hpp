@@ -826,18 +826,69 @@ struct RunnerArgs {
     float *last_values;        // [N]
     uint8_t *last_dones;       // [N]
     int env_major;             // mb_obs / mb_actions rows at env*T + t (already swap_and_flatten-ed) instead of t*N + env
+    const float *wtv1, *bv1;   // NET == kNetTowers, exact f32: vf_fc0 [128][12] (out, in), [128] (net.wt1 / b1 = pi_fc0)
 };
+
+// Tower image (policy_rollout.hpp "Tower actor-critic") into LDS by `nthr` threads; -> the per-wave stages.  FAST: the packed
+// blob plus 2 KiB of zeros right after the stages.  Lp / Lv: the exact image with W1 = pi_fc0 / vf_fc0.
+template <bool FAST>
+__device__ __forceinline__ float *load_towers_lds(char *lds_raw, const RunnerArgs &R, int nthr, AcLds &Lp, AcLds &Lv)
+{
+    if constexpr (FAST) {
+        for (int i = threadIdx.x; i < kAcTowFastBlobBytes / 16; i += nthr) reinterpret_cast<uint4 *>(lds_raw)[i] = R.blob[i];
+        for (int i = threadIdx.x; i < 2048 / 16; i += nthr) reinterpret_cast<uint4 *>(lds_raw + kAcTowFastLdsBytes)[i] = make_uint4(0, 0, 0, 0);
+        return reinterpret_cast<float *>(lds_raw + kAcTowFastBlobBytes);
+    } else {
+        float *sW2 = reinterpret_cast<float *>(lds_raw);                // row r: pi_fc1^T row r | vf_fc1^T row r | pad
+        float *sW3p = sW2 + kHid * kLdW2T;
+        float *sW3v = sW3p + 4 * kLdW;
+        float *sW1 = sW3v + kLdW;
+        float *sW1v = sW1 + kHid * kLdW1;
+        float *sB1 = sW1v + kHid * kLdW1;
+        float *sB2p = sB1 + kHid;
+        float *sB2v = sB2p + kHid;
+        float *sB1v = sB2v + kHid;
+        float *sB3 = sB1v + kHid;
+        for (int i = threadIdx.x; i < kHid * kHid; i += nthr) {
+            sW2[(i >> 7) * kLdW2T + (i & 127)] = R.net.wt2[i];
+            sW2[(i >> 7) * kLdW2T + kHid + (i & 127)] = R.net.wtv2[i];
+        }
+        for (int i = threadIdx.x; i < 4 * kHid; i += nthr) sW3p[(i >> 7) * kLdW + (i & 127)] = R.net.wt3[i];
+        for (int i = threadIdx.x; i < kHid; i += nthr) sW3v[i] = R.net.wtv3[i];
+        for (int i = threadIdx.x; i < kHid * 12; i += nthr) {
+            sW1[(i / 12) * kLdW1 + (i % 12)] = R.net.wt1[i];
+            sW1v[(i / 12) * kLdW1 + (i % 12)] = R.wtv1[i];
+        }
+        for (int i = threadIdx.x; i < kHid; i += nthr) { sB1[i] = R.net.b1[i]; sB2p[i] = R.net.b2[i]; sB2v[i] = R.net.bv2[i]; sB1v[i] = R.bv1[i]; }
+        if (threadIdx.x < 16) sB3[threadIdx.x] = threadIdx.x < 4 ? R.net.b3[threadIdx.x] : (threadIdx.x == 4 ? R.net.bv3[0] : 0.0f);
+        Lp = AcLds{sW1, sB1, sW2, sB2p, sW2 + kHid, sB2v, sW3p, sW3v, sB3};
+        Lv = Lp;
+        Lv.W1 = sW1v; Lv.B1 = sB1v;
+        return sB3 + 16;
+    }
+}
+
+template <bool FAST, int NET>
+constexpr int runner_lds_bytes()
+{
+    return NET == kNetTowers ? (FAST ? kAcTowFastLdsBytes + 2048 : (int)(tow_lds_floats() * sizeof(float)))
+                             : (FAST ? kAcFastLdsBytes : (int)(ac_lds_floats() * sizeof(float)));
+}
 
 // FAST: the networks on the bf16 matrix rate with split operands (mlp_actor_critic_fast; R.blob = host-packed image)
 // PARAMS: per-env mass / inertia (domain randomisation; RMODE 2 redraws them at every episode start)
-template <int INTEG, int RMODE, bool PARAMS, bool FAST>
+// NET: kNetShared (shared_fc0 trunk, the shipped best_model_v0) or kNetTowers (separate pi / vf towers, mlp_towers)
+template <int INTEG, int RMODE, bool PARAMS, bool FAST, int NET = kNetShared>
 __global__ __launch_bounds__(kBlock, 1) void k_runner_rollout(StepArgs A, RunnerArgs R)
 {
-    __shared__ __attribute__((aligned(16))) char lds_raw[FAST ? kAcFastLdsBytes : (int)(ac_lds_floats() * sizeof(float))];
+    constexpr bool TOW = NET == kNetTowers;
+    __shared__ __attribute__((aligned(16))) char lds_raw[runner_lds_bytes<FAST, NET>()];
     float *lds = reinterpret_cast<float *>(lds_raw);
-    AcLds L{};
+    AcLds L{}, Lv{};
     float *sStage;
-    if (FAST) {
+    if constexpr (TOW) {
+        sStage = load_towers_lds<FAST>(lds_raw, R, kBlock, L, Lv);
+    } else if (FAST) {
         for (int i = threadIdx.x; i < kAcFastBlobBytes / 16; i += kBlock) reinterpret_cast<uint4 *>(lds_raw)[i] = R.blob[i];
         sStage = reinterpret_cast<float *>(lds_raw + kAcFastBlobBytes);
     } else {
@@ -889,7 +940,8 @@ __global__ __launch_bounds__(kBlock, 1) void k_runner_rollout(StepArgs A, Runner
         const int64_t ow = R.env_major ? env * A.T + t : o;
         if (active) { if (R.env_major) store_obs_cached(A.obs, ow, obs); else store_obs(A.obs, ow, obs); }   // mb_obs: the observation the policy acts on
         float head[5];
-        if (FAST) mlp_actor_critic_fast(obs, head, lds_raw, stage, lane);
+        if constexpr (TOW) mlp_towers<FAST>(obs, head, lds_raw, kAcTowFastLdsBytes, L, Lv, stage, lane);
+        else if (FAST) mlp_actor_critic_fast(obs, head, lds_raw, stage, lane);
         else mlp_actor_critic(obs, head, L, stage, lane);
         float eps[4];
         if (R.noise) {
@@ -935,7 +987,8 @@ __global__ __launch_bounds__(kBlock, 1) void k_runner_rollout(StepArgs A, Runner
     }
     // last_values = model.value(obs) on the observation after the last step (ppo2.py:506)
     float head[5];
-    if (FAST) mlp_actor_critic_fast(obs, head, lds_raw, stage, lane);
+    if constexpr (TOW) mlp_towers<FAST>(obs, head, lds_raw, kAcTowFastLdsBytes, L, Lv, stage, lane);
+    else if (FAST) mlp_actor_critic_fast(obs, head, lds_raw, stage, lane);
     else mlp_actor_critic(obs, head, L, stage, lane);
     if (active) {
         R.last_values[env] = head[4];
@@ -957,15 +1010,20 @@ __global__ __launch_bounds__(kBlock, 1) void k_runner_rollout(StepArgs A, Runner
 // through the tile's obs stage (the matrix wave has its observations in registers by then), the values through a
 // buffer private to the matrix wave.  Every wave passes the same 2 T + 1 workgroup barriers.  FAST as in k_runner_rollout;
 // the heads are the same instruction sequences on the same operands as there, so the two kernels agree bit for bit.
-template <int INTEG, int RMODE, bool PARAMS, bool FAST>
+// NET == kNetTowers: the matrix wave runs pi layer 1 -> policy branch -> vf layer 1 (the stage still holds the observations)
+// -> means to LDS -> #b -> value branch; the values reach their lanes by ds_bpermute (no value buffer: see the tower image).
+template <int INTEG, int RMODE, bool PARAMS, bool FAST, int NET = kNetShared>
 __global__ __launch_bounds__(2 * kBlock, 1) void k_runner_split(StepArgs A, RunnerArgs R)
 {
+    constexpr bool TOW = NET == kNetTowers;
     constexpr int kHeadBytes = FAST ? kAcFastLdsBytes : (int)(ac_lds_floats() * sizeof(float));     // weights + 4 obs stages
-    constexpr int kZeros = kHeadBytes + 4 * kTile * 4;                                              // FAST: 2 KiB of zeros
-    __shared__ __attribute__((aligned(16))) char lds_raw[kZeros + (FAST ? 2048 : 0)];
-    AcLds L{};
+    constexpr int kZeros = TOW ? kAcTowFastLdsBytes : kHeadBytes + 4 * kTile * 4;                   // FAST: 2 KiB of zeros
+    __shared__ __attribute__((aligned(16))) char lds_raw[TOW ? runner_lds_bytes<FAST, NET>() : kZeros + (FAST ? 2048 : 0)];
+    AcLds L{}, Lv{};
     float *sStage;
-    if (FAST) {
+    if constexpr (TOW) {
+        sStage = load_towers_lds<FAST>(lds_raw, R, 2 * kBlock, L, Lv);
+    } else if (FAST) {
         for (int i = threadIdx.x; i < kAcFastBlobBytes / 16; i += 2 * kBlock) reinterpret_cast<uint4 *>(lds_raw)[i] = R.blob[i];
         if (threadIdx.x < 128) reinterpret_cast<uint4 *>(lds_raw + kZeros)[threadIdx.x] = make_uint4(0, 0, 0, 0);
         sStage = reinterpret_cast<float *>(lds_raw + kAcFastBlobBytes);
@@ -999,9 +1057,41 @@ __global__ __launch_bounds__(2 * kBlock, 1) void k_runner_split(StepArgs A, Runn
     const int64_t env = tile * kTile + lane;
     const bool active = env < A.n;             // MFMA needs the whole wave: idle lanes carry a nominal env, store nothing
     float *stage = sStage + w * (12 * 64);
-    float *sval = reinterpret_cast<float *>(lds_raw + kHeadBytes) + w * kTile;
-    QS_ASSERT((char *)(stage + 12 * 64) <= lds_raw + kHeadBytes);
-    if (matrix_role) {
+    float *sval = reinterpret_cast<float *>(lds_raw + kHeadBytes) + w * kTile;       // shared trunk only
+    QS_ASSERT((char *)(stage + 12 * 64) <= lds_raw + (TOW ? (int)sizeof lds_raw : kHeadBytes));
+    if (TOW && matrix_role) {
+        const int c = lane & 15, g = lane >> 4;
+        u32x4 bh[FAST ? 4 : 1][4], bl[FAST ? 4 : 1][4];
+        f32x4 h1[FAST ? 1 : 8][4];
+        f32x4 a3[4];
+        QS_PHASE_DECL;
+#pragma clang loop unroll(disable)
+        for (int64_t t = 0; t <= A.T; ++t) {
+            __syncthreads();                                                  // #a: this step's observations are in LDS
+            QS_PHASE(0);
+            if (t < A.T) tow_policy_part<FAST>(lds_raw, kZeros, L, stage, lane, bh, bl, h1, a3);
+            QS_PHASE(1);
+            tow_value_layer1<FAST>(lds_raw, Lv, stage, lane, bh, bl, h1);   // before the means overwrite the observations
+            if (t < A.T) {
+                if (g == 0) {
+#pragma unroll
+                    for (int et = 0; et < 4; ++et) *reinterpret_cast<f32x4 *>(stage + (16 * et + c) * 8) = a3[et];
+                }
+                QS_PHASE(2);
+                __syncthreads();                                              // #b: the means are in LDS
+                QS_PHASE(3);
+            }
+            tow_value_branch<FAST>(lds_raw, kZeros, Lv, bh, bl, h1, lane, a3);
+            QS_PHASE(4);
+            const float v = value_to_owner(a3, lane);
+            if (active) {
+                float *vout = t < A.T ? R.values + t * A.n : R.last_values;   // last: model.value(obs) after the last step (ppo2.py:506)
+                vout[env] = v;
+            }
+            QS_PHASE(5);
+        }
+        QS_PHASE_FLUSH(0);
+    } else if (matrix_role) {
         const int c = lane & 15, g = lane >> 4;
         // layer-1 result = the B operands of both 128 x 128 branches, 128 registers either way
         u32x4 bh[FAST ? 4 : 1][4], bl[FAST ? 4 : 1][4];

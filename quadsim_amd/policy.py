@@ -24,6 +24,14 @@ class MlpPolicy:
         with np.load(path, allow_pickle=False) as z:
             return cls({k: z[k] for k in z.files}, device)
 
+    @classmethod
+    def from_sb2_zip(cls, path, device="cuda"):
+        """the deterministic actor of a stable-baselines PPO2 archive (quadsim_amd.sb2): shared_fc0 -> pi_fc0 -> pi of the
+        shared-trunk layout or pi_fc0 -> pi_fc1 -> pi of the tower layout -- the same 12 -> 128 -> 128 -> 4 ReLU network
+        either way, so every actor kernel runs both"""
+        from .sb2 import read_sb2_weights
+        return cls(read_sb2_weights(path)[1], device)
+
     def predict(self, obs):
         """obs [N,12] float32 (device) -> actions [N,4] in [-1,1]"""
         t = self.torch

@@ -5,8 +5,10 @@ the GAE kernel and ``swap_and_flatten``.  Same class / method names and return t
 
 ``ActorCriticPolicy`` is the MlpPolicy the reference trains and ships (``trained_model/best_model_v0.zip``:
 shared_fc0 12->128, pi_fc0 / vf_fc0 128->128, pi 128->4, vf 128->1, ReLU, state-independent logstd;
-rl_baselines/common/policies.py:35-92,:583-603).  Its ``step`` / ``value`` are plain torch (library GEMMs) and serve
-the per-step API; the fused kernel evaluates the same network on the matrix cores in exact float32.
+rl_baselines/common/policies.py:35-92,:583-603), or the tower layout of the reference's ``ppo2_docking*.zip``
+(pi_fc0 / vf_fc0 12->128, pi_fc1 / vf_fc1 128->128, same heads; weights with a ``wv0`` key; quadsim_amd.sb2 loads either
+from an archive).  Its ``step`` / ``value`` are plain torch (library GEMMs) and serve the per-step API; the fused kernel
+evaluates the same network on the matrix cores in exact float32.
 """
 import ctypes as C
 import math
@@ -22,10 +24,13 @@ class ActorCriticPolicy:
         import torch
         self.torch = torch
         g = lambda k: torch.as_tensor(np.ascontiguousarray(weights[k], np.float32)).to(device)  # noqa: E731
-        self.w0, self.b0 = g("w0"), g("b0")            # shared_fc0
-        self.w1, self.b1 = g("w1"), g("b1")            # pi_fc0
+        self.towers = "wv0" in weights                  # separate pi / vf towers (quadsim_amd.sb2)
+        self.w0, self.b0 = g("w0"), g("b0")            # shared_fc0 | towers: pi_fc0
+        self.w1, self.b1 = g("w1"), g("b1")            # pi_fc0     | towers: pi_fc1
         self.w2, self.b2 = g("w2"), g("b2")            # pi
-        self.wv1, self.bv1 = g("wv1"), g("bv1")        # vf_fc0
+        if self.towers:
+            self.wv0, self.bv0 = g("wv0"), g("bv0")    # towers: vf_fc0 (12 -> 128, on the observation)
+        self.wv1, self.bv1 = g("wv1"), g("bv1")        # vf_fc0     | towers: vf_fc1
         self.wv2, self.bv2 = g("wv2"), g("bv2")        # vf
         self.logstd_host = np.asarray(weights["logstd"], np.float32).reshape(4).copy()
         self.logstd = torch.as_tensor(self.logstd_host).to(device)
@@ -43,7 +48,8 @@ class ActorCriticPolicy:
         t = self.torch
         h = t.relu(t.addmm(self.b0, obs, self.w0))
         mean = t.addmm(self.b2, t.relu(t.addmm(self.b1, h, self.w1)), self.w2)
-        value = t.addmm(self.bv2, t.relu(t.addmm(self.bv1, h, self.wv1)), self.wv2)[:, 0]
+        hv = t.relu(t.addmm(self.bv0, obs, self.wv0)) if self.towers else h
+        value = t.addmm(self.bv2, t.relu(t.addmm(self.bv1, hv, self.wv1)), self.wv2)[:, 0]
         return mean, value
 
     def step(self, obs, state=None, mask=None, deterministic=False, noise=None):
@@ -72,6 +78,9 @@ class ActorCriticPolicy:
 
     # -- device image for the fused kernel --------------------------------------------------------------------------
     def c_struct(self):
+        """QsActorCritic (shared trunk) or QsActorCriticNet (towers) over transposed device copies of the weights"""
+        if self.towers:
+            return self._c_struct_net()
         if self._wt is None:
             tr = lambda w: w.t().contiguous()                                                  # noqa: E731
             self._wt = [tr(self.w0), self.b0.contiguous(), tr(self.w1), self.b1.contiguous(), tr(self.w2),
@@ -80,6 +89,22 @@ class ActorCriticPolicy:
         s.struct_size = C.sizeof(_lib.QsActorCritic)
         s.squash = 1 if self.squash else 0
         for name, w in zip(("wt1", "b1", "wt2", "b2", "wt3", "b3", "wtv2", "bv2", "wtv3", "bv3"), self._wt):
+            setattr(s, name, w.data_ptr())
+        for i in range(4):
+            s.logstd[i] = float(self.logstd_host[i])
+        return s
+
+    def _c_struct_net(self):
+        if self._wt is None:
+            tr = lambda w: w.t().contiguous()                                                  # noqa: E731
+            self._wt = [tr(self.w0), self.b0.contiguous(), tr(self.w1), self.b1.contiguous(), tr(self.w2),
+                        self.b2.contiguous(), tr(self.wv0), self.bv0.contiguous(), tr(self.wv1), self.bv1.contiguous(),
+                        tr(self.wv2), self.bv2.contiguous()]
+        s = _lib.QsActorCriticNet()
+        s.struct_size = C.sizeof(_lib.QsActorCriticNet)
+        s.squash = 1 if self.squash else 0
+        s.layout = _lib.NET_TOWERS
+        for name, w in zip(("wt1", "b1", "wt2", "b2", "wt3", "b3", "wtv1", "bv1", "wtv2", "bv2", "wtv3", "bv3"), self._wt):
             setattr(s, name, w.data_ptr())
         for i in range(4):
             s.logstd[i] = float(self.logstd_host[i])
@@ -125,6 +150,11 @@ def pack_fast_actor_critic(policy):
     w1 = np.zeros((128, 13), np.float32); w1[:, :12] = w1t
     b3 = np.zeros(16, np.float32); b3[:4] = g(policy.b2); b3[4] = g(policy.bv2)[0]
     parts += [w1.tobytes(), g(policy.b0).tobytes(), g(policy.b1).tobytes(), g(policy.bv1).tobytes(), b3.tobytes()]
+    if getattr(policy, "towers", False):
+        # tower layout ('Tower actor-critic'): the image above is built from pi_fc0 / pi_fc1 / pi / vf_fc1 / vf; the value
+        # tower's own first layer follows in float32
+        wv1 = np.zeros((128, 13), np.float32); wv1[:, :12] = g(policy.wv0).T
+        parts += [wv1.tobytes(), g(policy.bv0).tobytes()]
     return np.frombuffer(b"".join(parts), np.uint8)
 
 
@@ -161,17 +191,27 @@ def fused_runner_rollout(env, policy, T, noise=None, dones_in=None, want_flags=F
     _lib.check(env._lib.qs_set_rollout_layout(env._h, 1 if env_major else 0), "qs_set_rollout_layout")
     tail = (p(noise), p(dones_in), p(out["obs"]), p(out["actions"]), p(out["values"]), p(out["neglogp"]), p(out["dones"]),
             p(out["rewards"]), p(out["flags"]), p(out["last_obs"]), p(out["last_values"]), p(out["last_dones"]))
+    towers = getattr(policy, "towers", False)
     if precision == "f32":
         pol = policy.c_struct()
-        _lib.check(env._lib.qs_runner_rollout(env._h, T, C.byref(pol), *tail), "qs_runner_rollout")
+        if towers:
+            _lib.check(env._lib.qs_runner_rollout_net(env._h, T, C.byref(pol), *tail), "qs_runner_rollout_net")
+        else:
+            _lib.check(env._lib.qs_runner_rollout(env._h, T, C.byref(pol), *tail), "qs_runner_rollout")
     elif precision == "bf16x3":
         if getattr(policy, "_ac_blob", None) is None:
             blob = pack_fast_actor_critic(policy)
-            assert blob.size == env._lib.qs_runner_rollout_fast_blob_bytes()
+            want = (env._lib.qs_runner_rollout_net_fast_blob_bytes(_lib.NET_TOWERS) if towers
+                    else env._lib.qs_runner_rollout_fast_blob_bytes())
+            assert blob.size == want
             policy._ac_blob = torch.as_tensor(blob.copy()).to(dev)
         ls = (C.c_float * 4)(*[float(x) for x in policy.logstd_host])
-        _lib.check(env._lib.qs_runner_rollout_fast(env._h, T, p(policy._ac_blob), ls, 1 if policy.squash else 0, *tail),
-                   "qs_runner_rollout_fast")
+        if towers:
+            _lib.check(env._lib.qs_runner_rollout_net_fast(env._h, T, _lib.NET_TOWERS, p(policy._ac_blob), ls,
+                                                           1 if policy.squash else 0, *tail), "qs_runner_rollout_net_fast")
+        else:
+            _lib.check(env._lib.qs_runner_rollout_fast(env._h, T, p(policy._ac_blob), ls, 1 if policy.squash else 0, *tail),
+                       "qs_runner_rollout_fast")
     else:
         raise ValueError("precision must be 'f32' or 'bf16x3'")
     env._outputs_ready()
@@ -194,7 +234,7 @@ class Runner:
         self.env, self.model, self.n_steps, self.gamma, self.lam = env, model, int(n_steps), float(gamma), float(lam)
         self.reset_after_run = reset_after_run
         self.precision = precision                     # "f32" | "bf16x3" (fused_runner_rollout)
-        # fused: the whole n_steps loop in one launch (docking envs + the shipped MlpPolicy architecture); None = whenever
+        # fused: the whole n_steps loop in one launch (docking envs + either ActorCriticPolicy layout); None = whenever
         # it applies, else the spelt-out loop (model.step on torch + env.step)
         can_fuse = isinstance(model, ActorCriticPolicy) and env.obs_dim == 12 and getattr(env, "auto_reset", True)
         self.fused = can_fuse if fused is None else bool(fused)
