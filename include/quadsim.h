@@ -188,8 +188,15 @@ int qs_groups_join(QsEnv *env);
  *     synchronises the old one.
  *   - QS_ORDER_HOST (round 2's contract, qs_set_queue_ordering; the fallback without stream memory operations): no
  *     hand-shake -- the buffers passed to a step must be complete when it is called, and its outputs may be read after
- *     qs_sync() (or any other entry point);
- *   - every workgroup checks that it runs on the XCD that holds its tile (the hardware deals blocks to XCDs round-robin
+ *     qs_sync() (or any other entry point).  Since round 4 such steps run as a RESIDENT roll-out: the first step after a
+ *     synchronisation dispatches one long-running step kernel per private queue, and every qs_step / qs_step_ex only
+ *     writes the step's buffer addresses into a descriptor ring the kernel polls (state in registers between steps,
+ *     outputs written every step, bit-identical results); the draining entry points end the roll-out and wait for it
+ *     (bounded: QS_ERR_HIP with a message after 30 s).  A pause of the caller longer than QS_RESIDENT_IDLE_US (default 50)
+ *     ends the kernel, the next step resumes it.  The resident path uses no owner words and does not depend on the
+ *     workgroup -> XCD placement below; it applies where every tile of the handle is on the chip at once (65 536 envs:
+ *     yes, 131 072: no -- those keep one packet per step).  QS_RESIDENT=0 at qs_set_queue_mode keeps the packets;
+ *   - packet steps: every workgroup checks that it runs on the XCD that holds its tile (the hardware deals blocks to XCDs round-robin
  *     from a fixed start; HIP does not promise it): the owning XCD of a tile is kept in a word that is only accessed by
  *     agent-scope atomics, so every XCD sees it; if the check ever fails the workgroup touches nothing, raises an error
  *     word in host memory, and both the next step call and the next synchronising call (qs_sync, qs_get_state, ...)

@@ -38,6 +38,18 @@ struct QsChainLane {                  // one private queue and the contiguous ti
     void *rev_ptr = nullptr;
     hsa_signal_t rev{};
     int64_t rev_value = 0;            // value of `rev` once every submission so far has completed (counts DOWN: AQL decrements)
+    // resident roll-out (k_env_resident): this lane's dispatch
+    char *res_kernarg = nullptr;      // its kernel-argument block (device memory, like the ring)
+    hsa_signal_t res_done{};          // 1 while it runs, 0 once it has ended (its release included)
+    bool res_launched = false;        // dispatched in the current roll-out (it may have ended since: idle limit)
+    uint64_t res_prog = 0;            // the largest progress word seen from it (host view of ResArgs::h_prog)
+};
+
+// a kernel of the loaded code object, as an AQL dispatch packet needs it
+struct QsKernel {
+    uint64_t object = 0;
+    uint32_t kernarg_size = 0, group_size = 0, private_size = 0;
+    unsigned block = 0;
 };
 
 struct QsChain {
@@ -67,6 +79,26 @@ struct QsChain {
     hsa_signal_t fwd{};
     uint64_t fwd_seq = 0;             // submissions so far
     int dbg_shift = 0;                // one-shot: the next step packet runs with StepArgs::dbg_shift (placement-guard test)
+    bool pkt_unreleased = false;      // step packets without a release fence since the last drain / release barrier
+    // resident roll-out (host-ordered mode): see "resident roll-out" below
+    bool res_enabled = false;         // QS_RESIDENT (read at qs_set_queue_mode) and a BAR-mapped device pool for the ring
+    bool res_dbg_packets = false;     // qs_debug_chain_poison_owner armed: the steps go through the packet chain and its guard
+    bool res_open = false;            // descriptors written since the last EXIT
+    bool res_fits = false;            // the resolved resident instantiation fits the chip in one round
+    QsKernel res_kernel;
+    int rv_integ = -1, rv_params = -1, rv_rmode = -1, rv_prep = -1;
+    int64_t res_wave_cap = 0;         // waves of k_env_resident the chip holds at once
+    unsigned long long *ring = nullptr;   // [ring_slots][8] descriptors (k_env_resident), BAR-mapped device memory
+    size_t ring_slots = 0;
+    uint64_t res_issued = 1;          // sequence number of the next descriptor (tags: 0 is never a valid one)
+    uint64_t res_retired = 1;         // every tile has consumed every descriptor below this one
+    uint64_t res_seq0 = 0;            // first descriptor of the current roll-out
+    uint64_t res_idle_ticks = 0;
+    uint64_t res_dispatches = 0;      // resident dispatches issued (qs_debug_chain_resident)
+    unsigned long long *d_rseq = nullptr; // [tiles] ResArgs::rseq
+    unsigned *d_rcnt = nullptr;       // [lanes][32]: kResWinSlots window counters, then the EXIT count
+    volatile unsigned long long *h_res = nullptr;   // pinned host words, [lanes][8]: progress, EXIT count reached
+    unsigned long long *d_hres = nullptr;           // ... their device address
 };
 
 namespace {
@@ -82,6 +114,12 @@ namespace {
     } while (0)
 
 constexpr int64_t kRevStart = (int64_t)1 << 40;
+// resident roll-out (see "resident roll-out" below)
+constexpr int kResIdleUs = 50;
+constexpr size_t kResRingSlots = 256;   // power of two; kResWinSlots > slots / kResWin + 2
+constexpr size_t kResKernargBytes = 4096;
+constexpr double kResTimeoutS = 30.0;   // bound of every host wait of the resident path
+static_assert((kResRingSlots & (kResRingSlots - 1)) == 0 && kResWinSlots > kResRingSlots / kResWin + 2, "ring / window sizes");
 
 struct AgentPick {
     uint32_t want_bdf, want_domain;
@@ -200,7 +238,13 @@ void chain_close(QsEnv *e)
         if (L.kernargs) hsa_amd_memory_pool_free(L.kernargs);
         if (L.done.handle) hsa_signal_destroy(L.done);
         if (L.rev_ptr) (void)hipFree(L.rev_ptr);
+        if (L.res_kernarg) hsa_amd_memory_pool_free(L.res_kernarg);
+        if (L.res_done.handle) hsa_signal_destroy(L.res_done);
     }
+    if (c->ring) hsa_amd_memory_pool_free(c->ring);
+    if (c->d_rseq) (void)hipFree(c->d_rseq);
+    if (c->d_rcnt) (void)hipFree(c->d_rcnt);
+    if (c->h_res) (void)hipHostFree((void *)c->h_res);
     if (c->fwd_ptr) (void)hipFree(c->fwd_ptr);
     if (c->have_exe) hsa_executable_destroy(c->exe);
     if (c->have_reader) hsa_code_object_reader_destroy(c->reader);
@@ -349,6 +393,31 @@ int chain_open(QsEnv *e, int nq)
         HIP_TRY(hipHostMalloc((void **)&c->h_err, 64, hipHostMallocMapped | hipHostMallocCoherent));
         *c->h_err = 0;
         HIP_TRY(hipHostGetDevicePointer((void **)&c->d_err, (void *)c->h_err, 0));
+        // resident roll-out: on unless QS_RESIDENT=0 (A/B runs); needs the ring in device memory the host can write
+        const char *res = getenv("QS_RESIDENT");
+        c->res_enabled = dp.found && !(res && res[0] == '0');
+        if (c->res_enabled) {
+            int cus = 0;
+            HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device));
+            c->res_wave_cap = (int64_t)cus * 4 * 3;          // 3 waves per SIMD: every k_env_resident has <= 168 VGPRs
+            const char *idle = getenv("QS_RESIDENT_IDLE_US");
+            c->res_idle_ticks = (uint64_t)(idle ? std::max(1, atoi(idle)) : kResIdleUs) * 100;   // s_memrealtime: 100 MHz
+            c->ring_slots = kResRingSlots;
+            HSA_TRY(hsa_amd_memory_pool_allocate(dp.pool, c->ring_slots * kResWords * 8, 0, (void **)&c->ring));
+            HSA_TRY(hsa_amd_agents_allow_access(1, &c->cpu, nullptr, c->ring));
+            memset(c->ring, 0, c->ring_slots * kResWords * 8);     // tag 0 / sequence 0: never a valid descriptor
+            for (QsChainLane &L : c->lanes) {
+                HSA_TRY(hsa_amd_memory_pool_allocate(dp.pool, kResKernargBytes, 0, (void **)&L.res_kernarg));
+                HSA_TRY(hsa_amd_agents_allow_access(1, &c->cpu, nullptr, L.res_kernarg));
+                memset(L.res_kernarg, 0, kResKernargBytes);
+                HSA_TRY(hsa_signal_create(0, 0, nullptr, &L.res_done));
+            }
+            HIP_TRY(hipMalloc((void **)&c->d_rseq, (size_t)e->tiles * sizeof(unsigned long long)));
+            HIP_TRY(hipMalloc((void **)&c->d_rcnt, c->lanes.size() * 32 * sizeof(unsigned)));
+            HIP_TRY(hipHostMalloc((void **)&c->h_res, c->lanes.size() * 64, hipHostMallocMapped | hipHostMallocCoherent));
+            memset((void *)c->h_res, 0, c->lanes.size() * 64);
+            HIP_TRY(hipHostGetDevicePointer((void **)&c->d_hres, (void *)c->h_res, 0));
+        }
         // stream-ordered hand-shake: needs HIP's stream memory operations and its signal memory; without them the mode
         // stays host-ordered (round 2's contract)
         const char *ord = getenv("QS_CHAIN_ORDER");            // "host": start with round 2's contract (A/B runs)
@@ -366,8 +435,9 @@ int chain_open(QsEnv *e, int nq)
 }
 
 // one AQL packet behind everything enqueued before it on lane L (barrier bit): kind 0 the step kernel, 1 a barrier-AND packet
-// (drain), 2 an AMD barrier-value packet that holds the lane until `wait_sig` >= wait_value (the caller's stream is ready)
-enum { PKT_STEP = 0, PKT_BARRIER = 1, PKT_WAIT_VALUE = 2 };
+// (drain), 2 an AMD barrier-value packet that holds the lane until `wait_sig` >= wait_value (the caller's stream is ready),
+// 3 the resident step kernel (c->res_kernel)
+enum { PKT_STEP = 0, PKT_BARRIER = 1, PKT_WAIT_VALUE = 2, PKT_RESIDENT = 3 };
 uint64_t chain_write_packet(QsChain *c, QsChainLane &L, int kind, const void *kernarg, unsigned grid, int acquire, int release,
                             hsa_signal_t completion, hsa_signal_t wait_sig = hsa_signal_t{0}, int64_t wait_value = 0)
 {
@@ -394,12 +464,13 @@ uint64_t chain_write_packet(QsChain *c, QsChainLane &L, int kind, const void *ke
                 ((uint32_t)HSA_AMD_PACKET_TYPE_BARRIER_VALUE << 16);
     } else {
         hsa_kernel_dispatch_packet_t *p = (hsa_kernel_dispatch_packet_t *)slot;
-        p->workgroup_size_x = (uint16_t)c->block; p->workgroup_size_y = 1; p->workgroup_size_z = 1;
+        const bool res = kind == PKT_RESIDENT;
+        p->workgroup_size_x = (uint16_t)(res ? c->res_kernel.block : c->block); p->workgroup_size_y = 1; p->workgroup_size_z = 1;
         p->reserved0 = 0;
         p->grid_size_x = grid; p->grid_size_y = 1; p->grid_size_z = 1;
-        p->private_segment_size = c->private_size;
-        p->group_segment_size = c->group_size;
-        p->kernel_object = c->kernel_object;
+        p->private_segment_size = res ? c->res_kernel.private_size : c->private_size;
+        p->group_segment_size = res ? c->res_kernel.group_size : c->group_size;
+        p->kernel_object = res ? c->res_kernel.object : c->kernel_object;
         p->kernarg_address = (void *)kernarg;
         p->reserved2 = 0;
         p->completion_signal = completion;
@@ -411,24 +482,222 @@ uint64_t chain_write_packet(QsChain *c, QsChainLane &L, int kind, const void *ke
     return idx;
 }
 
+// ---- resident roll-out (host-ordered mode) ---------------------------------------------------------------------------
+// A pre-staged roll-out does not need a launch per step: no output is consumed before qs_sync, and tiles never exchange
+// data.  So the first host-ordered qs_step after a drain dispatches k_env_resident once per lane over the lane's tiles, and
+// every qs_step writes ONE 64-B descriptor (the step's I/O pointers, tagged with its sequence number; step_kernels.hpp) into a
+// ring in BAR-mapped device memory.  The tiles keep their state in registers, poll the ring a step ahead and end on an EXIT
+// descriptor, which every draining entry point appends before it waits for the dispatches (host wait, bounded).  The ring
+// needs no read-back and no doorbell per step: a descriptor that lands late is polled for, never misread.
+//   Back-pressure: a slot is rewritten only when every tile has consumed the descriptor it held (the lanes' progress words,
+//   written by the last tile of each window, in pinned host memory).
+//   Idle limit: a tile that sees no new descriptor for QS_RESIDENT_IDLE_US (default kResIdleUs) stores its state and its
+//   position and ends; a dispatch whose tiles have all ended is dispatched again by the next qs_step (or the wait that needs
+//   it), and its tiles resume where they stopped.  Co-residency is therefore never needed for progress, only for speed.
+//   Coherence: the dispatch acquires and releases at system scope, so state, step counter and outputs are in memory when it
+//   has ended, whichever XCD ran a workgroup: the resident path needs no owner words and no placement guard.
+// QS_RESIDENT=0 (read at qs_set_queue_mode) keeps the packet chain (A/B runs).
+
+double res_now()
+{
+    timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+
+// the resident instantiation matching the packet chain's (chain_resolve_kernel first); res_fits says whether it may be used
+int res_resolve_kernel(QsEnv *e)
+{
+    QsChain *c = e->chain;
+    if (!c->v_split) { c->res_fits = false; return QS_OK; }
+    if (c->res_kernel.object && c->v_integ == c->rv_integ && c->v_params == c->rv_params && c->v_rmode == c->rv_rmode && c->v_prep == c->rv_prep)
+        return QS_OK;
+    char sym[200];
+    snprintf(sym, sizeof sym, "_ZN12_GLOBAL__N_114k_env_residentILi%dELb%dELi%dELi%dEEEvNS_8StepArgsENS_7ResArgsE.kd", c->v_integ,
+             c->v_params, c->v_rmode, c->v_prep);
+    hsa_executable_symbol_t ks;
+    QsKernel k;
+    HSA_TRY(hsa_executable_get_symbol_by_name(c->exe, sym, &c->gpu, &ks));
+    HSA_TRY(hsa_executable_symbol_get_info(ks, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_OBJECT, &k.object));
+    HSA_TRY(hsa_executable_symbol_get_info(ks, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_KERNARG_SEGMENT_SIZE, &k.kernarg_size));
+    HSA_TRY(hsa_executable_symbol_get_info(ks, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_GROUP_SEGMENT_SIZE, &k.group_size));
+    HSA_TRY(hsa_executable_symbol_get_info(ks, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_PRIVATE_SEGMENT_SIZE, &k.private_size));
+    if (k.kernarg_size > kResKernargBytes) return fail(QS_ERR_HIP, "queue mode: kernel argument block of %s is %u B", sym, k.kernarg_size);
+    const int waves = split_waves(c->v_rmode, c->v_prep);
+    k.block = (unsigned)(waves * kTile);
+    c->res_kernel = k;
+    c->rv_integ = c->v_integ; c->rv_params = c->v_params; c->rv_rmode = c->v_rmode; c->rv_prep = c->v_prep;
+    // every workgroup of every lane resident at once (the chaser waves of late workgroups would otherwise wait for the first
+    // round's idle limit); scratch would be a private segment per wave for the whole roll-out
+    c->res_fits = k.private_size == 0 && e->tiles * waves <= c->res_wave_cap;
+    return QS_OK;
+}
+
+bool res_running(const QsChainLane &L) { return L.res_launched && hsa_signal_load_relaxed(L.res_done) != 0; }
+
+// dispatch lane L's resident kernel: every tile from seq0 (!= 0) or from where it stopped (0); tiles already at or past
+// stop_seq end at once
+int res_launch(QsEnv *e, QsChainLane &L, uint64_t seq0, uint64_t stop_seq)
+{
+    QsChain *c = e->chain;
+    const size_t q = (size_t)(&L - c->lanes.data());
+    StepArgs A = make_args(e);
+    A.tile0 = L.tile0; A.tile_end = L.tile_end;
+    A.T = 1;
+    ResArgs R{};
+    R.ring = c->ring;
+    R.rseq = c->d_rseq;
+    R.wcnt = c->d_rcnt + q * 32;
+    R.fin = R.wcnt + kResWinSlots;
+    R.h_prog = c->d_hres + q * 8;
+    R.h_fin = R.h_prog + 1;
+    R.seq0 = seq0;
+    R.base = c->res_seq0;
+    R.stop_seq = stop_seq;
+    R.slots_mask = c->ring_slots - 1;
+    R.idle_ticks = c->res_idle_ticks;
+    R.lane_tiles = (unsigned)(L.tile_end - L.tile0);
+    const size_t roff = (sizeof(StepArgs) + alignof(ResArgs) - 1) / alignof(ResArgs) * alignof(ResArgs);
+    memcpy(L.res_kernarg, &A, sizeof A);
+    memcpy(L.res_kernarg + roff, &R, sizeof R);
+    __builtin_ia32_sfence();
+    (void)*(volatile uint32_t *)(L.res_kernarg + roff + sizeof R - sizeof(uint32_t));   // landed before the doorbell
+    hsa_signal_store_relaxed(L.res_done, 1);
+    chain_write_packet(c, L, PKT_RESIDENT, L.res_kernarg, (unsigned)((L.tile_end - L.tile0) * c->res_kernel.block),
+                       HSA_FENCE_SCOPE_SYSTEM, HSA_FENCE_SCOPE_SYSTEM, L.res_done);
+    L.res_launched = true;
+    ++c->res_dispatches;
+    return QS_OK;
+}
+
+// the host's view of consumption: the smallest progress word over the lanes
+void res_refresh(QsChain *c)
+{
+    uint64_t m = UINT64_MAX;
+    for (size_t q = 0; q < c->lanes.size(); ++q) {
+        QsChainLane &L = c->lanes[q];
+        L.res_prog = std::max<uint64_t>(L.res_prog, c->h_res[q * 8]);   // window words may land out of order: keep the largest
+        m = std::min<uint64_t>(m, L.res_prog);
+    }
+    c->res_retired = std::max<uint64_t>(c->res_retired, m);
+}
+
+// write descriptor s (cmd 0: a step with A's I/O pointers, 1: EXIT) once its slot is free (bounded wait)
+int res_write(QsEnv *e, uint64_t s, int cmd, const StepArgs *A)
+{
+    QsChain *c = e->chain;
+    if (c->res_retired + c->ring_slots <= s) {
+        const double t_end = res_now() + kResTimeoutS;
+        for (;;) {
+            res_refresh(c);
+            if (c->res_retired + c->ring_slots > s) break;
+            for (QsChainLane &L : c->lanes)                 // a dispatch whose tiles reached the idle limit: resume it
+                if (L.res_launched && !res_running(L)) { int r = res_launch(e, L, 0, UINT64_MAX); if (r) return r; }
+            if (res_now() > t_end)
+                return fail(QS_ERR_HIP, "queue mode: the resident step kernel consumed no descriptor for %.0f s (descriptor %llu, all "
+                            "consumed below %llu, first lane's progress %llu, %llu dispatches)", kResTimeoutS, (unsigned long long)s,
+                            (unsigned long long)c->res_retired, (unsigned long long)c->h_res[0], (unsigned long long)c->res_dispatches);
+            __builtin_ia32_pause();
+        }
+    }
+    const unsigned long long p[7] = {
+        A ? (unsigned long long)A->actions : 0, A ? (unsigned long long)A->obs : 0, A ? (unsigned long long)A->reward : 0,
+        A ? (unsigned long long)A->done : 0, A ? (unsigned long long)A->flags : 0, A ? (unsigned long long)A->term_obs : 0,
+        A ? (unsigned long long)A->term_state : 0};
+    for (int i = 0; i < 7; ++i)
+        if (p[i] & ~kResPtrMask) return fail(QS_ERR_INVALID, "queue mode: a buffer address above 2^48");
+    // eight aligned 8-byte stores, each word tagged (k_env_resident validates every word by itself: no order among them)
+    const unsigned long long tag = (unsigned long long)(s & 0xffff) << 48;
+    volatile unsigned long long *w = c->ring + (s & (c->ring_slots - 1)) * kResWords;
+    for (int i = 0; i < 7; ++i) w[i] = p[i] | tag;
+    w[7] = ((unsigned long long)cmd << 32) | (unsigned long long)(uint32_t)(s >> 16) | tag;
+    __builtin_ia32_sfence();                       // out of the write-combining buffers: the GPU sees it without a doorbell
+    return QS_OK;
+}
+
+// the resident roll-out in progress ends: EXIT, then every lane's dispatch has ended with every tile at the EXIT (bounded wait)
+int res_finish(QsEnv *e)
+{
+    QsChain *c = e->chain;
+    if (!c->res_open) return QS_OK;
+    const uint64_t s = c->res_issued;
+    int r = res_write(e, s, 1, nullptr);
+    if (r) return r;
+    c->res_issued = s + 1;
+    const double t_end = res_now() + kResTimeoutS;
+    for (;;) {
+        bool all = true;
+        for (size_t q = 0; q < c->lanes.size(); ++q) {
+            QsChainLane &L = c->lanes[q];
+            if (res_running(L)) { all = false; continue; }
+            if (hsa_signal_load_scacquire(L.res_done) == 0 && c->h_res[q * 8 + 1] >= s + 1) continue;
+            r = res_launch(e, L, 0, s + 1);          // tiles that stopped at the idle limit before the EXIT: to the EXIT
+            if (r) return r;
+            all = false;
+        }
+        if (all) break;
+        if (res_now() > t_end)
+            return fail(QS_ERR_HIP, "queue mode: the resident step kernel did not end within %.0f s of its EXIT descriptor", kResTimeoutS);
+        __builtin_ia32_pause();
+    }
+    c->res_retired = s + 1;
+    c->res_open = false;
+    return QS_OK;
+}
+
+// one host-ordered step through the resident kernel
+int res_step(QsEnv *e, const StepArgs &A)
+{
+    QsChain *c = e->chain;
+    if (!c->res_open) {
+        // a new roll-out: the handle's HIP-side work has finished and this roll-out's counters start from zero
+        if (c->hip_dirty) HIP_TRY(hipMemsetAsync(c->d_owner, 0xff, (size_t)e->tiles * sizeof(unsigned), e->stream));
+        HIP_TRY(hipMemsetAsync(c->d_rcnt, 0, c->lanes.size() * 32 * sizeof(unsigned), e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        c->hip_dirty = false;
+        if (c->pkt_unreleased) {
+            // step packets of this handle left tiles' state dirty in an XCD's L2: written back before any workgroup may load it
+            for (QsChainLane &L : c->lanes)
+                chain_write_packet(c, L, PKT_BARRIER, nullptr, 0, HSA_FENCE_SCOPE_NONE, HSA_FENCE_SCOPE_SYSTEM, hsa_signal_t{0});
+            c->pkt_unreleased = false;
+        }
+        c->res_seq0 = c->res_issued;
+        for (QsChainLane &L : c->lanes) L.res_launched = false;
+        c->res_open = true;
+    }
+    const uint64_t s = c->res_issued;
+    int r = res_write(e, s, 0, &A);
+    if (r) return r;
+    c->res_issued = s + 1;
+    for (QsChainLane &L : c->lanes)
+        if (!L.res_launched) { r = res_launch(e, L, c->res_seq0, UINT64_MAX); if (r) return r; }
+        else if (!res_running(L)) { r = res_launch(e, L, 0, UINT64_MAX); if (r) return r; }
+    return QS_OK;
+}
+
 // every packet has run and what it wrote is visible to the whole system (host wait); reports a misplaced tile
 int chain_drain(QsEnv *e)
 {
     QsChain *c = e->chain;
-    if (!c || !c->dirty) return QS_OK;
+    if (!c) return QS_OK;
+    int rr = res_finish(e);
+    if (!c->dirty) return rr;
     for (QsChainLane &L : c->lanes) {
         hsa_signal_store_relaxed(L.done, 1);
         chain_write_packet(c, L, PKT_BARRIER, nullptr, 0, HSA_FENCE_SCOPE_NONE, HSA_FENCE_SCOPE_SYSTEM, L.done);
     }
+    const double t_end = res_now() + kResTimeoutS;
     for (QsChainLane &L : c->lanes)
-        while (hsa_signal_wait_scacquire(L.done, HSA_SIGNAL_CONDITION_LT, 1, UINT64_MAX, HSA_WAIT_STATE_ACTIVE) != 0) {}
+        while (hsa_signal_wait_scacquire(L.done, HSA_SIGNAL_CONDITION_LT, 1, 1000000, HSA_WAIT_STATE_ACTIVE) != 0)
+            if (res_now() > t_end) return fail(QS_ERR_HIP, "queue mode: the private queue did not drain within %.0f s", kResTimeoutS);
     c->dirty = false;
+    c->pkt_unreleased = false;
     if (*c->h_err) {
         *c->h_err = 0;
         return fail(QS_ERR_HIP, "queue mode: a workgroup ran on another XCD than the one holding its tile; the steps since the last "
                                 "synchronisation are invalid (this placement is not promised by HIP: use qs_set_queue_mode(env, 0))");
     }
-    return QS_OK;
+    return rr;
 }
 
 // T consecutive steps (T kernarg blocks: steps[t] differ in their I/O pointers only) on every lane, behind ONE hand-shake with
@@ -436,6 +705,7 @@ int chain_drain(QsEnv *e)
 int chain_submit(QsEnv *e, const StepArgs *steps, int64_t T)
 {
     QsChain *c = e->chain;
+    if (c->res_open) { int rf = res_finish(e); if (rf) return rf; }   // the packet chain continues where the resident kernel ended
     if (*c->h_err) {
         // a workgroup of an EARLIER step found its tile on another XCD (the word is host memory: no synchronisation needed to see
         // it).  Reported here as well as at the next drain, so that a loop of nothing but steps cannot run on unnoticed; the flag
@@ -508,12 +778,29 @@ int chain_submit(QsEnv *e, const StepArgs *steps, int64_t T)
         }
     }
     c->dirty = true;
+    c->pkt_unreleased = true;
     if (c->stream_ordered)
         for (QsChainLane &L : c->lanes)
             HIP_TRY(hipStreamWaitValue64(e->stream, L.rev_ptr, (uint64_t)L.rev_value, hipStreamWaitValueEq, ~0ull));
     return QS_OK;
 }
 
-int chain_step(QsEnv *e, const StepArgs &A) { return chain_submit(e, &A, 1); }
+// one step: through the resident kernel where it applies (host-ordered, the role-split kernel, every tile on the chip at once,
+// no placement-guard test armed), else one packet per lane.  (The instantiation cannot change inside a roll-out: every call
+// that changes it drains first.)
+int chain_step(QsEnv *e, const StepArgs &A)
+{
+    QsChain *c = e->chain;
+    if (c->res_enabled && !c->stream_ordered && !c->dbg_shift && !c->res_dbg_packets && !*c->h_err) {
+        int r = chain_resolve_kernel(e);
+        if (r) return r;
+        r = res_resolve_kernel(e);
+        if (r) return r;
+        if (c->res_fits) {
+            return res_step(e, A);
+        }
+    }
+    return chain_submit(e, &A, 1);
+}
 
 }  // namespace

@@ -296,6 +296,22 @@ void launch_one(hipStream_t s, const StepArgs &A)
     else hipLaunchKernelGGL((k_env<INTEG, PARAMS, RMODE>), dim3((unsigned)((tiles + kBlock / kTile - 1) / (kBlock / kTile))), dim3(kBlock), 0, s, A);
 }
 
+// the resident form of every role-split instantiation: dispatched by name from the private queues only (private_queue.hpp)
+#define QS_RES_KERNELS(I)                                                                                               \
+    template __global__ void k_env_resident<I, false, 0, 0>(StepArgs, ResArgs);                                         \
+    template __global__ void k_env_resident<I, true, 0, 0>(StepArgs, ResArgs);                                          \
+    template __global__ void k_env_resident<I, false, 1, 0>(StepArgs, ResArgs);                                         \
+    template __global__ void k_env_resident<I, true, 1, 0>(StepArgs, ResArgs);                                          \
+    template __global__ void k_env_resident<I, false, 1, 2>(StepArgs, ResArgs);                                         \
+    template __global__ void k_env_resident<I, true, 1, 2>(StepArgs, ResArgs);                                          \
+    template __global__ void k_env_resident<I, true, 2, 0>(StepArgs, ResArgs);                                          \
+    template __global__ void k_env_resident<I, true, 2, 2>(StepArgs, ResArgs);                                          \
+    template __global__ void k_env_resident<I, false, 3, 0>(StepArgs, ResArgs);                                         \
+    template __global__ void k_env_resident<I, true, 3, 0>(StepArgs, ResArgs);
+QS_RES_KERNELS(0)
+QS_RES_KERNELS(1)
+#undef QS_RES_KERNELS
+
 template <int INTEG>
 void launch_integ(hipStream_t s, const StepArgs &A, bool params, int rmode)
 {
@@ -343,6 +359,7 @@ int main_stream_entry(QsEnv *e)
     if (e->chain) {
         int rc = chain_drain(e);
         e->chain->hip_dirty = true;
+        e->chain->res_dbg_packets = false;            // a placement-guard test's packet steps end here
         if (rc) return rc;
     }
     return QS_OK;
@@ -1447,6 +1464,7 @@ int qs_debug_chain_poison_owner(QsEnv *e)
     if (rc) return rc;
     HIP_TRY(hipMemset(e->chain->d_owner, 9, (size_t)e->tiles * sizeof(unsigned)));
     e->chain->hip_dirty = false;          // keep the poisoned owners: the next step must not reset them
+    e->chain->res_dbg_packets = true;     // ... and is a packet of the guarded chain, as are the steps up to the next drain
     return QS_OK;
 }
 
@@ -1462,6 +1480,16 @@ int qs_debug_chain_shift_once(QsEnv *e, int32_t shift)
 {
     if (!e || !e->chain) return fail(QS_ERR_INVALID, "qs_debug_chain_shift_once: not in private-queue mode");
     e->chain->dbg_shift = shift;
+    e->chain->res_dbg_packets = true;     // this step and the ones up to the next drain: packets of the guarded chain
+    return QS_OK;
+}
+
+// Diagnostic (not in quadsim.h; tests and A/B tools only): resident step-kernel dispatches the handle's private queues have
+// issued so far (relaunches after the idle limit included); 0 outside private-queue mode
+int qs_debug_chain_resident(QsEnv *e, uint64_t *dispatches)
+{
+    if (!e || !dispatches) return fail(QS_ERR_INVALID, "qs_debug_chain_resident: null argument");
+    *dispatches = e->chain ? e->chain->res_dispatches : 0;
     return QS_OK;
 }
 

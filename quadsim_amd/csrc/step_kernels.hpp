@@ -332,6 +332,424 @@ __global__ __launch_bounds__(kBlock) void k_env(StepArgs A)
 // waves per workgroup of k_env_split: with PREP == 2 the rocRAND reset modes get a third wave
 constexpr int split_waves(int rmode, int prep) { return (prep == 2 && (rmode == 1 || rmode == 2)) ? 3 : 2; }
 
+// ---- resident form of k_env_split (host-ordered private queues; private_queue.hpp, "resident roll-out") -------------------
+// One dispatch per private queue steps its tiles for as many steps as the host issues.  Before each step the chaser wave takes
+// that step's I/O pointers from a descriptor ring the host writes ahead of the GPU; the state stays in registers from one step
+// to the next and is stored once, when the tile leaves.  A step computes exactly what k_env_split computes (same body below).
+//
+// A descriptor is 8 naturally aligned 64-bit words (one 64-B slot): actions | obs | reward | done | flags | term_obs |
+// term_state | command.  EVERY word carries the low 16 bits of the step's sequence number (the tag) in bits 48..63, beside a
+// 48-bit pointer; the command word also holds sequence bits 16..47 in its bits 0..31.  Slot s % slots holds step s.
+//   - Torn slot: each word is single-copy atomic (an aligned 8-byte store on the host, an 8-byte atomic load here) and
+//     validates itself: a word of another lap carries another tag.  No ordering between the words is needed.
+//   - Stale slot: the host rewrites a slot only after every tile has consumed it, so memory holds the current or the previous
+//     lap; a slot of an earlier lap served from some cache carries an older sequence number in the command word (32 more bits),
+//     so it never passes for a fresh one.  A slot that is not fresh is polled again (system-scope loads, s_sleep between them)
+//     until it is or until the idle limit: a wrong descriptor -- a wild pointer -- is never used.
+constexpr int kResWords = 8;
+constexpr unsigned long long kResPtrMask = (1ull << 48) - 1;
+enum { RES_STEP = 0, RES_EXIT = 1, RES_IDLE = 2, RES_SKIP = 3 };
+// Progress: every tile reports once per kResWin descriptors (staggered by tile % kResWin, so ~tiles / kResWin agent-scope adds
+// per step, not one per tile) into window counter (s - base + tile % kResWin + 1) / kResWin, counted from the roll-out's first
+// descriptor `base` so that every window receives one report from every tile; the tile whose add completes a window writes
+// ONE host word: every tile of the dispatch has consumed every descriptor before it.  The host reuses slots by it.
+constexpr int kResWin = 32;
+constexpr int kResWinSlots = 16;     // > slots / kResWin + 2 windows in flight (the host checks)
+
+struct ResArgs {
+    const unsigned long long *ring;   // [slots][8] descriptors: device memory the host writes through the PCIe BAR
+    unsigned long long *rseq;         // [tiles] next descriptor of each tile (written when the tile leaves)
+    unsigned *wcnt;                   // [kResWinSlots] this dispatch's window counters (zeroed by the host per roll-out)
+    unsigned *fin;                    // this dispatch's count of tiles that consumed the EXIT descriptor (zeroed likewise)
+    unsigned long long *h_prog;       // host word: descriptors below it are consumed by every tile of the dispatch
+    unsigned long long *h_fin;        // host word: EXIT seq + 1 once every tile of the dispatch has consumed the EXIT
+    unsigned long long seq0;          // != 0: every tile starts at seq0 (first dispatch of a roll-out), else at rseq[tile]
+    unsigned long long base;          // the roll-out's first descriptor (progress windows count from it)
+    unsigned long long stop_seq;      // a tile whose next descriptor is >= stop_seq ends at once (relaunch after an EXIT)
+    unsigned long long slots_mask;    // slots - 1
+    unsigned long long idle_ticks;    // 100 MHz ticks without a fresh descriptor after which a tile stores its state and ends
+    unsigned lane_tiles;              // tiles of this dispatch
+};
+
+struct ResDesc {
+    const float *actions;
+    float *obs, *reward;
+    uint8_t *done, *flags;
+    float *term_obs, *term_state;
+};
+
+// lanes 0..7 (and their copies above) each request one word of slot s: one 64-B request, system scope (never an L1 line)
+__device__ __forceinline__ unsigned long long res_request(const ResArgs &R, unsigned long long s, int lane)
+{
+    return __hip_atomic_load(R.ring + (s & R.slots_mask) * kResWords + (lane & 7), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+__device__ __forceinline__ bool res_fresh(unsigned long long w, unsigned long long s, int lane)
+{
+    bool ok = (w >> 48) == (s & 0xffffull);
+    if ((lane & 7) == 7) ok = ok && (unsigned)w == (unsigned)(s >> 16);
+    return __all(ok);
+}
+
+__device__ __forceinline__ unsigned long long res_word(unsigned long long w, int i)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)w, i);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(w >> 32), i);
+    return (((unsigned long long)hi << 32) | lo) & kResPtrMask;
+}
+
+// descriptor s from the word `w` requested earlier, polled again until fresh or for at most R.idle_ticks
+__device__ __forceinline__ int res_resolve(const ResArgs &R, unsigned long long s, int lane, unsigned long long w, ResDesc &D)
+{
+    if (!res_fresh(w, s, lane)) {
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        for (;;) {
+            __builtin_amdgcn_s_sleep(4);
+            w = res_request(R, s, lane);
+            if (res_fresh(w, s, lane)) break;
+            if (__builtin_amdgcn_s_memrealtime() - t0 > R.idle_ticks) return RES_IDLE;
+        }
+    }
+    D.actions = (const float *)res_word(w, 0);
+    D.obs = (float *)res_word(w, 1);
+    D.reward = (float *)res_word(w, 2);
+    D.done = (uint8_t *)res_word(w, 3);
+    D.flags = (uint8_t *)res_word(w, 4);
+    D.term_obs = (float *)res_word(w, 5);
+    D.term_state = (float *)res_word(w, 6);
+    return ((res_word(w, 7) >> 32) & 0xff) == 0 ? RES_STEP : RES_EXIT;
+}
+
+// the action row of step descriptor D: a system-scope (`sc0 sc1`) buffer load -- the caller may have rewritten the same
+// buffer since an earlier step of this dispatch, so no L1 or stale L2 line may serve it; rows past io_n read as zeros
+__device__ __forceinline__ float4 res_action(const float *actions, int64_t io, int64_t io_n)
+{
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)actions, (short)0, (int)(io_n * 16), 0x00020000);
+    const u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(io * 16), 0, 17);   // cache policy 17: sc0 sc1
+    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+}
+
+// lane 0, after consuming step descriptor s: the tile's report into its progress window, if s closes one (wave-uniform);
+// returns the counter's previous value, checked by res_report_done once the add has long returned
+__device__ __forceinline__ unsigned res_report(const ResArgs &R, unsigned long long s, int64_t tile, int lane)
+{
+    const unsigned long long x = s - R.base + (unsigned long long)(tile % kResWin) + 1;
+    if (x % kResWin != 0) return ~0u;
+    unsigned old = 0;
+    if (lane == 0) old = __hip_atomic_fetch_add(R.wcnt + (x / kResWin) % kResWinSlots, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return old;
+}
+
+__device__ __forceinline__ void res_report_done(const ResArgs &R, unsigned old, unsigned long long s, int64_t tile, int lane)
+{
+    if (old == ~0u || lane != 0 || (old + 1) % R.lane_tiles != 0) return;
+    // the window is complete: every tile consumed its report descriptor, the earliest of them base + x - kResWin
+    const unsigned long long x = s - R.base + (unsigned long long)(tile % kResWin) + 1;
+    __hip_atomic_store(R.h_prog, R.base + x - kResWin + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// k_env_split's body, stepping from the descriptor ring until an EXIT descriptor or the idle limit: the same device functions in
+// the same order, phase for phase (k_env_split itself is left as it is: its machine code, and with it the packet chain's and the
+// HIP stream's timing, does not change).  Differences: barrier #0 before the first step, the next descriptor requested at the
+// top of a step and resolved where k_env_split requests the next action, the per-step pointers of descriptor D, the state
+// stored once when the tile leaves.
+template <int INTEG, bool PARAMS, int RMODE, int PREP>
+__global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs R)
+{
+    __shared__ float s_tgt[13][kTile];
+    // PREP == 2: [chaser reset state 13 | its observation 12 | per-episode params 4][lane]: what a reset of THIS step would
+    // install, prepared every step off the chaser wave's critical path.  One buffer suffices in a roll-out too: it is written
+    // between barriers #1 and #2 of a step and read behind #2; the next write is behind the NEXT step's #1, which the readers
+    // have passed.  PREP == 0: [step parity][block]: the chaser wave reads step t's Philox words while t+1's are drawn.
+    constexpr bool kPrep = PREP == 2 && (RMODE == 1 || RMODE == 2);
+    __shared__ float s_rst[kPrep ? 29 : 1][kTile];
+    __shared__ uint4 s_phx[kPrep ? 1 : 2][kPrep ? 1 : 2][kTile];
+    __shared__ unsigned char s_done[kTile], s_limt[kTile];
+    // [step parity] the command of the next step and its term_state pointer, written by the chaser wave before #1 of a step
+    // and read by every wave behind #2 of that step; the next write of the same parity is behind two more #1s
+    __shared__ int s_cmd[2];
+    __shared__ unsigned long long s_tsp[2];
+    const int lane = threadIdx.x & (kTile - 1);
+    const int role = threadIdx.x >> 6;
+    const int64_t tile = launch_tile(A, blockIdx.x);   // grid = the tiles of this launch's env group
+    const int64_t env = tile * kTile + lane;
+    bool active = env < A.n;                     // idle lanes of the tail tile compute on zeros and store nothing
+    const int64_t io = env - A.io_env0;          // row of this env in the I/O arrays
+    QS_ASSERT(tile < A.tile_end && (!active || (io >= 0 && io < A.io_n)));
+    const uint64_t k0 = step_counter_begin_vmem(A, tile);
+    // the tile's first descriptor, handed to the other waves behind one extra barrier per dispatch
+    unsigned long long seq = 0;
+    int cmd = RES_STEP;
+    ResDesc D{};
+    {
+        if (role == 0) {
+            seq = R.seq0 ? R.seq0 : R.rseq[tile];
+            seq = ((unsigned long long)__builtin_amdgcn_readfirstlane((int)(unsigned)(seq >> 32)) << 32) |
+                  (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)seq);
+            cmd = seq >= R.stop_seq ? RES_SKIP : res_resolve(R, seq, lane, res_request(R, seq, lane), D);
+            if (cmd == RES_STEP) res_report_done(R, res_report(R, seq, tile, lane), seq, tile, lane);
+            if (lane == 0) { s_cmd[0] = cmd; s_tsp[0] = (unsigned long long)D.term_state; }
+        }
+        __syncthreads();                                                  // #0
+        cmd = s_cmd[0];
+    }
+    QS_STAMP_DECL;
+    QS_STAMP_AT(0);
+    const float *b = A.st + tile * (int64_t)(kRecWords * kTile) + lane;
+    float *bw = A.st + tile * (int64_t)(kRecWords * kTile) + lane;
+    Par P = A.par_nom;
+    if (PARAMS) P = load_par(A.par, tile, lane);
+    if (role == 0) {
+        // in a roll-out the chaser wave is the long pole of every step while target waves on the same SIMD run ahead with
+        // speculative draws: give it the issue slots first (roll-out 2.28 -> 2.13 us/step; no help for a single step)
+        __builtin_amdgcn_s_setprio(3);
+        float sc[13], uc[4];
+#pragma unroll
+        for (int i = 0; i < 13; ++i) sc[i] = b[(F_SC + i) * kTile];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) uc[i] = b[(F_UC + i) * kTile];
+        float ls = b[F_LS * kTile], tt = b[F_T * kTile];
+        // the action is requested LAST: loads return in issue order, and the action -- fresh from the caller, the one
+        // operand that is not cache-resident -- is not needed before the integration (which uses the PREVIOUS limited
+        // control, quadrotor.py:126-144) is done; its miss latency hides under drone_advance
+        float4 av_next = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (cmd == RES_STEP && active) av_next = res_action(D.actions, io, A.io_n);
+#if defined(QS_STAMP) && QS_STAMP + 0 < 2
+        asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+#endif
+        QS_STAMP_AT(1);
+        int64_t t = 0;
+#pragma clang loop unroll(disable)
+        for (; cmd == RES_STEP; ++t) {
+            const uint64_t k = k0 + (uint64_t)t;
+            const int64_t o = io;
+            const unsigned long long wn = res_request(R, seq + t + 1, lane);   // the next descriptor, a step ahead of its use
+            tt += 1.0f;
+            const bool lim_c = drone_advance<INTEG>(sc, uc, P, A.C.dt);   // Drone.step's integration: previous control only
+            float a[4];
+            ResDesc Dn{};
+            unsigned rep = ~0u;
+            const float4 av = av_next;
+            const int cmdn = res_resolve(R, seq + t + 1, lane, wn, Dn);
+            if (cmdn == RES_STEP) {
+                if (active) av_next = res_action(Dn.actions, io, A.io_n);
+                rep = res_report(R, seq + t + 1, tile, lane);
+            }
+            if (lane == 0) { s_cmd[(t + 1) & 1] = cmdn; s_tsp[(t + 1) & 1] = (unsigned long long)Dn.term_state; }
+            a[0] = av.x; a[1] = av.y; a[2] = av.z; a[3] = av.w;
+            float u_c[4];
+            chaser_command(a, P.m, u_c);
+            u_limit(u_c, P.m * kG, uc);                                   // ... and the hand-over of the new limited control
+            QS_STAMP_AT(2);
+            __syncthreads();                                              // #1: the target's new state is in LDS
+            QS_STAMP_AT(3);
+            float st[13];
+#pragma unroll
+            for (int i = 0; i < 13; ++i) st[i] = s_tgt[i][lane];
+            const bool lim_t = s_limt[lane] != 0;
+            float obs[12], reward;
+            unsigned flags;
+            rel_obs(sc, st, obs);
+            score_step(obs, a, sc[2], tt, ls, A.C, lim_c, lim_t, reward, flags);
+            const bool done = (flags & (FLAG_OVERLIMIT | FLAG_OVERTIME)) != 0;
+            const bool rs = done && A.auto_reset;
+            s_done[lane] = rs ? 1 : 0;
+            QS_STAMP_AT(4);
+            __syncthreads();                                              // #2: reset flags out, this step's Philox words in
+            QS_STAMP_AT(5);
+            if (rs) {
+                if (D.term_obs && active) store_obs(D.term_obs, io, obs);
+                if (D.term_state && active) {
+                    float *ts = D.term_state + io * 26;
+#pragma unroll
+                    for (int i = 0; i < 13; ++i) ts[i] = sc[i];
+                }
+                float ic[13], it[13];
+                if (RMODE == 0) {
+                    nominal_init(ic, it);
+#pragma unroll
+                    for (int i = 0; i < 12; ++i) obs[i] = A.nominal_obs[i];
+                } else if (RMODE == 3) {
+                    const float *src = A.init + (active ? env : 0) * 26;
+#pragma unroll
+                    for (int i = 0; i < 13; ++i) { ic[i] = src[i]; it[i] = src[13 + i]; }
+                    rel_obs<false>(ic, it, obs);
+                } else {
+                    if (kPrep) {
+                        // the reset state, its observation and the episode's parameters were prepared by the third wave: a copy
+#pragma unroll
+                        for (int i = 0; i < 13; ++i) ic[i] = s_rst[i][lane];
+#pragma unroll
+                        for (int i = 0; i < 12; ++i) obs[i] = s_rst[13 + i][lane];
+                        if (PARAMS && RMODE == 2) P = Par{s_rst[25][lane], s_rst[26][lane], s_rst[27][lane], s_rst[28][lane]};
+                    } else {
+                        const uint4 w0 = s_phx[t & 1][0][lane], w1 = RMODE == 2 ? s_phx[t & 1][1][lane] : make_uint4(0, 0, 0, 0);
+                        Par Pn;
+                        random_init_apply<RMODE == 2>(A.rc, w0, w1, ic, it, Pn);
+                        if (PARAMS && RMODE == 2) P = Pn;
+                        rel_obs<true>(ic, it, obs);
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < 13; ++i) sc[i] = ic[i];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) uc[i] = 0.0f;
+                ls = 0.0f;
+                tt = 0.0f;
+            }
+            QS_STAMP_AT(6);
+            if (active) {
+                store_obs(D.obs, o, obs);
+                QS_SO(&D.reward[o], reward);
+                QS_SO(&D.done[o], (uint8_t)(done ? 1 : 0));
+                if (D.flags) QS_SO(&D.flags[o], (uint8_t)flags);
+            }
+            res_report_done(R, rep, seq + t + 1, tile, lane);
+            D = Dn;
+            cmd = cmdn;
+        }
+        if (t > 0) {
+            if (active) {
+#pragma unroll
+                for (int i = 0; i < 13; ++i) QS_ST(&bw[(F_SC + i) * kTile], sc[i]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) QS_ST(&bw[(F_UC + i) * kTile], uc[i]);
+                QS_ST(&bw[F_LS * kTile], ls);
+                QS_ST(&bw[F_T * kTile], tt);
+                if (PARAMS && RMODE == 2) store_par(A.par, tile, lane, P);
+            }
+        }
+        {
+            // the tile leaves: its step counter, its next descriptor, and -- after an EXIT -- its count towards the drain
+            if (cmd != RES_SKIP && lane == 0) {
+                if (t > 0) A.ctr[tile] = k0 + (uint64_t)t;
+                R.rseq[tile] = seq + (unsigned long long)t + (cmd == RES_EXIT ? 1 : 0);
+                if (cmd == RES_EXIT) {
+                    const unsigned old = __hip_atomic_fetch_add(R.fin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (old + 1 == R.lane_tiles)
+                        __hip_atomic_store(R.h_fin, seq + (unsigned long long)t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
+            }
+        }
+#if defined(QS_STAMP) && QS_STAMP + 0 < 2
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+        QS_STAMP_AT(7);
+        QS_STAMP_FLUSH();
+    } else if (role == 1) {
+        float st[13], ut[4], qd[4];
+#pragma unroll
+        for (int i = 0; i < 13; ++i) st[i] = b[(F_ST + i) * kTile];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ut[i] = b[(F_UT + i) * kTile];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) qd[i] = b[(F_QD + i) * kTile];
+        const float pdes[3] = {10.0f, -50.0f, 5.0f};              // docking_env.py:60
+        const float vdes[3] = {A.C.vdes_x, 0.0f, 0.0f};
+        const float dv[3] = {0.0f, 0.0f, 0.0f};
+#if defined(QS_STAMP) && QS_STAMP + 0 < 2
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+        QS_STAMP_AT(1);
+        int64_t t = 0;
+#pragma clang loop unroll(disable)
+        for (; cmd == RES_STEP; ++t) {
+            const uint64_t k = k0 + (uint64_t)t;
+            float pre[13];
+#pragma unroll
+            for (int i = 0; i < 13; ++i) pre[i] = st[i];
+            const bool lim_t = drone_advance<INTEG>(st, ut, P, A.C.dt);   // with the previous limited control
+#pragma unroll
+            for (int i = 0; i < 13; ++i) s_tgt[i][lane] = st[i];
+            s_limt[lane] = lim_t ? 1 : 0;
+            uint4 w0 = make_uint4(0, 0, 0, 0), w1 = w0;
+            Par Pn = P;
+            if ((RMODE == 1 || RMODE == 2) && !kPrep) {
+                random_init_words<RMODE == 2>(A.rc, STREAM_AUTORESET, A.gid0 + (uint64_t)env, k + 1, w0, w1);
+                s_phx[t & 1][0][lane] = w0;
+                if (RMODE == 2) s_phx[t & 1][1][lane] = w1;     // the params block: only drawn with per-episode params
+            }
+            QS_STAMP_AT(2);
+            __syncthreads();                                              // #1
+            QS_STAMP_AT(3);
+            float u_t[4];
+            target_control(A.C.kind, pdes, vdes, qd, 0.0f, pre, dv, P.m, u_t);   // from the state BEFORE stepping
+            u_limit(u_t, P.m * kG, ut);
+            QS_STAMP_AT(4);
+            __syncthreads();                                              // #2
+            QS_STAMP_AT(5);
+            if (s_done[lane]) {
+                float *const term_state = (float *)s_tsp[t & 1];
+                if (term_state && active) {
+                    float *ts = term_state + io * 26 + 13;
+#pragma unroll
+                    for (int i = 0; i < 13; ++i) ts[i] = st[i];
+                }
+                float ic[13], it[13];
+                if (RMODE == 3) {
+                    const float *src = A.init + (active ? env : 0) * 26;
+#pragma unroll
+                    for (int i = 0; i < 13; ++i) it[i] = src[13 + i];
+                } else {
+                    nominal_init(ic, it);
+                    if (PARAMS && RMODE == 2) {
+                        if (kPrep) {
+                            Pn = Par{s_rst[25][lane], s_rst[26][lane], s_rst[27][lane], s_rst[28][lane]};
+                        } else {
+                            random_init_apply<true>(A.rc, w0, w1, ic, it, Pn);
+                            nominal_init(ic, it);
+                        }
+                        P = Pn;
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < 13; ++i) st[i] = it[i];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) ut[i] = 0.0f;
+            }
+            cmd = s_cmd[(t + 1) & 1];
+        }
+        if (active && t > 0) {
+#pragma unroll
+            for (int i = 0; i < 13; ++i) QS_ST(&bw[(F_ST + i) * kTile], st[i]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) QS_ST(&bw[(F_UT + i) * kTile], ut[i]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) QS_ST(&bw[(F_QD + i) * kTile], qd[i]);
+        }
+        QS_STAMP_AT(6);
+        QS_STAMP_FLUSH();
+    }
+    else if (kPrep) {
+        // third wave (rocRAND reset modes only): what a reset of each step would install -- the draw, random_init_apply and the
+        // state2rel of the result: the same device functions the serial kernel runs inside its reset branch, so the same bits --
+        // for EVERY lane, into LDS; it touches no global memory but the step counter and joins both barriers of every step.  The
+        // chaser wave's reset branch is a 25-word copy, the target wave draws nothing.
+        int64_t t = 0;
+#pragma clang loop unroll(disable)
+        for (; cmd == RES_STEP; ++t) {
+            const uint64_t k = k0 + (uint64_t)t;
+            uint4 w0, w1 = make_uint4(0, 0, 0, 0);
+            random_init_words<RMODE == 2>(A.rc, STREAM_AUTORESET, A.gid0 + (uint64_t)env, k + 1, w0, w1);
+            __syncthreads();                                              // #1
+            float ic[13], it_[13], robs[12];
+            Par Pn;
+            random_init_apply<RMODE == 2>(A.rc, w0, w1, ic, it_, Pn);
+            rel_obs<true>(ic, it_, robs);
+#pragma unroll
+            for (int i = 0; i < 13; ++i) s_rst[i][lane] = ic[i];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) s_rst[13 + i][lane] = robs[i];
+            if (PARAMS && RMODE == 2) {
+                s_rst[25][lane] = Pn.m; s_rst[26][lane] = Pn.Ixx; s_rst[27][lane] = Pn.Iyy; s_rst[28][lane] = Pn.Izz;
+            }
+            __syncthreads();                                              // #2
+            cmd = s_cmd[(t + 1) & 1];
+        }
+    }
+}
+
 template <int INTEG, bool PARAMS, int RMODE, int PREP>
 __global__ __launch_bounds__(3 * kTile) void k_env_split(StepArgs A)
 {
