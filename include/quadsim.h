@@ -342,6 +342,22 @@ int qs_policy_rollout_fast(QsEnv *env, int64_t T, const void *packed_weights, fl
                            uint8_t *flags, float *actions);
 int qs_policy_rollout_fast_blob_bytes(void);
 
+/* Deterministic evaluation: every env runs `episodes` complete episodes of a = clip(MLP(obs), -1, 1) from its CURRENT state
+ * (auto-reset between them, as the step API), or stops after max_steps steps -- SB2's evaluate_policy / the EvalCallback of
+ * run_docking_ppo2.py:75-83 for N envs in one launch.  The handle's state, parameters and step counters are not modified:
+ * evaluating twice gives the same episodes, and the handle steps on afterwards as if the call had not been made.
+ * Outputs [episodes, N] episode-major; slots of episodes not finished are left untouched.  ep_return = float64 sum of the
+ * episode's float32 step rewards in step order; ep_length = steps; ep_flags = OR of the step flags of the episode;
+ * ep_docked = steps with QS_FLAG_DOCKED; finished [N] = episodes completed.  ep_flags / ep_docked nullable; ep_return
+ * 8-byte, ep_length / ep_docked / finished 4-byte aligned.  docking-v0 / v1 / v2, auto_reset, device buffers; every randomise
+ * mode, per-env params.  Weights as for qs_policy_rollout; _fast: packed_weights as for qs_policy_rollout_fast.
+ * Added after QS_VERSION 131 without changing it: callers detect these two entry points by symbol (dlsym). */
+int qs_policy_evaluate(QsEnv *env, int32_t episodes, int64_t max_steps,
+                       const float *wt1, const float *b1, const float *wt2, const float *b2, const float *wt3, const float *b3,
+                       double *ep_return, int32_t *ep_length, uint8_t *ep_flags, int32_t *ep_docked, int32_t *finished);
+int qs_policy_evaluate_fast(QsEnv *env, int32_t episodes, int64_t max_steps, const void *packed_weights,
+                            double *ep_return, int32_t *ep_length, uint8_t *ep_flags, int32_t *ep_docked, int32_t *finished);
+
 /* PPO2 data collection in ONE launch: Runner._run's loop, rl_baselines/ppo2/ppo2.py:472-499, plus last_values (:506),
  * for the N envs of the handle and T = n_steps, with the actor-critic MlpPolicy the reference trains and ships
  * (trained_model/best_model_v0.zip; rl_baselines/common/policies.py:35-92,:583-588): shared_fc0 12->128, then

@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("QUADSIM_HIP_LIB") or os.path.join(CSRC, "libquadsim_hip.so")  # override: A/B builds
 SOURCES = [os.path.join(CSRC, "quadsim_hip.hip")]
 HEADERS = [os.path.join(CSRC, h) for h in ("quadsim_device.hpp", "step_kernels.hpp", "rollout_ops.hpp", "policy_rollout.hpp", "env_groups.hpp",
-                                          "private_queue.hpp")] + [os.path.join(HERE, "..", "include", "quadsim.h")]
+                                          "private_queue.hpp", "policy_evaluate.hpp")] + [os.path.join(HERE, "..", "include", "quadsim.h")]
 
 QS_OK = 0
 KIND_V0, KIND_V2, KIND_V1, KIND_HOVER = 0, 1, 2, 3
@@ -28,7 +28,7 @@ EXPORTS = [
     "qs_rollout", "qs_rollout_slab", "qs_rollout_stepwise", "qs_fill_random_actions", "qs_get_state", "qs_set_state", "qs_set_params", "qs_get_params",
     "qs_set_init_state", "qs_get_init_state", "qs_obs_dim", "qs_get_step_counter", "qs_set_step_counter", "qs_set_stream", "qs_sync", "qs_timer_start", "qs_timer_stop",
     "qs_drone_step", "qs_ctrl", "qs_rel_obs", "qs_transform", "qs_gae", "qs_swap_and_flatten", "qs_expert_action", "qs_policy_rollout", "qs_policy_rollout_fast", "qs_policy_rollout_fast_blob_bytes",
-    "qs_policy_forward", "qs_policy_forward_fast",
+    "qs_policy_forward", "qs_policy_forward_fast", "qs_policy_evaluate", "qs_policy_evaluate_fast",
     "qs_runner_rollout", "qs_runner_rollout_fast", "qs_runner_rollout_fast_blob_bytes",
     "qs_runner_rollout_net", "qs_runner_rollout_net_fast", "qs_runner_rollout_net_fast_blob_bytes",
     "qs_step_ex", "qs_set_groups", "qs_group_count", "qs_group_range", "qs_group_stream", "qs_group_set_stream",
@@ -154,6 +154,8 @@ def load():
         "qs_policy_rollout_fast_blob_bytes": [],
         "qs_policy_forward": [vp, i64] + [vp] * 8,
         "qs_policy_forward_fast": [vp, i64, vp, vp, vp],
+        "qs_policy_evaluate": [vp, i32, i64] + [vp] * 11,
+        "qs_policy_evaluate_fast": [vp, i32, i64] + [vp] * 6,
         "qs_runner_rollout": [vp, i64, C.POINTER(QsActorCritic)] + [vp] * 12,
         "qs_runner_rollout_fast": [vp, i64, vp, C.POINTER(C.c_float), i32] + [vp] * 12,
         "qs_runner_rollout_fast_blob_bytes": [],

@@ -18,6 +18,7 @@
 //     step_kernels.hpp     StepArgs, the step / roll-out / policy / Runner kernels and their launch helpers
 //     rollout_ops.hpp      GAE, flatten, episode statistics            policy_rollout.hpp   the MLP on the matrix cores
 //     env_groups.hpp       env groups (qs_set_groups)                  private_queue.hpp    private AQL queues (qs_set_queue_mode)
+//     policy_evaluate.hpp  K complete episodes per env of the deterministic actor (qs_policy_evaluate)
 // and here: the handle (QsEnv), its launch / reset / bounce-buffer helpers, and the C ABI.
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
@@ -138,6 +139,7 @@ using namespace qs;
 #endif
 
 #include "step_kernels.hpp"
+#include "policy_evaluate.hpp"
 
 #ifdef QS_STAMP
 static unsigned long long *g_host_stamps = nullptr;     // qs_debug_set_stamps: handed to every launch through StepArgs
@@ -1277,6 +1279,50 @@ int qs_policy_rollout_fast(QsEnv *e, int64_t T, const void *packed_weights, floa
 }
 
 int qs_policy_rollout_fast_blob_bytes(void) { return kFastBlobBytes; }
+
+// qs_policy_evaluate / _fast: M (exact f32) or blob (split bf16), exactly one of them
+static int policy_evaluate(QsEnv *e, const char *who, int32_t episodes, int64_t max_steps, const MlpArgs *M, const void *blob,
+                           double *ep_return, int32_t *ep_length, uint8_t *ep_flags, int32_t *ep_docked, int32_t *finished)
+{
+    Range rg_(who);
+    if (episodes < 1) return fail(QS_ERR_INVALID, "%s: episodes must be >= 1", who);
+    if (max_steps < 1) return fail(QS_ERR_INVALID, "%s: max_steps must be >= 1", who);
+    if (!ep_return || !ep_length || !finished) return fail(QS_ERR_INVALID, "%s: ep_return, ep_length and finished are required", who);
+    if (e->cfg.kind == QS_KIND_HOVERING_V0) return fail(QS_ERR_INVALID, "%s: docking envs only (hovering-v0 has a 13-d observation)", who);
+    if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "%s: device buffers only", who);
+    if (!e->cfg.auto_reset) return fail(QS_ERR_INVALID, "%s: requires auto_reset (episodes follow each other as in the step API)", who);
+    if ((((uintptr_t)ep_return) & 7u) || ((((uintptr_t)ep_length) | ((uintptr_t)ep_docked) | ((uintptr_t)finished)) & 3u))
+        return fail(QS_ERR_INVALID, "%s: ep_return must be 8-byte aligned, ep_length, ep_docked and finished 4-byte aligned", who);
+    StepArgs A = make_args(e);
+    EvalArgs E{ep_return, ep_length, ep_flags, ep_docked, finished, max_steps, episodes};
+    const unsigned grid = grid_tiles(e->n);
+    const int rmode = e->init ? 3 : e->cfg.randomise;   // as launch_env_on
+    if (e->cfg.integrator == QS_INTEG_FROZEN) eval_integ<0>(e->stream, grid, A, M, (const uint4 *)blob, E, e->per_env_params, rmode);
+    else eval_integ<1>(e->stream, grid, A, M, (const uint4 *)blob, E, e->per_env_params, rmode);
+    HIP_TRY(hipGetLastError());
+    return QS_OK;
+}
+
+int qs_policy_evaluate(QsEnv *e, int32_t episodes, int64_t max_steps, const float *wt1, const float *b1, const float *wt2,
+                       const float *b2, const float *wt3, const float *b3, double *ep_return, int32_t *ep_length,
+                       uint8_t *ep_flags, int32_t *ep_docked, int32_t *finished)
+{
+    CHECK_ENV(e);
+    if (!wt1 || !b1 || !wt2 || !b2 || !wt3 || !b3) return fail(QS_ERR_INVALID, "qs_policy_evaluate: null weight pointer");
+    if ((((uintptr_t)wt2) | ((uintptr_t)wt3)) & 15u) return fail(QS_ERR_INVALID, "qs_policy_evaluate: wt2 and wt3 must be 16-byte aligned");
+    const MlpArgs M{wt1, b1, wt2, b2, wt3, b3};
+    return policy_evaluate(e, "qs_policy_evaluate", episodes, max_steps, &M, nullptr, ep_return, ep_length, ep_flags, ep_docked, finished);
+}
+
+int qs_policy_evaluate_fast(QsEnv *e, int32_t episodes, int64_t max_steps, const void *packed_weights, double *ep_return,
+                            int32_t *ep_length, uint8_t *ep_flags, int32_t *ep_docked, int32_t *finished)
+{
+    CHECK_ENV(e);
+    if (!packed_weights) return fail(QS_ERR_INVALID, "qs_policy_evaluate_fast: null packed_weights");
+    if (((uintptr_t)packed_weights & 15) != 0) return fail(QS_ERR_INVALID, "qs_policy_evaluate_fast: packed weights must be 16-byte aligned");
+    return policy_evaluate(e, "qs_policy_evaluate_fast", episodes, max_steps, nullptr, packed_weights, ep_return, ep_length, ep_flags,
+                           ep_docked, finished);
+}
 
 // 1: the one-wave-per-tile Runner kernels, 0: the role-split ones (default; QUADSIM_RUNNER_SERIAL=1 or the diagnostic entry
 // below select the former for A/B runs and for the bit-identity test)

@@ -161,3 +161,153 @@ def rollout_with_policy(env, policy, T, obs0=None):
         obs, r, d, info = env.step(a)
         O.append(obs.clone()); R.append(r.clone()); D.append(d.clone()); F.append(env._flags.clone()); A.append(a)
     return torch.stack(O), torch.stack(R), torch.stack(D), torch.stack(F), torch.stack(A)
+
+
+# ---------------------------------------------------------------- deterministic evaluation (qs_policy_evaluate)
+EPISODE_STEPS = 600          # DockingEnv's time-out: done_overtime = t >= 600 (docking_env.py:152) bounds every episode
+
+
+def _actor_of(policy):
+    """the deterministic actor (an MlpPolicy) of an MlpPolicy or an ActorCriticPolicy (either layout: its pi weights)"""
+    if isinstance(policy, MlpPolicy):
+        return policy
+    from .runner import ActorCriticPolicy
+    if isinstance(policy, ActorCriticPolicy):
+        if policy.squash:
+            raise ValueError("the evaluation kernels run the clipped actor; a squashed (tanh) ActorCriticPolicy is not supported")
+        actor = getattr(policy, "_eval_actor", None)
+        if actor is None:
+            actor = MlpPolicy.__new__(MlpPolicy)
+            actor.torch = policy.torch
+            actor.w0, actor.b0, actor.w1, actor.b1, actor.w2, actor.b2 = (policy.w0, policy.b0, policy.w1, policy.b1, policy.w2,
+                                                                          policy.b2)
+            policy._eval_actor = actor
+        return actor
+    raise TypeError("expected an MlpPolicy or an ActorCriticPolicy, got %s" % type(policy).__name__)
+
+
+class EvalResult:
+    """K episodes of N envs, as device tensors: returns [K,N] float64, lengths [K,N] int32, flags [K,N] uint8 (OR of the step
+    flags), docked_steps [K,N] int32, finished [N] int32.  Slot (k, env) holds an episode iff k < finished[env]; the summary
+    helpers use those episodes only."""
+
+    def __init__(self, returns, lengths, flags, docked_steps, finished):
+        self.returns, self.lengths, self.flags, self.docked_steps, self.finished = returns, lengths, flags, docked_steps, finished
+
+    @property
+    def episodes_per_env(self):
+        return int(self.returns.shape[0])
+
+    def valid(self):
+        """[K,N] bool: the slots that hold a finished episode"""
+        import torch
+        k = torch.arange(self.episodes_per_env, device=self.finished.device)[:, None]
+        return k < self.finished[None, :]
+
+    def _sel(self, t):
+        return t[self.valid()]
+
+    def num_episodes(self):
+        return int(self.finished.sum().item())
+
+    def mean_return(self):
+        return float(self._sel(self.returns).mean().item())
+
+    def std_return(self):
+        """population std (ddof = 0), as np.std in SB2's evaluate_policy"""
+        return float(self._sel(self.returns).std(unbiased=False).item())
+
+    def mean_length(self):
+        return float(self._sel(self.lengths).double().mean().item())
+
+    def docked_fraction(self):
+        """share of episodes with at least one docked step"""
+        return float((self._sel(self.docked_steps) > 0).double().mean().item())
+
+    def overlimit_fraction(self):
+        """share of episodes that ended out of bounds (QS_FLAG_OVERLIMIT among their flags)"""
+        from ._lib import FLAG_OVERLIMIT
+        return float(((self._sel(self.flags) & FLAG_OVERLIMIT) != 0).double().mean().item())
+
+    def numpy(self):
+        return {k: getattr(self, k).cpu().numpy() for k in ("returns", "lengths", "flags", "docked_steps", "finished")}
+
+
+def evaluate_policy_episodes(policy, env, episodes_per_env=1, precision="f32", max_steps=None):
+    """`episodes_per_env` complete episodes of ``action = policy.predict(obs, deterministic=True); env.step(action)`` for every
+    env of `env` (a VecDockingEnv: docking-v0 / v1 / v2, any randomise mode, per-env params) in ONE kernel launch
+    (qs_policy_evaluate: exact-f32 actor, or qs_policy_evaluate_fast with precision="bf16x3").  Each env starts from its current
+    state; the auto-reset between episodes is the step API's.  The same episodes, bit for bit, as the loop
+    ``obs -> policy.predict_hip(env, obs, precision) -> env.step`` from the same handle -- which the call leaves untouched (state,
+    parameters, step counter): every evaluation of a handle sees the same starts.  max_steps (default K x 600: the env's
+    time-out bounds every episode) caps the steps per env.  Returns an EvalResult of device tensors, on env's stream."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    K = int(episodes_per_env)          # K < 1 and max_steps < 1 are refused by the library (QuadsimError)
+    max_steps = K * EPISODE_STEPS if max_steps is None else int(max_steps)
+    actor = _actor_of(policy)
+    if precision not in ("f32", "bf16x3"):
+        raise ValueError("precision must be 'f32' or 'bf16x3'")
+    n, dev = env.num_envs, env.device
+    env._use_current_stream()
+    # weight images cached on the actor, as fused_policy_rollout / predict_hip do
+    if precision == "bf16x3" and not hasattr(actor, "_blob"):
+        blob = pack_fast_weights(actor)
+        assert blob.size == env._lib.qs_policy_rollout_fast_blob_bytes()
+        actor._blob = torch.as_tensor(blob.copy()).to(dev)
+    if precision == "f32" and not hasattr(actor, "_wt"):
+        actor._wt = [actor.w0.t().contiguous(), actor.b0.contiguous(), actor.w1.t().contiguous(),
+                     actor.b1.contiguous(), actor.w2.t().contiguous(), actor.b2.contiguous()]
+    kk = max(K, 0)
+    ret = torch.full((kk, n), float("nan"), dtype=torch.float64, device=dev)     # slots of unfinished episodes: NaN / 0
+    length = torch.zeros((kk, n), dtype=torch.int32, device=dev)
+    flags = torch.zeros((kk, n), dtype=torch.uint8, device=dev)
+    docked = torch.zeros((kk, n), dtype=torch.int32, device=dev)
+    finished = torch.empty((n,), dtype=torch.int32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())       # noqa: E731
+    outs = (p(ret), p(length), p(flags), p(docked), p(finished))
+    env._inputs_ready()
+    if precision == "bf16x3":
+        _lib.check(env._lib.qs_policy_evaluate_fast(env._h, K, max_steps, p(actor._blob), *outs), "qs_policy_evaluate_fast")
+    else:
+        _lib.check(env._lib.qs_policy_evaluate(env._h, K, max_steps, *[p(w) for w in actor._wt], *outs), "qs_policy_evaluate")
+    env._outputs_ready()
+    return EvalResult(ret, length, flags, docked, finished)
+
+
+def episodes_for(n_eval_episodes, num_envs):
+    """episodes per env of an evaluation of n_eval_episodes over num_envs envs (every env runs the same number)"""
+    n_eval_episodes, num_envs = int(n_eval_episodes), int(num_envs)
+    if n_eval_episodes < 1 or n_eval_episodes % num_envs:
+        raise ValueError("n_eval_episodes (%d) must be a positive multiple of the env's num_envs (%d): every env runs the same "
+                         "number of episodes" % (n_eval_episodes, num_envs))
+    return n_eval_episodes // num_envs
+
+
+def summarise_episodes(returns, lengths, finished, return_episode_rewards=False):
+    """host side of evaluate_policy on NumPy arrays returns [K,N], lengths [K,N], finished [N]: SB2's result -- (mean, std)
+    of the episode returns (np.mean / np.std), or (episode_rewards, episode_lengths) as lists in (k, env) order"""
+    returns, lengths, finished = np.asarray(returns), np.asarray(lengths), np.asarray(finished)
+    K = returns.shape[0]
+    if np.any(finished < K):
+        raise RuntimeError("%d of %d envs did not finish %d episodes within max_steps" % (int(np.sum(finished < K)), finished.size, K))
+    episode_rewards = [float(r) for r in returns.reshape(-1)]
+    episode_lengths = [int(x) for x in lengths.reshape(-1)]
+    if return_episode_rewards:
+        return episode_rewards, episode_lengths
+    return float(np.mean(episode_rewards)), float(np.std(episode_rewards))
+
+
+def evaluate_policy(model, env, n_eval_episodes=10, deterministic=True, return_episode_rewards=False, precision="f32"):
+    """stable_baselines.common.evaluation.evaluate_policy (run_docking_ppo2.py:8, the EvalCallback of :75-83) on the device:
+    -> (mean_reward, std_reward), or (episode_rewards, episode_lengths) lists with return_episode_rewards=True.
+    Differs from SB2, which runs n_eval_episodes one after another on one env: here every one of env.num_envs envs runs
+    n_eval_episodes / num_envs episodes in one launch (evaluate_policy_episodes), so n_eval_episodes must be a multiple of
+    num_envs (ValueError otherwise); the lists are in (episode k, env) order.  Deterministic actions only."""
+    if not deterministic:
+        raise NotImplementedError("evaluate_policy: only deterministic evaluation runs on the device")
+    K = episodes_for(n_eval_episodes, env.num_envs)
+    res = evaluate_policy_episodes(model, env, K, precision=precision)
+    h = res.numpy()
+    return summarise_episodes(h["returns"], h["lengths"], h["finished"], return_episode_rewards)
