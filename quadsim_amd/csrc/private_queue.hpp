@@ -259,15 +259,13 @@ void chain_close(QsEnv *e)
 int chain_resolve_kernel(QsEnv *e)
 {
     QsChain *c = e->chain;
-    const int integ = e->cfg.integrator == QS_INTEG_FROZEN ? 0 : 1;
-    const int rmode = e->init ? 3 : e->cfg.randomise;
-    const int params = (rmode == 2 || e->per_env_params) ? 1 : 0;
-    static const int forced = getenv("QS_SPLIT") ? atoi(getenv("QS_SPLIT")) : -1;
-    const int split = (forced >= 0 ? forced != 0 : e->n <= kSplitMaxEnvs) ? 1 : 0;
     int64_t lane_tiles = 0;
     for (const QsChainLane &L : c->lanes) lane_tiles = std::max<int64_t>(lane_tiles, L.tile_end - L.tile0);
     if (c->lanes.empty()) lane_tiles = e->tiles;          // chain_open resolves once before the lanes exist: re-resolved at the first step
-    const int prep = split ? prep_for(rmode, lane_tiles) : 0;
+    const StepVariant v = step_variant(e, lane_tiles);
+    const int integ = v.integ, rmode = v.rmode, params = v.params;
+    const int split = v.family == kFamSplit ? 1 : 0;
+    const int prep = split ? v.prep : 0;
     if (c->kernel_object && integ == c->v_integ && rmode == c->v_rmode && params == c->v_params && split == c->v_split && prep == c->v_prep) return QS_OK;
     char sym[160];
     if (split) snprintf(sym, sizeof sym, "_ZN12_GLOBAL__N_111k_env_splitILi%dELb%dELi%dELi%dEEEvNS_8StepArgsE.kd", integ, params, rmode, prep);
@@ -788,19 +786,41 @@ int chain_submit(QsEnv *e, const StepArgs *steps, int64_t T)
 // one step: through the resident kernel where it applies (host-ordered, the role-split kernel, every tile on the chip at once,
 // no placement-guard test armed), else one packet per lane.  (The instantiation cannot change inside a roll-out: every call
 // that changes it drains first.)
-int chain_step(QsEnv *e, const StepArgs &A)
+int chain_resident_fits(QsEnv *e, bool *resident)
 {
     QsChain *c = e->chain;
+    *resident = false;
     if (c->res_enabled && !c->stream_ordered && !c->dbg_shift && !c->res_dbg_packets && !*c->h_err) {
         int r = chain_resolve_kernel(e);
         if (r) return r;
         r = res_resolve_kernel(e);
         if (r) return r;
-        if (c->res_fits) {
-            return res_step(e, A);
-        }
+        *resident = c->res_fits;
     }
+    return QS_OK;
+}
+
+int chain_step(QsEnv *e, const StepArgs &A)
+{
+    bool resident = false;
+    int r = chain_resident_fits(e, &resident);
+    if (r) return r;
+    if (resident) return res_step(e, A);
     return chain_submit(e, &A, 1);
+}
+
+// the instantiation chain_step takes next (qs_debug_step_variant)
+int chain_step_variant(QsEnv *e, StepVariant *v)
+{
+    QsChain *c = e->chain;
+    bool resident = false;
+    int r = chain_resident_fits(e, &resident);
+    if (r) return r;
+    if (!resident && (r = chain_resolve_kernel(e))) return r;
+    v->family = resident ? kFamResident : c->v_split ? kFamChainSplit : kFamChainSerial;
+    v->integ = c->v_integ; v->params = c->v_params; v->rmode = c->v_rmode;
+    v->prep = c->v_split ? c->v_prep : -1;
+    return QS_OK;
 }
 
 }  // namespace

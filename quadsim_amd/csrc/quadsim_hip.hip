@@ -282,19 +282,50 @@ int prep_for(int rmode, int64_t tiles)
     return tiles <= kPrepMaxTiles ? 2 : 0;
 }
 
-template <int INTEG, bool PARAMS, int RMODE>
-void launch_one(hipStream_t s, const StepArgs &A)
+// ---- which step-kernel instantiation a launch of the handle uses ---------------------------------------------------------
+// The one choice behind launch_env_on (HIP stream), chain_resolve_kernel / res_resolve_kernel (private queues),
+// policy_evaluate and qs_debug_step_variant: they all call the helpers below, so that they cannot drift apart.
+enum StepFamily { kFamSerial = 0, kFamSplit = 1, kFamResident = 2, kFamChainSplit = 3, kFamChainSerial = 4, kFamHover = 5 };
+struct StepVariant {
+    int family, integ, params, rmode, prep;    // prep -1: the family has no PREP parameter; rmode -1: k_hover (no RMODE)
+};
+
+// (INTEG, PARAMS, RMODE) of the handle as it is now (qs_set_params / qs_set_init_state change it)
+StepVariant step_combo(const QsEnv *e)
 {
-    // role-split kernel up to kSplitMaxEnvs envs (few waves per SIMD: the two half-length streams of a tile overlap), the
-    // serial kernel above (SIMDs already saturated: the hand-overs only cost).  Both inline the same device functions and
-    // the library is built with -ffp-contract=on, so they compute the same bits.  QS_SPLIT=0/1 forces one (A/B runs).
-    // The choice follows the handle's env count, not the launch's: the groups of a handle are in flight together.
+    StepVariant v{kFamSplit, e->cfg.integrator == QS_INTEG_FROZEN ? 0 : 1, 0, 0, -1};
+    v.rmode = e->init ? 3 : e->cfg.randomise;          // stored initial states take precedence over `randomise`
+    v.params = (v.rmode == 2 || e->per_env_params) ? 1 : 0;    // per-episode params imply per-env params
+    return v;
+}
+
+// role-split kernel up to kSplitMaxEnvs envs (few waves per SIMD: the two half-length streams of a tile overlap), the serial
+// kernel above (SIMDs already saturated: the hand-overs only cost).  Both inline the same device functions and the library is
+// built with -ffp-contract=on, so they compute the same bits.  QS_SPLIT=0/1 forces one (A/B runs).  The choice follows the
+// handle's env count, not the launch's: the groups of a handle are in flight together.
+bool split_for(const QsEnv *e)
+{
     static const int forced = getenv("QS_SPLIT") ? atoi(getenv("QS_SPLIT")) : -1;
-    const bool split = forced >= 0 ? forced != 0 : A.n <= kSplitMaxEnvs;
+    return forced >= 0 ? forced != 0 : e->n <= kSplitMaxEnvs;
+}
+
+// the instantiation a launch of `tiles` tiles of the handle takes (HIP stream; the private queues map it onto their own)
+StepVariant step_variant(const QsEnv *e, int64_t tiles)
+{
+    StepVariant v = step_combo(e);
+    if (e->cfg.kind == QS_KIND_HOVERING_V0) { v.family = kFamHover; v.rmode = -1; return v; }
+    if (split_for(e)) { v.family = kFamSplit; v.prep = prep_for(v.rmode, tiles); }
+    else v.family = kFamSerial;
+    return v;
+}
+
+template <int INTEG, bool PARAMS, int RMODE>
+void launch_one(hipStream_t s, const StepArgs &A, const StepVariant &v)
+{
     const int64_t tiles = A.tile_end - A.tile0;
-    if (split && prep_for(RMODE, tiles) == 2 && (RMODE == 1 || RMODE == 2))
+    if (v.family == kFamSplit && v.prep == 2 && (RMODE == 1 || RMODE == 2))
         hipLaunchKernelGGL((k_env_split<INTEG, PARAMS, RMODE, (RMODE == 1 || RMODE == 2) ? 2 : 0>), dim3((unsigned)tiles), dim3(3 * kTile), 0, s, A);
-    else if (split) hipLaunchKernelGGL((k_env_split<INTEG, PARAMS, RMODE, 0>), dim3((unsigned)tiles), dim3(2 * kTile), 0, s, A);
+    else if (v.family == kFamSplit) hipLaunchKernelGGL((k_env_split<INTEG, PARAMS, RMODE, 0>), dim3((unsigned)tiles), dim3(2 * kTile), 0, s, A);
     else hipLaunchKernelGGL((k_env<INTEG, PARAMS, RMODE>), dim3((unsigned)((tiles + kBlock / kTile - 1) / (kBlock / kTile))), dim3(kBlock), 0, s, A);
 }
 
@@ -315,20 +346,21 @@ QS_RES_KERNELS(1)
 #undef QS_RES_KERNELS
 
 template <int INTEG>
-void launch_integ(hipStream_t s, const StepArgs &A, bool params, int rmode)
+void launch_integ(hipStream_t s, const StepArgs &A, const StepVariant &v)
 {
-    if (rmode == 3) { if (params) launch_one<INTEG, true, 3>(s, A); else launch_one<INTEG, false, 3>(s, A); }
-    else if (rmode == 2) launch_one<INTEG, true, 2>(s, A);      // per-episode params imply per-env params
-    else if (rmode == 1) { if (params) launch_one<INTEG, true, 1>(s, A); else launch_one<INTEG, false, 1>(s, A); }
-    else { if (params) launch_one<INTEG, true, 0>(s, A); else launch_one<INTEG, false, 0>(s, A); }
+    if (v.rmode == 3) { if (v.params) launch_one<INTEG, true, 3>(s, A, v); else launch_one<INTEG, false, 3>(s, A, v); }
+    else if (v.rmode == 2) launch_one<INTEG, true, 2>(s, A, v);      // per-episode params imply per-env params
+    else if (v.rmode == 1) { if (v.params) launch_one<INTEG, true, 1>(s, A, v); else launch_one<INTEG, false, 1>(s, A, v); }
+    else { if (v.params) launch_one<INTEG, true, 0>(s, A, v); else launch_one<INTEG, false, 0>(s, A, v); }
 }
 
 // the env kernels of tiles [A.tile0, A.tile_end) on stream s
 int launch_env_on(QsEnv *e, const StepArgs &A, hipStream_t s)
 {
-    if (e->cfg.kind == QS_KIND_HOVERING_V0) {
+    const StepVariant v = step_variant(e, A.tile_end - A.tile0);
+    if (v.family == kFamHover) {
         const unsigned grid = (unsigned)((A.tile_end - A.tile0 + kBlock / kTile - 1) / (kBlock / kTile));
-        const bool fr = e->cfg.integrator == QS_INTEG_FROZEN, pp = e->per_env_params;
+        const bool fr = v.integ == 0, pp = v.params != 0;
         if (fr && !pp) hipLaunchKernelGGL((k_hover<0, false>), dim3(grid), dim3(kBlock), 0, s, A);
         else if (fr) hipLaunchKernelGGL((k_hover<0, true>), dim3(grid), dim3(kBlock), 0, s, A);
         else if (!pp) hipLaunchKernelGGL((k_hover<1, false>), dim3(grid), dim3(kBlock), 0, s, A);
@@ -336,9 +368,8 @@ int launch_env_on(QsEnv *e, const StepArgs &A, hipStream_t s)
         HIP_TRY(hipGetLastError());
         return QS_OK;
     }
-    const int rmode = e->init ? 3 : e->cfg.randomise;   // stored initial states take precedence over `randomise`
-    if (e->cfg.integrator == QS_INTEG_FROZEN) launch_integ<0>(s, A, e->per_env_params, rmode);
-    else launch_integ<1>(s, A, e->per_env_params, rmode);
+    if (v.integ == 0) launch_integ<0>(s, A, v);
+    else launch_integ<1>(s, A, v);
     HIP_TRY(hipGetLastError());
     return QS_OK;
 }
@@ -1296,9 +1327,9 @@ static int policy_evaluate(QsEnv *e, const char *who, int32_t episodes, int64_t 
     StepArgs A = make_args(e);
     EvalArgs E{ep_return, ep_length, ep_flags, ep_docked, finished, max_steps, episodes};
     const unsigned grid = grid_tiles(e->n);
-    const int rmode = e->init ? 3 : e->cfg.randomise;   // as launch_env_on
-    if (e->cfg.integrator == QS_INTEG_FROZEN) eval_integ<0>(e->stream, grid, A, M, (const uint4 *)blob, E, e->per_env_params, rmode);
-    else eval_integ<1>(e->stream, grid, A, M, (const uint4 *)blob, E, e->per_env_params, rmode);
+    const StepVariant v = step_combo(e);                // as launch_env_on
+    if (v.integ == 0) eval_integ<0>(e->stream, grid, A, M, (const uint4 *)blob, E, v.params != 0, v.rmode);
+    else eval_integ<1>(e->stream, grid, A, M, (const uint4 *)blob, E, v.params != 0, v.rmode);
     HIP_TRY(hipGetLastError());
     return QS_OK;
 }
@@ -1536,6 +1567,23 @@ int qs_debug_chain_resident(QsEnv *e, uint64_t *dispatches)
 {
     if (!e || !dispatches) return fail(QS_ERR_INVALID, "qs_debug_chain_resident: null argument");
     *dispatches = e->chain ? e->chain->res_dispatches : 0;
+    return QS_OK;
+}
+
+// Diagnostic (not in quadsim.h; tests only): the step-kernel instantiation the handle's next qs_step launch takes, as
+// {family, INTEG, PARAMS, RMODE, PREP} -- family 0 k_env, 1 k_env_split, 2 k_env_resident, 3 / 4 k_env_split / k_env as packets
+// of the private queues, 5 k_hover; -1 for a template parameter the family does not have.  Computed by the helpers the launch
+// paths call (step_variant, chain_resident_fits).  HIP-stream mode reports the whole-handle launch: a group launch of fewer
+// tiles (qs_set_groups) may take PREP 2 where this says 0.
+int qs_debug_step_variant(QsEnv *e, int32_t out[5])
+{
+    if (!e || !out) return fail(QS_ERR_INVALID, "qs_debug_step_variant: null argument");
+    DeviceGuard guard(e->cfg.device);
+    if (!guard.ok) return fail(QS_ERR_HIP, "qs_debug_step_variant: hipSetDevice(%d) failed", e->cfg.device);
+    StepVariant v = step_variant(e, e->tiles);
+    if (e->chain) { int rc = chain_step_variant(e, &v); if (rc) return rc; }
+    const int32_t w[5] = {v.family, v.integ, v.params, v.rmode, v.prep};
+    memcpy(out, w, sizeof w);
     return QS_OK;
 }
 

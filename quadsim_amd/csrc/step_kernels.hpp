@@ -466,8 +466,10 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
     __shared__ float s_rst[kPrep ? 29 : 1][kTile];
     __shared__ uint4 s_phx[kPrep ? 1 : 2][kPrep ? 1 : 2][kTile];
     __shared__ unsigned char s_done[kTile], s_limt[kTile];
-    // [step parity] the command of the next step and its term_state pointer, written by the chaser wave before #1 of a step
-    // and read by every wave behind #2 of that step; the next write of the same parity is behind two more #1s
+    // [step parity] the command and the term_state pointer of step t + 1, written by the chaser wave in step t before #1.
+    // The command is read by every wave behind #2 of step t; the next write of that parity is behind two more #1s.  The
+    // pointer is read by the target wave between #1 and #2 of step t + 1: the chaser wave rewrites that parity in step t + 2
+    // before #1, with no barrier between it and #2 of step t + 1, so a read behind #2 could see step t + 3's pointer.
     __shared__ int s_cmd[2];
     __shared__ unsigned long long s_tsp[2];
     const int lane = threadIdx.x & (kTile - 1);
@@ -673,6 +675,7 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
             QS_STAMP_AT(2);
             __syncthreads();                                              // #1
             QS_STAMP_AT(3);
+            float *const term_state = (float *)s_tsp[t & 1];             // before #2 (see s_tsp)
             float u_t[4];
             target_control(A.C.kind, pdes, vdes, qd, 0.0f, pre, dv, P.m, u_t);   // from the state BEFORE stepping
             u_limit(u_t, P.m * kG, ut);
@@ -680,7 +683,6 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
             __syncthreads();                                              // #2
             QS_STAMP_AT(5);
             if (s_done[lane]) {
-                float *const term_state = (float *)s_tsp[t & 1];
                 if (term_state && active) {
                     float *ts = term_state + io * 26 + 13;
 #pragma unroll

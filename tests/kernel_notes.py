@@ -1,0 +1,37 @@
+"""The gfx950 code object of the built library and the kernel metadata in its notes (llvm-readelf --notes), for the CPU tests
+that check the instantiations and resources of the kernels.  A helper module, not a conftest: imported where it is needed."""
+import os
+import re
+import subprocess
+
+import pytest
+
+LLVM = "/opt/rocm/llvm/bin"
+
+
+def code_object(directory):
+    """unbundle the gfx950 code object of the built library into `directory` -> its path (skips without the ROCm LLVM tools)"""
+    from quadsim_amd import _lib
+    for tool in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf", "llvm-objdump"):
+        if not os.path.exists(os.path.join(LLVM, tool)):
+            pytest.skip("ROCm LLVM tools not installed")
+    so = _lib.build_library()
+    d = str(directory)
+    fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "dev.co")
+    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, so, os.path.join(d, "so.copy")])
+    subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
+                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
+    return co
+
+
+def kernel_notes(co):
+    """{mangled kernel name: resource fields} of every kernel in the code object"""
+    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
+    out = {}
+    for block in re.split(r"\n\s+- \.agpr_count", notes):
+        m = re.search(r"\.name:\s+(\S+)", block)
+        if m:
+            field = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", block).group(1))   # noqa: E731
+            out[m.group(1)] = {k: field(k) for k in ("group_segment_fixed_size", "private_segment_fixed_size", "vgpr_count",
+                                                     "vgpr_spill_count", "max_flat_workgroup_size")}
+    return out

@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from step_matrix import NEW_EVAL_ROWS
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -31,9 +33,9 @@ def policies(qa):
     return {k: qa.MlpPolicy.from_sb2_zip(os.path.join(GOLDEN, v)) for k, v in CKPT.items()}
 
 
-def _make(qa, env_id, rnd, n, params=False, seed=5, warm=17):
+def _make(qa, env_id, rnd, n, params=False, seed=5, warm=17, integrator="frozen"):
     """a handle mid-episode: some envs close to the time-out, `warm` random steps taken -> (env, the last observation)"""
-    kw = dict(num_envs=n, randomise=rnd, seed=seed)
+    kw = dict(num_envs=n, randomise=rnd, seed=seed, integrator=integrator)
     if rnd:
         kw.update(init_range=qa.C3_INIT_RANGE, mass_scale=(0.8, 1.2), inertia_scale=(0.8, 1.2))
     env = qa.VecDockingEnv(env_id, **kw)
@@ -112,6 +114,26 @@ def test_evaluate_equals_per_step_loop(qa, torch, policies, env_id, rnd, params,
     ref = _episodes(*_loop(torch, env, pol, obs, precision, K * 600), K)
     _assert_equal_episodes(res, ref)
     assert (ref[4] == K).all()                        # every episode ends by the env's time-out within K x 600 steps
+    env.close()
+
+
+@pytest.mark.parametrize("row", NEW_EVAL_ROWS, ids=[r["id"] for r in NEW_EVAL_ROWS])
+def test_evaluate_matrix_equals_per_step_loop(qa, torch, policies, row):
+    """the (INTEG, PARAMS, RMODE) instantiations of both evaluation kernels the cases above do not reach (every rk4 one; per-env
+    params with RMODE 0 and 3), K = 1, against the per-step loop through the step kernels (which tests/test_gpu_step_matrix.py
+    pins to the oracle)"""
+    K = 1
+    env, obs = _make(qa, row["env_id"], row["randomise"], row["n"], row["set_params"], integrator=row["integ"])
+    lib = env._lib
+    lib.qs_debug_step_variant.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    v = (C.c_int32 * 5)()
+    assert lib.qs_debug_step_variant(env._h, v) == 0
+    assert tuple(v)[1:4] == row["combo"]                   # the evaluation kernel takes the step kernel's (INTEG, PARAMS, RMODE)
+    pol = policies[row["ckpt"]]
+    res = qa.evaluate_policy_episodes(pol, env, K, precision=row["precision"])
+    ref = _episodes(*_loop(torch, env, pol, obs, row["precision"], K * 600), K)
+    _assert_equal_episodes(res, ref)
+    assert (ref[4] == K).all()
     env.close()
 
 

@@ -9,8 +9,10 @@ import types
 import numpy as np
 import pytest
 
+import kernel_notes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/llvm/bin"
+LLVM = kernel_notes.LLVM
 
 # the (INTEG, PARAMS, RMODE) combinations launch_integ dispatches for the step kernels
 COMBOS = [(i, p, r) for i in (0, 1) for (p, r) in ((0, 0), (1, 0), (0, 1), (1, 1), (1, 2), (0, 3), (1, 3))]
@@ -60,29 +62,10 @@ def test_evaluate_abi_symbols_and_plain_c(tmp_path):
 # ---------------------------------------------------------------- ISA
 @pytest.fixture(scope="module")
 def code_object(tmp_path_factory):
-    from quadsim_amd import _lib
-    for tool in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf", "llvm-objdump"):
-        if not os.path.exists(os.path.join(LLVM, tool)):
-            pytest.skip("ROCm LLVM tools not installed")
-    so = _lib.build_library()
-    d = tmp_path_factory.mktemp("isa_eval")
-    fat, co = str(d / "fat.bin"), str(d / "dev.co")
-    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, so, str(d / "so.copy")])
-    subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
-                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-    return co
+    return kernel_notes.code_object(tmp_path_factory.mktemp("isa_eval"))
 
 
-def _kernel_notes(co):
-    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
-    out = {}
-    for block in re.split(r"\n\s+- \.agpr_count", notes):
-        m = re.search(r"\.name:\s+(\S+)", block)
-        if m:
-            field = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", block).group(1))   # noqa: E731
-            out[m.group(1)] = {k: field(k) for k in ("group_segment_fixed_size", "private_segment_fixed_size", "vgpr_count",
-                                                     "vgpr_spill_count", "max_flat_workgroup_size")}
-    return out
+_kernel_notes = kernel_notes.kernel_notes
 
 
 def _eval_kernels(notes):
