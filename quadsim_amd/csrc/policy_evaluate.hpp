@@ -67,8 +67,7 @@ __device__ __forceinline__ void eval_episodes(const StepArgs &A, const EvalArgs 
     const int64_t env = tile * kTile + lane;
     const bool active = env < A.n;             // MFMA needs the whole wave: idle lanes carry a nominal env, record nothing
     Env e;
-    if (active) load_env(A.st, tile, lane, e);
-    else { nominal_init(e.sc, e.st); for (int i = 0; i < 4; ++i) { e.uc[i] = 0.0f; e.ut[i] = 0.0f; e.qd[i] = i == 0; } e.ls = 0.0f; e.t = 0.0f; }
+    load_env_or_nominal(A, tile, lane, active, e);
     // PARAMS: idle lanes read tile 0's parameters (they record nothing); a Par picked from A.par_nom or the loaded one by
     // `active` lived in a stack object in the RMODE 2 kernels
     Par P = A.par_nom;
@@ -139,22 +138,12 @@ __global__ __launch_bounds__(kBlock, 1) void k_policy_evaluate_fast(StepArgs A, 
     });
 }
 
-// one launch; (PARAMS, RMODE) as launch_integ picks them for the step kernels, and no other combination is instantiated
+// one launch; called through with_combo (quadsim_hip.hip), so for the step kernels' combinations and no other
 template <int INTEG, bool PARAMS, int RMODE>
 void eval_launch(hipStream_t s, unsigned grid, const StepArgs &A, const MlpArgs *M, const uint4 *blob, const EvalArgs &E)
 {
     if (blob) hipLaunchKernelGGL((k_policy_evaluate_fast<INTEG, PARAMS, RMODE>), dim3(grid), dim3(kBlock), 0, s, A, blob, E);
     else hipLaunchKernelGGL((k_policy_evaluate<INTEG, PARAMS, RMODE>), dim3(grid), dim3(kBlock), 0, s, A, *M, E);
-}
-
-template <int INTEG>
-void eval_integ(hipStream_t s, unsigned grid, const StepArgs &A, const MlpArgs *M, const uint4 *blob, const EvalArgs &E,
-                bool params, int rmode)
-{
-    if (rmode == 3) { if (params) eval_launch<INTEG, true, 3>(s, grid, A, M, blob, E); else eval_launch<INTEG, false, 3>(s, grid, A, M, blob, E); }
-    else if (rmode == 2) eval_launch<INTEG, true, 2>(s, grid, A, M, blob, E);
-    else if (rmode == 1) { if (params) eval_launch<INTEG, true, 1>(s, grid, A, M, blob, E); else eval_launch<INTEG, false, 1>(s, grid, A, M, blob, E); }
-    else { if (params) eval_launch<INTEG, true, 0>(s, grid, A, M, blob, E); else eval_launch<INTEG, false, 0>(s, grid, A, M, blob, E); }
 }
 
 }  // namespace

@@ -299,6 +299,24 @@ StepVariant step_combo(const QsEnv *e)
     return v;
 }
 
+// ... and the one mapping of that combination onto template arguments: f.operator()<INTEG, PARAMS, RMODE>() for the combinations
+// the step kernels exist in (per-episode params imply per-env params: RMODE 2 only with PARAMS), which every kernel family that
+// takes these parameters is instantiated through, guarding with `if constexpr` what it does not support
+template <int INTEG, class F>
+void with_combo_integ(const StepVariant &v, F &&f)
+{
+    if (v.rmode == 3) { if (v.params) f.template operator()<INTEG, true, 3>(); else f.template operator()<INTEG, false, 3>(); }
+    else if (v.rmode == 2) f.template operator()<INTEG, true, 2>();
+    else if (v.rmode == 1) { if (v.params) f.template operator()<INTEG, true, 1>(); else f.template operator()<INTEG, false, 1>(); }
+    else { if (v.params) f.template operator()<INTEG, true, 0>(); else f.template operator()<INTEG, false, 0>(); }
+}
+template <class F>
+void with_combo(const StepVariant &v, F &&f)
+{
+    if (v.integ == 0) with_combo_integ<0>(v, f);
+    else with_combo_integ<1>(v, f);
+}
+
 // role-split kernel up to kSplitMaxEnvs envs (few waves per SIMD: the two half-length streams of a tile overlap), the serial
 // kernel above (SIMDs already saturated: the hand-overs only cost).  Both inline the same device functions and the library is
 // built with -ffp-contract=on, so they compute the same bits.  QS_SPLIT=0/1 forces one (A/B runs).  The choice follows the
@@ -345,15 +363,6 @@ QS_RES_KERNELS(0)
 QS_RES_KERNELS(1)
 #undef QS_RES_KERNELS
 
-template <int INTEG>
-void launch_integ(hipStream_t s, const StepArgs &A, const StepVariant &v)
-{
-    if (v.rmode == 3) { if (v.params) launch_one<INTEG, true, 3>(s, A, v); else launch_one<INTEG, false, 3>(s, A, v); }
-    else if (v.rmode == 2) launch_one<INTEG, true, 2>(s, A, v);      // per-episode params imply per-env params
-    else if (v.rmode == 1) { if (v.params) launch_one<INTEG, true, 1>(s, A, v); else launch_one<INTEG, false, 1>(s, A, v); }
-    else { if (v.params) launch_one<INTEG, true, 0>(s, A, v); else launch_one<INTEG, false, 0>(s, A, v); }
-}
-
 // the env kernels of tiles [A.tile0, A.tile_end) on stream s
 int launch_env_on(QsEnv *e, const StepArgs &A, hipStream_t s)
 {
@@ -368,8 +377,7 @@ int launch_env_on(QsEnv *e, const StepArgs &A, hipStream_t s)
         HIP_TRY(hipGetLastError());
         return QS_OK;
     }
-    if (v.integ == 0) launch_integ<0>(s, A, v);
-    else launch_integ<1>(s, A, v);
+    with_combo(v, [&]<int INTEG, bool PARAMS, int RMODE>() { launch_one<INTEG, PARAMS, RMODE>(s, A, v); });
     HIP_TRY(hipGetLastError());
     return QS_OK;
 }
@@ -1246,12 +1254,9 @@ int qs_policy_rollout(QsEnv *e, int64_t T, const float *wt1, const float *b1, co
     A.T = T; A.obs = obs; A.reward = reward; A.done = done; A.flags = flags;
     MlpArgs M{wt1, b1, wt2, b2, wt3, b3};
     const unsigned grid = grid_tiles(e->n);
-    const bool fr = e->cfg.integrator == QS_INTEG_FROZEN;
-    const int rm = e->cfg.randomise;
-    if (fr && rm == 0) hipLaunchKernelGGL((k_policy_rollout<0, 0>), dim3(grid), dim3(kBlock), 0, e->stream, A, M, actions);
-    else if (fr) hipLaunchKernelGGL((k_policy_rollout<0, 1>), dim3(grid), dim3(kBlock), 0, e->stream, A, M, actions);
-    else if (rm == 0) hipLaunchKernelGGL((k_policy_rollout<1, 0>), dim3(grid), dim3(kBlock), 0, e->stream, A, M, actions);
-    else hipLaunchKernelGGL((k_policy_rollout<1, 1>), dim3(grid), dim3(kBlock), 0, e->stream, A, M, actions);
+    with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {     // the checks above leave RMODE 0 / 1 without PARAMS
+        if constexpr (!PARAMS && RMODE < 2) hipLaunchKernelGGL((k_policy_rollout<INTEG, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, M, actions);
+    });
     HIP_TRY(hipGetLastError());
     return QS_OK;
 }
@@ -1299,12 +1304,9 @@ int qs_policy_rollout_fast(QsEnv *e, int64_t T, const void *packed_weights, floa
     A.T = T; A.obs = obs; A.reward = reward; A.done = done; A.flags = flags;
     const uint4 *blob = (const uint4 *)packed_weights;
     const unsigned grid = grid_tiles(e->n);
-    const bool fr = e->cfg.integrator == QS_INTEG_FROZEN;
-    const int rm = e->cfg.randomise;
-    if (fr && rm == 0) hipLaunchKernelGGL((k_policy_rollout_fast<0, 0>), dim3(grid), dim3(kBlock), 0, e->stream, A, blob, actions);
-    else if (fr) hipLaunchKernelGGL((k_policy_rollout_fast<0, 1>), dim3(grid), dim3(kBlock), 0, e->stream, A, blob, actions);
-    else if (rm == 0) hipLaunchKernelGGL((k_policy_rollout_fast<1, 0>), dim3(grid), dim3(kBlock), 0, e->stream, A, blob, actions);
-    else hipLaunchKernelGGL((k_policy_rollout_fast<1, 1>), dim3(grid), dim3(kBlock), 0, e->stream, A, blob, actions);
+    with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {     // the checks above leave RMODE 0 / 1 without PARAMS
+        if constexpr (!PARAMS && RMODE < 2) hipLaunchKernelGGL((k_policy_rollout_fast<INTEG, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, blob, actions);
+    });
     HIP_TRY(hipGetLastError());
     return QS_OK;
 }
@@ -1327,9 +1329,9 @@ static int policy_evaluate(QsEnv *e, const char *who, int32_t episodes, int64_t 
     StepArgs A = make_args(e);
     EvalArgs E{ep_return, ep_length, ep_flags, ep_docked, finished, max_steps, episodes};
     const unsigned grid = grid_tiles(e->n);
-    const StepVariant v = step_combo(e);                // as launch_env_on
-    if (v.integ == 0) eval_integ<0>(e->stream, grid, A, M, (const uint4 *)blob, E, v.params != 0, v.rmode);
-    else eval_integ<1>(e->stream, grid, A, M, (const uint4 *)blob, E, v.params != 0, v.rmode);
+    with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {     // as launch_env_on
+        eval_launch<INTEG, PARAMS, RMODE>(e->stream, grid, A, M, (const uint4 *)blob, E);
+    });
     HIP_TRY(hipGetLastError());
     return QS_OK;
 }
@@ -1408,42 +1410,20 @@ static int runner_launch(QsEnv *e, const char *who, int64_t T, const float logst
 extern "C++" template <int NET>
 static void runner_dispatch(QsEnv *e, const StepArgs &A, const RunnerArgs &R, bool fast)
 {
-    const void *blob = fast ? R.blob : nullptr;
     const unsigned grid = grid_tiles(e->n);
-    const bool fr = e->cfg.integrator == QS_INTEG_FROZEN;
-    const int rm = e->cfg.randomise;
-    const bool params = e->per_env_params || rm == 2;
-#define QS_RUNNER_GO(I, RM, PA, FAST) hipLaunchKernelGGL((k_runner_rollout<I, RM, PA, FAST, NET>), dim3(grid), dim3(kBlock), 0, e->stream, A, R)
-#define QS_RUNNER_INTEG(I, FAST)                                  \
-    do {                                                          \
-        if (rm == 2) QS_RUNNER_GO(I, 2, true, FAST);              \
-        else if (rm == 1 && params) QS_RUNNER_GO(I, 1, true, FAST);  \
-        else if (rm == 1) QS_RUNNER_GO(I, 1, false, FAST);        \
-        else if (params) QS_RUNNER_GO(I, 0, true, FAST);          \
-        else QS_RUNNER_GO(I, 0, false, FAST);                     \
-    } while (0)
     // the role-split kernel (matrix waves + env waves); QUADSIM_RUNNER_SERIAL=1 keeps the one-wave-per-tile kernel for A/B
     // runs (same results bit for bit: the same instruction sequences on the same operands)
-    const bool serial_fast = runner_serial_flag().load(std::memory_order_relaxed) != 0;
-#define QS_RUNNER_SPLIT_GO(I, RM, PA, FAST) hipLaunchKernelGGL((k_runner_split<I, RM, PA, FAST, NET>), dim3(grid), dim3(2 * kBlock), 0, e->stream, A, R)
-#define QS_RUNNER_SPLIT(I, FAST)                                        \
-    do {                                                                \
-        if (rm == 2) QS_RUNNER_SPLIT_GO(I, 2, true, FAST);              \
-        else if (rm == 1 && params) QS_RUNNER_SPLIT_GO(I, 1, true, FAST);  \
-        else if (rm == 1) QS_RUNNER_SPLIT_GO(I, 1, false, FAST);        \
-        else if (params) QS_RUNNER_SPLIT_GO(I, 0, true, FAST);          \
-        else QS_RUNNER_SPLIT_GO(I, 0, false, FAST);                     \
-    } while (0)
-    if (!serial_fast) {
-        if (blob) { if (fr) QS_RUNNER_SPLIT(0, true); else QS_RUNNER_SPLIT(1, true); }
-        else { if (fr) QS_RUNNER_SPLIT(0, false); else QS_RUNNER_SPLIT(1, false); }
-    }
-    else if (blob) { if (fr) QS_RUNNER_INTEG(0, true); else QS_RUNNER_INTEG(1, true); }
-    else { if (fr) QS_RUNNER_INTEG(0, false); else QS_RUNNER_INTEG(1, false); }
-#undef QS_RUNNER_SPLIT
-#undef QS_RUNNER_SPLIT_GO
-#undef QS_RUNNER_INTEG
-#undef QS_RUNNER_GO
+    const bool serial = runner_serial_flag().load(std::memory_order_relaxed) != 0;
+    with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {
+        if constexpr (RMODE != 3) {           // runner_launch rejects stored initial states
+            auto go = [&]<bool FAST>() {
+                if (serial) hipLaunchKernelGGL((k_runner_rollout<INTEG, RMODE, PARAMS, FAST, NET>), dim3(grid), dim3(kBlock), 0, e->stream, A, R);
+                else hipLaunchKernelGGL((k_runner_split<INTEG, RMODE, PARAMS, FAST, NET>), dim3(grid), dim3(2 * kBlock), 0, e->stream, A, R);
+            };
+            if (fast) go.template operator()<true>();
+            else go.template operator()<false>();
+        }
+    });
 }
 
 int qs_runner_rollout(QsEnv *e, int64_t T, const QsActorCritic *pol, const float *noise, const uint8_t *dones_in,

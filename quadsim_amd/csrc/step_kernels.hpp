@@ -84,6 +84,13 @@ __device__ __forceinline__ void load_env(const float *__restrict__ st, int64_t t
     e.t = b[F_T * kTile];
 }
 
+// a wave that needs all 64 lanes (MFMA) on a tail tile: its idle lanes carry a nominal env and store nothing
+__device__ __forceinline__ void load_env_or_nominal(const StepArgs &A, int64_t tile, int lane, bool active, Env &e)
+{
+    if (active) load_env(A.st, tile, lane, e);
+    else { nominal_init(e.sc, e.st); for (int i = 0; i < 4; ++i) { e.uc[i] = 0.0f; e.ut[i] = 0.0f; e.qd[i] = i == 0; } e.ls = 0.0f; e.t = 0.0f; }
+}
+
 __device__ __forceinline__ void store_env(float *__restrict__ st, int64_t tile, int lane, const Env &e)
 {
     float *b = st + tile * (int64_t)(kRecWords * kTile) + lane;
@@ -332,10 +339,214 @@ __global__ __launch_bounds__(kBlock) void k_env(StepArgs A)
 // waves per workgroup of k_env_split: with PREP == 2 the rocRAND reset modes get a third wave
 constexpr int split_waves(int rmode, int prep) { return (prep == 2 && (rmode == 1 || rmode == 2)) ? 3 : 2; }
 
+// ---- the step body shared by k_env_split and k_env_resident ----------------------------------------------------------------
+// Everything a role wave computes in a step is one of the functions below; the two kernels differ in what surrounds them (loop
+// control, where a step's I/O pointers come from, the placement guard, s_setprio) and own every workgroup barrier: none of
+// these functions contains one.
+
+// LDS of a workgroup; an array that the instantiation does not use has no rows, so that it takes no LDS.
+// rst (third wave): [chaser reset state 13 | its observation 12 | per-episode params 4][lane]: what a reset of THIS step would
+// install, prepared every step off the chaser wave's critical path.  One buffer suffices in a roll-out too: it is written
+// between barriers #1 and #2 of a step and read behind #2; the next write is behind the NEXT step's #1, which the readers have
+// passed.  phx (rocRAND reset modes without the third wave): [step parity][block]: the chaser wave reads step t's Philox words
+// while t+1's are drawn.
+constexpr bool split_prep(int rmode, int prep) { return split_waves(rmode, prep) == 3; }
+constexpr bool split_draw(int rmode, int prep) { return (rmode == 1 || rmode == 2) && !split_prep(rmode, prep); }
+template <int RMODE, int PREP>
+struct SplitLds {
+    float tgt[13][kTile];
+    float rst[split_prep(RMODE, PREP) ? 29 : 0][kTile];
+    uint4 phx[split_draw(RMODE, PREP) ? 2 : 0][2][kTile];
+    unsigned char done[kTile], limt[kTile];
+    __device__ __forceinline__ Par reset_par(int lane) const { return Par{rst[25][lane], rst[26][lane], rst[27][lane], rst[28][lane]}; }
+};
+
+__device__ __forceinline__ void chaser_load(const float *b, float sc[13], float uc[4], float &ls, float &tt)
+{
+#pragma unroll
+    for (int i = 0; i < 13; ++i) sc[i] = b[(F_SC + i) * kTile];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) uc[i] = b[(F_UC + i) * kTile];
+    ls = b[F_LS * kTile];
+    tt = b[F_T * kTile];
+}
+
+__device__ __forceinline__ void chaser_store(float *bw, const float sc[13], const float uc[4], float ls, float tt)
+{
+#pragma unroll
+    for (int i = 0; i < 13; ++i) QS_ST(&bw[(F_SC + i) * kTile], sc[i]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) QS_ST(&bw[(F_UC + i) * kTile], uc[i]);
+    QS_ST(&bw[F_LS * kTile], ls);
+    QS_ST(&bw[F_T * kTile], tt);
+}
+
+// chaser wave between #1 and #2: state2rel against the target's new state, reward, flags; -> this lane resets (also into LDS)
+template <int RMODE, int PREP>
+__device__ __forceinline__ bool chaser_score(SplitLds<RMODE, PREP> &L, int lane, const float sc[13], const float a[4], float tt, float &ls,
+                                             const EnvConst &C, int auto_reset, bool lim_c, float obs[12], float &reward,
+                                             unsigned &flags, bool &done)
+{
+    float st[13];
+#pragma unroll
+    for (int i = 0; i < 13; ++i) st[i] = L.tgt[i][lane];
+    const bool lim_t = L.limt[lane] != 0;
+    rel_obs(sc, st, obs);
+    score_step(obs, a, sc[2], tt, ls, C, lim_c, lim_t, reward, flags);
+    done = (flags & (FLAG_OVERLIMIT | FLAG_OVERTIME)) != 0;
+    const bool rs = done && auto_reset;
+    L.done[lane] = rs ? 1 : 0;
+    return rs;
+}
+
+// one drone's half (0 chaser, 1 target) of a terminal-state row
+__device__ __forceinline__ void store_term_half(float *term_state, bool active, int64_t io, int half, const float s[13])
+{
+    if (term_state && active) {
+        float *ts = term_state + io * 26 + 13 * half;
+#pragma unroll
+        for (int i = 0; i < 13; ++i) ts[i] = s[i];
+    }
+}
+
+// the chaser's half of an auto-reset, behind #2: new state, its observation, the episode's parameters
+template <bool PARAMS, int RMODE, int PREP>
+__device__ __forceinline__ void chaser_reset(const SplitLds<RMODE, PREP> &L, const StepArgs &A, int64_t env, bool active, int lane, int64_t t,
+                                             float sc[13], float uc[4], float &ls, float &tt, Par &P, float obs[12])
+{
+    float ic[13], it[13];
+    if (RMODE == 0) {
+        nominal_init(ic, it);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) obs[i] = A.nominal_obs[i];
+    } else if (RMODE == 3) {
+        const float *src = A.init + (active ? env : 0) * 26;
+#pragma unroll
+        for (int i = 0; i < 13; ++i) { ic[i] = src[i]; it[i] = src[13 + i]; }
+        rel_obs<false>(ic, it, obs);
+    } else {
+        if constexpr (split_prep(RMODE, PREP)) {
+            // the reset state, its observation and the episode's parameters were prepared by the third wave: a copy
+#pragma unroll
+            for (int i = 0; i < 13; ++i) ic[i] = L.rst[i][lane];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) obs[i] = L.rst[13 + i][lane];
+            if (PARAMS && RMODE == 2) P = L.reset_par(lane);
+        } else {
+            const uint4 w0 = L.phx[t & 1][0][lane], w1 = RMODE == 2 ? L.phx[t & 1][1][lane] : make_uint4(0, 0, 0, 0);
+            Par Pn;
+            random_init_apply<RMODE == 2>(A.rc, w0, w1, ic, it, Pn);
+            if (PARAMS && RMODE == 2) P = Pn;
+            rel_obs<true>(ic, it, obs);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 13; ++i) sc[i] = ic[i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) uc[i] = 0.0f;
+    ls = 0.0f;
+    tt = 0.0f;
+}
+
+__device__ __forceinline__ void target_load(const float *b, float st[13], float ut[4], float qd[4])
+{
+#pragma unroll
+    for (int i = 0; i < 13; ++i) st[i] = b[(F_ST + i) * kTile];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ut[i] = b[(F_UT + i) * kTile];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) qd[i] = b[(F_QD + i) * kTile];
+}
+
+__device__ __forceinline__ void target_store(float *bw, const float st[13], const float ut[4], const float qd[4])
+{
+#pragma unroll
+    for (int i = 0; i < 13; ++i) QS_ST(&bw[(F_ST + i) * kTile], st[i]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) QS_ST(&bw[(F_UT + i) * kTile], ut[i]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) QS_ST(&bw[(F_QD + i) * kTile], qd[i]);
+}
+
+// target wave before #1: the advanced target -> LDS; without the third wave also the Philox words a reset of this step consumes
+template <int RMODE, int PREP>
+__device__ __forceinline__ void target_publish(SplitLds<RMODE, PREP> &L, const StepArgs &A, int64_t env, int lane, uint64_t k, int64_t t,
+                                               const float st[13], bool lim_t, uint4 &w0, uint4 &w1)
+{
+#pragma unroll
+    for (int i = 0; i < 13; ++i) L.tgt[i][lane] = st[i];
+    L.limt[lane] = lim_t ? 1 : 0;
+    w0 = make_uint4(0, 0, 0, 0);
+    w1 = w0;
+    if constexpr (split_draw(RMODE, PREP)) {
+        random_init_words<RMODE == 2>(A.rc, STREAM_AUTORESET, A.gid0 + (uint64_t)env, k + 1, w0, w1);
+        L.phx[t & 1][0][lane] = w0;
+        if (RMODE == 2) L.phx[t & 1][1][lane] = w1;     // the params block: only drawn with per-episode params
+    }
+}
+
+// target wave between #1 and #2: the PID from the state BEFORE stepping, and the new limited control
+__device__ __forceinline__ void target_command(const EnvConst &C, float qd[4], const float pre[13], float m, float ut[4])
+{
+    const float pdes[3] = {10.0f, -50.0f, 5.0f};              // docking_env.py:60
+    const float vdes[3] = {C.vdes_x, 0.0f, 0.0f};
+    const float dv[3] = {0.0f, 0.0f, 0.0f};
+    float u_t[4];
+    target_control(C.kind, pdes, vdes, qd, 0.0f, pre, dv, m, u_t);
+    u_limit(u_t, m * kG, ut);
+}
+
+// the target's half of an auto-reset, behind #2 (w0, w1: this step's words from target_publish)
+template <bool PARAMS, int RMODE, int PREP>
+__device__ __forceinline__ void target_reset(const SplitLds<RMODE, PREP> &L, const StepArgs &A, int64_t env, bool active, int lane,
+                                             const uint4 &w0, const uint4 &w1, float st[13], float ut[4], Par &P)
+{
+    float ic[13], it[13];
+    if (RMODE == 3) {
+        const float *src = A.init + (active ? env : 0) * 26;
+#pragma unroll
+        for (int i = 0; i < 13; ++i) it[i] = src[13 + i];
+    } else {
+        nominal_init(ic, it);
+        if (PARAMS && RMODE == 2) {
+            if constexpr (split_prep(RMODE, PREP)) {
+                P = L.reset_par(lane);
+            } else {
+                random_init_apply<true>(A.rc, w0, w1, ic, it, P);
+                nominal_init(ic, it);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 13; ++i) st[i] = it[i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ut[i] = 0.0f;
+}
+
+// third wave (rocRAND reset modes with PREP == 2 only) between #1 and #2: what a reset of this step would install --
+// random_init_apply on the words it drew before #1 and the state2rel of the result: the same device functions the serial kernel
+// runs inside its reset branch, so the same bits -- for EVERY lane, into LDS.  The wave touches no global memory but the step
+// counter and joins both barriers of every step; the chaser wave's reset branch is a 25-word copy, the target wave draws nothing.
+template <bool PARAMS, int RMODE, int PREP>
+__device__ __forceinline__ void prep_publish(SplitLds<RMODE, PREP> &L, const RandCfg &rc, int lane, const uint4 &w0, const uint4 &w1)
+{
+    float ic[13], it_[13], robs[12];
+    Par Pn;
+    random_init_apply<RMODE == 2>(rc, w0, w1, ic, it_, Pn);
+    rel_obs<true>(ic, it_, robs);
+#pragma unroll
+    for (int i = 0; i < 13; ++i) L.rst[i][lane] = ic[i];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) L.rst[13 + i][lane] = robs[i];
+    if (PARAMS && RMODE == 2) {
+        L.rst[25][lane] = Pn.m; L.rst[26][lane] = Pn.Ixx; L.rst[27][lane] = Pn.Iyy; L.rst[28][lane] = Pn.Izz;
+    }
+}
+
 // ---- resident form of k_env_split (host-ordered private queues; private_queue.hpp, "resident roll-out") -------------------
 // One dispatch per private queue steps its tiles for as many steps as the host issues.  Before each step the chaser wave takes
 // that step's I/O pointers from a descriptor ring the host writes ahead of the GPU; the state stays in registers from one step
-// to the next and is stored once, when the tile leaves.  A step computes exactly what k_env_split computes (same body below).
+// to the next and is stored once, when the tile leaves.  A step is k_env_split's: the same calls of the shared step body above.
 //
 // A descriptor is 8 naturally aligned 64-bit words (one 64-B slot): actions | obs | reward | done | flags | term_obs |
 // term_state | command.  EVERY word carries the low 16 bits of the step's sequence number (the tag) in bits 48..63, beside a
@@ -449,23 +660,14 @@ __device__ __forceinline__ void res_report_done(const ResArgs &R, unsigned old, 
     __hip_atomic_store(R.h_prog, R.base + x - kResWin + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// k_env_split's body, stepping from the descriptor ring until an EXIT descriptor or the idle limit: the same device functions in
-// the same order, phase for phase (k_env_split itself is left as it is: its machine code, and with it the packet chain's and the
-// HIP stream's timing, does not change).  Differences: barrier #0 before the first step, the next descriptor requested at the
-// top of a step and resolved where k_env_split requests the next action, the per-step pointers of descriptor D, the state
-// stored once when the tile leaves.
+// k_env_split's step, taken from the descriptor ring until an EXIT descriptor or the idle limit.  What differs from k_env_split:
+// barrier #0 before the first step; the next descriptor is requested at the top of a step and resolved where k_env_split
+// requests the next action; a step's I/O pointers are those of its descriptor D; no placement guard and no slab; the chaser
+// wave keeps its priority for the whole dispatch; the state is stored once, when the tile leaves.
 template <int INTEG, bool PARAMS, int RMODE, int PREP>
 __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs R)
 {
-    __shared__ float s_tgt[13][kTile];
-    // PREP == 2: [chaser reset state 13 | its observation 12 | per-episode params 4][lane]: what a reset of THIS step would
-    // install, prepared every step off the chaser wave's critical path.  One buffer suffices in a roll-out too: it is written
-    // between barriers #1 and #2 of a step and read behind #2; the next write is behind the NEXT step's #1, which the readers
-    // have passed.  PREP == 0: [step parity][block]: the chaser wave reads step t's Philox words while t+1's are drawn.
-    constexpr bool kPrep = PREP == 2 && (RMODE == 1 || RMODE == 2);
-    __shared__ float s_rst[kPrep ? 29 : 1][kTile];
-    __shared__ uint4 s_phx[kPrep ? 1 : 2][kPrep ? 1 : 2][kTile];
-    __shared__ unsigned char s_done[kTile], s_limt[kTile];
+    __shared__ SplitLds<RMODE, PREP> L;
     // [step parity] the command and the term_state pointer of step t + 1, written by the chaser wave in step t before #1.
     // The command is read by every wave behind #2 of step t; the next write of that parity is behind two more #1s.  The
     // pointer is read by the target wave between #1 and #2 of step t + 1: the chaser wave rewrites that parity in step t + 2
@@ -503,18 +705,10 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
     Par P = A.par_nom;
     if (PARAMS) P = load_par(A.par, tile, lane);
     if (role == 0) {
-        // in a roll-out the chaser wave is the long pole of every step while target waves on the same SIMD run ahead with
-        // speculative draws: give it the issue slots first (roll-out 2.28 -> 2.13 us/step; no help for a single step)
-        __builtin_amdgcn_s_setprio(3);
-        float sc[13], uc[4];
-#pragma unroll
-        for (int i = 0; i < 13; ++i) sc[i] = b[(F_SC + i) * kTile];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) uc[i] = b[(F_UC + i) * kTile];
-        float ls = b[F_LS * kTile], tt = b[F_T * kTile];
-        // the action is requested LAST: loads return in issue order, and the action -- fresh from the caller, the one
-        // operand that is not cache-resident -- is not needed before the integration (which uses the PREVIOUS limited
-        // control, quadrotor.py:126-144) is done; its miss latency hides under drone_advance
+        __builtin_amdgcn_s_setprio(3);           // as k_env_split in a roll-out
+        float sc[13], uc[4], ls, tt;
+        chaser_load(b, sc, uc, ls, tt);
+        // the action is requested LAST, as in k_env_split
         float4 av_next = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (cmd == RES_STEP && active) av_next = res_action(D.actions, io, A.io_n);
 #if defined(QS_STAMP) && QS_STAMP + 0 < 2
@@ -524,7 +718,6 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
         int64_t t = 0;
 #pragma clang loop unroll(disable)
         for (; cmd == RES_STEP; ++t) {
-            const uint64_t k = k0 + (uint64_t)t;
             const int64_t o = io;
             const unsigned long long wn = res_request(R, seq + t + 1, lane);   // the next descriptor, a step ahead of its use
             tt += 1.0f;
@@ -546,59 +739,17 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
             QS_STAMP_AT(2);
             __syncthreads();                                              // #1: the target's new state is in LDS
             QS_STAMP_AT(3);
-            float st[13];
-#pragma unroll
-            for (int i = 0; i < 13; ++i) st[i] = s_tgt[i][lane];
-            const bool lim_t = s_limt[lane] != 0;
             float obs[12], reward;
             unsigned flags;
-            rel_obs(sc, st, obs);
-            score_step(obs, a, sc[2], tt, ls, A.C, lim_c, lim_t, reward, flags);
-            const bool done = (flags & (FLAG_OVERLIMIT | FLAG_OVERTIME)) != 0;
-            const bool rs = done && A.auto_reset;
-            s_done[lane] = rs ? 1 : 0;
+            bool done;
+            const bool rs = chaser_score(L, lane, sc, a, tt, ls, A.C, A.auto_reset, lim_c, obs, reward, flags, done);
             QS_STAMP_AT(4);
             __syncthreads();                                              // #2: reset flags out, this step's Philox words in
             QS_STAMP_AT(5);
             if (rs) {
                 if (D.term_obs && active) store_obs(D.term_obs, io, obs);
-                if (D.term_state && active) {
-                    float *ts = D.term_state + io * 26;
-#pragma unroll
-                    for (int i = 0; i < 13; ++i) ts[i] = sc[i];
-                }
-                float ic[13], it[13];
-                if (RMODE == 0) {
-                    nominal_init(ic, it);
-#pragma unroll
-                    for (int i = 0; i < 12; ++i) obs[i] = A.nominal_obs[i];
-                } else if (RMODE == 3) {
-                    const float *src = A.init + (active ? env : 0) * 26;
-#pragma unroll
-                    for (int i = 0; i < 13; ++i) { ic[i] = src[i]; it[i] = src[13 + i]; }
-                    rel_obs<false>(ic, it, obs);
-                } else {
-                    if (kPrep) {
-                        // the reset state, its observation and the episode's parameters were prepared by the third wave: a copy
-#pragma unroll
-                        for (int i = 0; i < 13; ++i) ic[i] = s_rst[i][lane];
-#pragma unroll
-                        for (int i = 0; i < 12; ++i) obs[i] = s_rst[13 + i][lane];
-                        if (PARAMS && RMODE == 2) P = Par{s_rst[25][lane], s_rst[26][lane], s_rst[27][lane], s_rst[28][lane]};
-                    } else {
-                        const uint4 w0 = s_phx[t & 1][0][lane], w1 = RMODE == 2 ? s_phx[t & 1][1][lane] : make_uint4(0, 0, 0, 0);
-                        Par Pn;
-                        random_init_apply<RMODE == 2>(A.rc, w0, w1, ic, it, Pn);
-                        if (PARAMS && RMODE == 2) P = Pn;
-                        rel_obs<true>(ic, it, obs);
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < 13; ++i) sc[i] = ic[i];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) uc[i] = 0.0f;
-                ls = 0.0f;
-                tt = 0.0f;
+                store_term_half(D.term_state, active, io, 0, sc);
+                chaser_reset<PARAMS>(L, A, env, active, lane, t, sc, uc, ls, tt, P, obs);
             }
             QS_STAMP_AT(6);
             if (active) {
@@ -613,12 +764,7 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
         }
         if (t > 0) {
             if (active) {
-#pragma unroll
-                for (int i = 0; i < 13; ++i) QS_ST(&bw[(F_SC + i) * kTile], sc[i]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) QS_ST(&bw[(F_UC + i) * kTile], uc[i]);
-                QS_ST(&bw[F_LS * kTile], ls);
-                QS_ST(&bw[F_T * kTile], tt);
+                chaser_store(bw, sc, uc, ls, tt);
                 if (PARAMS && RMODE == 2) store_par(A.par, tile, lane, P);
             }
         }
@@ -641,15 +787,7 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
         QS_STAMP_FLUSH();
     } else if (role == 1) {
         float st[13], ut[4], qd[4];
-#pragma unroll
-        for (int i = 0; i < 13; ++i) st[i] = b[(F_ST + i) * kTile];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ut[i] = b[(F_UT + i) * kTile];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) qd[i] = b[(F_QD + i) * kTile];
-        const float pdes[3] = {10.0f, -50.0f, 5.0f};              // docking_env.py:60
-        const float vdes[3] = {A.C.vdes_x, 0.0f, 0.0f};
-        const float dv[3] = {0.0f, 0.0f, 0.0f};
+        target_load(b, st, ut, qd);
 #if defined(QS_STAMP) && QS_STAMP + 0 < 2
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
@@ -657,95 +795,37 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
         int64_t t = 0;
 #pragma clang loop unroll(disable)
         for (; cmd == RES_STEP; ++t) {
-            const uint64_t k = k0 + (uint64_t)t;
             float pre[13];
 #pragma unroll
             for (int i = 0; i < 13; ++i) pre[i] = st[i];
             const bool lim_t = drone_advance<INTEG>(st, ut, P, A.C.dt);   // with the previous limited control
-#pragma unroll
-            for (int i = 0; i < 13; ++i) s_tgt[i][lane] = st[i];
-            s_limt[lane] = lim_t ? 1 : 0;
-            uint4 w0 = make_uint4(0, 0, 0, 0), w1 = w0;
-            Par Pn = P;
-            if ((RMODE == 1 || RMODE == 2) && !kPrep) {
-                random_init_words<RMODE == 2>(A.rc, STREAM_AUTORESET, A.gid0 + (uint64_t)env, k + 1, w0, w1);
-                s_phx[t & 1][0][lane] = w0;
-                if (RMODE == 2) s_phx[t & 1][1][lane] = w1;     // the params block: only drawn with per-episode params
-            }
+            uint4 w0, w1;
+            target_publish(L, A, env, lane, k0 + (uint64_t)t, t, st, lim_t, w0, w1);
             QS_STAMP_AT(2);
             __syncthreads();                                              // #1
             QS_STAMP_AT(3);
             float *const term_state = (float *)s_tsp[t & 1];             // before #2 (see s_tsp)
-            float u_t[4];
-            target_control(A.C.kind, pdes, vdes, qd, 0.0f, pre, dv, P.m, u_t);   // from the state BEFORE stepping
-            u_limit(u_t, P.m * kG, ut);
+            target_command(A.C, qd, pre, P.m, ut);
             QS_STAMP_AT(4);
             __syncthreads();                                              // #2
             QS_STAMP_AT(5);
-            if (s_done[lane]) {
-                if (term_state && active) {
-                    float *ts = term_state + io * 26 + 13;
-#pragma unroll
-                    for (int i = 0; i < 13; ++i) ts[i] = st[i];
-                }
-                float ic[13], it[13];
-                if (RMODE == 3) {
-                    const float *src = A.init + (active ? env : 0) * 26;
-#pragma unroll
-                    for (int i = 0; i < 13; ++i) it[i] = src[13 + i];
-                } else {
-                    nominal_init(ic, it);
-                    if (PARAMS && RMODE == 2) {
-                        if (kPrep) {
-                            Pn = Par{s_rst[25][lane], s_rst[26][lane], s_rst[27][lane], s_rst[28][lane]};
-                        } else {
-                            random_init_apply<true>(A.rc, w0, w1, ic, it, Pn);
-                            nominal_init(ic, it);
-                        }
-                        P = Pn;
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < 13; ++i) st[i] = it[i];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) ut[i] = 0.0f;
+            if (L.done[lane]) {
+                store_term_half(term_state, active, io, 1, st);
+                target_reset<PARAMS>(L, A, env, active, lane, w0, w1, st, ut, P);
             }
             cmd = s_cmd[(t + 1) & 1];
         }
-        if (active && t > 0) {
-#pragma unroll
-            for (int i = 0; i < 13; ++i) QS_ST(&bw[(F_ST + i) * kTile], st[i]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) QS_ST(&bw[(F_UT + i) * kTile], ut[i]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) QS_ST(&bw[(F_QD + i) * kTile], qd[i]);
-        }
+        if (active && t > 0) target_store(bw, st, ut, qd);
         QS_STAMP_AT(6);
         QS_STAMP_FLUSH();
-    }
-    else if (kPrep) {
-        // third wave (rocRAND reset modes only): what a reset of each step would install -- the draw, random_init_apply and the
-        // state2rel of the result: the same device functions the serial kernel runs inside its reset branch, so the same bits --
-        // for EVERY lane, into LDS; it touches no global memory but the step counter and joins both barriers of every step.  The
-        // chaser wave's reset branch is a 25-word copy, the target wave draws nothing.
+    } else if constexpr (split_prep(RMODE, PREP)) {
         int64_t t = 0;
 #pragma clang loop unroll(disable)
         for (; cmd == RES_STEP; ++t) {
-            const uint64_t k = k0 + (uint64_t)t;
             uint4 w0, w1 = make_uint4(0, 0, 0, 0);
-            random_init_words<RMODE == 2>(A.rc, STREAM_AUTORESET, A.gid0 + (uint64_t)env, k + 1, w0, w1);
+            random_init_words<RMODE == 2>(A.rc, STREAM_AUTORESET, A.gid0 + (uint64_t)env, k0 + (uint64_t)t + 1, w0, w1);
             __syncthreads();                                              // #1
-            float ic[13], it_[13], robs[12];
-            Par Pn;
-            random_init_apply<RMODE == 2>(A.rc, w0, w1, ic, it_, Pn);
-            rel_obs<true>(ic, it_, robs);
-#pragma unroll
-            for (int i = 0; i < 13; ++i) s_rst[i][lane] = ic[i];
-#pragma unroll
-            for (int i = 0; i < 12; ++i) s_rst[13 + i][lane] = robs[i];
-            if (PARAMS && RMODE == 2) {
-                s_rst[25][lane] = Pn.m; s_rst[26][lane] = Pn.Ixx; s_rst[27][lane] = Pn.Iyy; s_rst[28][lane] = Pn.Izz;
-            }
+            prep_publish<PARAMS>(L, A.rc, lane, w0, w1);
             __syncthreads();                                              // #2
             cmd = s_cmd[(t + 1) & 1];
         }
@@ -755,15 +835,7 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
 template <int INTEG, bool PARAMS, int RMODE, int PREP>
 __global__ __launch_bounds__(3 * kTile) void k_env_split(StepArgs A)
 {
-    __shared__ float s_tgt[13][kTile];
-    // PREP == 2: [chaser reset state 13 | its observation 12 | per-episode params 4][lane]: what a reset of THIS step would
-    // install, prepared every step off the chaser wave's critical path.  One buffer suffices in a roll-out too: it is written
-    // between barriers #1 and #2 of a step and read behind #2; the next write is behind the NEXT step's #1, which the readers
-    // have passed.  PREP == 0: [step parity][block]: the chaser wave reads step t's Philox words while t+1's are drawn.
-    constexpr bool kPrep = PREP == 2 && (RMODE == 1 || RMODE == 2);
-    __shared__ float s_rst[kPrep ? 29 : 1][kTile];
-    __shared__ uint4 s_phx[kPrep ? 1 : 2][kPrep ? 1 : 2][kTile];
-    __shared__ unsigned char s_done[kTile], s_limt[kTile];
+    __shared__ SplitLds<RMODE, PREP> L;
     const int lane = threadIdx.x & (kTile - 1);
     const int role = threadIdx.x >> 6;
     const int64_t tile = launch_tile(A, blockIdx.x);   // grid = the tiles of this launch's env group
@@ -785,12 +857,8 @@ __global__ __launch_bounds__(3 * kTile) void k_env_split(StepArgs A)
         // in a roll-out the chaser wave is the long pole of every step while target waves on the same SIMD run ahead with
         // speculative draws: give it the issue slots first (roll-out 2.28 -> 2.13 us/step; no help for a single step)
         if (A.T > 1) __builtin_amdgcn_s_setprio(3);
-        float sc[13], uc[4];
-#pragma unroll
-        for (int i = 0; i < 13; ++i) sc[i] = b[(F_SC + i) * kTile];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) uc[i] = b[(F_UC + i) * kTile];
-        float ls = b[F_LS * kTile], tt = b[F_T * kTile];
+        float sc[13], uc[4], ls, tt;
+        chaser_load(b, sc, uc, ls, tt);
         // the action is requested LAST: loads return in issue order, and the action -- fresh from the caller, the one
         // operand that is not cache-resident -- is not needed before the integration (which uses the PREVIOUS limited
         // control, quadrotor.py:126-144) is done; its miss latency hides under drone_advance
@@ -822,59 +890,17 @@ __global__ __launch_bounds__(3 * kTile) void k_env_split(StepArgs A)
             __syncthreads();                                              // #1: the target's new state is in LDS
             QS_STAMP_AT(3);
             if (A.T == 1) __builtin_amdgcn_s_setprio(3);                 // single step: from here on this wave is the long pole
-            float st[13];
-#pragma unroll
-            for (int i = 0; i < 13; ++i) st[i] = s_tgt[i][lane];
-            const bool lim_t = s_limt[lane] != 0;
             float obs[12], reward;
             unsigned flags;
-            rel_obs(sc, st, obs);
-            score_step(obs, a, sc[2], tt, ls, A.C, lim_c, lim_t, reward, flags);
-            const bool done = (flags & (FLAG_OVERLIMIT | FLAG_OVERTIME)) != 0;
-            const bool rs = done && A.auto_reset;
-            s_done[lane] = rs ? 1 : 0;
+            bool done;
+            const bool rs = chaser_score(L, lane, sc, a, tt, ls, A.C, A.auto_reset, lim_c, obs, reward, flags, done);
             QS_STAMP_AT(4);
             __syncthreads();                                              // #2: reset flags out, this step's Philox words in
             QS_STAMP_AT(5);
             if (rs) {
                 if (A.term_obs && active) store_obs(A.term_obs, io, obs);
-                if (A.term_state && active) {
-                    float *ts = A.term_state + io * 26;
-#pragma unroll
-                    for (int i = 0; i < 13; ++i) ts[i] = sc[i];
-                }
-                float ic[13], it[13];
-                if (RMODE == 0) {
-                    nominal_init(ic, it);
-#pragma unroll
-                    for (int i = 0; i < 12; ++i) obs[i] = A.nominal_obs[i];
-                } else if (RMODE == 3) {
-                    const float *src = A.init + (active ? env : 0) * 26;
-#pragma unroll
-                    for (int i = 0; i < 13; ++i) { ic[i] = src[i]; it[i] = src[13 + i]; }
-                    rel_obs<false>(ic, it, obs);
-                } else {
-                    if (kPrep) {
-                        // the reset state, its observation and the episode's parameters were prepared by the third wave: a copy
-#pragma unroll
-                        for (int i = 0; i < 13; ++i) ic[i] = s_rst[i][lane];
-#pragma unroll
-                        for (int i = 0; i < 12; ++i) obs[i] = s_rst[13 + i][lane];
-                        if (PARAMS && RMODE == 2) P = Par{s_rst[25][lane], s_rst[26][lane], s_rst[27][lane], s_rst[28][lane]};
-                    } else {
-                        const uint4 w0 = s_phx[t & 1][0][lane], w1 = RMODE == 2 ? s_phx[t & 1][1][lane] : make_uint4(0, 0, 0, 0);
-                        Par Pn;
-                        random_init_apply<RMODE == 2>(A.rc, w0, w1, ic, it, Pn);
-                        if (PARAMS && RMODE == 2) P = Pn;
-                        rel_obs<true>(ic, it, obs);
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < 13; ++i) sc[i] = ic[i];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) uc[i] = 0.0f;
-                ls = 0.0f;
-                tt = 0.0f;
+                store_term_half(A.term_state, active, io, 0, sc);
+                chaser_reset<PARAMS>(L, A, env, active, lane, t, sc, uc, ls, tt, P, obs);
             }
             QS_STAMP_AT(6);
             if (active) {
@@ -892,12 +918,7 @@ __global__ __launch_bounds__(3 * kTile) void k_env_split(StepArgs A)
             }
         }
         if (active) {
-#pragma unroll
-            for (int i = 0; i < 13; ++i) QS_ST(&bw[(F_SC + i) * kTile], sc[i]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) QS_ST(&bw[(F_UC + i) * kTile], uc[i]);
-            QS_ST(&bw[F_LS * kTile], ls);
-            QS_ST(&bw[F_T * kTile], tt);
+            chaser_store(bw, sc, uc, ls, tt);
             if (PARAMS && RMODE == 2) store_par(A.par, tile, lane, P);
         }
         if (!A.owner || active || env >= A.n) step_counter_end(A, tile, lane, k0);   // a misplaced tile's counter stays put, too
@@ -908,15 +929,7 @@ __global__ __launch_bounds__(3 * kTile) void k_env_split(StepArgs A)
         QS_STAMP_FLUSH();
     } else if (role == 1) {
         float st[13], ut[4], qd[4];
-#pragma unroll
-        for (int i = 0; i < 13; ++i) st[i] = b[(F_ST + i) * kTile];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ut[i] = b[(F_UT + i) * kTile];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) qd[i] = b[(F_QD + i) * kTile];
-        const float pdes[3] = {10.0f, -50.0f, 5.0f};              // docking_env.py:60
-        const float vdes[3] = {A.C.vdes_x, 0.0f, 0.0f};
-        const float dv[3] = {0.0f, 0.0f, 0.0f};
+        target_load(b, st, ut, qd);
         if (A.T == 1) __builtin_amdgcn_s_setprio(3);   // single step: the chaser wave waits at #1 for this wave's step + draw
 #if defined(QS_STAMP) && QS_STAMP + 0 < 2
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -924,94 +937,36 @@ __global__ __launch_bounds__(3 * kTile) void k_env_split(StepArgs A)
         QS_STAMP_AT(1);
 #pragma clang loop unroll(disable)
         for (int64_t t = 0; t < A.T; ++t) {
-            const uint64_t k = k0 + (uint64_t)t;
             float pre[13];
 #pragma unroll
             for (int i = 0; i < 13; ++i) pre[i] = st[i];
             const bool lim_t = drone_advance<INTEG>(st, ut, P, A.C.dt);   // with the previous limited control
             if (A.owner && chain_owner_mismatch(A, tile, lane, owner_xcc)) active = false;
-#pragma unroll
-            for (int i = 0; i < 13; ++i) s_tgt[i][lane] = st[i];
-            s_limt[lane] = lim_t ? 1 : 0;
-            uint4 w0 = make_uint4(0, 0, 0, 0), w1 = w0;
-            Par Pn = P;
-            if ((RMODE == 1 || RMODE == 2) && !kPrep) {
-                random_init_words<RMODE == 2>(A.rc, STREAM_AUTORESET, A.gid0 + (uint64_t)env, k + 1, w0, w1);
-                s_phx[t & 1][0][lane] = w0;
-                if (RMODE == 2) s_phx[t & 1][1][lane] = w1;     // the params block: only drawn with per-episode params
-            }
+            uint4 w0, w1;
+            target_publish(L, A, env, lane, k0 + (uint64_t)t, t, st, lim_t, w0, w1);
             QS_STAMP_AT(2);
             __syncthreads();                                              // #1
             QS_STAMP_AT(3);
             if (A.T == 1) __builtin_amdgcn_s_setprio(0);
-            float u_t[4];
-            target_control(A.C.kind, pdes, vdes, qd, 0.0f, pre, dv, P.m, u_t);   // from the state BEFORE stepping
-            u_limit(u_t, P.m * kG, ut);
+            target_command(A.C, qd, pre, P.m, ut);
             QS_STAMP_AT(4);
             __syncthreads();                                              // #2
             QS_STAMP_AT(5);
-            if (s_done[lane]) {
-                if (A.term_state && active) {
-                    float *ts = A.term_state + io * 26 + 13;
-#pragma unroll
-                    for (int i = 0; i < 13; ++i) ts[i] = st[i];
-                }
-                float ic[13], it[13];
-                if (RMODE == 3) {
-                    const float *src = A.init + (active ? env : 0) * 26;
-#pragma unroll
-                    for (int i = 0; i < 13; ++i) it[i] = src[13 + i];
-                } else {
-                    nominal_init(ic, it);
-                    if (PARAMS && RMODE == 2) {
-                        if (kPrep) {
-                            Pn = Par{s_rst[25][lane], s_rst[26][lane], s_rst[27][lane], s_rst[28][lane]};
-                        } else {
-                            random_init_apply<true>(A.rc, w0, w1, ic, it, Pn);
-                            nominal_init(ic, it);
-                        }
-                        P = Pn;
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < 13; ++i) st[i] = it[i];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) ut[i] = 0.0f;
+            if (L.done[lane]) {
+                store_term_half(A.term_state, active, io, 1, st);
+                target_reset<PARAMS>(L, A, env, active, lane, w0, w1, st, ut, P);
             }
         }
-        if (active) {
-#pragma unroll
-            for (int i = 0; i < 13; ++i) QS_ST(&bw[(F_ST + i) * kTile], st[i]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) QS_ST(&bw[(F_UT + i) * kTile], ut[i]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) QS_ST(&bw[(F_QD + i) * kTile], qd[i]);
-        }
+        if (active) target_store(bw, st, ut, qd);
         QS_STAMP_AT(6);
         QS_STAMP_FLUSH();
-    }
-    else if (kPrep) {
-        // third wave (rocRAND reset modes only): what a reset of each step would install -- the draw, random_init_apply and the
-        // state2rel of the result: the same device functions the serial kernel runs inside its reset branch, so the same bits --
-        // for EVERY lane, into LDS; it touches no global memory but the step counter and joins both barriers of every step.  The
-        // chaser wave's reset branch is a 25-word copy, the target wave draws nothing.
+    } else if constexpr (split_prep(RMODE, PREP)) {
 #pragma clang loop unroll(disable)
         for (int64_t t = 0; t < A.T; ++t) {
-            const uint64_t k = k0 + (uint64_t)t;
             uint4 w0, w1 = make_uint4(0, 0, 0, 0);
-            random_init_words<RMODE == 2>(A.rc, STREAM_AUTORESET, A.gid0 + (uint64_t)env, k + 1, w0, w1);
+            random_init_words<RMODE == 2>(A.rc, STREAM_AUTORESET, A.gid0 + (uint64_t)env, k0 + (uint64_t)t + 1, w0, w1);
             __syncthreads();                                              // #1
-            float ic[13], it_[13], robs[12];
-            Par Pn;
-            random_init_apply<RMODE == 2>(A.rc, w0, w1, ic, it_, Pn);
-            rel_obs<true>(ic, it_, robs);
-#pragma unroll
-            for (int i = 0; i < 13; ++i) s_rst[i][lane] = ic[i];
-#pragma unroll
-            for (int i = 0; i < 12; ++i) s_rst[13 + i][lane] = robs[i];
-            if (PARAMS && RMODE == 2) {
-                s_rst[25][lane] = Pn.m; s_rst[26][lane] = Pn.Ixx; s_rst[27][lane] = Pn.Iyy; s_rst[28][lane] = Pn.Izz;
-            }
+            prep_publish<PARAMS>(L, A.rc, lane, w0, w1);
             __syncthreads();                                              // #2
         }
     }
@@ -1138,27 +1093,17 @@ __global__ __launch_bounds__(kBlock, 1) void k_policy_forward_fast(const uint4 *
 }
 
 // Policy-in-the-loop roll-out: T steps of  a = clip(MLP(obs));  obs, r, done = env.step(a)  in one launch
-// (run_trained_docking_ppo2.py:37-60 for N envs).  MLP on exact-f32 MFMA (policy_rollout.hpp), env step = the
-// device code of k_env.  obs_0 is derived from the stored state (an observation is always state2rel of the state).
-template <int INTEG, int RMODE>
-__global__ __launch_bounds__(kBlock, 1) void k_policy_rollout(StepArgs A, MlpArgs M, float *__restrict__ actions_out)
+// (run_trained_docking_ppo2.py:37-60 for N envs).  The env step = the device code of k_env; obs_0 is derived from the stored
+// state (an observation is always state2rel of the state).  The step loop of one wave; actor(obs, a, lane) = the kernel's MLP.
+template <int INTEG, int RMODE, class Actor>
+__device__ __forceinline__ void policy_rollout_steps(const StepArgs &A, float *__restrict__ actions_out, Actor &&actor)
 {
-    __shared__ __attribute__((aligned(16))) float lds[policy_lds_floats()];
-    const MlpLds L = mlp_lds_layout(lds);
-    float *const sW1 = L.W1, *const sB1 = L.B1, *const sW2 = L.W2, *const sB2 = L.B2, *const sW3 = L.W3, *const sB3 = L.B3;
-    float *const sObsAll = L.ObsAll, *const sActAll = L.ActAll;
-    mlp_stage_weights(M, L);
-    __syncthreads();
-
     const int lane = threadIdx.x & (kTile - 1);
-    const int w = threadIdx.x >> 6;
-    const int64_t tile = (int64_t)blockIdx.x * (kBlock / kTile) + w;
+    const int64_t tile = (int64_t)blockIdx.x * (kBlock / kTile) + (threadIdx.x >> 6);
     const int64_t env = tile * kTile + lane;
-    const bool active = env < A.n;             // MFMA needs the whole wave: idle lanes carry a nominal env, store nothing
-    float *sObs = sObsAll + w * (12 * 64), *sAct = sActAll + w * (64 * 4);
+    const bool active = env < A.n;
     Env e;
-    if (active) load_env(A.st, tile, lane, e);
-    else { nominal_init(e.sc, e.st); for (int i = 0; i < 4; ++i) { e.uc[i] = 0.0f; e.ut[i] = 0.0f; e.qd[i] = i == 0; } e.ls = 0.0f; e.t = 0.0f; }
+    load_env_or_nominal(A, tile, lane, active, e);
     Par P = A.par_nom;
     const uint64_t k0 = active ? step_counter_begin(A, tile) : 0;
     float obs[12];
@@ -1166,7 +1111,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_policy_rollout(StepArgs A, MlpArg
 #pragma clang loop unroll(disable)
     for (int64_t t = 0; t < A.T; ++t) {
         float a[4];
-        mlp_actor(obs, a, sW1, sB1, sW2, sB2, sW3, sB3, sObs, sAct, lane);
+        actor(obs, a, lane);
         float reward;
         unsigned flags;
         bool done;
@@ -1183,46 +1128,35 @@ __global__ __launch_bounds__(kBlock, 1) void k_policy_rollout(StepArgs A, MlpArg
     if (active) { store_env(A.st, tile, lane, e); step_counter_end(A, tile, lane, k0); }
 }
 
-// The same roll-out with the actor on the bf16 matrix rate and split (hi + lo) operands: policy_rollout.hpp,
-// "Fast actor".  `blob` = the host-packed weight image (kFastBlobBytes), copied verbatim into LDS.
+// the actor on exact-f32 MFMA (policy_rollout.hpp)
+template <int INTEG, int RMODE>
+__global__ __launch_bounds__(kBlock, 1) void k_policy_rollout(StepArgs A, MlpArgs M, float *__restrict__ actions_out)
+{
+    __shared__ __attribute__((aligned(16))) float lds[policy_lds_floats()];
+    const MlpLds L = mlp_lds_layout(lds);
+    mlp_stage_weights(M, L);
+    __syncthreads();
+    const int w = threadIdx.x >> 6;
+    float *const sObs = L.ObsAll + w * (12 * 64), *const sAct = L.ActAll + w * (64 * 4);
+    policy_rollout_steps<INTEG, RMODE>(A, actions_out, [&](const float o[12], float a[4], int lane) {
+        mlp_actor(o, a, L.W1, L.B1, L.W2, L.B2, L.W3, L.B3, sObs, sAct, lane);
+    });
+}
+
+// the actor on the bf16 matrix rate and split (hi + lo) operands: policy_rollout.hpp, "Fast actor".  `blob` = the host-packed
+// weight image (kFastBlobBytes), copied verbatim into LDS.
 template <int INTEG, int RMODE>
 __global__ __launch_bounds__(kBlock, 1) void k_policy_rollout_fast(StepArgs A, const uint4 *__restrict__ blob, float *__restrict__ actions_out)
 {
     __shared__ __attribute__((aligned(16))) char lds[kFastBlobBytes + 4 * (12 * 64 + 64 * 4) * 4];
     mlp_stage_blob(blob, lds);
     __syncthreads();
-    const int lane = threadIdx.x & (kTile - 1);
     const int w = threadIdx.x >> 6;
-    const int64_t tile = (int64_t)blockIdx.x * (kBlock / kTile) + w;
-    const int64_t env = tile * kTile + lane;
-    const bool active = env < A.n;
-    float *stage = reinterpret_cast<float *>(lds + kFastBlobBytes);
-    float *sObs = stage + w * (12 * 64), *sAct = stage + 4 * (12 * 64) + w * (64 * 4);
-    Env e;
-    if (active) load_env(A.st, tile, lane, e);
-    else { nominal_init(e.sc, e.st); for (int i = 0; i < 4; ++i) { e.uc[i] = 0.0f; e.ut[i] = 0.0f; e.qd[i] = i == 0; } e.ls = 0.0f; e.t = 0.0f; }
-    Par P = A.par_nom;
-    const uint64_t k0 = active ? step_counter_begin(A, tile) : 0;
-    float obs[12];
-    rel_obs(e.sc, e.st, obs);
-#pragma clang loop unroll(disable)
-    for (int64_t t = 0; t < A.T; ++t) {
-        float a[4];
-        mlp_actor_fast(obs, a, lds, sObs, sAct, lane);
-        float reward;
-        unsigned flags;
-        bool done;
-        step_and_maybe_reset<INTEG, false, RMODE>(e, P, a, A, active ? env : 0, k0 + (uint64_t)t, obs, reward, flags, done, false);
-        if (active) {
-            const int64_t o = t * A.n + env;
-            store_obs(A.obs, o, obs);
-            A.reward[o] = reward;
-            A.done[o] = done ? 1 : 0;
-            if (A.flags) A.flags[o] = (uint8_t)flags;
-            if (actions_out) reinterpret_cast<float4 *>(actions_out)[o] = make_float4(a[0], a[1], a[2], a[3]);
-        }
-    }
-    if (active) { store_env(A.st, tile, lane, e); step_counter_end(A, tile, lane, k0); }
+    float *const stage = reinterpret_cast<float *>(lds + kFastBlobBytes);
+    float *const sObs = stage + w * (12 * 64), *const sAct = stage + 4 * (12 * 64) + w * (64 * 4);
+    policy_rollout_steps<INTEG, RMODE>(A, actions_out, [&](const float o[12], float a[4], int lane) {
+        mlp_actor_fast(o, a, lds, sObs, sAct, lane);
+    });
 }
 
 // PPO2 data collection in one launch: the Runner loop of rl_baselines/ppo2/ppo2.py:472-499 (+ last_values, :506) for
@@ -1288,6 +1222,61 @@ __device__ __forceinline__ float *load_towers_lds(char *lds_raw, const RunnerArg
     }
 }
 
+// Shared-trunk image (policy_rollout.hpp) into LDS by `nthr` threads; -> the per-wave stages.  FAST: the packed blob verbatim.
+template <bool FAST>
+__device__ __forceinline__ float *load_shared_lds(char *lds_raw, const RunnerArgs &R, int nthr, AcLds &L)
+{
+    if constexpr (FAST) {
+        for (int i = threadIdx.x; i < kAcFastBlobBytes / 16; i += nthr) reinterpret_cast<uint4 *>(lds_raw)[i] = R.blob[i];
+        return reinterpret_cast<float *>(lds_raw + kAcFastBlobBytes);
+    } else {
+        float *sW2p = reinterpret_cast<float *>(lds_raw);
+        float *sW2v = sW2p + kHid * kLdW;
+        float *sW3p = sW2v + kHid * kLdW;
+        float *sW3v = sW3p + 4 * kLdW;
+        float *sW1 = sW3v + kLdW;
+        float *sB1 = sW1 + kHid * kLdW1;
+        float *sB2p = sB1 + kHid;
+        float *sB2v = sB2p + kHid;
+        float *sB3 = sB2v + kHid;
+        for (int i = threadIdx.x; i < kHid * kHid; i += nthr) {
+            sW2p[(i >> 7) * kLdW + (i & 127)] = R.net.wt2[i];
+            sW2v[(i >> 7) * kLdW + (i & 127)] = R.net.wtv2[i];
+        }
+        for (int i = threadIdx.x; i < 4 * kHid; i += nthr) sW3p[(i >> 7) * kLdW + (i & 127)] = R.net.wt3[i];
+        for (int i = threadIdx.x; i < kHid; i += nthr) sW3v[i] = R.net.wtv3[i];
+        for (int i = threadIdx.x; i < kHid * 12; i += nthr) sW1[(i / 12) * kLdW1 + (i % 12)] = R.net.wt1[i];
+        for (int i = threadIdx.x; i < kHid; i += nthr) { sB1[i] = R.net.b1[i]; sB2p[i] = R.net.b2[i]; sB2v[i] = R.net.bv2[i]; }
+        if (threadIdx.x < 16) sB3[threadIdx.x] = threadIdx.x < 4 ? R.net.b3[threadIdx.x] : (threadIdx.x == 4 ? R.net.bv3[0] : 0.0f);
+        L = AcLds{sW1, sB1, sW2p, sB2p, sW2v, sB2v, sW3p, sW3v, sB3};
+        return sB3 + 16;
+    }
+}
+
+// action = mean + std * eps, its neglogp under the diagonal Gaussian, and what the env gets: a = clip(u) or the squashed tanh(u)
+template <class Mean>
+__device__ __forceinline__ void sample_action(const RunnerArgs &R, const Mean &mean, const float eps[4], float u[4], float a[4], float &nl)
+{
+    nl = R.nl_const;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        u[i] = fmaf(R.std[i], eps[i], mean[i]);                   // distributions.py:429
+        const float d = (u[i] - mean[i]) * R.inv_std[i];          // :407
+        nl = fmaf(0.5f * d, d, nl);
+    }
+    if (R.squash) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float sech2;
+            a[i] = q_tanh(u[i], sech2);                           // policies.py:238
+            nl += q_ln(sech2 + 1e-6f);                            // distributions.py:414, 1 - tanh(u)^2 + 1e-6
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = fminf(fmaxf(u[i], -1.0f), 1.0f);   // ppo2.py:483
+    }
+}
+
 template <bool FAST, int NET>
 constexpr int runner_lds_bytes()
 {
@@ -1303,36 +1292,10 @@ __global__ __launch_bounds__(kBlock, 1) void k_runner_rollout(StepArgs A, Runner
 {
     constexpr bool TOW = NET == kNetTowers;
     __shared__ __attribute__((aligned(16))) char lds_raw[runner_lds_bytes<FAST, NET>()];
-    float *lds = reinterpret_cast<float *>(lds_raw);
     AcLds L{}, Lv{};
     float *sStage;
-    if constexpr (TOW) {
-        sStage = load_towers_lds<FAST>(lds_raw, R, kBlock, L, Lv);
-    } else if (FAST) {
-        for (int i = threadIdx.x; i < kAcFastBlobBytes / 16; i += kBlock) reinterpret_cast<uint4 *>(lds_raw)[i] = R.blob[i];
-        sStage = reinterpret_cast<float *>(lds_raw + kAcFastBlobBytes);
-    } else {
-        float *sW2p = lds;
-        float *sW2v = sW2p + kHid * kLdW;
-        float *sW3p = sW2v + kHid * kLdW;
-        float *sW3v = sW3p + 4 * kLdW;
-        float *sW1 = sW3v + kLdW;
-        float *sB1 = sW1 + kHid * kLdW1;
-        float *sB2p = sB1 + kHid;
-        float *sB2v = sB2p + kHid;
-        float *sB3 = sB2v + kHid;
-        sStage = sB3 + 16;
-        for (int i = threadIdx.x; i < kHid * kHid; i += kBlock) {
-            sW2p[(i >> 7) * kLdW + (i & 127)] = R.net.wt2[i];
-            sW2v[(i >> 7) * kLdW + (i & 127)] = R.net.wtv2[i];
-        }
-        for (int i = threadIdx.x; i < 4 * kHid; i += kBlock) sW3p[(i >> 7) * kLdW + (i & 127)] = R.net.wt3[i];
-        for (int i = threadIdx.x; i < kHid; i += kBlock) sW3v[i] = R.net.wtv3[i];
-        for (int i = threadIdx.x; i < kHid * 12; i += kBlock) sW1[(i / 12) * kLdW1 + (i % 12)] = R.net.wt1[i];
-        for (int i = threadIdx.x; i < kHid; i += kBlock) { sB1[i] = R.net.b1[i]; sB2p[i] = R.net.b2[i]; sB2v[i] = R.net.bv2[i]; }
-        if (threadIdx.x < 16) sB3[threadIdx.x] = threadIdx.x < 4 ? R.net.b3[threadIdx.x] : (threadIdx.x == 4 ? R.net.bv3[0] : 0.0f);
-        L = AcLds{sW1, sB1, sW2p, sB2p, sW2v, sB2v, sW3p, sW3v, sB3};
-    }
+    if constexpr (TOW) sStage = load_towers_lds<FAST>(lds_raw, R, kBlock, L, Lv);
+    else sStage = load_shared_lds<FAST>(lds_raw, R, kBlock, L);
     __syncthreads();
 
     const int lane = threadIdx.x & (kTile - 1);
@@ -1343,8 +1306,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_runner_rollout(StepArgs A, Runner
     float *stage = sStage + w * (12 * 64);
     QS_ASSERT((char *)(stage + 12 * 64) <= lds_raw + sizeof lds_raw);
     Env e;
-    if (active) load_env(A.st, tile, lane, e);
-    else { nominal_init(e.sc, e.st); for (int i = 0; i < 4; ++i) { e.uc[i] = 0.0f; e.ut[i] = 0.0f; e.qd[i] = i == 0; } e.ls = 0.0f; e.t = 0.0f; }
+    load_env_or_nominal(A, tile, lane, active, e);
     Par P = A.par_nom;
     if (PARAMS && active) P = load_par(A.par, tile, lane);
     const uint64_t k0 = active ? step_counter_begin(A, tile) : 0;
@@ -1370,25 +1332,8 @@ __global__ __launch_bounds__(kBlock, 1) void k_runner_rollout(StepArgs A, Runner
         } else {
             random_normal4(A.rc.seed, A.gid0 + (uint64_t)(active ? env : 0), k0 + (uint64_t)t, eps);
         }
-        float u[4], a[4];
-        float nl = R.nl_const;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            u[i] = fmaf(R.std[i], eps[i], head[i]);                   // distributions.py:429
-            const float d = (u[i] - head[i]) * R.inv_std[i];          // :407
-            nl = fmaf(0.5f * d, d, nl);
-        }
-        if (R.squash) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float sech2;
-                a[i] = q_tanh(u[i], sech2);                           // policies.py:238
-                nl += q_ln(sech2 + 1e-6f);                            // distributions.py:414, 1 - tanh(u)^2 + 1e-6
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[i] = fminf(fmaxf(u[i], -1.0f), 1.0f);   // ppo2.py:483
-        }
+        float u[4], a[4], nl;
+        sample_action(R, head, eps, u, a, nl);
         if (active) {
             reinterpret_cast<float4 *>(R.actions)[ow] = make_float4(u[0], u[1], u[2], u[3]);
             R.values[o] = head[4];
@@ -1441,34 +1386,9 @@ __global__ __launch_bounds__(2 * kBlock, 1) void k_runner_split(StepArgs A, Runn
     __shared__ __attribute__((aligned(16))) char lds_raw[TOW ? runner_lds_bytes<FAST, NET>() : kZeros + (FAST ? 2048 : 0)];
     AcLds L{}, Lv{};
     float *sStage;
-    if constexpr (TOW) {
-        sStage = load_towers_lds<FAST>(lds_raw, R, 2 * kBlock, L, Lv);
-    } else if (FAST) {
-        for (int i = threadIdx.x; i < kAcFastBlobBytes / 16; i += 2 * kBlock) reinterpret_cast<uint4 *>(lds_raw)[i] = R.blob[i];
-        if (threadIdx.x < 128) reinterpret_cast<uint4 *>(lds_raw + kZeros)[threadIdx.x] = make_uint4(0, 0, 0, 0);
-        sStage = reinterpret_cast<float *>(lds_raw + kAcFastBlobBytes);
-    } else {
-        float *sW2p = reinterpret_cast<float *>(lds_raw);
-        float *sW2v = sW2p + kHid * kLdW;
-        float *sW3p = sW2v + kHid * kLdW;
-        float *sW3v = sW3p + 4 * kLdW;
-        float *sW1 = sW3v + kLdW;
-        float *sB1 = sW1 + kHid * kLdW1;
-        float *sB2p = sB1 + kHid;
-        float *sB2v = sB2p + kHid;
-        float *sB3 = sB2v + kHid;
-        sStage = sB3 + 16;
-        for (int i = threadIdx.x; i < kHid * kHid; i += 2 * kBlock) {
-            sW2p[(i >> 7) * kLdW + (i & 127)] = R.net.wt2[i];
-            sW2v[(i >> 7) * kLdW + (i & 127)] = R.net.wtv2[i];
-        }
-        for (int i = threadIdx.x; i < 4 * kHid; i += 2 * kBlock) sW3p[(i >> 7) * kLdW + (i & 127)] = R.net.wt3[i];
-        for (int i = threadIdx.x; i < kHid; i += 2 * kBlock) sW3v[i] = R.net.wtv3[i];
-        for (int i = threadIdx.x; i < kHid * 12; i += 2 * kBlock) sW1[(i / 12) * kLdW1 + (i % 12)] = R.net.wt1[i];
-        for (int i = threadIdx.x; i < kHid; i += 2 * kBlock) { sB1[i] = R.net.b1[i]; sB2p[i] = R.net.b2[i]; sB2v[i] = R.net.bv2[i]; }
-        if (threadIdx.x < 16) sB3[threadIdx.x] = threadIdx.x < 4 ? R.net.b3[threadIdx.x] : (threadIdx.x == 4 ? R.net.bv3[0] : 0.0f);
-        L = AcLds{sW1, sB1, sW2p, sB2p, sW2v, sB2v, sW3p, sW3v, sB3};
-    }
+    if constexpr (TOW) sStage = load_towers_lds<FAST>(lds_raw, R, 2 * kBlock, L, Lv);
+    else sStage = load_shared_lds<FAST>(lds_raw, R, 2 * kBlock, L);
+    if (!TOW && FAST && threadIdx.x < 128) reinterpret_cast<uint4 *>(lds_raw + kZeros)[threadIdx.x] = make_uint4(0, 0, 0, 0);
     __syncthreads();
     const int lane = threadIdx.x & (kTile - 1);
     const int w = (threadIdx.x >> 6) & 3;
@@ -1556,8 +1476,7 @@ __global__ __launch_bounds__(2 * kBlock, 1) void k_runner_split(StepArgs A, Runn
         QS_PHASE_FLUSH(0);
     } else {
         Env e;
-        if (active) load_env(A.st, tile, lane, e);
-        else { nominal_init(e.sc, e.st); for (int i = 0; i < 4; ++i) { e.uc[i] = 0.0f; e.ut[i] = 0.0f; e.qd[i] = i == 0; } e.ls = 0.0f; e.t = 0.0f; }
+        load_env_or_nominal(A, tile, lane, active, e);
         Par P = A.par_nom;
         if (PARAMS && active) P = load_par(A.par, tile, lane);
         const uint64_t k0 = active ? step_counter_begin(A, tile) : 0;
@@ -1589,25 +1508,8 @@ __global__ __launch_bounds__(2 * kBlock, 1) void k_runner_split(StepArgs A, Runn
             __syncthreads();                                                  // #b
             QS_PHASE(3);
             const f32x4 mean = *reinterpret_cast<const f32x4 *>(stage + lane * 8);
-            float u[4], a[4];
-            float nl = R.nl_const;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                u[i] = fmaf(R.std[i], eps[i], mean[i]);                       // distributions.py:429
-                const float d = (u[i] - mean[i]) * R.inv_std[i];              // :407
-                nl = fmaf(0.5f * d, d, nl);
-            }
-            if (R.squash) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float sech2;
-                    a[i] = q_tanh(u[i], sech2);                               // policies.py:238
-                    nl += q_ln(sech2 + 1e-6f);                                // distributions.py:414
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) a[i] = fminf(fmaxf(u[i], -1.0f), 1.0f);   // ppo2.py:483
-            }
+            float u[4], a[4], nl;
+            sample_action(R, mean, eps, u, a, nl);
             if (active) {
                 reinterpret_cast<float4 *>(R.actions)[ow] = make_float4(u[0], u[1], u[2], u[3]);
                 R.neglogp[o] = nl;

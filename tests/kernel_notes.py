@@ -9,13 +9,17 @@ import pytest
 LLVM = "/opt/rocm/llvm/bin"
 
 
-def code_object(directory):
-    """unbundle the gfx950 code object of the built library into `directory` -> its path (skips without the ROCm LLVM tools)"""
+FIELDS = ("group_segment_fixed_size", "private_segment_fixed_size", "vgpr_count", "vgpr_spill_count", "max_flat_workgroup_size")
+
+
+def code_object(directory, so=None):
+    """unbundle the gfx950 code object of the built library (or of the library `so`) into `directory` -> its path (skips
+    without the ROCm LLVM tools)"""
     from quadsim_amd import _lib
     for tool in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf", "llvm-objdump"):
         if not os.path.exists(os.path.join(LLVM, tool)):
             pytest.skip("ROCm LLVM tools not installed")
-    so = _lib.build_library()
+    so = so or _lib.build_library()
     d = str(directory)
     fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "dev.co")
     subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, so, os.path.join(d, "so.copy")])
@@ -24,14 +28,13 @@ def code_object(directory):
     return co
 
 
-def kernel_notes(co):
+def kernel_notes(co, fields=FIELDS):
     """{mangled kernel name: resource fields} of every kernel in the code object"""
     notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
     out = {}
-    for block in re.split(r"\n\s+- \.agpr_count", notes):
+    for block in re.split(r"\n(?=\s+- \.agpr_count)", notes):
         m = re.search(r"\.name:\s+(\S+)", block)
         if m:
             field = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", block).group(1))   # noqa: E731
-            out[m.group(1)] = {k: field(k) for k in ("group_segment_fixed_size", "private_segment_fixed_size", "vgpr_count",
-                                                     "vgpr_spill_count", "max_flat_workgroup_size")}
+            out[m.group(1)] = {k: field(k) for k in fields}
     return out
