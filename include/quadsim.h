@@ -450,6 +450,27 @@ int qs_runner_rollout_net_fast_blob_bytes(int32_t layout);
  * the expert's persistent desired state (initialise to env.chaser_ini_state); actions [N,4] out.  Device buffers. */
 int qs_expert_action(QsEnv *env, float *state_des, float kp, float kd, float *actions);
 
+/* The expert in the loop, ONE launch: T steps of  a = expert(state); obs', r, done = env.step(a)  for all N docking envs --
+ * the loop of run_expert_policy.py:49-69 and the recorder's, run_expert_record.py:121-156 -- bit for bit what T times
+ * qs_expert_action; qs_step give (auto-reset and its random keys are the step API's; state_des persists across a reset).
+ * obs [T,N,12]: the observation BEFORE step t, which is what the recorder appends (:122-123; row 0 = what the preceding
+ * qs_step / qs_reset returned); actions [T,N,4] not clipped; reward, done [T,N]; flags nullable [T,N]; last_obs nullable
+ * [N,12] = the observation after the last step.  state_des [N,13] in/out as for qs_expert_action.  Advances the state, the
+ * step counter and, where parameters are redrawn per episode, the parameters.  With QS_LAYOUT_ENV_MAJOR
+ * (qs_set_rollout_layout) obs is [N,T,12] and actions [N,T,4] -- the order of an ExpertDataset; the scalars stay [T,N].
+ * docking-v0 / v1 / v2, auto_reset, device buffers; every randomise mode, stored initial states, per-env params, both
+ * integrators.  obs, actions, last_obs 16-byte aligned.
+ * Added after QS_VERSION 131 without changing it: callers detect these two entry points by symbol (dlsym). */
+int qs_expert_rollout(QsEnv *env, int64_t T, float *state_des /* [N,13] in/out */, float kp, float kd,
+                      float *obs /* [T,N,12] obs before step t */, float *actions /* [T,N,4] */, float *reward /* [T,N] */,
+                      uint8_t *done /* [T,N] */, uint8_t *flags /* nullable */, float *last_obs /* nullable [N,12] */);
+
+/* `episodes` complete expert episodes per env from its CURRENT state, or max_steps steps at most: qs_policy_evaluate with the
+ * expert of run_expert_policy.py:49-69 as the policy (its per-episode bookkeeping, :62-69), same outputs and alignment rules.
+ * Nothing is written back: not the state, the parameters, the step counters, nor state_des. */
+int qs_expert_evaluate(QsEnv *env, int32_t episodes, int64_t max_steps, const float *state_des, float kp, float kd,
+                       double *ep_return, int32_t *ep_length, uint8_t *ep_flags, int32_t *ep_docked, int32_t *finished);
+
 /* ---- layer-1 entry points: n independent drones / controllers (n need not equal N) ----------- */
 
 /* Drone.step (dynamics/quadrotor.py:126-144): state [n,13] in/out, u_prev [n,4] in/out (Drone.u),

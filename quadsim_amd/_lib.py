@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("QUADSIM_HIP_LIB") or os.path.join(CSRC, "libquadsim_hip.so")  # override: A/B builds
 SOURCES = [os.path.join(CSRC, "quadsim_hip.hip")]
 HEADERS = [os.path.join(CSRC, h) for h in ("quadsim_device.hpp", "step_kernels.hpp", "rollout_ops.hpp", "policy_rollout.hpp", "env_groups.hpp",
-                                          "private_queue.hpp", "policy_evaluate.hpp")] + [os.path.join(HERE, "..", "include", "quadsim.h")]
+                                          "private_queue.hpp", "policy_evaluate.hpp", "expert_rollout.hpp")] + [os.path.join(HERE, "..", "include", "quadsim.h")]
 
 QS_OK = 0
 KIND_V0, KIND_V2, KIND_V1, KIND_HOVER = 0, 1, 2, 3
@@ -35,6 +35,7 @@ EXPORTS = [
     "qs_step_group", "qs_step_groups", "qs_groups_fork", "qs_groups_join",
     "qs_swap_and_flatten_u8", "qs_gae_flatten", "qs_episode_stats", "qs_set_rollout_layout",
     "qs_set_queue_mode", "qs_get_queue_mode", "qs_set_queue_ordering", "qs_get_queue_ordering",
+    "qs_expert_rollout", "qs_expert_evaluate",
 ]
 
 
@@ -149,6 +150,8 @@ def load():
         "qs_gae": [vp, i64, i64, vp, vp, vp, vp, vp, f32, f32, vp, vp],
         "qs_swap_and_flatten": [vp, i64, i64, i64, vp, vp],
         "qs_expert_action": [vp, vp, f32, f32, vp],
+        "qs_expert_rollout": [vp, i64, vp, f32, f32] + [vp] * 6,
+        "qs_expert_evaluate": [vp, i32, i64, vp, f32, f32] + [vp] * 5,
         "qs_policy_rollout": [vp, i64] + [vp] * 11,
         "qs_policy_rollout_fast": [vp, i64] + [vp] * 6,
         "qs_policy_rollout_fast_blob_bytes": [],

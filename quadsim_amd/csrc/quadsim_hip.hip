@@ -19,6 +19,7 @@
 //     rollout_ops.hpp      GAE, flatten, episode statistics            policy_rollout.hpp   the MLP on the matrix cores
 //     env_groups.hpp       env groups (qs_set_groups)                  private_queue.hpp    private AQL queues (qs_set_queue_mode)
 //     policy_evaluate.hpp  K complete episodes per env of the deterministic actor (qs_policy_evaluate)
+//     expert_rollout.hpp   the PID expert in the loop: T steps / K complete episodes per env (qs_expert_rollout, qs_expert_evaluate)
 // and here: the handle (QsEnv), its launch / reset / bounce-buffer helpers, and the C ABI.
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
@@ -140,6 +141,7 @@ using namespace qs;
 
 #include "step_kernels.hpp"
 #include "policy_evaluate.hpp"
+#include "expert_rollout.hpp"
 
 #ifdef QS_STAMP
 static unsigned long long *g_host_stamps = nullptr;     // qs_debug_set_stamps: handed to every launch through StepArgs
@@ -1613,6 +1615,59 @@ int qs_expert_action(QsEnv *e, float *state_des, float kp, float kd, float *acti
         hipLaunchKernelGGL(k_expert_action<true>, dim3(grid_tiles(e->n)), dim3(kBlock), 0, e->stream, e->st, e->par, e->n, state_des, kp, kd, pn, actions);
     else
         hipLaunchKernelGGL(k_expert_action<false>, dim3(grid_tiles(e->n)), dim3(kBlock), 0, e->stream, e->st, e->par, e->n, state_des, kp, kd, pn, actions);
+    HIP_TRY(hipGetLastError());
+    return QS_OK;
+}
+
+// what both fused expert entry points refuse (the step API's other configurations are all taken)
+static int expert_fused_checks(const QsEnv *e, const char *who)
+{
+    if (e->cfg.kind == QS_KIND_HOVERING_V0) return fail(QS_ERR_INVALID, "%s: docking envs only (the reference has no expert for hovering-v0)", who);
+    if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "%s: device buffers only", who);
+    if (!e->cfg.auto_reset) return fail(QS_ERR_INVALID, "%s: requires auto_reset (episodes follow each other as in the step API)", who);
+    return QS_OK;
+}
+
+int qs_expert_rollout(QsEnv *e, int64_t T, float *state_des, float kp, float kd, float *obs, float *actions, float *reward,
+                      uint8_t *done, uint8_t *flags, float *last_obs)
+{
+    CHECK_ENV(e);
+    Range rg_("qs_expert_rollout");
+    if (T < 1) return fail(QS_ERR_INVALID, "qs_expert_rollout: T must be >= 1");
+    if (!state_des || !obs || !actions || !reward || !done)
+        return fail(QS_ERR_INVALID, "qs_expert_rollout: state_des, obs, actions, reward and done are required");
+    if (int rc = expert_fused_checks(e, "qs_expert_rollout")) return rc;
+    if ((((uintptr_t)obs) | ((uintptr_t)actions) | ((uintptr_t)last_obs)) & 15u)
+        return fail(QS_ERR_INVALID, "qs_expert_rollout: obs, actions and last_obs must be 16-byte aligned");
+    StepArgs A = make_args(e);
+    A.T = T; A.obs = obs; A.reward = reward; A.done = done; A.flags = flags;
+    const ExpertArgs X{state_des, kp, kd, actions, last_obs, e->runner_env_major ? 1 : 0};
+    const unsigned grid = grid_tiles(e->n);
+    with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {     // as launch_env_on
+        hipLaunchKernelGGL((k_expert_rollout<INTEG, PARAMS, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, X);
+    });
+    HIP_TRY(hipGetLastError());
+    return QS_OK;
+}
+
+int qs_expert_evaluate(QsEnv *e, int32_t episodes, int64_t max_steps, const float *state_des, float kp, float kd,
+                       double *ep_return, int32_t *ep_length, uint8_t *ep_flags, int32_t *ep_docked, int32_t *finished)
+{
+    CHECK_ENV(e);
+    Range rg_("qs_expert_evaluate");
+    if (episodes < 1) return fail(QS_ERR_INVALID, "qs_expert_evaluate: episodes must be >= 1");
+    if (max_steps < 1) return fail(QS_ERR_INVALID, "qs_expert_evaluate: max_steps must be >= 1");
+    if (!state_des || !ep_return || !ep_length || !finished)
+        return fail(QS_ERR_INVALID, "qs_expert_evaluate: state_des, ep_return, ep_length and finished are required");
+    if (int rc = expert_fused_checks(e, "qs_expert_evaluate")) return rc;
+    if ((((uintptr_t)ep_return) & 7u) || ((((uintptr_t)ep_length) | ((uintptr_t)ep_docked) | ((uintptr_t)finished)) & 3u))
+        return fail(QS_ERR_INVALID, "qs_expert_evaluate: ep_return must be 8-byte aligned, ep_length, ep_docked and finished 4-byte aligned");
+    const StepArgs A = make_args(e);
+    const EvalArgs E{ep_return, ep_length, ep_flags, ep_docked, finished, max_steps, episodes};
+    const unsigned grid = grid_tiles(e->n);
+    with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {
+        hipLaunchKernelGGL((k_expert_evaluate<INTEG, PARAMS, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, state_des, kp, kd, E);
+    });
     HIP_TRY(hipGetLastError());
     return QS_OK;
 }

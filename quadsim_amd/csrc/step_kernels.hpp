@@ -1789,10 +1789,31 @@ __global__ __launch_bounds__(kBlock) void k_ctrl(int64_t n, int mode, float *sta
 }
 
 // PID expert (run_expert_policy.py:49-69, run_expert_record.py:121-136): vel_controller on the chaser towards
-// 0.2 m behind the target, inverse action map (inv(rotor2control) u - mean)/std, not clipped.  Reads the envs'
-// current chaser / target state straight from the tiles; state_des [N][13] is the expert's persistent desired
-// state (pos = chaser start, vel = des_vel, [6:12] rewritten by the controller).  First step of an episode
-// (t == 0) keeps the previous des_vel (:58-59).
+// 0.2 m behind the target, inverse action map (inv(rotor2control) u - mean)/std, not clipped.  sd [13] is the
+// expert's persistent desired state (pos = chaser start, vel = des_vel, [6:12] rewritten by the controller).  First
+// step of an episode (t == 0) keeps the previous des_vel (:58-59).  The one copy of the expert: k_expert_action and the
+// fused kernels of expert_rollout.hpp inline it, so they compute the same bits (-ffp-contract=on).
+__device__ __forceinline__ void expert_action(const float sc[13], const float tp[3], float t, float m, float kp, float kd,
+                                              float sd[13], float act[4])
+{
+    if (t != 0.0f) {
+        sd[3] = kp * (tp[0] - 0.2f - sc[0]) + kd * (-sc[3]);
+        sd[4] = kp * (tp[1] - sc[1]) + kd * (-sc[4]);
+        sd[5] = kp * (tp[2] - sc[2]) + kd * (-sc[5]);
+    }
+    const float dv[3] = {0.0f, 0.0f, 0.0f};        // state_last aliases the current state
+    float u[4];
+    target_control(1, sd, sd + 3, sd + 6, sd[12], sc, dv, m, u);
+    sd[10] = 0.0f; sd[11] = 0.0f;
+    constexpr float a = 1.0f / (2.0f * kL), bq = 1.0f / (4.0f * kLambda);
+    const float f4 = 0.25f * u[0];
+    const float f0 = f4 - a * u[2] + bq * u[3], f1 = f4 + a * u[1] - bq * u[3];
+    const float f2 = f4 + a * u[2] + bq * u[3], f3 = f4 - a * u[1] - bq * u[3];
+    const float inv_mean = q_rcp(0.5f * m * kG);
+    act[0] = f0 * inv_mean - 1.0f; act[1] = f1 * inv_mean - 1.0f; act[2] = f2 * inv_mean - 1.0f; act[3] = f3 * inv_mean - 1.0f;
+}
+
+// qs_expert_action: reads the envs' current chaser / target state straight from the tiles; state_des [N][13]
 template <bool PARAMS>
 __global__ __launch_bounds__(kBlock) void k_expert_action(const float *__restrict__ st, const float *__restrict__ par, int64_t n,
                                                           float *__restrict__ state_des, float kp, float kd, Par par_nom,
@@ -1810,22 +1831,9 @@ __global__ __launch_bounds__(kBlock) void k_expert_action(const float *__restric
     for (int i = 0; i < 13; ++i) sd[i] = state_des[env * 13 + i];
     Par P = par_nom;
     if (PARAMS) P = load_par(par, tile, lane);
-    if (t != 0.0f) {
-        sd[3] = kp * (tp[0] - 0.2f - sc[0]) + kd * (-sc[3]);
-        sd[4] = kp * (tp[1] - sc[1]) + kd * (-sc[4]);
-        sd[5] = kp * (tp[2] - sc[2]) + kd * (-sc[5]);
-    }
-    const float dv[3] = {0.0f, 0.0f, 0.0f};        // state_last aliases the current state
-    float u[4];
-    target_control(1, sd, sd + 3, sd + 6, sd[12], sc, dv, P.m, u);
-    sd[10] = 0.0f; sd[11] = 0.0f;
-    constexpr float a = 1.0f / (2.0f * kL), bq = 1.0f / (4.0f * kLambda);
-    const float f4 = 0.25f * u[0];
-    const float f0 = f4 - a * u[2] + bq * u[3], f1 = f4 + a * u[1] - bq * u[3];
-    const float f2 = f4 + a * u[2] + bq * u[3], f3 = f4 - a * u[1] - bq * u[3];
-    const float inv_mean = q_rcp(0.5f * P.m * kG);
-    reinterpret_cast<float4 *>(actions)[env] = make_float4(f0 * inv_mean - 1.0f, f1 * inv_mean - 1.0f, f2 * inv_mean - 1.0f,
-                                                           f3 * inv_mean - 1.0f);
+    float a[4];
+    expert_action(sc, tp, t, P.m, kp, kd, sd, a);
+    reinterpret_cast<float4 *>(actions)[env] = make_float4(a[0], a[1], a[2], a[3]);
     for (int i = 3; i < 12; ++i) state_des[env * 13 + i] = sd[i];
 }
 
