@@ -337,7 +337,7 @@ int qs_policy_forward_fast(QsEnv *env, int64_t n, const void *packed_weights, co
  * value is carried as bf16 hi + lo and x*w is evaluated as hi*hi + hi*lo + lo*hi with f32 accumulation -- about 1e-5
  * error on an action instead of float32's 1e-7; opt-in, not bit-compatible with the float32 policy.
  * packed_weights: device image of qs_policy_rollout_fast_blob_bytes() bytes, 16-byte aligned (layout:
- * quadsim_amd/csrc/policy_rollout.hpp "Fast actor"; quadsim_amd.policy.pack_fast_weights builds it). */
+ * quadsim_amd/csrc/mlp.hpp "Fast actor"; quadsim_amd.policy.pack_fast_weights builds it). */
 int qs_policy_rollout_fast(QsEnv *env, int64_t T, const void *packed_weights, float *obs, float *reward, uint8_t *done,
                            uint8_t *flags, float *actions);
 int qs_policy_rollout_fast_blob_bytes(void);
@@ -401,7 +401,7 @@ int qs_set_rollout_layout(QsEnv *env, int32_t layout);
 
 /* qs_runner_rollout with the networks on the bf16 matrix rate and split (hi + lo) operands, as qs_policy_rollout_fast:
  * about 1e-5 error on means and values instead of float32's 1e-7; opt-in.  packed_weights: device image of
- * qs_runner_rollout_fast_blob_bytes() bytes, 16-byte aligned (layout: quadsim_amd/csrc/policy_rollout.hpp "Fast
+ * qs_runner_rollout_fast_blob_bytes() bytes, 16-byte aligned (layout: quadsim_amd/csrc/mlp.hpp "Fast
  * actor-critic heads"; quadsim_amd.runner.pack_fast_actor_critic builds it); logstd [4] on the HOST. */
 int qs_runner_rollout_fast(QsEnv *env, int64_t T, const void *packed_weights, const float *logstd, int squash,
                            const float *noise, const uint8_t *dones_in, float *mb_obs, float *mb_actions, float *mb_values,

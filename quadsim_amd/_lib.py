@@ -12,8 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("QUADSIM_HIP_LIB") or os.path.join(CSRC, "libquadsim_hip.so")  # override: A/B builds
 SOURCES = [os.path.join(CSRC, "quadsim_hip.hip")]
-HEADERS = [os.path.join(CSRC, h) for h in ("quadsim_device.hpp", "step_kernels.hpp", "rollout_ops.hpp", "policy_rollout.hpp", "env_groups.hpp",
-                                          "private_queue.hpp", "policy_evaluate.hpp", "expert_rollout.hpp")] + [os.path.join(HERE, "..", "include", "quadsim.h")]
+# every fragment of the one translation unit is a rebuild dependency
+HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp")) + [os.path.join(HERE, "..", "include", "quadsim.h")]
 
 QS_OK = 0
 KIND_V0, KIND_V2, KIND_V1, KIND_HOVER = 0, 1, 2, 3

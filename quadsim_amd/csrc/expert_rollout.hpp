@@ -1,6 +1,6 @@
 // expert_rollout.hpp -- the PID expert in the loop: T steps of  a = expert(state); obs', r, done = env.step(a)  in one launch
 // (qs_expert_rollout: run_expert_policy.py:49-69 / run_expert_record.py:121-156 for N envs), and K complete expert episodes
-// per env, read-only (qs_expert_evaluate).  A fragment of quadsim_hip.hip, included right after policy_evaluate.hpp, nowhere else.
+// per env, read-only (qs_expert_evaluate).  A fragment of quadsim_hip.hip, included right after runner_kernels.hpp, nowhere else.
 //
 // One lane per env, 256 threads = 4 tiles, no LDS, no barrier: the env state (40 words), the per-env parameters and the
 // expert's desired state stay in registers from the tile load to the tile store.  The expert = expert_action (the body of
@@ -10,6 +10,53 @@
 #pragma once
 
 namespace {
+
+// PID expert (run_expert_policy.py:49-69, run_expert_record.py:121-136): vel_controller on the chaser towards
+// 0.2 m behind the target, inverse action map (inv(rotor2control) u - mean)/std, not clipped.  sd [13] is the
+// expert's persistent desired state (pos = chaser start, vel = des_vel, [6:12] rewritten by the controller).  First
+// step of an episode (t == 0) keeps the previous des_vel (:58-59).  The one copy of the expert: k_expert_action and the
+// fused kernels below inline it, so they compute the same bits (-ffp-contract=on).
+__device__ __forceinline__ void expert_action(const float sc[13], const float tp[3], float t, float m, float kp, float kd,
+                                              float sd[13], float act[4])
+{
+    if (t != 0.0f) {
+        sd[3] = kp * (tp[0] - 0.2f - sc[0]) + kd * (-sc[3]);
+        sd[4] = kp * (tp[1] - sc[1]) + kd * (-sc[4]);
+        sd[5] = kp * (tp[2] - sc[2]) + kd * (-sc[5]);
+    }
+    const float dv[3] = {0.0f, 0.0f, 0.0f};        // state_last aliases the current state
+    float u[4];
+    target_control(1, sd, sd + 3, sd + 6, sd[12], sc, dv, m, u);
+    sd[10] = 0.0f; sd[11] = 0.0f;
+    constexpr float a = 1.0f / (2.0f * kL), bq = 1.0f / (4.0f * kLambda);
+    const float f4 = 0.25f * u[0];
+    const float f0 = f4 - a * u[2] + bq * u[3], f1 = f4 + a * u[1] - bq * u[3];
+    const float f2 = f4 + a * u[2] + bq * u[3], f3 = f4 - a * u[1] - bq * u[3];
+    const float inv_mean = q_rcp(0.5f * m * kG);
+    act[0] = f0 * inv_mean - 1.0f; act[1] = f1 * inv_mean - 1.0f; act[2] = f2 * inv_mean - 1.0f; act[3] = f3 * inv_mean - 1.0f;
+}
+
+// qs_expert_action: reads the envs' current chaser / target state straight from the tiles; state_des [N][13]
+template <bool PARAMS>
+__global__ __launch_bounds__(kBlock) void k_expert_action(const float *__restrict__ st, const float *__restrict__ par, int64_t n,
+                                                          float *__restrict__ state_des, float kp, float kd, Par par_nom,
+                                                          float *__restrict__ actions)
+{
+    const auto [lane, tile, env, active] = tile_lane(n);
+    if (!active) return;
+    const float *b = st + tile * (int64_t)(kRecWords * kTile) + lane;
+    float sc[13], tp[3], sd[13];
+    for (int i = 0; i < 13; ++i) sc[i] = b[(F_SC + i) * kTile];
+    for (int i = 0; i < 3; ++i) tp[i] = b[(F_ST + i) * kTile];
+    const float t = b[F_T * kTile];
+    for (int i = 0; i < 13; ++i) sd[i] = state_des[env * 13 + i];
+    Par P = par_nom;
+    if (PARAMS) P = load_par(par, tile, lane);
+    float a[4];
+    expert_action(sc, tp, t, P.m, kp, kd, sd, a);
+    reinterpret_cast<float4 *>(actions)[env] = make_float4(a[0], a[1], a[2], a[3]);
+    for (int i = 3; i < 12; ++i) state_des[env * 13 + i] = sd[i];
+}
 
 struct ExpertArgs {
     float *state_des;      // [n,13]: in / out (roll-out), read only (evaluation)
@@ -31,10 +78,8 @@ __device__ __forceinline__ void load_state_des(const float *__restrict__ state_d
 template <int INTEG, bool PARAMS, int RMODE>
 __global__ __launch_bounds__(kBlock) void k_expert_rollout(StepArgs A, ExpertArgs X)
 {
-    const int lane = threadIdx.x & (kTile - 1);
-    const int64_t tile = (int64_t)blockIdx.x * (kBlock / kTile) + (threadIdx.x >> 6);
-    const int64_t env = tile * kTile + lane;
-    if (env >= A.n) return;                    // no MFMA, no barrier: idle lanes of the tail tile simply leave
+    const auto [lane, tile, env, active] = tile_lane(A.n);
+    if (!active) return;                       // no MFMA, no barrier: idle lanes of the tail tile simply leave
     QS_ASSERT(tile < A.tile_end);
     const uint64_t k0 = step_counter_begin_vmem(A, tile);
     Env e;
@@ -73,15 +118,13 @@ __global__ __launch_bounds__(kBlock) void k_expert_rollout(StepArgs A, ExpertArg
     for (int i = 3; i < 12; ++i) X.state_des[env * 13 + i] = sd[i];
 }
 
-// K complete expert episodes per env from the env's CURRENT state (the contract of k_policy_evaluate, policy_evaluate.hpp):
+// K complete expert episodes per env from the env's CURRENT state (the contract of k_policy_evaluate, policy_kernels.hpp):
 // the only global stores are the episode records and finished[]; a wave leaves as soon as all its lanes hold K records.
 template <int INTEG, bool PARAMS, int RMODE>
 __global__ __launch_bounds__(kBlock) void k_expert_evaluate(StepArgs A, const float *__restrict__ state_des, float kp, float kd, EvalArgs E)
 {
-    const int lane = threadIdx.x & (kTile - 1);
-    const int64_t tile = (int64_t)blockIdx.x * (kBlock / kTile) + (threadIdx.x >> 6);
-    const int64_t env = tile * kTile + lane;
-    if (env >= A.n) return;
+    const auto [lane, tile, env, active] = tile_lane(A.n);
+    if (!active) return;
     const uint64_t k0 = step_counter_begin(A, tile);
     Env e;
     load_env(A.st, tile, lane, e);
@@ -89,35 +132,18 @@ __global__ __launch_bounds__(kBlock) void k_expert_evaluate(StepArgs A, const fl
     if (PARAMS) P = load_par(A.par, tile, lane);
     float sd[13];
     load_state_des(state_des, env, sd);
-    double ret = 0.0;
-    int32_t len = 0, docked = 0, ep = 0;
-    unsigned fl = 0;
+    EpisodeAcc acc(0);
 #pragma clang loop unroll(disable)
     for (int64_t t = 0; t < E.max_steps; ++t) {
-        if (__builtin_amdgcn_ballot_w64(ep < E.K) == 0) break;      // wave-uniform: every live lane of the tile is finished
+        if (acc.all_finished(E)) break;            // every live lane of the tile
         float a[4], obs[12], reward;
         unsigned flags;
         bool done;
         expert_action(e.sc, e.st, e.t, P.m, kp, kd, sd, a);
         step_and_maybe_reset<INTEG, PARAMS, RMODE>(e, P, a, A, env, k0 + (uint64_t)t, obs, reward, flags, done, false);
-        if (ep < E.K) {
-            ret += (double)reward;
-            ++len;
-            fl |= flags;
-            docked += (flags & FLAG_DOCKED) ? 1 : 0;
-            if (done) {
-                const int64_t o = (int64_t)ep * A.n + env;
-                QS_ASSERT(o >= 0 && o < (int64_t)E.K * A.n);
-                E.ret[o] = ret;
-                E.len[o] = len;
-                if (E.flags) E.flags[o] = (uint8_t)fl;
-                if (E.docked) E.docked[o] = docked;
-                ret = 0.0; len = 0; docked = 0; fl = 0;
-                ++ep;
-            }
-        }
+        acc.add(E, A.n, env, reward, flags, done);
     }
-    E.finished[env] = ep;
+    acc.finish(E, env);
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-// policy_rollout.hpp -- policy-in-the-loop roll-out in ONE launch:
+// mlp.hpp -- the MLP device functions of the policy-in-the-loop roll-out in ONE launch:
 //   for t in 0..T-1:  a_t = clip(MLP(obs_t), -1, 1);  obs_{t+1}, r_t, done_t = env.step(a_t)
 // i.e. the loop of run_trained_docking_ppo2.py:37-60 (model.predict(obs, deterministic=True); env.step(action))
 // for N envs with the actor of the shipped PPO2 model (shared_fc0 12->128, pi_fc0 128->128, pi 128->4, ReLU).

@@ -15,11 +15,14 @@
 // ONE translation unit (the private-queue code looks the step kernels up by their mangled names in the code object of this
 // very library), kept in pieces that are included below at fixed positions:
 //     quadsim_device.hpp   the per-env device functions (drone step, controller, state2rel, reward, rocRAND draws)
-//     step_kernels.hpp     StepArgs, the step / roll-out / policy / Runner kernels and their launch helpers
-//     rollout_ops.hpp      GAE, flatten, episode statistics            policy_rollout.hpp   the MLP on the matrix cores
+//     rollout_ops.hpp      GAE, flatten, episode statistics            mlp.hpp              the MLP on the matrix cores
+//     step_kernels.hpp     StepArgs, the tile I/O helpers, the env step kernels, the reset / fill / state I/O kernels
+//     layer1_kernels.hpp   drone step, controller, transforms and state2rel on row-major user arrays
+//     policy_kernels.hpp   the actor alone, in a T-step roll-out and over K complete episodes per env (qs_policy_*)
+//     runner_kernels.hpp   PPO2 data collection: the one-wave-per-tile and the role-split Runner kernel (qs_runner_rollout*)
+//     expert_rollout.hpp   the PID expert: one action, T steps, K complete episodes per env (qs_expert_*)
 //     env_groups.hpp       env groups (qs_set_groups)                  private_queue.hpp    private AQL queues (qs_set_queue_mode)
-//     policy_evaluate.hpp  K complete episodes per env of the deterministic actor (qs_policy_evaluate)
-//     expert_rollout.hpp   the PID expert in the loop: T steps / K complete episodes per env (qs_expert_rollout, qs_expert_evaluate)
+//     host_util.hpp        host only: the last-error text (fail), HIP_TRY, roctx ranges, the device guard
 // and here: the handle (QsEnv), its launch / reset / bounce-buffer helpers, and the C ABI.
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
@@ -55,9 +58,10 @@
 #endif
 
 #include "../../include/quadsim.h"
+#include "host_util.hpp"
 #include "quadsim_device.hpp"
 #include "rollout_ops.hpp"
-#include "policy_rollout.hpp"
+#include "mlp.hpp"
 
 using namespace qs;
 
@@ -140,7 +144,9 @@ using namespace qs;
 #endif
 
 #include "step_kernels.hpp"
-#include "policy_evaluate.hpp"
+#include "layer1_kernels.hpp"
+#include "policy_kernels.hpp"
+#include "runner_kernels.hpp"
 #include "expert_rollout.hpp"
 
 #ifdef QS_STAMP
@@ -1240,25 +1246,69 @@ int qs_episode_stats(QsEnv *e, int64_t T, int64_t n, const float *rewards, const
     return QS_OK;
 }
 
+// The weights of a qs_policy_* call are M (exact f32: six arrays) or else blob (the packed split-bf16 image); the static helpers
+// below take both, check the one that is given first of all, and launch its kernel.
+static int check_mlp_args(const char *who, const MlpArgs &M)
+{
+    if (!M.wt1 || !M.b1 || !M.wt2 || !M.b2 || !M.wt3 || !M.b3) return fail(QS_ERR_INVALID, "%s: null weight pointer", who);
+    if ((((uintptr_t)M.wt2) | ((uintptr_t)M.wt3)) & 15u) return fail(QS_ERR_INVALID, "%s: wt2 and wt3 must be 16-byte aligned", who);
+    return QS_OK;
+}
+
+static int check_blob(const char *who, const void *blob)
+{
+    if (!blob) return fail(QS_ERR_INVALID, "%s: null packed_weights", who);
+    if (((uintptr_t)blob & 15) != 0) return fail(QS_ERR_INVALID, "%s: packed weights must be 16-byte aligned", who);
+    return QS_OK;
+}
+
+static int policy_rollout(QsEnv *e, const char *who, int64_t T, const MlpArgs *M, const void *blob, float *obs, float *reward,
+                          uint8_t *done, uint8_t *flags, float *actions)
+{
+    Range rg_(who);
+    if (int rc = M ? check_mlp_args(who, *M) : check_blob(who, blob)) return rc;
+    if (T < 1 || !obs || !reward || !done) return fail(QS_ERR_INVALID, "%s: bad arguments", who);
+    if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "%s: device buffers only", who);
+    if (!e->cfg.auto_reset) return fail(QS_ERR_INVALID, "%s: requires auto_reset", who);
+    if (e->cfg.kind == QS_KIND_HOVERING_V0 || e->per_env_params || e->init || e->cfg.randomise > 1)
+        return fail(QS_ERR_INVALID, "%s: docking-v0/v2 with nominal or rocRAND-initialised resets only", who);
+    StepArgs A = make_args(e);
+    A.T = T; A.obs = obs; A.reward = reward; A.done = done; A.flags = flags;
+    const unsigned grid = grid_tiles(e->n);
+    with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {     // the checks above leave RMODE 0 / 1 without PARAMS
+        if constexpr (!PARAMS && RMODE < 2) {
+            if (blob) hipLaunchKernelGGL((k_policy_rollout_fast<INTEG, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, (const uint4 *)blob, actions);
+            else hipLaunchKernelGGL((k_policy_rollout<INTEG, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, *M, actions);
+        }
+    });
+    HIP_TRY(hipGetLastError());
+    return QS_OK;
+}
+
 int qs_policy_rollout(QsEnv *e, int64_t T, const float *wt1, const float *b1, const float *wt2, const float *b2,
                       const float *wt3, const float *b3, float *obs, float *reward, uint8_t *done, uint8_t *flags, float *actions)
 {
-    Range rg_("qs_policy_rollout");
     CHECK_ENV(e);
-    if (T < 1 || !wt1 || !b1 || !wt2 || !b2 || !wt3 || !b3 || !obs || !reward || !done)
-        return fail(QS_ERR_INVALID, "qs_policy_rollout: bad arguments");
-    if ((((uintptr_t)wt2) | ((uintptr_t)wt3)) & 15u) return fail(QS_ERR_INVALID, "qs_policy_rollout: wt2 and wt3 must be 16-byte aligned");
-    if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "qs_policy_rollout: device buffers only");
-    if (!e->cfg.auto_reset) return fail(QS_ERR_INVALID, "qs_policy_rollout: requires auto_reset");
-    if (e->cfg.kind == QS_KIND_HOVERING_V0 || e->per_env_params || e->init || e->cfg.randomise > 1)
-        return fail(QS_ERR_INVALID, "qs_policy_rollout: docking-v0/v2 with nominal or rocRAND-initialised resets only");
-    StepArgs A = make_args(e);
-    A.T = T; A.obs = obs; A.reward = reward; A.done = done; A.flags = flags;
-    MlpArgs M{wt1, b1, wt2, b2, wt3, b3};
-    const unsigned grid = grid_tiles(e->n);
-    with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {     // the checks above leave RMODE 0 / 1 without PARAMS
-        if constexpr (!PARAMS && RMODE < 2) hipLaunchKernelGGL((k_policy_rollout<INTEG, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, M, actions);
-    });
+    const MlpArgs M{wt1, b1, wt2, b2, wt3, b3};
+    return policy_rollout(e, "qs_policy_rollout", T, &M, nullptr, obs, reward, done, flags, actions);
+}
+
+int qs_policy_rollout_fast(QsEnv *e, int64_t T, const void *packed_weights, float *obs, float *reward, uint8_t *done,
+                           uint8_t *flags, float *actions)
+{
+    CHECK_ENV(e);
+    return policy_rollout(e, "qs_policy_rollout_fast", T, nullptr, packed_weights, obs, reward, done, flags, actions);
+}
+
+static int policy_forward(QsEnv *e, const char *who, int64_t n, const MlpArgs *M, const void *blob, const float *obs, float *actions)
+{
+    Range rg_(who);
+    if (int rc = M ? check_mlp_args(who, *M) : check_blob(who, blob)) return rc;
+    if (n < 1 || !obs || !actions) return fail(QS_ERR_INVALID, "%s: bad arguments", who);
+    if ((((uintptr_t)obs) | ((uintptr_t)actions)) & 15u) return fail(QS_ERR_INVALID, "%s: obs and actions must be 16-byte aligned", who);
+    if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "%s: device buffers only", who);
+    if (blob) hipLaunchKernelGGL(k_policy_forward_fast, dim3(grid_tiles(n)), dim3(kBlock), 0, e->stream, (const uint4 *)blob, obs, actions, n);
+    else hipLaunchKernelGGL(k_policy_forward, dim3(grid_tiles(n)), dim3(kBlock), 0, e->stream, *M, obs, actions, n);
     HIP_TRY(hipGetLastError());
     return QS_OK;
 }
@@ -1266,60 +1316,24 @@ int qs_policy_rollout(QsEnv *e, int64_t T, const float *wt1, const float *b1, co
 int qs_policy_forward(QsEnv *e, int64_t n, const float *wt1, const float *b1, const float *wt2, const float *b2, const float *wt3,
                       const float *b3, const float *obs, float *actions)
 {
-    Range rg_("qs_policy_forward");
     CHECK_ENV(e);
-    if (n < 1 || !wt1 || !b1 || !wt2 || !b2 || !wt3 || !b3 || !obs || !actions) return fail(QS_ERR_INVALID, "qs_policy_forward: bad arguments");
-    if ((((uintptr_t)wt2) | ((uintptr_t)wt3) | ((uintptr_t)obs) | ((uintptr_t)actions)) & 15u)
-        return fail(QS_ERR_INVALID, "qs_policy_forward: wt2, wt3, obs and actions must be 16-byte aligned");
-    if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "qs_policy_forward: device buffers only");
-    MlpArgs M{wt1, b1, wt2, b2, wt3, b3};
-    hipLaunchKernelGGL(k_policy_forward, dim3(grid_tiles(n)), dim3(kBlock), 0, e->stream, M, obs, actions, n);
-    HIP_TRY(hipGetLastError());
-    return QS_OK;
+    const MlpArgs M{wt1, b1, wt2, b2, wt3, b3};
+    return policy_forward(e, "qs_policy_forward", n, &M, nullptr, obs, actions);
 }
 
 int qs_policy_forward_fast(QsEnv *e, int64_t n, const void *packed_weights, const float *obs, float *actions)
 {
-    Range rg_("qs_policy_forward_fast");
     CHECK_ENV(e);
-    if (n < 1 || !packed_weights || !obs || !actions) return fail(QS_ERR_INVALID, "qs_policy_forward_fast: bad arguments");
-    if ((((uintptr_t)packed_weights) | ((uintptr_t)obs) | ((uintptr_t)actions)) & 15u)
-        return fail(QS_ERR_INVALID, "qs_policy_forward_fast: packed_weights, obs and actions must be 16-byte aligned");
-    if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "qs_policy_forward_fast: device buffers only");
-    hipLaunchKernelGGL(k_policy_forward_fast, dim3(grid_tiles(n)), dim3(kBlock), 0, e->stream, (const uint4 *)packed_weights, obs, actions, n);
-    HIP_TRY(hipGetLastError());
-    return QS_OK;
-}
-
-int qs_policy_rollout_fast(QsEnv *e, int64_t T, const void *packed_weights, float *obs, float *reward, uint8_t *done,
-                           uint8_t *flags, float *actions)
-{
-    Range rg_("qs_policy_rollout_fast");
-    CHECK_ENV(e);
-    if (T < 1 || !packed_weights || !obs || !reward || !done) return fail(QS_ERR_INVALID, "qs_policy_rollout_fast: bad arguments");
-    if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "qs_policy_rollout_fast: device buffers only");
-    if (!e->cfg.auto_reset) return fail(QS_ERR_INVALID, "qs_policy_rollout_fast: requires auto_reset");
-    if (e->cfg.kind == QS_KIND_HOVERING_V0 || e->per_env_params || e->init || e->cfg.randomise > 1)
-        return fail(QS_ERR_INVALID, "qs_policy_rollout_fast: docking-v0/v2 with nominal or rocRAND-initialised resets only");
-    if (((uintptr_t)packed_weights & 15) != 0) return fail(QS_ERR_INVALID, "qs_policy_rollout_fast: packed weights must be 16-byte aligned");
-    StepArgs A = make_args(e);
-    A.T = T; A.obs = obs; A.reward = reward; A.done = done; A.flags = flags;
-    const uint4 *blob = (const uint4 *)packed_weights;
-    const unsigned grid = grid_tiles(e->n);
-    with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {     // the checks above leave RMODE 0 / 1 without PARAMS
-        if constexpr (!PARAMS && RMODE < 2) hipLaunchKernelGGL((k_policy_rollout_fast<INTEG, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, blob, actions);
-    });
-    HIP_TRY(hipGetLastError());
-    return QS_OK;
+    return policy_forward(e, "qs_policy_forward_fast", n, nullptr, packed_weights, obs, actions);
 }
 
 int qs_policy_rollout_fast_blob_bytes(void) { return kFastBlobBytes; }
 
-// qs_policy_evaluate / _fast: M (exact f32) or blob (split bf16), exactly one of them
 static int policy_evaluate(QsEnv *e, const char *who, int32_t episodes, int64_t max_steps, const MlpArgs *M, const void *blob,
                            double *ep_return, int32_t *ep_length, uint8_t *ep_flags, int32_t *ep_docked, int32_t *finished)
 {
     Range rg_(who);
+    if (int rc = M ? check_mlp_args(who, *M) : check_blob(who, blob)) return rc;
     if (episodes < 1) return fail(QS_ERR_INVALID, "%s: episodes must be >= 1", who);
     if (max_steps < 1) return fail(QS_ERR_INVALID, "%s: max_steps must be >= 1", who);
     if (!ep_return || !ep_length || !finished) return fail(QS_ERR_INVALID, "%s: ep_return, ep_length and finished are required", who);
@@ -1332,7 +1346,8 @@ static int policy_evaluate(QsEnv *e, const char *who, int32_t episodes, int64_t 
     EvalArgs E{ep_return, ep_length, ep_flags, ep_docked, finished, max_steps, episodes};
     const unsigned grid = grid_tiles(e->n);
     with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {     // as launch_env_on
-        eval_launch<INTEG, PARAMS, RMODE>(e->stream, grid, A, M, (const uint4 *)blob, E);
+        if (blob) hipLaunchKernelGGL((k_policy_evaluate_fast<INTEG, PARAMS, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, (const uint4 *)blob, E);
+        else hipLaunchKernelGGL((k_policy_evaluate<INTEG, PARAMS, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, *M, E);
     });
     HIP_TRY(hipGetLastError());
     return QS_OK;
@@ -1343,8 +1358,6 @@ int qs_policy_evaluate(QsEnv *e, int32_t episodes, int64_t max_steps, const floa
                        uint8_t *ep_flags, int32_t *ep_docked, int32_t *finished)
 {
     CHECK_ENV(e);
-    if (!wt1 || !b1 || !wt2 || !b2 || !wt3 || !b3) return fail(QS_ERR_INVALID, "qs_policy_evaluate: null weight pointer");
-    if ((((uintptr_t)wt2) | ((uintptr_t)wt3)) & 15u) return fail(QS_ERR_INVALID, "qs_policy_evaluate: wt2 and wt3 must be 16-byte aligned");
     const MlpArgs M{wt1, b1, wt2, b2, wt3, b3};
     return policy_evaluate(e, "qs_policy_evaluate", episodes, max_steps, &M, nullptr, ep_return, ep_length, ep_flags, ep_docked, finished);
 }
@@ -1353,8 +1366,6 @@ int qs_policy_evaluate_fast(QsEnv *e, int32_t episodes, int64_t max_steps, const
                             int32_t *ep_length, uint8_t *ep_flags, int32_t *ep_docked, int32_t *finished)
 {
     CHECK_ENV(e);
-    if (!packed_weights) return fail(QS_ERR_INVALID, "qs_policy_evaluate_fast: null packed_weights");
-    if (((uintptr_t)packed_weights & 15) != 0) return fail(QS_ERR_INVALID, "qs_policy_evaluate_fast: packed weights must be 16-byte aligned");
     return policy_evaluate(e, "qs_policy_evaluate_fast", episodes, max_steps, nullptr, packed_weights, ep_return, ep_length, ep_flags,
                            ep_docked, finished);
 }

@@ -1,4 +1,4 @@
-// step_kernels.hpp -- StepArgs, the step / roll-out / policy / Runner kernels and their launch helpers
+// step_kernels.hpp -- StepArgs, the tile / obs / counter I/O helpers, the env step kernels, the reset / fill / state I/O kernels
 // A fragment of quadsim_hip.hip (ONE translation unit: the kernels' mangled names, which the private-queue code resolves
 // in the code object, live in that unit's anonymous namespace); included there at a fixed position, nowhere else.
 #pragma once
@@ -120,6 +120,17 @@ __device__ __forceinline__ void store_par(float *__restrict__ par, int64_t tile,
 {
     float *b = par + tile * (int64_t)(kParWords * kTile) + lane;
     b[0] = P.m; b[kTile] = P.Ixx; b[2 * kTile] = P.Iyy; b[3 * kTile] = P.Izz;
+}
+
+// the wave prologue of a kernel that gives every wave of its kBlock-thread workgroups one tile of a whole-handle launch:
+// this lane, its tile, its env, and whether that env exists (env < n)
+struct TileLane { int lane; int64_t tile, env; bool active; };
+__device__ __forceinline__ TileLane tile_lane(int64_t n)
+{
+    const int lane = threadIdx.x & (kTile - 1);
+    const int64_t tile = (int64_t)blockIdx.x * (kBlock / kTile) + (threadIdx.x >> 6);
+    const int64_t env = tile * kTile + lane;
+    return {lane, tile, env, env < n};
 }
 
 __device__ __forceinline__ void store_obs(float *__restrict__ obs, int64_t env, const float o[12])
@@ -972,576 +983,6 @@ __global__ __launch_bounds__(3 * kTile) void k_env_split(StepArgs A)
     }
 }
 
-// LDS image of the f32 actor (policy_lds_floats()): W2^T | W3^T (16-row tile) | W1^T | b1 | b2 | b3 (16) | per-wave obs / action staging
-struct MlpLds {
-    float *W2, *W3, *W1, *B1, *B2, *B3, *ObsAll, *ActAll;
-};
-__device__ __forceinline__ MlpLds mlp_lds_layout(float *lds)
-{
-    MlpLds L;
-    L.W2 = lds;
-    L.W3 = L.W2 + kHid * kLdW;
-    L.W1 = L.W3 + 16 * kLdW;
-    L.B1 = L.W1 + kHid * kLdW1;
-    L.B2 = L.B1 + kHid;
-    L.B3 = L.B2 + kHid;
-    L.ObsAll = L.B3 + 16;
-    L.ActAll = L.ObsAll + 4 * (12 * 64);
-    return L;
-}
-// weights -> LDS (W3^T rows 4..15 and b3[4..15] are zero padding of the 16-row MFMA tile), by the 256 threads of a workgroup.
-// Every request of a thread goes out before the first LDS write waits for one: a copy loop of load / wait / write pairs costs a
-// launch with T = 1 (one step per launch, VecDockingEnv.step_policy) one L2 round trip per iteration
-__device__ __forceinline__ void mlp_stage_weights(const MlpArgs &M, const MlpLds &L)
-{
-    static_assert(kHid == 128 && kBlock == 256 && kLdW % 4 == 0, "staging layout");
-    const float4 *w2v = reinterpret_cast<const float4 *>(M.wt2);
-    float4 v2[16], v3[2];
-    float v1[6];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v2[j] = w2v[j * kBlock + threadIdx.x];                       // 4 096 float4: row i4 >> 5
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int i4 = j * kBlock + threadIdx.x;                                              // 512 float4 of the padded tile
-        v3[j] = (i4 >> 5) < 4 ? reinterpret_cast<const float4 *>(M.wt3)[i4] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-#pragma unroll
-    for (int j = 0; j < 6; ++j) v1[j] = M.wt1[j * kBlock + threadIdx.x];                      // 1 536 floats
-    const float vb1 = threadIdx.x < kHid ? M.b1[threadIdx.x] : 0.0f, vb2 = threadIdx.x < kHid ? M.b2[threadIdx.x] : 0.0f;
-    const float vb3 = threadIdx.x < 4 ? M.b3[threadIdx.x] : 0.0f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int i4 = j * kBlock + threadIdx.x;
-        *reinterpret_cast<float4 *>(L.W2 + (i4 >> 5) * kLdW + (i4 & 31) * 4) = v2[j];
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int i4 = j * kBlock + threadIdx.x;
-        *reinterpret_cast<float4 *>(L.W3 + (i4 >> 5) * kLdW + (i4 & 31) * 4) = v3[j];
-    }
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const int i = j * kBlock + threadIdx.x;
-        L.W1[(i / 12) * kLdW1 + (i % 12)] = v1[j];
-    }
-    if (threadIdx.x < kHid) { L.B1[threadIdx.x] = vb1; L.B2[threadIdx.x] = vb2; }
-    if (threadIdx.x < 16) L.B3[threadIdx.x] = vb3;
-}
-// the split-bf16 weight image (host-packed, kFastBlobBytes) verbatim into LDS: all requests first, then the LDS writes
-__device__ __forceinline__ void mlp_stage_blob(const uint4 *__restrict__ blob, char *lds)
-{
-    constexpr int kN16 = kFastBlobBytes / 16, kPer = (kN16 + kBlock - 1) / kBlock;
-    uint4 v[kPer];
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-        const int i = j * kBlock + threadIdx.x;
-        v[j] = i < kN16 ? blob[i] : make_uint4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-        const int i = j * kBlock + threadIdx.x;
-        if (i < kN16) reinterpret_cast<uint4 *>(lds)[i] = v[j];
-    }
-}
-
-// The actor alone: actions [n,4] = clip(MLP(obs [n,12])) on the matrix cores -- model.predict(obs, deterministic=True) of
-// run_trained_docking_ppo2.py:41 for n rows, for loops that need the env step as a call of its own (terminal observations,
-// infos).  One wave per 64 rows; the same mlp_actor as the fused kernels, hence the same bits for the same observations.
-__global__ __launch_bounds__(kBlock, 1) void k_policy_forward(MlpArgs M, const float *__restrict__ obs, float *__restrict__ actions, int64_t n)
-{
-    __shared__ __attribute__((aligned(16))) float lds[policy_lds_floats()];
-    const MlpLds L = mlp_lds_layout(lds);
-    mlp_stage_weights(M, L);
-    __syncthreads();
-    const int lane = threadIdx.x & (kTile - 1), w = threadIdx.x >> 6;
-    const int64_t row = ((int64_t)blockIdx.x * (kBlock / kTile) + w) * kTile + lane;
-    float o[12], a[4];
-    if (row < n) {
-        const float4 *p = reinterpret_cast<const float4 *>(obs + row * 12);
-        const float4 v0 = p[0], v1 = p[1], v2 = p[2];
-        o[0] = v0.x; o[1] = v0.y; o[2] = v0.z; o[3] = v0.w; o[4] = v1.x; o[5] = v1.y; o[6] = v1.z; o[7] = v1.w;
-        o[8] = v2.x; o[9] = v2.y; o[10] = v2.z; o[11] = v2.w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) o[i] = 0.0f;          // MFMA needs the whole wave
-    }
-    mlp_actor(o, a, L.W1, L.B1, L.W2, L.B2, L.W3, L.B3, L.ObsAll + w * (12 * 64), L.ActAll + w * (64 * 4), lane);
-    if (row < n) reinterpret_cast<float4 *>(actions)[row] = make_float4(a[0], a[1], a[2], a[3]);
-}
-
-__global__ __launch_bounds__(kBlock, 1) void k_policy_forward_fast(const uint4 *__restrict__ blob, const float *__restrict__ obs,
-                                                                   float *__restrict__ actions, int64_t n)
-{
-    __shared__ __attribute__((aligned(16))) char lds[kFastBlobBytes + 4 * (12 * 64 + 64 * 4) * 4];
-    mlp_stage_blob(blob, lds);
-    __syncthreads();
-    const int lane = threadIdx.x & (kTile - 1), w = threadIdx.x >> 6;
-    const int64_t row = ((int64_t)blockIdx.x * (kBlock / kTile) + w) * kTile + lane;
-    float *stage = reinterpret_cast<float *>(lds + kFastBlobBytes);
-    float o[12], a[4];
-    if (row < n) {
-        const float4 *p = reinterpret_cast<const float4 *>(obs + row * 12);
-        const float4 v0 = p[0], v1 = p[1], v2 = p[2];
-        o[0] = v0.x; o[1] = v0.y; o[2] = v0.z; o[3] = v0.w; o[4] = v1.x; o[5] = v1.y; o[6] = v1.z; o[7] = v1.w;
-        o[8] = v2.x; o[9] = v2.y; o[10] = v2.z; o[11] = v2.w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) o[i] = 0.0f;
-    }
-    mlp_actor_fast(o, a, lds, stage + w * (12 * 64), stage + 4 * (12 * 64) + w * (64 * 4), lane);
-    if (row < n) reinterpret_cast<float4 *>(actions)[row] = make_float4(a[0], a[1], a[2], a[3]);
-}
-
-// Policy-in-the-loop roll-out: T steps of  a = clip(MLP(obs));  obs, r, done = env.step(a)  in one launch
-// (run_trained_docking_ppo2.py:37-60 for N envs).  The env step = the device code of k_env; obs_0 is derived from the stored
-// state (an observation is always state2rel of the state).  The step loop of one wave; actor(obs, a, lane) = the kernel's MLP.
-template <int INTEG, int RMODE, class Actor>
-__device__ __forceinline__ void policy_rollout_steps(const StepArgs &A, float *__restrict__ actions_out, Actor &&actor)
-{
-    const int lane = threadIdx.x & (kTile - 1);
-    const int64_t tile = (int64_t)blockIdx.x * (kBlock / kTile) + (threadIdx.x >> 6);
-    const int64_t env = tile * kTile + lane;
-    const bool active = env < A.n;
-    Env e;
-    load_env_or_nominal(A, tile, lane, active, e);
-    Par P = A.par_nom;
-    const uint64_t k0 = active ? step_counter_begin(A, tile) : 0;
-    float obs[12];
-    rel_obs(e.sc, e.st, obs);
-#pragma clang loop unroll(disable)
-    for (int64_t t = 0; t < A.T; ++t) {
-        float a[4];
-        actor(obs, a, lane);
-        float reward;
-        unsigned flags;
-        bool done;
-        step_and_maybe_reset<INTEG, false, RMODE>(e, P, a, A, active ? env : 0, k0 + (uint64_t)t, obs, reward, flags, done, false);
-        if (active) {
-            const int64_t o = t * A.n + env;
-            store_obs(A.obs, o, obs);
-            A.reward[o] = reward;
-            A.done[o] = done ? 1 : 0;
-            if (A.flags) A.flags[o] = (uint8_t)flags;
-            if (actions_out) reinterpret_cast<float4 *>(actions_out)[o] = make_float4(a[0], a[1], a[2], a[3]);
-        }
-    }
-    if (active) { store_env(A.st, tile, lane, e); step_counter_end(A, tile, lane, k0); }
-}
-
-// the actor on exact-f32 MFMA (policy_rollout.hpp)
-template <int INTEG, int RMODE>
-__global__ __launch_bounds__(kBlock, 1) void k_policy_rollout(StepArgs A, MlpArgs M, float *__restrict__ actions_out)
-{
-    __shared__ __attribute__((aligned(16))) float lds[policy_lds_floats()];
-    const MlpLds L = mlp_lds_layout(lds);
-    mlp_stage_weights(M, L);
-    __syncthreads();
-    const int w = threadIdx.x >> 6;
-    float *const sObs = L.ObsAll + w * (12 * 64), *const sAct = L.ActAll + w * (64 * 4);
-    policy_rollout_steps<INTEG, RMODE>(A, actions_out, [&](const float o[12], float a[4], int lane) {
-        mlp_actor(o, a, L.W1, L.B1, L.W2, L.B2, L.W3, L.B3, sObs, sAct, lane);
-    });
-}
-
-// the actor on the bf16 matrix rate and split (hi + lo) operands: policy_rollout.hpp, "Fast actor".  `blob` = the host-packed
-// weight image (kFastBlobBytes), copied verbatim into LDS.
-template <int INTEG, int RMODE>
-__global__ __launch_bounds__(kBlock, 1) void k_policy_rollout_fast(StepArgs A, const uint4 *__restrict__ blob, float *__restrict__ actions_out)
-{
-    __shared__ __attribute__((aligned(16))) char lds[kFastBlobBytes + 4 * (12 * 64 + 64 * 4) * 4];
-    mlp_stage_blob(blob, lds);
-    __syncthreads();
-    const int w = threadIdx.x >> 6;
-    float *const stage = reinterpret_cast<float *>(lds + kFastBlobBytes);
-    float *const sObs = stage + w * (12 * 64), *const sAct = stage + 4 * (12 * 64) + w * (64 * 4);
-    policy_rollout_steps<INTEG, RMODE>(A, actions_out, [&](const float o[12], float a[4], int lane) {
-        mlp_actor_fast(o, a, lds, sObs, sAct, lane);
-    });
-}
-
-// PPO2 data collection in one launch: the Runner loop of rl_baselines/ppo2/ppo2.py:472-499 (+ last_values, :506) for
-// N envs and T = n_steps.  Per step: mb_obs <- obs; (mean, value) <- MLP heads on exact-f32 MFMA; action = mean +
-// std * N(0,1) (rocRAND Philox + Box-Muller, or caller-supplied noise); neglogp of the diagonal Gaussian
-// (common/distributions.py:406-410); env.step(clip(action, -1, 1)); mb_dones holds the done flags BEFORE the step
-// (ppo2.py:479), rewards / the new done after it.  squash: the fork's tanh variant (common/policies.py:238-242,
-// distributions.py:412-415): env gets tanh(u), neglogp += sum log(1 - tanh(u)^2 + 1e-6), mb_actions keeps u.
-struct RunnerArgs {
-    AcArgs net;
-    float std[4], inv_std[4];
-    float nl_const;            // 0.5 log(2 pi) * 4 + sum(logstd)
-    int squash;
-    const float *noise;        // nullable [T,N,4]
-    const uint8_t *dones_in;   // nullable [N]: done flags carried over from the previous run
-    const uint4 *blob;         // FAST only: packed split-bf16 weight image (kAcFastBlobBytes)
-    float *actions;            // [T,N,4]
-    float *values;             // [T,N]
-    float *neglogp;            // [T,N]
-    float *last_obs;           // nullable [N,12]
-    float *last_values;        // [N]
-    uint8_t *last_dones;       // [N]
-    int env_major;             // mb_obs / mb_actions rows at env*T + t (already swap_and_flatten-ed) instead of t*N + env
-    const float *wtv1, *bv1;   // NET == kNetTowers, exact f32: vf_fc0 [128][12] (out, in), [128] (net.wt1 / b1 = pi_fc0)
-};
-
-// Tower image (policy_rollout.hpp "Tower actor-critic") into LDS by `nthr` threads; -> the per-wave stages.  FAST: the packed
-// blob plus 2 KiB of zeros right after the stages.  Lp / Lv: the exact image with W1 = pi_fc0 / vf_fc0.
-template <bool FAST>
-__device__ __forceinline__ float *load_towers_lds(char *lds_raw, const RunnerArgs &R, int nthr, AcLds &Lp, AcLds &Lv)
-{
-    if constexpr (FAST) {
-        for (int i = threadIdx.x; i < kAcTowFastBlobBytes / 16; i += nthr) reinterpret_cast<uint4 *>(lds_raw)[i] = R.blob[i];
-        for (int i = threadIdx.x; i < 2048 / 16; i += nthr) reinterpret_cast<uint4 *>(lds_raw + kAcTowFastLdsBytes)[i] = make_uint4(0, 0, 0, 0);
-        return reinterpret_cast<float *>(lds_raw + kAcTowFastBlobBytes);
-    } else {
-        float *sW2 = reinterpret_cast<float *>(lds_raw);                // row r: pi_fc1^T row r | vf_fc1^T row r | pad
-        float *sW3p = sW2 + kHid * kLdW2T;
-        float *sW3v = sW3p + 4 * kLdW;
-        float *sW1 = sW3v + kLdW;
-        float *sW1v = sW1 + kHid * kLdW1;
-        float *sB1 = sW1v + kHid * kLdW1;
-        float *sB2p = sB1 + kHid;
-        float *sB2v = sB2p + kHid;
-        float *sB1v = sB2v + kHid;
-        float *sB3 = sB1v + kHid;
-        for (int i = threadIdx.x; i < kHid * kHid; i += nthr) {
-            sW2[(i >> 7) * kLdW2T + (i & 127)] = R.net.wt2[i];
-            sW2[(i >> 7) * kLdW2T + kHid + (i & 127)] = R.net.wtv2[i];
-        }
-        for (int i = threadIdx.x; i < 4 * kHid; i += nthr) sW3p[(i >> 7) * kLdW + (i & 127)] = R.net.wt3[i];
-        for (int i = threadIdx.x; i < kHid; i += nthr) sW3v[i] = R.net.wtv3[i];
-        for (int i = threadIdx.x; i < kHid * 12; i += nthr) {
-            sW1[(i / 12) * kLdW1 + (i % 12)] = R.net.wt1[i];
-            sW1v[(i / 12) * kLdW1 + (i % 12)] = R.wtv1[i];
-        }
-        for (int i = threadIdx.x; i < kHid; i += nthr) { sB1[i] = R.net.b1[i]; sB2p[i] = R.net.b2[i]; sB2v[i] = R.net.bv2[i]; sB1v[i] = R.bv1[i]; }
-        if (threadIdx.x < 16) sB3[threadIdx.x] = threadIdx.x < 4 ? R.net.b3[threadIdx.x] : (threadIdx.x == 4 ? R.net.bv3[0] : 0.0f);
-        Lp = AcLds{sW1, sB1, sW2, sB2p, sW2 + kHid, sB2v, sW3p, sW3v, sB3};
-        Lv = Lp;
-        Lv.W1 = sW1v; Lv.B1 = sB1v;
-        return sB3 + 16;
-    }
-}
-
-// Shared-trunk image (policy_rollout.hpp) into LDS by `nthr` threads; -> the per-wave stages.  FAST: the packed blob verbatim.
-template <bool FAST>
-__device__ __forceinline__ float *load_shared_lds(char *lds_raw, const RunnerArgs &R, int nthr, AcLds &L)
-{
-    if constexpr (FAST) {
-        for (int i = threadIdx.x; i < kAcFastBlobBytes / 16; i += nthr) reinterpret_cast<uint4 *>(lds_raw)[i] = R.blob[i];
-        return reinterpret_cast<float *>(lds_raw + kAcFastBlobBytes);
-    } else {
-        float *sW2p = reinterpret_cast<float *>(lds_raw);
-        float *sW2v = sW2p + kHid * kLdW;
-        float *sW3p = sW2v + kHid * kLdW;
-        float *sW3v = sW3p + 4 * kLdW;
-        float *sW1 = sW3v + kLdW;
-        float *sB1 = sW1 + kHid * kLdW1;
-        float *sB2p = sB1 + kHid;
-        float *sB2v = sB2p + kHid;
-        float *sB3 = sB2v + kHid;
-        for (int i = threadIdx.x; i < kHid * kHid; i += nthr) {
-            sW2p[(i >> 7) * kLdW + (i & 127)] = R.net.wt2[i];
-            sW2v[(i >> 7) * kLdW + (i & 127)] = R.net.wtv2[i];
-        }
-        for (int i = threadIdx.x; i < 4 * kHid; i += nthr) sW3p[(i >> 7) * kLdW + (i & 127)] = R.net.wt3[i];
-        for (int i = threadIdx.x; i < kHid; i += nthr) sW3v[i] = R.net.wtv3[i];
-        for (int i = threadIdx.x; i < kHid * 12; i += nthr) sW1[(i / 12) * kLdW1 + (i % 12)] = R.net.wt1[i];
-        for (int i = threadIdx.x; i < kHid; i += nthr) { sB1[i] = R.net.b1[i]; sB2p[i] = R.net.b2[i]; sB2v[i] = R.net.bv2[i]; }
-        if (threadIdx.x < 16) sB3[threadIdx.x] = threadIdx.x < 4 ? R.net.b3[threadIdx.x] : (threadIdx.x == 4 ? R.net.bv3[0] : 0.0f);
-        L = AcLds{sW1, sB1, sW2p, sB2p, sW2v, sB2v, sW3p, sW3v, sB3};
-        return sB3 + 16;
-    }
-}
-
-// action = mean + std * eps, its neglogp under the diagonal Gaussian, and what the env gets: a = clip(u) or the squashed tanh(u)
-template <class Mean>
-__device__ __forceinline__ void sample_action(const RunnerArgs &R, const Mean &mean, const float eps[4], float u[4], float a[4], float &nl)
-{
-    nl = R.nl_const;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        u[i] = fmaf(R.std[i], eps[i], mean[i]);                   // distributions.py:429
-        const float d = (u[i] - mean[i]) * R.inv_std[i];          // :407
-        nl = fmaf(0.5f * d, d, nl);
-    }
-    if (R.squash) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float sech2;
-            a[i] = q_tanh(u[i], sech2);                           // policies.py:238
-            nl += q_ln(sech2 + 1e-6f);                            // distributions.py:414, 1 - tanh(u)^2 + 1e-6
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) a[i] = fminf(fmaxf(u[i], -1.0f), 1.0f);   // ppo2.py:483
-    }
-}
-
-template <bool FAST, int NET>
-constexpr int runner_lds_bytes()
-{
-    return NET == kNetTowers ? (FAST ? kAcTowFastLdsBytes + 2048 : (int)(tow_lds_floats() * sizeof(float)))
-                             : (FAST ? kAcFastLdsBytes : (int)(ac_lds_floats() * sizeof(float)));
-}
-
-// FAST: the networks on the bf16 matrix rate with split operands (mlp_actor_critic_fast; R.blob = host-packed image)
-// PARAMS: per-env mass / inertia (domain randomisation; RMODE 2 redraws them at every episode start)
-// NET: kNetShared (shared_fc0 trunk, the shipped best_model_v0) or kNetTowers (separate pi / vf towers, mlp_towers)
-template <int INTEG, int RMODE, bool PARAMS, bool FAST, int NET = kNetShared>
-__global__ __launch_bounds__(kBlock, 1) void k_runner_rollout(StepArgs A, RunnerArgs R)
-{
-    constexpr bool TOW = NET == kNetTowers;
-    __shared__ __attribute__((aligned(16))) char lds_raw[runner_lds_bytes<FAST, NET>()];
-    AcLds L{}, Lv{};
-    float *sStage;
-    if constexpr (TOW) sStage = load_towers_lds<FAST>(lds_raw, R, kBlock, L, Lv);
-    else sStage = load_shared_lds<FAST>(lds_raw, R, kBlock, L);
-    __syncthreads();
-
-    const int lane = threadIdx.x & (kTile - 1);
-    const int w = threadIdx.x >> 6;
-    const int64_t tile = (int64_t)blockIdx.x * (kBlock / kTile) + w;
-    const int64_t env = tile * kTile + lane;
-    const bool active = env < A.n;             // MFMA needs the whole wave: idle lanes carry a nominal env, store nothing
-    float *stage = sStage + w * (12 * 64);
-    QS_ASSERT((char *)(stage + 12 * 64) <= lds_raw + sizeof lds_raw);
-    Env e;
-    load_env_or_nominal(A, tile, lane, active, e);
-    Par P = A.par_nom;
-    if (PARAMS && active) P = load_par(A.par, tile, lane);
-    const uint64_t k0 = active ? step_counter_begin(A, tile) : 0;
-    bool done_prev = (active && R.dones_in) ? R.dones_in[env] != 0 : false;
-    float obs[12];
-    rel_obs(e.sc, e.st, obs);
-#pragma clang loop unroll(disable)
-    for (int64_t t = 0; t < A.T; ++t) {
-        const int64_t o = t * A.n + env;
-        QS_ASSERT(!active || (o >= 0 && o < A.T * A.n));
-        // the two wide arrays can be written env-major right away (ppo2.py:522-523 flattens them afterwards anyway): a
-        // lane's consecutive steps then fill consecutive 48- / 16-byte slots of its own row, which the XCD's L2 merges
-        const int64_t ow = R.env_major ? env * A.T + t : o;
-        if (active) { if (R.env_major) store_obs_cached(A.obs, ow, obs); else store_obs(A.obs, ow, obs); }   // mb_obs: the observation the policy acts on
-        float head[5];
-        if constexpr (TOW) mlp_towers<FAST>(obs, head, lds_raw, kAcTowFastLdsBytes, L, Lv, stage, lane);
-        else if (FAST) mlp_actor_critic_fast(obs, head, lds_raw, stage, lane);
-        else mlp_actor_critic(obs, head, L, stage, lane);
-        float eps[4];
-        if (R.noise) {
-            const float4 nv = active ? reinterpret_cast<const float4 *>(R.noise)[o] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            eps[0] = nv.x; eps[1] = nv.y; eps[2] = nv.z; eps[3] = nv.w;
-        } else {
-            random_normal4(A.rc.seed, A.gid0 + (uint64_t)(active ? env : 0), k0 + (uint64_t)t, eps);
-        }
-        float u[4], a[4], nl;
-        sample_action(R, head, eps, u, a, nl);
-        if (active) {
-            reinterpret_cast<float4 *>(R.actions)[ow] = make_float4(u[0], u[1], u[2], u[3]);
-            R.values[o] = head[4];
-            R.neglogp[o] = nl;
-            A.done[o] = done_prev ? 1 : 0;                            // mb_dones: flags before the step (ppo2.py:479)
-        }
-        float reward;
-        unsigned flags;
-        bool done;
-        step_and_maybe_reset<INTEG, PARAMS, RMODE>(e, P, a, A, active ? env : 0, k0 + (uint64_t)t, obs, reward, flags, done, false);
-        done_prev = done;
-        if (active) {
-            A.reward[o] = reward;
-            if (A.flags) A.flags[o] = (uint8_t)flags;
-        }
-    }
-    // last_values = model.value(obs) on the observation after the last step (ppo2.py:506)
-    float head[5];
-    if constexpr (TOW) mlp_towers<FAST>(obs, head, lds_raw, kAcTowFastLdsBytes, L, Lv, stage, lane);
-    else if (FAST) mlp_actor_critic_fast(obs, head, lds_raw, stage, lane);
-    else mlp_actor_critic(obs, head, L, stage, lane);
-    if (active) {
-        R.last_values[env] = head[4];
-        R.last_dones[env] = done_prev ? 1 : 0;
-        if (R.last_obs) store_obs(R.last_obs, env, obs);
-        store_env(A.st, tile, lane, e);
-        if (PARAMS && RMODE == 2) store_par(A.par, tile, lane, P);
-        step_counter_end(A, tile, lane, k0);
-    }
-}
-
-// Role-split variant of the Runner kernel: one workgroup = four tiles = EIGHT waves.  Waves 0..3 ("matrix" role,
-// one per SIMD) only evaluate the networks, waves 4..7 ("env" role, wave 4 + i next to wave i) own the environment state of
-// the same four tiles: sampling, neglogp, env.step, every mb_* store except the values.  Per step and tile
-//   env wave:     obs -> LDS | draw N(0,1), target's half of env.step -> #b -> sample, neglogp, stores, chaser's half, new obs -> LDS -> #a
-//   matrix wave:  -> #a -> layer 1, policy branch, means -> LDS       -> #b -> value branch, store value
-// so the value branch (almost half of a step's MFMAs) and the env step (VALU) run at the same time on the same SIMD, and
-// the matrix wave keeps no environment registers: both roles fit 256 registers, two waves per SIMD.  The means travel
-// through the tile's obs stage (the matrix wave has its observations in registers by then), the values through a
-// buffer private to the matrix wave.  Every wave passes the same 2 T + 1 workgroup barriers.  FAST as in k_runner_rollout;
-// the heads are the same instruction sequences on the same operands as there, so the two kernels agree bit for bit.
-// NET == kNetTowers: the matrix wave runs pi layer 1 -> policy branch -> vf layer 1 (the stage still holds the observations)
-// -> means to LDS -> #b -> value branch; the values reach their lanes by ds_bpermute (no value buffer: see the tower image).
-template <int INTEG, int RMODE, bool PARAMS, bool FAST, int NET = kNetShared>
-__global__ __launch_bounds__(2 * kBlock, 1) void k_runner_split(StepArgs A, RunnerArgs R)
-{
-    constexpr bool TOW = NET == kNetTowers;
-    constexpr int kHeadBytes = FAST ? kAcFastLdsBytes : (int)(ac_lds_floats() * sizeof(float));     // weights + 4 obs stages
-    constexpr int kZeros = TOW ? kAcTowFastLdsBytes : kHeadBytes + 4 * kTile * 4;                   // FAST: 2 KiB of zeros
-    __shared__ __attribute__((aligned(16))) char lds_raw[TOW ? runner_lds_bytes<FAST, NET>() : kZeros + (FAST ? 2048 : 0)];
-    AcLds L{}, Lv{};
-    float *sStage;
-    if constexpr (TOW) sStage = load_towers_lds<FAST>(lds_raw, R, 2 * kBlock, L, Lv);
-    else sStage = load_shared_lds<FAST>(lds_raw, R, 2 * kBlock, L);
-    if (!TOW && FAST && threadIdx.x < 128) reinterpret_cast<uint4 *>(lds_raw + kZeros)[threadIdx.x] = make_uint4(0, 0, 0, 0);
-    __syncthreads();
-    const int lane = threadIdx.x & (kTile - 1);
-    const int w = (threadIdx.x >> 6) & 3;
-    const bool matrix_role = threadIdx.x < kBlock;
-    const int64_t tile = (int64_t)blockIdx.x * (kBlock / kTile) + w;
-    const int64_t env = tile * kTile + lane;
-    const bool active = env < A.n;             // MFMA needs the whole wave: idle lanes carry a nominal env, store nothing
-    float *stage = sStage + w * (12 * 64);
-    float *sval = reinterpret_cast<float *>(lds_raw + kHeadBytes) + w * kTile;       // shared trunk only
-    QS_ASSERT((char *)(stage + 12 * 64) <= lds_raw + (TOW ? (int)sizeof lds_raw : kHeadBytes));
-    if (TOW && matrix_role) {
-        const int c = lane & 15, g = lane >> 4;
-        u32x4 bh[FAST ? 4 : 1][4], bl[FAST ? 4 : 1][4];
-        f32x4 h1[FAST ? 1 : 8][4];
-        f32x4 a3[4];
-        QS_PHASE_DECL;
-#pragma clang loop unroll(disable)
-        for (int64_t t = 0; t <= A.T; ++t) {
-            __syncthreads();                                                  // #a: this step's observations are in LDS
-            QS_PHASE(0);
-            if (t < A.T) tow_policy_part<FAST>(lds_raw, kZeros, L, stage, lane, bh, bl, h1, a3);
-            QS_PHASE(1);
-            tow_value_layer1<FAST>(lds_raw, Lv, stage, lane, bh, bl, h1);   // before the means overwrite the observations
-            if (t < A.T) {
-                if (g == 0) {
-#pragma unroll
-                    for (int et = 0; et < 4; ++et) *reinterpret_cast<f32x4 *>(stage + (16 * et + c) * 8) = a3[et];
-                }
-                QS_PHASE(2);
-                __syncthreads();                                              // #b: the means are in LDS
-                QS_PHASE(3);
-            }
-            tow_value_branch<FAST>(lds_raw, kZeros, Lv, bh, bl, h1, lane, a3);
-            QS_PHASE(4);
-            const float v = value_to_owner(a3, lane);
-            if (active) {
-                float *vout = t < A.T ? R.values + t * A.n : R.last_values;   // last: model.value(obs) after the last step (ppo2.py:506)
-                vout[env] = v;
-            }
-            QS_PHASE(5);
-        }
-        QS_PHASE_FLUSH(0);
-    } else if (matrix_role) {
-        const int c = lane & 15, g = lane >> 4;
-        // layer-1 result = the B operands of both 128 x 128 branches, 128 registers either way
-        u32x4 bh[FAST ? 4 : 1][4], bl[FAST ? 4 : 1][4];
-        f32x4 h1[FAST ? 1 : 8][4];
-        f32x4 a3[4];
-        QS_PHASE_DECL;
-#pragma clang loop unroll(disable)
-        for (int64_t t = 0; t <= A.T; ++t) {
-            __syncthreads();                                                  // #a: this step's observations are in LDS
-            QS_PHASE(0);
-            if constexpr (FAST) ac_fast_layer1(lds_raw, stage, lane, bh, bl);
-            else ac_exact_layer1(L, stage, lane, h1);
-            QS_PHASE(1);
-            if (t < A.T) {
-                if constexpr (FAST) ac_fast_branch<0>(lds_raw, kZeros, bh, bl, lane, a3);
-                else ac_exact_branch<0>(L, h1, lane, a3);
-                if (g == 0) {
-#pragma unroll
-                    for (int et = 0; et < 4; ++et) *reinterpret_cast<f32x4 *>(stage + (16 * et + c) * 8) = a3[et];
-                }
-                QS_PHASE(2);
-                __syncthreads();                                              // #b: the means are in LDS
-                QS_PHASE(3);
-            }
-            if constexpr (FAST) ac_fast_branch<1>(lds_raw, kZeros, bh, bl, lane, a3);
-            else ac_exact_branch<1>(L, h1, lane, a3);
-            QS_PHASE(4);
-            if (g == 1) {
-#pragma unroll
-                for (int et = 0; et < 4; ++et) sval[16 * et + c] = a3[et][0];
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const float v = sval[lane];
-            __builtin_amdgcn_wave_barrier();
-            if (active) {
-                float *vout = t < A.T ? R.values + t * A.n : R.last_values;   // last: model.value(obs) after the last step (ppo2.py:506)
-                vout[env] = v;
-            }
-            QS_PHASE(5);
-        }
-        QS_PHASE_FLUSH(0);
-    } else {
-        Env e;
-        load_env_or_nominal(A, tile, lane, active, e);
-        Par P = A.par_nom;
-        if (PARAMS && active) P = load_par(A.par, tile, lane);
-        const uint64_t k0 = active ? step_counter_begin(A, tile) : 0;
-        bool done_prev = (active && R.dones_in) ? R.dones_in[env] != 0 : false;
-        float obs[12];
-        rel_obs(e.sc, e.st, obs);
-#pragma unroll
-        for (int k = 0; k < 12; ++k) stage[k * 64 + lane] = obs[k];
-        QS_PHASE_DECL;
-#pragma clang loop unroll(disable)
-        for (int64_t t = 0; t < A.T; ++t) {
-            const int64_t o = t * A.n + env;
-            QS_ASSERT(!active || (o >= 0 && o < A.T * A.n));
-            const int64_t ow = R.env_major ? env * A.T + t : o;
-            if (active) { if (R.env_major) store_obs_cached(A.obs, ow, obs); else store_obs(A.obs, ow, obs); }
-            QS_PHASE(0);
-            __syncthreads();                                                  // #a
-            QS_PHASE(1);
-            float eps[4];
-            if (R.noise) {
-                const float4 nv = active ? reinterpret_cast<const float4 *>(R.noise)[o] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                eps[0] = nv.x; eps[1] = nv.y; eps[2] = nv.z; eps[3] = nv.w;
-            } else {
-                random_normal4(A.rc.seed, A.gid0 + (uint64_t)(active ? env : 0), k0 + (uint64_t)t, eps);
-            }
-            // the target's half of env.step does not need the action: it runs here, next to the policy branch
-            const bool lim_t = env_step_target<INTEG>(e, P, A.C);
-            QS_PHASE(2);
-            __syncthreads();                                                  // #b
-            QS_PHASE(3);
-            const f32x4 mean = *reinterpret_cast<const f32x4 *>(stage + lane * 8);
-            float u[4], a[4], nl;
-            sample_action(R, mean, eps, u, a, nl);
-            if (active) {
-                reinterpret_cast<float4 *>(R.actions)[ow] = make_float4(u[0], u[1], u[2], u[3]);
-                R.neglogp[o] = nl;
-                A.done[o] = done_prev ? 1 : 0;                                // mb_dones: flags before the step (ppo2.py:479)
-            }
-            QS_PHASE(4);
-            float reward;
-            unsigned flags;
-            bool done;
-            env_step_chaser<INTEG>(e, a, P, A.C, lim_t, obs, reward, flags);
-            maybe_reset<PARAMS, RMODE>(e, P, A, active ? env : 0, k0 + (uint64_t)t, obs, flags, done, false);
-            done_prev = done;
-#pragma unroll
-            for (int k = 0; k < 12; ++k) stage[k * 64 + lane] = obs[k];
-            if (active) {
-                A.reward[o] = reward;
-                if (A.flags) A.flags[o] = (uint8_t)flags;
-            }
-            QS_PHASE(5);
-        }
-        QS_PHASE_FLUSH(1);
-        __syncthreads();                                                      // #a of the value-only pass
-        if (active) {
-            R.last_dones[env] = done_prev ? 1 : 0;
-            if (R.last_obs) store_obs(R.last_obs, env, obs);
-            store_env(A.st, tile, lane, e);
-            if (PARAMS && RMODE == 2) store_par(A.par, tile, lane, P);
-            step_counter_end(A, tile, lane, k0);
-        }
-    }
-}
-
 // hovering-v0 (HoveringEnv.step, hovering_env.py:47-78): T fused steps, one drone per lane.  Uses rows F_SC..
 // (state) and F_UC.. (last limited control) of the tile; obs [T,N,13] = state after the step (or the stored
 // ini_state after an auto-reset, hovering_env.py:80-82).
@@ -1755,188 +1196,6 @@ __global__ __launch_bounds__(kBlock) void k_par_io(float *par, int64_t n, float 
         if (inertia) for (int i = 0; i < 3; ++i) b[(1 + i) * kTile] = inertia[env * 3 + i];
     }
 }
-
-// ---- layer-1 kernels on row-major user arrays ------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_drone_step(int64_t n, float *state, float *u_prev, const float *u,
-                                                       const float *par, uint8_t *limited, Par par_nom, float dt,
-                                                       int integ)
-{
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    float s[13], up[4], uu[4];
-    for (int j = 0; j < 13; ++j) s[j] = state[i * 13 + j];
-    for (int j = 0; j < 4; ++j) { up[j] = u_prev[i * 4 + j]; uu[j] = u[i * 4 + j]; }
-    Par P = par_nom;
-    if (par) { P.m = par[i * 4]; P.Ixx = par[i * 4 + 1]; P.Iyy = par[i * 4 + 2]; P.Izz = par[i * 4 + 3]; }
-    bool over = integ == 0 ? drone_step<0>(s, up, uu, P, dt) : drone_step<1>(s, up, uu, P, dt);
-    for (int j = 0; j < 13; ++j) state[i * 13 + j] = s[j];
-    for (int j = 0; j < 4; ++j) u_prev[i * 4 + j] = up[j];
-    if (limited) limited[i] = over ? 1 : 0;
-}
-
-__global__ __launch_bounds__(kBlock) void k_ctrl(int64_t n, int mode, float *state_des, const float *state,
-                                                 const float *state_last, float mass, float *u_out)
-{
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    float sd[13], s[13], dv[3] = {0.0f, 0.0f, 0.0f}, u[4];
-    for (int j = 0; j < 13; ++j) { sd[j] = state_des[i * 13 + j]; s[j] = state[i * 13 + j]; }
-    if (mode == 1 && state_last) for (int j = 0; j < 3; ++j) dv[j] = s[3 + j] - state_last[i * 13 + 3 + j];
-    target_control(mode, sd, sd + 3, sd + 6, sd[12], s, dv, mass, u);
-    for (int j = 0; j < 4; ++j) { state_des[i * 13 + 6 + j] = sd[6 + j]; u_out[i * 4 + j] = u[j]; }
-    state_des[i * 13 + 10] = 0.0f;   // roll_rate_des,  PIDController.py:101
-    state_des[i * 13 + 11] = 0.0f;   // pitch_rate_des, PIDController.py:102
-}
-
-// PID expert (run_expert_policy.py:49-69, run_expert_record.py:121-136): vel_controller on the chaser towards
-// 0.2 m behind the target, inverse action map (inv(rotor2control) u - mean)/std, not clipped.  sd [13] is the
-// expert's persistent desired state (pos = chaser start, vel = des_vel, [6:12] rewritten by the controller).  First
-// step of an episode (t == 0) keeps the previous des_vel (:58-59).  The one copy of the expert: k_expert_action and the
-// fused kernels of expert_rollout.hpp inline it, so they compute the same bits (-ffp-contract=on).
-__device__ __forceinline__ void expert_action(const float sc[13], const float tp[3], float t, float m, float kp, float kd,
-                                              float sd[13], float act[4])
-{
-    if (t != 0.0f) {
-        sd[3] = kp * (tp[0] - 0.2f - sc[0]) + kd * (-sc[3]);
-        sd[4] = kp * (tp[1] - sc[1]) + kd * (-sc[4]);
-        sd[5] = kp * (tp[2] - sc[2]) + kd * (-sc[5]);
-    }
-    const float dv[3] = {0.0f, 0.0f, 0.0f};        // state_last aliases the current state
-    float u[4];
-    target_control(1, sd, sd + 3, sd + 6, sd[12], sc, dv, m, u);
-    sd[10] = 0.0f; sd[11] = 0.0f;
-    constexpr float a = 1.0f / (2.0f * kL), bq = 1.0f / (4.0f * kLambda);
-    const float f4 = 0.25f * u[0];
-    const float f0 = f4 - a * u[2] + bq * u[3], f1 = f4 + a * u[1] - bq * u[3];
-    const float f2 = f4 + a * u[2] + bq * u[3], f3 = f4 - a * u[1] - bq * u[3];
-    const float inv_mean = q_rcp(0.5f * m * kG);
-    act[0] = f0 * inv_mean - 1.0f; act[1] = f1 * inv_mean - 1.0f; act[2] = f2 * inv_mean - 1.0f; act[3] = f3 * inv_mean - 1.0f;
-}
-
-// qs_expert_action: reads the envs' current chaser / target state straight from the tiles; state_des [N][13]
-template <bool PARAMS>
-__global__ __launch_bounds__(kBlock) void k_expert_action(const float *__restrict__ st, const float *__restrict__ par, int64_t n,
-                                                          float *__restrict__ state_des, float kp, float kd, Par par_nom,
-                                                          float *__restrict__ actions)
-{
-    const int lane = threadIdx.x & (kTile - 1);
-    const int64_t tile = (int64_t)blockIdx.x * (kBlock / kTile) + (threadIdx.x >> 6);
-    const int64_t env = tile * kTile + lane;
-    if (env >= n) return;
-    const float *b = st + tile * (int64_t)(kRecWords * kTile) + lane;
-    float sc[13], tp[3], sd[13];
-    for (int i = 0; i < 13; ++i) sc[i] = b[(F_SC + i) * kTile];
-    for (int i = 0; i < 3; ++i) tp[i] = b[(F_ST + i) * kTile];
-    const float t = b[F_T * kTile];
-    for (int i = 0; i < 13; ++i) sd[i] = state_des[env * 13 + i];
-    Par P = par_nom;
-    if (PARAMS) P = load_par(par, tile, lane);
-    float a[4];
-    expert_action(sc, tp, t, P.m, kp, kd, sd, a);
-    reinterpret_cast<float4 *>(actions)[env] = make_float4(a[0], a[1], a[2], a[3]);
-    for (int i = 3; i < 12; ++i) state_des[env * 13 + i] = sd[i];
-}
-
-// layer 0: utils/transform.py as batch functions.  op 0 quat2euler [n,4]->[n,3] (:94-120), 1 euler2quat [n,3]->[n,4]
-// (:123-136), 2 quat2rot [n,4]->[n,9] (:4-20), 3 rot2euler [n,9]->[n,3] (:23-46)
-__global__ __launch_bounds__(kBlock) void k_transform(int op, int64_t n, const float *in, float *out)
-{
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    if (op == 0) {
-        float q[4] = {in[i * 4], in[i * 4 + 1], in[i * 4 + 2], in[i * 4 + 3]};
-        quat2euler(q, out[i * 3], out[i * 3 + 1], out[i * 3 + 2]);
-    } else if (op == 1) {
-        float q[4];
-        euler2quat(in[i * 3], in[i * 3 + 1], in[i * 3 + 2], q);
-        for (int j = 0; j < 4; ++j) out[i * 4 + j] = q[j];
-    } else if (op == 2) {
-        float q[4] = {in[i * 4], in[i * 4 + 1], in[i * 4 + 2], in[i * 4 + 3]};
-        Rot R = quat2rot(q);
-        const float r[9] = {1.0f, R.r01, R.r02, R.r10, 1.0f, R.r12, R.r20, R.r21, 1.0f};
-        for (int j = 0; j < 9; ++j) out[i * 9 + j] = r[j];
-    } else {
-        const float *R = in + i * 9;
-        const float r12 = R[5];
-        const bool sat = (r12 >= 1.0f) || (r12 < -1.0f);
-        out[i * 3] = q_asin(fminf(fmaxf(r12, -1.0f), 1.0f));
-        out[i * 3 + 1] = sat ? 0.0f : q_atan2(-R[2], R[8]);
-        out[i * 3 + 2] = q_atan2(-R[3], R[4]);
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void k_rel_obs(int64_t n, const float *chaser, const float *target, float *obs)
-{
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    float sc[13], st[13], o[12];
-    for (int j = 0; j < 13; ++j) { sc[j] = chaser[i * 13 + j]; st[j] = target[i * 13 + j]; }
-    rel_obs(sc, st, o);
-    for (int j = 0; j < 12; ++j) obs[i * 12 + j] = o[j];
-}
-
-// ---------------------------------------------------------------------------------------------
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return fail(QS_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-// roctx ranges around the hot entry points (trace readability under rocprofv3 --marker-trace): resolved at run time and
-// only when QS_ROCTX=1, so the library carries no link-time dependency on a profiler library
-struct Roctx {
-    int (*push)(const char *) = nullptr;
-    int (*pop)() = nullptr;
-    bool on = false;
-};
-inline Roctx &roctx()
-{
-    static Roctx r = [] {
-        Roctx x;
-        const char *en = getenv("QS_ROCTX");
-        if (en && atoi(en)) {
-            void *h = dlopen("librocprofiler-sdk-roctx.so", RTLD_NOW | RTLD_GLOBAL);
-            if (!h) h = dlopen("libroctx64.so", RTLD_NOW | RTLD_GLOBAL);
-            if (h) {
-                x.push = (int (*)(const char *))dlsym(h, "roctxRangePushA");
-                x.pop = (int (*)())dlsym(h, "roctxRangePop");
-                x.on = x.push && x.pop;
-            }
-        }
-        return x;
-    }();
-    return r;
-}
-struct Range {
-    bool on;
-    explicit Range(const char *name) : on(roctx().on) { if (on) roctx().push(name); }
-    ~Range() { if (on) roctx().pop(); }
-};
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 inline int64_t tiles_of(int64_t n) { return (n + kTile - 1) / kTile; }
 inline unsigned grid_tiles(int64_t n) { return (unsigned)((tiles_of(n) + (kBlock / kTile) - 1) / (kBlock / kTile)); }

@@ -85,7 +85,7 @@ def _bf16_to_f32(b):
 
 def pack_fast_weights(policy):
     """Weight image of qs_policy_rollout_fast: every weight split into bf16 hi + lo, A-operand fragments stored
-    ready-made in the k-order the accumulator-as-B-operand chaining needs (csrc/policy_rollout.hpp, 'Fast actor')."""
+    ready-made in the k-order the accumulator-as-B-operand chaining needs (csrc/mlp.hpp, 'Fast actor')."""
     w1t = policy.w0.t().contiguous().cpu().numpy()      # [128][12]
     w2t = policy.w1.t().contiguous().cpu().numpy()      # [128][128]
     w3t = policy.w2.t().contiguous().cpu().numpy()      # [4][128]

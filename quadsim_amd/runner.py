@@ -112,7 +112,7 @@ class ActorCriticPolicy:
 
 
 def pack_fast_actor_critic(policy):
-    """Weight image of qs_runner_rollout_fast (csrc/policy_rollout.hpp, 'Fast actor-critic heads'): the two 128x128
+    """Weight image of qs_runner_rollout_fast (csrc/mlp.hpp, 'Fast actor-critic heads'): the two 128x128
     layers and the output rows as ready-made split-bf16 A fragments in the k-order of the accumulator-as-B-operand
     chaining, the first layer and the biases in float32."""
     from .policy import _bf16_bits, _bf16_to_f32

@@ -2,7 +2,7 @@
 no GPU, no torch needed except by the packers).
 
 Every network evaluation on the device runs one of two MFMA paths: exact float32 (mlp_actor / mlp_actor_critic) or split bf16
-("bf16x3": mlp_actor_fast / mlp_actor_critic_fast, csrc/policy_rollout.hpp).  Neither is held to a fixed tolerance here.
+("bf16x3": mlp_actor_fast / mlp_actor_critic_fast, csrc/mlp.hpp).  Neither is held to a fixed tolerance here.
 err_scale() propagates the magnitudes of the summed terms layer by layer,
 
     E_0 = 0,   E_l = |W_l|^T E_{l-1} + (|h_{l-1}| |W_l| + |b_l|),
@@ -225,7 +225,7 @@ def _bf(raw):
 
 
 # ---------------------------------------------------------------------------------------------------- packed-image decoders
-# Fragment layout (csrc/policy_rollout.hpp, 'Fast actor'): element j of lane l (g = l >> 4, c = l & 15) of k-step p of row tile
+# Fragment layout (csrc/mlp.hpp, 'Fast actor'): element j of lane l (g = l >> 4, c = l & 15) of k-step p of row tile
 # t holds W^T[16 t + c][hid(p, g, j)], hid(p, g, j) = 16 (2p + (j >> 2)) + 4g + (j & 3); the first layer of the actor-only image
 # holds input k = 8g + j (zero for k >= 12); the output layer lives in rows c < 4 (zero elsewhere).
 _LANE = np.arange(64)

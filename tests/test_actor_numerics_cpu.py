@@ -156,7 +156,7 @@ def test_hi_lo_images_hold_every_weight(layout):
 
 
 # ---------------------------------------------------------------------------------------------------- mutants fail the bound
-# byte offsets of the images (csrc/policy_rollout.hpp)
+# byte offsets of the images (csrc/mlp.hpp)
 ACTOR_A2, ACTOR_A1, ACTOR_A3, ACTOR_B3 = 0, 65536, 81920, 91136
 AC_A2PI, AC_A2VF, AC_B3 = 0, 65536, 141824
 
