@@ -471,6 +471,46 @@ int qs_expert_rollout(QsEnv *env, int64_t T, float *state_des /* [N,13] in/out *
 int qs_expert_evaluate(QsEnv *env, int32_t episodes, int64_t max_steps, const float *state_des, float kp, float kd,
                        double *ep_return, int32_t *ep_length, uint8_t *ep_flags, int32_t *ep_docked, int32_t *finished);
 
+/* Random-shooting MPC, ONE launch: the planner of MPC-based_RL.py:170-210 (Mpc_Controller.choose_action / compute_cost) for
+ * all N docking envs, with the exact simulator in the place of the script's learned dynamics net.
+ *   Candidates and horizon.  For every env i of the handle and every candidate c in [0, paths): a copy of the env's current
+ *     state (chaser, target, both stored controls, q_des, last_shaping, t) and parameters (the per-env ones if set) takes
+ *     env.step for h = 0 .. horizon-1 with the candidate's actions.  There is no reset inside a horizon, whatever auto_reset
+ *     is.  A candidate stops after its first done step -- done as qs_step reports it: QS_FLAG_OVERLIMIT | QS_FLAG_OVERTIME;
+ *     QS_FLAG_DOCKED is reported in the flags and rewarded but does not end an episode (docking_env.py:155) -- and later steps
+ *     contribute nothing.
+ *   Random keys.  a[c][h] = 2 u - 1 component-wise, u the (0,1] uniforms of the four words of Philox4x32-10 block
+ *     (k << 26) | (c << 10) | h of subsequence (5 << 48) | gid: stream 5 is the planner's, gid = env_id_offset + i, k the
+ *     handle's step counter at the call.  Plans before different steps differ, a plan repeated at the same k is reproducible,
+ *     and candidate c does not depend on `paths`: the candidates of a call with fewer paths are a prefix of those of a call
+ *     with more.
+ *   Score, QS_SHOOT_REWARD.  The float64 sum, in step order, of the float32 step rewards (ep_return of qs_policy_evaluate).
+ *   Score, QS_SHOOT_POSITION.  The reference's cost (:200-208): the float64 sum over h of the float32 value
+ *     -(o0^2 + o1^2 + o2^2) of the observation BEFORE step h; the h = 0 term is the current observation, common to all
+ *     candidates; a candidate that has stopped adds nothing more.  Because an action acts with one step's delay (the drone
+ *     integrates with the control stored by the previous step), the first action cannot influence this score with
+ *     horizon < 3: such calls are allowed and return candidate 0's or an arbitrary tie-broken winner's first action.
+ *   Winner.  The highest score; ties go to the lowest index, so the result does not depend on how candidates are mapped to
+ *     lanes, waves or workgroups.
+ *   Outputs.  actions [N,4]: the first action of the winner; best_score [N], best_index [N], sequence [N,horizon,4] (all of
+ *     the winner's actions) and scores [N,paths] (every candidate's score: the hook for MPPI / CEM weighting) are nullable.
+ *     actions and sequence 16-byte aligned, best_score and scores 8-byte, best_index 4-byte.
+ *   Read-only.  State, parameters, initial states, step counter, q_des and the rollout layout are not modified: the handle
+ *     steps on afterwards as if the call had not been made (the contract of qs_policy_evaluate).
+ *   1 <= paths <= 65536 (need not be a multiple of 64), 1 <= horizon <= 256, step counter < 2^36, else QS_ERR_INVALID.
+ *   docking-v0 / v1 / v2, both integrators, every randomise mode and stored initial states (none is consulted), per-env
+ *   params, auto_reset 0 or 1, device buffers; hovering handles and QS_IO_HOST give QS_ERR_INVALID.  In private-queue mode
+ *   pending queue work is drained first, as by every entry point that is not a step.  The call reads the step counter back
+ *   (one stream synchronisation) before it launches.
+ * Added after QS_VERSION 131 without changing it: callers detect this entry point by symbol (dlsym). */
+enum { QS_SHOOT_REWARD = 0, QS_SHOOT_POSITION = 1 };
+int qs_shooting_plan(QsEnv *env, int32_t horizon, int32_t paths, int32_t objective,
+                     float *actions      /* [N,4]  first action of the best candidate */,
+                     double *best_score  /* nullable [N] */,
+                     int32_t *best_index /* nullable [N] */,
+                     float *sequence     /* nullable [N,horizon,4] the best candidate's actions */,
+                     double *scores      /* nullable [N,paths] every candidate's score */);
+
 /* ---- layer-1 entry points: n independent drones / controllers (n need not equal N) ----------- */
 
 /* Drone.step (dynamics/quadrotor.py:126-144): state [n,13] in/out, u_prev [n,4] in/out (Drone.u),

@@ -35,7 +35,7 @@ constexpr int kParWords = 4;
 constexpr int F_SC = 0, F_ST = 13, F_UC = 26, F_UT = 30, F_QD = 34, F_LS = 38, F_T = 39;
 
 enum : unsigned { FLAG_DOCKED = 1, FLAG_OVERLIMIT = 2, FLAG_OVERTIME = 4, FLAG_CLIM = 8, FLAG_TLIM = 16 };
-enum : uint64_t { STREAM_AUTORESET = 0, STREAM_RESET = 1, STREAM_ACTIONS = 2, STREAM_CTOR = 3, STREAM_POLICY = 4 };
+enum : uint64_t { STREAM_AUTORESET = 0, STREAM_RESET = 1, STREAM_ACTIONS = 2, STREAM_CTOR = 3, STREAM_POLICY = 4, STREAM_PLAN = 5 };
 
 struct Par {
     float m, Ixx, Iyy, Izz;

@@ -148,6 +148,7 @@ using namespace qs;
 #include "policy_kernels.hpp"
 #include "runner_kernels.hpp"
 #include "expert_rollout.hpp"
+#include "shooting.hpp"
 
 #ifdef QS_STAMP
 static unsigned long long *g_host_stamps = nullptr;     // qs_debug_set_stamps: handed to every launch through StepArgs
@@ -1679,6 +1680,41 @@ int qs_expert_evaluate(QsEnv *e, int32_t episodes, int64_t max_steps, const floa
     with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {
         hipLaunchKernelGGL((k_expert_evaluate<INTEG, PARAMS, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, state_des, kp, kd, E);
     });
+    HIP_TRY(hipGetLastError());
+    return QS_OK;
+}
+
+// ---- random-shooting MPC ---------------------------------------------------------------------
+int qs_shooting_plan(QsEnv *e, int32_t horizon, int32_t paths, int32_t objective, float *actions, double *best_score,
+                     int32_t *best_index, float *sequence, double *scores)
+{
+    CHECK_ENV(e);
+    Range rg_("qs_shooting_plan");
+    if (e->cfg.kind == QS_KIND_HOVERING_V0) return fail(QS_ERR_INVALID, "qs_shooting_plan: docking envs only");
+    if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "qs_shooting_plan: device buffers only");
+    if (paths < 1 || paths > 65536) return fail(QS_ERR_INVALID, "qs_shooting_plan: paths must be in [1, 65536], got %d", paths);
+    if (horizon < 1 || horizon > 256) return fail(QS_ERR_INVALID, "qs_shooting_plan: horizon must be in [1, 256], got %d", horizon);
+    if (objective != QS_SHOOT_REWARD && objective != QS_SHOOT_POSITION)
+        return fail(QS_ERR_INVALID, "qs_shooting_plan: unknown objective %d", objective);
+    if (!actions) return fail(QS_ERR_INVALID, "qs_shooting_plan: actions is required");
+    if (e->n > 0x7fffffff) return fail(QS_ERR_INVALID, "qs_shooting_plan: one workgroup per env: at most 2^31 - 1 envs");
+    if (((((uintptr_t)actions) | ((uintptr_t)sequence)) & 15u) || ((((uintptr_t)best_score) | ((uintptr_t)scores)) & 7u)
+        || (((uintptr_t)best_index) & 3u))
+        return fail(QS_ERR_INVALID, "qs_shooting_plan: actions and sequence must be 16-byte aligned, best_score and scores 8-byte, best_index 4-byte");
+    // the candidate keys hold the step counter in 36 bits: (k << 26) | (c << 10) | h
+    unsigned long long k = 0;
+    HIP_TRY(hipMemcpyAsync(&k, e->d_ctr, sizeof k, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (k >> 36) return fail(QS_ERR_INVALID, "qs_shooting_plan: step counter %llu does not fit the 36 bits of the candidate keys", k);
+    const StepArgs A = make_args(e);
+    const PlanArgs X{horizon, paths, objective, actions, best_score, best_index, sequence, scores};
+    const unsigned block = (unsigned)std::min<int64_t>(kBlock, ((int64_t)paths + kTile - 1) / kTile * kTile);
+    const size_t lds = plan_lds_bytes(horizon);
+    const StepVariant v = step_combo(e);
+    if (v.integ == 0 && !v.params) hipLaunchKernelGGL((k_shooting_plan<0, false>), dim3((unsigned)e->n), dim3(block), lds, e->stream, A, X);
+    else if (v.integ == 0) hipLaunchKernelGGL((k_shooting_plan<0, true>), dim3((unsigned)e->n), dim3(block), lds, e->stream, A, X);
+    else if (!v.params) hipLaunchKernelGGL((k_shooting_plan<1, false>), dim3((unsigned)e->n), dim3(block), lds, e->stream, A, X);
+    else hipLaunchKernelGGL((k_shooting_plan<1, true>), dim3((unsigned)e->n), dim3(block), lds, e->stream, A, X);
     HIP_TRY(hipGetLastError());
     return QS_OK;
 }

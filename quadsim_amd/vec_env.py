@@ -473,6 +473,11 @@ class VecDockingEnv:
         self._outputs_ready()
         return a
 
+    def shooting_plan(self, horizon=20, paths=200, objective="reward", return_scores=False, return_sequence=False):
+        """random-shooting MPC from the envs' current states, read-only, one launch (qs_shooting_plan): see quadsim_amd.mpc"""
+        from .mpc import shooting_plan
+        return shooting_plan(self, horizon, paths, objective, return_scores, return_sequence)
+
     def seed(self, seed=None):
         return [seed] * self.num_envs
 
