@@ -16,14 +16,17 @@
 // very library), kept in pieces that are included below at fixed positions:
 //     quadsim_device.hpp   the per-env device functions (drone step, controller, state2rel, reward, rocRAND draws)
 //     rollout_ops.hpp      GAE, flatten, episode statistics            mlp.hpp              the MLP on the matrix cores
+//     kernel_diag.hpp      the in-kernel stamps of the diagnostic builds, the store flavour of the step kernels
 //     step_kernels.hpp     StepArgs, the tile I/O helpers, the env step kernels, the reset / fill / state I/O kernels
 //     layer1_kernels.hpp   drone step, controller, transforms and state2rel on row-major user arrays
 //     policy_kernels.hpp   the actor alone, in a T-step roll-out and over K complete episodes per env (qs_policy_*)
 //     runner_kernels.hpp   PPO2 data collection: the one-wave-per-tile and the role-split Runner kernel (qs_runner_rollout*)
 //     expert_rollout.hpp   the PID expert: one action, T steps, K complete episodes per env (qs_expert_*)
 //     env_groups.hpp       env groups (qs_set_groups)                  private_queue.hpp    private AQL queues (qs_set_queue_mode)
-//     host_util.hpp        host only: the last-error text (fail), HIP_TRY, roctx ranges, the device guard
-// and here: the handle (QsEnv), its launch / reset / bounce-buffer helpers, and the C ABI.
+//     host_util.hpp        host only: the last-error text (fail), HIP_TRY, roctx ranges, the device guard, and UserIO: how every
+//                          entry point hands the caller's buffers to its kernels (in place on a QS_IO_DEVICE handle, through the
+//                          staging buffer and its pinned mirror on a QS_IO_HOST handle)
+// and here: the handle (QsEnv), its launch / reset helpers, and the C ABI.
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
@@ -65,84 +68,7 @@
 
 using namespace qs;
 
-// -DQS_STAMP (diagnostic build, tools/build_stamp.sh): every workgroup of the role-split step kernel records the
-// 100 MHz real-time counter at its phase boundaries into a caller-provided buffer (qs_debug_set_stamps), keyed by
-// (step counter, tile) -- the in-kernel timeline of consecutive launches of the real chain.  Never in the product build.
-#ifdef QS_STAMP
-// The stamp buffer travels in StepArgs (not in a __device__ global): the private-queue launches run a second copy of the code
-// object, loaded through HSA, whose globals HIP's hipMemcpyToSymbol never reaches.
-// stamps stay in registers until the wave's last instruction: a store next to a barrier would be waited for by it
-#define QS_STAMP_DECL unsigned long long stamp_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; (void)stamp_
-// -DQS_STAMP=2 ("light"): only the first and the last stamp of a wave.  The first stays in a register; the last -- taken when
-// all of the wave's stores have been ISSUED, not drained -- is stored together with it by lane 0 (two 8-byte stores, never waited
-// for).  The full build's eight scalar-memory round trips, its load-landed waits and, above all, its flush of eight stores
-// BEHIND the drained wave end (a store-acknowledge latency on every workgroup's tail) cost ~0.7-0.9 us per step: too much for a
-// timeline whose PERIOD is to be compared with the unstamped chain.  Even two stamps per wave cost ~0.4 us per step when every
-// workgroup takes them (each is a scalar-memory round trip at the wave's head / tail), so only one workgroup in 64 does.
-#if QS_STAMP + 0 >= 2
-#define QS_STAMP_AT(slot)                                                                                       \
-    do {                                                                                                        \
-        /* no control flow near the loads: the first stamp is taken unconditionally (a scalar-memory read nobody waits */ \
-        /* for until the wave's end); a branch here changes where the compiler waits for the state rows (+0.8 us)       */ \
-        /* ... and it is taken at stamp site 1, BEHIND the issue of the wave's state loads (~50 ns after the wave's start): a  */ \
-        /* scalar-memory read in front of them delays every later s_waitcnt lgkmcnt(0), i.e. the loads' addresses              */ \
-        if ((slot) == 1) stamp_[0] = __builtin_amdgcn_s_memrealtime();                                          \
-        else if ((slot) == (role == 0 ? 7 : 6)) {                                                               \
-            if (lane == 0 && A.stamps && (tile & 63) == 0) {     /* one workgroup in 64 records */               \
-                const unsigned long long now_ = __builtin_amdgcn_s_memrealtime();                               \
-                const unsigned long long ix_ = ((k0 % 64ull) * (unsigned long long)(A.stamp_tiles) + (unsigned long long)tile) * 16ull + 8 * role; \
-                if (ix_ + 8 <= A.stamp_cap) { A.stamps[ix_] = stamp_[0]; A.stamps[ix_ + (slot)] = now_; }       \
-            }                                                                                                   \
-        }                                                                                                       \
-    } while (0)
-#else
-#define QS_STAMP_AT(slot) (stamp_[slot] = __builtin_amdgcn_s_memrealtime())
-#endif
-#if QS_STAMP + 0 >= 2
-#define QS_STAMP_FLUSH() ((void)0)
-#else
-#define QS_STAMP_FLUSH()                                                                                        \
-    do {                                                                                                        \
-        if (lane == 0 && A.stamps) {                                                                            \
-            const unsigned long long ix_ = ((k0 % 64ull) * (unsigned long long)(A.stamp_tiles) + (unsigned long long)tile) * 16ull + 8 * role; \
-            if (ix_ + 8 <= A.stamp_cap) for (int j_ = 0; j_ < 8; ++j_) A.stamps[ix_ + j_] = stamp_[j_];          \
-        }                                                                                                       \
-    } while (0)
-#endif
-// runner kernels: phase durations summed over the T steps of one launch, [tile][role][8] words
-#define QS_PHASE_DECL unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ph_t_ = __builtin_amdgcn_s_memrealtime(); \
-    const unsigned long long ph_c0_ = __builtin_amdgcn_s_memtime(), ph_r0_ = ph_t_
-#define QS_PHASE(slot) do { const unsigned long long n_ = __builtin_amdgcn_s_memrealtime(); ph_[slot] += n_ - ph_t_; ph_t_ = n_; } while (0)
-#define QS_PHASE_FLUSH(role_)                                                                                   \
-    do {                                                                                                        \
-        ph_[6] = __builtin_amdgcn_s_memtime() - ph_c0_;          /* shader clocks ... */                         \
-        ph_[7] = __builtin_amdgcn_s_memrealtime() - ph_r0_;      /* ... per 10 ns ticks = the clock frequency */ \
-        if (lane == 0 && A.stamps) {                                                                            \
-            const unsigned long long ix_ = (unsigned long long)tile * 16ull + 8 * (role_);                      \
-            if (ix_ + 8 <= A.stamp_cap) for (int j_ = 0; j_ < 8; ++j_) A.stamps[ix_ + j_] = ph_[j_];             \
-        }                                                                                                       \
-    } while (0)
-#else
-#define QS_STAMP_DECL ((void)0)
-#define QS_STAMP_AT(slot) ((void)0)
-#define QS_STAMP_FLUSH() ((void)0)
-#define QS_PHASE_DECL ((void)0)
-#define QS_PHASE(slot) ((void)0)
-#define QS_PHASE_FLUSH(role_) ((void)0)
-#endif
-
-// Store flavour of the step kernels' state rows and outputs: non-temporal (`nt`).  Every byte a step writes is consumed by a
-// LATER launch (the next step, the policy), never by this one, and each launch ends with the write-back of the L2s' dirty lines:
-// streaming stores leave that write-back less to do (65 536 envs: 6.92 -> 6.60 us per step; 131 072: 9.21 -> 8.87 us; plain
-// stores with -DQS_PLAIN_STORES for A/B).  `sc1` write-through stores, in contrast, evict the lines and cost more than they save.
-#if defined(QS_PLAIN_STORES)
-#define QS_ST(p, v) (*(p) = (v))
-#define QS_SO(p, v) QS_ST(p, v)
-#else
-#define QS_ST(p, v) __builtin_nontemporal_store((v), (p))
-#define QS_SO(p, v) QS_ST(p, v)
-#endif
-
+#include "kernel_diag.hpp"
 #include "step_kernels.hpp"
 #include "layer1_kernels.hpp"
 #include "policy_kernels.hpp"
@@ -169,11 +95,7 @@ struct QsEnv {
     size_t gae_ws_floats = 0;
     float *init = nullptr;      // stored per-env initial states (docking-v1, hovering-v0, qs_set_init_state)
     int obs_dim = 12;
-    // staging for QS_IO_HOST: a device buffer plus a pinned, device-mapped host mirror of the same size
-    void *stage = nullptr;
-    size_t stage_bytes = 0;
-    char *hpin = nullptr;       // host address of the mirror
-    char *hpin_dev = nullptr;   // its device address (kernels of small batches read / write it in place)
+    HostStage stage;            // QS_IO_HOST: where UserIO keeps the caller's buffers during a call
     // env groups (qs_set_groups): contiguous tile ranges stepped on their own streams, optionally by their own launcher threads
     std::vector<struct QsGroup *> groups;
     hipEvent_t fork_ev = nullptr;
@@ -220,61 +142,8 @@ StepArgs make_args(const QsEnv *e)
     return A;
 }
 
-int ensure_stage(QsEnv *e, size_t bytes)
-{
-    if (e->stage_bytes >= bytes) return QS_OK;
-    if (e->stage) { HIP_TRY(hipStreamSynchronize(e->stream)); HIP_TRY(hipFree(e->stage)); e->stage = nullptr; e->stage_bytes = 0; }
-    if (e->hpin) { HIP_TRY(hipHostFree(e->hpin)); e->hpin = nullptr; e->hpin_dev = nullptr; }
-    HIP_TRY(hipMalloc(&e->stage, bytes));
-    e->stage_bytes = bytes;
-    if (e->cfg.io_space == QS_IO_HOST) {
-        HIP_TRY(hipHostMalloc((void **)&e->hpin, bytes, hipHostMallocMapped));
-        HIP_TRY(hipHostGetDevicePointer((void **)&e->hpin_dev, e->hpin, 0));
-    }
-    return QS_OK;
-}
-
-// bump allocator over the staging buffer (256-B aligned slices)
-struct Stage {
-    char *base;
-    size_t off = 0;
-    template <typename T> T *take(size_t count)
-    {
-        T *p = reinterpret_cast<T *>(base + off);
-        off += (count * sizeof(T) + 255) & ~size_t(255);
-        return p;
-    }
-};
-
-// Host-buffer calls (QS_IO_HOST: the single-env gym shims, SB2-style numpy VecEnvs) bounce through the pinned mirror.
-// Up to kDirectBytes the kernels read and write the mapped host memory in place (a step of a few envs costs one
-// launch and one stream sync, no copy engine); larger blocks take ONE DMA in and ONE DMA out of the device buffer.
-// Slices are taken in the same order on both sides, so a device pointer maps to its host twin by offset.
-constexpr size_t kDirectBytes = 64u << 10;
-struct Bounce {
-    QsEnv *e;
-    bool direct;
-    char *dbase;
-    Stage S;
-    size_t in_end = 0;      // inputs occupy [0, in_end), outputs [in_end, S.off)
-    Bounce(QsEnv *env, size_t bytes)
-        : e(env), direct(bytes <= kDirectBytes), dbase(direct ? env->hpin_dev : (char *)env->stage), S{dbase} {}
-    template <typename T> T *take(size_t count) { return S.take<T>(count); }
-    template <typename T> T *host(T *dptr) const { return reinterpret_cast<T *>(e->hpin + ((char *)dptr - dbase)); }
-    void inputs_done() { in_end = S.off; }
-    int push()              // after the caller filled host(...) of every input slice
-    {
-        if (!direct && in_end) HIP_TRY(hipMemcpyAsync(dbase, e->hpin, in_end, hipMemcpyHostToDevice, e->stream));
-        return QS_OK;
-    }
-    int pull()              // after the kernels were enqueued: outputs land in host(...) of every output slice
-    {
-        if (!direct && S.off > in_end)
-            HIP_TRY(hipMemcpyAsync(e->hpin + in_end, dbase + in_end, S.off - in_end, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        return QS_OK;
-    }
-};
+// the user buffers of one call of the handle (host_util.hpp)
+UserIO user_io(QsEnv *e) { return UserIO(e->cfg.io_space == QS_IO_HOST ? &e->stage : nullptr, e->stream); }
 
 // reset-preparation variant of the role-split kernel for a launch of `tiles` tiles (see kPrepMaxTiles)
 std::atomic<int> &prep_forced()
@@ -324,6 +193,14 @@ void with_combo(const StepVariant &v, F &&f)
 {
     if (v.integ == 0) with_combo_integ<0>(v, f);
     else with_combo_integ<1>(v, f);
+}
+// ... and f.operator()<INTEG, PARAMS>() for the kernels that have no RMODE (k_hover, k_shooting_plan).  <.., false> is named before
+// <.., true>: the order of instantiation shows in the machine code of two k_shooting_plan (one instruction each)
+template <class F>
+void with_integ_params(const StepVariant &v, F &&f)
+{
+    if (v.integ == 0) { if (!v.params) f.template operator()<0, false>(); else f.template operator()<0, true>(); }
+    else { if (!v.params) f.template operator()<1, false>(); else f.template operator()<1, true>(); }
 }
 
 // role-split kernel up to kSplitMaxEnvs envs (few waves per SIMD: the two half-length streams of a tile overlap), the serial
@@ -378,15 +255,8 @@ int launch_env_on(QsEnv *e, const StepArgs &A, hipStream_t s)
     const StepVariant v = step_variant(e, A.tile_end - A.tile0);
     if (v.family == kFamHover) {
         const unsigned grid = (unsigned)((A.tile_end - A.tile0 + kBlock / kTile - 1) / (kBlock / kTile));
-        const bool fr = v.integ == 0, pp = v.params != 0;
-        if (fr && !pp) hipLaunchKernelGGL((k_hover<0, false>), dim3(grid), dim3(kBlock), 0, s, A);
-        else if (fr) hipLaunchKernelGGL((k_hover<0, true>), dim3(grid), dim3(kBlock), 0, s, A);
-        else if (!pp) hipLaunchKernelGGL((k_hover<1, false>), dim3(grid), dim3(kBlock), 0, s, A);
-        else hipLaunchKernelGGL((k_hover<1, true>), dim3(grid), dim3(kBlock), 0, s, A);
-        HIP_TRY(hipGetLastError());
-        return QS_OK;
-    }
-    with_combo(v, [&]<int INTEG, bool PARAMS, int RMODE>() { launch_one<INTEG, PARAMS, RMODE>(s, A, v); });
+        with_integ_params(v, [&]<int INTEG, bool PARAMS>() { hipLaunchKernelGGL((k_hover<INTEG, PARAMS>), dim3(grid), dim3(kBlock), 0, s, A); });
+    } else with_combo(v, [&]<int INTEG, bool PARAMS, int RMODE>() { launch_one<INTEG, PARAMS, RMODE>(s, A, v); });
     HIP_TRY(hipGetLastError());
     return QS_OK;
 }
@@ -423,14 +293,17 @@ int fill_params(QsEnv *e)
     return QS_OK;
 }
 
+// init_all (qs_create): every env gets its initial state (nominal / stored) and q_des = identity; the per-episode randomisation
+// starts at the first reset
 int do_reset(QsEnv *e, const uint8_t *d_mask, float *d_obs, int init_all)
 {
     StepArgs A = make_args(e);
     A.obs = d_obs;
+    if (init_all) A.randomise = 0;
     if (e->cfg.kind == QS_KIND_HOVERING_V0)
         hipLaunchKernelGGL(k_hover_reset, dim3(grid_tiles(e->n)), dim3(kBlock), 0, e->stream, A, d_mask);
     else
-    hipLaunchKernelGGL(k_reset, dim3(grid_tiles(e->n)), dim3(kBlock), 0, e->stream, A, d_mask, init_all);
+        hipLaunchKernelGGL(k_reset, dim3(grid_tiles(e->n)), dim3(kBlock), 0, e->stream, A, d_mask, init_all);
     HIP_TRY(hipGetLastError());
     return QS_OK;
 }
@@ -473,7 +346,7 @@ int qs_debug_step_kernargs(QsEnv *e, const float *actions, float *obs, float *re
     if (cap < sizeof A) return fail(QS_ERR_INVALID, "qs_debug_step_kernargs: buffer too small (%zu needed)", sizeof A);
     memcpy(out, &A, sizeof A);
     *size = sizeof A;
-    if (split) *split = e->n <= kSplitMaxEnvs ? 1 : 0;
+    if (split) *split = split_for(e) ? 1 : 0;
     if (tiles) *tiles = e->tiles;
     return QS_OK;
 }
@@ -535,7 +408,6 @@ int qs_create(const QsConfig *cfg, QsEnv **out)
     e->tiles = tiles_of(e->n);
     e->per_env_params = cfg->randomise >= QS_RANDOMISE_PARAMS;
     e->obs_dim = cfg->kind == QS_KIND_HOVERING_V0 ? 13 : 12;
-    int rc = QS_OK;
     auto body = [&]() -> int {
         if (cfg->external_stream) e->stream = (hipStream_t)cfg->stream;
         else { HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking)); e->own_stream = true; }
@@ -564,18 +436,11 @@ int qs_create(const QsConfig *cfg, QsEnv **out)
                                cfg->seed, cfg->env_id_offset);
             HIP_TRY(hipGetLastError());
         }
-        // __init__: initial states (nominal / stored), q_des = identity; per-episode randomisation starts at the first reset
-        StepArgs A = make_args(e);
-        A.randomise = 0;
-        if (cfg->kind == QS_KIND_HOVERING_V0)
-            hipLaunchKernelGGL(k_hover_reset, dim3(grid_tiles(e->n)), dim3(kBlock), 0, e->stream, A, (const uint8_t *)nullptr);
-        else
-            hipLaunchKernelGGL(k_reset, dim3(grid_tiles(e->n)), dim3(kBlock), 0, e->stream, A, (const uint8_t *)nullptr, 1);
-        HIP_TRY(hipGetLastError());
+        if ((r = do_reset(e, nullptr, nullptr, 1))) return r;          // __init__
         HIP_TRY(hipStreamSynchronize(e->stream));
         return QS_OK;
     };
-    rc = body();
+    const int rc = body();
     if (rc != QS_OK) { qs_destroy(e); return rc; }
     *out = e;
     return QS_OK;
@@ -593,8 +458,8 @@ int qs_destroy(QsEnv *e)
     if (e->init) (void)hipFree(e->init);
     if (e->d_ctr) (void)hipFree(e->d_ctr);
     if (e->gae_ws) (void)hipFree(e->gae_ws);
-    if (e->stage) (void)hipFree(e->stage);
-    if (e->hpin) (void)hipHostFree(e->hpin);
+    if (e->stage.dev) (void)hipFree(e->stage.dev);
+    if (e->stage.pin) (void)hipHostFree(e->stage.pin);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
@@ -664,28 +529,13 @@ int qs_reset(QsEnv *e, const uint8_t *mask, float *obs_out)
 {
     Range rg_("qs_reset");
     CHECK_ENV(e);
-    const int64_t n = e->n;
-    if (e->cfg.io_space == QS_IO_DEVICE) return do_reset(e, mask, obs_out, 0);
-    const int64_t od = e->obs_dim;
-    const size_t need = (size_t)n * (od * 4 + 1) + 1024;
-    int r = ensure_stage(e, need);
-    if (r) return r;
-    Bounce B(e, need);
-    uint8_t *d_mask = B.take<uint8_t>(n);
-    B.inputs_done();
-    float *d_obs = B.take<float>(n * od);
-    if (mask) memcpy(B.host(d_mask), mask, n);
-    if (obs_out && mask) {
-        // rows of envs that are not reset keep the caller's values: seed the output slice with them
-        memcpy(B.host(d_obs), obs_out, n * od * sizeof(float));
-        if (!B.direct) HIP_TRY(hipMemcpyAsync(d_obs, B.host(d_obs), n * od * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    }
-    if (mask && (r = B.push())) return r;
-    r = do_reset(e, mask ? d_mask : nullptr, d_obs, 0);
-    if (r) return r;
-    if ((r = B.pull())) return r;
-    if (obs_out) memcpy(obs_out, B.host(d_obs), n * od * sizeof(float));
-    return QS_OK;
+    UserIO io = user_io(e);
+    io.in(mask, e->n);
+    if (mask) io.inout(obs_out, e->n * e->obs_dim);     // rows of envs that are not reset keep the caller's values
+    else io.out(obs_out, e->n * e->obs_dim);
+    int r = io.push();
+    if (r || (r = do_reset(e, mask, obs_out, 0))) return r;
+    return io.pull();
 }
 
 int qs_step_ex(QsEnv *e, const float *actions, float *obs, float *reward, uint8_t *done, uint8_t *flags, float *terminal_obs,
@@ -705,51 +555,17 @@ int qs_step_ex(QsEnv *e, const float *actions, float *obs, float *reward, uint8_
         return chain_step(e, A);
     }
     if (!e->groups.empty()) { int rcj = main_stream_entry(e); if (rcj) return rcj; }
-    const int64_t n = e->n;
+    const int64_t n = e->n, od = e->obs_dim;
     StepArgs A = make_args(e);
-    int r;
-    if (e->cfg.io_space == QS_IO_DEVICE) {
-        A.actions = actions; A.obs = obs; A.reward = reward; A.done = done; A.flags = flags; A.term_obs = terminal_obs;
-        A.term_state = terminal_state;
-        r = launch_env(e, A);
-        if (r) return r;
-    } else {
-        const int64_t od = e->obs_dim;
-        const size_t need = (size_t)n * (4 * 4 + od * 4 + 4 + 1 + 1 + od * 4 + 26 * 4) + 4096;
-        r = ensure_stage(e, need);
-        if (r) return r;
-        Bounce B(e, need);
-        float *d_act = B.take<float>(n * 4);
-        B.inputs_done();
-        float *d_obs = B.take<float>(n * od), *d_rew = B.take<float>(n);
-        uint8_t *d_done = B.take<uint8_t>(n), *d_flags = B.take<uint8_t>(n);
-        float *d_term = B.take<float>(n * od);
-        float *d_tst = B.take<float>(n * 26);
-        memcpy(B.host(d_act), actions, n * 4 * sizeof(float));
-        if ((r = B.push())) return r;
-        if (terminal_obs) {
-            // rows of envs that did not finish keep the caller's values
-            memcpy(B.host(d_term), terminal_obs, n * od * sizeof(float));
-            if (!B.direct) HIP_TRY(hipMemcpyAsync(d_term, B.host(d_term), n * od * sizeof(float), hipMemcpyHostToDevice, e->stream));
-        }
-        if (terminal_state) {
-            memcpy(B.host(d_tst), terminal_state, n * 26 * sizeof(float));
-            if (!B.direct) HIP_TRY(hipMemcpyAsync(d_tst, B.host(d_tst), n * 26 * sizeof(float), hipMemcpyHostToDevice, e->stream));
-        }
-        A.actions = d_act; A.obs = d_obs; A.reward = d_rew; A.done = d_done; A.flags = d_flags;
-        A.term_obs = terminal_obs ? d_term : nullptr;
-        A.term_state = terminal_state ? d_tst : nullptr;
-        r = launch_env(e, A);
-        if (r) return r;
-        if ((r = B.pull())) return r;
-        memcpy(obs, B.host(d_obs), n * od * sizeof(float));
-        memcpy(reward, B.host(d_rew), n * sizeof(float));
-        memcpy(done, B.host(d_done), n);
-        if (flags) memcpy(flags, B.host(d_flags), n);
-        if (terminal_obs) memcpy(terminal_obs, B.host(d_term), n * od * sizeof(float));
-        if (terminal_state) memcpy(terminal_state, B.host(d_tst), n * 26 * sizeof(float));
-    }
-    return QS_OK;
+    A.actions = actions; A.obs = obs; A.reward = reward; A.done = done; A.flags = flags; A.term_obs = terminal_obs;
+    A.term_state = terminal_state;
+    UserIO io = user_io(e);
+    io.in(A.actions, n * 4);
+    io.out(A.obs, n * od); io.out(A.reward, n); io.out(A.done, n); io.out(A.flags, n);
+    io.inout(A.term_obs, n * od); io.inout(A.term_state, n * 26);    // rows of envs that did not finish keep the caller's values
+    int r = io.push();
+    if (r || (r = launch_env(e, A))) return r;
+    return io.pull();
 }
 
 int qs_step(QsEnv *e, const float *actions, float *obs, float *reward, uint8_t *done, uint8_t *flags, float *terminal_obs)
@@ -903,32 +719,15 @@ int qs_rollout(QsEnv *e, int64_t T, const float *actions, float *obs, float *rew
     if (T < 1) return fail(QS_ERR_INVALID, "qs_rollout: T must be >= 1");
     if (!obs || !reward || !done) return fail(QS_ERR_INVALID, "qs_rollout: obs, reward and done are required");
     if (!e->cfg.auto_reset) return fail(QS_ERR_INVALID, "qs_rollout: requires auto_reset (a roll-out runs through episode ends)");
-    const int64_t n = e->n, tn = T * n;
+    const int64_t tn = T * e->n, od = e->obs_dim;
     StepArgs A = make_args(e);
-    A.T = T;
-    int r;
-    if (e->cfg.io_space == QS_IO_DEVICE) {
-        A.actions = actions; A.obs = obs; A.reward = reward; A.done = done; A.flags = flags;
-        r = launch_env(e, A);
-        if (r) return r;
-    } else {
-        const int64_t od = e->obs_dim;
-        r = ensure_stage(e, (size_t)tn * (4 * 4 + od * 4 + 4 + 1 + 1) + 4096);
-        if (r) return r;
-        Stage S{(char *)e->stage};
-        float *d_act = S.take<float>(tn * 4), *d_obs = S.take<float>(tn * od), *d_rew = S.take<float>(tn);
-        uint8_t *d_done = S.take<uint8_t>(tn), *d_flags = S.take<uint8_t>(tn);
-        if (actions) HIP_TRY(hipMemcpyAsync(d_act, actions, tn * 4 * sizeof(float), hipMemcpyHostToDevice, e->stream));
-        A.actions = actions ? d_act : nullptr; A.obs = d_obs; A.reward = d_rew; A.done = d_done; A.flags = d_flags;
-        r = launch_env(e, A);
-        if (r) return r;
-        HIP_TRY(hipMemcpyAsync(obs, d_obs, tn * od * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync(reward, d_rew, tn * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync(done, d_done, tn, hipMemcpyDeviceToHost, e->stream));
-        if (flags) HIP_TRY(hipMemcpyAsync(flags, d_flags, tn, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    return QS_OK;
+    A.T = T; A.actions = actions; A.obs = obs; A.reward = reward; A.done = done; A.flags = flags;
+    UserIO io = user_io(e);
+    io.in(A.actions, tn * 4);
+    io.out(A.obs, tn * od); io.out(A.reward, tn); io.out(A.done, tn); io.out(A.flags, tn);
+    int r = io.push();
+    if (r || (r = launch_env(e, A))) return r;
+    return io.pull();
 }
 
 int qs_rollout_slab(QsEnv *e, int64_t T, const float *actions, float *slab, uint8_t *flags)
@@ -981,54 +780,31 @@ int qs_fill_random_actions(QsEnv *e, int64_t T, uint64_t step0, float *actions)
     CHECK_ENV(e);
     if (T < 1 || !actions) return fail(QS_ERR_INVALID, "qs_fill_random_actions: bad arguments");
     const int64_t tn = T * e->n;
-    float *d = actions;
-    if (e->cfg.io_space == QS_IO_HOST) {
-        int r = ensure_stage(e, (size_t)tn * 16 + 1024);
-        if (r) return r;
-        d = (float *)e->stage;
-    }
-    hipLaunchKernelGGL(k_fill_actions, dim3(grid_flat(tn)), dim3(kBlock), 0, e->stream, d, e->n, T, e->cfg.seed,
+    UserIO io = user_io(e);
+    io.out(actions, tn * 4);
+    if (int r = io.push()) return r;
+    hipLaunchKernelGGL(k_fill_actions, dim3(grid_flat(tn)), dim3(kBlock), 0, e->stream, actions, e->n, T, e->cfg.seed,
                        e->cfg.env_id_offset, step0);
     HIP_TRY(hipGetLastError());
-    if (e->cfg.io_space == QS_IO_HOST) {
-        HIP_TRY(hipMemcpyAsync(actions, d, tn * 16, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    return QS_OK;
+    return io.pull();
 }
 
 static int state_io(QsEnv *e, bool to_user, float *chaser, float *target, float *u_prev, float *qdes, float *ls, float *t)
 {
     const int64_t n = e->n;
     const int64_t words[6] = {13, 13, 8, 4, 1, 1};
-    float *user[6] = {chaser, target, u_prev, qdes, ls, t};
-    StateIO io{chaser, target, u_prev, qdes, ls, t};
-    if (e->cfg.io_space == QS_IO_DEVICE) {
-        if (to_user) hipLaunchKernelGGL(k_state_io<true>, dim3(grid_tiles(n)), dim3(kBlock), 0, e->stream, e->st, n, io);
-        else hipLaunchKernelGGL(k_state_io<false>, dim3(grid_tiles(n)), dim3(kBlock), 0, e->stream, e->st, n, io);
-        HIP_TRY(hipGetLastError());
-        return QS_OK;
-    }
-    const size_t need = (size_t)n * 40 * 4 + 4096;
-    int r = ensure_stage(e, need);
-    if (r) return r;
-    Bounce B(e, need);
-    float *dev[6];
+    float *p[6] = {chaser, target, u_prev, qdes, ls, t};
+    UserIO io = user_io(e);
     for (int i = 0; i < 6; ++i) {
-        dev[i] = B.take<float>(n * words[i]);
-        if (user[i] && !to_user) memcpy(B.host(dev[i]), user[i], n * words[i] * 4);
+        if (to_user) io.out(p[i], n * words[i]);
+        else io.in(p[i], n * words[i]);
     }
-    if (!to_user) { B.inputs_done(); if ((r = B.push())) return r; }
-    io = StateIO{chaser ? dev[0] : nullptr, target ? dev[1] : nullptr, u_prev ? dev[2] : nullptr,
-                 qdes ? dev[3] : nullptr, ls ? dev[4] : nullptr, t ? dev[5] : nullptr};
-    if (to_user) hipLaunchKernelGGL(k_state_io<true>, dim3(grid_tiles(n)), dim3(kBlock), 0, e->stream, e->st, n, io);
-    else hipLaunchKernelGGL(k_state_io<false>, dim3(grid_tiles(n)), dim3(kBlock), 0, e->stream, e->st, n, io);
+    if (int r = io.push()) return r;
+    const StateIO sio{p[0], p[1], p[2], p[3], p[4], p[5]};
+    if (to_user) hipLaunchKernelGGL(k_state_io<true>, dim3(grid_tiles(n)), dim3(kBlock), 0, e->stream, e->st, n, sio);
+    else hipLaunchKernelGGL(k_state_io<false>, dim3(grid_tiles(n)), dim3(kBlock), 0, e->stream, e->st, n, sio);
     HIP_TRY(hipGetLastError());
-    if ((r = B.pull())) return r;
-    if (to_user)
-        for (int i = 0; i < 6; ++i)
-            if (user[i]) memcpy(user[i], B.host(dev[i]), n * words[i] * 4);
-    return QS_OK;
+    return io.pull();
 }
 
 int qs_get_state(QsEnv *e, float *chaser, float *target, float *u_prev, float *qdes, float *last_shaping, float *t)
@@ -1047,30 +823,14 @@ int qs_set_state(QsEnv *e, const float *chaser, const float *target, const float
 static int par_io(QsEnv *e, bool to_user, float *mass, float *inertia)
 {
     const int64_t n = e->n;
-    float *dm = mass, *di = inertia;
-    if (e->cfg.io_space == QS_IO_HOST) {
-        int r = ensure_stage(e, (size_t)n * 16 + 1024);
-        if (r) return r;
-        Stage S{(char *)e->stage};
-        dm = S.take<float>(n); di = S.take<float>(n * 3);
-        if (!to_user) {
-            if (mass) HIP_TRY(hipMemcpyAsync(dm, mass, n * 4, hipMemcpyHostToDevice, e->stream));
-            if (inertia) HIP_TRY(hipMemcpyAsync(di, inertia, n * 12, hipMemcpyHostToDevice, e->stream));
-        }
-        if (!mass) dm = nullptr;
-        if (!inertia) di = nullptr;
-    }
-    if (to_user) hipLaunchKernelGGL(k_par_io<true>, dim3(grid_tiles(n)), dim3(kBlock), 0, e->stream, e->par, n, dm, di);
-    else hipLaunchKernelGGL(k_par_io<false>, dim3(grid_tiles(n)), dim3(kBlock), 0, e->stream, e->par, n, dm, di);
+    UserIO io = user_io(e);
+    if (to_user) { io.out(mass, n); io.out(inertia, n * 3); }
+    else { io.in(mass, n); io.in(inertia, n * 3); }
+    if (int r = io.push()) return r;
+    if (to_user) hipLaunchKernelGGL(k_par_io<true>, dim3(grid_tiles(n)), dim3(kBlock), 0, e->stream, e->par, n, mass, inertia);
+    else hipLaunchKernelGGL(k_par_io<false>, dim3(grid_tiles(n)), dim3(kBlock), 0, e->stream, e->par, n, mass, inertia);
     HIP_TRY(hipGetLastError());
-    if (e->cfg.io_space == QS_IO_HOST) {
-        if (to_user) {
-            if (mass) HIP_TRY(hipMemcpyAsync(mass, dm, n * 4, hipMemcpyDeviceToHost, e->stream));
-            if (inertia) HIP_TRY(hipMemcpyAsync(inertia, di, n * 12, hipMemcpyDeviceToHost, e->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    return QS_OK;
+    return io.pull();
 }
 
 int qs_set_params(QsEnv *e, const float *mass, const float *inertia)
@@ -1120,7 +880,6 @@ int qs_set_init_state(QsEnv *e, const float *chaser_init, const float *target_in
 {
     CHECK_ENV(e);
     if (!chaser_init) return fail(QS_ERR_INVALID, "qs_set_init_state: chaser_init is required");
-    const bool hover = e->cfg.kind == QS_KIND_HOVERING_V0;
     if (!e->init) {
         // first use on a docking-v0/v2 handle: start from the nominal pair for every env
         HIP_TRY(hipStreamSynchronize(e->stream));
@@ -1128,7 +887,6 @@ int qs_set_init_state(QsEnv *e, const float *chaser_init, const float *target_in
         hipLaunchKernelGGL(k_fill_init_nominal, dim3(grid_flat(e->n)), dim3(kBlock), 0, e->stream, e->init, e->n);
         HIP_TRY(hipGetLastError());
     }
-    (void)hover;
     return init_io(e, false, (float *)chaser_init, (float *)target_init);
 }
 
@@ -1710,11 +1468,9 @@ int qs_shooting_plan(QsEnv *e, int32_t horizon, int32_t paths, int32_t objective
     const PlanArgs X{horizon, paths, objective, actions, best_score, best_index, sequence, scores};
     const unsigned block = (unsigned)std::min<int64_t>(kBlock, ((int64_t)paths + kTile - 1) / kTile * kTile);
     const size_t lds = plan_lds_bytes(horizon);
-    const StepVariant v = step_combo(e);
-    if (v.integ == 0 && !v.params) hipLaunchKernelGGL((k_shooting_plan<0, false>), dim3((unsigned)e->n), dim3(block), lds, e->stream, A, X);
-    else if (v.integ == 0) hipLaunchKernelGGL((k_shooting_plan<0, true>), dim3((unsigned)e->n), dim3(block), lds, e->stream, A, X);
-    else if (!v.params) hipLaunchKernelGGL((k_shooting_plan<1, false>), dim3((unsigned)e->n), dim3(block), lds, e->stream, A, X);
-    else hipLaunchKernelGGL((k_shooting_plan<1, true>), dim3((unsigned)e->n), dim3(block), lds, e->stream, A, X);
+    with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
+        hipLaunchKernelGGL((k_shooting_plan<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(block), lds, e->stream, A, X);
+    });
     HIP_TRY(hipGetLastError());
     return QS_OK;
 }
@@ -1725,31 +1481,15 @@ int qs_drone_step(QsEnv *e, int64_t n, float *state, float *u_prev, const float 
     CHECK_ENV(e);
     if (n < 1 || !state || !u_prev || !u) return fail(QS_ERR_INVALID, "qs_drone_step: bad arguments");
     Par pn{e->cfg.mass, e->cfg.inertia[0], e->cfg.inertia[1], e->cfg.inertia[2]};
-    float *ds = state, *dup = u_prev;
-    const float *du = u, *dp = par;
-    uint8_t *dl = limited;
-    if (e->cfg.io_space == QS_IO_HOST) {
-        int r = ensure_stage(e, (size_t)n * (13 + 4 + 4 + 4) * 4 + n + 4096);
-        if (r) return r;
-        Stage S{(char *)e->stage};
-        float *a = S.take<float>(n * 13), *b = S.take<float>(n * 4), *c = S.take<float>(n * 4), *d = S.take<float>(n * 4);
-        uint8_t *l = S.take<uint8_t>(n);
-        HIP_TRY(hipMemcpyAsync(a, state, n * 52, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(b, u_prev, n * 16, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(c, u, n * 16, hipMemcpyHostToDevice, e->stream));
-        if (par) HIP_TRY(hipMemcpyAsync(d, par, n * 16, hipMemcpyHostToDevice, e->stream));
-        ds = a; dup = b; du = c; dp = par ? d : nullptr; dl = limited ? l : nullptr;
-    }
-    hipLaunchKernelGGL(k_drone_step, dim3(grid_flat(n)), dim3(kBlock), 0, e->stream, n, ds, dup, du, dp, dl, pn, e->cfg.dt,
+    UserIO io = user_io(e);
+    io.inout(state, n * 13); io.inout(u_prev, n * 4);
+    io.in(u, n * 4); io.in(par, n * 4);
+    io.out(limited, n);
+    if (int r = io.push()) return r;
+    hipLaunchKernelGGL(k_drone_step, dim3(grid_flat(n)), dim3(kBlock), 0, e->stream, n, state, u_prev, u, par, limited, pn, e->cfg.dt,
                        e->cfg.integrator);
     HIP_TRY(hipGetLastError());
-    if (e->cfg.io_space == QS_IO_HOST) {
-        HIP_TRY(hipMemcpyAsync(state, ds, n * 52, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync(u_prev, dup, n * 16, hipMemcpyDeviceToHost, e->stream));
-        if (limited) HIP_TRY(hipMemcpyAsync(limited, dl, n, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    return QS_OK;
+    return io.pull();
 }
 
 int qs_ctrl(QsEnv *e, int64_t n, int32_t mode, float *state_des, const float *state, const float *state_last, float mass,
@@ -1758,26 +1498,14 @@ int qs_ctrl(QsEnv *e, int64_t n, int32_t mode, float *state_des, const float *st
     CHECK_ENV(e);
     if (n < 1 || !state_des || !state || !u_out || (mode != 0 && mode != 1)) return fail(QS_ERR_INVALID, "qs_ctrl: bad arguments");
     if (mode == 1 && !state_last) return fail(QS_ERR_INVALID, "qs_ctrl: vel_controller needs state_last");
-    float *dsd = state_des, *duo = u_out;
-    const float *dsn = state, *dsl = state_last;
-    if (e->cfg.io_space == QS_IO_HOST) {
-        int r = ensure_stage(e, (size_t)n * (13 * 3 + 4) * 4 + 4096);
-        if (r) return r;
-        Stage S{(char *)e->stage};
-        float *a = S.take<float>(n * 13), *b = S.take<float>(n * 13), *c = S.take<float>(n * 13), *d = S.take<float>(n * 4);
-        HIP_TRY(hipMemcpyAsync(a, state_des, n * 52, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(b, state, n * 52, hipMemcpyHostToDevice, e->stream));
-        if (state_last) HIP_TRY(hipMemcpyAsync(c, state_last, n * 52, hipMemcpyHostToDevice, e->stream));
-        dsd = a; dsn = b; dsl = state_last ? c : nullptr; duo = d;
-    }
-    hipLaunchKernelGGL(k_ctrl, dim3(grid_flat(n)), dim3(kBlock), 0, e->stream, n, (int)mode, dsd, dsn, dsl, mass, duo);
+    UserIO io = user_io(e);
+    io.inout(state_des, n * 13);
+    io.in(state, n * 13); io.in(state_last, n * 13);
+    io.out(u_out, n * 4);
+    if (int r = io.push()) return r;
+    hipLaunchKernelGGL(k_ctrl, dim3(grid_flat(n)), dim3(kBlock), 0, e->stream, n, (int)mode, state_des, state, state_last, mass, u_out);
     HIP_TRY(hipGetLastError());
-    if (e->cfg.io_space == QS_IO_HOST) {
-        HIP_TRY(hipMemcpyAsync(state_des, dsd, n * 52, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipMemcpyAsync(u_out, duo, n * 16, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    return QS_OK;
+    return io.pull();
 }
 
 int qs_transform(QsEnv *e, int32_t op, int64_t n, const float *in, float *out)
@@ -1785,47 +1513,26 @@ int qs_transform(QsEnv *e, int32_t op, int64_t n, const float *in, float *out)
     CHECK_ENV(e);
     if (n < 1 || !in || !out || op < 0 || op > 3) return fail(QS_ERR_INVALID, "qs_transform: bad arguments");
     const int wi[4] = {4, 3, 4, 9}, wo[4] = {3, 4, 9, 3};
-    const float *di = in;
-    float *dout = out;
-    if (e->cfg.io_space == QS_IO_HOST) {
-        int r = ensure_stage(e, (size_t)n * (wi[op] + wo[op]) * 4 + 1024);
-        if (r) return r;
-        Stage S{(char *)e->stage};
-        float *a = S.take<float>(n * wi[op]), *b = S.take<float>(n * wo[op]);
-        HIP_TRY(hipMemcpyAsync(a, in, n * wi[op] * 4, hipMemcpyHostToDevice, e->stream));
-        di = a; dout = b;
-    }
-    hipLaunchKernelGGL(k_transform, dim3(grid_flat(n)), dim3(kBlock), 0, e->stream, (int)op, n, di, dout);
+    UserIO io = user_io(e);
+    io.in(in, n * wi[op]);
+    io.out(out, n * wo[op]);
+    if (int r = io.push()) return r;
+    hipLaunchKernelGGL(k_transform, dim3(grid_flat(n)), dim3(kBlock), 0, e->stream, (int)op, n, in, out);
     HIP_TRY(hipGetLastError());
-    if (e->cfg.io_space == QS_IO_HOST) {
-        HIP_TRY(hipMemcpyAsync(out, dout, n * wo[op] * 4, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    return QS_OK;
+    return io.pull();
 }
 
 int qs_rel_obs(QsEnv *e, int64_t n, const float *chaser, const float *target, float *obs)
 {
     CHECK_ENV(e);
     if (n < 1 || !chaser || !target || !obs) return fail(QS_ERR_INVALID, "qs_rel_obs: bad arguments");
-    const float *dc = chaser, *dt = target;
-    float *dob = obs;
-    if (e->cfg.io_space == QS_IO_HOST) {
-        int r = ensure_stage(e, (size_t)n * (13 * 2 + 12) * 4 + 4096);
-        if (r) return r;
-        Stage S{(char *)e->stage};
-        float *a = S.take<float>(n * 13), *b = S.take<float>(n * 13), *c = S.take<float>(n * 12);
-        HIP_TRY(hipMemcpyAsync(a, chaser, n * 52, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(b, target, n * 52, hipMemcpyHostToDevice, e->stream));
-        dc = a; dt = b; dob = c;
-    }
-    hipLaunchKernelGGL(k_rel_obs, dim3(grid_flat(n)), dim3(kBlock), 0, e->stream, n, dc, dt, dob);
+    UserIO io = user_io(e);
+    io.in(chaser, n * 13); io.in(target, n * 13);
+    io.out(obs, n * 12);
+    if (int r = io.push()) return r;
+    hipLaunchKernelGGL(k_rel_obs, dim3(grid_flat(n)), dim3(kBlock), 0, e->stream, n, chaser, target, obs);
     HIP_TRY(hipGetLastError());
-    if (e->cfg.io_space == QS_IO_HOST) {
-        HIP_TRY(hipMemcpyAsync(obs, dob, n * 48, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    return QS_OK;
+    return io.pull();
 }
 
 }  // extern "C"

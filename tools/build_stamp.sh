@@ -1,5 +1,5 @@
 #!/bin/bash
-# Diagnostic twins with in-kernel stamps (see QS_STAMP in quadsim_hip.hip); use with QUADSIM_HIP_LIB=...
+# Diagnostic twins with in-kernel stamps (see QS_STAMP in kernel_diag.hpp); use with QUADSIM_HIP_LIB=...
 #   libquadsim_hip_stamp.so   -DQS_STAMP      every phase boundary of the step kernel (costs ~0.7 us per step)
 #   libquadsim_hip_stamp2.so  -DQS_STAMP=2    first / last stamp of each wave only: period, span and gap of the unperturbed chain
 set -e
