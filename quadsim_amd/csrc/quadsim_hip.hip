@@ -1021,6 +1021,26 @@ static int check_blob(const char *who, const void *blob)
     return QS_OK;
 }
 
+// the handles qs_policy_rollout* takes, and the one choice of its kernel: f.operator()<INTEG, RMODE, FAST>() for the launch and
+// for qs_debug_rollout_variant
+static int policy_rollout_handle_ok(const QsEnv *e, const char *who)
+{
+    if (e->cfg.kind == QS_KIND_HOVERING_V0 || e->per_env_params || e->init || e->cfg.randomise > 1)
+        return fail(QS_ERR_INVALID, "%s: docking-v0/v2 with nominal or rocRAND-initialised resets only", who);
+    return QS_OK;
+}
+
+extern "C++" template <class F>
+static void with_policy_rollout_kernel(const QsEnv *e, bool fast, F &&f)
+{
+    with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {     // policy_rollout_handle_ok leaves RMODE 0 / 1 without PARAMS
+        if constexpr (!PARAMS && RMODE < 2) {
+            if (fast) f.template operator()<INTEG, RMODE, true>();
+            else f.template operator()<INTEG, RMODE, false>();
+        }
+    });
+}
+
 static int policy_rollout(QsEnv *e, const char *who, int64_t T, const MlpArgs *M, const void *blob, float *obs, float *reward,
                           uint8_t *done, uint8_t *flags, float *actions)
 {
@@ -1029,16 +1049,13 @@ static int policy_rollout(QsEnv *e, const char *who, int64_t T, const MlpArgs *M
     if (T < 1 || !obs || !reward || !done) return fail(QS_ERR_INVALID, "%s: bad arguments", who);
     if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "%s: device buffers only", who);
     if (!e->cfg.auto_reset) return fail(QS_ERR_INVALID, "%s: requires auto_reset", who);
-    if (e->cfg.kind == QS_KIND_HOVERING_V0 || e->per_env_params || e->init || e->cfg.randomise > 1)
-        return fail(QS_ERR_INVALID, "%s: docking-v0/v2 with nominal or rocRAND-initialised resets only", who);
+    if (int rc = policy_rollout_handle_ok(e, who)) return rc;
     StepArgs A = make_args(e);
     A.T = T; A.obs = obs; A.reward = reward; A.done = done; A.flags = flags;
     const unsigned grid = grid_tiles(e->n);
-    with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {     // the checks above leave RMODE 0 / 1 without PARAMS
-        if constexpr (!PARAMS && RMODE < 2) {
-            if (blob) hipLaunchKernelGGL((k_policy_rollout_fast<INTEG, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, (const uint4 *)blob, actions);
-            else hipLaunchKernelGGL((k_policy_rollout<INTEG, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, *M, actions);
-        }
+    with_policy_rollout_kernel(e, blob != nullptr, [&]<int INTEG, int RMODE, bool FAST>() {
+        if constexpr (FAST) hipLaunchKernelGGL((k_policy_rollout_fast<INTEG, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, (const uint4 *)blob, actions);
+        else hipLaunchKernelGGL((k_policy_rollout<INTEG, RMODE>), dim3(grid), dim3(kBlock), 0, e->stream, A, *M, actions);
     });
     HIP_TRY(hipGetLastError());
     return QS_OK;
@@ -1140,6 +1157,33 @@ static std::atomic<int> &runner_serial_flag()
 extern "C++" template <int NET>
 static void runner_dispatch(QsEnv *e, const StepArgs &A, const RunnerArgs &R, bool fast);
 
+// the handles qs_runner_rollout* takes, and the one choice of its kernel: f.operator()<SERIAL, INTEG, RMODE, PARAMS, FAST>()
+// (SERIAL: k_runner_rollout, else k_runner_split) for the launch and for qs_debug_rollout_variant
+static int runner_handle_ok(const QsEnv *e, const char *who)
+{
+    if (e->cfg.kind == QS_KIND_HOVERING_V0 || e->init)
+        return fail(QS_ERR_INVALID, "%s: docking-v0/v2 with nominal or rocRAND resets only (no stored initial states)", who);
+    return QS_OK;
+}
+
+extern "C++" template <class F>
+static void with_runner_kernel(const QsEnv *e, bool fast, F &&f)
+{
+    // the role-split kernel (matrix waves + env waves); QUADSIM_RUNNER_SERIAL=1 keeps the one-wave-per-tile kernel for A/B
+    // runs (same results bit for bit: the same instruction sequences on the same operands)
+    const bool serial = runner_serial_flag().load(std::memory_order_relaxed) != 0;
+    with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {
+        if constexpr (RMODE != 3) {           // runner_handle_ok rejects stored initial states
+            auto go = [&]<bool FAST>() {
+                if (serial) f.template operator()<true, INTEG, RMODE, PARAMS, FAST>();
+                else f.template operator()<false, INTEG, RMODE, PARAMS, FAST>();
+            };
+            if (fast) go.template operator()<true>();
+            else go.template operator()<false>();
+        }
+    });
+}
+
 // layout: QS_NET_SHARED_TRUNK / QS_NET_TOWERS; wtv1 / bv1: the towers' vf_fc0 (exact f32 only)
 static int runner_launch(QsEnv *e, const char *who, int64_t T, const float logstd[4], int squash, const AcArgs *net,
                          const void *blob, const float *noise, const uint8_t *dones_in, float *mb_obs, float *mb_actions,
@@ -1152,8 +1196,7 @@ static int runner_launch(QsEnv *e, const char *who, int64_t T, const float logst
         return fail(QS_ERR_INVALID, "%s: bad arguments", who);
     if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "%s: device buffers only", who);
     if (!e->cfg.auto_reset) return fail(QS_ERR_INVALID, "%s: requires auto_reset", who);
-    if (e->cfg.kind == QS_KIND_HOVERING_V0 || e->init)
-        return fail(QS_ERR_INVALID, "%s: docking-v0/v2 with nominal or rocRAND resets only (no stored initial states)", who);
+    if (int rc = runner_handle_ok(e, who)) return rc;
     StepArgs A = make_args(e);
     A.T = T; A.obs = mb_obs; A.reward = mb_rewards; A.done = mb_dones; A.flags = mb_flags;
     RunnerArgs R{};
@@ -1183,18 +1226,9 @@ extern "C++" template <int NET>
 static void runner_dispatch(QsEnv *e, const StepArgs &A, const RunnerArgs &R, bool fast)
 {
     const unsigned grid = grid_tiles(e->n);
-    // the role-split kernel (matrix waves + env waves); QUADSIM_RUNNER_SERIAL=1 keeps the one-wave-per-tile kernel for A/B
-    // runs (same results bit for bit: the same instruction sequences on the same operands)
-    const bool serial = runner_serial_flag().load(std::memory_order_relaxed) != 0;
-    with_combo(step_combo(e), [&]<int INTEG, bool PARAMS, int RMODE>() {
-        if constexpr (RMODE != 3) {           // runner_launch rejects stored initial states
-            auto go = [&]<bool FAST>() {
-                if (serial) hipLaunchKernelGGL((k_runner_rollout<INTEG, RMODE, PARAMS, FAST, NET>), dim3(grid), dim3(kBlock), 0, e->stream, A, R);
-                else hipLaunchKernelGGL((k_runner_split<INTEG, RMODE, PARAMS, FAST, NET>), dim3(grid), dim3(2 * kBlock), 0, e->stream, A, R);
-            };
-            if (fast) go.template operator()<true>();
-            else go.template operator()<false>();
-        }
+    with_runner_kernel(e, fast, [&]<bool SERIAL, int INTEG, int RMODE, bool PARAMS, bool FAST>() {
+        if constexpr (SERIAL) hipLaunchKernelGGL((k_runner_rollout<INTEG, RMODE, PARAMS, FAST, NET>), dim3(grid), dim3(kBlock), 0, e->stream, A, R);
+        else hipLaunchKernelGGL((k_runner_split<INTEG, RMODE, PARAMS, FAST, NET>), dim3(grid), dim3(2 * kBlock), 0, e->stream, A, R);
     });
 }
 
@@ -1335,6 +1369,35 @@ int qs_debug_step_variant(QsEnv *e, int32_t out[5])
     StepVariant v = step_variant(e, e->tiles);
     if (e->chain) { int rc = chain_step_variant(e, &v); if (rc) return rc; }
     const int32_t w[5] = {v.family, v.integ, v.params, v.rmode, v.prep};
+    memcpy(out, w, sizeof w);
+    return QS_OK;
+}
+
+// Diagnostic (not in quadsim.h; tests only): the roll-out kernel instantiation a call on the handle would launch, without launching
+// anything.  family 0: qs_runner_rollout* (fast: the *_fast entry points; layout: QS_NET_SHARED_TRUNK / QS_NET_TOWERS), family 1:
+// qs_policy_rollout / _fast (layout ignored).  out = {kernel, INTEG, RMODE, PARAMS, FAST, NET}: kernel 0 k_runner_rollout,
+// 1 k_runner_split, 2 k_policy_rollout, 3 k_policy_rollout_fast; -1 for a template parameter the kernel does not have.  Computed
+// by the helpers the launches call (runner_handle_ok + with_runner_kernel, policy_rollout_handle_ok + with_policy_rollout_kernel):
+// a handle those entry points refuse is refused here with the same message.
+int qs_debug_rollout_variant(QsEnv *e, int32_t family, int32_t fast, int32_t layout, int32_t out[6])
+{
+    if (!e || !out) return fail(QS_ERR_INVALID, "qs_debug_rollout_variant: null argument");
+    int32_t w[6] = {-1, -1, -1, -1, -1, -1};
+    if (family == 0) {
+        if (layout != QS_NET_SHARED_TRUNK && layout != QS_NET_TOWERS)
+            return fail(QS_ERR_INVALID, "qs_debug_rollout_variant: layout must be QS_NET_SHARED_TRUNK or QS_NET_TOWERS");
+        if (int rc = runner_handle_ok(e, "qs_debug_rollout_variant")) return rc;
+        with_runner_kernel(e, fast != 0, [&]<bool SERIAL, int INTEG, int RMODE, bool PARAMS, bool FAST>() {
+            const int32_t v[6] = {SERIAL ? 0 : 1, INTEG, RMODE, PARAMS ? 1 : 0, FAST ? 1 : 0, layout == QS_NET_TOWERS ? kNetTowers : kNetShared};
+            memcpy(w, v, sizeof v);
+        });
+    } else if (family == 1) {
+        if (int rc = policy_rollout_handle_ok(e, "qs_debug_rollout_variant")) return rc;
+        with_policy_rollout_kernel(e, fast != 0, [&]<int INTEG, int RMODE, bool FAST>() {
+            const int32_t v[6] = {FAST ? 3 : 2, INTEG, RMODE, -1, -1, -1};
+            memcpy(w, v, sizeof v);
+        });
+    } else return fail(QS_ERR_INVALID, "qs_debug_rollout_variant: family must be 0 (Runner) or 1 (policy roll-out)");
     memcpy(out, w, sizeof w);
     return QS_OK;
 }

@@ -112,6 +112,32 @@ def check_unclipped(y, ref64, E, precision, what=""):
     return float(ratio(err, E, precision).max()) if err.size else 0.0
 
 
+# ---------------------------------------------------------------------------------------------------- the Runner's neglogp
+def _neglogp64(W, u64, eps, squash):
+    logstd = np.asarray(W["logstd"], np.float32).astype(np.float64).reshape(1, 4)
+    nl = 0.5 * np.sum(np.square(eps), 1) + 0.5 * np.log(2 * np.pi) * 4 + np.sum(logstd)
+    if squash:
+        nl = nl + np.sum(np.log(1.0 - np.tanh(u64) ** 2 + 1e-6), 1)
+    return nl
+
+
+def _neglogp_bound(W, u64, m64, eps, mean_bound, squash):
+    """the kernel: u = fma(std, eps, mean) (one rounding), d = (u - mean) * inv_std on ITS mean, nl = nl_const + sum 0.5 d^2
+    (fma).  The mean's own error cancels in d, so d differs from eps by the roundings of u, of u - mean and of std / inv_std;
+    the squashed term log(sech^2 u + 1e-6) (slope <= 2 in u) also sees the error of u, i.e. the mean's bound plus u's rounding,
+    and the hardware exp2 / log2 (1 ulp, arguments up to 2|u| log2 e)."""
+    u32 = UNIT["f32"] * KAPPA["f32"]
+    std = np.exp(np.asarray(W["logstd"], np.float32).astype(np.float64)).reshape(1, 4)
+    dd = u32 * ((np.abs(u64) + np.abs(u64 - m64)) / std + 3.0 * np.abs(eps))
+    nl_const = abs(0.5 * np.log(2 * np.pi) * 4 + float(np.sum(np.asarray(W["logstd"], np.float64))))
+    b = np.sum(np.abs(eps) * dd + 0.5 * dd * dd, 1) + u32 * (2.0 * np.sum(eps * eps, 1) + 2.0 * nl_const)
+    if squash:
+        du = mean_bound + u32 * np.abs(u64)
+        L = np.log(1.0 - np.tanh(u64) ** 2 + 1e-6)
+        b = b + np.sum(2.0 * du + u32 * (4.0 * np.abs(u64) + 8.0 + np.abs(L)), 1)
+    return b
+
+
 # ---------------------------------------------------------------------------------------------------- observations
 def box_obs(n, seed):
     """the existing actor tests' uniform box"""

@@ -38,3 +38,16 @@ def kernel_notes(co, fields=FIELDS):
             field = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", block).group(1))   # noqa: E731
             out[m.group(1)] = {k: field(k) for k in fields}
     return out
+
+
+def instantiations(notes, kernels):
+    """{(kernel, template arguments...)} of the kernels named in `kernels` (integer and bool template arguments, in declaration
+    order) among the symbols of the code object's notes"""
+    # longest name first: k_env must not match inside k_env_split, k_policy_rollout not inside k_policy_rollout_fast
+    sym_re = re.compile(r"_GLOBAL__N_1\d+(%s)I((?:L[ib]\d+E)+)E" % "|".join(sorted(kernels, key=len, reverse=True)))
+    got = set()
+    for sym in notes:
+        m = sym_re.search(sym)
+        if m:
+            got.add((m.group(1),) + tuple(int(a) for a in re.findall(r"L[ib](\d+)E", m.group(2))))
+    return got

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import actor_numerics as an
+from actor_numerics import _neglogp64, _neglogp_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -124,31 +125,6 @@ def test_fused_policy_rollout_and_step_policy_within_bound(qa, torch, sets, name
 
 
 # ---------------------------------------------------------------------------------------------------- fused Runner
-def _neglogp64(W, u64, eps, squash):
-    logstd = np.asarray(W["logstd"], np.float32).astype(np.float64).reshape(1, 4)
-    nl = 0.5 * np.sum(np.square(eps), 1) + 0.5 * np.log(2 * np.pi) * 4 + np.sum(logstd)
-    if squash:
-        nl = nl + np.sum(np.log(1.0 - np.tanh(u64) ** 2 + 1e-6), 1)
-    return nl
-
-
-def _neglogp_bound(W, u64, m64, eps, mean_bound, squash):
-    """the kernel: u = fma(std, eps, mean) (one rounding), d = (u - mean) * inv_std on ITS mean, nl = nl_const + sum 0.5 d^2
-    (fma).  The mean's own error cancels in d, so d differs from eps by the roundings of u, of u - mean and of std / inv_std;
-    the squashed term log(sech^2 u + 1e-6) (slope <= 2 in u) also sees the error of u, i.e. the mean's bound plus u's rounding,
-    and the hardware exp2 / log2 (1 ulp, arguments up to 2|u| log2 e)."""
-    u32 = an.UNIT["f32"] * an.KAPPA["f32"]
-    std = np.exp(np.asarray(W["logstd"], np.float32).astype(np.float64)).reshape(1, 4)
-    dd = u32 * ((np.abs(u64) + np.abs(u64 - m64)) / std + 3.0 * np.abs(eps))
-    nl_const = abs(0.5 * np.log(2 * np.pi) * 4 + float(np.sum(np.asarray(W["logstd"], np.float64))))
-    b = np.sum(np.abs(eps) * dd + 0.5 * dd * dd, 1) + u32 * (2.0 * np.sum(eps * eps, 1) + 2.0 * nl_const)
-    if squash:
-        du = mean_bound + u32 * np.abs(u64)
-        L = np.log(1.0 - np.tanh(u64) ** 2 + 1e-6)
-        b = b + np.sum(2.0 * du + u32 * (4.0 * np.abs(u64) + 8.0 + np.abs(L)), 1)
-    return b
-
-
 @pytest.mark.parametrize("precision", PRECS)
 @pytest.mark.parametrize("name", an.WEIGHT_SETS)
 def test_fused_runner_within_bound(qa, torch, sets, name, precision):

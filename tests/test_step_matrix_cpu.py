@@ -2,7 +2,6 @@
 k_env_resident, k_hover) and of the evaluation kernels that share their step, as the built code object holds them, and every
 row names a GPU test case that exists -- a new instantiation without a test row fails here."""
 import os
-import re
 import subprocess
 import sys
 
@@ -13,17 +12,6 @@ import step_matrix
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = ("k_env_resident", "k_env_split", "k_env", "k_hover", "k_policy_evaluate_fast", "k_policy_evaluate")
-_SYM = re.compile(r"_GLOBAL__N_1\d+(%s)I((?:L[ib]\d+E)+)E" % "|".join(KERNELS))
-
-
-def instantiations(notes):
-    """{(kernel, template arguments...)} of the step and evaluation kernels in the code object's notes"""
-    got = set()
-    for sym in notes:
-        m = _SYM.search(sym)
-        if m:
-            got.add((m.group(1),) + tuple(int(a) for a in re.findall(r"L[ib](\d+)E", m.group(2))))
-    return got
 
 
 @pytest.fixture(scope="module")
@@ -34,7 +22,7 @@ def notes(tmp_path_factory):
 def test_rows_are_exactly_the_instantiations(notes):
     keys = [r["key"] for r in step_matrix.ROWS]
     assert len(keys) == len(set(keys)), "duplicate rows"
-    got = instantiations(notes)
+    got = kernel_notes.instantiations(notes, KERNELS)
     assert {k[0] for k in got} == set(KERNELS)
     assert set(keys) == got, "rows without an instantiation: %s; instantiations without a row: %s" % (
         sorted(set(keys) - got), sorted(got - set(keys)))
