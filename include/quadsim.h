@@ -493,7 +493,8 @@ int qs_expert_evaluate(QsEnv *env, int32_t episodes, int64_t max_steps, const fl
  *   Winner.  The highest score; ties go to the lowest index, so the result does not depend on how candidates are mapped to
  *     lanes, waves or workgroups.
  *   Outputs.  actions [N,4]: the first action of the winner; best_score [N], best_index [N], sequence [N,horizon,4] (all of
- *     the winner's actions) and scores [N,paths] (every candidate's score: the hook for MPPI / CEM weighting) are nullable.
+ *     the winner's actions) and scores [N,paths] (every candidate's score, for a caller's own weighting such as CEM; MPPI is qs_mppi_plan below) are
+ *     nullable.
  *     actions and sequence 16-byte aligned, best_score and scores 8-byte, best_index 4-byte.
  *   Read-only.  State, parameters, initial states, step counter, q_des and the rollout layout are not modified: the handle
  *     steps on afterwards as if the call had not been made (the contract of qs_policy_evaluate).
@@ -510,6 +511,51 @@ int qs_shooting_plan(QsEnv *env, int32_t horizon, int32_t paths, int32_t objecti
                      int32_t *best_index /* nullable [N] */,
                      float *sequence     /* nullable [N,horizon,4] the best candidate's actions */,
                      double *scores      /* nullable [N,paths] every candidate's score */);
+
+/* MPPI (model-predictive path integral control), ONE launch: `iterations` rounds of sampling around a nominal action sequence
+ * and softmax-weighted averaging, for all N docking envs on the exact simulator.  The nominal goes in and comes out, so a
+ * closed loop warm-starts every plan from the previous one (shift = 1); the loop itself (plan, qs_step) is the caller's.
+ *   Nominal.  U[h] = nominal_in[i][min(h + shift, horizon - 1)], h = 0 .. horizon-1, or zeros if nominal_in is null.  All of it
+ *     is read before anything is written: nominal_in may be nominal_out.
+ *   Candidates.  In iteration it, for c in [0, paths): a[c][h] = clamp(fma(sigma, z[c][h], U[h]), -1, 1) component-wise in
+ *     float32; candidate 0 is the nominal itself, a[0][h] = clamp(U[h], -1, 1), and has no draw.  Each candidate takes env.step
+ *     from a copy of the env's current state exactly as a candidate of qs_shooting_plan does: no reset inside the horizon, it
+ *     stops after its first done step.
+ *   Random keys.  z = noise[it][c][h] if noise is given (one array shared by all envs; row c = 0 is never read).  Else the
+ *     four normals of Philox4x32-10 block (1 << 63) | (k << 30) | (it << 26) | (c << 10) | h of subsequence (5 << 48) | gid,
+ *     gid = env_id_offset + i, k the handle's step counter at the call: Box-Muller on the (0,1] uniforms of the words, paired
+ *     as the policy sampler pairs them, (w.x, w.y) -> z0 = r cos, z1 = r sin and (w.z, w.w) -> z2, z3.  Bit 63 keeps these
+ *     blocks apart from every block qs_shooting_plan draws (those are below 2^62).  A plan repeated at the same k is
+ *     reproducible; candidate c of iteration it does not depend on `paths`; the first j iterations of a call with more
+ *     iterations are the call with iterations = j.
+ *   Score.  That of qs_shooting_plan under the same objective (QS_SHOOT_REWARD / QS_SHOOT_POSITION), a float64 sum.
+ *   Weights.  Smax = the largest score that is not NaN; w[c] = exp((S[c] - Smax) / lambda) in float64; a NaN score gives
+ *     w[c] = 0.
+ *   Update.  U'[h] = (float)(sum_c w[c] a[c][h] / sum_c w[c]) component-wise, both sums float64, over ALL horizon steps of
+ *     every candidate (also those behind its first done step).  The order of summation is a function of `paths` alone, so the
+ *     result does not depend on N, on the env's index in the handle, or on the queue mode.  If no weight is positive (every
+ *     score NaN: a non-finite state) U stays as it is.
+ *   Outputs.  nominal_out [N,horizon,4] = U after the last iteration; actions [N,4] = nominal_out[:,0]; best_score [N] = Smax
+ *     of the last iteration (-inf if every score was NaN); scores [N,iterations,paths]; trace [N,iterations+1,horizon,4] = U
+ *     before iteration 0 (after the shift) and after each iteration; candidates [N,paths,horizon,4] = a[c][h] of the LAST
+ *     iteration, the whole horizon of every candidate.  best_score, scores, trace, candidates are nullable.  nominal_in,
+ *     noise, actions, nominal_out, trace, candidates 16-byte aligned, best_score and scores 8-byte.
+ *   Read-only.  As qs_shooting_plan: nothing of the handle is modified.
+ *   1 <= paths <= 4096, 1 <= horizon <= 128, 1 <= iterations <= 16, lambda > 0 and finite, sigma >= 0 and finite, shift 0 or
+ *   1, step counter < 2^33, else QS_ERR_INVALID.  docking-v0 / v1 / v2, both integrators, every randomise mode, per-env params,
+ *   auto_reset 0 or 1, device buffers; hovering handles and QS_IO_HOST give QS_ERR_INVALID.  In private-queue mode pending
+ *   queue work is drained first.  The call reads the step counter back (one stream synchronisation) before it launches.
+ * Added after QS_VERSION 131 without changing it: callers detect this entry point by symbol (dlsym). */
+int qs_mppi_plan(QsEnv *env, int32_t horizon, int32_t paths, int32_t iterations, int32_t objective /* QS_SHOOT_* */,
+                 float lambda, float sigma, int32_t shift,
+                 const float *nominal_in /* nullable [N,horizon,4]; null = zeros; may alias nominal_out */,
+                 const float *noise      /* nullable [iterations,paths,horizon,4], shared by all envs; row c = 0 unused */,
+                 float *actions          /* [N,4] = nominal_out[:,0] */,
+                 float *nominal_out      /* [N,horizon,4] */,
+                 double *best_score      /* nullable [N] */,
+                 double *scores          /* nullable [N,iterations,paths] */,
+                 float *trace            /* nullable [N,iterations+1,horizon,4]: nominal before iteration 0 (after the shift), then after each */,
+                 float *candidates       /* nullable [N,paths,horizon,4]: the actions of the LAST iteration's candidates */);
 
 /* ---- layer-1 entry points: n independent drones / controllers (n need not equal N) ----------- */
 

@@ -555,15 +555,19 @@ __device__ __forceinline__ float q_tanh(float x, float &sech2)
 // four standard normals for (env gid, step k): Philox block k of the POLICY stream, Box-Muller on (0,1] uniforms,
 // (w.x, w.y) -> n0 = r cos, n1 = r sin; (w.z, w.w) -> n2, n3.  Stands in for tf.random_normal in
 // DiagGaussianProbabilityDistribution.sample (rl_baselines/common/distributions.py:426-430); pinned in the oracle.
-__device__ __forceinline__ void random_normal4(uint64_t seed, uint64_t gid, uint64_t k, float n[4])
+// normals_from_words is the arithmetic alone (the MPPI planner feeds it words of its own blocks, mppi.hpp).
+__device__ __forceinline__ void normals_from_words(const uint4 &w, float n[4])
 {
-    uint4 w = philox_block(seed, STREAM_POLICY, gid, k);
     float r0 = q_sqrt(-2.0f * q_ln(u01(w.x)));
     float r1 = q_sqrt(-2.0f * q_ln(u01(w.z)));
     float s0, c0, s1, c1;
     q_sincos(2.0f * kPi * u01(w.y), s0, c0);
     q_sincos(2.0f * kPi * u01(w.w), s1, c1);
     n[0] = r0 * c0; n[1] = r0 * s0; n[2] = r1 * c1; n[3] = r1 * s1;
+}
+__device__ __forceinline__ void random_normal4(uint64_t seed, uint64_t gid, uint64_t k, float n[4])
+{
+    normals_from_words(philox_block(seed, STREAM_POLICY, gid, k), n);
 }
 
 // per-env registers

@@ -22,6 +22,7 @@
 //     policy_kernels.hpp   the actor alone, in a T-step roll-out and over K complete episodes per env (qs_policy_*)
 //     runner_kernels.hpp   PPO2 data collection: the one-wave-per-tile and the role-split Runner kernel (qs_runner_rollout*)
 //     expert_rollout.hpp   the PID expert: one action, T steps, K complete episodes per env (qs_expert_*)
+//     shooting.hpp         random-shooting MPC (qs_shooting_plan)      mppi.hpp             the MPPI planner (qs_mppi_plan)
 //     env_groups.hpp       env groups (qs_set_groups)                  private_queue.hpp    private AQL queues (qs_set_queue_mode)
 //     host_util.hpp        host only: the last-error text (fail), HIP_TRY, roctx ranges, the device guard, and UserIO: how every
 //                          entry point hands the caller's buffers to its kernels (in place on a QS_IO_DEVICE handle, through the
@@ -45,6 +46,7 @@
 #include <dlfcn.h>
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <mutex>
 #include <new>
@@ -75,6 +77,7 @@ using namespace qs;
 #include "runner_kernels.hpp"
 #include "expert_rollout.hpp"
 #include "shooting.hpp"
+#include "mppi.hpp"
 
 #ifdef QS_STAMP
 static unsigned long long *g_host_stamps = nullptr;     // qs_debug_set_stamps: handed to every launch through StepArgs
@@ -194,7 +197,7 @@ void with_combo(const StepVariant &v, F &&f)
     if (v.integ == 0) with_combo_integ<0>(v, f);
     else with_combo_integ<1>(v, f);
 }
-// ... and f.operator()<INTEG, PARAMS>() for the kernels that have no RMODE (k_hover, k_shooting_plan).  <.., false> is named before
+// ... and f.operator()<INTEG, PARAMS>() for the kernels that have no RMODE (k_hover, k_shooting_plan, k_mppi).  <.., false> is named before
 // <.., true>: the order of instantiation shows in the machine code of two k_shooting_plan (one instruction each)
 template <class F>
 void with_integ_params(const StepVariant &v, F &&f)
@@ -1533,6 +1536,48 @@ int qs_shooting_plan(QsEnv *e, int32_t horizon, int32_t paths, int32_t objective
     const size_t lds = plan_lds_bytes(horizon);
     with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
         hipLaunchKernelGGL((k_shooting_plan<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(block), lds, e->stream, A, X);
+    });
+    HIP_TRY(hipGetLastError());
+    return QS_OK;
+}
+
+// ---- MPPI: iterated, warm-started sampling MPC ------------------------------------------------
+int qs_mppi_plan(QsEnv *e, int32_t horizon, int32_t paths, int32_t iterations, int32_t objective, float lambda, float sigma,
+                 int32_t shift, const float *nominal_in, const float *noise, float *actions, float *nominal_out,
+                 double *best_score, double *scores, float *trace, float *candidates)
+{
+    CHECK_ENV(e);
+    Range rg_("qs_mppi_plan");
+    if (e->cfg.kind == QS_KIND_HOVERING_V0) return fail(QS_ERR_INVALID, "qs_mppi_plan: docking envs only");
+    if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "qs_mppi_plan: device buffers only");
+    if (paths < 1 || paths > 4096) return fail(QS_ERR_INVALID, "qs_mppi_plan: paths must be in [1, 4096], got %d", paths);
+    if (horizon < 1 || horizon > 128) return fail(QS_ERR_INVALID, "qs_mppi_plan: horizon must be in [1, 128], got %d", horizon);
+    if (iterations < 1 || iterations > 16)
+        return fail(QS_ERR_INVALID, "qs_mppi_plan: iterations must be in [1, 16], got %d", iterations);
+    if (objective != QS_SHOOT_REWARD && objective != QS_SHOOT_POSITION)
+        return fail(QS_ERR_INVALID, "qs_mppi_plan: unknown objective %d", objective);
+    if (!(lambda > 0.0f) || !std::isfinite(lambda))
+        return fail(QS_ERR_INVALID, "qs_mppi_plan: lambda must be positive and finite, got %g", (double)lambda);
+    if (!(sigma >= 0.0f) || !std::isfinite(sigma))
+        return fail(QS_ERR_INVALID, "qs_mppi_plan: sigma must be non-negative and finite, got %g", (double)sigma);
+    if (shift != 0 && shift != 1) return fail(QS_ERR_INVALID, "qs_mppi_plan: shift must be 0 or 1, got %d", shift);
+    if (!actions || !nominal_out) return fail(QS_ERR_INVALID, "qs_mppi_plan: actions and nominal_out are required");
+    if (e->n > 0x7fffffff) return fail(QS_ERR_INVALID, "qs_mppi_plan: one workgroup per env: at most 2^31 - 1 envs");
+    if (((((uintptr_t)actions) | ((uintptr_t)nominal_out) | ((uintptr_t)nominal_in) | ((uintptr_t)noise) | ((uintptr_t)trace)
+          | ((uintptr_t)candidates)) & 15u) || ((((uintptr_t)best_score) | ((uintptr_t)scores)) & 7u))
+        return fail(QS_ERR_INVALID, "qs_mppi_plan: actions, nominal_in, nominal_out, noise, trace and candidates must be 16-byte aligned, best_score and scores 8-byte");
+    // the candidate keys hold the step counter in 33 bits: (1 << 63) | (k << 30) | (it << 26) | (c << 10) | h
+    unsigned long long k = 0;
+    HIP_TRY(hipMemcpyAsync(&k, e->d_ctr, sizeof k, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (k >> 33) return fail(QS_ERR_INVALID, "qs_mppi_plan: step counter %llu does not fit the 33 bits of the candidate keys", k);
+    const StepArgs A = make_args(e);
+    const MppiArgs X{horizon, paths, iterations, objective, shift, lambda, sigma, nominal_in, noise, actions, nominal_out,
+                     best_score, scores, trace, candidates};
+    const unsigned block = (unsigned)std::min<int64_t>(kBlock, ((int64_t)paths + kTile - 1) / kTile * kTile);
+    const size_t lds = mppi_lds_bytes(horizon, paths);      // < 64 KiB at the largest horizon and paths: no function attribute
+    with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
+        hipLaunchKernelGGL((k_mppi<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(block), lds, e->stream, A, X);
     });
     HIP_TRY(hipGetLastError());
     return QS_OK;

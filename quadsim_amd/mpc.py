@@ -1,9 +1,13 @@
-"""Random-shooting MPC on the exact simulator (qs_shooting_plan).
+"""Sampling-based MPC on the exact simulator: random shooting (qs_shooting_plan) and MPPI (qs_mppi_plan).
 
 ``Mpc_Controller.choose_action`` of MPC-based_RL.py:170-210 rolls 200 random action sequences of horizon 20 through a learned
 dynamics net, scores each by ``-sum |rel_pos|^2`` and applies the first action of the best one.  Here the model is the env
 itself: ``shooting_plan`` rolls ``paths`` candidates per env through ``horizon`` env steps in ONE launch, read-only on the
 env, and ``ShootingMPC`` is the closed loop of ``model_train`` (:213-241) without the dynamics net and its training.
+
+``mppi_plan`` / ``MPPI`` are the iterated, warm-started member of the same family (model-predictive path integral control):
+Gaussian candidates around a nominal action sequence, scored the same way, and the nominal replaced by their softmax-weighted
+mean, ``iterations`` times in one launch; the nominal is carried from plan to plan.
 """
 import ctypes as C
 
@@ -11,6 +15,10 @@ from . import _lib
 
 OBJECTIVES = {"reward": _lib.SHOOT_REWARD, "position": _lib.SHOOT_POSITION}
 MAX_PATHS, MAX_HORIZON = 65536, 256
+MPPI_MAX_PATHS, MPPI_MAX_HORIZON, MPPI_MAX_ITERATIONS = 4096, 128, 16
+# Tuned on ONE setting only (4096 docking-v0 envs, horizon 20, 200 paths, 2 iterations, objective "reward", 600 steps):
+# the sweep is in profiles/mppi/README.md.
+MPPI_DEFAULT_LAMBDA, MPPI_DEFAULT_SIGMA = 0.05, 0.25
 
 
 def check_plan_args(horizon, paths, objective):
@@ -73,4 +81,109 @@ class ShootingMPC:
         for _ in range(steps):
             _, r, d, _ = self.env.step(self.act())
             R.append(torch.as_tensor(r).clone()); D.append(torch.as_tensor(d).clone())
+        return torch.stack(R), torch.stack(D)
+
+
+def check_mppi_args(horizon, paths, iterations, objective, lam, sigma, shift):
+    """-> (horizon, paths, iterations, objective id, lam, sigma, shift as 0 / 1); ValueError for what qs_mppi_plan would
+    refuse, before anything touches the GPU"""
+    import math
+    if objective not in OBJECTIVES:
+        raise ValueError("objective must be one of %s, got %r" % (sorted(OBJECTIVES), objective))
+    horizon, paths, iterations = int(horizon), int(paths), int(iterations)
+    if not 1 <= horizon <= MPPI_MAX_HORIZON:
+        raise ValueError("horizon must be in [1, %d], got %d" % (MPPI_MAX_HORIZON, horizon))
+    if not 1 <= paths <= MPPI_MAX_PATHS:
+        raise ValueError("paths must be in [1, %d], got %d" % (MPPI_MAX_PATHS, paths))
+    if not 1 <= iterations <= MPPI_MAX_ITERATIONS:
+        raise ValueError("iterations must be in [1, %d], got %d" % (MPPI_MAX_ITERATIONS, iterations))
+    lam, sigma = float(lam), float(sigma)
+    if not (lam > 0.0 and math.isfinite(lam)):
+        raise ValueError("lam must be positive and finite, got %r" % lam)
+    if not (sigma >= 0.0 and math.isfinite(sigma)):
+        raise ValueError("sigma must be non-negative and finite, got %r" % sigma)
+    if not (isinstance(shift, (bool, int)) and shift in (0, 1)):
+        raise ValueError("shift must be False / True (or the int 0 / 1), got %r" % (shift,))
+    return horizon, paths, iterations, OBJECTIVES[objective], lam, sigma, int(shift)
+
+
+def mppi_plan(env, horizon=20, paths=200, iterations=2, objective="reward", lam=MPPI_DEFAULT_LAMBDA, sigma=MPPI_DEFAULT_SIGMA,
+              nominal=None, shift=False, noise=None, return_scores=False, return_trace=False, return_candidates=False):
+    """One MPPI plan for every env of `env` from its current state (the env is not modified), `iterations` refinement rounds in
+    one launch.  Candidate c >= 1 of a round is clamp(nominal + sigma z, -1, 1), candidate 0 the nominal itself; the new
+    nominal is the mean of the candidates weighted by exp((score - best score) / lam).  `nominal` [N,horizon,4] (float32,
+    device, contiguous) is the warm start, shifted by one step first if `shift`; None starts from zeros.  It is not written:
+    the result is a new tensor.  `noise` [iterations,paths,horizon,4] replaces the keyed in-kernel normals (shared by all envs).
+    Returns a dict of device tensors: actions [N,4] (= nominal[:,0]), nominal [N,horizon,4], best_score [N] float64, plus
+    scores [N,iterations,paths] float64, trace [N,iterations+1,horizon,4] (the nominal before the first round and after each)
+    and candidates [N,paths,horizon,4] (the last round's) on request.  The defaults of `lam` and `sigma` are tuned on one
+    setting only (4096 docking-v0 envs, horizon 20, 200 paths x 2 iterations, "reward"; profiles/mppi/README.md)."""
+    horizon, paths, iterations, obj, lam, sigma, shift = check_mppi_args(horizon, paths, iterations, objective, lam, sigma, shift)
+    import torch
+    n, dev = env.num_envs, env.device
+
+    def given(t, shape, name):
+        if t is None:
+            return None
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == torch.device(dev)
+                and tuple(t.shape) == shape and t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float32 tensor of shape %s on %s" % (name, shape, dev))
+        return t
+    nominal = given(nominal, (n, horizon, 4), "nominal")
+    noise = given(noise, (iterations, paths, horizon, 4), "noise")
+    out = {"actions": torch.empty((n, 4), dtype=torch.float32, device=dev),
+           "nominal": torch.empty((n, horizon, 4), dtype=torch.float32, device=dev),
+           "best_score": torch.empty((n,), dtype=torch.float64, device=dev)}
+    if return_scores:
+        out["scores"] = torch.empty((n, iterations, paths), dtype=torch.float64, device=dev)
+    if return_trace:
+        out["trace"] = torch.empty((n, iterations + 1, horizon, 4), dtype=torch.float32, device=dev)
+    if return_candidates:
+        out["candidates"] = torch.empty((n, paths, horizon, 4), dtype=torch.float32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+    env._use_current_stream()
+    env._inputs_ready()
+    _lib.check(env._lib.qs_mppi_plan(env._h, horizon, paths, iterations, obj, lam, sigma, shift, p(nominal), p(noise),
+                                     p(out["actions"]), p(out["nominal"]), p(out["best_score"]), p(out.get("scores")),
+                                     p(out.get("trace")), p(out.get("candidates"))), "qs_mppi_plan")
+    env._outputs_ready()
+    return out
+
+
+class MPPI:
+    """MPPI as a policy object beside ShootingMPC.  The nominal sequence [N,horizon,4] stays on the device between plans:
+    ``act()`` plans (shifting the previous nominal by one step after the first call) and returns the actions [N,4];
+    ``run(steps)`` is the closed loop ``a = act(); env.step(a)`` and, after each step, zeroes the nominal of the envs whose
+    episode ended (one masked op, no host synchronisation); ``reset()`` forgets the nominal.  `lam` and `sigma` default to
+    values tuned on one setting only (see ``mppi_plan``)."""
+
+    def __init__(self, env, horizon=20, paths=200, iterations=2, objective="reward", lam=MPPI_DEFAULT_LAMBDA,
+                 sigma=MPPI_DEFAULT_SIGMA):
+        self.horizon, self.paths, self.iterations, _, self.lam, self.sigma, _ = check_mppi_args(
+            horizon, paths, iterations, objective, lam, sigma, False)
+        self.env, self.objective = env, objective
+        self.nominal = None
+        self.last_plan = None
+
+    def reset(self):
+        self.nominal = None
+
+    def act(self):
+        self.last_plan = mppi_plan(self.env, self.horizon, self.paths, self.iterations, self.objective, self.lam, self.sigma,
+                                   nominal=self.nominal, shift=self.nominal is not None)
+        self.nominal = self.last_plan["nominal"]
+        return self.last_plan["actions"]
+
+    def run(self, steps):
+        """`steps` times plan + env.step -> (rewards [steps,N] float32, dones [steps,N] bool), device tensors"""
+        import torch
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("steps must be >= 1")
+        R, D = [], []
+        for _ in range(steps):
+            _, r, d, _ = self.env.step(self.act())
+            d = torch.as_tensor(d).clone()
+            self.nominal.masked_fill_(d.bool().view(-1, 1, 1), 0.0)     # a new episode starts from a cold nominal
+            R.append(torch.as_tensor(r).clone()); D.append(d)
         return torch.stack(R), torch.stack(D)

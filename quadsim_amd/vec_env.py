@@ -478,6 +478,12 @@ class VecDockingEnv:
         from .mpc import shooting_plan
         return shooting_plan(self, horizon, paths, objective, return_scores, return_sequence)
 
+    def mppi_plan(self, *args, **kwargs):
+        """MPPI from the envs' current states, read-only, one launch for all refinement iterations (qs_mppi_plan): the
+        arguments of quadsim_amd.mpc.mppi_plan after `env`"""
+        from .mpc import mppi_plan
+        return mppi_plan(self, *args, **kwargs)
+
     def seed(self, seed=None):
         return [seed] * self.num_envs
 

@@ -1,0 +1,234 @@
+"""-m "not gpu": qs_mppi_plan -- the C ABI from plain C99, the instantiations and resources of k_mppi in the built library
+(metadata only), the candidate keying and the update of the float64 reference (tests/mppi_ref.py), the Python argument
+checks."""
+import os
+import re
+import shutil
+import subprocess
+import types
+
+import numpy as np
+import pytest
+
+import kernel_notes
+import mppi_ref
+import shooting_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+C_PROGRAM = r"""
+#include <stdio.h>
+#include <string.h>
+#include "quadsim.h"
+typedef int (*mppi_fn)(QsEnv *, int32_t, int32_t, int32_t, int32_t, float, float, int32_t, const float *, const float *, float *,
+                       float *, double *, double *, float *, float *);
+int main(void) {
+    mppi_fn pl = &qs_mppi_plan;
+    static float act[4], nom[80];
+    int a = pl(NULL, 20, 200, 2, QS_SHOOT_REWARD, 1.0f, 0.5f, 0, NULL, NULL, act, nom, NULL, NULL, NULL, NULL);
+    printf("%d %d %d %s\n", a, QS_ERR_INVALID, qs_version(), strstr(qs_last_error(), "null handle") ? "msg" : "nomsg");
+    return 0;
+}
+"""
+
+MPPI_SIG = ("int qs_mppi_plan(QsEnv *env, int32_t horizon, int32_t paths, int32_t iterations, int32_t objective, float lambda, "
+            "float sigma, int32_t shift, const float *nominal_in, const float *noise, float *actions, float *nominal_out, "
+            "double *best_score, double *scores, float *trace, float *candidates);")
+
+
+def _declarations(header):
+    text = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    text = re.sub(r"\s+", " ", text)
+    return re.sub(r" ([,)])", r"\1", text)
+
+
+def test_mppi_abi_symbol_and_plain_c(tmp_path):
+    """the header declares the entry point with the agreed signature, the library exports it, QS_VERSION stays 131, and a C99
+    caller that takes its address compiles with -Wall -Werror and gets QS_ERR_INVALID with a message for a null handle"""
+    from quadsim_amd import _lib
+    _lib.build_library()
+    lib = _lib.load()
+    header = open(os.path.join(ROOT, "include", "quadsim.h")).read()
+    assert MPPI_SIG in _declarations(header)
+    assert hasattr(lib, "qs_mppi_plan") and "qs_mppi_plan" in _lib.EXPORTS
+    assert len(lib.qs_mppi_plan.argtypes) == 16
+    assert lib.qs_version() == 131
+    assert shutil.which("gcc") is not None
+    src = tmp_path / "mppi.c"
+    src.write_text(C_PROGRAM)
+    exe = str(tmp_path / "mppi")
+    libdir = os.path.join(ROOT, "quadsim_amd", "csrc")
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + libdir,
+                           "-lquadsim_hip", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib",
+                           "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    assert out.stdout.split() == ["-1", "-1", "131", "msg"]
+
+
+def test_mppi_kernel_instantiations_and_resources(tmp_path):
+    """exactly four k_mppi (INTEG x PARAMS; objective and noise source are runtime arguments); no private segment, no spills,
+    at most 128 VGPRs (four waves per SIMD), 256 threads at most, LDS dynamic"""
+    notes = kernel_notes.kernel_notes(kernel_notes.code_object(tmp_path))
+    got = {}
+    for sym in notes:
+        if "mppi" in sym:
+            m = re.search(r"\d+k_mppiILi(\d)ELb([01])EEEv", sym)
+            assert m, sym
+            got[(int(m.group(1)), int(m.group(2)))] = sym
+    assert set(got) == {(i, p) for i in (0, 1) for p in (0, 1)}, sorted(got)
+    for key, sym in got.items():
+        n = notes[sym]
+        print(key, n)
+        assert n["private_segment_fixed_size"] == 0 and n["vgpr_spill_count"] == 0, (key, n)
+        assert n["group_segment_fixed_size"] == 0 and n["max_flat_workgroup_size"] == 256, (key, n)
+        assert n["vgpr_count"] <= 128, (key, n)
+
+
+def test_keying_disjoint_from_shooting_and_prefix():
+    """bit 63 is set and the largest shooting block is below 2^62 < the smallest MPPI block; the fields fill the 63 bits
+    below exactly and their widths assert; candidate c does not depend on `paths`, step h not on `horizon`, and iteration
+    `it` of a key is the same whatever `iterations` is (it is a field of the key); draws differ between envs, iterations,
+    k and k + 1"""
+    B = mppi_ref.block_index
+    assert B(0, 0, 0, 0) == 1 << 63
+    assert B(0, 0, 0, 1) == (1 << 63) | 1 and B(0, 0, 1, 0) == (1 << 63) | (1 << 10)
+    assert B(0, 1, 0, 0) == (1 << 63) | (1 << 26) and B(1, 0, 0, 0) == (1 << 63) | (1 << 30)
+    assert B((1 << 33) - 1, 15, 65535, 1023) == (1 << 64) - 1
+    smallest = B(0, 0, 0, 0)
+    largest_shooting = shooting_ref.block_index((1 << 36) - 1, 65535, 1023)
+    assert largest_shooting < 1 << 62 < smallest                # the two ranges are [0, 2^62) and [2^63, 2^64)
+    for bad in ((1 << 33, 0, 0, 0), (0, 16, 0, 0), (0, 0, 1 << 16, 0), (0, 0, 0, 1 << 10), (-1, 0, 0, 0)):
+        with pytest.raises(AssertionError):
+            B(*bad)
+    # the vectorised words are the blocks of block_index, on the oracle's Philox
+    from oracle.pyoracle import Oracle
+    seed, gid, k = 12345, 7, 3
+    w = mppi_ref.words(seed, gid, k, 2, 70, 6)
+    for (it, c, h) in ((2, 0, 0), (2, 69, 5), (2, 1, 3)):
+        one = shooting_ref.philox_np(seed, (5 << 48) | gid, np.array([B(k, it, c, h)], np.uint64))[0]
+        assert np.array_equal(w[c, h], one)
+    # philox_np at a block below 2^62 is the oracle's generator: the same function serves both planners
+    assert np.array_equal(shooting_ref.philox_np(99, (5 << 48) | 11, np.array([12345], np.uint64))[0],
+                          Oracle("f64").philox(99, (5 << 48) | 11, 12345))
+    big = mppi_ref.normals(seed, gid, k, 2, 300, 20)
+    small = mppi_ref.normals(seed, gid, k, 2, 64, 5)
+    assert np.array_equal(small, big[:64, :5])
+    assert np.isfinite(big).all() and abs(big.mean()) < 0.03 and abs(big.std() - 1.0) < 0.03
+    for other in (mppi_ref.normals(seed, gid + 1, k, 2, 300, 20), mppi_ref.normals(seed, gid, k + 1, 2, 300, 20),
+                  mppi_ref.normals(seed, gid, k, 3, 300, 20), mppi_ref.normals(seed + 1, gid, k, 2, 300, 20)):
+        assert not np.array_equal(big, other)
+    flat = mppi_ref.words(seed, gid, k, 2, 300, 20).reshape(-1, 4)
+    assert len(np.unique(flat, axis=0)) == len(flat)
+
+
+def test_candidates32_is_one_rounding():
+    """fma32 against exact rational arithmetic on values chosen to sit on and around float32 ties, and the clamp / row 0"""
+    from fractions import Fraction
+    rng = np.random.default_rng(5)
+    a = rng.standard_normal(4000).astype(np.float32)
+    b = rng.standard_normal(4000).astype(np.float32)
+    c = (rng.standard_normal(4000) * 10.0 ** rng.integers(-12, 3, 4000)).astype(np.float32)
+    # exact ties: c + a*b with a*b = half an ulp of c
+    c[:8] = np.float32(1.0)
+    a[:8] = np.float32(2.0 ** -12)
+    b[:8] = np.float32(2.0 ** -12) * np.array([1, -1, 1, -1, 1, -1, 1, -1], np.float32)
+    c[4:8] = np.nextafter(np.float32(1.0), np.float32(2.0))
+    got = mppi_ref.fma32(a, b, c)
+    for i in range(len(a)):
+        exact = Fraction(float(a[i])) * Fraction(float(b[i])) + Fraction(float(c[i]))
+        lo = np.float32(float(exact))                   # float(Fraction) rounds once to binary64; refine around it
+        cand = [np.nextafter(lo, np.float32(-np.inf)), lo, np.nextafter(lo, np.float32(np.inf))]
+        best = min(cand, key=lambda x: (abs(Fraction(float(x)) - exact), int(np.float32(x).view(np.uint32)) & 1))
+        assert np.float32(got[i]) == np.float32(best), (i, a[i], b[i], c[i])
+    U = np.array([[[0.5, -0.5, 2.0, -0.0]]], np.float32)
+    z = np.array([[[9.0, 9.0, 9.0, 9.0]], [[1.0, -1.0, -4.0, 0.0]]], np.float32)
+    out = mppi_ref.candidates32(U, 0.75, z)
+    assert out.shape == (1, 2, 1, 4)
+    assert np.array_equal(out[0, 0, 0], np.array([0.5, -0.5, 1.0, -0.0], np.float32)) and np.signbit(out[0, 0, 0, 3])
+    assert np.array_equal(out[0, 1, 0], np.array([1.0, -1.0, -1.0, 0.0], np.float32))
+
+
+@pytest.fixture(scope="module")
+def oracle_plan():
+    """N = 4, paths 64, horizon 5 on the oracle: rocRAND-style starts, candidates around zero, float64 scores, computed once"""
+    from oracle.pyoracle import PAR_NOMINAL, Oracle
+    rec = Oracle("f64").env_init(4)
+    rng = np.random.default_rng(3)
+    rec[:, 0:3] += rng.uniform(-0.5, 0.5, (4, 3))
+    par = np.tile(np.array(PAR_NOMINAL), (4, 1))
+    z = mppi_ref.normals(23, 0, 2, 0, 64, 5).astype(np.float32)
+    U = np.zeros((4, 5, 4), np.float32)
+    cands = mppi_ref.candidates32(U, 0.5, z)
+    scores = shooting_ref.plan_scores(rec, par, cands)
+    return rec, par, z, U, cands, scores
+
+
+def test_update64_limits_and_nan_rule(oracle_plan):
+    rec, par, z, U, cands, scores = oracle_plan
+    assert scores.shape == (4, 64) and all(len(np.unique(s)) > 32 for s in scores)
+    # a temperature far above the spread of the scores: the plain mean of the candidates
+    flat = mppi_ref.update64(scores, cands, 1e6)
+    assert np.max(np.abs(flat - cands.astype(np.float64).mean(axis=1))) <= 1e-6
+    # a temperature far below the smallest gap: the first-argmax candidate, exactly
+    cold = mppi_ref.update64(scores, cands, 1e-9)
+    win = shooting_ref.first_argmax(scores)
+    assert np.array_equal(cold, cands[np.arange(4), win].astype(np.float64))
+    # every score NaN: U stays
+    U1 = np.full((4, 5, 4), 0.25, np.float32)
+    s = scores.copy()
+    s[2] = np.nan
+    out = mppi_ref.update64(s, cands, 0.5, U1)
+    assert np.array_equal(out[2], U1[2].astype(np.float64)) and not np.array_equal(out[1], U1[1].astype(np.float64))
+    assert np.array_equal(out[[0, 1, 3]], mppi_ref.update64(scores, cands, 0.5, U1)[[0, 1, 3]])
+    # one NaN candidate has no influence: the same as leaving it out, whatever its actions are
+    s = scores.copy()
+    s[:, 7] = np.nan
+    c2 = cands.copy()
+    c2[:, 7] = 1.0
+    keep = np.arange(64) != 7
+    a = mppi_ref.update64(s, c2, 0.5)
+    b = mppi_ref.update64(scores[:, keep], cands[:, keep], 0.5)
+    assert np.max(np.abs(a - b)) <= 1e-15
+    # plan64 is candidates32 + plan_scores + update64
+    got, S, _ = mppi_ref.plan64(rec, par, U, 0.5, z, 0.5)
+    assert np.array_equal(S, scores) and np.array_equal(got, mppi_ref.update64(scores, cands, 0.5, U))
+
+
+def test_python_argument_checks_raise_before_any_gpu_work():
+    """ValueError for every out-of-range argument; the env is never touched (it is an empty namespace here)"""
+    import quadsim_amd
+    env = types.SimpleNamespace()
+    bad = (dict(objective="cost"), dict(objective=0), dict(horizon=0), dict(horizon=129), dict(paths=0), dict(paths=4097),
+           dict(iterations=0), dict(iterations=17), dict(lam=0.0), dict(lam=-1.0), dict(lam=float("inf")), dict(lam=float("nan")),
+           dict(sigma=-1.0), dict(sigma=float("inf")), dict(sigma=float("nan")))
+    for kw in bad:
+        with pytest.raises(ValueError):
+            quadsim_amd.mppi_plan(env, **kw)
+        with pytest.raises(ValueError):
+            quadsim_amd.VecDockingEnv.mppi_plan(env, **kw)
+        with pytest.raises(ValueError):
+            quadsim_amd.MPPI(env, **kw)
+    for kw in (dict(shift=2), dict(shift=-1), dict(shift="yes"), dict(shift=1.0), dict(shift=None), dict(shift=np.array([0, 1]))):
+        with pytest.raises(ValueError):
+            quadsim_amd.mppi_plan(env, **kw)
+    # the limits themselves pass the checks
+    from quadsim_amd import mpc
+    assert mpc.check_mppi_args(128, 4096, 16, "position", 1e-3, 0.0, True) == (128, 4096, 16, 1, 1e-3, 0.0, 1)
+
+
+def test_mppi_defaults_and_run_zero():
+    import quadsim_amd
+    from quadsim_amd import mpc
+    ctl = quadsim_amd.MPPI(types.SimpleNamespace())
+    assert (ctl.horizon, ctl.paths, ctl.iterations, ctl.objective) == (20, 200, 2, "reward")
+    assert (ctl.lam, ctl.sigma) == (mpc.MPPI_DEFAULT_LAMBDA, mpc.MPPI_DEFAULT_SIGMA)
+    # the documented defaults: the cell with the best mean return of the recorded sweep (profiles/mppi/mppi_sweep.json)
+    import json
+    rows = [r for r in json.load(open(os.path.join(ROOT, "profiles", "mppi", "mppi_sweep.json")))["rows"] if r["controller"] == "mppi"]
+    best = max(rows, key=lambda r: r["mean_return"])
+    assert len(rows) >= 9 and (ctl.lam, ctl.sigma) == (best["lam"], best["sigma"]) == (0.05, 0.25)
+    assert (ctl.horizon, ctl.paths, ctl.iterations) == (20, best["paths"], best["iterations"])
+    assert ctl.nominal is None
+    with pytest.raises(ValueError):
+        ctl.run(0)
