@@ -1508,76 +1508,73 @@ int qs_expert_evaluate(QsEnv *e, int32_t episodes, int64_t max_steps, const floa
     return QS_OK;
 }
 
-// ---- random-shooting MPC ---------------------------------------------------------------------
+// ---- the sampling planners: random-shooting MPC and MPPI --------------------------------------
+// What both entry points check alike, after their own arguments; then the step counter, read synchronously: the candidate
+// keys hold it in `key_bits` bits (shooting: (k << 26) | (c << 10) | h; MPPI: (1 << 63) | (k << 30) | (it << 26) | (c << 10) | h).
+static int plan_prepare(QsEnv *e, const char *name, int horizon, int max_horizon, int paths, int max_paths, int objective, int key_bits)
+{
+    if (e->cfg.kind == QS_KIND_HOVERING_V0) return fail(QS_ERR_INVALID, "%s: docking envs only", name);
+    if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "%s: device buffers only", name);
+    if (paths < 1 || paths > max_paths) return fail(QS_ERR_INVALID, "%s: paths must be in [1, %d], got %d", name, max_paths, paths);
+    if (horizon < 1 || horizon > max_horizon)
+        return fail(QS_ERR_INVALID, "%s: horizon must be in [1, %d], got %d", name, max_horizon, horizon);
+    if (objective != QS_SHOOT_REWARD && objective != QS_SHOOT_POSITION) return fail(QS_ERR_INVALID, "%s: unknown objective %d", name, objective);
+    if (e->n > 0x7fffffff) return fail(QS_ERR_INVALID, "%s: one workgroup per env: at most 2^31 - 1 envs", name);
+    unsigned long long k = 0;
+    HIP_TRY(hipMemcpyAsync(&k, e->d_ctr, sizeof k, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (k >> key_bits)
+        return fail(QS_ERR_INVALID, "%s: step counter %llu does not fit the %d bits of the candidate keys", name, k, key_bits);
+    return QS_OK;
+}
+
+// min(256, paths rounded up to a wave) threads
+static unsigned plan_block(int paths) { return (unsigned)std::min<int64_t>(kBlock, ((int64_t)paths + kTile - 1) / kTile * kTile); }
+
 int qs_shooting_plan(QsEnv *e, int32_t horizon, int32_t paths, int32_t objective, float *actions, double *best_score,
                      int32_t *best_index, float *sequence, double *scores)
 {
     CHECK_ENV(e);
     Range rg_("qs_shooting_plan");
-    if (e->cfg.kind == QS_KIND_HOVERING_V0) return fail(QS_ERR_INVALID, "qs_shooting_plan: docking envs only");
-    if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "qs_shooting_plan: device buffers only");
-    if (paths < 1 || paths > 65536) return fail(QS_ERR_INVALID, "qs_shooting_plan: paths must be in [1, 65536], got %d", paths);
-    if (horizon < 1 || horizon > 256) return fail(QS_ERR_INVALID, "qs_shooting_plan: horizon must be in [1, 256], got %d", horizon);
-    if (objective != QS_SHOOT_REWARD && objective != QS_SHOOT_POSITION)
-        return fail(QS_ERR_INVALID, "qs_shooting_plan: unknown objective %d", objective);
     if (!actions) return fail(QS_ERR_INVALID, "qs_shooting_plan: actions is required");
-    if (e->n > 0x7fffffff) return fail(QS_ERR_INVALID, "qs_shooting_plan: one workgroup per env: at most 2^31 - 1 envs");
     if (((((uintptr_t)actions) | ((uintptr_t)sequence)) & 15u) || ((((uintptr_t)best_score) | ((uintptr_t)scores)) & 7u)
         || (((uintptr_t)best_index) & 3u))
         return fail(QS_ERR_INVALID, "qs_shooting_plan: actions and sequence must be 16-byte aligned, best_score and scores 8-byte, best_index 4-byte");
-    // the candidate keys hold the step counter in 36 bits: (k << 26) | (c << 10) | h
-    unsigned long long k = 0;
-    HIP_TRY(hipMemcpyAsync(&k, e->d_ctr, sizeof k, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (k >> 36) return fail(QS_ERR_INVALID, "qs_shooting_plan: step counter %llu does not fit the 36 bits of the candidate keys", k);
+    if (int rc = plan_prepare(e, "qs_shooting_plan", horizon, 256, paths, 65536, objective, 36)) return rc;
     const StepArgs A = make_args(e);
     const PlanArgs X{horizon, paths, objective, actions, best_score, best_index, sequence, scores};
-    const unsigned block = (unsigned)std::min<int64_t>(kBlock, ((int64_t)paths + kTile - 1) / kTile * kTile);
     const size_t lds = plan_lds_bytes(horizon);
     with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
-        hipLaunchKernelGGL((k_shooting_plan<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(block), lds, e->stream, A, X);
+        hipLaunchKernelGGL((k_shooting_plan<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(plan_block(paths)), lds, e->stream, A, X);
     });
     HIP_TRY(hipGetLastError());
     return QS_OK;
 }
 
-// ---- MPPI: iterated, warm-started sampling MPC ------------------------------------------------
 int qs_mppi_plan(QsEnv *e, int32_t horizon, int32_t paths, int32_t iterations, int32_t objective, float lambda, float sigma,
                  int32_t shift, const float *nominal_in, const float *noise, float *actions, float *nominal_out,
                  double *best_score, double *scores, float *trace, float *candidates)
 {
     CHECK_ENV(e);
     Range rg_("qs_mppi_plan");
-    if (e->cfg.kind == QS_KIND_HOVERING_V0) return fail(QS_ERR_INVALID, "qs_mppi_plan: docking envs only");
-    if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "qs_mppi_plan: device buffers only");
-    if (paths < 1 || paths > 4096) return fail(QS_ERR_INVALID, "qs_mppi_plan: paths must be in [1, 4096], got %d", paths);
-    if (horizon < 1 || horizon > 128) return fail(QS_ERR_INVALID, "qs_mppi_plan: horizon must be in [1, 128], got %d", horizon);
     if (iterations < 1 || iterations > 16)
         return fail(QS_ERR_INVALID, "qs_mppi_plan: iterations must be in [1, 16], got %d", iterations);
-    if (objective != QS_SHOOT_REWARD && objective != QS_SHOOT_POSITION)
-        return fail(QS_ERR_INVALID, "qs_mppi_plan: unknown objective %d", objective);
     if (!(lambda > 0.0f) || !std::isfinite(lambda))
         return fail(QS_ERR_INVALID, "qs_mppi_plan: lambda must be positive and finite, got %g", (double)lambda);
     if (!(sigma >= 0.0f) || !std::isfinite(sigma))
         return fail(QS_ERR_INVALID, "qs_mppi_plan: sigma must be non-negative and finite, got %g", (double)sigma);
     if (shift != 0 && shift != 1) return fail(QS_ERR_INVALID, "qs_mppi_plan: shift must be 0 or 1, got %d", shift);
     if (!actions || !nominal_out) return fail(QS_ERR_INVALID, "qs_mppi_plan: actions and nominal_out are required");
-    if (e->n > 0x7fffffff) return fail(QS_ERR_INVALID, "qs_mppi_plan: one workgroup per env: at most 2^31 - 1 envs");
     if (((((uintptr_t)actions) | ((uintptr_t)nominal_out) | ((uintptr_t)nominal_in) | ((uintptr_t)noise) | ((uintptr_t)trace)
           | ((uintptr_t)candidates)) & 15u) || ((((uintptr_t)best_score) | ((uintptr_t)scores)) & 7u))
         return fail(QS_ERR_INVALID, "qs_mppi_plan: actions, nominal_in, nominal_out, noise, trace and candidates must be 16-byte aligned, best_score and scores 8-byte");
-    // the candidate keys hold the step counter in 33 bits: (1 << 63) | (k << 30) | (it << 26) | (c << 10) | h
-    unsigned long long k = 0;
-    HIP_TRY(hipMemcpyAsync(&k, e->d_ctr, sizeof k, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (k >> 33) return fail(QS_ERR_INVALID, "qs_mppi_plan: step counter %llu does not fit the 33 bits of the candidate keys", k);
+    if (int rc = plan_prepare(e, "qs_mppi_plan", horizon, 128, paths, 4096, objective, 33)) return rc;
     const StepArgs A = make_args(e);
     const MppiArgs X{horizon, paths, iterations, objective, shift, lambda, sigma, nominal_in, noise, actions, nominal_out,
                      best_score, scores, trace, candidates};
-    const unsigned block = (unsigned)std::min<int64_t>(kBlock, ((int64_t)paths + kTile - 1) / kTile * kTile);
     const size_t lds = mppi_lds_bytes(horizon, paths);      // < 64 KiB at the largest horizon and paths: no function attribute
     with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
-        hipLaunchKernelGGL((k_mppi<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(block), lds, e->stream, A, X);
+        hipLaunchKernelGGL((k_mppi<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(plan_block(paths)), lds, e->stream, A, X);
     });
     HIP_TRY(hipGetLastError());
     return QS_OK;

@@ -21,16 +21,46 @@ MPPI_MAX_PATHS, MPPI_MAX_HORIZON, MPPI_MAX_ITERATIONS = 4096, 128, 16
 MPPI_DEFAULT_LAMBDA, MPPI_DEFAULT_SIGMA = 0.05, 0.25
 
 
-def check_plan_args(horizon, paths, objective):
-    """-> (horizon, paths, objective id); ValueError for what qs_shooting_plan would refuse, before anything touches the GPU"""
+def _check_common(horizon, paths, objective, max_horizon, max_paths):
+    """-> (horizon, paths, objective id), what both planners check alike"""
     if objective not in OBJECTIVES:
         raise ValueError("objective must be one of %s, got %r" % (sorted(OBJECTIVES), objective))
     horizon, paths = int(horizon), int(paths)
-    if not 1 <= horizon <= MAX_HORIZON:
-        raise ValueError("horizon must be in [1, %d], got %d" % (MAX_HORIZON, horizon))
-    if not 1 <= paths <= MAX_PATHS:
-        raise ValueError("paths must be in [1, %d], got %d" % (MAX_PATHS, paths))
+    if not 1 <= horizon <= max_horizon:
+        raise ValueError("horizon must be in [1, %d], got %d" % (max_horizon, horizon))
+    if not 1 <= paths <= max_paths:
+        raise ValueError("paths must be in [1, %d], got %d" % (max_paths, paths))
     return horizon, paths, OBJECTIVES[objective]
+
+
+def _call(env, fn_name, *args):
+    """one planner entry point on the handle of `env` (tensors as their device pointers, None as NULL), in the env's stream"""
+    args = [C.c_void_p(a.data_ptr()) if hasattr(a, "data_ptr") else a for a in args]
+    env._use_current_stream()
+    env._inputs_ready()
+    _lib.check(getattr(env._lib, fn_name)(env._h, *args), fn_name)
+    env._outputs_ready()
+
+
+def _closed_loop(env, act, steps, after_step=None):
+    """`steps` times ``env.step(act())`` -> (rewards [steps,N] float32, dones [steps,N] bool); after_step(done) follows each step"""
+    import torch
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError("steps must be >= 1")
+    R, D = [], []
+    for _ in range(steps):
+        _, r, d, _ = env.step(act())
+        d = torch.as_tensor(d).clone()
+        if after_step is not None:
+            after_step(d)
+        R.append(torch.as_tensor(r).clone()); D.append(d)
+    return torch.stack(R), torch.stack(D)
+
+
+def check_plan_args(horizon, paths, objective):
+    """-> (horizon, paths, objective id); ValueError for what qs_shooting_plan would refuse, before anything touches the GPU"""
+    return _check_common(horizon, paths, objective, MAX_HORIZON, MAX_PATHS)
 
 
 def shooting_plan(env, horizon=20, paths=200, objective="reward", return_scores=False, return_sequence=False):
@@ -49,12 +79,8 @@ def shooting_plan(env, horizon=20, paths=200, objective="reward", return_scores=
         out["sequence"] = torch.empty((n, horizon, 4), dtype=torch.float32, device=dev)
     if return_scores:
         out["scores"] = torch.empty((n, paths), dtype=torch.float64, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-    env._use_current_stream()
-    env._inputs_ready()
-    _lib.check(env._lib.qs_shooting_plan(env._h, horizon, paths, obj, p(out["actions"]), p(out["best_score"]), p(out["best_index"]),
-                                         p(out.get("sequence")), p(out.get("scores"))), "qs_shooting_plan")
-    env._outputs_ready()
+    _call(env, "qs_shooting_plan", horizon, paths, obj, out["actions"], out["best_score"], out["best_index"], out.get("sequence"),
+          out.get("scores"))
     return out
 
 
@@ -73,28 +99,15 @@ class ShootingMPC:
 
     def run(self, steps):
         """`steps` times plan + env.step -> (rewards [steps,N] float32, dones [steps,N] bool), device tensors"""
-        import torch
-        steps = int(steps)
-        if steps < 1:
-            raise ValueError("steps must be >= 1")
-        R, D = [], []
-        for _ in range(steps):
-            _, r, d, _ = self.env.step(self.act())
-            R.append(torch.as_tensor(r).clone()); D.append(torch.as_tensor(d).clone())
-        return torch.stack(R), torch.stack(D)
+        return _closed_loop(self.env, self.act, steps)
 
 
 def check_mppi_args(horizon, paths, iterations, objective, lam, sigma, shift):
     """-> (horizon, paths, iterations, objective id, lam, sigma, shift as 0 / 1); ValueError for what qs_mppi_plan would
     refuse, before anything touches the GPU"""
     import math
-    if objective not in OBJECTIVES:
-        raise ValueError("objective must be one of %s, got %r" % (sorted(OBJECTIVES), objective))
-    horizon, paths, iterations = int(horizon), int(paths), int(iterations)
-    if not 1 <= horizon <= MPPI_MAX_HORIZON:
-        raise ValueError("horizon must be in [1, %d], got %d" % (MPPI_MAX_HORIZON, horizon))
-    if not 1 <= paths <= MPPI_MAX_PATHS:
-        raise ValueError("paths must be in [1, %d], got %d" % (MPPI_MAX_PATHS, paths))
+    horizon, paths, obj = _check_common(horizon, paths, objective, MPPI_MAX_HORIZON, MPPI_MAX_PATHS)
+    iterations = int(iterations)
     if not 1 <= iterations <= MPPI_MAX_ITERATIONS:
         raise ValueError("iterations must be in [1, %d], got %d" % (MPPI_MAX_ITERATIONS, iterations))
     lam, sigma = float(lam), float(sigma)
@@ -104,7 +117,7 @@ def check_mppi_args(horizon, paths, iterations, objective, lam, sigma, shift):
         raise ValueError("sigma must be non-negative and finite, got %r" % sigma)
     if not (isinstance(shift, (bool, int)) and shift in (0, 1)):
         raise ValueError("shift must be False / True (or the int 0 / 1), got %r" % (shift,))
-    return horizon, paths, iterations, OBJECTIVES[objective], lam, sigma, int(shift)
+    return horizon, paths, iterations, obj, lam, sigma, int(shift)
 
 
 def mppi_plan(env, horizon=20, paths=200, iterations=2, objective="reward", lam=MPPI_DEFAULT_LAMBDA, sigma=MPPI_DEFAULT_SIGMA,
@@ -140,13 +153,8 @@ def mppi_plan(env, horizon=20, paths=200, iterations=2, objective="reward", lam=
         out["trace"] = torch.empty((n, iterations + 1, horizon, 4), dtype=torch.float32, device=dev)
     if return_candidates:
         out["candidates"] = torch.empty((n, paths, horizon, 4), dtype=torch.float32, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-    env._use_current_stream()
-    env._inputs_ready()
-    _lib.check(env._lib.qs_mppi_plan(env._h, horizon, paths, iterations, obj, lam, sigma, shift, p(nominal), p(noise),
-                                     p(out["actions"]), p(out["nominal"]), p(out["best_score"]), p(out.get("scores")),
-                                     p(out.get("trace")), p(out.get("candidates"))), "qs_mppi_plan")
-    env._outputs_ready()
+    _call(env, "qs_mppi_plan", horizon, paths, iterations, obj, lam, sigma, shift, nominal, noise, out["actions"], out["nominal"],
+          out["best_score"], out.get("scores"), out.get("trace"), out.get("candidates"))
     return out
 
 
@@ -176,14 +184,5 @@ class MPPI:
 
     def run(self, steps):
         """`steps` times plan + env.step -> (rewards [steps,N] float32, dones [steps,N] bool), device tensors"""
-        import torch
-        steps = int(steps)
-        if steps < 1:
-            raise ValueError("steps must be >= 1")
-        R, D = [], []
-        for _ in range(steps):
-            _, r, d, _ = self.env.step(self.act())
-            d = torch.as_tensor(d).clone()
-            self.nominal.masked_fill_(d.bool().view(-1, 1, 1), 0.0)     # a new episode starts from a cold nominal
-            R.append(torch.as_tensor(r).clone()); D.append(d)
-        return torch.stack(R), torch.stack(D)
+        # a new episode starts from a cold nominal
+        return _closed_loop(self.env, self.act, steps, lambda d: self.nominal.masked_fill_(d.bool().view(-1, 1, 1), 0.0))

@@ -12,18 +12,12 @@ import numpy as np
 import pytest
 
 import mppi_ref
+from plan_cases import DT, HANDLES, HORIZONS, N, PATHS, SEED, in_flight_pair, make_handle, make_twin, slice_handle, twin_scores
+from plan_cases import rec_par as _rec_par, same as _same, same_bits as _same_bits, snapshot as _snapshot
 
 pytestmark = pytest.mark.gpu
 
-N = 96                               # one full tile and a tail tile
-PATHS = (1, 64, 200, 1000)           # one lane, one wave, a ragged last wave, a lane loop (4 candidates per lane, ragged)
-HORIZONS = (1, 3, 20)
 ITERATIONS = (1, 3)
-KINDS = ("docking-v0", "docking-v1", "docking-v2")
-SEED = 23
-PAR_NOM = np.array([0.18, 0.00025, 0.000232, 0.0003738])
-DT = float(np.float32(0.02))
-HANDLES = [(k, g, p) for k in KINDS for g in ("frozen", "rk4") for p in (False, True)]
 SUBSET = [("docking-v0", "frozen", False), ("docking-v1", "rk4", True), ("docking-v2", "frozen", True), ("docking-v0", "rk4", False)]
 LAM, SIGMA = 0.5, 0.4
 
@@ -40,56 +34,7 @@ def torch():
     return torch
 
 
-# ---------------------------------------------------------------- handles and their states (the recipe of the shooting tests)
-def _make(qa, env_id, integ, params, n=N, provoke="all", offset=0, auto_reset=True):
-    """a handle with rocRAND initial states (docking-v1: its own stored jittered starts) after a reset and two random steps
-    (stored controls and last_shaping are live, k = 2), then -- by env index modulo 6 --
-      0  t = 595: times out at horizon step 5;          1  t = 599: times out at the first step;
-      2  chaser at z = 0.13 m falling at 2 m/s: under the 0.1 m floor after the first step, whatever the action;
-      3  ("all" only) chaser 0.17 m up falling at 2 m/s: crosses the floor around the second step, action-dependent;
-      4  ("all" only) chaser's port 5 cm from the target's with zero relative velocity: inside the docked thresholds;
-      5  untouched.
-    provoke="decisive" leaves 3 and 4 out: there a float32 and a float64 simulator may decide a threshold differently."""
-    kw = dict(num_envs=n, seed=SEED, integrator=integ, env_id_offset=offset, auto_reset=auto_reset)
-    if env_id != "docking-v1":
-        kw.update(randomise=1, init_range=qa.C3_INIT_RANGE)
-    env = qa.VecDockingEnv(env_id, **kw)
-    rng = np.random.default_rng(SEED)
-    if params:
-        env.set_params(mass=(0.18 * rng.uniform(0.85, 1.15, n)).astype(np.float32),
-                       inertia=(PAR_NOM[1:] * rng.uniform(0.85, 1.15, (n, 3))).astype(np.float32))
-    env.reset()
-    for a in env.random_actions(2, step0=0):
-        env.step(a)
-    if provoke:
-        st = env.get_state()
-        idx = np.arange(n)
-        t0, c = st["t"].copy(), st["chaser"].copy()
-        t0[idx % 6 == 0] = 595.0
-        t0[idx % 6 == 1] = 599.0
-        for m, z in ((2, 0.13), (3, 0.17)):
-            sel = idx % 6 == m
-            if m == 3 and provoke != "all":
-                continue
-            c[sel, 2] = z
-            c[sel, 3:6] = np.array([0.0, 0.0, -2.0], np.float32)
-        if provoke == "all":
-            sel = idx % 6 == 4
-            c[sel] = st["target"][sel]
-            c[sel, 0] -= 0.25                                # ports at +0.1 / -0.1: 5 cm apart
-        env.set_state(chaser=c, t=t0)
-    return env
-
-
-def _rec_par(env):
-    st = env.get_state()
-    rec = np.zeros((env.num_envs, 40), np.float64)
-    rec[:, 0:13], rec[:, 13:26], rec[:, 26:34], rec[:, 34:38] = st["chaser"], st["target"], st["u_prev"], st["qdes"]
-    rec[:, 38], rec[:, 39] = st["last_shaping"], st["t"]
-    m, i = env.get_params()
-    return st, rec, np.concatenate([m[:, None], i], axis=1).astype(np.float64)
-
-
+# ---------------------------------------------------------------- plans
 def _plan(env, horizon, paths, iterations=1, objective="reward", lam=LAM, sigma=SIGMA, **kw):
     kw.setdefault("return_scores", True)
     kw.setdefault("return_trace", True)
@@ -98,28 +43,16 @@ def _plan(env, horizon, paths, iterations=1, objective="reward", lam=LAM, sigma=
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def _bits(x):
-    return np.ascontiguousarray(x).view(np.uint32 if x.dtype.itemsize == 4 else np.uint64)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
 # ---------------------------------------------------------------- 1. scores, bit for bit
 @pytest.mark.parametrize("env_id,integ,params", HANDLES)
 def test_scores_bit_for_bit_and_iteration_prefix(qa, torch, env_id, integ, params):
-    env = _make(qa, env_id, integ, params)
+    env = make_handle(qa, env_id, integ, params)
     k = env.step_counter
     st, _, _ = _rec_par(env)
-    mass, inertia = env.get_params()
     stopped_inside = 0
     iters = max(ITERATIONS)
     for paths in PATHS:
-        rep = lambda x: np.repeat(x, paths, axis=0)           # noqa: E731
-        twin = qa.VecDockingEnv(env_id, num_envs=N * paths, integrator=integ, auto_reset=False, seed=SEED + 1)
-        if params:
-            twin.set_params(mass=rep(mass), inertia=rep(inertia))
+        twin = make_twin(qa, env, env_id, integ, params, paths)
         for horizon in HORIZONS:
             full = None
             for j in range(iters, 0, -1):
@@ -128,19 +61,10 @@ def test_scores_bit_for_bit_and_iteration_prefix(qa, torch, env_id, integ, param
                     full = got
                 assert _same_bits(got["scores"], full["scores"][:, :j]), (paths, horizon, j)      # iteration prefix
                 assert _same_bits(got["trace"], full["trace"][:, :j + 1]), (paths, horizon, j)
-                twin.set_state(chaser=rep(st["chaser"]), target=rep(st["target"]), u_prev=rep(st["u_prev"]),
-                               qdes=rep(st["qdes"]), last_shaping=rep(st["last_shaping"]), t=rep(st["t"]))
                 acts = got["candidates"]
                 assert acts.shape == (N, paths, horizon, 4) and np.all(np.abs(acts) <= 1.0)
-                staged = torch.from_numpy(np.ascontiguousarray(acts.reshape(N * paths, horizon, 4).transpose(1, 0, 2))).to(env.device)
-                total = torch.zeros(N * paths, dtype=torch.float64, device=env.device)
-                alive = torch.ones(N * paths, dtype=torch.bool, device=env.device)
-                for h in range(horizon):
-                    _, r, d, _ = twin.step(staged[h])
-                    total += torch.where(alive, r.double(), torch.zeros_like(total))
-                    alive &= ~d
-                want = total.cpu().numpy().reshape(N, paths)
-                stopped_inside += int((~alive).sum())
+                want, stopped = twin_scores(torch, twin, st, acts, paths)
+                stopped_inside += stopped
                 assert _same_bits(got["scores"][:, j - 1], want), (paths, horizon, j)
                 assert _same_bits(got["best_score"], want.max(axis=1)), (paths, horizon, j)
         twin.close()
@@ -152,7 +76,7 @@ def test_scores_bit_for_bit_and_iteration_prefix(qa, torch, env_id, integ, param
 # ---------------------------------------------------------------- 2. candidates with caller noise, shift, zero nominal
 @pytest.mark.parametrize("env_id,integ,params", SUBSET)
 def test_candidates_exact_with_caller_noise(qa, torch, env_id, integ, params):
-    env = _make(qa, env_id, integ, params)
+    env = make_handle(qa, env_id, integ, params)
     gen = torch.Generator(device="cpu").manual_seed(7)
     for paths in PATHS:
         for horizon in HORIZONS:
@@ -185,7 +109,7 @@ UPDATE_TOL = 2.0 * 2.0 ** -24
 
 @pytest.mark.parametrize("env_id,integ,params", SUBSET)
 def test_update_against_float64_on_device_outputs(qa, torch, env_id, integ, params):
-    env = _make(qa, env_id, integ, params)
+    env = make_handle(qa, env_id, integ, params)
     gen = torch.Generator(device="cpu").manual_seed(11)
     worst = 0.0
     for objective, lam in (("reward", 0.05), ("position", 2.0)):
@@ -213,7 +137,7 @@ NORMAL_TOL = 4.0 * NORMAL_ERR_MEASURED
 
 
 def test_in_kernel_normals_against_float64(qa, torch):
-    env = _make(qa, "docking-v0", "frozen", False, provoke=None)
+    env = make_handle(qa, "docking-v0", "frozen", False, provoke=None)
     k = env.step_counter
     sigma, paths, horizon = 0.25, 1000, 20
     got = _plan(env, horizon, paths, 1, sigma=sigma)
@@ -254,7 +178,7 @@ _worst = {"reward": 0.0, "position": 0.0}
 
 @pytest.mark.parametrize("env_id,integ,params,paths,horizon", E2E_CASES)
 def test_end_to_end_against_float64_oracle(qa, torch, env_id, integ, params, paths, horizon):
-    env = _make(qa, env_id, integ, params, provoke="decisive")
+    env = make_handle(qa, env_id, integ, params, provoke="decisive")
     _, rec, par = _rec_par(env)
     gen = torch.Generator(device="cpu").manual_seed(13)
     noise = torch.randn((1, paths, horizon, 4), generator=gen).to(env.device)
@@ -281,20 +205,10 @@ def test_end_to_end_against_float64_oracle(qa, torch, env_id, integ, params, pat
 
 
 # ---------------------------------------------------------------- 6. read-only, reproducible
-def _snapshot(env):
-    st = env.get_state()
-    m, i = env.get_params()
-    return [st[k].copy() for k in sorted(st)] + [m, i, env.step_counter]
-
-
-def _same(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
 @pytest.mark.parametrize("env_id,params,auto_reset", [("docking-v0", False, True), ("docking-v2", True, False), ("docking-v1", False, True)])
 def test_read_only_and_reproducible(qa, torch, env_id, params, auto_reset):
-    env = _make(qa, env_id, "frozen", params, auto_reset=auto_reset)
-    twin = _make(qa, env_id, "frozen", params, auto_reset=auto_reset)
+    env = make_handle(qa, env_id, "frozen", params, auto_reset=auto_reset)
+    twin = make_handle(qa, env_id, "frozen", params, auto_reset=auto_reset)
     before = _snapshot(env)
     assert _same(before, _snapshot(twin))
     init_before = env.get_init_state() if env_id == "docking-v1" else None      # the only kind with stored initial states
@@ -367,13 +281,8 @@ def test_one_env_handle_plans_like_the_same_env_of_a_large_handle(qa, torch):
     state, parameters and step counter -- 1, 64, 200 and 1000 paths (blocks of 64, 64, 256 and 256 threads); and a nominal
     buffer that is both input and output"""
     g = 1234
-    big = _make(qa, "docking-v0", "frozen", True, n=4096)
-    one = qa.VecDockingEnv("docking-v0", num_envs=1, seed=SEED, env_id_offset=g)
-    st = big.get_state()
-    m, i = big.get_params()
-    one.set_params(mass=m[g:g + 1], inertia=i[g:g + 1])
-    one.set_state(**{k: v[g:g + 1] for k, v in st.items()})
-    one.step_counter = big.step_counter
+    big = make_handle(qa, "docking-v0", "frozen", True, n=4096)
+    one = slice_handle(qa, big, g, 1)
     gen = torch.Generator(device="cpu").manual_seed(17)
     for paths in PATHS:
         nominal = (torch.rand((4096, 20, 4), generator=gen) - 0.5).to(big.device)
@@ -393,20 +302,13 @@ def test_one_env_handle_plans_like_the_same_env_of_a_large_handle(qa, torch):
 def test_private_queue_handle_plans_like_hip_stream_twin(qa, torch):
     """a private-queue handle with steps still in flight: drained first, then the same plan as a HIP-stream twin, and both step
     on alike"""
-    a = _make(qa, "docking-v0", "frozen", False, n=4096)
-    b = _make(qa, "docking-v0", "frozen", False, n=4096)
-    b.set_queue_mode(True, 2, ordering="host")
-    acts = a.random_actions(6, step0=50)
-    torch.cuda.synchronize()
-    for t in range(5):
-        a.step(acts[t])
-        b.step_async(acts[t])                                 # not waited for
+    a, b, last = in_flight_pair(qa, torch)
     pa, pb = _plan(a, 20, 200, 3, return_candidates=False), _plan(b, 20, 200, 3, return_candidates=False)
     for key in pa:
         assert _same_bits(pa[key], pb[key]), key
     assert a.step_counter == b.step_counter == 7
-    oa, ra, _, _ = a.step(acts[5])
-    ob, rb, _, _ = b.step(acts[5])
+    oa, ra, _, _ = a.step(last)
+    ob, rb, _, _ = b.step(last)
     assert torch.equal(oa, ob) and torch.equal(ra, rb)
     a.close(); b.close()
 
@@ -414,7 +316,7 @@ def test_private_queue_handle_plans_like_hip_stream_twin(qa, torch):
 # ---------------------------------------------------------------- 8. closed loop
 def test_closed_loop_is_plan_step_and_masked_zeroing(qa, torch):
     def make():
-        env = _make(qa, "docking-v0", "frozen", False, provoke=None)
+        env = make_handle(qa, "docking-v0", "frozen", False, provoke=None)
         st = env.get_state()
         t0 = st["t"].copy()
         t0[5] = 595.0                                         # times out inside the 8 steps

@@ -12,17 +12,10 @@ import numpy as np
 import pytest
 
 import shooting_ref
+from plan_cases import DT, HANDLES, HORIZONS, N, PATHS, SEED, in_flight_pair, make_handle, make_twin, slice_handle, twin_scores
+from plan_cases import bits as _bits, rec_par as _rec_par, same as _same, snapshot as _snapshot
 
 pytestmark = pytest.mark.gpu
-
-N = 96                               # one full tile and a tail tile
-PATHS = (1, 64, 200, 1000)           # one lane, one wave, a ragged last wave, a lane loop (4 candidates per lane, ragged)
-HORIZONS = (1, 3, 20)
-KINDS = ("docking-v0", "docking-v1", "docking-v2")
-SEED = 23
-PAR_NOM = np.array([0.18, 0.00025, 0.000232, 0.0003738])
-DT = float(np.float32(0.02))
-HANDLES = [(k, g, p) for k in KINDS for g in ("frozen", "rk4") for p in (False, True)]
 
 
 @pytest.fixture(scope="module")
@@ -37,57 +30,7 @@ def torch():
     return torch
 
 
-# ---------------------------------------------------------------- handles and their states
-def _make(qa, torch, env_id, integ, params, n=N, provoke="all", offset=0, auto_reset=True):
-    """a handle with rocRAND initial states (docking-v1: its own stored jittered starts, the only reset it has) after a reset
-    and two random steps (stored controls and last_shaping are live, k = 2), then -- by env index modulo 6 --
-      0  t = 595: times out at horizon step 5;          1  t = 599: times out at the first step;
-      2  chaser at z = 0.13 m falling at 2 m/s: under the 0.1 m floor after the first step (0.09 m), whatever the action;
-      3  ("all" only) chaser 0.17 m up falling at 2 m/s: crosses the floor around the second step, action-dependent;
-      4  ("all" only) chaser's port 5 cm from the target's with zero relative velocity: inside the docked thresholds;
-      5  untouched.
-    provoke="decisive" leaves 3 and 4 out: there a threshold is crossed within float32 rounding of some candidate, where a
-    float32 and a float64 simulator may decide differently; the definition test takes them, the float64 comparison does not."""
-    kw = dict(num_envs=n, seed=SEED, integrator=integ, env_id_offset=offset, auto_reset=auto_reset)
-    if env_id != "docking-v1":
-        kw.update(randomise=1, init_range=qa.C3_INIT_RANGE)
-    env = qa.VecDockingEnv(env_id, **kw)
-    rng = np.random.default_rng(SEED)
-    if params:
-        env.set_params(mass=(0.18 * rng.uniform(0.85, 1.15, n)).astype(np.float32),
-                       inertia=(PAR_NOM[1:] * rng.uniform(0.85, 1.15, (n, 3))).astype(np.float32))
-    env.reset()
-    for a in env.random_actions(2, step0=0):
-        env.step(a)
-    if provoke:
-        st = env.get_state()
-        idx = np.arange(n)
-        t0, c = st["t"].copy(), st["chaser"].copy()
-        t0[idx % 6 == 0] = 595.0
-        t0[idx % 6 == 1] = 599.0
-        for m, z in ((2, 0.13), (3, 0.17)):
-            sel = idx % 6 == m
-            if m == 3 and provoke != "all":
-                continue
-            c[sel, 2] = z
-            c[sel, 3:6] = np.array([0.0, 0.0, -2.0], np.float32)
-        if provoke == "all":
-            sel = idx % 6 == 4
-            c[sel] = st["target"][sel]
-            c[sel, 0] -= 0.25                                # ports at +0.1 / -0.1: 5 cm apart
-        env.set_state(chaser=c, t=t0)
-    return env
-
-
-def _rec_par(env):
-    st = env.get_state()
-    rec = np.zeros((env.num_envs, 40), np.float64)
-    rec[:, 0:13], rec[:, 13:26], rec[:, 26:34], rec[:, 34:38] = st["chaser"], st["target"], st["u_prev"], st["qdes"]
-    rec[:, 38], rec[:, 39] = st["last_shaping"], st["t"]
-    m, i = env.get_params()
-    return st, rec, np.concatenate([m[:, None], i], axis=1).astype(np.float64)
-
-
+# ---------------------------------------------------------------- candidates and plans
 _ACTS = {}
 
 
@@ -105,36 +48,19 @@ def _plan(env, horizon, paths, objective="reward"):
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def _bits(x):
-    return np.ascontiguousarray(x).view(np.uint32 if x.dtype.itemsize == 4 else np.uint64)
-
-
 # ---------------------------------------------------------------- 1. the definition
 @pytest.mark.parametrize("env_id,integ,params", HANDLES)
 def test_definition_bit_for_bit(qa, torch, env_id, integ, params):
-    env = _make(qa, torch, env_id, integ, params)
+    env = make_handle(qa, env_id, integ, params)
     k = env.step_counter
     st, _, _ = _rec_par(env)
-    mass, inertia = env.get_params()
     stopped_inside = 0
     for paths in PATHS:
-        rep = lambda x: np.repeat(x, paths, axis=0)           # noqa: E731
-        twin = qa.VecDockingEnv(env_id, num_envs=N * paths, integrator=integ, auto_reset=False, seed=SEED + 1)
-        if params:
-            twin.set_params(mass=rep(mass), inertia=rep(inertia))
+        twin = make_twin(qa, env, env_id, integ, params, paths)
         for horizon in HORIZONS:
             acts = _actions(k, N, paths, horizon)
-            twin.set_state(chaser=rep(st["chaser"]), target=rep(st["target"]), u_prev=rep(st["u_prev"]), qdes=rep(st["qdes"]),
-                           last_shaping=rep(st["last_shaping"]), t=rep(st["t"]))
-            staged = torch.from_numpy(np.ascontiguousarray(acts.reshape(N * paths, horizon, 4).transpose(1, 0, 2))).to(env.device)
-            total = torch.zeros(N * paths, dtype=torch.float64, device=env.device)
-            alive = torch.ones(N * paths, dtype=torch.bool, device=env.device)
-            for h in range(horizon):
-                _, r, d, _ = twin.step(staged[h])
-                total += torch.where(alive, r.double(), torch.zeros_like(total))
-                alive &= ~d
-            want = total.cpu().numpy().reshape(N, paths)
-            stopped_inside += int((~alive).sum())
+            want, stopped = twin_scores(torch, twin, st, acts, paths)
+            stopped_inside += stopped
             got = _plan(env, horizon, paths)
             assert np.array_equal(_bits(got["scores"]), _bits(want)), (paths, horizon)
             win = shooting_ref.first_argmax(want)
@@ -164,8 +90,8 @@ _worst = {"reward": 0.0, "position": 0.0, "reward_pick": 0.0, "position_pick": 0
 def test_against_float64_reference(qa, torch, env_id, integ, params, paths, horizon):
     """the paths x horizon cross product on docking-v0 / frozen / nominal, every other (kind, integrator, params) handle at the
     reference's 200 x 20, and the other path counts and horizons spread over RK4 and per-env-parameter handles; every env
-    counts.  The states are _make's "decisive" ones (see there); the definition test takes the knife-edge ones."""
-    env = _make(qa, torch, env_id, integ, params, provoke="decisive")
+    counts.  The states are plan_cases.make_handle's "decisive" ones (see there); the definition test takes the knife-edge ones."""
+    env = make_handle(qa, env_id, integ, params, provoke="decisive")
     k = env.step_counter
     _, rec, par = _rec_par(env)
     acts = _actions(k, N, paths, horizon)
@@ -189,20 +115,10 @@ def test_against_float64_reference(qa, torch, env_id, integ, params, paths, hori
 
 
 # ---------------------------------------------------------------- 3. read-only, reproducible
-def _snapshot(env):
-    st = env.get_state()
-    m, i = env.get_params()
-    return [st[k].copy() for k in sorted(st)] + [m, i, env.step_counter]
-
-
-def _same(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
 @pytest.mark.parametrize("env_id,params,auto_reset", [("docking-v0", False, True), ("docking-v2", True, False), ("docking-v1", False, True)])
 def test_read_only_and_reproducible(qa, torch, env_id, params, auto_reset):
-    env = _make(qa, torch, env_id, "frozen", params, auto_reset=auto_reset)
-    twin = _make(qa, torch, env_id, "frozen", params, auto_reset=auto_reset)
+    env = make_handle(qa, env_id, "frozen", params, auto_reset=auto_reset)
+    twin = make_handle(qa, env_id, "frozen", params, auto_reset=auto_reset)
     before = _snapshot(env)
     assert _same(before, _snapshot(twin))
     p1 = _plan(env, 20, 200)
@@ -228,7 +144,7 @@ def test_read_only_and_reproducible(qa, torch, env_id, params, auto_reset):
 # ---------------------------------------------------------------- 4. prefix property
 @pytest.mark.parametrize("objective", ["reward", "position"])
 def test_prefix_property_on_the_device(qa, torch, objective):
-    env = _make(qa, torch, "docking-v0", "rk4", True)
+    env = make_handle(qa, "docking-v0", "rk4", True)
     p64, p200, p1000 = (_plan(env, 20, p, objective) for p in (64, 200, 1000))
     assert np.all(p1000["best_score"] >= p200["best_score"]) and np.all(p200["best_score"] >= p64["best_score"])
     assert np.array_equal(_bits(p1000["scores"][:, :200]), _bits(p200["scores"]))
@@ -242,23 +158,15 @@ def test_one_env_handle_plans_like_the_same_env_of_a_large_handle(qa, torch):
     """N = 1 against N = 4096: env 1234 of the large handle and the single env of a handle with env_id_offset = 1234, the same
     state, parameters and step counter -- 1, 64, 200 and 1000 paths (blocks of 64, 64, 256 and 256 threads)"""
     g = 1234
-    big = _make(qa, torch, "docking-v0", "frozen", True, n=4096)
-    one = qa.VecDockingEnv("docking-v0", num_envs=1, seed=SEED, env_id_offset=g)
-    st = big.get_state()
-    m, i = big.get_params()
-    one.set_params(mass=m[g:g + 1], inertia=i[g:g + 1])
-    one.set_state(**{k: v[g:g + 1] for k, v in st.items()})
-    one.step_counter = big.step_counter
+    big = make_handle(qa, "docking-v0", "frozen", True, n=4096)
+    one = slice_handle(qa, big, g, 1)
     for paths in PATHS:
         for objective in ("reward", "position"):
             a, b = _plan(big, 20, paths, objective), _plan(one, 20, paths, objective)
             for key in a:
                 assert np.array_equal(_bits(a[key][g:g + 1]), _bits(b[key])), (paths, objective, key)
     # and equal-gid envs of two handles of different size: envs 0..95 of both
-    small = qa.VecDockingEnv("docking-v0", num_envs=N, seed=SEED)
-    small.set_params(mass=m[:N], inertia=i[:N])
-    small.set_state(**{k: v[:N] for k, v in st.items()})
-    small.step_counter = big.step_counter
+    small = slice_handle(qa, big, 0, N)
     a, b = _plan(big, 3, 1000), _plan(small, 3, 1000)
     for key in a:
         assert np.array_equal(_bits(a[key][:N]), _bits(b[key])), key
@@ -268,28 +176,21 @@ def test_one_env_handle_plans_like_the_same_env_of_a_large_handle(qa, torch):
 def test_private_queue_handle_plans_like_hip_stream_twin(qa, torch):
     """a private-queue handle with steps still in flight: drained first, then the same plan as a HIP-stream twin, and both step
     on alike"""
-    a = _make(qa, torch, "docking-v0", "frozen", False, n=4096)
-    b = _make(qa, torch, "docking-v0", "frozen", False, n=4096)
-    b.set_queue_mode(True, 2, ordering="host")
-    acts = a.random_actions(6, step0=50)
-    torch.cuda.synchronize()
-    for t in range(5):
-        a.step(acts[t])
-        b.step_async(acts[t])                                 # not waited for
+    a, b, last = in_flight_pair(qa, torch)
     pa, pb = _plan(a, 20, 200), _plan(b, 20, 200)
     for key in pa:
         assert np.array_equal(_bits(pa[key]), _bits(pb[key])), key
     assert a.step_counter == b.step_counter == 7
-    oa, ra, _, _ = a.step(acts[5])
-    ob, rb, _, _ = b.step(acts[5])
+    oa, ra, _, _ = a.step(last)
+    ob, rb, _, _ = b.step(last)
     assert torch.equal(oa, ob) and torch.equal(ra, rb)
     a.close(); b.close()
 
 
 # ---------------------------------------------------------------- 6. closed loop
 def test_closed_loop_is_plan_then_step(qa, torch):
-    a = _make(qa, torch, "docking-v0", "frozen", False, provoke=None)
-    b = _make(qa, torch, "docking-v0", "frozen", False, provoke=None)
+    a = make_handle(qa, "docking-v0", "frozen", False, provoke=None)
+    b = make_handle(qa, "docking-v0", "frozen", False, provoke=None)
     mpc = qa.ShootingMPC(a, horizon=10, paths=64)
     rew, done = mpc.run(5)
     assert rew.shape == (5, N) and done.shape == (5, N) and done.dtype == torch.bool

@@ -14,41 +14,35 @@
 (a)/(b) and (c)/(a).  Timed with qs_timer_start / qs_timer_stop on the handles' stream (= torch's current stream).  The
 acceptance condition of the planner: (a) below (c) in every round.  One JSON line per (paths, iterations, round) on stdout,
 everything in --out, with the VGPRs, SGPRs, scratch and waves per SIMD of the four k_mppi instantiations read from the notes of
-the library's gfx950 code object (llvm-readelf; the tool fails if the ROCm LLVM tools are missing) and the dynamic LDS."""
+the library's gfx950 code object (through tests.kernel_notes, so pytest must be importable; llvm-readelf; the tool fails if the
+ROCm LLVM tools are missing, with kernel_notes' Skipped exception) and the dynamic LDS."""
 import argparse
 import json
 import os
 import re
-import subprocess
 import sys
 import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-
-LLVM = "/opt/rocm/llvm/bin"
+from tests.kernel_notes import code_object, kernel_notes  # noqa: E402
 
 
 def code_object_notes(so):
     """{instantiation: vgprs, sgprs, scratch bytes, spills, waves per SIMD} of the k_mppi kernels in the library's gfx950 code
     object (gfx950: 512 VGPRs per SIMD lane, allocated in blocks of 8, 8 waves at most)"""
     with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "dev.co")
-        subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, so, os.path.join(d, "so.copy")])
-        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
+        notes = kernel_notes(code_object(d, so), ("vgpr_count", "agpr_count", "sgpr_count", "private_segment_fixed_size",
+                                                  "vgpr_spill_count", "group_segment_fixed_size"))
     out = {}
-    for block in re.split(r"\n(?=\s+- \.agpr_count)", notes):
-        m = re.search(r"\.name:\s+\S*k_mppiILi(\d)ELb([01])EEEv", block)
+    for name, f in notes.items():
+        m = re.search(r"k_mppiILi(\d)ELb([01])EEEv", name)
         if m:
-            f = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", block).group(1))      # noqa: E731
-            v = f("vgpr_count") + f("agpr_count")
+            v = f["vgpr_count"] + f["agpr_count"]
             out["k_mppi<%s, %s params>" % ("RK4" if m.group(1) == "1" else "frozen", "per-env" if m.group(2) == "1" else "nominal")] = dict(
-                vgprs=v, sgprs=f("sgpr_count"), scratch_bytes=f("private_segment_fixed_size"), vgpr_spills=f("vgpr_spill_count"),
-                static_lds_bytes=f("group_segment_fixed_size"), waves_per_simd=min(8, 512 // ((v + 7) // 8 * 8)))
+                vgprs=v, sgprs=f["sgpr_count"], scratch_bytes=f["private_segment_fixed_size"], vgpr_spills=f["vgpr_spill_count"],
+                static_lds_bytes=f["group_segment_fixed_size"], waves_per_simd=min(8, 512 // ((v + 7) // 8 * 8)))
     assert len(out) == 4, sorted(out)
     return out
 
