@@ -512,6 +512,32 @@ int qs_shooting_plan(QsEnv *env, int32_t horizon, int32_t paths, int32_t objecti
                      float *sequence     /* nullable [N,horizon,4] the best candidate's actions */,
                      double *scores      /* nullable [N,paths] every candidate's score */);
 
+/* qs_shooting_plan with ONE ENV'S CANDIDATES SPREAD OVER `splits` WORKGROUPS: for handles of few envs (a real-time MPC on one
+ * drone), where qs_shooting_plan's one workgroup per env leaves most of the chip idle.
+ *   Contract.  Everything qs_shooting_plan documents holds: candidates, keys, scores, winner, outputs and their alignment,
+ *     read-only, the limits on horizon, paths and the step counter, kinds, integrators, per-env params, the drain in
+ *     private-queue mode and the read-back of the step counter.  For every legal `splits` the five outputs have the bits
+ *     qs_shooting_plan gives: the winner is defined by a total order (higher score, then lower index), so it does not depend
+ *     on how the candidates are partitioned.
+ *   splits = S >= 1.  Env i's candidates are divided into S contiguous ranges of ceil(paths / S) candidates; the last ranges
+ *     may be short or empty.  Each range is one workgroup of a first launch (grid N x S) that leaves its best (score, index)
+ *     in a workspace of the handle; a second launch (one wave per env) reduces the S partial winners and writes actions,
+ *     best_score, best_index and sequence.  The boundary between the two launches is the only ordering across workgroups.
+ *     1 <= S <= min(paths, 1024) and N x S < 2^31, else QS_ERR_INVALID.  With S = 1, passed or chosen, the call launches
+ *     qs_shooting_plan's own kernel exactly as qs_shooting_plan does.
+ *   splits = 0: the library chooses.  With CU the device's compute-unit count (multiProcessorCount): S = 1 if N >= 2 CU;
+ *     otherwise S = ceil(2 CU / N) -- the smallest S with N x S >= 2 CU -- but at most ceil(paths / 256), so that no part has
+ *     fewer candidates than a full 256-thread workgroup takes at once, and at most 1024.  qs_shooting_plan_splits returns
+ *     that choice for a handle and a path count without planning anything.
+ *   Workspace.  N x S x 12 bytes of device memory owned by the handle: allocated by the first call with S > 1, grown (after
+ *     one stream synchronisation) when a call needs more, never shrunk, freed by qs_destroy.
+ *   QS_IO_HOST handles are accepted, unlike qs_shooting_plan: the five outputs are host arrays then (any alignment the
+ *     element type allows) and the call returns after they have been written.  hovering handles give QS_ERR_INVALID.
+ * Added after QS_VERSION 131 without changing it: callers detect these entry points by symbol (dlsym). */
+int qs_shooting_plan_split(QsEnv *env, int32_t horizon, int32_t paths, int32_t objective, int32_t splits,
+                           float *actions, double *best_score, int32_t *best_index, float *sequence, double *scores);
+int qs_shooting_plan_splits(QsEnv *env, int32_t paths, int32_t *splits);   /* what splits == 0 would choose */
+
 /* MPPI (model-predictive path integral control), ONE launch: `iterations` rounds of sampling around a nominal action sequence
  * and softmax-weighted averaging, for all N docking envs on the exact simulator.  The nominal goes in and comes out, so a
  * closed loop warm-starts every plan from the previous one (shift = 1); the loop itself (plan, qs_step) is the caller's.

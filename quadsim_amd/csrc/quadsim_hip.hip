@@ -23,6 +23,7 @@
 //     runner_kernels.hpp   PPO2 data collection: the one-wave-per-tile and the role-split Runner kernel (qs_runner_rollout*)
 //     expert_rollout.hpp   the PID expert: one action, T steps, K complete episodes per env (qs_expert_*)
 //     shooting.hpp         random-shooting MPC (qs_shooting_plan)      mppi.hpp             the MPPI planner (qs_mppi_plan)
+//     shooting_split.hpp   random shooting with one env's candidates over several workgroups (qs_shooting_plan_split)
 //     env_groups.hpp       env groups (qs_set_groups)                  private_queue.hpp    private AQL queues (qs_set_queue_mode)
 //     host_util.hpp        host only: the last-error text (fail), HIP_TRY, roctx ranges, the device guard, and UserIO: how every
 //                          entry point hands the caller's buffers to its kernels (in place on a QS_IO_DEVICE handle, through the
@@ -78,6 +79,7 @@ using namespace qs;
 #include "expert_rollout.hpp"
 #include "shooting.hpp"
 #include "mppi.hpp"
+#include "shooting_split.hpp"
 
 #ifdef QS_STAMP
 static unsigned long long *g_host_stamps = nullptr;     // qs_debug_set_stamps: handed to every launch through StepArgs
@@ -106,6 +108,9 @@ struct QsEnv {
     bool groups_dirty = false;  // group streams hold work the main stream has not been ordered behind
     bool runner_env_major = false;   // qs_set_rollout_layout
     struct QsChain *chain = nullptr; // qs_set_queue_mode: private AQL queue for the step launches
+    char *wide_ws = nullptr;    // qs_shooting_plan_split: partial winners, double score[wide_slots] then int32 index[wide_slots]
+    size_t wide_slots = 0;
+    int cu_count = 0;           // multiProcessorCount of cfg.device, read at the first automatic choice of `splits`
 };
 
 namespace {
@@ -461,6 +466,7 @@ int qs_destroy(QsEnv *e)
     if (e->init) (void)hipFree(e->init);
     if (e->d_ctr) (void)hipFree(e->d_ctr);
     if (e->gae_ws) (void)hipFree(e->gae_ws);
+    if (e->wide_ws) (void)hipFree(e->wide_ws);
     if (e->stage.dev) (void)hipFree(e->stage.dev);
     if (e->stage.pin) (void)hipHostFree(e->stage.pin);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
@@ -1511,21 +1517,33 @@ int qs_expert_evaluate(QsEnv *e, int32_t episodes, int64_t max_steps, const floa
 // ---- the sampling planners: random-shooting MPC and MPPI --------------------------------------
 // What both entry points check alike, after their own arguments; then the step counter, read synchronously: the candidate
 // keys hold it in `key_bits` bits (shooting: (k << 26) | (c << 10) | h; MPPI: (1 << 63) | (k << 30) | (it << 26) | (c << 10) | h).
-static int plan_prepare(QsEnv *e, const char *name, int horizon, int max_horizon, int paths, int max_paths, int objective, int key_bits)
+static int plan_check(QsEnv *e, const char *name, int horizon, int max_horizon, int paths, int max_paths, int objective, bool host_ok)
 {
     if (e->cfg.kind == QS_KIND_HOVERING_V0) return fail(QS_ERR_INVALID, "%s: docking envs only", name);
-    if (e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "%s: device buffers only", name);
+    if (!host_ok && e->cfg.io_space != QS_IO_DEVICE) return fail(QS_ERR_INVALID, "%s: device buffers only", name);
     if (paths < 1 || paths > max_paths) return fail(QS_ERR_INVALID, "%s: paths must be in [1, %d], got %d", name, max_paths, paths);
     if (horizon < 1 || horizon > max_horizon)
         return fail(QS_ERR_INVALID, "%s: horizon must be in [1, %d], got %d", name, max_horizon, horizon);
     if (objective != QS_SHOOT_REWARD && objective != QS_SHOOT_POSITION) return fail(QS_ERR_INVALID, "%s: unknown objective %d", name, objective);
     if (e->n > 0x7fffffff) return fail(QS_ERR_INVALID, "%s: one workgroup per env: at most 2^31 - 1 envs", name);
+    return QS_OK;
+}
+
+static int plan_counter(QsEnv *e, const char *name, int key_bits)
+{
     unsigned long long k = 0;
     HIP_TRY(hipMemcpyAsync(&k, e->d_ctr, sizeof k, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (k >> key_bits)
         return fail(QS_ERR_INVALID, "%s: step counter %llu does not fit the %d bits of the candidate keys", name, k, key_bits);
     return QS_OK;
+}
+
+// the two one-workgroup-per-env planners: device handles only
+static int plan_prepare(QsEnv *e, const char *name, int horizon, int max_horizon, int paths, int max_paths, int objective, int key_bits)
+{
+    if (int rc = plan_check(e, name, horizon, max_horizon, paths, max_paths, objective, false)) return rc;
+    return plan_counter(e, name, key_bits);
 }
 
 // min(256, paths rounded up to a wave) threads
@@ -1549,6 +1567,84 @@ int qs_shooting_plan(QsEnv *e, int32_t horizon, int32_t paths, int32_t objective
     });
     HIP_TRY(hipGetLastError());
     return QS_OK;
+}
+
+// The automatic `splits` of qs_shooting_plan_split (the rule is stated in quadsim.h): 1 where the envs alone give every CU two
+// workgroups, else as many parts as reach that, but no part under kWideMinPart candidates and at most kWideMaxSplits parts.
+constexpr int kWideMinPart = 256;
+static int plan_auto_splits(QsEnv *e, int paths, int *splits)
+{
+    if (!e->cu_count) HIP_TRY(hipDeviceGetAttribute(&e->cu_count, hipDeviceAttributeMultiprocessorCount, e->cfg.device));
+    const int64_t want = 2 * (int64_t)std::max(e->cu_count, 1);
+    int64_t s = e->n >= want ? 1 : (want + e->n - 1) / e->n;
+    s = std::min<int64_t>(s, (paths + kWideMinPart - 1) / kWideMinPart);
+    *splits = (int)std::max<int64_t>(1, std::min<int64_t>(s, kWideMaxSplits));
+    return QS_OK;
+}
+
+int qs_shooting_plan_splits(QsEnv *e, int32_t paths, int32_t *splits)
+{
+    CHECK_ENV_RAW(e);
+    if (!splits) return fail(QS_ERR_INVALID, "qs_shooting_plan_splits: splits is required");
+    if (paths < 1 || paths > 65536) return fail(QS_ERR_INVALID, "qs_shooting_plan_splits: paths must be in [1, 65536], got %d", paths);
+    int s = 1;
+    if (int rc = plan_auto_splits(e, paths, &s)) return rc;
+    *splits = s;
+    return QS_OK;
+}
+
+int qs_shooting_plan_split(QsEnv *e, int32_t horizon, int32_t paths, int32_t objective, int32_t splits, float *actions,
+                           double *best_score, int32_t *best_index, float *sequence, double *scores)
+{
+    CHECK_ENV(e);
+    Range rg_("qs_shooting_plan_split");
+    const char *const name = "qs_shooting_plan_split";
+    if (!actions) return fail(QS_ERR_INVALID, "%s: actions is required", name);
+    // a host handle's buffers are copied through the staging slices, which are aligned whatever the caller's are
+    if (e->cfg.io_space == QS_IO_DEVICE
+        && (((((uintptr_t)actions) | ((uintptr_t)sequence)) & 15u) || ((((uintptr_t)best_score) | ((uintptr_t)scores)) & 7u)
+            || (((uintptr_t)best_index) & 3u)))
+        return fail(QS_ERR_INVALID, "%s: actions and sequence must be 16-byte aligned, best_score and scores 8-byte, best_index 4-byte", name);
+    if (int rc = plan_check(e, name, horizon, 256, paths, 65536, objective, true)) return rc;
+    const int max_splits = std::min<int>(paths, kWideMaxSplits);
+    if (splits < 0 || splits > max_splits)
+        return fail(QS_ERR_INVALID, "%s: splits must be 0 (automatic) or in [1, min(paths, %d)] = [1, %d], got %d", name,
+                    kWideMaxSplits, max_splits, splits);
+    int S = splits;
+    if (S == 0) { if (int rc = plan_auto_splits(e, paths, &S)) return rc; }
+    if (e->n * (int64_t)S > 0x7fffffff)
+        return fail(QS_ERR_INVALID, "%s: one workgroup per part: envs x splits must be below 2^31, got %lld x %d", name, (long long)e->n, S);
+    if (int rc = plan_counter(e, name, 36)) return rc;
+    const size_t slots = (size_t)e->n * (size_t)S;
+    if (S > 1 && e->wide_slots < slots) {                   // grown, never shrunk: a later call with fewer parts reuses it
+        HIP_TRY(hipStreamSynchronize(e->stream));           // an earlier call's kernels may still read the old one
+        if (e->wide_ws) HIP_TRY(hipFree(e->wide_ws));
+        e->wide_ws = nullptr; e->wide_slots = 0;
+        HIP_TRY(hipMalloc((void **)&e->wide_ws, slots * (sizeof(double) + sizeof(int32_t))));
+        e->wide_slots = slots;
+    }
+    UserIO io = user_io(e);
+    io.out(actions, (size_t)e->n * 4); io.out(best_score, (size_t)e->n); io.out(best_index, (size_t)e->n);
+    io.out(sequence, (size_t)e->n * horizon * 4); io.out(scores, (size_t)e->n * paths);
+    if (int r = io.push()) return r;
+    const StepArgs A = make_args(e);
+    const PlanArgs X{horizon, paths, objective, actions, best_score, best_index, sequence, scores};
+    const size_t lds = plan_lds_bytes(horizon);
+    if (S == 1) {
+        with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
+            hipLaunchKernelGGL((k_shooting_plan<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(plan_block(paths)), lds, e->stream, A, X);
+        });
+    } else {
+        const WideArgs W{S, reinterpret_cast<double *>(e->wide_ws), reinterpret_cast<int32_t *>(e->wide_ws + e->wide_slots * sizeof(double))};
+        const unsigned block = plan_block((paths + S - 1) / S);
+        with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
+            hipLaunchKernelGGL((k_wide_candidates<INTEG, PARAMS>), dim3((unsigned)slots), dim3(block), lds, e->stream, A, X, W);
+        });
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_wide_finish, dim3((unsigned)e->n), dim3(kTile), 0, e->stream, A, X, W);
+    }
+    HIP_TRY(hipGetLastError());
+    return io.pull();
 }
 
 int qs_mppi_plan(QsEnv *e, int32_t horizon, int32_t paths, int32_t iterations, int32_t objective, float lambda, float sigma,

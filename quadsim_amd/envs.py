@@ -107,6 +107,14 @@ class _SingleDockingEnv:
                 "done_overlimit": bool(flags[0] & _lib.FLAG_OVERLIMIT)}
         return self.rel_state, self.reward, self.done, info
 
+    def shooting_plan(self, horizon=20, paths=200, objective="reward", splits="auto", return_scores=False, return_sequence=False):
+        """Mpc_Controller.choose_action (MPC-based_RL.py:170-210) on the env itself: the best of `paths` random action
+        sequences of `horizon` steps from the current state, which is not modified.  -> dict of numpy results: actions [4]
+        (pass it to step()), best_score, best_index, plus sequence [horizon,4] and scores [paths] on request; `splits` as in
+        quadsim_amd.mpc.shooting_plan"""
+        from .mpc import shooting_plan_host
+        return shooting_plan_host(self, horizon, paths, objective, splits, return_scores, return_sequence)
+
     def render(self, mode="human"):
         return None
 

@@ -4,17 +4,20 @@
 dynamics net, scores each by ``-sum |rel_pos|^2`` and applies the first action of the best one.  Here the model is the env
 itself: ``shooting_plan`` rolls ``paths`` candidates per env through ``horizon`` env steps in ONE launch, read-only on the
 env, and ``ShootingMPC`` is the closed loop of ``model_train`` (:213-241) without the dynamics net and its training.
+With ``splits`` one env's candidates are spread over that many workgroups (qs_shooting_plan_split: two launches, the same
+bits), which is what a handle of one or a few envs needs to use more than one compute unit.
 
 ``mppi_plan`` / ``MPPI`` are the iterated, warm-started member of the same family (model-predictive path integral control):
 Gaussian candidates around a nominal action sequence, scored the same way, and the nominal replaced by their softmax-weighted
 mean, ``iterations`` times in one launch; the nominal is carried from plan to plan.
 """
 import ctypes as C
+import operator
 
 from . import _lib
 
 OBJECTIVES = {"reward": _lib.SHOOT_REWARD, "position": _lib.SHOOT_POSITION}
-MAX_PATHS, MAX_HORIZON = 65536, 256
+MAX_PATHS, MAX_HORIZON, MAX_SPLITS = 65536, 256, 1024
 MPPI_MAX_PATHS, MPPI_MAX_HORIZON, MPPI_MAX_ITERATIONS = 4096, 128, 16
 # Tuned on ONE setting only (4096 docking-v0 envs, horizon 20, 200 paths, 2 iterations, objective "reward", 600 steps):
 # the sweep is in profiles/mppi/README.md.
@@ -58,18 +61,51 @@ def _closed_loop(env, act, steps, after_step=None):
     return torch.stack(R), torch.stack(D)
 
 
-def check_plan_args(horizon, paths, objective):
-    """-> (horizon, paths, objective id); ValueError for what qs_shooting_plan would refuse, before anything touches the GPU"""
-    return _check_common(horizon, paths, objective, MAX_HORIZON, MAX_PATHS)
+def check_splits(splits, paths):
+    """-> None (qs_shooting_plan), 0 ("auto": the library chooses) or the int S in [1, min(paths, 1024)]; ValueError otherwise"""
+    if splits is None:
+        return None
+    if isinstance(splits, str):
+        if splits != "auto":
+            raise ValueError("splits must be None, \"auto\" or an int, got %r" % (splits,))
+        return 0
+    if isinstance(splits, (bool, float)):
+        raise ValueError("splits must be None, \"auto\" or an int, got %r" % (splits,))
+    try:
+        s = operator.index(splits)
+    except TypeError:
+        raise ValueError("splits must be None, \"auto\" or an int, got %r" % (splits,)) from None
+    if not 1 <= s <= min(paths, MAX_SPLITS):
+        raise ValueError("splits must be in [1, min(paths, %d)] = [1, %d], got %d" % (MAX_SPLITS, min(paths, MAX_SPLITS), s))
+    return s
 
 
-def shooting_plan(env, horizon=20, paths=200, objective="reward", return_scores=False, return_sequence=False):
+def check_plan_args(horizon, paths, objective, splits=None):
+    """-> (horizon, paths, objective id, splits as check_splits returns it); ValueError for what qs_shooting_plan /
+    qs_shooting_plan_split would refuse, before anything touches the GPU"""
+    horizon, paths, obj = _check_common(horizon, paths, objective, MAX_HORIZON, MAX_PATHS)
+    return horizon, paths, obj, check_splits(splits, paths)
+
+
+def plan_splits(env, paths):
+    """the number of parts per env that ``splits="auto"`` gives a plan of `paths` candidates on the handle of `env`
+    (qs_shooting_plan_splits; `env` a VecDockingEnv or a single-env shim)"""
+    _, paths, _, _ = check_plan_args(1, paths, "reward")
+    s = C.c_int32(0)
+    _lib.check(env._lib.qs_shooting_plan_splits(env._h, paths, C.byref(s)), "qs_shooting_plan_splits")
+    return int(s.value)
+
+
+def shooting_plan(env, horizon=20, paths=200, objective="reward", return_scores=False, return_sequence=False, splits=None):
     """One plan for every env of `env` from its current state (the env is not modified).  objective "reward": the sum of the
     step rewards; "position": the reference's ``-sum |rel_pos|^2`` over the observations before each step.  Returns a dict of
     device tensors: actions [N,4] (the best candidate's first action), best_score [N] float64, best_index [N] int32, plus
     sequence [N,horizon,4] and scores [N,paths] float64 on request.  Candidates are keyed by (seed, env id, step counter,
-    candidate, horizon step): a plan repeated before the same step is identical, and fewer paths are a prefix of more."""
-    horizon, paths, obj = check_plan_args(horizon, paths, objective)
+    candidate, horizon step): a plan repeated before the same step is identical, and fewer paths are a prefix of more.
+    `splits`: None plans with one workgroup per env (qs_shooting_plan); an int S in [1, min(paths, 1024)] spreads every env's
+    candidates over S workgroups and "auto" lets the library choose S (qs_shooting_plan_split).  The results have the same
+    bits either way."""
+    horizon, paths, obj, splits = check_plan_args(horizon, paths, objective, splits)
     import torch
     n, dev = env.num_envs, env.device
     out = {"actions": torch.empty((n, 4), dtype=torch.float32, device=dev),
@@ -79,22 +115,48 @@ def shooting_plan(env, horizon=20, paths=200, objective="reward", return_scores=
         out["sequence"] = torch.empty((n, horizon, 4), dtype=torch.float32, device=dev)
     if return_scores:
         out["scores"] = torch.empty((n, paths), dtype=torch.float64, device=dev)
-    _call(env, "qs_shooting_plan", horizon, paths, obj, out["actions"], out["best_score"], out["best_index"], out.get("sequence"),
-          out.get("scores"))
+    bufs = (out["actions"], out["best_score"], out["best_index"], out.get("sequence"), out.get("scores"))
+    if splits is None:
+        _call(env, "qs_shooting_plan", horizon, paths, obj, *bufs)
+    else:
+        _call(env, "qs_shooting_plan_split", horizon, paths, obj, splits, *bufs)
+    return out
+
+
+def shooting_plan_host(env, horizon=20, paths=200, objective="reward", splits="auto", return_scores=False,
+                       return_sequence=False):
+    """``shooting_plan`` for the ONE env of a QS_IO_HOST handle (`env` a single-env gym shim): numpy results through the host
+    path of qs_shooting_plan_split -- actions [4] float32, best_score (numpy float64), best_index (int), plus sequence
+    [horizon,4] and scores [paths] float64 on request.  `splits` None counts as 1: the split entry point is the only one that
+    takes host handles, and with one part it launches the kernel of qs_shooting_plan."""
+    import numpy as np
+    horizon, paths, obj, splits = check_plan_args(horizon, paths, objective, splits)
+    act, score, index = np.zeros((1, 4), np.float32), np.zeros(1, np.float64), np.zeros(1, np.int32)
+    seq = np.zeros((1, horizon, 4), np.float32) if return_sequence else None
+    sc = np.zeros((1, paths), np.float64) if return_scores else None
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)    # noqa: E731
+    _lib.check(env._lib.qs_shooting_plan_split(env._h, horizon, paths, obj, 1 if splits is None else splits, p(act), p(score),
+                                          p(index), p(seq), p(sc)), "qs_shooting_plan_split")
+    out = {"actions": act[0], "best_score": score[0], "best_index": int(index[0])}
+    if return_sequence:
+        out["sequence"] = seq[0]
+    if return_scores:
+        out["scores"] = sc[0]
     return out
 
 
 class ShootingMPC:
     """The sampling-based controller as a policy object beside PIDExpert: ``act()`` plans and returns the actions [N,4],
-    ``run(steps)`` is the closed loop ``a = act(); env.step(a)``.  Defaults as Mpc_Controller.__init__ (:171)."""
+    ``run(steps)`` is the closed loop ``a = act(); env.step(a)``.  Defaults as Mpc_Controller.__init__ (:171); `splits` as in
+    ``shooting_plan``."""
 
-    def __init__(self, env, horizon=20, paths=200, objective="reward"):
-        self.horizon, self.paths, _ = check_plan_args(horizon, paths, objective)
-        self.env, self.objective = env, objective
+    def __init__(self, env, horizon=20, paths=200, objective="reward", splits=None):
+        self.horizon, self.paths, _, _ = check_plan_args(horizon, paths, objective, splits)
+        self.env, self.objective, self.splits = env, objective, splits
         self.last_plan = None
 
     def act(self):
-        self.last_plan = shooting_plan(self.env, self.horizon, self.paths, self.objective)
+        self.last_plan = shooting_plan(self.env, self.horizon, self.paths, self.objective, splits=self.splits)
         return self.last_plan["actions"]
 
     def run(self, steps):

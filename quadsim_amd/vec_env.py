@@ -473,10 +473,11 @@ class VecDockingEnv:
         self._outputs_ready()
         return a
 
-    def shooting_plan(self, horizon=20, paths=200, objective="reward", return_scores=False, return_sequence=False):
-        """random-shooting MPC from the envs' current states, read-only, one launch (qs_shooting_plan): see quadsim_amd.mpc"""
+    def shooting_plan(self, horizon=20, paths=200, objective="reward", return_scores=False, return_sequence=False, splits=None):
+        """random-shooting MPC from the envs' current states, read-only, one launch (qs_shooting_plan) or, with `splits`, every
+        env's candidates over several workgroups (qs_shooting_plan_split): see quadsim_amd.mpc"""
         from .mpc import shooting_plan
-        return shooting_plan(self, horizon, paths, objective, return_scores, return_sequence)
+        return shooting_plan(self, horizon, paths, objective, return_scores, return_sequence, splits)
 
     def mppi_plan(self, *args, **kwargs):
         """MPPI from the envs' current states, read-only, one launch for all refinement iterations (qs_mppi_plan): the
