@@ -583,6 +583,40 @@ int qs_mppi_plan(QsEnv *env, int32_t horizon, int32_t paths, int32_t iterations,
                  float *trace            /* nullable [N,iterations+1,horizon,4]: nominal before iteration 0 (after the shift), then after each */,
                  float *candidates       /* nullable [N,paths,horizon,4]: the actions of the LAST iteration's candidates */);
 
+/* qs_mppi_plan with ONE ENV'S CANDIDATES SPREAD OVER `splits` WORKGROUPS: for handles of few envs (a real-time controller on one
+ * drone), where qs_mppi_plan's one workgroup per env leaves most of the chip idle, and for more than 4096 paths.
+ *   Contract.  Everything qs_mppi_plan documents holds -- nominal, candidates, random keys, score, weights, update, outputs,
+ *     read-only, kinds, integrators, per-env params, the drain in private-queue mode, the read-back of the step counter -- with
+ *     1 <= paths <= 65536 and one difference: the ORDER of the two float64 sums of the update is a function of (paths, S)
+ *     alone instead of `paths` alone.  So trace[:,0], the scores of iteration 0 and, with iterations = 1, the candidates have
+ *     qs_mppi_plan's bits for every S; the nominal after an update is within one float32 rounding (2^-24) of qs_mppi_plan's,
+ *     and later iterations start from that nominal.  For a fixed S the result does not depend on N, on the env's index in the
+ *     handle, on env_id_offset or on the queue mode; the first j iterations of a call with more are the call with j.
+ *   splits = S >= 2.  Env i's candidates are divided into S contiguous ranges of ceil(paths / S) candidates, as
+ *     qs_shooting_plan_split divides them; the last ranges may be short or empty.  Three launches per iteration: the roll-out
+ *     (grid N x S) leaves every score and each part's largest score in a workspace of the handle; the second (grid N x S)
+ *     takes Smax over the env's parts, forms the weights and leaves each part's weighted sums, added within a part in
+ *     ascending candidate order per wave and then in wave order; the third (one wave per env) adds the S partial sums in part
+ *     order, divides and writes the nominal.  The boundary between two launches is the only ordering across workgroups.
+ *     1 <= S <= min(paths, 1024) and N x S < 2^31, else QS_ERR_INVALID.
+ *   splits = 1 launches qs_mppi_plan's own kernel exactly as qs_mppi_plan does: every output has its bits.  That kernel keeps
+ *     all scores of an env in one workgroup's LDS, so S = 1 needs paths <= 4096: an explicit splits = 1 with paths > 4096 is
+ *     QS_ERR_INVALID.
+ *   splits = 0: the library chooses.  S is the automatic choice of qs_shooting_plan_split for this handle and `paths` (what
+ *     qs_shooting_plan_splits reports), raised to 2 when paths > 4096.
+ *   Workspace.  N x (16 horizon + 8 paths + S x (32 horizon + 16)) bytes of device memory owned by the handle, separate from
+ *     qs_shooting_plan_split's: allocated by the first call with S > 1, grown (after one stream synchronisation) when a call
+ *     needs more, never shrunk, freed by qs_destroy.  If it cannot be allocated the call fails with QS_ERR_HIP and the handle
+ *     stays usable.
+ *   QS_IO_HOST handles are accepted, unlike qs_mppi_plan: nominal_in, noise and the six outputs are host arrays then (any
+ *     alignment the element type allows) and the call returns after the outputs have been written.  hovering handles give
+ *     QS_ERR_INVALID.
+ * Added after QS_VERSION 131 without changing it: callers detect this entry point by symbol (dlsym). */
+int qs_mppi_plan_split(QsEnv *env, int32_t horizon, int32_t paths, int32_t iterations, int32_t objective,
+                       float lambda, float sigma, int32_t shift, int32_t splits,
+                       const float *nominal_in, const float *noise, float *actions, float *nominal_out,
+                       double *best_score, double *scores, float *trace, float *candidates);
+
 /* ---- layer-1 entry points: n independent drones / controllers (n need not equal N) ----------- */
 
 /* Drone.step (dynamics/quadrotor.py:126-144): state [n,13] in/out, u_prev [n,4] in/out (Drone.u),

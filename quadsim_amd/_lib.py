@@ -37,7 +37,7 @@ EXPORTS = [
     "qs_swap_and_flatten_u8", "qs_gae_flatten", "qs_episode_stats", "qs_set_rollout_layout",
     "qs_set_queue_mode", "qs_get_queue_mode", "qs_set_queue_ordering", "qs_get_queue_ordering",
     "qs_expert_rollout", "qs_expert_evaluate", "qs_shooting_plan", "qs_mppi_plan",
-    "qs_shooting_plan_split", "qs_shooting_plan_splits",
+    "qs_shooting_plan_split", "qs_shooting_plan_splits", "qs_mppi_plan_split",
 ]
 
 
@@ -158,6 +158,7 @@ def load():
         "qs_mppi_plan": [vp, i32, i32, i32, i32, f32, f32, i32] + [vp] * 8,
         "qs_shooting_plan_split": [vp, i32, i32, i32, i32] + [vp] * 5,
         "qs_shooting_plan_splits": [vp, i32, C.POINTER(i32)],
+        "qs_mppi_plan_split": [vp, i32, i32, i32, i32, f32, f32, i32, i32] + [vp] * 8,
         "qs_policy_rollout": [vp, i64] + [vp] * 11,
         "qs_policy_rollout_fast": [vp, i64] + [vp] * 6,
         "qs_policy_rollout_fast_blob_bytes": [],

@@ -24,6 +24,7 @@
 //     expert_rollout.hpp   the PID expert: one action, T steps, K complete episodes per env (qs_expert_*)
 //     shooting.hpp         random-shooting MPC (qs_shooting_plan)      mppi.hpp             the MPPI planner (qs_mppi_plan)
 //     shooting_split.hpp   random shooting with one env's candidates over several workgroups (qs_shooting_plan_split)
+//     mppi_split.hpp       MPPI with one env's candidates over several workgroups (qs_mppi_plan_split)
 //     env_groups.hpp       env groups (qs_set_groups)                  private_queue.hpp    private AQL queues (qs_set_queue_mode)
 //     host_util.hpp        host only: the last-error text (fail), HIP_TRY, roctx ranges, the device guard, and UserIO: how every
 //                          entry point hands the caller's buffers to its kernels (in place on a QS_IO_DEVICE handle, through the
@@ -80,6 +81,7 @@ using namespace qs;
 #include "shooting.hpp"
 #include "mppi.hpp"
 #include "shooting_split.hpp"
+#include "mppi_split.hpp"
 
 #ifdef QS_STAMP
 static unsigned long long *g_host_stamps = nullptr;     // qs_debug_set_stamps: handed to every launch through StepArgs
@@ -110,6 +112,8 @@ struct QsEnv {
     struct QsChain *chain = nullptr; // qs_set_queue_mode: private AQL queue for the step launches
     char *wide_ws = nullptr;    // qs_shooting_plan_split: partial winners, double score[wide_slots] then int32 index[wide_slots]
     size_t wide_slots = 0;
+    char *mppi_ws = nullptr;    // qs_mppi_plan_split: nominal, scores, per-part maxima and partial sums (laid out per call)
+    size_t mppi_ws_bytes = 0;
     int cu_count = 0;           // multiProcessorCount of cfg.device, read at the first automatic choice of `splits`
 };
 
@@ -467,6 +471,7 @@ int qs_destroy(QsEnv *e)
     if (e->d_ctr) (void)hipFree(e->d_ctr);
     if (e->gae_ws) (void)hipFree(e->gae_ws);
     if (e->wide_ws) (void)hipFree(e->wide_ws);
+    if (e->mppi_ws) (void)hipFree(e->mppi_ws);
     if (e->stage.dev) (void)hipFree(e->stage.dev);
     if (e->stage.pin) (void)hipHostFree(e->stage.pin);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
@@ -1674,6 +1679,88 @@ int qs_mppi_plan(QsEnv *e, int32_t horizon, int32_t paths, int32_t iterations, i
     });
     HIP_TRY(hipGetLastError());
     return QS_OK;
+}
+
+int qs_mppi_plan_split(QsEnv *e, int32_t horizon, int32_t paths, int32_t iterations, int32_t objective, float lambda, float sigma,
+                       int32_t shift, int32_t splits, const float *nominal_in, const float *noise, float *actions,
+                       float *nominal_out, double *best_score, double *scores, float *trace, float *candidates)
+{
+    CHECK_ENV(e);
+    Range rg_("qs_mppi_plan_split");
+    const char *const name = "qs_mppi_plan_split";
+    if (iterations < 1 || iterations > 16) return fail(QS_ERR_INVALID, "%s: iterations must be in [1, 16], got %d", name, iterations);
+    if (!(lambda > 0.0f) || !std::isfinite(lambda))
+        return fail(QS_ERR_INVALID, "%s: lambda must be positive and finite, got %g", name, (double)lambda);
+    if (!(sigma >= 0.0f) || !std::isfinite(sigma))
+        return fail(QS_ERR_INVALID, "%s: sigma must be non-negative and finite, got %g", name, (double)sigma);
+    if (shift != 0 && shift != 1) return fail(QS_ERR_INVALID, "%s: shift must be 0 or 1, got %d", name, shift);
+    if (!actions || !nominal_out) return fail(QS_ERR_INVALID, "%s: actions and nominal_out are required", name);
+    // a host handle's buffers are copied through the staging slices, which are aligned whatever the caller's are
+    if (e->cfg.io_space == QS_IO_DEVICE
+        && (((((uintptr_t)actions) | ((uintptr_t)nominal_out) | ((uintptr_t)nominal_in) | ((uintptr_t)noise) | ((uintptr_t)trace)
+              | ((uintptr_t)candidates)) & 15u) || ((((uintptr_t)best_score) | ((uintptr_t)scores)) & 7u)))
+        return fail(QS_ERR_INVALID, "%s: actions, nominal_in, nominal_out, noise, trace and candidates must be 16-byte aligned, best_score and scores 8-byte", name);
+    if (int rc = plan_check(e, name, horizon, 128, paths, 65536, objective, true)) return rc;
+    const int max_splits = std::min<int>(paths, kWideMaxSplits);
+    if (splits < 0 || splits > max_splits)
+        return fail(QS_ERR_INVALID, "%s: splits must be 0 (automatic) or in [1, min(paths, %d)] = [1, %d], got %d", name,
+                    kWideMaxSplits, max_splits, splits);
+    if (splits == 1 && paths > 4096)
+        return fail(QS_ERR_INVALID, "%s: splits = 1 launches qs_mppi_plan's kernel, which holds at most 4096 paths, got %d", name, paths);
+    int S = splits;
+    if (S == 0) {
+        if (int rc = plan_auto_splits(e, paths, &S)) return rc;
+        if (paths > 4096) S = std::max(S, 2);
+    }
+    if (e->n * (int64_t)S > 0x7fffffff)
+        return fail(QS_ERR_INVALID, "%s: one workgroup per part: envs x splits must be below 2^31, got %lld x %d", name, (long long)e->n, S);
+    if (int rc = plan_counter(e, name, 33)) return rc;
+    // workspace: U [n][horizon] float4 | scores [n][paths] f64 | maxima [n S] f64 | partial sums [n S][horizon 4 + 1] f64
+    const uint64_t n = (uint64_t)e->n, slots = n * (uint64_t)S, words = (uint64_t)horizon * 4 + 1;
+    const uint64_t off_score = n * (uint64_t)horizon * sizeof(float4), off_max = off_score + n * (uint64_t)paths * sizeof(double),
+                   off_sum = off_max + slots * sizeof(double), need = off_sum + slots * words * sizeof(double);
+    if (S > 1 && e->mppi_ws_bytes < need) {                 // grown, never shrunk
+        HIP_TRY(hipStreamSynchronize(e->stream));           // an earlier call's kernels may still use the old one
+        if (e->mppi_ws) HIP_TRY(hipFree(e->mppi_ws));
+        e->mppi_ws = nullptr; e->mppi_ws_bytes = 0;
+        if (hipMalloc((void **)&e->mppi_ws, need) != hipSuccess) {
+            (void)hipGetLastError();                        // reported here; the handle stays usable
+            e->mppi_ws = nullptr;
+            return fail(QS_ERR_HIP, "%s: cannot allocate the workspace of %llu bytes", name, (unsigned long long)need);
+        }
+        e->mppi_ws_bytes = need;
+    }
+    UserIO io = user_io(e);
+    io.in(nominal_in, (size_t)e->n * horizon * 4); io.in(noise, (size_t)iterations * paths * horizon * 4);
+    io.out(actions, (size_t)e->n * 4); io.out(nominal_out, (size_t)e->n * horizon * 4); io.out(best_score, (size_t)e->n);
+    io.out(scores, (size_t)e->n * iterations * paths); io.out(trace, (size_t)e->n * (iterations + 1) * horizon * 4);
+    io.out(candidates, (size_t)e->n * paths * horizon * 4);
+    if (int r = io.push()) return r;
+    const StepArgs A = make_args(e);
+    const MppiArgs X{horizon, paths, iterations, objective, shift, lambda, sigma, nominal_in, noise, actions, nominal_out,
+                     best_score, scores, trace, candidates};
+    if (S == 1) {
+        const size_t lds = mppi_lds_bytes(horizon, paths);
+        with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
+            hipLaunchKernelGGL((k_mppi<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(plan_block(paths)), lds, e->stream, A, X);
+        });
+    } else {
+        MppiPartArgs W{S, 0, reinterpret_cast<float4 *>(e->mppi_ws), reinterpret_cast<double *>(e->mppi_ws + off_score),
+                       reinterpret_cast<double *>(e->mppi_ws + off_max), reinterpret_cast<double *>(e->mppi_ws + off_sum)};
+        const unsigned block = plan_block((paths + S - 1) / S);
+        const size_t lds_roll = mppi_roll_lds_bytes(horizon), lds_sums = mppi_sums_lds_bytes(horizon);
+        for (int it = 0; it < iterations; ++it) {
+            W.it = it;
+            with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
+                hipLaunchKernelGGL((k_pathint_part_roll<INTEG, PARAMS>), dim3((unsigned)slots), dim3(block), lds_roll, e->stream, A, X, W);
+            });
+            hipLaunchKernelGGL(k_pathint_part_sums, dim3((unsigned)slots), dim3(block), lds_sums, e->stream, A, X, W);
+            hipLaunchKernelGGL(k_pathint_part_finish, dim3((unsigned)e->n), dim3(kTile), 0, e->stream, A, X, W);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return io.pull();
 }
 
 // ---- layer 1 ---------------------------------------------------------------------------------

@@ -115,6 +115,18 @@ class _SingleDockingEnv:
         from .mpc import shooting_plan_host
         return shooting_plan_host(self, horizon, paths, objective, splits, return_scores, return_sequence)
 
+    def mppi_plan(self, horizon=20, paths=200, iterations=2, objective="reward", lam=None, sigma=None, nominal=None, shift=False,
+                  noise=None, splits="auto", return_scores=False, return_trace=False, return_candidates=False):
+        """MPPI on the env itself from the current state, which is not modified: `iterations` rounds of `paths` Gaussian
+        candidates around `nominal` [horizon,4] (None: zeros; shifted by one step first if `shift`).  -> dict of numpy results:
+        actions [4] (pass it to step()), nominal [horizon,4] (carry it to the next plan with shift=True), best_score, plus
+        scores, trace and candidates on request; `lam` and `sigma` default to, and every argument is as in,
+        quadsim_amd.mpc.mppi_plan"""
+        from . import mpc
+        return mpc.mppi_plan_host(self, horizon, paths, iterations, objective, mpc.MPPI_DEFAULT_LAMBDA if lam is None else lam,
+                                  mpc.MPPI_DEFAULT_SIGMA if sigma is None else sigma, nominal, shift, noise, splits, return_scores,
+                                  return_trace, return_candidates)
+
     def render(self, mode="human"):
         return None
 

@@ -9,7 +9,9 @@ bits), which is what a handle of one or a few envs needs to use more than one co
 
 ``mppi_plan`` / ``MPPI`` are the iterated, warm-started member of the same family (model-predictive path integral control):
 Gaussian candidates around a nominal action sequence, scored the same way, and the nominal replaced by their softmax-weighted
-mean, ``iterations`` times in one launch; the nominal is carried from plan to plan.
+mean, ``iterations`` times in one launch; the nominal is carried from plan to plan.  With ``splits`` the candidates of one env
+are spread over that many workgroups here too (qs_mppi_plan_split: three launches per iteration, up to 65536 paths; the order
+of the update's sums depends on the number of parts, so the nominal agrees with the unsplit one to one float32 rounding).
 """
 import ctypes as C
 import operator
@@ -19,6 +21,7 @@ from . import _lib
 OBJECTIVES = {"reward": _lib.SHOOT_REWARD, "position": _lib.SHOOT_POSITION}
 MAX_PATHS, MAX_HORIZON, MAX_SPLITS = 65536, 256, 1024
 MPPI_MAX_PATHS, MPPI_MAX_HORIZON, MPPI_MAX_ITERATIONS = 4096, 128, 16
+MPPI_SPLIT_MAX_PATHS = 65536          # qs_mppi_plan_split; one part (splits = 1) is qs_mppi_plan's kernel and keeps its 4096
 # Tuned on ONE setting only (4096 docking-v0 envs, horizon 20, 200 paths, 2 iterations, objective "reward", 600 steps):
 # the sweep is in profiles/mppi/README.md.
 MPPI_DEFAULT_LAMBDA, MPPI_DEFAULT_SIGMA = 0.05, 0.25
@@ -164,11 +167,9 @@ class ShootingMPC:
         return _closed_loop(self.env, self.act, steps)
 
 
-def check_mppi_args(horizon, paths, iterations, objective, lam, sigma, shift):
-    """-> (horizon, paths, iterations, objective id, lam, sigma, shift as 0 / 1); ValueError for what qs_mppi_plan would
-    refuse, before anything touches the GPU"""
+def _check_mppi(horizon, paths, iterations, objective, lam, sigma, shift, max_paths):
     import math
-    horizon, paths, obj = _check_common(horizon, paths, objective, MPPI_MAX_HORIZON, MPPI_MAX_PATHS)
+    horizon, paths, obj = _check_common(horizon, paths, objective, MPPI_MAX_HORIZON, max_paths)
     iterations = int(iterations)
     if not 1 <= iterations <= MPPI_MAX_ITERATIONS:
         raise ValueError("iterations must be in [1, %d], got %d" % (MPPI_MAX_ITERATIONS, iterations))
@@ -182,8 +183,27 @@ def check_mppi_args(horizon, paths, iterations, objective, lam, sigma, shift):
     return horizon, paths, iterations, obj, lam, sigma, int(shift)
 
 
+def check_mppi_args(horizon, paths, iterations, objective, lam, sigma, shift):
+    """-> (horizon, paths, iterations, objective id, lam, sigma, shift as 0 / 1); ValueError for what qs_mppi_plan would
+    refuse, before anything touches the GPU"""
+    return _check_mppi(horizon, paths, iterations, objective, lam, sigma, shift, MPPI_MAX_PATHS)
+
+
+def check_mppi_split_args(horizon, paths, iterations, objective, lam, sigma, shift, splits):
+    """-> check_mppi_args' tuple plus `splits` as check_splits returns it.  None is qs_mppi_plan and its 4096 paths; with
+    `splits` (qs_mppi_plan_split) up to 65536 paths, except that one part is qs_mppi_plan's kernel and keeps its limit"""
+    if splits is None:
+        return check_mppi_args(horizon, paths, iterations, objective, lam, sigma, shift) + (None,)
+    out = _check_mppi(horizon, paths, iterations, objective, lam, sigma, shift, MPPI_SPLIT_MAX_PATHS)
+    splits = check_splits(splits, out[1])
+    if splits == 1 and out[1] > MPPI_MAX_PATHS:
+        raise ValueError("splits=1 plans with qs_mppi_plan's kernel, which takes at most %d paths, got %d" % (MPPI_MAX_PATHS, out[1]))
+    return out + (splits,)
+
+
 def mppi_plan(env, horizon=20, paths=200, iterations=2, objective="reward", lam=MPPI_DEFAULT_LAMBDA, sigma=MPPI_DEFAULT_SIGMA,
-              nominal=None, shift=False, noise=None, return_scores=False, return_trace=False, return_candidates=False):
+              nominal=None, shift=False, noise=None, return_scores=False, return_trace=False, return_candidates=False,
+              splits=None):
     """One MPPI plan for every env of `env` from its current state (the env is not modified), `iterations` refinement rounds in
     one launch.  Candidate c >= 1 of a round is clamp(nominal + sigma z, -1, 1), candidate 0 the nominal itself; the new
     nominal is the mean of the candidates weighted by exp((score - best score) / lam).  `nominal` [N,horizon,4] (float32,
@@ -192,8 +212,14 @@ def mppi_plan(env, horizon=20, paths=200, iterations=2, objective="reward", lam=
     Returns a dict of device tensors: actions [N,4] (= nominal[:,0]), nominal [N,horizon,4], best_score [N] float64, plus
     scores [N,iterations,paths] float64, trace [N,iterations+1,horizon,4] (the nominal before the first round and after each)
     and candidates [N,paths,horizon,4] (the last round's) on request.  The defaults of `lam` and `sigma` are tuned on one
-    setting only (4096 docking-v0 envs, horizon 20, 200 paths x 2 iterations, "reward"; profiles/mppi/README.md)."""
-    horizon, paths, iterations, obj, lam, sigma, shift = check_mppi_args(horizon, paths, iterations, objective, lam, sigma, shift)
+    setting only (4096 docking-v0 envs, horizon 20, 200 paths x 2 iterations, "reward"; profiles/mppi/README.md).
+    `splits`: None plans with one workgroup per env (qs_mppi_plan, at most 4096 paths); an int S in [1, min(paths, 1024)]
+    spreads every env's candidates over S workgroups and "auto" lets the library choose S (qs_mppi_plan_split, at most 65536
+    paths, three launches per iteration).  S = 1 gives qs_mppi_plan's bits; for S > 1 the scores of the first iteration are
+    the same bits and the nominal after an update is within one float32 rounding of the unsplit one, because the order of the
+    update's float64 sums depends on S; for a fixed S the plan is reproducible."""
+    horizon, paths, iterations, obj, lam, sigma, shift, splits = check_mppi_split_args(horizon, paths, iterations, objective, lam,
+                                                                                       sigma, shift, splits)
     import torch
     n, dev = env.num_envs, env.device
 
@@ -215,8 +241,49 @@ def mppi_plan(env, horizon=20, paths=200, iterations=2, objective="reward", lam=
         out["trace"] = torch.empty((n, iterations + 1, horizon, 4), dtype=torch.float32, device=dev)
     if return_candidates:
         out["candidates"] = torch.empty((n, paths, horizon, 4), dtype=torch.float32, device=dev)
-    _call(env, "qs_mppi_plan", horizon, paths, iterations, obj, lam, sigma, shift, nominal, noise, out["actions"], out["nominal"],
-          out["best_score"], out.get("scores"), out.get("trace"), out.get("candidates"))
+    bufs = (nominal, noise, out["actions"], out["nominal"], out["best_score"], out.get("scores"), out.get("trace"), out.get("candidates"))
+    if splits is None:
+        _call(env, "qs_mppi_plan", horizon, paths, iterations, obj, lam, sigma, shift, *bufs)
+    else:
+        _call(env, "qs_mppi_plan_split", horizon, paths, iterations, obj, lam, sigma, shift, splits, *bufs)
+    return out
+
+
+def mppi_plan_host(env, horizon=20, paths=200, iterations=2, objective="reward", lam=MPPI_DEFAULT_LAMBDA, sigma=MPPI_DEFAULT_SIGMA,
+                   nominal=None, shift=False, noise=None, splits="auto", return_scores=False, return_trace=False,
+                   return_candidates=False):
+    """``mppi_plan`` for the ONE env of a QS_IO_HOST handle (`env` a single-env gym shim): numpy in and out through the host
+    path of qs_mppi_plan_split -- `nominal` [horizon,4] and `noise` [iterations,paths,horizon,4] float32 arrays or None;
+    actions [4] float32, nominal [horizon,4], best_score (numpy float64), plus scores [iterations,paths] float64, trace
+    [iterations+1,horizon,4] and candidates [paths,horizon,4] on request.  `splits` None counts as 1: the split entry point is
+    the only one that takes host handles, and with one part it launches the kernel of qs_mppi_plan."""
+    import numpy as np
+    horizon, paths, iterations, obj, lam, sigma, shift, splits = check_mppi_split_args(
+        horizon, paths, iterations, objective, lam, sigma, shift, 1 if splits is None else splits)
+
+    def given(a, shape, name):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != shape:
+            raise ValueError("%s must have shape %s, got %s" % (name, shape, a.shape))
+        return a
+    nominal = given(nominal, (horizon, 4), "nominal")
+    noise = given(noise, (iterations, paths, horizon, 4), "noise")
+    act, nom, score = np.zeros((1, 4), np.float32), np.zeros((1, horizon, 4), np.float32), np.zeros(1, np.float64)
+    sc = np.zeros((1, iterations, paths), np.float64) if return_scores else None
+    tr = np.zeros((1, iterations + 1, horizon, 4), np.float32) if return_trace else None
+    cand = np.zeros((1, paths, horizon, 4), np.float32) if return_candidates else None
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)    # noqa: E731
+    _lib.check(env._lib.qs_mppi_plan_split(env._h, horizon, paths, iterations, obj, lam, sigma, shift, splits, p(nominal), p(noise),
+                                           p(act), p(nom), p(score), p(sc), p(tr), p(cand)), "qs_mppi_plan_split")
+    out = {"actions": act[0], "nominal": nom[0], "best_score": score[0]}
+    if return_scores:
+        out["scores"] = sc[0]
+    if return_trace:
+        out["trace"] = tr[0]
+    if return_candidates:
+        out["candidates"] = cand[0]
     return out
 
 
@@ -225,13 +292,13 @@ class MPPI:
     ``act()`` plans (shifting the previous nominal by one step after the first call) and returns the actions [N,4];
     ``run(steps)`` is the closed loop ``a = act(); env.step(a)`` and, after each step, zeroes the nominal of the envs whose
     episode ended (one masked op, no host synchronisation); ``reset()`` forgets the nominal.  `lam` and `sigma` default to
-    values tuned on one setting only (see ``mppi_plan``)."""
+    values tuned on one setting only (see ``mppi_plan``); `splits` as in ``mppi_plan``."""
 
     def __init__(self, env, horizon=20, paths=200, iterations=2, objective="reward", lam=MPPI_DEFAULT_LAMBDA,
-                 sigma=MPPI_DEFAULT_SIGMA):
-        self.horizon, self.paths, self.iterations, _, self.lam, self.sigma, _ = check_mppi_args(
-            horizon, paths, iterations, objective, lam, sigma, False)
-        self.env, self.objective = env, objective
+                 sigma=MPPI_DEFAULT_SIGMA, splits=None):
+        self.horizon, self.paths, self.iterations, _, self.lam, self.sigma, _, _ = check_mppi_split_args(
+            horizon, paths, iterations, objective, lam, sigma, False, splits)
+        self.env, self.objective, self.splits = env, objective, splits
         self.nominal = None
         self.last_plan = None
 
@@ -240,7 +307,7 @@ class MPPI:
 
     def act(self):
         self.last_plan = mppi_plan(self.env, self.horizon, self.paths, self.iterations, self.objective, self.lam, self.sigma,
-                                   nominal=self.nominal, shift=self.nominal is not None)
+                                   nominal=self.nominal, shift=self.nominal is not None, splits=self.splits)
         self.nominal = self.last_plan["nominal"]
         return self.last_plan["actions"]
 

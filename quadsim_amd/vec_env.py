@@ -480,8 +480,9 @@ class VecDockingEnv:
         return shooting_plan(self, horizon, paths, objective, return_scores, return_sequence, splits)
 
     def mppi_plan(self, *args, **kwargs):
-        """MPPI from the envs' current states, read-only, one launch for all refinement iterations (qs_mppi_plan): the
-        arguments of quadsim_amd.mpc.mppi_plan after `env`"""
+        """MPPI from the envs' current states, read-only, one launch for all refinement iterations (qs_mppi_plan) or, with
+        `splits`, every env's candidates over several workgroups (qs_mppi_plan_split): the arguments of
+        quadsim_amd.mpc.mppi_plan after `env`, `splits=None` last"""
         from .mpc import mppi_plan
         return mppi_plan(self, *args, **kwargs)
 

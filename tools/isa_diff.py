@@ -26,7 +26,7 @@ def disassembly(co):
         m = re.match(r"^[0-9a-f]* ?<(\S+)>:$", line)
         if m:
             cur = out.setdefault(m.group(1), [])
-        elif cur is not None and line.strip():
+        elif cur is not None and line.strip() and line.strip() != "...":      # "...": zero padding behind a kernel, no instruction
             cur.append(re.sub(r"\s*(//|<).*$", "", line).strip())
     return out
 
