@@ -149,7 +149,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_mppi(StepArgs A, MppiArgs X)
         // the observation before step 0 is the current one, common to all candidates
         float obs0[12];
         rel_obs(e.sc, e.st, obs0);
-        const float pos0 = -(obs0[0] * obs0[0] + obs0[1] * obs0[1] + obs0[2] * obs0[2]);
+        const float pos0 = plan_pos(obs0);
         int tid0 = threadIdx.x;                             // opaque as `tid` below, for the same reason
         asm volatile("" : "+v"(tid0));
 #pragma clang loop unroll(disable)
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_mppi(StepArgs A, MppiArgs X)
                 for (int i = 0; i < 13; ++i) ec.st[i] = r[i];
                 env_step_chaser<INTEG>(ec, a, P, A.C, r[13] != 0.0f, obs, reward, flags);
                 if (!by_position) score += (double)reward;
-                pos = -(obs[0] * obs[0] + obs[1] * obs[1] + obs[2] * obs[2]);
+                pos = plan_pos(obs);
                 alive = (flags & (FLAG_OVERLIMIT | FLAG_OVERTIME)) == 0;      // `done` of the step kernels (maybe_reset)
             }
             S[c] = score;

@@ -6,7 +6,8 @@
 // The update is a softmax over ALL of an env's candidates, so a partition needs two reductions across workgroups per iteration:
 // Smax first, then the weighted sums.  Three launches per iteration on the handle's stream; the kernel boundary between two
 // launches is the only ordering across workgroups.  No workgroup waits for, polls, counts or signals another one, so there is
-// nothing that could hang; what crosses from one kernel to the next does so through the handle's workspace, which the earlier
+// nothing that could hang; what crosses from one kernel to the next does so through the handle's workspace (the one workspace
+// of both split planners: plan_workspace in quadsim_hip.hip, which lays it out for this call), which the earlier
 // kernel has finished writing before the later one starts.  Part p of env i owns the candidates
 // [p * ceil(paths / S), (p + 1) * ceil(paths / S)) cut at `paths`, as k_wide_candidates cuts them; trailing parts may be
 // short or empty.  The two N x S grids are flat: env = blockIdx.x / S, part = blockIdx.x % S, slot = blockIdx.x.
@@ -64,8 +65,8 @@ __global__ __launch_bounds__(kBlock, 4) void k_pathint_part_roll(StepArgs A, Mpp
 
     const int64_t env = blockIdx.x / (unsigned)W.splits;    // < A.n: the grid is n x S workgroups
     const int part = (int)(blockIdx.x % (unsigned)W.splits);
-    const int chunk = (X.paths + W.splits - 1) / W.splits;  // S <= 1024, chunk <= 65536: part * chunk fits an int
-    const int lo = min(part * chunk, X.paths), hi = min(lo + chunk, X.paths);
+    const PlanPart own = plan_part(part, W.splits, X.paths);
+    const int lo = own.lo, hi = own.hi;
     const int64_t tile = env / kTile;
     const int slot = (int)(env % kTile);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_pathint_part_roll(StepArgs A, Mpp
     // the observation before step 0 is the current one, common to all candidates
     float obs0[12];
     rel_obs(e.sc, e.st, obs0);
-    const float pos0 = -(obs0[0] * obs0[0] + obs0[1] * obs0[1] + obs0[2] * obs0[2]);
+    const float pos0 = plan_pos(obs0);
     int tid0 = threadIdx.x;                               // opaque as `tid` below, for k_mppi's reason
     asm volatile("" : "+v"(tid0));
 #pragma clang loop unroll(disable)
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_pathint_part_roll(StepArgs A, Mpp
             for (int i = 0; i < 13; ++i) ec.st[i] = r[i];
             env_step_chaser<INTEG>(ec, a, P, A.C, r[13] != 0.0f, obs, reward, flags);
             if (!by_position) score += (double)reward;
-            pos = -(obs[0] * obs[0] + obs[1] * obs[1] + obs[2] * obs[2]);
+            pos = plan_pos(obs);
             alive = (flags & (FLAG_OVERLIMIT | FLAG_OVERTIME)) == 0;      // `done` of the step kernels (maybe_reset)
         }
         S[c] = score;
@@ -178,8 +179,8 @@ __global__ __launch_bounds__(kBlock) void k_pathint_part_sums(StepArgs A, MppiAr
 
     const int64_t env = blockIdx.x / (unsigned)W.splits;    // < A.n: the grid is n x S workgroups
     const int part = (int)(blockIdx.x % (unsigned)W.splits);
-    const int chunk = (X.paths + W.splits - 1) / W.splits;
-    const int lo = min(part * chunk, X.paths), hi = min(lo + chunk, X.paths);
+    const PlanPart own = plan_part(part, W.splits, X.paths);
+    const int lo = own.lo, hi = own.hi;
     const int tid = threadIdx.x, wv = tid >> 6, ln = tid & 63;
     const int waves = (int)(blockDim.x >> 6);
     const int it = W.it;

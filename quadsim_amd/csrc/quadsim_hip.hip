@@ -78,6 +78,7 @@ using namespace qs;
 #include "policy_kernels.hpp"
 #include "runner_kernels.hpp"
 #include "expert_rollout.hpp"
+#include "plan_common.hpp"
 #include "shooting.hpp"
 #include "mppi.hpp"
 #include "shooting_split.hpp"
@@ -110,10 +111,8 @@ struct QsEnv {
     bool groups_dirty = false;  // group streams hold work the main stream has not been ordered behind
     bool runner_env_major = false;   // qs_set_rollout_layout
     struct QsChain *chain = nullptr; // qs_set_queue_mode: private AQL queue for the step launches
-    char *wide_ws = nullptr;    // qs_shooting_plan_split: partial winners, double score[wide_slots] then int32 index[wide_slots]
-    size_t wide_slots = 0;
-    char *mppi_ws = nullptr;    // qs_mppi_plan_split: nominal, scores, per-part maxima and partial sums (laid out per call)
-    size_t mppi_ws_bytes = 0;
+    char *plan_ws = nullptr;    // qs_shooting_plan_split, qs_mppi_plan_split: what crosses between a plan's kernels (plan_workspace)
+    size_t plan_ws_bytes = 0;
     int cu_count = 0;           // multiProcessorCount of cfg.device, read at the first automatic choice of `splits`
 };
 
@@ -470,8 +469,7 @@ int qs_destroy(QsEnv *e)
     if (e->init) (void)hipFree(e->init);
     if (e->d_ctr) (void)hipFree(e->d_ctr);
     if (e->gae_ws) (void)hipFree(e->gae_ws);
-    if (e->wide_ws) (void)hipFree(e->wide_ws);
-    if (e->mppi_ws) (void)hipFree(e->mppi_ws);
+    if (e->plan_ws) (void)hipFree(e->plan_ws);
     if (e->stage.dev) (void)hipFree(e->stage.dev);
     if (e->stage.pin) (void)hipHostFree(e->stage.pin);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
@@ -1520,7 +1518,7 @@ int qs_expert_evaluate(QsEnv *e, int32_t episodes, int64_t max_steps, const floa
 }
 
 // ---- the sampling planners: random-shooting MPC and MPPI --------------------------------------
-// What both entry points check alike, after their own arguments; then the step counter, read synchronously: the candidate
+// What every entry point checks alike, after its own arguments; then the step counter, read synchronously: the candidate
 // keys hold it in `key_bits` bits (shooting: (k << 26) | (c << 10) | h; MPPI: (1 << 63) | (k << 30) | (it << 26) | (c << 10) | h).
 static int plan_check(QsEnv *e, const char *name, int horizon, int max_horizon, int paths, int max_paths, int objective, bool host_ok)
 {
@@ -1544,37 +1542,10 @@ static int plan_counter(QsEnv *e, const char *name, int key_bits)
     return QS_OK;
 }
 
-// the two one-workgroup-per-env planners: device handles only
-static int plan_prepare(QsEnv *e, const char *name, int horizon, int max_horizon, int paths, int max_paths, int objective, int key_bits)
-{
-    if (int rc = plan_check(e, name, horizon, max_horizon, paths, max_paths, objective, false)) return rc;
-    return plan_counter(e, name, key_bits);
-}
-
 // min(256, paths rounded up to a wave) threads
 static unsigned plan_block(int paths) { return (unsigned)std::min<int64_t>(kBlock, ((int64_t)paths + kTile - 1) / kTile * kTile); }
 
-int qs_shooting_plan(QsEnv *e, int32_t horizon, int32_t paths, int32_t objective, float *actions, double *best_score,
-                     int32_t *best_index, float *sequence, double *scores)
-{
-    CHECK_ENV(e);
-    Range rg_("qs_shooting_plan");
-    if (!actions) return fail(QS_ERR_INVALID, "qs_shooting_plan: actions is required");
-    if (((((uintptr_t)actions) | ((uintptr_t)sequence)) & 15u) || ((((uintptr_t)best_score) | ((uintptr_t)scores)) & 7u)
-        || (((uintptr_t)best_index) & 3u))
-        return fail(QS_ERR_INVALID, "qs_shooting_plan: actions and sequence must be 16-byte aligned, best_score and scores 8-byte, best_index 4-byte");
-    if (int rc = plan_prepare(e, "qs_shooting_plan", horizon, 256, paths, 65536, objective, 36)) return rc;
-    const StepArgs A = make_args(e);
-    const PlanArgs X{horizon, paths, objective, actions, best_score, best_index, sequence, scores};
-    const size_t lds = plan_lds_bytes(horizon);
-    with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
-        hipLaunchKernelGGL((k_shooting_plan<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(plan_block(paths)), lds, e->stream, A, X);
-    });
-    HIP_TRY(hipGetLastError());
-    return QS_OK;
-}
-
-// The automatic `splits` of qs_shooting_plan_split (the rule is stated in quadsim.h): 1 where the envs alone give every CU two
+// The automatic `splits` of the split entry points (the rule is stated in quadsim.h): 1 where the envs alone give every CU two
 // workgroups, else as many parts as reach that, but no part under kWideMinPart candidates and at most kWideMaxSplits parts.
 constexpr int kWideMinPart = 256;
 static int plan_auto_splits(QsEnv *e, int paths, int *splits)
@@ -1598,50 +1569,63 @@ int qs_shooting_plan_splits(QsEnv *e, int32_t paths, int32_t *splits)
     return QS_OK;
 }
 
-int qs_shooting_plan_split(QsEnv *e, int32_t horizon, int32_t paths, int32_t objective, int32_t splits, float *actions,
-                           double *best_score, int32_t *best_index, float *sequence, double *scores)
+// What all four entry points check after their own arguments, in this order: plan_check, the range of `splits` (0: automatic),
+// the one-part rule (S = 1 holds at most one_part_max_paths candidates; only MPPI's kernel has such a limit), the automatic
+// choice, the grid limit, and last the step counter -> the number of parts S >= 1, or a negative QS_ERR_*.
+static int plan_admit(QsEnv *e, const char *name, bool host_ok, int horizon, int max_horizon, int paths, int max_paths,
+                      int one_part_max_paths, int objective, int splits, int key_bits)
 {
-    CHECK_ENV(e);
-    Range rg_("qs_shooting_plan_split");
-    const char *const name = "qs_shooting_plan_split";
-    if (!actions) return fail(QS_ERR_INVALID, "%s: actions is required", name);
-    // a host handle's buffers are copied through the staging slices, which are aligned whatever the caller's are
-    if (e->cfg.io_space == QS_IO_DEVICE
-        && (((((uintptr_t)actions) | ((uintptr_t)sequence)) & 15u) || ((((uintptr_t)best_score) | ((uintptr_t)scores)) & 7u)
-            || (((uintptr_t)best_index) & 3u)))
-        return fail(QS_ERR_INVALID, "%s: actions and sequence must be 16-byte aligned, best_score and scores 8-byte, best_index 4-byte", name);
-    if (int rc = plan_check(e, name, horizon, 256, paths, 65536, objective, true)) return rc;
+    if (int rc = plan_check(e, name, horizon, max_horizon, paths, max_paths, objective, host_ok)) return rc;
     const int max_splits = std::min<int>(paths, kWideMaxSplits);
     if (splits < 0 || splits > max_splits)
         return fail(QS_ERR_INVALID, "%s: splits must be 0 (automatic) or in [1, min(paths, %d)] = [1, %d], got %d", name,
                     kWideMaxSplits, max_splits, splits);
+    if (splits == 1 && paths > one_part_max_paths)
+        return fail(QS_ERR_INVALID, "%s: splits = 1 launches qs_mppi_plan's kernel, which holds at most %d paths, got %d", name,
+                    one_part_max_paths, paths);
     int S = splits;
-    if (S == 0) { if (int rc = plan_auto_splits(e, paths, &S)) return rc; }
+    if (S == 0) {
+        if (int rc = plan_auto_splits(e, paths, &S)) return rc;
+        if (paths > one_part_max_paths) S = std::max(S, 2);
+    }
     if (e->n * (int64_t)S > 0x7fffffff)
         return fail(QS_ERR_INVALID, "%s: one workgroup per part: envs x splits must be below 2^31, got %lld x %d", name, (long long)e->n, S);
-    if (int rc = plan_counter(e, name, 36)) return rc;
-    const size_t slots = (size_t)e->n * (size_t)S;
-    if (S > 1 && e->wide_slots < slots) {                   // grown, never shrunk: a later call with fewer parts reuses it
-        HIP_TRY(hipStreamSynchronize(e->stream));           // an earlier call's kernels may still read the old one
-        if (e->wide_ws) HIP_TRY(hipFree(e->wide_ws));
-        e->wide_ws = nullptr; e->wide_slots = 0;
-        HIP_TRY(hipMalloc((void **)&e->wide_ws, slots * (sizeof(double) + sizeof(int32_t))));
-        e->wide_slots = slots;
+    if (int rc = plan_counter(e, name, key_bits)) return rc;
+    return S;
+}
+
+// The one workspace of both planner families, for what crosses from one kernel of a split plan to the next: at least `bytes`,
+// grown and never shrunk; each call lays its arrays out from its own sizes.  Sharing it is safe: every planner kernel of a
+// handle runs on the handle's one stream, so a plan's kernels have finished with it before the next plan's start, and a
+// growth waits for the stream before it frees.  A failed allocation leaves the handle usable, without a workspace.
+static int plan_workspace(QsEnv *e, const char *name, uint64_t bytes)
+{
+    if (e->plan_ws_bytes >= bytes) return QS_OK;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->plan_ws) HIP_TRY(hipFree(e->plan_ws));
+    e->plan_ws = nullptr; e->plan_ws_bytes = 0;
+    if (hipMalloc((void **)&e->plan_ws, bytes) != hipSuccess) {
+        (void)hipGetLastError();                            // reported here
+        e->plan_ws = nullptr;
+        return fail(QS_ERR_HIP, "%s: cannot allocate the workspace of %llu bytes", name, (unsigned long long)bytes);
     }
-    UserIO io = user_io(e);
-    io.out(actions, (size_t)e->n * 4); io.out(best_score, (size_t)e->n); io.out(best_index, (size_t)e->n);
-    io.out(sequence, (size_t)e->n * horizon * 4); io.out(scores, (size_t)e->n * paths);
-    if (int r = io.push()) return r;
-    const StepArgs A = make_args(e);
-    const PlanArgs X{horizon, paths, objective, actions, best_score, best_index, sequence, scores};
-    const size_t lds = plan_lds_bytes(horizon);
+    e->plan_ws_bytes = bytes;
+    return QS_OK;
+}
+
+// ---- random shooting: S = 1 is k_shooting_plan, S > 1 the two kernels of shooting_split.hpp
+static int launch_shooting(QsEnv *e, const StepArgs &A, const PlanArgs &X, int S)
+{
+    const size_t lds = plan_lds_bytes(X.horizon);
     if (S == 1) {
         with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
-            hipLaunchKernelGGL((k_shooting_plan<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(plan_block(paths)), lds, e->stream, A, X);
+            hipLaunchKernelGGL((k_shooting_plan<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(plan_block(X.paths)), lds, e->stream, A, X);
         });
     } else {
-        const WideArgs W{S, reinterpret_cast<double *>(e->wide_ws), reinterpret_cast<int32_t *>(e->wide_ws + e->wide_slots * sizeof(double))};
-        const unsigned block = plan_block((paths + S - 1) / S);
+        // workspace: partial winners, score [n S] f64 | index [n S] int32
+        const size_t slots = (size_t)e->n * (size_t)S;
+        const WideArgs W{S, reinterpret_cast<double *>(e->plan_ws), reinterpret_cast<int32_t *>(e->plan_ws + slots * sizeof(double))};
+        const unsigned block = plan_block((X.paths + S - 1) / S);
         with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
             hipLaunchKernelGGL((k_wide_candidates<INTEG, PARAMS>), dim3((unsigned)slots), dim3(block), lds, e->stream, A, X, W);
         });
@@ -1649,6 +1633,135 @@ int qs_shooting_plan_split(QsEnv *e, int32_t horizon, int32_t paths, int32_t obj
         hipLaunchKernelGGL(k_wide_finish, dim3((unsigned)e->n), dim3(kTile), 0, e->stream, A, X, W);
     }
     HIP_TRY(hipGetLastError());
+    return QS_OK;
+}
+
+// A device handle's kernels work on the caller's memory, so its alignment matters; a host handle's buffers are copied through
+// the staging slices, which are aligned whatever the caller's are.
+static int shooting_check_aligned(const char *name, bool device, const PlanArgs &X)
+{
+    if (device && (((((uintptr_t)X.actions) | ((uintptr_t)X.sequence)) & 15u) || ((((uintptr_t)X.best_score) | ((uintptr_t)X.scores)) & 7u)
+                   || (((uintptr_t)X.best_index) & 3u)))
+        return fail(QS_ERR_INVALID, "%s: actions and sequence must be 16-byte aligned, best_score and scores 8-byte, best_index 4-byte", name);
+    return QS_OK;
+}
+
+// both entry points: the unsplit one is S = 1 on a device handle (host_ok = false), which never takes a workspace
+static int shooting_plan(QsEnv *e, const char *name, bool host_ok, int splits, PlanArgs X)
+{
+    if (!X.actions) return fail(QS_ERR_INVALID, "%s: actions is required", name);
+    if (int rc = shooting_check_aligned(name, !host_ok || e->cfg.io_space == QS_IO_DEVICE, X)) return rc;
+    const int S = plan_admit(e, name, host_ok, X.horizon, 256, X.paths, 65536, 65536, X.objective, splits, 36);
+    if (S < 0) return S;
+    if (S > 1)
+        if (int rc = plan_workspace(e, name, (uint64_t)e->n * (uint64_t)S * (sizeof(double) + sizeof(int32_t)))) return rc;
+    const size_t n = (size_t)e->n;
+    UserIO io = user_io(e);
+    io.out(X.actions, n * 4); io.out(X.best_score, n); io.out(X.best_index, n);
+    io.out(X.sequence, n * X.horizon * 4); io.out(X.scores, n * X.paths);
+    if (int r = io.push()) return r;
+    if (int r = launch_shooting(e, make_args(e), X, S)) return r;
+    return io.pull();
+}
+
+int qs_shooting_plan(QsEnv *e, int32_t horizon, int32_t paths, int32_t objective, float *actions, double *best_score,
+                     int32_t *best_index, float *sequence, double *scores)
+{
+    CHECK_ENV(e);
+    Range rg_("qs_shooting_plan");
+    return shooting_plan(e, "qs_shooting_plan", false, 1, PlanArgs{horizon, paths, objective, actions, best_score, best_index, sequence, scores});
+}
+
+int qs_shooting_plan_split(QsEnv *e, int32_t horizon, int32_t paths, int32_t objective, int32_t splits, float *actions,
+                           double *best_score, int32_t *best_index, float *sequence, double *scores)
+{
+    CHECK_ENV(e);
+    Range rg_("qs_shooting_plan_split");
+    return shooting_plan(e, "qs_shooting_plan_split", true, splits,
+                         PlanArgs{horizon, paths, objective, actions, best_score, best_index, sequence, scores});
+}
+
+// ---- MPPI: S = 1 is k_mppi (at most kMppiOnePartPaths candidates: their scores live in LDS), S > 1 the three kernels per
+// iteration of mppi_split.hpp
+constexpr int kMppiOnePartPaths = 4096;
+
+static int mppi_check_scalars(const char *name, const MppiArgs &X)
+{
+    if (X.iterations < 1 || X.iterations > 16) return fail(QS_ERR_INVALID, "%s: iterations must be in [1, 16], got %d", name, X.iterations);
+    if (!(X.lambda > 0.0) || !std::isfinite(X.lambda)) return fail(QS_ERR_INVALID, "%s: lambda must be positive and finite, got %g", name, X.lambda);
+    if (!(X.sigma >= 0.0f) || !std::isfinite(X.sigma))
+        return fail(QS_ERR_INVALID, "%s: sigma must be non-negative and finite, got %g", name, (double)X.sigma);
+    if (X.shift != 0 && X.shift != 1) return fail(QS_ERR_INVALID, "%s: shift must be 0 or 1, got %d", name, X.shift);
+    if (!X.actions || !X.nominal_out) return fail(QS_ERR_INVALID, "%s: actions and nominal_out are required", name);
+    return QS_OK;
+}
+
+// as shooting_check_aligned
+static int mppi_check_aligned(const char *name, bool device, const MppiArgs &X)
+{
+    if (device && (((((uintptr_t)X.actions) | ((uintptr_t)X.nominal_out) | ((uintptr_t)X.nominal_in) | ((uintptr_t)X.noise)
+                     | ((uintptr_t)X.trace) | ((uintptr_t)X.candidates)) & 15u) || ((((uintptr_t)X.best_score) | ((uintptr_t)X.scores)) & 7u)))
+        return fail(QS_ERR_INVALID, "%s: actions, nominal_in, nominal_out, noise, trace and candidates must be 16-byte aligned, best_score and scores 8-byte", name);
+    return QS_OK;
+}
+
+// the workspace of a split plan: U [n][horizon] float4 | scores [n][paths] f64 | maxima [n S] f64 | partial sums [n S][horizon 4 + 1] f64
+struct MppiWorkspace {
+    uint64_t off_score, off_max, off_sum, bytes;
+    MppiWorkspace(int64_t n, const MppiArgs &X, int S)
+    {
+        const uint64_t slots = (uint64_t)n * (uint64_t)S, words = (uint64_t)X.horizon * 4 + 1;
+        off_score = (uint64_t)n * (uint64_t)X.horizon * sizeof(float4);
+        off_max = off_score + (uint64_t)n * (uint64_t)X.paths * sizeof(double);
+        off_sum = off_max + slots * sizeof(double);
+        bytes = off_sum + slots * words * sizeof(double);
+    }
+};
+
+static int launch_mppi(QsEnv *e, const StepArgs &A, const MppiArgs &X, int S)
+{
+    if (S == 1) {
+        const size_t lds = mppi_lds_bytes(X.horizon, X.paths);  // < 64 KiB at the largest horizon and paths: no function attribute
+        with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
+            hipLaunchKernelGGL((k_mppi<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(plan_block(X.paths)), lds, e->stream, A, X);
+        });
+    } else {
+        const MppiWorkspace L(e->n, X, S);
+        MppiPartArgs W{S, 0, reinterpret_cast<float4 *>(e->plan_ws), reinterpret_cast<double *>(e->plan_ws + L.off_score),
+                       reinterpret_cast<double *>(e->plan_ws + L.off_max), reinterpret_cast<double *>(e->plan_ws + L.off_sum)};
+        const unsigned slots = (unsigned)(e->n * S), block = plan_block((X.paths + S - 1) / S);
+        const size_t lds_roll = mppi_roll_lds_bytes(X.horizon), lds_sums = mppi_sums_lds_bytes(X.horizon);
+        for (int it = 0; it < X.iterations; ++it) {
+            W.it = it;
+            with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
+                hipLaunchKernelGGL((k_pathint_part_roll<INTEG, PARAMS>), dim3(slots), dim3(block), lds_roll, e->stream, A, X, W);
+            });
+            hipLaunchKernelGGL(k_pathint_part_sums, dim3(slots), dim3(block), lds_sums, e->stream, A, X, W);
+            hipLaunchKernelGGL(k_pathint_part_finish, dim3((unsigned)e->n), dim3(kTile), 0, e->stream, A, X, W);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return QS_OK;
+}
+
+// both entry points, as shooting_plan; the unsplit one keeps k_mppi's limit on `paths` as its own
+static int mppi_plan(QsEnv *e, const char *name, bool host_ok, int splits, MppiArgs X)
+{
+    if (int rc = mppi_check_scalars(name, X)) return rc;
+    if (int rc = mppi_check_aligned(name, !host_ok || e->cfg.io_space == QS_IO_DEVICE, X)) return rc;
+    const int S = plan_admit(e, name, host_ok, X.horizon, 128, X.paths, host_ok ? 65536 : kMppiOnePartPaths, kMppiOnePartPaths,
+                             X.objective, splits, 33);
+    if (S < 0) return S;
+    if (S > 1)
+        if (int rc = plan_workspace(e, name, MppiWorkspace(e->n, X, S).bytes)) return rc;
+    const size_t n = (size_t)e->n, seq = (size_t)X.horizon * 4;
+    UserIO io = user_io(e);
+    io.in(X.nominal_in, n * seq); io.in(X.noise, (size_t)X.iterations * X.paths * seq);
+    io.out(X.actions, n * 4); io.out(X.nominal_out, n * seq); io.out(X.best_score, n);
+    io.out(X.scores, n * X.iterations * X.paths); io.out(X.trace, n * (X.iterations + 1) * seq); io.out(X.candidates, n * X.paths * seq);
+    if (int r = io.push()) return r;
+    if (int r = launch_mppi(e, make_args(e), X, S)) return r;
     return io.pull();
 }
 
@@ -1658,27 +1771,8 @@ int qs_mppi_plan(QsEnv *e, int32_t horizon, int32_t paths, int32_t iterations, i
 {
     CHECK_ENV(e);
     Range rg_("qs_mppi_plan");
-    if (iterations < 1 || iterations > 16)
-        return fail(QS_ERR_INVALID, "qs_mppi_plan: iterations must be in [1, 16], got %d", iterations);
-    if (!(lambda > 0.0f) || !std::isfinite(lambda))
-        return fail(QS_ERR_INVALID, "qs_mppi_plan: lambda must be positive and finite, got %g", (double)lambda);
-    if (!(sigma >= 0.0f) || !std::isfinite(sigma))
-        return fail(QS_ERR_INVALID, "qs_mppi_plan: sigma must be non-negative and finite, got %g", (double)sigma);
-    if (shift != 0 && shift != 1) return fail(QS_ERR_INVALID, "qs_mppi_plan: shift must be 0 or 1, got %d", shift);
-    if (!actions || !nominal_out) return fail(QS_ERR_INVALID, "qs_mppi_plan: actions and nominal_out are required");
-    if (((((uintptr_t)actions) | ((uintptr_t)nominal_out) | ((uintptr_t)nominal_in) | ((uintptr_t)noise) | ((uintptr_t)trace)
-          | ((uintptr_t)candidates)) & 15u) || ((((uintptr_t)best_score) | ((uintptr_t)scores)) & 7u))
-        return fail(QS_ERR_INVALID, "qs_mppi_plan: actions, nominal_in, nominal_out, noise, trace and candidates must be 16-byte aligned, best_score and scores 8-byte");
-    if (int rc = plan_prepare(e, "qs_mppi_plan", horizon, 128, paths, 4096, objective, 33)) return rc;
-    const StepArgs A = make_args(e);
-    const MppiArgs X{horizon, paths, iterations, objective, shift, lambda, sigma, nominal_in, noise, actions, nominal_out,
-                     best_score, scores, trace, candidates};
-    const size_t lds = mppi_lds_bytes(horizon, paths);      // < 64 KiB at the largest horizon and paths: no function attribute
-    with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
-        hipLaunchKernelGGL((k_mppi<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(plan_block(paths)), lds, e->stream, A, X);
-    });
-    HIP_TRY(hipGetLastError());
-    return QS_OK;
+    return mppi_plan(e, "qs_mppi_plan", false, 1, MppiArgs{horizon, paths, iterations, objective, shift, lambda, sigma, nominal_in, noise,
+                                                          actions, nominal_out, best_score, scores, trace, candidates});
 }
 
 int qs_mppi_plan_split(QsEnv *e, int32_t horizon, int32_t paths, int32_t iterations, int32_t objective, float lambda, float sigma,
@@ -1687,80 +1781,8 @@ int qs_mppi_plan_split(QsEnv *e, int32_t horizon, int32_t paths, int32_t iterati
 {
     CHECK_ENV(e);
     Range rg_("qs_mppi_plan_split");
-    const char *const name = "qs_mppi_plan_split";
-    if (iterations < 1 || iterations > 16) return fail(QS_ERR_INVALID, "%s: iterations must be in [1, 16], got %d", name, iterations);
-    if (!(lambda > 0.0f) || !std::isfinite(lambda))
-        return fail(QS_ERR_INVALID, "%s: lambda must be positive and finite, got %g", name, (double)lambda);
-    if (!(sigma >= 0.0f) || !std::isfinite(sigma))
-        return fail(QS_ERR_INVALID, "%s: sigma must be non-negative and finite, got %g", name, (double)sigma);
-    if (shift != 0 && shift != 1) return fail(QS_ERR_INVALID, "%s: shift must be 0 or 1, got %d", name, shift);
-    if (!actions || !nominal_out) return fail(QS_ERR_INVALID, "%s: actions and nominal_out are required", name);
-    // a host handle's buffers are copied through the staging slices, which are aligned whatever the caller's are
-    if (e->cfg.io_space == QS_IO_DEVICE
-        && (((((uintptr_t)actions) | ((uintptr_t)nominal_out) | ((uintptr_t)nominal_in) | ((uintptr_t)noise) | ((uintptr_t)trace)
-              | ((uintptr_t)candidates)) & 15u) || ((((uintptr_t)best_score) | ((uintptr_t)scores)) & 7u)))
-        return fail(QS_ERR_INVALID, "%s: actions, nominal_in, nominal_out, noise, trace and candidates must be 16-byte aligned, best_score and scores 8-byte", name);
-    if (int rc = plan_check(e, name, horizon, 128, paths, 65536, objective, true)) return rc;
-    const int max_splits = std::min<int>(paths, kWideMaxSplits);
-    if (splits < 0 || splits > max_splits)
-        return fail(QS_ERR_INVALID, "%s: splits must be 0 (automatic) or in [1, min(paths, %d)] = [1, %d], got %d", name,
-                    kWideMaxSplits, max_splits, splits);
-    if (splits == 1 && paths > 4096)
-        return fail(QS_ERR_INVALID, "%s: splits = 1 launches qs_mppi_plan's kernel, which holds at most 4096 paths, got %d", name, paths);
-    int S = splits;
-    if (S == 0) {
-        if (int rc = plan_auto_splits(e, paths, &S)) return rc;
-        if (paths > 4096) S = std::max(S, 2);
-    }
-    if (e->n * (int64_t)S > 0x7fffffff)
-        return fail(QS_ERR_INVALID, "%s: one workgroup per part: envs x splits must be below 2^31, got %lld x %d", name, (long long)e->n, S);
-    if (int rc = plan_counter(e, name, 33)) return rc;
-    // workspace: U [n][horizon] float4 | scores [n][paths] f64 | maxima [n S] f64 | partial sums [n S][horizon 4 + 1] f64
-    const uint64_t n = (uint64_t)e->n, slots = n * (uint64_t)S, words = (uint64_t)horizon * 4 + 1;
-    const uint64_t off_score = n * (uint64_t)horizon * sizeof(float4), off_max = off_score + n * (uint64_t)paths * sizeof(double),
-                   off_sum = off_max + slots * sizeof(double), need = off_sum + slots * words * sizeof(double);
-    if (S > 1 && e->mppi_ws_bytes < need) {                 // grown, never shrunk
-        HIP_TRY(hipStreamSynchronize(e->stream));           // an earlier call's kernels may still use the old one
-        if (e->mppi_ws) HIP_TRY(hipFree(e->mppi_ws));
-        e->mppi_ws = nullptr; e->mppi_ws_bytes = 0;
-        if (hipMalloc((void **)&e->mppi_ws, need) != hipSuccess) {
-            (void)hipGetLastError();                        // reported here; the handle stays usable
-            e->mppi_ws = nullptr;
-            return fail(QS_ERR_HIP, "%s: cannot allocate the workspace of %llu bytes", name, (unsigned long long)need);
-        }
-        e->mppi_ws_bytes = need;
-    }
-    UserIO io = user_io(e);
-    io.in(nominal_in, (size_t)e->n * horizon * 4); io.in(noise, (size_t)iterations * paths * horizon * 4);
-    io.out(actions, (size_t)e->n * 4); io.out(nominal_out, (size_t)e->n * horizon * 4); io.out(best_score, (size_t)e->n);
-    io.out(scores, (size_t)e->n * iterations * paths); io.out(trace, (size_t)e->n * (iterations + 1) * horizon * 4);
-    io.out(candidates, (size_t)e->n * paths * horizon * 4);
-    if (int r = io.push()) return r;
-    const StepArgs A = make_args(e);
-    const MppiArgs X{horizon, paths, iterations, objective, shift, lambda, sigma, nominal_in, noise, actions, nominal_out,
-                     best_score, scores, trace, candidates};
-    if (S == 1) {
-        const size_t lds = mppi_lds_bytes(horizon, paths);
-        with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
-            hipLaunchKernelGGL((k_mppi<INTEG, PARAMS>), dim3((unsigned)e->n), dim3(plan_block(paths)), lds, e->stream, A, X);
-        });
-    } else {
-        MppiPartArgs W{S, 0, reinterpret_cast<float4 *>(e->mppi_ws), reinterpret_cast<double *>(e->mppi_ws + off_score),
-                       reinterpret_cast<double *>(e->mppi_ws + off_max), reinterpret_cast<double *>(e->mppi_ws + off_sum)};
-        const unsigned block = plan_block((paths + S - 1) / S);
-        const size_t lds_roll = mppi_roll_lds_bytes(horizon), lds_sums = mppi_sums_lds_bytes(horizon);
-        for (int it = 0; it < iterations; ++it) {
-            W.it = it;
-            with_integ_params(step_combo(e), [&]<int INTEG, bool PARAMS>() {
-                hipLaunchKernelGGL((k_pathint_part_roll<INTEG, PARAMS>), dim3((unsigned)slots), dim3(block), lds_roll, e->stream, A, X, W);
-            });
-            hipLaunchKernelGGL(k_pathint_part_sums, dim3((unsigned)slots), dim3(block), lds_sums, e->stream, A, X, W);
-            hipLaunchKernelGGL(k_pathint_part_finish, dim3((unsigned)e->n), dim3(kTile), 0, e->stream, A, X, W);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    return io.pull();
+    return mppi_plan(e, "qs_mppi_plan_split", true, splits, MppiArgs{horizon, paths, iterations, objective, shift, lambda, sigma, nominal_in,
+                                                                   noise, actions, nominal_out, best_score, scores, trace, candidates});
 }
 
 // ---- layer 1 ---------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // shooting.hpp -- random-shooting MPC (qs_shooting_plan): `paths` random action sequences of length `horizon` per env, rolled
 // through the exact env from the env's CURRENT state, scored, and the best one's first action returned -- the planner of
 // MPC-based_RL.py:170-210 (Mpc_Controller.choose_action / compute_cost) with the simulator itself as the model.  Read-only on
-// the handle.  A fragment of quadsim_hip.hip, included right after expert_rollout.hpp, nowhere else.
+// the handle.  A fragment of quadsim_hip.hip, included right after plan_common.hpp, nowhere else.
 //
 // Mapping: ONE WORKGROUP PER ENV (blockIdx.x = env), candidates on lanes.  Every lane of the workgroup reads the same env
 // record, so the loads of the env, its parameters and its step counter are wave-uniform (scalar loads; tile_lane's
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(kBlock) void k_shooting_plan(StepArgs A, PlanArgs X
     // the observation before step 0 is the current one, common to all candidates
     float obs0[12];
     rel_obs(e.sc, e.st, obs0);
-    const float pos0 = -(obs0[0] * obs0[0] + obs0[1] * obs0[1] + obs0[2] * obs0[2]);
+    const float pos0 = plan_pos(obs0);
     const bool by_position = X.objective != 0;
 
     double best_s = -__builtin_huge_val();
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(kBlock) void k_shooting_plan(StepArgs A, PlanArgs X
             for (int i = 0; i < 13; ++i) ec.st[i] = r[i];
             env_step_chaser<INTEG>(ec, a, P, A.C, r[13] != 0.0f, obs, reward, flags);
             if (!by_position) score += (double)reward;
-            pos = -(obs[0] * obs[0] + obs[1] * obs[1] + obs[2] * obs[2]);
+            pos = plan_pos(obs);
             alive = (flags & (FLAG_OVERLIMIT | FLAG_OVERTIME)) == 0;      // `done` of the step kernels (maybe_reset)
         }
         if (X.scores) X.scores[env * X.paths + c] = score;

@@ -10,8 +10,8 @@
 //      is k_shooting_plan up to the in-workgroup reduction -- wave 0 integrates the target into the LDS rows (every part
 //      repeats that: `horizon` steps of one wave), lanes take c = lo + threadIdx.x, + blockDim.x, ... and keep the float64
 //      score and the running best under plan_better -- and thread 0 writes the part's (score, index) to slot env * S + part
-//      of the handle's workspace.  An empty part writes (-inf, 0x7fffffff), which loses to everything.  `scores` is the only
-//      output it writes.
+//      of the handle's workspace (the one workspace of both split planners: plan_workspace in quadsim_hip.hip).  An empty
+//      part writes (-inf, 0x7fffffff), which loses to everything.  `scores` is the only output it writes.
 //   2. k_wide_finish, one 64-lane workgroup per env: lanes read parts lane, lane + 64, ..., reduce with plan_better over
 //      shuffles, and write best_score, best_index, actions and sequence, regenerated from the winner's index (lane h draws
 //      step h).  It needs k, gid and the seed only: no INTEG / PARAMS.
@@ -41,8 +41,8 @@ __global__ __launch_bounds__(kBlock) void k_wide_candidates(StepArgs A, PlanArgs
 
     const int64_t env = blockIdx.x / (unsigned)W.splits;    // < A.n: the grid is n x S workgroups
     const int part = (int)(blockIdx.x % (unsigned)W.splits);
-    const int chunk = (X.paths + W.splits - 1) / W.splits;  // S <= 1024, chunk <= 65536: part * chunk fits an int
-    const int lo = min(part * chunk, X.paths), hi = min(lo + chunk, X.paths);
+    const PlanPart own = plan_part(part, W.splits, X.paths);
+    const int lo = own.lo, hi = own.hi;
     const int64_t tile = env / kTile;
     const int slot = (int)(env % kTile);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(kBlock) void k_wide_candidates(StepArgs A, PlanArgs
     // the observation before step 0 is the current one, common to all candidates
     float obs0[12];
     rel_obs(e.sc, e.st, obs0);
-    const float pos0 = -(obs0[0] * obs0[0] + obs0[1] * obs0[1] + obs0[2] * obs0[2]);
+    const float pos0 = plan_pos(obs0);
     const bool by_position = X.objective != 0;
 
 #pragma clang loop unroll(disable)
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(kBlock) void k_wide_candidates(StepArgs A, PlanArgs
             for (int i = 0; i < 13; ++i) ec.st[i] = r[i];
             env_step_chaser<INTEG>(ec, a, P, A.C, r[13] != 0.0f, obs, reward, flags);
             if (!by_position) score += (double)reward;
-            pos = -(obs[0] * obs[0] + obs[1] * obs[1] + obs[2] * obs[2]);
+            pos = plan_pos(obs);
             alive = (flags & (FLAG_OVERLIMIT | FLAG_OVERTIME)) == 0;      // `done` of the step kernels (maybe_reset)
         }
         if (X.scores) X.scores[env * X.paths + c] = score;

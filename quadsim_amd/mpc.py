@@ -99,6 +99,41 @@ def plan_splits(env, paths):
     return int(s.value)
 
 
+def _torch_arrays(env):
+    """the array factory of the device path -> (new(shape, dtype), float32, float64, int32): uninitialised tensors on the env's
+    device"""
+    import torch
+    dev = env.device
+    return (lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)), torch.float32, torch.float64, torch.int32
+
+
+def _numpy_arrays():
+    """the array factory of the host path, as _torch_arrays: zeroed numpy arrays"""
+    import numpy as np
+    return np.zeros, np.float32, np.float64, np.int32
+
+
+def _call_host(env, fn, scalars, bufs):
+    """the planner entry point `fn` on the QS_IO_HOST handle of `env` (numpy arrays as their addresses, None as NULL)"""
+    _lib.check(fn(env._h, *scalars, *[None if a is None else a.ctypes.data_as(C.c_void_p) for a in bufs]), fn.__name__)
+
+
+def _host_result(out, **as_python):
+    """the host path's view of an output dict: the leading env axis (of length 1) stripped"""
+    return {k: as_python[k](v[0]) if k in as_python else v[0] for k, v in out.items()}
+
+
+def _shooting_buffers(arrays, n, horizon, paths, return_scores, return_sequence):
+    """-> (the output dict of a shooting plan over n envs, the entry points' buffer arguments) from an array factory"""
+    new, f4, f8, i4 = arrays
+    out = {"actions": new((n, 4), f4), "best_score": new((n,), f8), "best_index": new((n,), i4)}
+    if return_sequence:
+        out["sequence"] = new((n, horizon, 4), f4)
+    if return_scores:
+        out["scores"] = new((n, paths), f8)
+    return out, (out["actions"], out["best_score"], out["best_index"], out.get("sequence"), out.get("scores"))
+
+
 def shooting_plan(env, horizon=20, paths=200, objective="reward", return_scores=False, return_sequence=False, splits=None):
     """One plan for every env of `env` from its current state (the env is not modified).  objective "reward": the sum of the
     step rewards; "position": the reference's ``-sum |rel_pos|^2`` over the observations before each step.  Returns a dict of
@@ -109,16 +144,7 @@ def shooting_plan(env, horizon=20, paths=200, objective="reward", return_scores=
     candidates over S workgroups and "auto" lets the library choose S (qs_shooting_plan_split).  The results have the same
     bits either way."""
     horizon, paths, obj, splits = check_plan_args(horizon, paths, objective, splits)
-    import torch
-    n, dev = env.num_envs, env.device
-    out = {"actions": torch.empty((n, 4), dtype=torch.float32, device=dev),
-           "best_score": torch.empty((n,), dtype=torch.float64, device=dev),
-           "best_index": torch.empty((n,), dtype=torch.int32, device=dev)}
-    if return_sequence:
-        out["sequence"] = torch.empty((n, horizon, 4), dtype=torch.float32, device=dev)
-    if return_scores:
-        out["scores"] = torch.empty((n, paths), dtype=torch.float64, device=dev)
-    bufs = (out["actions"], out["best_score"], out["best_index"], out.get("sequence"), out.get("scores"))
+    out, bufs = _shooting_buffers(_torch_arrays(env), env.num_envs, horizon, paths, return_scores, return_sequence)
     if splits is None:
         _call(env, "qs_shooting_plan", horizon, paths, obj, *bufs)
     else:
@@ -132,20 +158,10 @@ def shooting_plan_host(env, horizon=20, paths=200, objective="reward", splits="a
     path of qs_shooting_plan_split -- actions [4] float32, best_score (numpy float64), best_index (int), plus sequence
     [horizon,4] and scores [paths] float64 on request.  `splits` None counts as 1: the split entry point is the only one that
     takes host handles, and with one part it launches the kernel of qs_shooting_plan."""
-    import numpy as np
     horizon, paths, obj, splits = check_plan_args(horizon, paths, objective, splits)
-    act, score, index = np.zeros((1, 4), np.float32), np.zeros(1, np.float64), np.zeros(1, np.int32)
-    seq = np.zeros((1, horizon, 4), np.float32) if return_sequence else None
-    sc = np.zeros((1, paths), np.float64) if return_scores else None
-    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)    # noqa: E731
-    _lib.check(env._lib.qs_shooting_plan_split(env._h, horizon, paths, obj, 1 if splits is None else splits, p(act), p(score),
-                                          p(index), p(seq), p(sc)), "qs_shooting_plan_split")
-    out = {"actions": act[0], "best_score": score[0], "best_index": int(index[0])}
-    if return_sequence:
-        out["sequence"] = seq[0]
-    if return_scores:
-        out["scores"] = sc[0]
-    return out
+    out, bufs = _shooting_buffers(_numpy_arrays(), 1, horizon, paths, return_scores, return_sequence)
+    _call_host(env, env._lib.qs_shooting_plan_split, (horizon, paths, obj, 1 if splits is None else splits), bufs)
+    return _host_result(out, best_index=int)
 
 
 class ShootingMPC:
@@ -201,6 +217,20 @@ def check_mppi_split_args(horizon, paths, iterations, objective, lam, sigma, shi
     return out + (splits,)
 
 
+def _mppi_buffers(arrays, n, horizon, paths, iterations, nominal, noise, return_scores, return_trace, return_candidates):
+    """-> (the output dict of an MPPI plan over n envs, the entry points' buffer arguments) from an array factory"""
+    new, f4, f8, _ = arrays
+    out = {"actions": new((n, 4), f4), "nominal": new((n, horizon, 4), f4), "best_score": new((n,), f8)}
+    if return_scores:
+        out["scores"] = new((n, iterations, paths), f8)
+    if return_trace:
+        out["trace"] = new((n, iterations + 1, horizon, 4), f4)
+    if return_candidates:
+        out["candidates"] = new((n, paths, horizon, 4), f4)
+    return out, (nominal, noise, out["actions"], out["nominal"], out["best_score"], out.get("scores"), out.get("trace"),
+                 out.get("candidates"))
+
+
 def mppi_plan(env, horizon=20, paths=200, iterations=2, objective="reward", lam=MPPI_DEFAULT_LAMBDA, sigma=MPPI_DEFAULT_SIGMA,
               nominal=None, shift=False, noise=None, return_scores=False, return_trace=False, return_candidates=False,
               splits=None):
@@ -230,18 +260,8 @@ def mppi_plan(env, horizon=20, paths=200, iterations=2, objective="reward", lam=
                 and tuple(t.shape) == shape and t.is_contiguous()):
             raise ValueError("%s must be a contiguous float32 tensor of shape %s on %s" % (name, shape, dev))
         return t
-    nominal = given(nominal, (n, horizon, 4), "nominal")
-    noise = given(noise, (iterations, paths, horizon, 4), "noise")
-    out = {"actions": torch.empty((n, 4), dtype=torch.float32, device=dev),
-           "nominal": torch.empty((n, horizon, 4), dtype=torch.float32, device=dev),
-           "best_score": torch.empty((n,), dtype=torch.float64, device=dev)}
-    if return_scores:
-        out["scores"] = torch.empty((n, iterations, paths), dtype=torch.float64, device=dev)
-    if return_trace:
-        out["trace"] = torch.empty((n, iterations + 1, horizon, 4), dtype=torch.float32, device=dev)
-    if return_candidates:
-        out["candidates"] = torch.empty((n, paths, horizon, 4), dtype=torch.float32, device=dev)
-    bufs = (nominal, noise, out["actions"], out["nominal"], out["best_score"], out.get("scores"), out.get("trace"), out.get("candidates"))
+    out, bufs = _mppi_buffers(_torch_arrays(env), n, horizon, paths, iterations, given(nominal, (n, horizon, 4), "nominal"),
+                              given(noise, (iterations, paths, horizon, 4), "noise"), return_scores, return_trace, return_candidates)
     if splits is None:
         _call(env, "qs_mppi_plan", horizon, paths, iterations, obj, lam, sigma, shift, *bufs)
     else:
@@ -268,23 +288,10 @@ def mppi_plan_host(env, horizon=20, paths=200, iterations=2, objective="reward",
         if a.shape != shape:
             raise ValueError("%s must have shape %s, got %s" % (name, shape, a.shape))
         return a
-    nominal = given(nominal, (horizon, 4), "nominal")
-    noise = given(noise, (iterations, paths, horizon, 4), "noise")
-    act, nom, score = np.zeros((1, 4), np.float32), np.zeros((1, horizon, 4), np.float32), np.zeros(1, np.float64)
-    sc = np.zeros((1, iterations, paths), np.float64) if return_scores else None
-    tr = np.zeros((1, iterations + 1, horizon, 4), np.float32) if return_trace else None
-    cand = np.zeros((1, paths, horizon, 4), np.float32) if return_candidates else None
-    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)    # noqa: E731
-    _lib.check(env._lib.qs_mppi_plan_split(env._h, horizon, paths, iterations, obj, lam, sigma, shift, splits, p(nominal), p(noise),
-                                           p(act), p(nom), p(score), p(sc), p(tr), p(cand)), "qs_mppi_plan_split")
-    out = {"actions": act[0], "nominal": nom[0], "best_score": score[0]}
-    if return_scores:
-        out["scores"] = sc[0]
-    if return_trace:
-        out["trace"] = tr[0]
-    if return_candidates:
-        out["candidates"] = cand[0]
-    return out
+    out, bufs = _mppi_buffers(_numpy_arrays(), 1, horizon, paths, iterations, given(nominal, (horizon, 4), "nominal"),
+                              given(noise, (iterations, paths, horizon, 4), "noise"), return_scores, return_trace, return_candidates)
+    _call_host(env, env._lib.qs_mppi_plan_split, (horizon, paths, iterations, obj, lam, sigma, shift, splits), bufs)
+    return _host_result(out)
 
 
 class MPPI:

@@ -276,6 +276,31 @@ def test_workspace_grows_is_reused_and_belongs_to_its_handle(qa, torch):
     b.close()
 
 
+def test_one_workspace_serves_both_planners_on_one_handle(qa, torch):
+    """Shooting and MPPI split plans share the handle's one workspace: issued back to back on one handle with nothing read back
+    in between -- shooting S = 2, MPPI S = 256 (grows the buffer behind shooting's kernels), shooting S = 256, MPPI S = 2,
+    shooting S = 2 -- every output of every call has the bits a fresh twin handle gives for that call alone.  1000 paths:
+    ragged and empty parts at S = 256, a lane loop at S = 2."""
+    every = dict(shooting=dict(return_scores=True, return_sequence=True),
+                 mppi=dict(return_scores=True, return_trace=True, return_candidates=True))
+
+    def issue(env, family, s):
+        if family == "shooting":
+            return env.shooting_plan(3, 1000, "reward", splits=s, **every[family])
+        return env.mppi_plan(3, 1000, 2, "reward", LAM, SIGMA, splits=s, **every[family])
+
+    host = lambda out: {k: v.cpu().numpy() for k, v in out.items()}      # noqa: E731
+    twin = make_handle(qa, "docking-v2", "rk4", True)
+    want = {(f, s): host(issue(twin, f, s)) for f in ("shooting", "mppi") for s in (2, 256)}
+    twin.close()
+    env = make_handle(qa, "docking-v2", "rk4", True)
+    sequence = [("shooting", 2), ("mppi", 256), ("shooting", 256), ("mppi", 2), ("shooting", 2)]
+    got = [issue(env, f, s) for f, s in sequence]             # nothing is read back before the last call is issued
+    for i, (key, out) in enumerate(zip(sequence, got)):
+        _assert_same_plan(host(out), want[key], (i,) + key)
+    env.close()
+
+
 # ---------------------------------------------------------------- 9. host handles
 def _shim_state(shim):
     """the whole state and the step counter of a single-env shim, through its host handle"""

@@ -3,18 +3,14 @@
 checks."""
 import os
 import re
-import shutil
-import subprocess
 import types
 
 import numpy as np
 import pytest
 
-import kernel_notes
 import mppi_ref
 import shooting_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from plan_cases_cpu import ALL_COMBOS, ROOT, code_object, declarations, library_and_header, notes, run_c_caller  # noqa: F401
 
 C_PROGRAM = r"""
 #include <stdio.h>
@@ -36,47 +32,28 @@ MPPI_SIG = ("int qs_mppi_plan(QsEnv *env, int32_t horizon, int32_t paths, int32_
             "double *best_score, double *scores, float *trace, float *candidates);")
 
 
-def _declarations(header):
-    text = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    text = re.sub(r"\s+", " ", text)
-    return re.sub(r" ([,)])", r"\1", text)
-
-
 def test_mppi_abi_symbol_and_plain_c(tmp_path):
     """the header declares the entry point with the agreed signature, the library exports it, QS_VERSION stays 131, and a C99
     caller that takes its address compiles with -Wall -Werror and gets QS_ERR_INVALID with a message for a null handle"""
     from quadsim_amd import _lib
-    _lib.build_library()
-    lib = _lib.load()
-    header = open(os.path.join(ROOT, "include", "quadsim.h")).read()
-    assert MPPI_SIG in _declarations(header)
+    lib, header = library_and_header()
+    assert MPPI_SIG in declarations(header)
     assert hasattr(lib, "qs_mppi_plan") and "qs_mppi_plan" in _lib.EXPORTS
     assert len(lib.qs_mppi_plan.argtypes) == 16
     assert lib.qs_version() == 131
-    assert shutil.which("gcc") is not None
-    src = tmp_path / "mppi.c"
-    src.write_text(C_PROGRAM)
-    exe = str(tmp_path / "mppi")
-    libdir = os.path.join(ROOT, "quadsim_amd", "csrc")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + libdir,
-                           "-lquadsim_hip", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    assert out.stdout.split() == ["-1", "-1", "131", "msg"]
+    assert run_c_caller(tmp_path, C_PROGRAM, "mppi") == ["-1", "-1", "131", "msg"]
 
 
-def test_mppi_kernel_instantiations_and_resources(tmp_path):
+def test_mppi_kernel_instantiations_and_resources(notes):
     """exactly four k_mppi (INTEG x PARAMS; objective and noise source are runtime arguments); no private segment, no spills,
     at most 128 VGPRs (four waves per SIMD), 256 threads at most, LDS dynamic"""
-    notes = kernel_notes.kernel_notes(kernel_notes.code_object(tmp_path))
     got = {}
     for sym in notes:
         if "mppi" in sym:
             m = re.search(r"\d+k_mppiILi(\d)ELb([01])EEEv", sym)
             assert m, sym
             got[(int(m.group(1)), int(m.group(2)))] = sym
-    assert set(got) == {(i, p) for i in (0, 1) for p in (0, 1)}, sorted(got)
+    assert set(got) == ALL_COMBOS, sorted(got)
     for key, sym in got.items():
         n = notes[sym]
         print(key, n)

@@ -1,16 +1,12 @@
 """-m "not gpu": qs_mppi_plan_split -- the C ABI from plain C99, the instantiations and resources of the three new kernels in
 the built library beside the planner kernels that stay, and the Python `splits` argument of the MPPI entry points."""
-import os
 import re
-import shutil
-import subprocess
 import types
 
 import pytest
 
-import kernel_notes
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from plan_cases_cpu import (ALL_COMBOS, StubLib, code_object, combos, declarations, library_and_header, notes,  # noqa: F401
+                            run_c_caller, stub_env)
 
 C_PROGRAM = r"""
 #include <stdio.h>
@@ -33,23 +29,14 @@ SPLIT_SIG = ("int qs_mppi_plan_split(QsEnv *env, int32_t horizon, int32_t paths,
              "float *actions, float *nominal_out, double *best_score, double *scores, float *trace, float *candidates);")
 
 
-def _declarations(header):
-    """the header without comments, white space normalised"""
-    text = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    text = re.sub(r"\s+", " ", text)
-    return re.sub(r" ([,)])", r"\1", text)
-
-
 def test_split_abi_symbol_and_plain_c(tmp_path):
     """include/quadsim.h declares the entry point with the agreed signature and documents the one-part rule (qs_mppi_plan's
     kernel, at most 4096 paths) and the automatic rule, the library exports it, QS_VERSION stays 131, and a C99 caller that
     takes its address compiles with -Wall -Werror, links and gets QS_ERR_INVALID with a message for a null handle, without a
     device"""
     from quadsim_amd import _lib
-    _lib.build_library()
-    lib = _lib.load()
-    header = open(os.path.join(ROOT, "include", "quadsim.h")).read()
-    assert SPLIT_SIG in _declarations(header)
+    lib, header = library_and_header()
+    assert SPLIT_SIG in declarations(header)
     doc = re.sub(r"\s+\*?\s*", " ", header[header.index("/* qs_mppi_plan with ONE ENV'S CANDIDATES"):header.index("int qs_mppi_plan_split(")])
     assert "splits = 1 launches qs_mppi_plan's own kernel" in doc and "S = 1 needs paths <= 4096" in doc
     assert "what qs_shooting_plan_splits reports), raised to 2 when paths > 4096" in doc
@@ -57,39 +44,20 @@ def test_split_abi_symbol_and_plain_c(tmp_path):
     assert hasattr(lib, "qs_mppi_plan_split") and "qs_mppi_plan_split" in _lib.EXPORTS
     assert len(lib.qs_mppi_plan_split.argtypes) == 17
     assert lib.qs_version() == 131
-    assert shutil.which("gcc") is not None
-    src = tmp_path / "mppi_split.c"
-    src.write_text(C_PROGRAM)
-    exe = str(tmp_path / "mppi_split")
-    libdir = os.path.join(ROOT, "quadsim_amd", "csrc")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + libdir,
-                           "-lquadsim_hip", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    assert out.stdout.split() == ["-1", "msg", "-1", "131"]
+    assert run_c_caller(tmp_path, C_PROGRAM, "mppi_split") == ["-1", "msg", "-1", "131"]
 
 
 # ---------------------------------------------------------------- code object
-@pytest.fixture(scope="module")
-def notes(tmp_path_factory):
-    return kernel_notes.kernel_notes(kernel_notes.code_object(tmp_path_factory.mktemp("isa_mppi_split")))
-
-
-def _combos(notes, pattern):
-    return {(int(m.group(1)), int(m.group(2))): sym for sym in notes for m in [re.search(pattern, sym)] if m}
-
-
 def test_part_kernel_instantiations_and_resources(notes):
     """exactly four k_pathint_part_roll (INTEG x PARAMS), one k_pathint_part_sums and one k_pathint_part_finish -- the weights and the
     sums need the candidates' keys only, no integrator and no per-env parameters, so those two have no template parameters --
     and no other kernel with `k_pathint` in its name; no private segment, no spills, at most 128 VGPRs; 256 / 256 / 64
     threads at most; all LDS is dynamic (the finish kernel has none)"""
-    roll = _combos(notes, r"\d+k_pathint_part_rollILi(\d)ELb([01])EEEv")
+    roll = combos(notes, r"\d+k_pathint_part_rollILi(\d)ELb([01])EEEv")
     sums = [s for s in notes if re.search(r"\d+k_pathint_part_sumsE", s)]
     finish = [s for s in notes if re.search(r"\d+k_pathint_part_finishE", s)]
     other = [s for s in notes if "k_pathint" in s and s not in roll.values() and s not in sums and s not in finish]
-    assert set(roll) == {(i, p) for i in (0, 1) for p in (0, 1)} and len(sums) == 1 and len(finish) == 1 and not other, \
+    assert set(roll) == ALL_COMBOS and len(sums) == 1 and len(finish) == 1 and not other, \
         (sorted(roll), sums, finish, other)
     for key, sym in list(roll.items()) + [("sums", sums[0]), ("finish", finish[0])]:
         n = notes[sym]
@@ -105,8 +73,8 @@ def test_existing_planner_kernels_are_still_there(notes):
     """the four k_mppi, the four k_shooting_plan, the four k_wide_candidates and the one k_wide_finish"""
     for pattern in (r"\d+k_mppiILi(\d)ELb([01])EEEv", r"\d+k_shooting_planILi(\d)ELb([01])EEEv",
                     r"\d+k_wide_candidatesILi(\d)ELb([01])EEEv"):
-        got = _combos(notes, pattern)
-        assert set(got) == {(i, p) for i in (0, 1) for p in (0, 1)}, (pattern, sorted(got))
+        got = combos(notes, pattern)
+        assert set(got) == ALL_COMBOS, (pattern, sorted(got))
         for key, sym in got.items():
             n = notes[sym]
             assert n["private_segment_fixed_size"] == 0 and n["vgpr_spill_count"] == 0, (key, n)
@@ -146,28 +114,13 @@ def test_splits_argument_checks_raise_before_any_gpu_work():
         mpc.check_mppi_args(20, 4097, 2, "reward", 0.5, 0.4, False)
 
 
-class _StubLib:
-    """records the name and the scalar arguments of every entry point called on it and reports success"""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def fn(handle, *args):
-            self.calls.append((name, tuple(a for a in args if isinstance(a, (int, float)))))
-            return 0
-        return fn
-
-
 def test_splits_none_keeps_the_old_call_path():
     """by symbol name on a stub library: without `splits` the call is qs_mppi_plan with its old scalar arguments; an int or
     "auto" (= 0) goes to qs_mppi_plan_split with `splits` after `shift`"""
     torch = pytest.importorskip("torch")
     from quadsim_amd import mpc
-    lib = _StubLib()
-    noop = lambda: None                                       # noqa: E731
-    env = types.SimpleNamespace(num_envs=3, device=torch.device("cpu"), _lib=lib, _h=None, _use_current_stream=noop,
-                                _inputs_ready=noop, _outputs_ready=noop)
+    lib = StubLib((int, float))
+    env = stub_env(torch, lib)
     out = mpc.mppi_plan(env, 5, 64, 2, "position", 0.5, 0.25)
     assert out["actions"].shape == (3, 4) and out["nominal"].shape == (3, 5, 4) and "scores" not in out
     mpc.MPPI(env, 5, 64, 2, lam=0.5, sigma=0.25).act()

@@ -2,7 +2,6 @@
 built library, the Python argument checks, and the candidate keying of the float64 reference (tests/shooting_ref.py)."""
 import os
 import re
-import shutil
 import subprocess
 import types
 
@@ -11,8 +10,8 @@ import pytest
 
 import kernel_notes
 import shooting_ref
+from plan_cases_cpu import ALL_COMBOS, ROOT, code_object, declarations, library_and_header, notes, run_c_caller  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = kernel_notes.LLVM
 
 C_PROGRAM = r"""
@@ -34,38 +33,19 @@ PLAN_SIG = ("int qs_shooting_plan(QsEnv *env, int32_t horizon, int32_t paths, in
             "int32_t *best_index, float *sequence, double *scores);")
 
 
-def _declarations(header):
-    """the header without comments, white space normalised"""
-    text = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    text = re.sub(r"\s+", " ", text)
-    return re.sub(r" ([,)])", r"\1", text)
-
-
 def test_shooting_abi_symbol_and_plain_c(tmp_path):
     """include/quadsim.h declares the entry point with the agreed signature and the objective ids, the library exports it,
     QS_VERSION stays 131, and a C99 caller that takes its address compiles, links and gets QS_ERR_INVALID for a null handle"""
     from quadsim_amd import _lib
-    _lib.build_library()
-    lib = _lib.load()
-    header = open(os.path.join(ROOT, "include", "quadsim.h")).read()
-    decl = _declarations(header)
+    lib, header = library_and_header()
+    decl = declarations(header)
     assert PLAN_SIG in decl
     assert "enum { QS_SHOOT_REWARD = 0, QS_SHOOT_POSITION = 1 };" in decl
     assert "MPC-based_RL.py:170-210" in header
     assert hasattr(lib, "qs_shooting_plan") and "qs_shooting_plan" in _lib.EXPORTS
     assert lib.qs_shooting_plan.argtypes is not None and len(lib.qs_shooting_plan.argtypes) == 9
     assert lib.qs_version() == 131
-    assert shutil.which("gcc") is not None
-    src = tmp_path / "plan.c"
-    src.write_text(C_PROGRAM)
-    exe = str(tmp_path / "plan")
-    libdir = os.path.join(ROOT, "quadsim_amd", "csrc")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + libdir,
-                           "-lquadsim_hip", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    assert out.stdout.split() == ["-1", "-1", "131", "0", "1", "msg"]
+    assert run_c_caller(tmp_path, C_PROGRAM, "plan") == ["-1", "-1", "131", "0", "1", "msg"]
 
 
 def test_plan_stream_id_is_new():
@@ -78,11 +58,6 @@ def test_plan_stream_id_is_new():
 
 
 # ---------------------------------------------------------------- ISA
-@pytest.fixture(scope="module")
-def code_object(tmp_path_factory):
-    return kernel_notes.code_object(tmp_path_factory.mktemp("isa_shooting"))
-
-
 def _plan_kernels(notes):
     """{(INTEG, PARAMS): symbol} of the planning kernel; any other kernel with `shooting` or `plan` in its name counts as
     unexpected"""
@@ -96,12 +71,11 @@ def _plan_kernels(notes):
     return got, other
 
 
-def test_plan_kernel_instantiations_and_resources(code_object):
+def test_plan_kernel_instantiations_and_resources(notes):
     """four instantiations (INTEG x PARAMS; the objective is a runtime argument, there is no RMODE); no private segment, no
     spills; LDS is dynamic (sized by the horizon); 256 threads at most; five (frozen) / four (RK4) waves per SIMD"""
-    notes = kernel_notes.kernel_notes(code_object)
     got, other = _plan_kernels(notes)
-    assert set(got) == {(i, p) for i in (0, 1) for p in (0, 1)} and not other, (sorted(got), other)
+    assert set(got) == ALL_COMBOS and not other, (sorted(got), other)
     for key, sym in got.items():
         n = notes[sym]
         print(key, n)
@@ -110,10 +84,10 @@ def test_plan_kernel_instantiations_and_resources(code_object):
         assert n["vgpr_count"] <= 128, (key, n)               # four waves per SIMD at least
 
 
-def test_plan_kernel_isa(code_object):
+def test_plan_kernel_isa(code_object, notes):
     """no scratch instruction, no buffer store, no matrix instruction; the target rows go through LDS
     and the kernel has its barriers"""
-    got, _ = _plan_kernels(kernel_notes.kernel_notes(code_object))
+    got, _ = _plan_kernels(notes)
     syms = sorted(got.values())
     dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", "--disassemble-symbols=" + ",".join(syms),
                           code_object], capture_output=True, text=True, check=True).stdout

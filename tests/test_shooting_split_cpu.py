@@ -1,16 +1,12 @@
 """-m "not gpu": qs_shooting_plan_split / qs_shooting_plan_splits -- the C ABI from plain C99, the instantiations and resources
 of the two new kernels in the built library beside the eight planner kernels that stay, and the Python `splits` argument."""
-import os
 import re
-import shutil
-import subprocess
 import types
 
 import pytest
 
-import kernel_notes
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from plan_cases_cpu import (ALL_COMBOS, StubLib, code_object, combos, declarations, library_and_header, notes,  # noqa: F401
+                            run_c_caller, stub_env)
 
 C_PROGRAM = r"""
 #include <stdio.h>
@@ -37,59 +33,31 @@ SPLIT_SIG = ("int qs_shooting_plan_split(QsEnv *env, int32_t horizon, int32_t pa
 SPLITS_SIG = "int qs_shooting_plan_splits(QsEnv *env, int32_t paths, int32_t *splits);"
 
 
-def _declarations(header):
-    """the header without comments, white space normalised"""
-    text = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    text = re.sub(r"\s+", " ", text)
-    return re.sub(r" ([,)])", r"\1", text)
-
-
 def test_split_abi_symbols_and_plain_c(tmp_path):
     """include/quadsim.h declares both entry points with the agreed signatures and documents the automatic rule, the library
     exports them, QS_VERSION stays 131, and a C99 caller that takes their addresses compiles with -Wall -Werror, links and
     gets QS_ERR_INVALID with a message for a null handle from both, without a device; `splits` is left alone on failure"""
     from quadsim_amd import _lib
-    _lib.build_library()
-    lib = _lib.load()
-    header = open(os.path.join(ROOT, "include", "quadsim.h")).read()
-    decl = _declarations(header)
+    lib, header = library_and_header()
+    decl = declarations(header)
     assert SPLIT_SIG in decl and SPLITS_SIG in decl
     assert "multiProcessorCount" in header and "QS_IO_HOST handles are accepted" in header
     for name, nargs in (("qs_shooting_plan_split", 10), ("qs_shooting_plan_splits", 3)):
         assert hasattr(lib, name) and name in _lib.EXPORTS
         assert len(getattr(lib, name).argtypes) == nargs
     assert lib.qs_version() == 131
-    assert shutil.which("gcc") is not None
-    src = tmp_path / "split.c"
-    src.write_text(C_PROGRAM)
-    exe = str(tmp_path / "split")
-    libdir = os.path.join(ROOT, "quadsim_amd", "csrc")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + libdir,
-                           "-lquadsim_hip", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr
-    assert out.stdout.split() == ["-1", "msg", "-1", "msg", "-7", "-1", "131"]
+    assert run_c_caller(tmp_path, C_PROGRAM, "split") == ["-1", "msg", "-1", "msg", "-7", "-1", "131"]
 
 
 # ---------------------------------------------------------------- code object
-@pytest.fixture(scope="module")
-def notes(tmp_path_factory):
-    return kernel_notes.kernel_notes(kernel_notes.code_object(tmp_path_factory.mktemp("isa_shooting_split")))
-
-
-def _combos(notes, pattern):
-    return {(int(m.group(1)), int(m.group(2))): sym for sym in notes for m in [re.search(pattern, sym)] if m}
-
-
 def test_wide_kernel_instantiations_and_resources(notes):
     """exactly four k_wide_candidates (INTEG x PARAMS) and one k_wide_finish (no template parameters), and no other kernel
     with `k_wide` in its name; no private segment, no spills, at most 128 VGPRs; 256 / 64 threads at most; the candidates
     kernel's LDS is dynamic (sized by the horizon) and the finish kernel has none"""
-    cand = _combos(notes, r"\d+k_wide_candidatesILi(\d)ELb([01])EEEv")
+    cand = combos(notes, r"\d+k_wide_candidatesILi(\d)ELb([01])EEEv")
     finish = [s for s in notes if re.search(r"\d+k_wide_finishE", s)]
     other = [s for s in notes if "k_wide" in s and s not in cand.values() and s not in finish]
-    assert set(cand) == {(i, p) for i in (0, 1) for p in (0, 1)} and len(finish) == 1 and not other, (sorted(cand), finish, other)
+    assert set(cand) == ALL_COMBOS and len(finish) == 1 and not other, (sorted(cand), finish, other)
     for key, sym in list(cand.items()) + [("finish", finish[0])]:
         n = notes[sym]
         print(key, n)
@@ -102,8 +70,8 @@ def test_wide_kernel_instantiations_and_resources(notes):
 def test_existing_planner_kernels_are_still_there(notes):
     """the four k_shooting_plan and the four k_mppi, with the resources their own tests assert"""
     for pattern in (r"\d+k_shooting_planILi(\d)ELb([01])EEEv", r"\d+k_mppiILi(\d)ELb([01])EEEv"):
-        got = _combos(notes, pattern)
-        assert set(got) == {(i, p) for i in (0, 1) for p in (0, 1)}, (pattern, sorted(got))
+        got = combos(notes, pattern)
+        assert set(got) == ALL_COMBOS, (pattern, sorted(got))
         for key, sym in got.items():
             n = notes[sym]
             assert n["private_segment_fixed_size"] == 0 and n["vgpr_spill_count"] == 0, (key, n)
@@ -141,28 +109,13 @@ def test_splits_argument_checks_raise_before_any_gpu_work():
         quadsim_amd.plan_splits(env, 65537)
 
 
-class _StubLib:
-    """records the name and the scalar arguments of every entry point called on it and reports success"""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def fn(handle, *args):
-            self.calls.append((name, tuple(a for a in args if isinstance(a, int))))
-            return 0
-        return fn
-
-
 def test_splits_none_keeps_the_old_call_path():
     """by symbol name on a stub library: without `splits` the call is qs_shooting_plan with its nine arguments; an int or
     "auto" (= 0) goes to qs_shooting_plan_split with `splits` after the objective"""
     torch = pytest.importorskip("torch")
     from quadsim_amd import mpc
-    lib = _StubLib()
-    noop = lambda: None                                       # noqa: E731
-    env = types.SimpleNamespace(num_envs=3, device=torch.device("cpu"), _lib=lib, _h=None, _use_current_stream=noop,
-                                _inputs_ready=noop, _outputs_ready=noop)
+    lib = StubLib()
+    env = stub_env(torch, lib)
     out = mpc.shooting_plan(env, 5, 64, "position")
     assert out["actions"].shape == (3, 4) and "scores" not in out
     mpc.ShootingMPC(env, 5, 64).act()

@@ -22,10 +22,10 @@ import os
 import re
 import sys
 import tempfile
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import plan_timing  # noqa: E402  (tools/ is the script's directory)
 from tests.kernel_notes import code_object, kernel_notes  # noqa: E402
 
 
@@ -68,10 +68,7 @@ def main():
     results = []
     for paths in [int(p) for p in args.paths.split(",")]:
         m = n * paths
-        env = qa.VecDockingEnv("docking-v0", num_envs=n, randomise=1, seed=5, init_range=qa.C3_INIT_RANGE)
-        env.reset()
-        for a in env.random_actions(2, step0=0):
-            env.step(a)
+        env = plan_timing.stepped_env(qa, n)
         big = qa.VecDockingEnv("docking-v0", num_envs=m, seed=6)    # qs_rollout needs auto_reset; steps after a done are masked
         out = tuple(torch.empty(s, dtype=d, device=env.device) for s, d in
                     (((H, m, 12), torch.float32), ((H, m), torch.float32), ((H, m), torch.uint8)))
@@ -97,11 +94,7 @@ def main():
                 U = torch.einsum("np,hnpi->nhi", w, acts.double()).float()
             return U
 
-        def window(env_, fn):
-            env_.timer_start()
-            for _ in range(args.reps):
-                r = fn()
-            return env_.timer_stop() / args.reps, r
+        window = lambda env_, fn: plan_timing.window(env_, fn, args.reps)    # noqa: E731
 
         for iterations in [int(i) for i in args.iterations.split(",")]:
             steps = m * H * iterations
@@ -123,18 +116,12 @@ def main():
     summary = []
     for key in sorted({(r["paths"], r["iterations"]) for r in results}):
         rows = [r for r in results if (r["paths"], r["iterations"]) == key]
-        rng = lambda k: [min(r[k] for r in rows), max(r[k] for r in rows)]      # noqa: E731
         summary.append(dict(paths=key[0], iterations=key[1], rounds=len(rows),
                             lds_bytes=64 + H * 200 + key[0] * 8,
-                            **{k: rng(k) for k in ("a_mppi_ms", "b_shooting_ms", "c_composed_ms", "a_over_b", "c_over_a", "a_g_steps_per_s")},
+                            **plan_timing.ranges(rows, ("a_mppi_ms", "b_shooting_ms", "c_composed_ms", "a_over_b", "c_over_a", "a_g_steps_per_s")),
                             a_below_c_in_every_round=all(r["a_mppi_ms"] < r["c_composed_ms"] for r in rows)))
         print(json.dumps(dict(summary=summary[-1])), flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(dict(device=torch.cuda.get_device_name(0), date=time.strftime("%Y-%m-%d"), lam=lam, sigma=sigma,
-                           code_object_notes=notes, rounds=results, summary=summary), f, indent=1)
-
+    plan_timing.write_out(args.out, torch, lam=lam, sigma=sigma, code_object_notes=notes, rounds=results, summary=summary)
 
 if __name__ == "__main__":
     main()

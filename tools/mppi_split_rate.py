@@ -30,33 +30,19 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import plan_timing  # noqa: E402  (tools/ is the script's directory)
 
 SWEEP = (2, 8, 32, 128, 512)
 LAM, SIGMA = 0.05, 0.25
 
 
-def host_path(qa, rounds, iters=200):
-    """wall time per plan + step iteration of the single-env shim, per round"""
-    env = qa.DockingEnv()
-    rows = []
-    for rnd in range(rounds + 1):
-        env.reset()
-        nominal, t_plan = None, 0.0
-        t0 = time.perf_counter()
-        for _ in range(iters):
-            t1 = time.perf_counter()
-            plan = env.mppi_plan(20, 200, 2, nominal=nominal, shift=nominal is not None)
-            t_plan += time.perf_counter() - t1
-            _, _, done, _ = env.step(plan["actions"])
-            nominal = None if done else plan["nominal"]
-        dt = time.perf_counter() - t0
-        if rnd:
-            rows.append(dict(round=rnd, iterations=iters, plan_and_step_ms=dt / iters * 1e3, plan_ms=t_plan / iters * 1e3))
-    splits = qa.plan_splits(env, 200)
-    env.close()
-    return dict(paths=200, horizon=20, mppi_iterations=2, auto_splits=splits, control_period_ms=20.0, rounds=rows,
-                plan_and_step_ms=[min(r["plan_and_step_ms"] for r in rows), max(r["plan_and_step_ms"] for r in rows)],
-                plan_ms=[min(r["plan_ms"] for r in rows), max(r["plan_ms"] for r in rows)])
+def plan_and_step(env, carry):
+    nominal = carry.get("nominal")
+    t1 = time.perf_counter()
+    plan = env.mppi_plan(20, 200, 2, nominal=nominal, shift=nominal is not None)
+    carry["plan_s"] += time.perf_counter() - t1
+    _, _, done, _ = env.step(plan["actions"])
+    carry["nominal"] = None if done else plan["nominal"]
 
 
 def main():
@@ -79,10 +65,7 @@ def main():
     H = args.horizon
     results, summary = [], []
     for n in [int(x) for x in args.envs.split(",")]:
-        env = qa.VecDockingEnv("docking-v0", num_envs=n, randomise=1, seed=5, init_range=qa.C3_INIT_RANGE)
-        env.reset()
-        for a in env.random_actions(2, step0=0):
-            env.step(a)
+        env = plan_timing.stepped_env(qa, n)
         act = torch.empty((n, 4), dtype=torch.float32, device=env.device)
         nom = torch.empty((n, H, 4), dtype=torch.float32, device=env.device)
         score = torch.empty((n,), dtype=torch.float64, device=env.device)
@@ -114,44 +97,27 @@ def main():
                     torch.cuda.synchronize()
                     want = nom.clone() if want is None else want
                     assert float((nom - want).abs().max()) <= iters * 1e-3, (n, paths, iters, name)
-                for rnd in range(args.rounds + 1):            # round 0 warms up and is not reported
-                    row = dict(envs=n, paths=paths, iterations=iters, horizon=H, round=rnd, auto_splits=auto, reps=reps,
-                               candidate_steps=steps)
-                    order = configs if rnd % 2 else configs[::-1]
-                    for name, s in order:
-                        torch.cuda.synchronize()
-                        t0 = time.perf_counter()
-                        env.timer_start()
-                        for _ in range(reps):
-                            plan(s)
-                        row[name + "_ms"] = env.timer_stop() / reps
-                        row[name + "_wall_ms"] = (time.perf_counter() - t0) * 1e3 / reps
-                    if rnd:
-                        results.append(row)
-                        print(json.dumps(row), flush=True)
-                rows = [r for r in results if (r["envs"], r["paths"], r["iterations"]) == (n, paths, iters)]
-                rng = lambda k: [min(r[k] for r in rows), max(r[k] for r in rows)]      # noqa: E731
+                rows = plan_timing.alternating_rounds(torch, env, configs, plan, args.rounds, reps,
+                                                      dict(envs=n, paths=paths, iterations=iters, horizon=H, auto_splits=auto, reps=reps,
+                                                           candidate_steps=steps))
+                results += rows
                 cell = dict(envs=n, paths=paths, iterations=iters, horizon=H, auto_splits=auto, rounds=len(rows), reps=reps,
-                            **{k: rng(k) for k in rows[0] if k.endswith("_ms")})
-                cell["floor_over_auto"] = [min(r["floor_ms"] / r["auto_ms"] for r in rows), max(r["floor_ms"] / r["auto_ms"] for r in rows)]
+                            **plan_timing.ranges(rows, [k for k in rows[0] if k.endswith("_ms")]))
+                cell["floor_over_auto"] = plan_timing.ratio_range(rows, "floor_ms", "auto_ms")
                 if paths <= 4096:
                     spread = max(cell["S=1_ms"][1] - cell["S=1_ms"][0], cell["auto_ms"][1] - cell["auto_ms"][0])
                     cell["spread_ms"] = spread
                     cell["auto_faster_than_base_in_every_round"] = all(r["auto_ms"] < r["base_ms"] for r in rows)
                     cell["auto_not_slower_than_one_part_beyond_spread"] = cell["auto_ms"][1] <= cell["S=1_ms"][1] + spread
-                    cell["base_over_auto"] = [min(r["base_ms"] / r["auto_ms"] for r in rows), max(r["base_ms"] / r["auto_ms"] for r in rows)]
+                    cell["base_over_auto"] = plan_timing.ratio_range(rows, "base_ms", "auto_ms")
                 summary.append(cell)
                 print(json.dumps(dict(summary=cell)), flush=True)
         env.close()
-    host = host_path(qa, args.rounds) if args.host else None
+    host = plan_timing.host_path(qa, args.rounds, plan_and_step, paths=200, horizon=20, mppi_iterations=2) if args.host else None
     if host:
         print(json.dumps(dict(host=host)), flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(dict(device=torch.cuda.get_device_name(0), date=time.strftime("%Y-%m-%d"), cus=torch.cuda.get_device_properties(0).multi_processor_count,
-                           reps=args.reps, big=args.big, big_reps=args.big_reps, summary=summary, host=host, rounds=results), f, indent=1)
-
+    plan_timing.write_out(args.out, torch, cus=torch.cuda.get_device_properties(0).multi_processor_count, reps=args.reps, big=args.big,
+                          big_reps=args.big_reps, summary=summary, host=host, rounds=results)
 
 if __name__ == "__main__":
     main()

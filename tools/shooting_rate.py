@@ -21,6 +21,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import plan_timing  # noqa: E402  (tools/ is the script's directory)
 
 
 def main():
@@ -39,10 +40,7 @@ def main():
     results = []
     for paths in [int(p) for p in args.paths.split(",")]:
         m = n * paths
-        env = qa.VecDockingEnv("docking-v0", num_envs=n, randomise=1, seed=5, init_range=qa.C3_INIT_RANGE)
-        env.reset()
-        for a in env.random_actions(2, step0=0):
-            env.step(a)
+        env = plan_timing.stepped_env(qa, n)
         big = qa.VecDockingEnv("docking-v0", num_envs=m, seed=6)    # qs_rollout needs auto_reset; steps after a done are masked
         acts = big.random_actions(H, step0=0)
         out = tuple(torch.empty(s, dtype=d, device=env.device) for s, d in
@@ -60,11 +58,7 @@ def main():
             best = score.argmax(1)
             return acts[0].view(n, paths, 4)[torch.arange(n, device=best.device), best], score
 
-        def window(env_, fn):
-            env_.timer_start()
-            for _ in range(args.reps):
-                r = fn()
-            return env_.timer_stop() / args.reps, r
+        window = lambda env_, fn: plan_timing.window(env_, fn, args.reps)    # noqa: E731
 
         steps = m * H
         for rnd in range(args.rounds + 1):                   # round 0 warms every shape up and is not reported
@@ -93,15 +87,10 @@ def main():
     summary = []
     for paths in sorted({r["paths"] for r in results}):
         rows = [r for r in results if r["paths"] == paths]
-        rng = lambda k: [min(r[k] for r in rows), max(r[k] for r in rows)]      # noqa: E731
-        summary.append(dict(paths=paths, rounds=len(rows), **{k: rng(k) for k in rows[0] if k.endswith(("_ms", "_per_s", "_reward", "_c"))},
+        summary.append(dict(paths=paths, rounds=len(rows), **plan_timing.ranges(rows, [k for k in rows[0] if k.endswith(("_ms", "_per_s", "_reward", "_c"))]),
                             a_no_slower_than_b_kernels_in_every_round=all(max(r["a_reward_ms"], r["a_position_ms"]) <= r["b_kernels_ms"] for r in rows)))
         print(json.dumps(dict(summary=summary[-1])), flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(dict(device=torch.cuda.get_device_name(0), date=time.strftime("%Y-%m-%d"), rounds=results, summary=summary), f, indent=1)
-
+    plan_timing.write_out(args.out, torch, rounds=results, summary=summary)
 
 if __name__ == "__main__":
     main()
