@@ -45,48 +45,119 @@ __device__ __forceinline__ f32x4 relu4(f32x4 v)
     return f32x4{fmaxf(v.x, 0.0f), fmaxf(v.y, 0.0f), fmaxf(v.z, 0.0f), fmaxf(v.w, 0.0f)};
 }
 
+// ---- the pieces every actor and actor-critic kernel is built from, each written once ------------------------
+// obs^T [12][64] of the wave's 64 envs into its stage, so that each lane can fetch the (k, env column) element its B operand needs
+__device__ __forceinline__ void stage_obs(const float obs[12], float *stage, int lane)
+{
+#pragma unroll
+    for (int k = 0; k < 12; ++k) stage[k * 64 + lane] = obs[k];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Layer 1 on the f32 MFMA: H1^T [128][64] = W1^T [128][12] . obs^T [12][64] + b1, 3 k-steps x 4 env tiles per 16-row tile;
+// epi(rt, acc) takes the four finished accumulators of row tile rt.  The caller supplies the lane's three base addresses,
+// w1 = &W1^T[c][g] (+ 16 rt kLdW1 + 4 s), b1 = &b1[4 g] (+ 16 rt), xs = &stage[g][c] (+ 256 s + 16 et): plain (layer1_relu)
+// or through lds_opaque (ac_fast_layer1) -- the addressing is the flavour, the arithmetic is this one body.
+template <class Epi>
+__device__ __forceinline__ void layer1_f32(const float *w1, const float *b1, const float *xs, Epi &&epi)
+{
+    float xb[3][4];
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+        for (int et = 0; et < 4; ++et) xb[s][et] = xs[256 * s + 16 * et];
+#pragma unroll
+    for (int rt = 0; rt < 8; ++rt) {
+        const f32x4 bias = *reinterpret_cast<const f32x4 *>(b1 + 16 * rt);
+        float a[3];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) a[s] = w1[16 * rt * kLdW1 + 4 * s];
+        f32x4 acc[4] = {bias, bias, bias, bias};              // k-step outermost: consecutive MFMAs on different accumulators
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+#pragma unroll
+            for (int et = 0; et < 4; ++et) acc[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], xb[s][et], acc[et], 0, 0, 0);
+        epi(rt, acc);
+    }
+}
+
+// exact-f32 flavour: ReLU into h1, the B operands of the f32 128 x 128 layer
+__device__ __forceinline__ void layer1_relu(const float *W1, const float *B1, const float *stage, int lane, f32x4 (&h1)[8][4])
+{
+    const int c = lane & 15, g = lane >> 4;
+    layer1_f32(W1 + c * kLdW1 + g, B1 + 4 * g, stage + g * 64 + c, [&](int rt, const f32x4 (&acc)[4]) {
+#pragma unroll
+        for (int et = 0; et < 4; ++et) h1[rt][et] = relu4(acc[et]);
+    });
+}
+
+// output-layer accumulators of the four env tiles = the lane's four rows of the padded output bias b3 [16]
+__device__ __forceinline__ void init_a3(const float *B3, int lane, f32x4 (&a3)[4])
+{
+    const f32x4 bias3 = *reinterpret_cast<const f32x4 *>(B3 + 4 * (lane >> 4));
+#pragma unroll
+    for (int et = 0; et < 4; ++et) a3[et] = bias3;
+}
+
+// Hand-over of the actors: rows 0..3 of the action tile live in lanes 0..15 (g == 0); through sAct [64][4] to the lane that
+// owns the env, clipped to [-1, 1]
+__device__ __forceinline__ void actions_to_owner(const f32x4 (&a3)[4], float *sAct, int lane, float act[4])
+{
+    const int c = lane & 15, g = lane >> 4;
+    if (g == 0) {
+#pragma unroll
+        for (int et = 0; et < 4; ++et) *reinterpret_cast<f32x4 *>(sAct + (16 * et + c) * 4) = a3[et];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const f32x4 av = *reinterpret_cast<const f32x4 *>(sAct + lane * 4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) act[i] = fminf(fmaxf(av[i], -1.0f), 1.0f);
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Hand-over of the heads through the wave's stage, [64][8] floats.  The means are rows 0..3 of a3p, which sit in lanes g == 0
+// (the caller's guard; c = lane & 15): into slots 0..3 of their env.  k_runner_split's matrix waves stop here: the env wave of
+// the tile reads them after a workgroup barrier.
+__device__ __forceinline__ void means_to_stage(const f32x4 (&a3p)[4], float *stage, int c)
+{
+#pragma unroll
+    for (int et = 0; et < 4; ++et) *reinterpret_cast<f32x4 *>(stage + (16 * et + c) * 8) = a3p[et];
+}
+
+// ... and the value (row 4 of a3v = register 0 of lanes g == 1) into slot 4, then all five to the lane that owns the env.
+// The stage is free by then: every lane of the wave read its layer-1 operands before the branches.
+__device__ __forceinline__ void heads_to_owner(const f32x4 (&a3p)[4], const f32x4 (&a3v)[4], float *stage, int lane, float out[5])
+{
+    const int c = lane & 15, g = lane >> 4;
+    if (g == 0) {
+        means_to_stage(a3p, stage, c);
+    } else if (g == 1) {
+#pragma unroll
+        for (int et = 0; et < 4; ++et) stage[(16 * et + c) * 8 + 4] = a3v[et][0];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const f32x4 av = *reinterpret_cast<const f32x4 *>(stage + lane * 8);
+    out[0] = av[0]; out[1] = av[1]; out[2] = av[2]; out[3] = av[3];
+    out[4] = stage[lane * 8 + 4];
+    __builtin_amdgcn_wave_barrier();
+}
+
 // MLP for the 64 envs of one wave: obs (per owning lane) -> 4 actions (per owning lane), clipped to [-1,1]
 __device__ __forceinline__ void mlp_actor(const float obs[12], float act[4], const float *sW1, const float *sB1,
                                           const float *sW2, const float *sB2, const float *sW3, const float *sB3,
                                           float *sObs, float *sAct, int lane)
 {
     const int c = lane & 15, g = lane >> 4;
-    // stage obs^T [12][64] so that each lane can fetch the (k, env column) element its B operand needs
-#pragma unroll
-    for (int k = 0; k < 12; ++k) sObs[k * 64 + lane] = obs[k];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    // ---- layer 1: H1^T [128][64] = W1^T [128][12] . obs^T [12][64]  (+ b1)
+    stage_obs(obs, sObs, lane);
     f32x4 h1[8][4];
-    float xb[3][4];
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-        for (int et = 0; et < 4; ++et) xb[s][et] = sObs[(4 * s + g) * 64 + 16 * et + c];
-#pragma unroll
-    for (int rt = 0; rt < 8; ++rt) {
-        const f32x4 bias = *reinterpret_cast<const f32x4 *>(sB1 + 16 * rt + 4 * g);
-        float a[3];
-#pragma unroll
-        for (int s = 0; s < 3; ++s) a[s] = sW1[(16 * rt + c) * kLdW1 + 4 * s + g];
-        f32x4 acc[4] = {bias, bias, bias, bias};              // k-step outermost: consecutive MFMAs on different accumulators
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-#pragma unroll
-            for (int et = 0; et < 4; ++et) acc[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], xb[s][et], acc[et], 0, 0, 0);
-#pragma unroll
-        for (int et = 0; et < 4; ++et) {
-            h1[rt][et] = relu4(acc[et]);
-        }
-    }
+    layer1_relu(sW1, sB1, sObs, lane, h1);
     // ---- layers 2 + 3: for each 16-row tile of H2^T: 32 k-steps over H1^T, bias, ReLU, then straight into the
     //      action accumulators (rows 0..3 of a 16-row tile; W3^T rows 4..15 are zero)
     f32x4 a3[4];
-    {
-        const f32x4 bias3 = *reinterpret_cast<const f32x4 *>(sB3 + 4 * g);
-#pragma unroll
-        for (int et = 0; et < 4; ++et) a3[et] = bias3;
-    }
+    init_a3(sB3, lane, a3);
 #pragma unroll
     for (int nt = 0; nt < 8; ++nt) {
         const f32x4 bias = *reinterpret_cast<const f32x4 *>(sB2 + 16 * nt + 4 * g);
@@ -110,7 +181,7 @@ __device__ __forceinline__ void mlp_actor(const float obs[12], float act[4], con
             for (int et = 0; et < 4; ++et) a3[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(w3[i], r[et][i], a3[et], 0, 0, 0);
         // issue order of this tile: every weight read one 16-MFMA group ahead of its use (left alone, hipcc emits
         // read -> wait -> 16 MFMAs and exposes the LDS latency 8 times per tile): 24.9 -> 24.3 us/step.  The same
-        // directives change nothing in mlp_actor_critic (43.7 vs 43.8 us/step) and are not applied there.
+        // directives change nothing in the actor-critic heads (43.7 vs 43.8 us/step) and are not applied there.
         __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
 #pragma unroll
         for (int r = 0; r < 7; ++r) {
@@ -120,17 +191,7 @@ __device__ __forceinline__ void mlp_actor(const float obs[12], float act[4], con
         __builtin_amdgcn_sched_group_barrier(0x8, 16, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
-    // rows 0..3 of the action tile live in lanes 0..15 (g == 0): hand them to the lane that owns the env
-    if (g == 0) {
-#pragma unroll
-        for (int et = 0; et < 4; ++et) *reinterpret_cast<f32x4 *>(sAct + (16 * et + c) * 4) = a3[et];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const f32x4 av = *reinterpret_cast<const f32x4 *>(sAct + lane * 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) act[i] = fminf(fmaxf(av[i], -1.0f), 1.0f);
-    __builtin_amdgcn_wave_barrier();
+    actions_to_owner(a3, sAct, lane, act);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -155,100 +216,6 @@ struct AcLds {
 constexpr size_t ac_lds_floats()
 {
     return (size_t)2 * kHid * kLdW + 4 * kLdW + kLdW + kHid * kLdW1 + 3 * kHid + 16 + 4 * (12 * 64);
-}
-
-// obs (per owning lane) -> out[0..3] = action mean, out[4] = value (per owning lane).  `stage` = 768 floats per wave.
-__device__ __forceinline__ void mlp_actor_critic(const float obs[12], float out[5], const AcLds &L, float *stage, int lane)
-{
-    const int c = lane & 15, g = lane >> 4;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) stage[k * 64 + lane] = obs[k];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    f32x4 h1[8][4];
-    float xb[3][4];
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-        for (int et = 0; et < 4; ++et) xb[s][et] = stage[(4 * s + g) * 64 + 16 * et + c];
-#pragma unroll
-    for (int rt = 0; rt < 8; ++rt) {
-        const f32x4 bias = *reinterpret_cast<const f32x4 *>(L.B1 + 16 * rt + 4 * g);
-        float a[3];
-#pragma unroll
-        for (int s = 0; s < 3; ++s) a[s] = L.W1[(16 * rt + c) * kLdW1 + 4 * s + g];
-        f32x4 acc[4] = {bias, bias, bias, bias};              // k-step outermost: consecutive MFMAs on different accumulators
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-#pragma unroll
-            for (int et = 0; et < 4; ++et) acc[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], xb[s][et], acc[et], 0, 0, 0);
-#pragma unroll
-        for (int et = 0; et < 4; ++et) {
-            h1[rt][et] = relu4(acc[et]);
-        }
-    }
-    f32x4 a3[4];
-    {
-        const f32x4 bias3 = *reinterpret_cast<const f32x4 *>(L.B3 + 4 * g);
-#pragma unroll
-        for (int et = 0; et < 4; ++et) a3[et] = bias3;
-    }
-    // Source order = issue order (scheduling barriers): the weights of k-group G + 1 (16 MFMAs = 512 matrix cycles later) are
-    // requested before the MFMAs of group G, across tile and branch boundaries too; left alone, hipcc emits read -> wait ->
-    // MFMAs and exposes the LDS latency 4-5 times per tile.  The dead rows of the output-layer tile read 16 zero bytes
-    // (slots 8..11 of the padded b3): an address select, no branch in the MFMA stream.
-    auto w2_group = [&](int G) {                           // G = 64 br + 8 nt + rt
-        return *reinterpret_cast<const f32x4 *>(((G >> 6) ? L.W2v : L.W2p) + (16 * ((G >> 3) & 7) + c) * kLdW + 16 * (G & 7) + 4 * g);
-    };
-    f32x4 wbuf[2];
-    wbuf[0] = w2_group(0);
-#pragma unroll
-    for (int br = 0; br < 2; ++br) {                       // 0: policy branch -> rows 0..3, 1: value branch -> row 4
-        const float *B2 = br ? L.B2v : L.B2p;
-        const bool row_live = br == 0 ? c < 4 : c == 4;
-        const float *w3row = br == 0 ? L.W3p + (c & 3) * kLdW + 4 * g : L.W3v + 4 * g;
-#pragma unroll
-        for (int nt = 0; nt < 8; ++nt) {
-            const f32x4 bias = *reinterpret_cast<const f32x4 *>(B2 + 16 * nt + 4 * g);
-            const f32x4 w3 = *reinterpret_cast<const f32x4 *>(row_live ? w3row + 16 * nt : L.B3 + 8);
-            f32x4 h2[4] = {bias, bias, bias, bias};
-#pragma unroll
-            for (int rt = 0; rt < 8; ++rt) {
-                const int G = 64 * br + 8 * nt + rt;
-                if (G + 1 < 128) wbuf[(G + 1) & 1] = w2_group(G + 1);
-                const f32x4 w = wbuf[G & 1];
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int et = 0; et < 4; ++et)
-                        h2[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i], h1[rt][et][i], h2[et], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            f32x4 r[4];
-#pragma unroll
-            for (int et = 0; et < 4; ++et) r[et] = relu4(h2[et]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)                     // k-step outermost: consecutive MFMAs on different accumulators
-#pragma unroll
-                for (int et = 0; et < 4; ++et) a3[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(w3[i], r[et][i], a3[et], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    // rows 0..3 sit in lanes g == 0, row 4 in register 0 of lanes g == 1: hand them to the lane that owns the env
-    // (the stage is free again: every lane of this wave read its layer-1 operands long ago)
-    if (g == 0) {
-#pragma unroll
-        for (int et = 0; et < 4; ++et) *reinterpret_cast<f32x4 *>(stage + (16 * et + c) * 8) = a3[et];
-    } else if (g == 1) {
-#pragma unroll
-        for (int et = 0; et < 4; ++et) stage[(16 * et + c) * 8 + 4] = a3[et][0];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const f32x4 av = *reinterpret_cast<const f32x4 *>(stage + lane * 8);
-    out[0] = av[0]; out[1] = av[1]; out[2] = av[2]; out[3] = av[3];
-    out[4] = stage[lane * 8 + 4];
-    __builtin_amdgcn_wave_barrier();
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -289,6 +256,35 @@ __device__ __forceinline__ void relu_split_pair(float v0, float v1, uint32_t &hi
     lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, bf16x2));
 }
 __device__ __forceinline__ bf16x8 as_bf16x8(u32x4 w) { return __builtin_bit_cast(bf16x8, w); }
+__device__ __forceinline__ bf16x8 as_bf16x8(bf16x8 w) { return w; }
+
+// Layer-1 epilogue of every split-bf16 network: ReLU + split of row tile rt, straight into the B operands of layer 2
+// (tiles 2p, 2p+1 -> k-step p).  bh / bl [p][et]: element j of the B operand = half (j & 1) of word j >> 1
+__device__ __forceinline__ void relu_split_tile(int rt, const f32x4 (&acc)[4], u32x4 (&bh)[4][4], u32x4 (&bl)[4][4])
+{
+#pragma unroll
+    for (int et = 0; et < 4; ++et) {
+#pragma unroll
+        for (int pr = 0; pr < 2; ++pr) {
+            uint32_t h, l;
+            relu_split_pair(acc[et][2 * pr], acc[et][2 * pr + 1], h, l);
+            bh[rt >> 1][et][2 * (rt & 1) + pr] = h;
+            bl[rt >> 1][et][2 * (rt & 1) + pr] = l;
+        }
+    }
+}
+
+// One k-step of a split product over N env tiles: acc[et] += lo*hi + hi*lo + hi*hi of the A fragment (ah, al) and the B
+// operands (bh[et], bl[et]); term outermost, so that consecutive MFMAs use different accumulators
+template <int N, class B>
+__device__ __forceinline__ void mfma_split3(bf16x8 ah, bf16x8 al, const B (&bh)[N], const B (&bl)[N], f32x4 *acc)
+{
+#pragma unroll
+    for (int term = 0; term < 3; ++term)
+#pragma unroll
+        for (int et = 0; et < N; ++et)
+            acc[et] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(term == 0 ? al : ah, as_bf16x8(term == 1 ? bl[et] : bh[et]), acc[et], 0, 0, 0);
+}
 
 #ifndef QS_WEAVE
 #define QS_WEAVE 1      // 0: layer-2 tiles one after the other (A/B reference), 1: hand-woven software pipeline
@@ -406,10 +402,7 @@ __device__ __forceinline__ void mlp_actor_fast(const float obs[12], float act[4]
     const float *sB2 = sB1 + 128;
     const float *sB3 = sB2 + 128;
     const int c = lane & 15, g = lane >> 4;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) sObs[k * 64 + lane] = obs[k];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    stage_obs(obs, sObs, lane);
     // ---- layer 1 B operands: k-slot 8g+j = input 8g+j (12 inputs, the rest zero)
     bf16x8 xh[4], xl[4];
 #pragma unroll
@@ -428,58 +421,28 @@ __device__ __forceinline__ void mlp_actor_fast(const float obs[12], float act[4]
     for (int rt = 0; rt < 8; ++rt) {
         const f32x4 bias = *reinterpret_cast<const f32x4 *>(sB1 + 16 * rt + 4 * g);
         const bf16x8 ah = A1hi[rt * 64 + lane], al = A1lo[rt * 64 + lane];
-        f32x4 acc[4] = {bias, bias, bias, bias};              // term outermost: consecutive MFMAs on different accumulators
-#pragma unroll
-        for (int term = 0; term < 3; ++term)
-#pragma unroll
-            for (int et = 0; et < 4; ++et)
-                acc[et] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(term == 0 ? al : ah, term == 1 ? xl[et] : xh[et], acc[et], 0, 0, 0);
-#pragma unroll
-        for (int et = 0; et < 4; ++et) {
-#pragma unroll
-            for (int pr = 0; pr < 2; ++pr) {
-                uint32_t h, l;
-                relu_split_pair(acc[et][2 * pr], acc[et][2 * pr + 1], h, l);
-                bh[rt >> 1][et][2 * (rt & 1) + pr] = h;
-                bl[rt >> 1][et][2 * (rt & 1) + pr] = l;
-            }
-        }
+        f32x4 acc[4] = {bias, bias, bias, bias};
+        mfma_split3(ah, al, xh, xl, acc);
+        relu_split_tile(rt, acc, bh, bl);
     }
     // ---- layer 2 in row-tile pairs, each pair folded into the action accumulators (layer 3 k-step = the pair)
     f32x4 a3[4];
-    {
-        const f32x4 bias3 = *reinterpret_cast<const f32x4 *>(sB3 + 4 * g);
-#pragma unroll
-        for (int et = 0; et < 4; ++et) a3[et] = bias3;
-    }
+    init_a3(sB3, lane, a3);
     mlp_layer2_split<8, 4, 0>(bh, bl, lane, g,
         [&](int nt) { return L2Tile{A2hi + nt * 4 * 64, A2lo + nt * 4 * 64, sB2 + 16 * nt + 4 * g}; },
         [&](int q, const u32x4 (&ch)[4], const u32x4 (&cl)[4]) {
-            const bf16x8 wh = A3hi[q * 64 + lane], wl = A3lo[q * 64 + lane];
-#pragma unroll
-            for (int term = 0; term < 3; ++term)            // term outermost: consecutive MFMAs on different accumulators
-#pragma unroll
-                for (int et = 0; et < 4; ++et)
-                    a3[et] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(term == 0 ? wl : wh, as_bf16x8(term == 1 ? cl[et] : ch[et]), a3[et], 0, 0, 0);
+            mfma_split3(A3hi[q * 64 + lane], A3lo[q * 64 + lane], ch, cl, a3);
         });
-    if (g == 0) {
-#pragma unroll
-        for (int et = 0; et < 4; ++et) *reinterpret_cast<f32x4 *>(sAct + (16 * et + c) * 4) = a3[et];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const f32x4 av = *reinterpret_cast<const f32x4 *>(sAct + lane * 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) act[i] = fminf(fmaxf(av[i], -1.0f), 1.0f);
-    __builtin_amdgcn_wave_barrier();
+    actions_to_owner(a3, sAct, lane, act);
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Fast actor-critic heads (qs_runner_rollout_fast): mlp_actor_critic with the two 128x128 layers and the output layer
+// Fast actor-critic heads (qs_runner_rollout_fast): the heads above with the two 128x128 layers and the output layer
 // on the bf16 matrix rate with split (hi + lo) operands, exactly as mlp_actor_fast; the 12-input first layer stays on
 // the f32 MFMA (96 MFMAs, and its f32 weights are a third of the size of split fragments padded to k = 32).
 // LDS image (bytes): A2pi hi 32768 | lo 32768 | A2vf hi 32768 | lo 32768 | A3pi hi 1024 | lo 1024 | A3vf hi 256 | lo 256 |
-// W1^T f32 128x13 6656 | b1 512 | b2pi 512 | b2vf 512 | b3 64 | per-wave stage 4 x 3072  = 154 176 B.
+// W1^T f32 128x13 6656 | b1 512 | b2pi 512 | b2vf 512 | b3 64 | per-wave stage 4 x 3072  = 154 176 B, + 2 KiB of zeros for the
+// dead output rows (ac_fast_branch) = 156 224 B in k_runner_rollout; k_runner_split puts its 1 KiB value buffer in between.
 // A3pi keeps only output rows 0..3, A3vf only row 4 of the 16-row tile: [k-step q][row][g][8 bf16] / [q][g][8 bf16].
 constexpr int kAcFastA2 = 0;
 constexpr int kAcFastA3p = 4 * 32768;
@@ -489,96 +452,12 @@ constexpr int kAcFastB = kAcFastW1 + kHid * kLdW1 * 4;
 constexpr int kAcFastBlobBytes = kAcFastB + (3 * kHid + 16) * 4;
 constexpr int kAcFastLdsBytes = kAcFastBlobBytes + 4 * (12 * 64) * 4;
 
-__device__ __forceinline__ void mlp_actor_critic_fast(const float obs[12], float out[5], const char *blob, float *stage,
-                                                      int lane)
-{
-    const float *sW1 = reinterpret_cast<const float *>(blob + kAcFastW1);
-    const float *sB1 = reinterpret_cast<const float *>(blob + kAcFastB);
-    const float *sB2p = sB1 + kHid, *sB2v = sB2p + kHid, *sB3 = sB2v + kHid;
-    const int c = lane & 15, g = lane >> 4;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) stage[k * 64 + lane] = obs[k];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    // ---- layer 1 on the f32 MFMA, ReLU, straight into split B operands of layer 2 (tiles 2p, 2p+1 -> k-step p)
-    float xb[3][4];
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-        for (int et = 0; et < 4; ++et) xb[s][et] = stage[(4 * s + g) * 64 + 16 * et + c];
-    u32x4 bh[4][4], bl[4][4];       // [p][et]: element j of the B operand = word j >> 1
-#pragma unroll
-    for (int rt = 0; rt < 8; ++rt) {
-        const f32x4 bias = *reinterpret_cast<const f32x4 *>(sB1 + 16 * rt + 4 * g);
-        float a[3];
-#pragma unroll
-        for (int s = 0; s < 3; ++s) a[s] = sW1[(16 * rt + c) * kLdW1 + 4 * s + g];
-        f32x4 acc[4] = {bias, bias, bias, bias};              // k-step outermost: consecutive MFMAs on different accumulators
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-#pragma unroll
-            for (int et = 0; et < 4; ++et) acc[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], xb[s][et], acc[et], 0, 0, 0);
-#pragma unroll
-        for (int et = 0; et < 4; ++et) {
-#pragma unroll
-            for (int pr = 0; pr < 2; ++pr) {
-                uint32_t h, l;
-                relu_split_pair(acc[et][2 * pr], acc[et][2 * pr + 1], h, l);
-                bh[rt >> 1][et][2 * (rt & 1) + pr] = h;
-                bl[rt >> 1][et][2 * (rt & 1) + pr] = l;
-            }
-        }
-    }
-    f32x4 a3[4];
-    {
-        const f32x4 bias3 = *reinterpret_cast<const f32x4 *>(sB3 + 4 * g);
-#pragma unroll
-        for (int et = 0; et < 4; ++et) a3[et] = bias3;
-    }
-    // the 16 layer-2 row tiles: s2 = 8 br + nt; br 0: policy branch -> output rows 0..3, br 1: value branch -> row 4
-    mlp_layer2_split<16, 4, 0>(bh, bl, lane, g,
-        [&](int s2) {
-            const int br = s2 >> 3, nt = s2 & 7;
-            return L2Tile{reinterpret_cast<const bf16x8 *>(blob + kAcFastA2 + br * 65536) + nt * 4 * 64,
-                          reinterpret_cast<const bf16x8 *>(blob + kAcFastA2 + br * 65536 + 32768) + nt * 4 * 64,
-                          (br ? sB2v : sB2p) + 16 * nt + 4 * g};
-        },
-        [&](int pair, const u32x4 (&ch)[4], const u32x4 (&cl)[4]) {
-            // output-layer A fragments: rows 0..3 (policy) / row 4 (value) hold weights, every other row of the 16-row tile
-            // reads 16 zero bytes (slots 8..11 of the padded b3) -- an address select, no branch in the MFMA stream
-            const int br = pair >> 2, q = pair & 3;
-            const bf16x8 *ph = br == 0 ? reinterpret_cast<const bf16x8 *>(blob + kAcFastA3p) + (q * 4 + (c & 3)) * 4 + g
-                                       : reinterpret_cast<const bf16x8 *>(blob + kAcFastA3v) + q * 4 + g;
-            const bf16x8 *pl = br == 0 ? ph + 1024 / 16 : ph + 256 / 16;
-            const bool row_live = br == 0 ? c < 4 : c == 4;
-            const bf16x8 *pz = reinterpret_cast<const bf16x8 *>(sB3 + 8);
-            const bf16x8 wh = *(row_live ? ph : pz), wl = *(row_live ? pl : pz);
-#pragma unroll
-            for (int term = 0; term < 3; ++term)            // term outermost: consecutive MFMAs on different accumulators
-#pragma unroll
-                for (int et = 0; et < 4; ++et)
-                    a3[et] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(term == 0 ? wl : wh, as_bf16x8(term == 1 ? cl[et] : ch[et]), a3[et], 0, 0, 0);
-        });
-    if (g == 0) {
-#pragma unroll
-        for (int et = 0; et < 4; ++et) *reinterpret_cast<f32x4 *>(stage + (16 * et + c) * 8) = a3[et];
-    } else if (g == 1) {
-#pragma unroll
-        for (int et = 0; et < 4; ++et) stage[(16 * et + c) * 8 + 4] = a3[et][0];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const f32x4 av = *reinterpret_cast<const f32x4 *>(stage + lane * 8);
-    out[0] = av[0]; out[1] = av[1]; out[2] = av[2]; out[3] = av[3];
-    out[4] = stage[lane * 8 + 4];
-    __builtin_amdgcn_wave_barrier();
-}
-
 // ------------------------------------------------------------------------------------------------------------
-// Role-split runner (k_runner_split): the heads cut into the pieces a MATRIX wave runs while an ENV wave of the same tile
-// steps the environments.  ac_fast_layer1: shared layer for the wave's 64 envs (observations read from the tile's LDS
-// stage, [k][env]), result = the B operands of BOTH 128 x 128 branches, kept in registers.  ac_fast_branch<BR>: one branch
-// (0 policy -> rows 0..3 of a3, 1 value -> row 4) over QS_SPLIT_NET env tiles per pass (256 registers per wave at two waves
+// The heads in pieces: what mlp_heads runs back to back for one wave per tile (k_runner_rollout), and what a MATRIX wave of
+// the role-split runner (k_runner_split) runs while an ENV wave of the same tile steps the environments.  ac_fast_layer1:
+// shared layer for the wave's 64 envs (observations read from the tile's LDS stage, [k][env]), result = the B operands of
+// BOTH 128 x 128 branches, kept in registers.  ac_fast_branch<BR>: one branch (0 policy -> rows 0..3 of a3, 1 value -> row 4)
+// over QS_SPLIT_NET env tiles per pass (256 registers per wave at two waves
 // per SIMD: the four-tile pass fits next to the 128 operand registers once the LDS addresses share base registers, lds_opaque).
 // An LDS byte offset the optimiser cannot see through: everything addressed as `blob + opaque + constant` then shares ONE
 // address register with the constants in the instructions' offset fields, instead of one materialised address per constant
@@ -599,33 +478,7 @@ __device__ __forceinline__ void ac_fast_layer1(const char *blob, const float *st
     const float *w1 = reinterpret_cast<const float *>(blob + lds_opaque(W1OFF + (c * kLdW1 + g) * 4));        // + 16 rt kLdW1 + 4 s
     const float *b1 = reinterpret_cast<const float *>(blob + lds_opaque(B1OFF + 16 * g));                     // + 16 rt
     const float *xs = stage + lds_opaque(g * 64 + c);                                                         // + 256 s + 16 et
-    float xb[3][4];
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-        for (int et = 0; et < 4; ++et) xb[s][et] = xs[256 * s + 16 * et];
-#pragma unroll
-    for (int rt = 0; rt < 8; ++rt) {
-        const f32x4 bias = *reinterpret_cast<const f32x4 *>(b1 + 16 * rt);
-        float a[3];
-#pragma unroll
-        for (int s = 0; s < 3; ++s) a[s] = w1[16 * rt * kLdW1 + 4 * s];
-        f32x4 acc[4] = {bias, bias, bias, bias};              // k-step outermost: consecutive MFMAs on different accumulators
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-#pragma unroll
-            for (int et = 0; et < 4; ++et) acc[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], xb[s][et], acc[et], 0, 0, 0);
-#pragma unroll
-        for (int et = 0; et < 4; ++et) {
-#pragma unroll
-            for (int pr = 0; pr < 2; ++pr) {
-                uint32_t h, l;
-                relu_split_pair(acc[et][2 * pr], acc[et][2 * pr + 1], h, l);
-                bh[rt >> 1][et][2 * (rt & 1) + pr] = h;
-                bl[rt >> 1][et][2 * (rt & 1) + pr] = l;
-            }
-        }
-    }
+    layer1_f32(w1, b1, xs, [&](int rt, const f32x4 (&acc)[4]) { relu_split_tile(rt, acc, bh, bl); });
 }
 
 #ifndef QS_SPLIT_NET
@@ -655,11 +508,7 @@ __device__ __forceinline__ void ac_fast_branch_pass(const char *blob, int zeros,
         [&](int q, const u32x4 (&ch)[QS_SPLIT_NET], const u32x4 (&cl)[QS_SPLIT_NET]) {
             const bf16x8 wh = *reinterpret_cast<const bf16x8 *>(a3_base + q * (BR == 0 ? 256 : 64));
             const bf16x8 wl = *reinterpret_cast<const bf16x8 *>(a3_base + q * (BR == 0 ? 256 : 64) + (BR == 0 ? 1024 : 256));
-#pragma unroll
-            for (int term = 0; term < 3; ++term)            // term outermost: consecutive MFMAs on different accumulators
-#pragma unroll
-                for (int et = 0; et < QS_SPLIT_NET; ++et)
-                    a3[E0 + et] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(term == 0 ? wl : wh, as_bf16x8(term == 1 ? cl[et] : ch[et]), a3[E0 + et], 0, 0, 0);
+            mfma_split3(wh, wl, ch, cl, a3 + E0);
         });
 }
 
@@ -667,51 +516,20 @@ template <int BR>
 __device__ __forceinline__ void ac_fast_branch(const char *blob, int zeros, const u32x4 (&bh)[4][4], const u32x4 (&bl)[4][4], int lane,
                                                f32x4 (&a3)[4])
 {
-    const float *sB3 = reinterpret_cast<const float *>(blob + kAcFastB) + 3 * kHid;
-    const f32x4 bias3 = *reinterpret_cast<const f32x4 *>(sB3 + 4 * (lane >> 4));
-#pragma unroll
-    for (int et = 0; et < 4; ++et) a3[et] = bias3;
+    init_a3(reinterpret_cast<const float *>(blob + kAcFastB) + 3 * kHid, lane, a3);
     ac_fast_branch_pass<BR, 0>(blob, zeros, bh, bl, lane, a3);
     if (QS_SPLIT_NET == 2) ac_fast_branch_pass<BR, QS_SPLIT_NET == 2 ? 2 : 0>(blob, zeros, bh, bl, lane, a3);
 }
 
-// The exact-float32 heads in the same two pieces: identical MFMA sequences per accumulator as mlp_actor_critic -- the one
-// difference is that each branch starts its own accumulators from the output bias instead of sharing one set, which adds the
-// other branch's exact zeros in a different place (the same sums bit for bit).
-__device__ __forceinline__ void ac_exact_layer1(const AcLds &L, const float *stage, int lane, f32x4 (&h1)[8][4])
-{
-    const int c = lane & 15, g = lane >> 4;
-    float xb[3][4];
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-        for (int et = 0; et < 4; ++et) xb[s][et] = stage[(4 * s + g) * 64 + 16 * et + c];
-#pragma unroll
-    for (int rt = 0; rt < 8; ++rt) {
-        const f32x4 bias = *reinterpret_cast<const f32x4 *>(L.B1 + 16 * rt + 4 * g);
-        float a[3];
-#pragma unroll
-        for (int s = 0; s < 3; ++s) a[s] = L.W1[(16 * rt + c) * kLdW1 + 4 * s + g];
-        f32x4 acc[4] = {bias, bias, bias, bias};              // k-step outermost: consecutive MFMAs on different accumulators
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-#pragma unroll
-            for (int et = 0; et < 4; ++et) acc[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], xb[s][et], acc[et], 0, 0, 0);
-#pragma unroll
-        for (int et = 0; et < 4; ++et) {
-            h1[rt][et] = relu4(acc[et]);
-        }
-    }
-}
-
+// The exact-float32 heads in the same pieces (layer 1: layer1_relu).  Each branch starts its OWN accumulators from the output
+// bias; one set shared by both branches would add the other branch's exact zeros in a different place -- the same sums bit
+// for bit.  mlp_heads relies on this: the one-wave kernel and the role-split kernel run these very functions.
 // LDW2: row stride (floats) of W2p^T / W2v^T (the tower image interleaves the two: kLdW2T)
 template <int BR, int LDW2 = kLdW>
 __device__ __forceinline__ void ac_exact_branch(const AcLds &L, const f32x4 (&h1)[8][4], int lane, f32x4 (&a3)[4])
 {
     const int c = lane & 15, g = lane >> 4;
-    const f32x4 bias3 = *reinterpret_cast<const f32x4 *>(L.B3 + 4 * g);
-#pragma unroll
-    for (int et = 0; et < 4; ++et) a3[et] = bias3;
+    init_a3(L.B3, lane, a3);
     const float *W2 = (BR ? L.W2v : L.W2p) + c * LDW2 + 4 * g;          // + 16 nt LDW2 + 16 rt
     const float *B2 = (BR ? L.B2v : L.B2p) + 4 * g;                     // + 16 nt
     // output-layer A operand: row c of the 16-row tile; only rows 0..3 (policy) / row 4 (value) are non-zero -- every other
@@ -755,9 +573,9 @@ __device__ __forceinline__ void ac_exact_branch(const AcLds &L, const f32x4 (&h1
 // Tower actor-critic: the OTHER layout the reference trains and ships (every ppo2_docking*.zip; run_docking_gail.py:56),
 // net_arch [dict(pi=[128, 128], vf=[128, 128])], ReLU -- no shared layer: pi_fc0 12->128 -> pi_fc1 128->128 -> pi 128->4 and
 // vf_fc0 12->128 -> vf_fc1 128->128 -> vf 128->1 (rl_baselines/common/policies.py:35-92 with an empty shared part).
-// Both Runner kernels evaluate it as the same four pieces of the shared-trunk heads: layer 1 (pi_fc0) -> policy branch ->
-// layer 1 (vf_fc0) -> value branch, the second layer 1 written into the registers of the first (a role-split matrix wave
-// holds ONE set of layer-1 B operands: 128 registers).  Per wave and step: 2 x 96 more f32 MFMAs than the shared trunk.
+// Both Runner kernels evaluate it as the pieces of the shared-trunk heads plus a second layer 1: layer 1 (pi_fc0) -> policy
+// branch -> layer 1 (vf_fc0) -> value branch, the second layer 1 written into the registers of the first (a role-split matrix
+// wave holds ONE set of layer-1 B operands: 128 registers).  Per wave and step: 2 x 96 more f32 MFMAs than the shared trunk.
 // Exact-f32 LDS image (floats): W2^T 128 x 260 (row r = pi_fc1^T row r | vf_fc1^T row r | 4 pad: a 1040-byte row meets the
 // banks as the shared image's 528-byte row does, and pads 1 KiB where two 132-float images pad 4 KiB -- the room for the
 // second layer 1) | W3pi^T 4x132 | W3vf 132 | W1pi^T 128x13 | W1vf^T 128x13 | b1pi 128 | b2pi 128 | b2vf 128 | b1vf 128 |
@@ -766,10 +584,6 @@ __device__ __forceinline__ void ac_exact_branch(const AcLds &L, const f32x4 (&h1
 // per-wave stage 4 x 3072  = 161 344 B, + 2 KiB of zeros for the dead output rows (ac_fast_branch) = 163 392 B.
 // Neither leaves room for the role-split kernel's 1 KiB value buffer: its matrix waves hand the values over by ds_bpermute.
 enum : int { kNetShared = 0, kNetTowers = 1 };
-
-// a wave's layer-1 result: FAST the split B operands of the 128 x 128 layer (bh / bl), else the f32 accumulators (h1)
-template <bool FAST> using TowB = u32x4[FAST ? 4 : 1][4];
-template <bool FAST> using TowH = f32x4[FAST ? 1 : 8][4];
 
 constexpr int kLdW2T = 2 * kHid + 4;
 
@@ -784,67 +598,49 @@ constexpr int kAcTowFastBlobBytes = kAcTowFastB1v + kHid * 4;
 constexpr int kAcTowFastLdsBytes = kAcTowFastBlobBytes + 4 * (12 * 64) * 4;
 static_assert(tow_lds_floats() * 4 == 163472 && kAcTowFastLdsBytes == 161344, "tower LDS images as documented");
 
-// layer 1 of the policy tower + policy branch -> a3p (rows 0..3), then layer 1 of the value tower + value branch -> a3v (row 4).
-// Lp: the exact image with W1 = pi_fc0; Lv: the same with W1 = vf_fc0.  FAST: split-bf16 image at `blob`, zeros at `zeros`.
-template <bool FAST>
-__device__ __forceinline__ void tow_policy_part(const char *blob, int zeros, const AcLds &Lp, const float *stage, int lane,
-                                                TowB<FAST> &bh, TowB<FAST> &bl, TowH<FAST> &h1, f32x4 (&a3p)[4])
+// The heads' LDS image as a wave addresses it.  FAST: the split-bf16 image at `blob`, its 2 KiB of zeros at byte `zeros`;
+// else the exact image L, and for the towers Lv = L with W1 / B1 = vf_fc0 (L's = pi_fc0).
+struct HeadsLds {
+    const char *blob;
+    int zeros;
+    AcLds L, Lv;
+};
+
+// a wave's layer-1 result: FAST the split B operands of the 128 x 128 layer (bh / bl), else the f32 accumulators (h1)
+template <bool FAST> using HeadB = u32x4[FAST ? 4 : 1][4];
+template <bool FAST> using HeadH = f32x4[FAST ? 1 : 8][4];
+
+// layer 1 of the wave's 64 envs from the observations in `stage`.  VF: vf_fc0 of the tower layout, else shared_fc0 / pi_fc0
+template <bool FAST, bool VF>
+__device__ __forceinline__ void heads_layer1(const HeadsLds &H, const float *stage, int lane, HeadB<FAST> &bh, HeadB<FAST> &bl, HeadH<FAST> &h1)
 {
-    if constexpr (FAST) {
-        ac_fast_layer1(blob, stage, lane, bh, bl);
-        ac_fast_branch<0>(blob, zeros, bh, bl, lane, a3p);
-    } else {
-        ac_exact_layer1(Lp, stage, lane, h1);
-        ac_exact_branch<0, kLdW2T>(Lp, h1, lane, a3p);
-    }
+    if constexpr (FAST) ac_fast_layer1<VF ? kAcTowFastW1v : kAcFastW1, VF ? kAcTowFastB1v : kAcFastB>(H.blob, stage, lane, bh, bl);
+    else layer1_relu(VF ? H.Lv.W1 : H.L.W1, VF ? H.Lv.B1 : H.L.B1, stage, lane, h1);
 }
 
-template <bool FAST>
-__device__ __forceinline__ void tow_value_layer1(const char *blob, const AcLds &Lv, const float *stage, int lane,
-                                                 TowB<FAST> &bh, TowB<FAST> &bl, TowH<FAST> &h1)
+// branch BR (0 policy -> rows 0..3 of a3, 1 value -> row 4) from the layer-1 result
+template <bool FAST, int NET, int BR>
+__device__ __forceinline__ void heads_branch(const HeadsLds &H, const HeadB<FAST> &bh, const HeadB<FAST> &bl, const HeadH<FAST> &h1, int lane,
+                                             f32x4 (&a3)[4])
 {
-    if constexpr (FAST) ac_fast_layer1<kAcTowFastW1v, kAcTowFastB1v>(blob, stage, lane, bh, bl);
-    else ac_exact_layer1(Lv, stage, lane, h1);
+    if constexpr (FAST) ac_fast_branch<BR>(H.blob, H.zeros, bh, bl, lane, a3);
+    else ac_exact_branch<BR, NET == kNetTowers ? kLdW2T : kLdW>(H.L, h1, lane, a3);
 }
 
-template <bool FAST>
-__device__ __forceinline__ void tow_value_branch(const char *blob, int zeros, const AcLds &Lv, const TowB<FAST> &bh,
-                                                 const TowB<FAST> &bl, const TowH<FAST> &h1, int lane, f32x4 (&a3v)[4])
+// One wave per tile: obs (per owning lane) -> out[0..3] = action mean, out[4] = value (per owning lane).  `stage` = 768 floats
+// per wave.  Towers: the second layer 1 is written into the registers of the first.
+template <bool FAST, int NET>
+__device__ __forceinline__ void mlp_heads(const float obs[12], float out[5], const HeadsLds &H, float *stage, int lane)
 {
-    if constexpr (FAST) ac_fast_branch<1>(blob, zeros, bh, bl, lane, a3v);
-    else ac_exact_branch<1, kLdW2T>(Lv, h1, lane, a3v);
-}
-
-// One wave per tile: obs (per owning lane) -> out[0..3] = action mean, out[4] = value (per owning lane), as mlp_actor_critic.
-template <bool FAST>
-__device__ __forceinline__ void mlp_towers(const float obs[12], float out[5], const char *blob, int zeros, const AcLds &Lp,
-                                           const AcLds &Lv, float *stage, int lane)
-{
-    const int c = lane & 15, g = lane >> 4;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) stage[k * 64 + lane] = obs[k];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    TowB<FAST> bh, bl;
-    TowH<FAST> h1;
+    stage_obs(obs, stage, lane);
+    HeadB<FAST> bh, bl;
+    HeadH<FAST> h1;
     f32x4 a3p[4], a3v[4];
-    tow_policy_part<FAST>(blob, zeros, Lp, stage, lane, bh, bl, h1, a3p);
-    tow_value_layer1<FAST>(blob, Lv, stage, lane, bh, bl, h1);
-    tow_value_branch<FAST>(blob, zeros, Lv, bh, bl, h1, lane, a3v);
-    // every lane read its layer-1 operands before the branches: the stage is free for the hand-over
-    if (g == 0) {
-#pragma unroll
-        for (int et = 0; et < 4; ++et) *reinterpret_cast<f32x4 *>(stage + (16 * et + c) * 8) = a3p[et];
-    } else if (g == 1) {
-#pragma unroll
-        for (int et = 0; et < 4; ++et) stage[(16 * et + c) * 8 + 4] = a3v[et][0];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const f32x4 av = *reinterpret_cast<const f32x4 *>(stage + lane * 8);
-    out[0] = av[0]; out[1] = av[1]; out[2] = av[2]; out[3] = av[3];
-    out[4] = stage[lane * 8 + 4];
-    __builtin_amdgcn_wave_barrier();
+    heads_layer1<FAST, false>(H, stage, lane, bh, bl, h1);
+    heads_branch<FAST, NET, 0>(H, bh, bl, h1, lane, a3p);
+    if constexpr (NET == kNetTowers) heads_layer1<FAST, true>(H, stage, lane, bh, bl, h1);
+    heads_branch<FAST, NET, 1>(H, bh, bl, h1, lane, a3v);
+    heads_to_owner(a3p, a3v, stage, lane, out);
 }
 
 // value of the env of this lane from row 4 of the value tile (register 0 of lanes 16..31) without LDS memory: lane l reads

@@ -67,7 +67,8 @@ __device__ __forceinline__ float *load_towers_lds(char *lds_raw, const RunnerArg
     }
 }
 
-// Shared-trunk image (mlp.hpp) into LDS by `nthr` threads; -> the per-wave stages.  FAST: the packed blob verbatim.
+// Shared-trunk image (mlp.hpp) into LDS by `nthr` threads; -> the per-wave stages.  FAST: the packed blob verbatim (the
+// kernels zero their 2 KiB for the dead output rows themselves: it lies where their own layout leaves room).
 template <bool FAST>
 __device__ __forceinline__ float *load_shared_lds(char *lds_raw, const RunnerArgs &R, int nthr, AcLds &L)
 {
@@ -126,22 +127,26 @@ template <bool FAST, int NET>
 constexpr int runner_lds_bytes()
 {
     return NET == kNetTowers ? (FAST ? kAcTowFastLdsBytes + 2048 : (int)(tow_lds_floats() * sizeof(float)))
-                             : (FAST ? kAcFastLdsBytes : (int)(ac_lds_floats() * sizeof(float)));
+                             : (FAST ? kAcFastLdsBytes + 2048 : (int)(ac_lds_floats() * sizeof(float)));
 }
 
-// FAST: the networks on the bf16 matrix rate with split operands (mlp_actor_critic_fast; R.blob = host-packed image)
+// FAST: the networks on the bf16 matrix rate with split operands (mlp_heads<true, NET>; R.blob = host-packed image, and
+//       2 KiB of zeros right after the stages)
 // PARAMS: per-env mass / inertia (domain randomisation; RMODE 2 redraws them at every episode start)
-// NET: kNetShared (shared_fc0 trunk, the shipped best_model_v0) or kNetTowers (separate pi / vf towers, mlp_towers)
+// NET: kNetShared (shared_fc0 trunk, the shipped best_model_v0) or kNetTowers (separate pi / vf towers)
 template <int INTEG, int RMODE, bool PARAMS, bool FAST, int NET = kNetShared>
 __global__ __launch_bounds__(kBlock, 1) void k_runner_rollout(StepArgs A, RunnerArgs R)
 {
     constexpr bool TOW = NET == kNetTowers;
+    constexpr int kZeros = TOW ? kAcTowFastLdsBytes : kAcFastLdsBytes;                               // FAST: 2 KiB of zeros
     __shared__ __attribute__((aligned(16))) char lds_raw[runner_lds_bytes<FAST, NET>()];
     AcLds L{}, Lv{};
     float *sStage;
     if constexpr (TOW) sStage = load_towers_lds<FAST>(lds_raw, R, kBlock, L, Lv);
     else sStage = load_shared_lds<FAST>(lds_raw, R, kBlock, L);
+    if (!TOW && FAST && threadIdx.x < 128) reinterpret_cast<uint4 *>(lds_raw + kZeros)[threadIdx.x] = make_uint4(0, 0, 0, 0);
     __syncthreads();
+    const HeadsLds H{lds_raw, kZeros, L, Lv};
 
     const int lane = threadIdx.x & (kTile - 1);
     const int w = threadIdx.x >> 6;
@@ -167,9 +172,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_runner_rollout(StepArgs A, Runner
         const int64_t ow = R.env_major ? env * A.T + t : o;
         if (active) { if (R.env_major) store_obs_cached(A.obs, ow, obs); else store_obs(A.obs, ow, obs); }   // mb_obs: the observation the policy acts on
         float head[5];
-        if constexpr (TOW) mlp_towers<FAST>(obs, head, lds_raw, kAcTowFastLdsBytes, L, Lv, stage, lane);
-        else if (FAST) mlp_actor_critic_fast(obs, head, lds_raw, stage, lane);
-        else mlp_actor_critic(obs, head, L, stage, lane);
+        mlp_heads<FAST, NET>(obs, head, H, stage, lane);
         float eps[4];
         if (R.noise) {
             const float4 nv = active ? reinterpret_cast<const float4 *>(R.noise)[o] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -197,9 +200,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_runner_rollout(StepArgs A, Runner
     }
     // last_values = model.value(obs) on the observation after the last step (ppo2.py:506)
     float head[5];
-    if constexpr (TOW) mlp_towers<FAST>(obs, head, lds_raw, kAcTowFastLdsBytes, L, Lv, stage, lane);
-    else if (FAST) mlp_actor_critic_fast(obs, head, lds_raw, stage, lane);
-    else mlp_actor_critic(obs, head, L, stage, lane);
+    mlp_heads<FAST, NET>(obs, head, H, stage, lane);
     if (active) {
         R.last_values[env] = head[4];
         R.last_dones[env] = done_prev ? 1 : 0;
@@ -219,7 +220,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_runner_rollout(StepArgs A, Runner
 // the matrix wave keeps no environment registers: both roles fit 256 registers, two waves per SIMD.  The means travel
 // through the tile's obs stage (the matrix wave has its observations in registers by then), the values through a
 // buffer private to the matrix wave.  Every wave passes the same 2 T + 1 workgroup barriers.  FAST as in k_runner_rollout;
-// the heads are the same instruction sequences on the same operands as there, so the two kernels agree bit for bit.
+// the heads are the very pieces mlp_heads runs there (mlp.hpp), in its order, so the two kernels agree bit for bit.
 // NET == kNetTowers: the matrix wave runs pi layer 1 -> policy branch -> vf layer 1 (the stage still holds the observations)
 // -> means to LDS -> #b -> value branch; the values reach their lanes by ds_bpermute (no value buffer: see the tower image).
 template <int INTEG, int RMODE, bool PARAMS, bool FAST, int NET = kNetShared>
@@ -244,74 +245,43 @@ __global__ __launch_bounds__(2 * kBlock, 1) void k_runner_split(StepArgs A, Runn
     float *stage = sStage + w * (12 * 64);
     float *sval = reinterpret_cast<float *>(lds_raw + kHeadBytes) + w * kTile;       // shared trunk only
     QS_ASSERT((char *)(stage + 12 * 64) <= lds_raw + (TOW ? (int)sizeof lds_raw : kHeadBytes));
-    if (TOW && matrix_role) {
-        const int c = lane & 15, g = lane >> 4;
-        u32x4 bh[FAST ? 4 : 1][4], bl[FAST ? 4 : 1][4];
-        f32x4 h1[FAST ? 1 : 8][4];
-        f32x4 a3[4];
-        QS_PHASE_DECL;
-#pragma clang loop unroll(disable)
-        for (int64_t t = 0; t <= A.T; ++t) {
-            __syncthreads();                                                  // #a: this step's observations are in LDS
-            QS_PHASE(0);
-            if (t < A.T) tow_policy_part<FAST>(lds_raw, kZeros, L, stage, lane, bh, bl, h1, a3);
-            QS_PHASE(1);
-            tow_value_layer1<FAST>(lds_raw, Lv, stage, lane, bh, bl, h1);   // before the means overwrite the observations
-            if (t < A.T) {
-                if (g == 0) {
-#pragma unroll
-                    for (int et = 0; et < 4; ++et) *reinterpret_cast<f32x4 *>(stage + (16 * et + c) * 8) = a3[et];
-                }
-                QS_PHASE(2);
-                __syncthreads();                                              // #b: the means are in LDS
-                QS_PHASE(3);
-            }
-            tow_value_branch<FAST>(lds_raw, kZeros, Lv, bh, bl, h1, lane, a3);
-            QS_PHASE(4);
-            const float v = value_to_owner(a3, lane);
-            if (active) {
-                float *vout = t < A.T ? R.values + t * A.n : R.last_values;   // last: model.value(obs) after the last step (ppo2.py:506)
-                vout[env] = v;
-            }
-            QS_PHASE(5);
-        }
-        QS_PHASE_FLUSH(0);
-    } else if (matrix_role) {
+    const HeadsLds H{lds_raw, kZeros, L, Lv};
+    if (matrix_role) {
         const int c = lane & 15, g = lane >> 4;
         // layer-1 result = the B operands of both 128 x 128 branches, 128 registers either way
-        u32x4 bh[FAST ? 4 : 1][4], bl[FAST ? 4 : 1][4];
-        f32x4 h1[FAST ? 1 : 8][4];
+        HeadB<FAST> bh, bl;
+        HeadH<FAST> h1;
         f32x4 a3[4];
         QS_PHASE_DECL;
 #pragma clang loop unroll(disable)
         for (int64_t t = 0; t <= A.T; ++t) {
             __syncthreads();                                                  // #a: this step's observations are in LDS
             QS_PHASE(0);
-            if constexpr (FAST) ac_fast_layer1(lds_raw, stage, lane, bh, bl);
-            else ac_exact_layer1(L, stage, lane, h1);
+            if (!TOW || t < A.T) heads_layer1<FAST, false>(H, stage, lane, bh, bl, h1);
             QS_PHASE(1);
+            if (t < A.T) heads_branch<FAST, NET, 0>(H, bh, bl, h1, lane, a3);
+            if constexpr (TOW) heads_layer1<FAST, true>(H, stage, lane, bh, bl, h1);   // before the means overwrite the observations
             if (t < A.T) {
-                if constexpr (FAST) ac_fast_branch<0>(lds_raw, kZeros, bh, bl, lane, a3);
-                else ac_exact_branch<0>(L, h1, lane, a3);
-                if (g == 0) {
-#pragma unroll
-                    for (int et = 0; et < 4; ++et) *reinterpret_cast<f32x4 *>(stage + (16 * et + c) * 8) = a3[et];
-                }
+                if (g == 0) means_to_stage(a3, stage, c);
                 QS_PHASE(2);
                 __syncthreads();                                              // #b: the means are in LDS
                 QS_PHASE(3);
             }
-            if constexpr (FAST) ac_fast_branch<1>(lds_raw, kZeros, bh, bl, lane, a3);
-            else ac_exact_branch<1>(L, h1, lane, a3);
+            heads_branch<FAST, NET, 1>(H, bh, bl, h1, lane, a3);
             QS_PHASE(4);
-            if (g == 1) {
+            float v;
+            if constexpr (TOW) {
+                v = value_to_owner(a3, lane);
+            } else {
+                if (g == 1) {
 #pragma unroll
-                for (int et = 0; et < 4; ++et) sval[16 * et + c] = a3[et][0];
+                    for (int et = 0; et < 4; ++et) sval[16 * et + c] = a3[et][0];
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                v = sval[lane];
+                __builtin_amdgcn_wave_barrier();
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const float v = sval[lane];
-            __builtin_amdgcn_wave_barrier();
             if (active) {
                 float *vout = t < A.T ? R.values + t * A.n : R.last_values;   // last: model.value(obs) after the last step (ppo2.py:506)
                 vout[env] = v;

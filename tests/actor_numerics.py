@@ -1,8 +1,8 @@
 """Float64 reference of the device actor / critic heads and a first-order forward-error bound for them (test helper; CPU only,
 no GPU, no torch needed except by the packers).
 
-Every network evaluation on the device runs one of two MFMA paths: exact float32 (mlp_actor / mlp_actor_critic) or split bf16
-("bf16x3": mlp_actor_fast / mlp_actor_critic_fast, csrc/mlp.hpp).  Neither is held to a fixed tolerance here.
+Every network evaluation on the device runs one of two MFMA paths: exact float32 (mlp_actor / mlp_heads<false>) or split bf16
+("bf16x3": mlp_actor_fast / mlp_heads<true>, csrc/mlp.hpp).  Neither is held to a fixed tolerance here.
 err_scale() propagates the magnitudes of the summed terms layer by layer,
 
     E_0 = 0,   E_l = |W_l|^T E_{l-1} + (|h_{l-1}| |W_l| + |b_l|),
@@ -373,7 +373,7 @@ def emulate_actor_blob(blob, obs, drop=None):
 
 
 def emulate_actor_critic_blob(blob, obs, towers=False, drop=None):
-    """mlp_actor_critic_fast / the tower heads from the bytes of pack_fast_actor_critic -> (mean [N,4], value [N]).  The first
+    """mlp_heads<true> (either layout) from the bytes of pack_fast_actor_critic -> (mean [N,4], value [N]).  The first
     layer is exact float32; drop = (branch 'pi' | 'vf', layer 1..2, term) mutant."""
     d = decode_actor_critic_blob(blob, towers)
     x = np.asarray(obs, np.float32)
