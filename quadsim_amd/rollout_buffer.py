@@ -112,9 +112,11 @@ class EpisodeTracker:
         import torch
         env = self.env
         T, n = rewards.shape
+        if n != env.num_envs:                          # ep_ret / ep_len hold num_envs carries: the kernel walks n of them
+            raise ValueError("EpisodeTracker.update: rewards has %d envs, the tracker's env has %d" % (n, env.num_envs))
         env._use_current_stream()
         rewards, dones, last_dones = _f32(env, rewards), _u8(env, dones), _u8(env, last_dones)
-        cap = T * n                                    # an episode is at least one step long: cannot overflow
+        cap = T * n                                   # an episode is at least one step long: cannot overflow
         if self._bufs is None or self._bufs[0].numel() < cap:
             self._bufs = (torch.empty((cap,), dtype=torch.int64, device=env.device),
                           torch.empty((cap,), dtype=torch.float32, device=env.device),

@@ -51,3 +51,25 @@ def instantiations(notes, kernels):
         if m:
             got.add((m.group(1),) + tuple(int(a) for a in re.findall(r"L[ib](\d+)E", m.group(2))))
     return got
+
+
+_ITANIUM_TYPES = {"f": "float", "d": "double", "h": "uint8_t", "a": "int8_t", "i": "int", "j": "unsigned", "l": "long", "m": "unsigned long"}
+
+
+def instantiations_with_types(notes, kernels, namespace="qs"):
+    """{(kernel, template arguments...)} of the kernels named in `kernels`, which live in the named namespace `namespace`:
+    plain kernels give (kernel,), integer / bool template arguments give ints and builtin type arguments their C names
+    (k_swap_flatten<13, float> -> ("k_swap_flatten", 13, "float")).  instantiations() above sees none of the first and
+    third kind."""
+    arg = r"L[ib]\d+E|[%s]" % "".join(_ITANIUM_TYPES)
+    # the length prefix of the Itanium mangling keeps k_swap_flatten from matching inside k_swap_flatten_v4
+    sym_re = re.compile(r"^_ZN%d%s(?:%s)(?:I((?:%s)+)E)?E" % (len(namespace), namespace, "|".join(
+        "%d(?P<k%d>%s)" % (len(k), j, re.escape(k)) for j, k in enumerate(kernels)), arg))
+    got = set()
+    for sym in notes:
+        m = sym_re.match(sym)
+        if m:
+            name = next(v for k, v in m.groupdict().items() if v)
+            args = re.findall(arg, m.group(len(kernels) + 1) or "")
+            got.add((name,) + tuple(int(a[2:-1]) if a[0] == "L" else _ITANIUM_TYPES[a] for a in args))
+    return got
