@@ -118,7 +118,11 @@ int qs_destroy(QsEnv *env);
 
 /* DockingEnv.reset (docking_env.py:233-244) for the envs with mask[i] != 0 (mask NULL = all).
  * obs_out [N,12] nullable; rows of unmasked envs are left untouched.
- * Does not touch the target's desired attitude (the reference never resets it). */
+ * Does not touch the target's desired attitude (the reference never resets it), the step counter, or -- without
+ * QS_RANDOMISE_PARAMS -- the parameters; an unmasked env keeps every bit of its state and parameters.
+ * A randomised reset draws from the reset stream at (global env id, step counter).  The counter is kept per 64-env tile and
+ * every env is keyed by its own tile's: after qs_step / qs_rollout all tiles agree, after uneven qs_step_group calls a tile
+ * holds the number of steps its group has taken (qs_get_step_counter reads tile 0; qs_set_step_counter sets every tile). */
 int qs_reset(QsEnv *env, const uint8_t *mask, float *obs_out);
 
 /* DockingEnv.step (docking_env.py:104-231) / MovingDockingEnv.step (moving_docking_env.py:111-192)
@@ -247,7 +251,8 @@ int qs_set_state(QsEnv *env, const float *chaser, const float *target, const flo
 
 /* Per-env initial states that reset() (and the auto-reset) return to: env.chaser_ini_state / env.target_ini_state
  * (docking_env.py:39-57; scripts mutate them, run_expert_policy.py:44,63-64) or HoveringEnv.ini_state
- * (hovering_env.py:26-29).  chaser_init [N,13]; target_init [N,13] nullable = nominal (ignored for hovering).
+ * (hovering_env.py:26-29).  chaser_init [N,13]; target_init [N,13] nullable = the stored targets stay as they are: nominal on
+ * a handle that had no stored initial states, else what construction or an earlier call left (ignored for hovering).
  * docking-v1 and hovering-v0 handles are created with rocRAND-drawn per-env initial states (the reference draws
  * them from numpy's global RNG at construction); this call overrides them.  Switches the handle to stored-init
  * resets (takes precedence over `randomise`) and re-initialises nothing by itself: call qs_reset afterwards. */

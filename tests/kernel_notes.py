@@ -53,6 +53,47 @@ def instantiations(notes, kernels):
     return got
 
 
+def anon_instantiations(notes, kernels):
+    """{(kernel, bool template arguments...)} of the kernels named in `kernels` that live in the anonymous namespace and are
+    plain kernels -- (kernel,) -- or templated on bools alone -- k_state_io<true> -> ("k_state_io", 1).  instantiations() above
+    sees only templated kernels, instantiations_with_types() only a named namespace."""
+    # the length prefix of the Itanium mangling keeps k_reset from matching inside k_reset_all; a plain kernel's name is followed
+    # by the E that closes the nested name, a templated one's by I <arguments> E E
+    sym_re = re.compile(r"^_ZN12_GLOBAL__N_1(?:%s)(?:I(?P<args>(?:Lb[01]E)+)E)?E" % "|".join(
+        "%d(?P<k%d>%s)" % (len(k), j, re.escape(k)) for j, k in enumerate(kernels)))
+    got = set()
+    for sym in notes:
+        m = sym_re.match(sym)
+        if m:
+            name = next(v for k, v in m.groupdict().items() if v and k != "args")
+            got.add((name,) + tuple(int(a) for a in re.findall(r"Lb([01])E", m.group("args") or "")))
+    return got
+
+
+def base_names(notes):
+    """{kernel base name} of every kernel symbol: the last component of the (nested) name, without template arguments --
+    _ZN12_GLOBAL__N_15k_envILi0ELb1EEEvPf and _ZN2qs5k_envE... both give k_env.  A symbol that is not an Itanium-mangled function
+    name is returned as it is, so that a census cannot lose it."""
+    got = set()
+    for sym in notes:
+        m = re.match(r"^_Z(N?)", sym)
+        if not m:
+            got.add(sym)
+            continue
+        pos, name = m.end(), None
+        while True:
+            d = re.match(r"\d+", sym[pos:])
+            if not d:
+                break
+            ln = int(d.group(0))
+            name = sym[pos + d.end():pos + d.end() + ln]
+            pos += d.end() + ln
+            if not m.group(1):
+                break
+        got.add(name if name else sym)
+    return got
+
+
 _ITANIUM_TYPES = {"f": "float", "d": "double", "h": "uint8_t", "a": "int8_t", "i": "int", "j": "unsigned", "l": "long", "m": "unsigned long"}
 
 
