@@ -622,7 +622,14 @@ int qs_mppi_plan_split(QsEnv *env, int32_t horizon, int32_t paths, int32_t itera
                        const float *nominal_in, const float *noise, float *actions, float *nominal_out,
                        double *best_score, double *scores, float *trace, float *candidates);
 
-/* ---- layer-1 entry points: n independent drones / controllers (n need not equal N) ----------- */
+/* ---- layer-1 entry points: n independent drones / controllers (n need not equal N) -----------
+ * Argument domain.  Every attitude below goes through a float32 atan2 that forms a reciprocal of the larger of its two
+ * arguments: results are finite, and inside the error bounds that tests/layer1_ref.py derives and tests/test_gpu_layer1.py asserts,
+ * for max(|y|, |x|) in [2^-125, 2^125) or y = x = 0.  The arguments are entries of the reference's quat2euler, quadratic in the
+ * quaternion; a quaternion an env can hold (|q| in [0.5, 2]) never leaves that range, gimbal lock included.  For the quaternion inputs
+ * of qs_drone_step the bounds are held at |q| in [0.5, 2], for those of qs_ctrl and qs_rel_obs within 2 % of |q| = 1; they grow with
+ * the condition of the Euler angles, |q|^2 / sqrt(|q|^4 - r12^2) (1 / cos roll for a unit quaternion).  Outside these ranges the
+ * behaviour is unspecified and results may be non-finite; no argument makes a call fault. */
 
 /* Drone.step (dynamics/quadrotor.py:126-144): state [n,13] in/out, u_prev [n,4] in/out (Drone.u),
  * u [n,4] commanded control, par [n,4] = mass,Ixx,Iyy,Izz or NULL (nominal), limited [n] u8 nullable. */
@@ -641,7 +648,10 @@ int qs_rel_obs(QsEnv *env, int64_t n, const float *chaser, const float *target, 
 
 /* ---- layer 0: utils/transform.py for n inputs -------------------------------------------------
  * op 0 quat2euler [n,4] -> [n,3] (transform.py:94-120); 1 euler2quat [n,3] -> [n,4] (:123-136);
- * 2 quat2rot [n,4] -> [n,9] row-major (:4-20; the reference's element-wise form); 3 rot2euler [n,9] -> [n,3] (:23-46) */
+ * 2 quat2rot [n,4] -> [n,9] row-major (:4-20; the reference's element-wise form); 3 rot2euler [n,9] -> [n,3] (:23-46).
+ * Domain (finite results inside the bounds of tests/layer1_ref.py): op 0 and 2 |q| in [2^-61, 2^62); op 1 angles up to 2e4 in magnitude (the half angle is reduced by quadrants up to 1e4);
+ * op 3 any finite R[1][2] (clamped to [-1, 1]; pitch is 0 where R[1][2] >= 1 or < -1) and, for each of the pairs (R[0][2], R[2][2]) and
+ * (R[1][0], R[1][1]), the larger magnitude in [2^-125, 2^125) or both zero.  Outside: unspecified, may be non-finite. */
 int qs_transform(QsEnv *env, int32_t op, int64_t n, const float *in, float *out);
 
 #ifdef __cplusplus

@@ -58,8 +58,8 @@ __global__ __launch_bounds__(kBlock) void k_transform(int op, int64_t n, const f
         const float r12 = R[5];
         const bool sat = (r12 >= 1.0f) || (r12 < -1.0f);
         out[i * 3] = q_asin(fminf(fmaxf(r12, -1.0f), 1.0f));
-        out[i * 3 + 1] = sat ? 0.0f : q_atan2(-R[2], R[8]);
-        out[i * 3 + 2] = q_atan2(-R[3], R[4]);
+        out[i * 3 + 1] = sat ? 0.0f : q_atan2<true>(-R[2], R[8]);      // a caller's matrix may hold -0: as numpy.arctan2 treats it
+        out[i * 3 + 2] = q_atan2<true>(-R[3], R[4]);
     }
 }
 

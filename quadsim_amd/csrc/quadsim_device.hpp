@@ -53,9 +53,14 @@ struct EnvConst {
 // scalar math.  Hardware rcp / rsq / sqrt (1 ulp) and hand-rolled inverse trig /
 // sincos: the arguments on this path are bounded (angles in [-pi, pi], ratios in
 // [0, 1]), so none of libm's huge-argument or denormal paths are needed.
-// Polynomials are near-minimax fits (tools/fit_polys.py); measured against
-// float64 on the full argument range: atan2 <= 1.1e-7 abs, asin <= 9.3e-8 abs,
-// sin <= 4.4e-8, cos <= 7.4e-8 abs -- about 1 ulp of the result's scale.
+// Polynomials are near-minimax fits (tools/fit_polys.py).  Absolute error against
+// float64, asserted on the device by the sweeps of tests/test_gpu_layer1.py with the
+// bounds derived in tests/layer1_ref.py (measured worst cases: profiles/layer1/):
+//   q_sincos  1.04e-7 for |x| <= pi/4 (no reduction), 1.34e-7 + 1.9e-15 |k| after a reduction by k quadrants; swept to |x| = 1e4
+//   q_asin    6.9e-8 for |x| <= 1/2 (2^-23 relative for |x| <= 2^-6), 2.7e-7 above; +-pi/2 in float32 at and beyond +-1 (the callers clamp)
+//   q_atan2   1.9e-7 for |y| <= |x|, x > 0; 3.0e-7 for |y| > |x|; 5.1e-7 for x < 0 -- for max(|y|, |x|) in [2^-125, 2^125), or both zero.
+//             Outside that range the reciprocal leaves the normal numbers and the result is unspecified and may be non-finite.
+// Half an ulp of pi is 1.2e-7: these are one to two ulps of the result's scale.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float q_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float q_rsqrt(float x) { return __builtin_amdgcn_rsqf(x); }
@@ -78,7 +83,11 @@ __device__ __forceinline__ float q_asin(float x)
     return copysignf(r, x);
 }
 
-// atan2 for finite arguments; atan2(0, 0) = 0 like numpy.  atan(t) = t + t s P(s), s = t^2, t in [0, 1].
+// atan2 for max(|y|, |x|) in [2^-125, 2^125) or y = x = 0.  atan(t) = t + t s P(s), s = t^2, t in [0, 1].  A zero x counts as +0 whatever
+// its sign: atan2(+-0, +-0) = +-0 -- numpy's answer for x = +0, and no caller in this library can hold x = -0 (x is r11, r22 of a
+// quaternion or R11, R22 of rel_obs: an exact cancellation gives +0; tests/test_layer1_cpu.py).  SIGNED_ZERO_X, for the one caller
+// whose x comes from outside (qs_transform op 3): -0 is on the negative axis as in numpy.arctan2, atan2(+-0, -0) = +-pi.
+template <bool SIGNED_ZERO_X = false>
 __device__ __forceinline__ float q_atan2(float y, float x)
 {
     float ax = fabsf(x), ay = fabsf(y);
@@ -96,7 +105,8 @@ __device__ __forceinline__ float q_atan2(float y, float x)
     p = fmaf(p, s, -0.3333306610584259f);
     float r = fmaf(t * s, p, t);
     r = (ay > ax) ? (kHalfPi - r) : r;
-    r = (x < 0.0f) ? (kPi - r) : r;
+    bool neg = SIGNED_ZERO_X ? (__float_as_uint(x) >> 31) != 0 : x < 0.0f;   // with y != 0 and x = -0: kPi - kHalfPi == kHalfPi exactly
+    r = neg ? (kPi - r) : r;
     return copysignf(r, y);
 }
 

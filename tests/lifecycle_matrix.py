@@ -55,11 +55,8 @@ CENSUS = {
     # the actor alone: the actor numerics
     "k_policy_forward": "tests/test_gpu_actor_numerics.py::test_predict_hip_within_bound",
     "k_policy_forward_fast": "tests/test_gpu_actor_numerics.py::test_predict_hip_within_bound",
-    # layer 1 and layer 0
-    "k_drone_step": "tests/test_gpu_parity.py::test_g1_drone_step_golden",
-    "k_ctrl": "tests/test_gpu_parity.py::test_g3_controller_golden",
-    "k_rel_obs": "tests/test_gpu_parity.py::test_g2_rel_obs_matches_reference_formula",
-    "k_transform": "tests/test_gpu_parity.py::test_g2_transforms_golden_and_math_accuracy",
+    # layer 1 and layer 0: tests/layer1_matrix.py
+    "k_drone_step": "layer1_matrix", "k_ctrl": "layer1_matrix", "k_rel_obs": "layer1_matrix", "k_transform": "layer1_matrix",
     # the planners: instantiations and resources on the CPU, values in the GPU files beside them
     "k_shooting_plan": "tests/test_shooting_cpu.py::test_plan_kernel_instantiations_and_resources",
     "k_wide_candidates": "tests/test_shooting_split_cpu.py::test_wide_kernel_instantiations_and_resources",
