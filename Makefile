@@ -2,13 +2,20 @@
 HIPCC ?= hipcc
 LIB    = quadsim_amd/csrc/libquadsim_hip.so
 SRC    = quadsim_amd/csrc/quadsim_hip.hip
-HDR    = $(wildcard quadsim_amd/csrc/*.hpp) include/quadsim.h
+HDR    = $(filter-out quadsim_amd/csrc/dynplan_%.hpp,$(wildcard quadsim_amd/csrc/*.hpp)) include/quadsim.h
+# the second library (include/quadsim_dyn.h): its own translation unit, same flags
+DYNLIB = quadsim_amd/csrc/libquadsim_dyn.so
+DYNSRC = quadsim_amd/csrc/dynplan.hip
+DYNHDR = $(wildcard quadsim_amd/csrc/dynplan_*.hpp) quadsim_amd/csrc/quadsim_device.hpp include/quadsim_dyn.h
 
 all: lib oracle
 
-lib: $(LIB)
+lib: $(LIB) $(DYNLIB)
 $(LIB): $(SRC) $(HDR)
 	$(HIPCC) -std=c++20 -O3 -fno-slp-vectorize -ffp-contract=on --offload-arch=gfx950 -fPIC -shared -Wno-unused-result $(SRC) -lhsa-runtime64 -o $@
+
+$(DYNLIB): $(DYNSRC) $(DYNHDR)
+	$(HIPCC) -std=c++20 -O3 -fno-slp-vectorize -ffp-contract=on --offload-arch=gfx950 -fPIC -shared -Wno-unused-result $(DYNSRC) -o $@
 
 oracle:
 	$(MAKE) -C oracle
@@ -23,6 +30,6 @@ bench: all
 	python bench.py
 
 clean:
-	rm -f $(LIB) oracle/libqso.so oracle/*.o
+	rm -f $(LIB) $(DYNLIB) oracle/libqso.so oracle/*.o
 
 .PHONY: all lib oracle test-cpu test-gpu bench clean

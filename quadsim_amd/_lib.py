@@ -12,8 +12,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("QUADSIM_HIP_LIB") or os.path.join(CSRC, "libquadsim_hip.so")  # override: A/B builds
 SOURCES = [os.path.join(CSRC, "quadsim_hip.hip")]
-# every fragment of the one translation unit is a rebuild dependency
-HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp")) + [os.path.join(HERE, "..", "include", "quadsim.h")]
+# every fragment of the one translation unit is a rebuild dependency (dynplan_*.hpp belong to the second library)
+HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith("dynplan_")) + [os.path.join(HERE, "..", "include", "quadsim.h")]
+# the second library, libquadsim_dyn.so (include/quadsim_dyn.h; bound in dynplan.py): its own translation unit and code object
+DYN_LIB_PATH = os.environ.get("QUADSIM_DYN_LIB") or os.path.join(CSRC, "libquadsim_dyn.so")
+DYN_SOURCES = [os.path.join(CSRC, "dynplan.hip")]
+DYN_HEADERS = [os.path.join(CSRC, h) for h in ("dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp")] + [os.path.join(HERE, "..", "include", "quadsim_dyn.h")]
 
 QS_OK = 0
 KIND_V0, KIND_V2, KIND_V1, KIND_HOVER = 0, 1, 2, 3
@@ -84,11 +88,27 @@ def hipcc_path():
     raise QuadsimError("hipcc not found: cannot build libquadsim_hip.so")
 
 
+def _up_to_date(lib, deps):
+    return os.path.exists(lib) and all(os.path.getmtime(lib) >= os.path.getmtime(d) for d in deps)
+
+
+def build_dyn_library(force=False, verbose=False):
+    """libquadsim_dyn.so with the flags of the main library -> its path"""
+    if not force and _up_to_date(DYN_LIB_PATH, DYN_SOURCES + DYN_HEADERS):
+        return DYN_LIB_PATH
+    cmd = [hipcc_path(), "-std=c++20", "-O3", "-fno-slp-vectorize", "-ffp-contract=on", "--offload-arch=gfx950", "-fPIC", "-shared",
+           "-Wno-unused-result", *DYN_SOURCES, "-o", DYN_LIB_PATH]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return DYN_LIB_PATH
+
+
 def build_library(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU."""
+    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds both libraries, returns the main one's path."""
+    build_dyn_library(force, verbose)
     deps = SOURCES + HEADERS
-    if (not force and os.path.exists(LIB_PATH)
-            and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps)):
+    if not force and _up_to_date(LIB_PATH, deps):
         return LIB_PATH
     # -ffp-contract=on: a*b+c fuses only where one expression says so, so every kernel that inlines the same device
     # function computes the same bits (the serial and the role-split step kernel, the policy kernels' env step);

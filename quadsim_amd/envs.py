@@ -34,6 +34,7 @@ class _SingleDockingEnv:
         cfg.auto_reset = 0
         cfg.io_space = _lib.IO_HOST
         self._config_hook(cfg)
+        self.cfg = cfg
         self._h = C.c_void_p()
         _lib.check(self._lib.qs_create(C.byref(cfg), C.byref(self._h)), "qs_create")
         self._nominal_chaser = np.array([8, -50, 5, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0], dtype=np.float64)
