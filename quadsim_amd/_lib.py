@@ -28,22 +28,6 @@ ORDER_HOST, ORDER_STREAM = 0, 1
 SHOOT_REWARD, SHOOT_POSITION = 0, 1
 FLAG_DOCKED, FLAG_OVERLIMIT, FLAG_OVERTIME, FLAG_CHASER_LIMITED, FLAG_TARGET_LIMITED = 1, 2, 4, 8, 16
 
-EXPORTS = [
-    "qs_config_default", "qs_version", "qs_last_error", "qs_create", "qs_destroy", "qs_reset", "qs_step",
-    "qs_rollout", "qs_rollout_slab", "qs_rollout_stepwise", "qs_fill_random_actions", "qs_get_state", "qs_set_state", "qs_set_params", "qs_get_params",
-    "qs_set_init_state", "qs_get_init_state", "qs_obs_dim", "qs_get_step_counter", "qs_set_step_counter", "qs_set_stream", "qs_sync", "qs_timer_start", "qs_timer_stop",
-    "qs_drone_step", "qs_ctrl", "qs_rel_obs", "qs_transform", "qs_gae", "qs_swap_and_flatten", "qs_expert_action", "qs_policy_rollout", "qs_policy_rollout_fast", "qs_policy_rollout_fast_blob_bytes",
-    "qs_policy_forward", "qs_policy_forward_fast", "qs_policy_evaluate", "qs_policy_evaluate_fast",
-    "qs_runner_rollout", "qs_runner_rollout_fast", "qs_runner_rollout_fast_blob_bytes",
-    "qs_runner_rollout_net", "qs_runner_rollout_net_fast", "qs_runner_rollout_net_fast_blob_bytes",
-    "qs_step_ex", "qs_set_groups", "qs_group_count", "qs_group_range", "qs_group_stream", "qs_group_set_stream",
-    "qs_step_group", "qs_step_groups", "qs_groups_fork", "qs_groups_join",
-    "qs_swap_and_flatten_u8", "qs_gae_flatten", "qs_episode_stats", "qs_set_rollout_layout",
-    "qs_set_queue_mode", "qs_get_queue_mode", "qs_set_queue_ordering", "qs_get_queue_ordering",
-    "qs_expert_rollout", "qs_expert_evaluate", "qs_shooting_plan", "qs_mppi_plan",
-    "qs_shooting_plan_split", "qs_shooting_plan_splits", "qs_mppi_plan_split",
-]
-
 
 class QsConfig(C.Structure):
     _fields_ = [
@@ -75,6 +59,82 @@ class QsActorCriticNet(C.Structure):
         ("wt3", C.c_void_p), ("b3", C.c_void_p), ("wtv1", C.c_void_p), ("bv1", C.c_void_p),
         ("wtv2", C.c_void_p), ("bv2", C.c_void_p), ("wtv3", C.c_void_p), ("bv3", C.c_void_p), ("logstd", C.c_float * 4),
     ]
+
+
+vp, i64, u64, i32, f32 = C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_float
+# argument types of every entry point (all return int), the handle included: load() applies this table, EXPORTS is derived from
+# it, and tests/test_call_path_cpu.py compares it with the prototypes of include/quadsim.h
+SIGNATURES = {
+    "qs_config_default": [C.POINTER(QsConfig)],
+    "qs_version": [],
+    "qs_create": [C.POINTER(QsConfig), C.POINTER(vp)],
+    "qs_destroy": [vp],
+    "qs_reset": [vp, vp, vp],
+    "qs_step": [vp, vp, vp, vp, vp, vp, vp],
+    "qs_rollout": [vp, i64, vp, vp, vp, vp, vp],
+    "qs_rollout_stepwise": [vp, i64, vp, vp, vp, vp, vp],
+    "qs_rollout_slab": [vp, i64, vp, vp, vp],
+    "qs_fill_random_actions": [vp, i64, u64, vp],
+    "qs_get_state": [vp] + [vp] * 6,
+    "qs_set_state": [vp] + [vp] * 6,
+    "qs_set_params": [vp, vp, vp],
+    "qs_get_params": [vp, vp, vp],
+    "qs_set_init_state": [vp, vp, vp],
+    "qs_get_init_state": [vp, vp, vp],
+    "qs_obs_dim": [vp, C.POINTER(i32)],
+    "qs_get_step_counter": [vp, C.POINTER(u64)],
+    "qs_set_step_counter": [vp, u64],
+    "qs_set_stream": [vp, vp, i32],
+    "qs_sync": [vp],
+    "qs_timer_start": [vp],
+    "qs_timer_stop": [vp, C.POINTER(f32)],
+    "qs_drone_step": [vp, i64, vp, vp, vp, vp, vp],
+    "qs_ctrl": [vp, i64, i32, vp, vp, vp, f32, vp],
+    "qs_rel_obs": [vp, i64, vp, vp, vp],
+    "qs_transform": [vp, i32, i64, vp, vp],
+    "qs_gae": [vp, i64, i64, vp, vp, vp, vp, vp, f32, f32, vp, vp],
+    "qs_swap_and_flatten": [vp, i64, i64, i64, vp, vp],
+    "qs_expert_action": [vp, vp, f32, f32, vp],
+    "qs_expert_rollout": [vp, i64, vp, f32, f32] + [vp] * 6,
+    "qs_expert_evaluate": [vp, i32, i64, vp, f32, f32] + [vp] * 5,
+    "qs_shooting_plan": [vp, i32, i32, i32] + [vp] * 5,
+    "qs_mppi_plan": [vp, i32, i32, i32, i32, f32, f32, i32] + [vp] * 8,
+    "qs_shooting_plan_split": [vp, i32, i32, i32, i32] + [vp] * 5,
+    "qs_shooting_plan_splits": [vp, i32, C.POINTER(i32)],
+    "qs_mppi_plan_split": [vp, i32, i32, i32, i32, f32, f32, i32, i32] + [vp] * 8,
+    "qs_policy_rollout": [vp, i64] + [vp] * 11,
+    "qs_policy_rollout_fast": [vp, i64] + [vp] * 6,
+    "qs_policy_rollout_fast_blob_bytes": [],
+    "qs_policy_forward": [vp, i64] + [vp] * 8,
+    "qs_policy_forward_fast": [vp, i64, vp, vp, vp],
+    "qs_policy_evaluate": [vp, i32, i64] + [vp] * 11,
+    "qs_policy_evaluate_fast": [vp, i32, i64] + [vp] * 6,
+    "qs_runner_rollout": [vp, i64, C.POINTER(QsActorCritic)] + [vp] * 12,
+    "qs_runner_rollout_fast": [vp, i64, vp, C.POINTER(C.c_float), i32] + [vp] * 12,
+    "qs_runner_rollout_fast_blob_bytes": [],
+    "qs_runner_rollout_net": [vp, i64, C.POINTER(QsActorCriticNet)] + [vp] * 12,
+    "qs_runner_rollout_net_fast": [vp, i64, i32, vp, C.POINTER(C.c_float), i32] + [vp] * 12,
+    "qs_runner_rollout_net_fast_blob_bytes": [i32],
+    "qs_step_ex": [vp] * 8,
+    "qs_set_groups": [vp, i32, i32],
+    "qs_group_count": [vp, C.POINTER(i32)],
+    "qs_group_range": [vp, i32, C.POINTER(i64), C.POINTER(i64)],
+    "qs_group_stream": [vp, i32, C.POINTER(vp)],
+    "qs_group_set_stream": [vp, i32, vp],
+    "qs_step_group": [vp, i32] + [vp] * 7,
+    "qs_step_groups": [vp] * 8,
+    "qs_groups_fork": [vp],
+    "qs_groups_join": [vp],
+    "qs_swap_and_flatten_u8": [vp, i64, i64, vp, vp],
+    "qs_gae_flatten": [vp, i64, i64, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp],
+    "qs_episode_stats": [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp],
+    "qs_set_rollout_layout": [vp, i32],
+    "qs_set_queue_mode": [vp, i32],
+    "qs_get_queue_mode": [vp, C.POINTER(i32)],
+    "qs_set_queue_ordering": [vp, i32],
+    "qs_get_queue_ordering": [vp, C.POINTER(i32)],
+}
+EXPORTS = sorted(SIGNATURES) + ["qs_last_error"]
 
 
 class QuadsimError(RuntimeError):
@@ -140,78 +200,7 @@ def load():
     # runtimes end up in one process and device pointers / streams cannot be shared.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    vp, i64, u64, i32, f32 = C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_float
-    sig = {
-        "qs_config_default": [C.POINTER(QsConfig)],
-        "qs_version": [],
-        "qs_create": [C.POINTER(QsConfig), C.POINTER(vp)],
-        "qs_destroy": [vp],
-        "qs_reset": [vp, vp, vp],
-        "qs_step": [vp, vp, vp, vp, vp, vp, vp],
-        "qs_rollout": [vp, i64, vp, vp, vp, vp, vp],
-        "qs_rollout_stepwise": [vp, i64, vp, vp, vp, vp, vp],
-        "qs_rollout_slab": [vp, i64, vp, vp, vp],
-        "qs_fill_random_actions": [vp, i64, u64, vp],
-        "qs_get_state": [vp] + [vp] * 6,
-        "qs_set_state": [vp] + [vp] * 6,
-        "qs_set_params": [vp, vp, vp],
-        "qs_get_params": [vp, vp, vp],
-        "qs_set_init_state": [vp, vp, vp],
-        "qs_get_init_state": [vp, vp, vp],
-        "qs_obs_dim": [vp, C.POINTER(i32)],
-        "qs_get_step_counter": [vp, C.POINTER(u64)],
-        "qs_set_step_counter": [vp, u64],
-        "qs_set_stream": [vp, vp, i32],
-        "qs_sync": [vp],
-        "qs_timer_start": [vp],
-        "qs_timer_stop": [vp, C.POINTER(f32)],
-        "qs_drone_step": [vp, i64, vp, vp, vp, vp, vp],
-        "qs_ctrl": [vp, i64, i32, vp, vp, vp, f32, vp],
-        "qs_rel_obs": [vp, i64, vp, vp, vp],
-        "qs_transform": [vp, i32, i64, vp, vp],
-        "qs_gae": [vp, i64, i64, vp, vp, vp, vp, vp, f32, f32, vp, vp],
-        "qs_swap_and_flatten": [vp, i64, i64, i64, vp, vp],
-        "qs_expert_action": [vp, vp, f32, f32, vp],
-        "qs_expert_rollout": [vp, i64, vp, f32, f32] + [vp] * 6,
-        "qs_expert_evaluate": [vp, i32, i64, vp, f32, f32] + [vp] * 5,
-        "qs_shooting_plan": [vp, i32, i32, i32] + [vp] * 5,
-        "qs_mppi_plan": [vp, i32, i32, i32, i32, f32, f32, i32] + [vp] * 8,
-        "qs_shooting_plan_split": [vp, i32, i32, i32, i32] + [vp] * 5,
-        "qs_shooting_plan_splits": [vp, i32, C.POINTER(i32)],
-        "qs_mppi_plan_split": [vp, i32, i32, i32, i32, f32, f32, i32, i32] + [vp] * 8,
-        "qs_policy_rollout": [vp, i64] + [vp] * 11,
-        "qs_policy_rollout_fast": [vp, i64] + [vp] * 6,
-        "qs_policy_rollout_fast_blob_bytes": [],
-        "qs_policy_forward": [vp, i64] + [vp] * 8,
-        "qs_policy_forward_fast": [vp, i64, vp, vp, vp],
-        "qs_policy_evaluate": [vp, i32, i64] + [vp] * 11,
-        "qs_policy_evaluate_fast": [vp, i32, i64] + [vp] * 6,
-        "qs_runner_rollout": [vp, i64, C.POINTER(QsActorCritic)] + [vp] * 12,
-        "qs_runner_rollout_fast": [vp, i64, vp, C.POINTER(C.c_float), i32] + [vp] * 12,
-        "qs_runner_rollout_fast_blob_bytes": [],
-        "qs_runner_rollout_net": [vp, i64, C.POINTER(QsActorCriticNet)] + [vp] * 12,
-        "qs_runner_rollout_net_fast": [vp, i64, i32, vp, C.POINTER(C.c_float), i32] + [vp] * 12,
-        "qs_runner_rollout_net_fast_blob_bytes": [i32],
-        "qs_step_ex": [vp] * 8,
-        "qs_set_groups": [vp, i32, i32],
-        "qs_group_count": [vp, C.POINTER(i32)],
-        "qs_group_range": [vp, i32, C.POINTER(i64), C.POINTER(i64)],
-        "qs_group_stream": [vp, i32, C.POINTER(vp)],
-        "qs_group_set_stream": [vp, i32, vp],
-        "qs_step_group": [vp, i32] + [vp] * 7,
-        "qs_step_groups": [vp] * 8,
-        "qs_groups_fork": [vp],
-        "qs_groups_join": [vp],
-        "qs_swap_and_flatten_u8": [vp, i64, i64, vp, vp],
-        "qs_gae_flatten": [vp, i64, i64, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp],
-        "qs_episode_stats": [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp],
-        "qs_set_rollout_layout": [vp, i32],
-        "qs_set_queue_mode": [vp, i32],
-        "qs_get_queue_mode": [vp, C.POINTER(i32)],
-        "qs_set_queue_ordering": [vp, i32],
-        "qs_get_queue_ordering": [vp, C.POINTER(i32)],
-    }
-    for name, args in sig.items():
+    for name, args in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
@@ -225,6 +214,37 @@ def check(rc, what=""):
     if rc != QS_OK:
         msg = load().qs_last_error().decode("utf-8", "replace")
         raise QuadsimError("%s failed (%d): %s" % (what or "quadsim call", rc, msg))
+
+
+def as_arg(a):
+    """what an entry point receives for `a`: a torch tensor as its device pointer, a numpy array as its data pointer, None as
+    NULL; anything else (scalars, ctypes values, byref) as it is.  Pointers go as plain ints, which the argtypes of SIGNATURES
+    turn into void * (building a c_void_p for each costs 0.1 us, seven times per step); the caller keeps the array alive"""
+    if a is None:
+        return None
+    data_ptr = getattr(a, "data_ptr", None)
+    if data_ptr is not None:
+        return data_ptr()
+    ct = getattr(a, "ctypes", None)
+    return a if ct is None else ct.data
+
+
+def call(h, name, *args):
+    """the entry point `name` on the handle `h`, arguments through as_arg; QuadsimError unless it returns QS_OK.  Nothing is
+    ordered against any stream here: handles with a stream protocol call through VecDockingEnv._call"""
+    check(getattr(_lib or load(), name)(h, *map(as_arg, args)), name)
+
+
+def create(cfg):
+    """qs_create -> the new handle"""
+    h = C.c_void_p()
+    check(load().qs_create(C.byref(cfg), C.byref(h)), "qs_create")
+    return h
+
+
+def fast_blob_bytes(entry, *args):
+    """the size the library expects of the packed weight image of the split-bf16 entry point `entry` (a size, not a status)"""
+    return getattr(load(), entry + "_blob_bytes")(*args)
 
 
 def default_config():

@@ -30,7 +30,6 @@ def _context(device=0, integrator=_lib.INTEG_FROZEN, dt=0.02, mass=0.18, inertia
     key = (device, integrator, float(dt), float(mass), tuple(float(x) for x in inertia))
     h = _ctx.get(key)
     if h is None:
-        lib = _lib.load()
         cfg = _lib.default_config()
         cfg.num_envs = 1
         cfg.device = device
@@ -39,18 +38,12 @@ def _context(device=0, integrator=_lib.INTEG_FROZEN, dt=0.02, mass=0.18, inertia
         cfg.io_space = _lib.IO_HOST
         cfg.mass = mass
         cfg.inertia = (C.c_float * 3)(*inertia)
-        h = C.c_void_p()
-        _lib.check(lib.qs_create(C.byref(cfg), C.byref(h)), "qs_create")
-        _ctx[key] = h
+        h = _ctx[key] = _lib.create(cfg)
     return h
 
 
 def _f32(x, shape):
     return np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(shape))
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 def drone_step_batch(state, u_prev, u, par=None, dt=0.02, integrator="frozen", device=0):
@@ -63,7 +56,7 @@ def drone_step_batch(state, u_prev, u, par=None, dt=0.02, integrator="frozen", d
     par = None if par is None else _f32(par, (n, 4))
     lim = np.zeros(n, np.uint8)
     h = _context(device, _lib.INTEG_RK4 if integrator == "rk4" else _lib.INTEG_FROZEN, dt)
-    _lib.check(_lib.load().qs_drone_step(h, n, _p(state), _p(u_prev), _p(u), _p(par), _p(lim)), "qs_drone_step")
+    _lib.call(h, "qs_drone_step", n, state, u_prev, u, par, lim)
     return state, u_prev, lim.astype(bool)
 
 
@@ -75,8 +68,7 @@ def ctrl_batch(mode, state_des, state, state_last=None, mass=0.18, device=0):
     state = _f32(state, (n, 13))
     sl = None if state_last is None else _f32(state_last, (n, 13))
     u = np.zeros((n, 4), np.float32)
-    h = _context(device)
-    _lib.check(_lib.load().qs_ctrl(h, n, int(mode), _p(state_des), _p(state), _p(sl), C.c_float(mass), _p(u)), "qs_ctrl")
+    _lib.call(_context(device), "qs_ctrl", n, int(mode), state_des, state, sl, C.c_float(mass), u)
     return u, state_des
 
 
@@ -86,7 +78,7 @@ def rel_obs_batch(chaser, target, device=0):
     n = chaser.shape[0]
     target = _f32(target, (n, 13))
     obs = np.zeros((n, 12), np.float32)
-    _lib.check(_lib.load().qs_rel_obs(_context(device), n, _p(chaser), _p(target), _p(obs)), "qs_rel_obs")
+    _lib.call(_context(device), "qs_rel_obs", n, chaser, target, obs)
     return obs
 
 
@@ -99,7 +91,7 @@ def transform_batch(name, x, device=0):
     op, wi, wo = _TRANSFORM[name]
     x = _f32(x, (-1, wi))
     out = np.zeros((x.shape[0], wo), np.float32)
-    _lib.check(_lib.load().qs_transform(_context(device), op, x.shape[0], _p(x), _p(out)), "qs_transform")
+    _lib.call(_context(device), "qs_transform", op, x.shape[0], x, out)
     return out.reshape(-1, 3, 3) if name == "quat2rot" else out
 
 

@@ -271,7 +271,7 @@ class LearnedShootingMPC:
         import torch
         env = self.env
         k = C.c_uint64(0)
-        _lib.check(env._lib.qs_get_step_counter(env._h, C.byref(k)), "qs_get_step_counter")
+        env._call("qs_get_step_counter", C.byref(k))
         if self.single:
             import numpy as np
             obs = torch.as_tensor(np.asarray(env.rel_state, np.float32).reshape(1, OBS_DIM)).to(self.net.device)

@@ -5,8 +5,6 @@ host I/O: ``reset() -> ndarray(12,)``, ``step(a) -> (obs, reward, done, info)``;
 ``step`` never resets by itself (docking_env.py:104-231).  The attribute surface
 the reference scripts rely on is kept.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
@@ -18,14 +16,42 @@ class _ChaserView(Drone):
     """env.chaser / env.target: constants + get_* only (run_expert_policy.py:41, run_trained_docking_ppo2.py:45)"""
 
 
-class _SingleDockingEnv:
+class _HostHandle:
+    """a QS_IO_HOST handle of one env: numpy arrays in and out, every call complete when it returns -- no stream protocol"""
     metadata = {"render.modes": ["human"]}
+
+    def _create(self, cfg):
+        self._lib = _lib.load()
+        self._h = _lib.create(cfg)
+
+    def _call(self, name, *args):
+        _lib.call(self._h, name, *args)
+
+    def render(self, mode="human"):
+        return None
+
+    def seed(self, seed=None):
+        self.np_random = np.random.RandomState(seed)
+        return [seed]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.qs_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _SingleDockingEnv(_HostHandle):
     _kind = _lib.KIND_V0
     spec = None
     reward_range = (-float("inf"), float("inf"))
 
     def __init__(self, device=0, integrator="frozen"):
-        self._lib = _lib.load()
         cfg = _lib.default_config()
         cfg.kind = self._kind
         cfg.num_envs = 1
@@ -35,8 +61,7 @@ class _SingleDockingEnv:
         cfg.io_space = _lib.IO_HOST
         self._config_hook(cfg)
         self.cfg = cfg
-        self._h = C.c_void_p()
-        _lib.check(self._lib.qs_create(C.byref(cfg), C.byref(self._h)), "qs_create")
+        self._create(cfg)
         self._nominal_chaser = np.array([8, -50, 5, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0], dtype=np.float64)
         self.chaser = _ChaserView(device)
         self.target = _ChaserView(device)
@@ -64,8 +89,7 @@ class _SingleDockingEnv:
     def _pull_state(self):
         sc = np.zeros((1, 13), np.float32); st = np.zeros((1, 13), np.float32)
         ls = np.zeros(1, np.float32); t = np.zeros(1, np.float32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        _lib.check(self._lib.qs_get_state(self._h, p(sc), p(st), None, None, p(ls), p(t)), "qs_get_state")
+        self._call("qs_get_state", sc, st, None, None, ls, t)
         self.state_chaser = sc[0].astype(np.float64)
         self.state_target = st[0].astype(np.float64)
         self.last_shaping = float(ls[0])
@@ -81,10 +105,9 @@ class _SingleDockingEnv:
         if not np.array_equal(self.chaser_ini_state, self._nominal_chaser):
             sc = np.ascontiguousarray(self.chaser_ini_state[None], dtype=np.float32)
             st = np.ascontiguousarray(self.target_ini_state[None], dtype=np.float32)
-            _lib.check(self._lib.qs_set_init_state(self._h, sc.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p)),
-                       "qs_set_init_state")
+            self._call("qs_set_init_state", sc, st)
             self._nominal_chaser = self.chaser_ini_state.copy()
-        _lib.check(self._lib.qs_reset(self._h, None, obs.ctypes.data_as(C.c_void_p)), "qs_reset")
+        self._call("qs_reset", None, obs)
         self._pull_state()
         self.done = False
         self.t = 0.0
@@ -96,8 +119,7 @@ class _SingleDockingEnv:
         a = np.ascontiguousarray(np.asarray(action, dtype=np.float32).reshape(1, 4))
         obs = np.zeros((1, 12), np.float32); rew = np.zeros(1, np.float32)
         done = np.zeros(1, np.uint8); flags = np.zeros(1, np.uint8)
-        p = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
-        _lib.check(self._lib.qs_step(self._h, p(a), p(obs), p(rew), p(done), p(flags), None), "qs_step")
+        self._call("qs_step", a, obs, rew, done, flags, None)
         self.t += 1
         self._pull_state()
         self.rel_state = obs[0].astype(np.float64)
@@ -128,26 +150,6 @@ class _SingleDockingEnv:
                                   mpc.MPPI_DEFAULT_SIGMA if sigma is None else sigma, nominal, shift, noise, splits, return_scores,
                                   return_trace, return_candidates)
 
-    def render(self, mode="human"):
-        return None
-
-    def close(self):
-        if self._h:
-            self._lib.qs_destroy(self._h)
-            self._h = C.c_void_p()
-        return None
-
-    def seed(self, seed=None):
-        self.np_random = np.random.RandomState(seed)
-        return [seed]
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 class DockingEnv(_SingleDockingEnv):
     """docking-v0"""
     _kind = _lib.KIND_V0
@@ -167,8 +169,7 @@ class ImitatingDockingEnv(_SingleDockingEnv):
         self._seed0 = seed
         super().__init__(device, integrator)
         sc = np.zeros((1, 13), np.float32); st = np.zeros((1, 13), np.float32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        _lib.check(self._lib.qs_get_init_state(self._h, p(sc), p(st)), "qs_get_init_state")
+        self._call("qs_get_init_state", sc, st)
         self.chaser_ini_state = sc[0].astype(np.float64)
         self._nominal_chaser = self.chaser_ini_state.copy()
 
@@ -176,24 +177,21 @@ class ImitatingDockingEnv(_SingleDockingEnv):
         cfg.seed = int(self._seed0)
 
 
-class HoveringEnv:
+class HoveringEnv(_HostHandle):
     """hovering-v0 (hovering_env.py:10-92): one drone, obs = raw state [13], action in [0,1]^4, step never resets."""
-    metadata = {"render.modes": ["human"]}
 
     def __init__(self, device=0, integrator="frozen", seed=0):
         from .spaces import hovering_spaces
-        self._lib = _lib.load()
         cfg = _lib.default_config()
         cfg.kind, cfg.num_envs, cfg.device, cfg.auto_reset, cfg.io_space = _lib.KIND_HOVER, 1, device, 0, _lib.IO_HOST
         cfg.integrator = _lib.INTEG_RK4 if integrator == "rk4" else _lib.INTEG_FROZEN
         cfg.seed = int(seed)
-        self._h = C.c_void_p()
-        _lib.check(self._lib.qs_create(C.byref(cfg), C.byref(self._h)), "qs_create")
+        self._create(cfg)
         self.drone = _ChaserView(device)
         self.observation_space, self.action_space = hovering_spaces()
         self.action_max = np.ones(4) * self.drone.mass * self.drone.gravity
         ini = np.zeros((1, 13), np.float32)
-        _lib.check(self._lib.qs_get_init_state(self._h, ini.ctypes.data_as(C.c_void_p), None), "qs_get_init_state")
+        self._call("qs_get_init_state", ini, None)
         self.ini_state = ini[0].astype(np.float64)
         self.state_des = np.array([0, 0, 5.0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0])
         self.state = np.zeros(13)
@@ -201,38 +199,18 @@ class HoveringEnv:
 
     def reset(self):
         ini = np.ascontiguousarray(self.ini_state[None], dtype=np.float32)      # honours a caller-set ini_state
-        _lib.check(self._lib.qs_set_init_state(self._h, ini.ctypes.data_as(C.c_void_p), None), "qs_set_init_state")
+        self._call("qs_set_init_state", ini, None)
         obs = np.zeros((1, 13), np.float32)
-        _lib.check(self._lib.qs_reset(self._h, None, obs.ctypes.data_as(C.c_void_p)), "qs_reset")
+        self._call("qs_reset", None, obs)
         self.state = obs[0].astype(np.float64)
         return self.state
 
     def step(self, action):
         a = np.ascontiguousarray(np.asarray(action, dtype=np.float32).reshape(1, 4))
         obs = np.zeros((1, 13), np.float32); rew = np.zeros(1, np.float32); done = np.zeros(1, np.uint8)
-        p = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
-        _lib.check(self._lib.qs_step(self._h, p(a), p(obs), p(rew), p(done), None, None), "qs_step")
+        self._call("qs_step", a, obs, rew, done, None, None)
         self.state = obs[0].astype(np.float64)
         return self.state, float(rew[0]), bool(done[0]), {}
-
-    def render(self, mode="human"):
-        return None
-
-    def seed(self, seed=None):
-        self.np_random = np.random.RandomState(seed)
-        return [seed]
-
-    def close(self):
-        if self._h:
-            self._lib.qs_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def register_gym_ids():
     """register 'docking-v0' / 'docking-v2' with gym when gym is importable

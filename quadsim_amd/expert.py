@@ -9,8 +9,6 @@ The expert runs in the loop on the device: ``PIDExpert.rollout`` is T steps of `
 launch (qs_expert_rollout), ``PIDExpert.evaluate`` K complete episodes per env, read-only (qs_expert_evaluate); both give
 the per-step loop's results bit for bit.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
@@ -30,9 +28,7 @@ class PIDExpert:
 
     def act(self):
         """expert actions [N,4] for the envs' current states (a fresh tensor view is overwritten by the next call)"""
-        e = self.env
-        _lib.check(e._lib.qs_expert_action(e._h, C.c_void_p(self.state_des.data_ptr()), self.kp, self.kd,
-                                           C.c_void_p(self._actions.data_ptr())), "qs_expert_action")
+        self.env._call("qs_expert_action", self.state_des, self.kp, self.kd, self._actions)
         return self._actions
 
     def rollout(self, T, flags=False, env_major=False):
@@ -51,15 +47,10 @@ class PIDExpert:
         if flags:
             out["flags"] = torch.empty((tt, n), dtype=torch.uint8, **kw)
         out["last_obs"] = torch.empty((n, 12), dtype=torch.float32, **kw)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-        e._use_current_stream()
-        e._inputs_ready()
-        _lib.check(e._lib.qs_set_rollout_layout(e._h, 1 if env_major else 0), "qs_set_rollout_layout")
-        _lib.check(e._lib.qs_expert_rollout(e._h, T, p(self.state_des), self.kp, self.kd, p(out["obs"]), p(out["actions"]),
-                                            p(out["rewards"]), p(out["dones"]), p(out.get("flags")), p(out["last_obs"])),
-                   "qs_expert_rollout")
+        e._call("qs_set_rollout_layout", 1 if env_major else 0)
+        e._call("qs_expert_rollout", T, self.state_des, self.kp, self.kd, out["obs"], out["actions"], out["rewards"], out["dones"],
+                out.get("flags"), out["last_obs"])
         e._nstep += T
-        e._outputs_ready()
         out["dones"] = out["dones"].view(torch.bool)
         return out
 
@@ -67,23 +58,12 @@ class PIDExpert:
         """`n_episodes` complete expert episodes for every env from its CURRENT state in ONE launch (qs_expert_evaluate), or
         `max_steps` steps per env at most (default n_episodes x 600: the env's time-out bounds every episode).  The env and
         ``self.state_des`` are left untouched.  Returns an EvalResult, as evaluate_policy_episodes does."""
-        import torch
         from .policy import EPISODE_STEPS, EvalResult
         e, K = self.env, int(n_episodes)      # K < 1 and max_steps < 1 are refused by the library (QuadsimError)
         max_steps = K * EPISODE_STEPS if max_steps is None else int(max_steps)
-        n, dev, kk = e.num_envs, e.device, max(K, 0)
-        ret = torch.full((kk, n), float("nan"), dtype=torch.float64, device=dev)     # slots of unfinished episodes: NaN / 0
-        length = torch.zeros((kk, n), dtype=torch.int32, device=dev)
-        flags = torch.zeros((kk, n), dtype=torch.uint8, device=dev)
-        docked = torch.zeros((kk, n), dtype=torch.int32, device=dev)
-        finished = torch.empty((n,), dtype=torch.int32, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr())       # noqa: E731
-        e._use_current_stream()
-        e._inputs_ready()
-        _lib.check(e._lib.qs_expert_evaluate(e._h, K, max_steps, p(self.state_des), self.kp, self.kd, p(ret), p(length), p(flags),
-                                             p(docked), p(finished)), "qs_expert_evaluate")
-        e._outputs_ready()
-        return EvalResult(ret, length, flags, docked, finished)
+        res = EvalResult.empty(K, e.num_envs, e.device)
+        e._call("qs_expert_evaluate", K, max_steps, self.state_des, self.kp, self.kd, *res.tensors())
+        return res
 
 
 class IncompleteEpisodes(RuntimeError):

@@ -39,15 +39,6 @@ def _check_common(horizon, paths, objective, max_horizon, max_paths):
     return horizon, paths, OBJECTIVES[objective]
 
 
-def _call(env, fn_name, *args):
-    """one planner entry point on the handle of `env` (tensors as their device pointers, None as NULL), in the env's stream"""
-    args = [C.c_void_p(a.data_ptr()) if hasattr(a, "data_ptr") else a for a in args]
-    env._use_current_stream()
-    env._inputs_ready()
-    _lib.check(getattr(env._lib, fn_name)(env._h, *args), fn_name)
-    env._outputs_ready()
-
-
 def _closed_loop(env, act, steps, after_step=None):
     """`steps` times ``env.step(act())`` -> (rewards [steps,N] float32, dones [steps,N] bool); after_step(done) follows each step"""
     import torch
@@ -95,7 +86,7 @@ def plan_splits(env, paths):
     (qs_shooting_plan_splits; `env` a VecDockingEnv or a single-env shim)"""
     _, paths, _, _ = check_plan_args(1, paths, "reward")
     s = C.c_int32(0)
-    _lib.check(env._lib.qs_shooting_plan_splits(env._h, paths, C.byref(s)), "qs_shooting_plan_splits")
+    env._call("qs_shooting_plan_splits", paths, C.byref(s))
     return int(s.value)
 
 
@@ -111,11 +102,6 @@ def _numpy_arrays():
     """the array factory of the host path, as _torch_arrays: zeroed numpy arrays"""
     import numpy as np
     return np.zeros, np.float32, np.float64, np.int32
-
-
-def _call_host(env, fn, scalars, bufs):
-    """the planner entry point `fn` on the QS_IO_HOST handle of `env` (numpy arrays as their addresses, None as NULL)"""
-    _lib.check(fn(env._h, *scalars, *[None if a is None else a.ctypes.data_as(C.c_void_p) for a in bufs]), fn.__name__)
 
 
 def _host_result(out, **as_python):
@@ -146,9 +132,9 @@ def shooting_plan(env, horizon=20, paths=200, objective="reward", return_scores=
     horizon, paths, obj, splits = check_plan_args(horizon, paths, objective, splits)
     out, bufs = _shooting_buffers(_torch_arrays(env), env.num_envs, horizon, paths, return_scores, return_sequence)
     if splits is None:
-        _call(env, "qs_shooting_plan", horizon, paths, obj, *bufs)
+        env._call("qs_shooting_plan", horizon, paths, obj, *bufs)
     else:
-        _call(env, "qs_shooting_plan_split", horizon, paths, obj, splits, *bufs)
+        env._call("qs_shooting_plan_split", horizon, paths, obj, splits, *bufs)
     return out
 
 
@@ -160,7 +146,7 @@ def shooting_plan_host(env, horizon=20, paths=200, objective="reward", splits="a
     takes host handles, and with one part it launches the kernel of qs_shooting_plan."""
     horizon, paths, obj, splits = check_plan_args(horizon, paths, objective, splits)
     out, bufs = _shooting_buffers(_numpy_arrays(), 1, horizon, paths, return_scores, return_sequence)
-    _call_host(env, env._lib.qs_shooting_plan_split, (horizon, paths, obj, 1 if splits is None else splits), bufs)
+    env._call("qs_shooting_plan_split", horizon, paths, obj, 1 if splits is None else splits, *bufs)
     return _host_result(out, best_index=int)
 
 
@@ -263,9 +249,9 @@ def mppi_plan(env, horizon=20, paths=200, iterations=2, objective="reward", lam=
     out, bufs = _mppi_buffers(_torch_arrays(env), n, horizon, paths, iterations, given(nominal, (n, horizon, 4), "nominal"),
                               given(noise, (iterations, paths, horizon, 4), "noise"), return_scores, return_trace, return_candidates)
     if splits is None:
-        _call(env, "qs_mppi_plan", horizon, paths, iterations, obj, lam, sigma, shift, *bufs)
+        env._call("qs_mppi_plan", horizon, paths, iterations, obj, lam, sigma, shift, *bufs)
     else:
-        _call(env, "qs_mppi_plan_split", horizon, paths, iterations, obj, lam, sigma, shift, splits, *bufs)
+        env._call("qs_mppi_plan_split", horizon, paths, iterations, obj, lam, sigma, shift, splits, *bufs)
     return out
 
 
@@ -290,7 +276,7 @@ def mppi_plan_host(env, horizon=20, paths=200, iterations=2, objective="reward",
         return a
     out, bufs = _mppi_buffers(_numpy_arrays(), 1, horizon, paths, iterations, given(nominal, (horizon, 4), "nominal"),
                               given(noise, (iterations, paths, horizon, 4), "noise"), return_scores, return_trace, return_candidates)
-    _call_host(env, env._lib.qs_mppi_plan_split, (horizon, paths, iterations, obj, lam, sigma, shift, splits), bufs)
+    env._call("qs_mppi_plan_split", horizon, paths, iterations, obj, lam, sigma, shift, splits, *bufs)
     return _host_result(out)
 
 

@@ -39,14 +39,27 @@ class MlpPolicy:
         h = t.relu(t.addmm(self.b1, h, self.w1))
         return t.clamp(t.addmm(self.b2, h, self.w2), -1.0, 1.0)
 
+    def transposed_weights(self):
+        """[W0^T, b0, W1^T, b1, W2^T, b2], contiguous: the weight arguments of every exact-f32 actor kernel (built once)"""
+        if not hasattr(self, "_wt"):
+            self._wt = [self.w0.t().contiguous(), self.b0.contiguous(), self.w1.t().contiguous(),
+                        self.b1.contiguous(), self.w2.t().contiguous(), self.b2.contiguous()]
+        return self._wt
+
+    def fast_blob(self):
+        """pack_fast_weights as a device tensor: the weight argument of every split-bf16 actor kernel (built once)"""
+        if not hasattr(self, "_blob"):
+            from . import _lib
+            blob = pack_fast_weights(self)
+            assert blob.size == _lib.fast_blob_bytes("qs_policy_rollout_fast")
+            self._blob = self.torch.as_tensor(blob.copy()).to(self.w0.device)
+        return self._blob
 
     def predict_hip(self, env, obs, precision="f32", out=None):
         """the same actor as ONE hand-written kernel on the matrix cores (qs_policy_forward: exact-f32 MFMA; "bf16x3":
         split-bf16 operands, ~1e-5 on an action), launched on `env`'s stream: obs [n,12] float32 device tensor -> actions
         [n,4].  65 536 rows: ~22 us against ~80 us for the three library GEMMs of predict()."""
-        import ctypes as C
         import torch
-        from . import _lib
         if (not isinstance(obs, torch.Tensor) or obs.dtype != torch.float32 or obs.dim() != 2 or obs.shape[1] != 12
                 or obs.device != env.device):
             raise ValueError("predict_hip: obs must be a float32 [n, 12] tensor on %s" % (env.device,))
@@ -55,19 +68,10 @@ class MlpPolicy:
         if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (n, 4) or not out.is_contiguous() or out.device != obs.device):
             raise ValueError("predict_hip: out must be a contiguous float32 [n, 4] tensor on the same device")
         acts = out if out is not None else torch.empty((n, 4), dtype=torch.float32, device=obs.device)
-        p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
-        env._use_current_stream()
         if precision == "bf16x3":
-            if not hasattr(self, "_blob"):
-                blob = pack_fast_weights(self)
-                assert blob.size == env._lib.qs_policy_rollout_fast_blob_bytes()
-                self._blob = torch.as_tensor(blob.copy()).to(obs.device)
-            _lib.check(env._lib.qs_policy_forward_fast(env._h, n, p(self._blob), p(obs), p(acts)), "qs_policy_forward_fast")
+            env._call("qs_policy_forward_fast", n, self.fast_blob(), obs, acts)
         elif precision == "f32":
-            if not hasattr(self, "_wt"):
-                self._wt = [self.w0.t().contiguous(), self.b0.contiguous(), self.w1.t().contiguous(),
-                            self.b1.contiguous(), self.w2.t().contiguous(), self.b2.contiguous()]
-            _lib.check(env._lib.qs_policy_forward(env._h, n, *[p(w) for w in self._wt], p(obs), p(acts)), "qs_policy_forward")
+            env._call("qs_policy_forward", n, *self.transposed_weights(), obs, acts)
         else:
             raise ValueError("precision must be 'f32' or 'bf16x3'")
         return acts
@@ -121,30 +125,17 @@ def fused_policy_rollout(env, policy, T, want_actions=True, precision="f32"):
     precision "f32": qs_policy_rollout, exact-float32 MFMA (an ordinary float32 network evaluation);
     precision "bf16x3": qs_policy_rollout_fast, split-bf16 operands on the 16x faster bf16 matrix rate, ~1e-5 error
     on the actions.  Returns (obs [T,N,12], reward [T,N], done [T,N] u8, flags [T,N] u8, actions [T,N,4] or None)."""
-    import ctypes as C
     import torch
-    from . import _lib
-    if not hasattr(policy, "_wt"):
-        policy._wt = [policy.w0.t().contiguous(), policy.b0.contiguous(), policy.w1.t().contiguous(),
-                      policy.b1.contiguous(), policy.w2.t().contiguous(), policy.b2.contiguous()]
     n, dev = env.num_envs, env.device
     obs = torch.empty((T, n, 12), dtype=torch.float32, device=dev)
     rew = torch.empty((T, n), dtype=torch.float32, device=dev)
     done = torch.empty((T, n), dtype=torch.uint8, device=dev)
     flags = torch.empty((T, n), dtype=torch.uint8, device=dev)
     acts = torch.empty((T, n, 4), dtype=torch.float32, device=dev) if want_actions else None
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-    env._use_current_stream()
     if precision == "bf16x3":
-        if not hasattr(policy, "_blob"):
-            blob = pack_fast_weights(policy)
-            assert blob.size == env._lib.qs_policy_rollout_fast_blob_bytes()
-            policy._blob = torch.as_tensor(blob.copy()).to(dev)
-        _lib.check(env._lib.qs_policy_rollout_fast(env._h, T, p(policy._blob), p(obs), p(rew), p(done), p(flags), p(acts)),
-                   "qs_policy_rollout_fast")
+        env._call("qs_policy_rollout_fast", T, policy.fast_blob(), obs, rew, done, flags, acts)
     elif precision == "f32":
-        _lib.check(env._lib.qs_policy_rollout(env._h, T, *[p(w) for w in policy._wt], p(obs), p(rew), p(done), p(flags),
-                                              p(acts)), "qs_policy_rollout")
+        env._call("qs_policy_rollout", T, *policy.transposed_weights(), obs, rew, done, flags, acts)
     else:
         raise ValueError("precision must be 'f32' or 'bf16x3'")
     return obs, rew, done, flags, acts
@@ -194,6 +185,20 @@ class EvalResult:
     def __init__(self, returns, lengths, flags, docked_steps, finished):
         self.returns, self.lengths, self.flags, self.docked_steps, self.finished = returns, lengths, flags, docked_steps, finished
 
+    @classmethod
+    def empty(cls, K, n, device):
+        """the result of K episodes of n envs before the evaluation kernel has run: the slots of unfinished episodes stay as
+        they are here (returns NaN, the rest 0)"""
+        import torch
+        kk = max(int(K), 0)          # K < 1 is refused by the library (QuadsimError)
+        return cls(torch.full((kk, n), float("nan"), dtype=torch.float64, device=device),
+                   torch.zeros((kk, n), dtype=torch.int32, device=device), torch.zeros((kk, n), dtype=torch.uint8, device=device),
+                   torch.zeros((kk, n), dtype=torch.int32, device=device), torch.empty((n,), dtype=torch.int32, device=device))
+
+    def tensors(self):
+        """(returns, lengths, flags, docked_steps, finished): the output arguments of the evaluation entry points, in order"""
+        return self.returns, self.lengths, self.flags, self.docked_steps, self.finished
+
     @property
     def episodes_per_env(self):
         return int(self.returns.shape[0])
@@ -230,7 +235,7 @@ class EvalResult:
         return float(((self._sel(self.flags) & FLAG_OVERLIMIT) != 0).double().mean().item())
 
     def numpy(self):
-        return {k: getattr(self, k).cpu().numpy() for k in ("returns", "lengths", "flags", "docked_steps", "finished")}
+        return {k: t.cpu().numpy() for k, t in zip(("returns", "lengths", "flags", "docked_steps", "finished"), self.tensors())}
 
 
 def evaluate_policy_episodes(policy, env, episodes_per_env=1, precision="f32", max_steps=None):
@@ -241,39 +246,17 @@ def evaluate_policy_episodes(policy, env, episodes_per_env=1, precision="f32", m
     ``obs -> policy.predict_hip(env, obs, precision) -> env.step`` from the same handle -- which the call leaves untouched (state,
     parameters, step counter): every evaluation of a handle sees the same starts.  max_steps (default K x 600: the env's
     time-out bounds every episode) caps the steps per env.  Returns an EvalResult of device tensors, on env's stream."""
-    import ctypes as C
-    import torch
-    from . import _lib
     K = int(episodes_per_env)          # K < 1 and max_steps < 1 are refused by the library (QuadsimError)
     max_steps = K * EPISODE_STEPS if max_steps is None else int(max_steps)
     actor = _actor_of(policy)
     if precision not in ("f32", "bf16x3"):
         raise ValueError("precision must be 'f32' or 'bf16x3'")
-    n, dev = env.num_envs, env.device
-    env._use_current_stream()
-    # weight images cached on the actor, as fused_policy_rollout / predict_hip do
-    if precision == "bf16x3" and not hasattr(actor, "_blob"):
-        blob = pack_fast_weights(actor)
-        assert blob.size == env._lib.qs_policy_rollout_fast_blob_bytes()
-        actor._blob = torch.as_tensor(blob.copy()).to(dev)
-    if precision == "f32" and not hasattr(actor, "_wt"):
-        actor._wt = [actor.w0.t().contiguous(), actor.b0.contiguous(), actor.w1.t().contiguous(),
-                     actor.b1.contiguous(), actor.w2.t().contiguous(), actor.b2.contiguous()]
-    kk = max(K, 0)
-    ret = torch.full((kk, n), float("nan"), dtype=torch.float64, device=dev)     # slots of unfinished episodes: NaN / 0
-    length = torch.zeros((kk, n), dtype=torch.int32, device=dev)
-    flags = torch.zeros((kk, n), dtype=torch.uint8, device=dev)
-    docked = torch.zeros((kk, n), dtype=torch.int32, device=dev)
-    finished = torch.empty((n,), dtype=torch.int32, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr())       # noqa: E731
-    outs = (p(ret), p(length), p(flags), p(docked), p(finished))
-    env._inputs_ready()
+    res = EvalResult.empty(K, env.num_envs, env.device)
     if precision == "bf16x3":
-        _lib.check(env._lib.qs_policy_evaluate_fast(env._h, K, max_steps, p(actor._blob), *outs), "qs_policy_evaluate_fast")
+        env._call("qs_policy_evaluate_fast", K, max_steps, actor.fast_blob(), *res.tensors())
     else:
-        _lib.check(env._lib.qs_policy_evaluate(env._h, K, max_steps, *[p(w) for w in actor._wt], *outs), "qs_policy_evaluate")
-    env._outputs_ready()
-    return EvalResult(ret, length, flags, docked, finished)
+        env._call("qs_policy_evaluate", K, max_steps, *actor.transposed_weights(), *res.tensors())
+    return res
 
 
 def episodes_for(n_eval_episodes, num_envs):

@@ -2,14 +2,7 @@
 either side of ``env.step`` -- GAE(lambda) (rl_baselines/ppo2/ppo2.py:507-520), ``swap_and_flatten``
 (:531-539) and the episode accounting behind ``ep_infos`` (:486-489) -- on the [T,N,.] tensors a roll-out leaves
 in HBM.  Same names and argument meaning as the reference.  Every launch goes to the stream torch considers
-current (the env follows it), so the torch temporaries made here and the kernels that read them stay ordered."""
-import ctypes as C
-
-from . import _lib
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+current (env._call follows it), so the torch temporaries made here and the kernels that read them stay ordered."""
 
 
 def _f32(env, x):
@@ -29,15 +22,11 @@ def compute_gae(env, rewards, values, dones, last_values, last_dones, gamma=0.99
     import torch
     T, n = rewards.shape
     dev = env.device
-    env._use_current_stream()
     rewards, values, last_values = _f32(env, rewards), _f32(env, values), _f32(env, last_values)
     dones, last_dones = _u8(env, dones), _u8(env, last_dones)
     advs = torch.empty((T, n), dtype=torch.float32, device=dev)
     rets = torch.empty((T, n), dtype=torch.float32, device=dev)
-    env._inputs_ready()
-    _lib.check(env._lib.qs_gae(env._h, T, n, _ptr(rewards), _ptr(values), _ptr(dones), _ptr(last_values),
-                               _ptr(last_dones), float(gamma), float(lam), _ptr(advs), _ptr(rets)), "qs_gae")
-    env._outputs_ready()
+    env._call("qs_gae", T, n, rewards, values, dones, last_values, last_dones, float(gamma), float(lam), advs, rets)
     return advs, rets
 
 
@@ -49,19 +38,14 @@ def swap_and_flatten(env, arr):
     d = 1
     for k in arr.shape[2:]:
         d *= int(k)
-    env._use_current_stream()
     if arr.dtype in (torch.uint8, torch.bool) and d == 1:
         x = arr.to(device=env.device).contiguous()
         out = torch.empty((n * T,) + tuple(arr.shape[2:]), dtype=x.dtype, device=env.device)
-        env._inputs_ready()
-        _lib.check(env._lib.qs_swap_and_flatten_u8(env._h, T, n, _ptr(x), _ptr(out)), "qs_swap_and_flatten_u8")
-        env._outputs_ready()
+        env._call("qs_swap_and_flatten_u8", T, n, x, out)
         return out
     x = _f32(env, arr)
     out = torch.empty((n * T,) + tuple(arr.shape[2:]), dtype=torch.float32, device=env.device)
-    env._inputs_ready()
-    _lib.check(env._lib.qs_swap_and_flatten(env._h, T, n, d, _ptr(x), _ptr(out)), "qs_swap_and_flatten")
-    env._outputs_ready()
+    env._call("qs_swap_and_flatten", T, n, d, x, out)
     return out
 
 
@@ -72,7 +56,6 @@ def gae_and_flatten(env, rewards, values, neglogp, dones, last_values, last_done
     import torch
     T, n = rewards.shape
     dev = env.device
-    env._use_current_stream()
     rewards, values, last_values = _f32(env, rewards), _f32(env, values), _f32(env, last_values)
     neglogp = _f32(env, neglogp) if neglogp is not None else None
     dones, last_dones = _u8(env, dones), _u8(env, last_dones)
@@ -81,12 +64,8 @@ def gae_and_flatten(env, rewards, values, neglogp, dones, last_values, last_done
            "masks": mk(torch.uint8)}
     advs = torch.empty((T, n), dtype=torch.float32, device=dev) if want_advs else None
     rets = torch.empty((T, n), dtype=torch.float32, device=dev) if want_advs else None
-    env._inputs_ready()
-    _lib.check(env._lib.qs_gae_flatten(env._h, T, n, _ptr(rewards), _ptr(values), _ptr(neglogp), _ptr(dones),
-                                       _ptr(last_values), _ptr(last_dones), float(gamma), float(lam),
-                                       _ptr(out["returns"]), _ptr(out["values"]), _ptr(out["neglogp"]), _ptr(out["rewards"]),
-                                       _ptr(out["masks"]), _ptr(advs), _ptr(rets)), "qs_gae_flatten")
-    env._outputs_ready()
+    env._call("qs_gae_flatten", T, n, rewards, values, neglogp, dones, last_values, last_dones, float(gamma), float(lam),
+              out["returns"], out["values"], out["neglogp"], out["rewards"], out["masks"], advs, rets)
     out["masks"] = out["masks"].view(torch.bool)
     out["advs"], out["returns_tm"] = advs, rets
     return out
@@ -114,7 +93,6 @@ class EpisodeTracker:
         T, n = rewards.shape
         if n != env.num_envs:                          # ep_ret / ep_len hold num_envs carries: the kernel walks n of them
             raise ValueError("EpisodeTracker.update: rewards has %d envs, the tracker's env has %d" % (n, env.num_envs))
-        env._use_current_stream()
         rewards, dones, last_dones = _f32(env, rewards), _u8(env, dones), _u8(env, last_dones)
         cap = T * n                                   # an episode is at least one step long: cannot overflow
         if self._bufs is None or self._bufs[0].numel() < cap:
@@ -122,11 +100,7 @@ class EpisodeTracker:
                           torch.empty((cap,), dtype=torch.float32, device=env.device),
                           torch.empty((cap,), dtype=torch.int32, device=env.device))
         key, ret, ln = self._bufs
-        env._inputs_ready()
-        _lib.check(env._lib.qs_episode_stats(env._h, T, n, _ptr(rewards), _ptr(dones), _ptr(last_dones), _ptr(self.ep_ret),
-                                             _ptr(self.ep_len), _ptr(self._count), cap, _ptr(key), _ptr(ret), _ptr(ln)),
-                   "qs_episode_stats")
-        env._outputs_ready()
+        env._call("qs_episode_stats", T, n, rewards, dones, last_dones, self.ep_ret, self.ep_len, self._count, cap, key, ret, ln)
         self._n = None
         return self
 

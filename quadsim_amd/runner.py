@@ -36,7 +36,7 @@ class ActorCriticPolicy:
         self.logstd = torch.as_tensor(self.logstd_host).to(device)
         self.squash = bool(squash)
         self.initial_state = None
-        self._wt = None
+        self._wt = self._ac_blob = None
 
     @classmethod
     def from_npz(cls, path, device="cuda", squash=False):
@@ -78,37 +78,30 @@ class ActorCriticPolicy:
 
     # -- device image for the fused kernel --------------------------------------------------------------------------
     def c_struct(self):
-        """QsActorCritic (shared trunk) or QsActorCriticNet (towers) over transposed device copies of the weights"""
-        if self.towers:
-            return self._c_struct_net()
-        if self._wt is None:
-            tr = lambda w: w.t().contiguous()                                                  # noqa: E731
-            self._wt = [tr(self.w0), self.b0.contiguous(), tr(self.w1), self.b1.contiguous(), tr(self.w2),
-                        self.b2.contiguous(), tr(self.wv1), self.bv1.contiguous(), tr(self.wv2), self.bv2.contiguous()]
-        s = _lib.QsActorCritic()
-        s.struct_size = C.sizeof(_lib.QsActorCritic)
+        """QsActorCritic (shared trunk) or QsActorCriticNet (towers) over transposed device copies of the weights; the towers'
+        struct has the value tower's own first layer (wtv1, bv1) and a layout field on top"""
+        vf0 = (("wtv1", self.wv0), ("bv1", self.bv0)) if self.towers else ()
+        fields = (("wt1", self.w0), ("b1", self.b0), ("wt2", self.w1), ("b2", self.b1), ("wt3", self.w2), ("b3", self.b2), *vf0,
+                  ("wtv2", self.wv1), ("bv2", self.bv1), ("wtv3", self.wv2), ("bv3", self.bv2))
+        if self._wt is None:                           # weights are stored [in][out], the kernels read [out][in]
+            self._wt = [(w.t() if name.startswith("w") else w).contiguous() for name, w in fields]
+        s = _lib.QsActorCriticNet(layout=_lib.NET_TOWERS) if self.towers else _lib.QsActorCritic()
+        s.struct_size = C.sizeof(s)
         s.squash = 1 if self.squash else 0
-        for name, w in zip(("wt1", "b1", "wt2", "b2", "wt3", "b3", "wtv2", "bv2", "wtv3", "bv3"), self._wt):
-            setattr(s, name, w.data_ptr())
+        for (name, _), w in zip(fields, self._wt):
+            setattr(s, name, _lib.as_arg(w))
         for i in range(4):
             s.logstd[i] = float(self.logstd_host[i])
         return s
 
-    def _c_struct_net(self):
-        if self._wt is None:
-            tr = lambda w: w.t().contiguous()                                                  # noqa: E731
-            self._wt = [tr(self.w0), self.b0.contiguous(), tr(self.w1), self.b1.contiguous(), tr(self.w2),
-                        self.b2.contiguous(), tr(self.wv0), self.bv0.contiguous(), tr(self.wv1), self.bv1.contiguous(),
-                        tr(self.wv2), self.bv2.contiguous()]
-        s = _lib.QsActorCriticNet()
-        s.struct_size = C.sizeof(_lib.QsActorCriticNet)
-        s.squash = 1 if self.squash else 0
-        s.layout = _lib.NET_TOWERS
-        for name, w in zip(("wt1", "b1", "wt2", "b2", "wt3", "b3", "wtv1", "bv1", "wtv2", "bv2", "wtv3", "bv3"), self._wt):
-            setattr(s, name, w.data_ptr())
-        for i in range(4):
-            s.logstd[i] = float(self.logstd_host[i])
-        return s
+    def fast_blob(self):
+        """pack_fast_actor_critic as a device tensor: the weight argument of the split-bf16 Runner kernels (built once)"""
+        if self._ac_blob is None:
+            blob = pack_fast_actor_critic(self)
+            assert blob.size == (_lib.fast_blob_bytes("qs_runner_rollout_net_fast", _lib.NET_TOWERS) if self.towers
+                                 else _lib.fast_blob_bytes("qs_runner_rollout_fast"))
+            self._ac_blob = self.torch.as_tensor(blob.copy()).to(self.w0.device)
+        return self._ac_blob
 
 
 def pack_fast_actor_critic(policy):
@@ -185,36 +178,20 @@ def fused_runner_rollout(env, policy, T, noise=None, dones_in=None, want_flags=F
             raise ValueError("noise must be [T, num_envs, 4]")
     if dones_in is not None:
         dones_in = dones_in.to(device=dev).to(u8).contiguous()
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-    env._use_current_stream()
-    env._inputs_ready()
-    _lib.check(env._lib.qs_set_rollout_layout(env._h, 1 if env_major else 0), "qs_set_rollout_layout")
-    tail = (p(noise), p(dones_in), p(out["obs"]), p(out["actions"]), p(out["values"]), p(out["neglogp"]), p(out["dones"]),
-            p(out["rewards"]), p(out["flags"]), p(out["last_obs"]), p(out["last_values"]), p(out["last_dones"]))
+    if precision not in ("f32", "bf16x3"):
+        raise ValueError("precision must be 'f32' or 'bf16x3'")
+    env._call("qs_set_rollout_layout", 1 if env_major else 0)
+    tail = (noise, dones_in, out["obs"], out["actions"], out["values"], out["neglogp"], out["dones"], out["rewards"], out["flags"],
+            out["last_obs"], out["last_values"], out["last_dones"])
     towers = getattr(policy, "towers", False)
     if precision == "f32":
-        pol = policy.c_struct()
-        if towers:
-            _lib.check(env._lib.qs_runner_rollout_net(env._h, T, C.byref(pol), *tail), "qs_runner_rollout_net")
-        else:
-            _lib.check(env._lib.qs_runner_rollout(env._h, T, C.byref(pol), *tail), "qs_runner_rollout")
-    elif precision == "bf16x3":
-        if getattr(policy, "_ac_blob", None) is None:
-            blob = pack_fast_actor_critic(policy)
-            want = (env._lib.qs_runner_rollout_net_fast_blob_bytes(_lib.NET_TOWERS) if towers
-                    else env._lib.qs_runner_rollout_fast_blob_bytes())
-            assert blob.size == want
-            policy._ac_blob = torch.as_tensor(blob.copy()).to(dev)
+        env._call("qs_runner_rollout_net" if towers else "qs_runner_rollout", T, C.byref(policy.c_struct()), *tail)
+    else:
         ls = (C.c_float * 4)(*[float(x) for x in policy.logstd_host])
         if towers:
-            _lib.check(env._lib.qs_runner_rollout_net_fast(env._h, T, _lib.NET_TOWERS, p(policy._ac_blob), ls,
-                                                           1 if policy.squash else 0, *tail), "qs_runner_rollout_net_fast")
+            env._call("qs_runner_rollout_net_fast", T, _lib.NET_TOWERS, policy.fast_blob(), ls, 1 if policy.squash else 0, *tail)
         else:
-            _lib.check(env._lib.qs_runner_rollout_fast(env._h, T, p(policy._ac_blob), ls, 1 if policy.squash else 0, *tail),
-                       "qs_runner_rollout_fast")
-    else:
-        raise ValueError("precision must be 'f32' or 'bf16x3'")
-    env._outputs_ready()
+            env._call("qs_runner_rollout_fast", T, policy.fast_blob(), ls, 1 if policy.squash else 0, *tail)
     return out
 
 

@@ -103,14 +103,10 @@ class VecDockingEnv:
             cfg.stream = self._stream or None
             cfg.external_stream = 1
         self.cfg = cfg
-        self._h = C.c_void_p()
-        _lib.check(self._lib.qs_create(C.byref(cfg), C.byref(self._h)), "qs_create")
+        self._h = _lib.create(cfg)
         n = self.num_envs
         kw = dict(device=self.device)
-        self._obs = torch.empty((n, self.obs_dim), dtype=torch.float32, **kw)
-        self._rew = torch.empty((n,), dtype=torch.float32, **kw)
-        self._done = torch.empty((n,), dtype=torch.uint8, **kw)
-        self._flags = torch.empty((n,), dtype=torch.uint8, **kw)
+        self._obs, self._rew, self._done, self._flags = self._step_outputs(n)
         self._term = torch.zeros((n, self.obs_dim), dtype=torch.float32, **kw)
         self._tstate = None if self.kind == _lib.KIND_HOVER else torch.zeros((n, 26), dtype=torch.float32, **kw)
         self._actions = None
@@ -125,7 +121,14 @@ class VecDockingEnv:
 
     # ------------------------------------------------------------------ plumbing
     def _ptr(self, t):
-        return C.c_void_p(t.data_ptr()) if t is not None else None
+        """for callers that drive the library themselves (bench.py); the wrappers hand tensors to _call"""
+        return _lib.as_arg(t)
+
+    def _step_outputs(self, n):
+        """fresh (obs, reward, done, flags) tensors for one step of n envs"""
+        torch, kw = _torch(), dict(device=self.device)
+        return (torch.empty((n, self.obs_dim), dtype=torch.float32, **kw), torch.empty((n,), dtype=torch.float32, **kw),
+                torch.empty((n,), dtype=torch.uint8, **kw), torch.empty((n,), dtype=torch.uint8, **kw))
 
     def _as_device(self, x, shape, dtype=None):
         torch = _torch()
@@ -152,23 +155,37 @@ class VecDockingEnv:
             raw = getattr(_torch()._C, "_cuda_getCurrentRawStream", None)       # ~0.2 us; the public API costs ~2 us
             s = raw(self.device_index) if raw is not None else _torch().cuda.current_stream(self.device).cuda_stream
             if s != self._stream:
-                _lib.check(self._lib.qs_set_stream(self._h, C.c_void_p(s) if s else None, 1), "qs_set_stream")
+                _lib.call(self._h, "qs_set_stream", s or None, 1)
                 self._stream = s
 
-    def _outputs_ready(self):
-        """an owned (non-torch) stream is not ordered with torch's: drain it before torch touches what a kernel wrote"""
-        if not self._follow_torch_stream:
-            self.sync()
-
-    def _inputs_ready(self):
-        """... and make sure torch has finished producing the inputs before a kernel on the owned stream reads them"""
-        if not self._follow_torch_stream:
+    def _inputs_ready(self, queued=False):
+        """an owned (non-torch) stream is not ordered with torch's: make sure torch has finished producing the inputs before a
+        kernel on it reads them.  queued: the entry point launches steps (step, rollout), which in private-queue mode with
+        "host" ordering go to a queue that is not ordered behind the caller's stream either"""
+        if not self._follow_torch_stream or (queued and self._queue_host_ordered):
             _torch().cuda.current_stream(self.device).synchronize()
 
+    def _outputs_ready(self, queued=False):
+        """... and drain the owned stream (the host-ordered queue) before torch touches what a kernel wrote"""
+        if not self._follow_torch_stream or (queued and self._queue_host_ordered):
+            self.sync()
+
+    def _launch(self, name, *args, queued=False):
+        """the entry point `name` on this handle, on the stream torch considers current and after its inputs; its outputs are
+        not ordered yet (step_async, which leaves that to step_wait).  Tensors go in as they are (_lib.as_arg)"""
+        self._use_current_stream()
+        self._inputs_ready(queued)
+        _lib.call(self._h, name, *args)
+
+    def _call(self, name, *args, queued=False):
+        """THE way from a wrapper, in this module or another, to the library: _launch, then the outputs are torch's to read"""
+        self._launch(name, *args, queued=queued)
+        self._outputs_ready(queued)
+
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
+        if getattr(self, "_h", None):
             self._lib.qs_destroy(self._h)
-            self._h = C.c_void_p()
+            self._h = None
 
     def __del__(self):
         try:
@@ -177,22 +194,18 @@ class VecDockingEnv:
             pass
 
     def sync(self):
-        _lib.check(self._lib.qs_sync(self._h), "qs_sync")
+        _lib.call(self._h, "qs_sync")                  # what _outputs_ready does: not through _call
 
     # ------------------------------------------------------------------ VecEnv protocol
     def reset(self, mask=None):
         """DockingEnv.reset for all (or masked) envs -> obs [N,12]"""
-        self._use_current_stream()
         m = None
         if mask is not None:
             m = self._as_device(mask, (self.num_envs,), _torch().uint8)
-        self._inputs_ready()
-        _lib.check(self._lib.qs_reset(self._h, self._ptr(m), self._ptr(self._obs)), "qs_reset")
-        self._outputs_ready()
+        self._call("qs_reset", m, self._obs)
         return self._out(self._obs.clone() if self.backend == "torch" else self._obs)
 
     def step_async(self, actions):
-        self._use_current_stream()
         torch = _torch()
         if self.backend == "numpy" and isinstance(actions, np.ndarray):
             # host actions: through a pinned staging tensor, asynchronously (no pageable-memory copy on the way up)
@@ -207,27 +220,17 @@ class VecDockingEnv:
         if self.copy and self.backend == "torch":
             # this step's outputs get tensors of their own: whatever the caller kept from earlier steps stays intact
             n, kw = self.num_envs, dict(device=self.device)
-            self._obs = torch.empty((n, self.obs_dim), dtype=torch.float32, **kw)
-            self._rew = torch.empty((n,), dtype=torch.float32, **kw)
-            self._done = torch.empty((n,), dtype=torch.uint8, **kw)
-            self._flags = torch.empty((n,), dtype=torch.uint8, **kw)
+            self._obs, self._rew, self._done, self._flags = self._step_outputs(n)
             if self.auto_reset:
                 self._term = torch.empty((n, self.obs_dim), dtype=torch.float32, **kw)
                 if self._tstate is not None:
                     self._tstate = torch.empty((n, 26), dtype=torch.float32, **kw)
-        self._inputs_ready()
-        if self._queue_host_ordered:
-            _torch().cuda.current_stream(self.device).synchronize()      # the queue is not ordered behind the caller's stream
-        _lib.check(self._lib.qs_step_ex(self._h, self._ptr(self._actions), self._ptr(self._obs), self._ptr(self._rew),
-                                        self._ptr(self._done), self._ptr(self._flags),
-                                        self._ptr(self._term) if self.auto_reset else None,
-                                        self._ptr(self._tstate) if self.auto_reset else None), "qs_step")
+        self._launch("qs_step_ex", self._actions, self._obs, self._rew, self._done, self._flags,
+                     self._term if self.auto_reset else None, self._tstate if self.auto_reset else None, queued=True)
         self._nstep += 1
 
     def step_wait(self):
-        self._outputs_ready()
-        if self._queue_host_ordered:
-            self.sync()                                                    # outputs of a host-ordered private-queue step: valid after the drain
+        self._outputs_ready(queued=True)
         if self.backend == "torch":
             # done is the uint8 buffer seen as bool.  The InfoView keeps THIS step's tensors (done, flags, terminal
             # observation / states): with copy=True they are never written again, so it can be read at any time
@@ -268,35 +271,20 @@ class VecDockingEnv:
         stream order.  65 536 envs: 32 us (f32) / 17 us (bf16x3) per step against 85-94 us for step(policy.predict(obs)).
         Returns (obs, reward, done, actions); flags in `env.last_flags`.  No terminal_observation (use step() where needed).
         torch backend, docking envs."""
-        from .policy import pack_fast_weights
         torch = _torch()
         if self.backend != "torch":
             raise _lib.QuadsimError("step_policy: torch backend only")
-        self._use_current_stream()
-        n, kw = self.num_envs, dict(device=self.device)
-        if self.copy:
-            self._obs = torch.empty((n, self.obs_dim), dtype=torch.float32, **kw)
-            self._rew = torch.empty((n,), dtype=torch.float32, **kw)
-            self._done = torch.empty((n,), dtype=torch.uint8, **kw)
-            self._flags = torch.empty((n,), dtype=torch.uint8, **kw)
-        acts = torch.empty((n, 4), dtype=torch.float32, **kw)
-        self._inputs_ready()
-        io = (self._ptr(self._obs), self._ptr(self._rew), self._ptr(self._done), self._ptr(self._flags), self._ptr(acts))
-        if precision == "bf16x3":
-            if not hasattr(policy, "_blob"):
-                blob = pack_fast_weights(policy)
-                assert blob.size == self._lib.qs_policy_rollout_fast_blob_bytes()
-                policy._blob = torch.as_tensor(blob.copy()).to(self.device)
-            _lib.check(self._lib.qs_policy_rollout_fast(self._h, 1, self._ptr(policy._blob), *io), "qs_policy_rollout_fast")
-        elif precision == "f32":
-            if not hasattr(policy, "_wt"):
-                policy._wt = [policy.w0.t().contiguous(), policy.b0.contiguous(), policy.w1.t().contiguous(),
-                              policy.b1.contiguous(), policy.w2.t().contiguous(), policy.b2.contiguous()]
-            _lib.check(self._lib.qs_policy_rollout(self._h, 1, *[self._ptr(w) for w in policy._wt], *io), "qs_policy_rollout")
-        else:
+        if precision not in ("f32", "bf16x3"):
             raise ValueError("precision must be 'f32' or 'bf16x3'")
+        if self.copy:
+            self._obs, self._rew, self._done, self._flags = self._step_outputs(self.num_envs)
+        acts = torch.empty((self.num_envs, 4), dtype=torch.float32, device=self.device)
+        io = (self._obs, self._rew, self._done, self._flags, acts)
+        if precision == "bf16x3":
+            self._call("qs_policy_rollout_fast", 1, policy.fast_blob(), *io)
+        else:
+            self._call("qs_policy_rollout", 1, *policy.transposed_weights(), *io)
         self._nstep += 1
-        self._outputs_ready()
         return self._obs, self._rew, self._done.view(torch.bool), acts
 
     @property
@@ -315,18 +303,16 @@ class VecDockingEnv:
         as in the default mode.  "host" (round 2's contract): no hand-shake; tensors handed to step() must be complete when
         it is called and its outputs are valid after sync() -- step_async / step_wait then synchronise the host per step.
         queues (1..4): split the tiles over that many private queues; their chains overlap each other's kernel boundary."""
-        self._use_current_stream()
-        _lib.check(self._lib.qs_set_queue_mode(self._h, int(queues) if private else 0), "qs_set_queue_mode")
+        self._call("qs_set_queue_mode", int(queues) if private else 0)
         self._queue_private = bool(private)
         self._queue_host_ordered = False
         if private:
             if ordering is not None:
                 if ordering not in ("stream", "host"):
                     raise ValueError("ordering must be 'stream' or 'host'")
-                _lib.check(self._lib.qs_set_queue_ordering(self._h, _lib.ORDER_STREAM if ordering == "stream" else _lib.ORDER_HOST),
-                           "qs_set_queue_ordering")
+                self._call("qs_set_queue_ordering", _lib.ORDER_STREAM if ordering == "stream" else _lib.ORDER_HOST)
             o = C.c_int32(0)
-            _lib.check(self._lib.qs_get_queue_ordering(self._h, C.byref(o)), "qs_get_queue_ordering")
+            self._call("qs_get_queue_ordering", C.byref(o))
             self._queue_host_ordered = o.value == _lib.ORDER_HOST
 
     @property
@@ -344,18 +330,17 @@ class VecDockingEnv:
         of one group overlaps the kernel boundary -- or the policy -- of the others.  groups <= 1 removes the grouping.
         threads: one native launcher thread per group (the calling thread only posts launch records).
         Results are bit-identical to step() for any grouping."""
-        self._use_current_stream()
-        _lib.check(self._lib.qs_set_groups(self._h, int(groups), 1 if threads else 0), "qs_set_groups")
+        self._call("qs_set_groups", int(groups), 1 if threads else 0)
         self._groups = None
         k = C.c_int32(0)
-        _lib.check(self._lib.qs_group_count(self._h, C.byref(k)), "qs_group_count")
+        self._call("qs_group_count", C.byref(k))
         if groups > 1:
             torch = _torch()
             self._groups = []
             for g in range(k.value):
-                lo, hi, sp = C.c_int64(0), C.c_int64(0), C.c_void_p()
-                _lib.check(self._lib.qs_group_range(self._h, g, C.byref(lo), C.byref(hi)), "qs_group_range")
-                _lib.check(self._lib.qs_group_stream(self._h, g, C.byref(sp)), "qs_group_stream")
+                lo, hi, sp = C.c_int64(0), C.c_int64(0), _lib.vp()
+                self._call("qs_group_range", g, C.byref(lo), C.byref(hi))
+                self._call("qs_group_stream", g, C.byref(sp))
                 self._groups.append({"range": (lo.value, hi.value), "stream_ptr": sp.value,
                                      "stream": torch.cuda.ExternalStream(sp.value, device=self.device)})
         return k.value
@@ -384,14 +369,11 @@ class VecDockingEnv:
         actions = self._as_device(actions, (n, 4))
         with torch.cuda.stream(G["stream"]):
             kw = dict(device=self.device)
-            obs = torch.empty((n, self.obs_dim), dtype=torch.float32, **kw)
-            rew = torch.empty((n,), dtype=torch.float32, **kw)
-            done = torch.empty((n,), dtype=torch.uint8, **kw)
-            flags = torch.empty((n,), dtype=torch.uint8, **kw)
+            obs, rew, done, flags = self._step_outputs(n)
             term = torch.empty((n, self.obs_dim), dtype=torch.float32, **kw) if self.auto_reset else None
             tst = torch.empty((n, 26), dtype=torch.float32, **kw) if (self.auto_reset and self._tstate is not None) else None
-        _lib.check(self._lib.qs_step_group(self._h, g, self._ptr(actions), self._ptr(obs), self._ptr(rew), self._ptr(done),
-                                           self._ptr(flags), self._ptr(term), self._ptr(tst)), "qs_step_group")
+        # not _call: the launch goes to the group's stream, whatever stream torch considers current, and the caller orders it
+        _lib.call(self._h, "qs_step_group", g, actions, obs, rew, done, flags, term, tst)
         self._nstep += 1
         return obs, rew, done.view(torch.bool), flags, term, tst
 
@@ -399,22 +381,19 @@ class VecDockingEnv:
         """one step of ALL groups in one call (G launches, one per group stream), full-batch tensors as step(); the
         outputs are the env's own buffers, complete once groups_join() / sync() has ordered the group streams"""
         self._actions = self._as_device(actions, (self.num_envs, 4))
-        _lib.check(self._lib.qs_step_groups(self._h, self._ptr(self._actions), self._ptr(self._obs), self._ptr(self._rew),
-                                            self._ptr(self._done), self._ptr(self._flags),
-                                            self._ptr(self._term) if self.auto_reset else None,
-                                            self._ptr(self._tstate) if self.auto_reset else None), "qs_step_groups")
+        # not _call: one launch per group stream; groups_fork() / groups_join() order them against the env's main stream
+        _lib.call(self._h, "qs_step_groups", self._actions, self._obs, self._rew, self._done, self._flags,
+                  self._term if self.auto_reset else None, self._tstate if self.auto_reset else None)
         self._nstep += 1
         return self._obs, self._rew, self._done.view(_torch().bool)
 
     def groups_fork(self):
         """group streams wait for everything enqueued so far on the env's main stream (torch's current stream)"""
-        self._use_current_stream()
-        _lib.check(self._lib.qs_groups_fork(self._h), "qs_groups_fork")
+        self._call("qs_groups_fork")
 
     def groups_join(self):
         """the env's main stream waits for everything enqueued so far on the group streams"""
-        self._use_current_stream()
-        _lib.check(self._lib.qs_groups_join(self._h), "qs_groups_join")
+        self._call("qs_groups_join")
 
     def rollout(self, actions=None, T=None, want_flags=True, stepwise=False, out=None):
         """T fused steps in one launch (qs_rollout), or T single-step launches issued from native code
@@ -422,7 +401,6 @@ class VecDockingEnv:
         out: optional (obs, reward, done, flags) tensors to write into.
         -> obs [T,N,12], reward [T,N], done [T,N] (uint8), flags [T,N] or None (torch tensors)."""
         torch = _torch()
-        self._use_current_stream()
         if actions is not None:
             T = int(actions.shape[0])
             actions = self._as_device(actions, (T, self.num_envs, 4))
@@ -436,30 +414,19 @@ class VecDockingEnv:
             rew = torch.empty((T, n), dtype=torch.float32, device=self.device)
             done = torch.empty((T, n), dtype=torch.uint8, device=self.device)
             flags = torch.empty((T, n), dtype=torch.uint8, device=self.device) if want_flags else None
-        fn = self._lib.qs_rollout_stepwise if stepwise else self._lib.qs_rollout
-        self._inputs_ready()
-        if self._queue_host_ordered:
-            _torch().cuda.current_stream(self.device).synchronize()
-        _lib.check(fn(self._h, T, self._ptr(actions), self._ptr(obs), self._ptr(rew), self._ptr(done),
-                      self._ptr(flags)), "qs_rollout")
-        self._outputs_ready()
-        if self._queue_host_ordered:
-            self.sync()
+        self._call("qs_rollout_stepwise" if stepwise else "qs_rollout", T, actions, obs, rew, done, flags, queued=True)
         return obs, rew, done, flags
 
     def rollout_slab(self, actions=None, T=None, out=None):
         """qs_rollout_slab: T fused steps written as one packed slab [T,N,14] (obs 12, reward, done as 0/1)."""
         torch = _torch()
-        self._use_current_stream()
         if actions is not None:
             T = int(actions.shape[0])
             actions = self._as_device(actions, (T, self.num_envs, 4))
         elif T is None:
             raise ValueError("give actions or T")
         slab = out if out is not None else torch.empty((T, self.num_envs, 14), dtype=torch.float32, device=self.device)
-        self._inputs_ready()
-        _lib.check(self._lib.qs_rollout_slab(self._h, T, self._ptr(actions), self._ptr(slab), None), "qs_rollout_slab")
-        self._outputs_ready()
+        self._call("qs_rollout_slab", T, actions, slab, None)
         return slab
 
     def random_actions(self, T, step0=None):
@@ -467,10 +434,8 @@ class VecDockingEnv:
         torch = _torch()
         if step0 is None:
             step0 = self.step_counter
-        self._use_current_stream()
         a = torch.empty((T, self.num_envs, 4), dtype=torch.float32, device=self.device)
-        _lib.check(self._lib.qs_fill_random_actions(self._h, T, int(step0), self._ptr(a)), "qs_fill_random_actions")
-        self._outputs_ready()
+        self._call("qs_fill_random_actions", T, int(step0), a)
         return a
 
     def shooting_plan(self, horizon=20, paths=200, objective="reward", return_scores=False, return_sequence=False, splits=None):
@@ -525,84 +490,65 @@ class VecDockingEnv:
     @property
     def step_counter(self):
         k = C.c_uint64(0)
-        _lib.check(self._lib.qs_get_step_counter(self._h, C.byref(k)), "qs_get_step_counter")
+        self._call("qs_get_step_counter", C.byref(k))
         return int(k.value)
 
     @step_counter.setter
     def step_counter(self, k):
-        _lib.check(self._lib.qs_set_step_counter(self._h, int(k)), "qs_set_step_counter")
+        self._call("qs_set_step_counter", int(k))
 
     def get_state(self, as_numpy=True):
         """dict(chaser[N,13], target[N,13], u_prev[N,8], qdes[N,4], last_shaping[N], t[N])"""
         torch = _torch()
         n = self.num_envs
         shapes = dict(chaser=(n, 13), target=(n, 13), u_prev=(n, 8), qdes=(n, 4), last_shaping=(n,), t=(n,))
-        self._use_current_stream()
         bufs = {k: torch.empty(s, dtype=torch.float32, device=self.device) for k, s in shapes.items()}
-        _lib.check(self._lib.qs_get_state(self._h, *[self._ptr(bufs[k]) for k in shapes]), "qs_get_state")
-        self._outputs_ready()
+        self._call("qs_get_state", *bufs.values())
         return {k: (v.cpu().numpy() if as_numpy else v) for k, v in bufs.items()}
 
     def set_state(self, chaser=None, target=None, u_prev=None, qdes=None, last_shaping=None, t=None):
         n = self.num_envs
         shapes = dict(chaser=(n, 13), target=(n, 13), u_prev=(n, 8), qdes=(n, 4), last_shaping=(n,), t=(n,))
         given = dict(chaser=chaser, target=target, u_prev=u_prev, qdes=qdes, last_shaping=last_shaping, t=t)
-        self._use_current_stream()
-        ptrs, keep = [], []
-        for k, s in shapes.items():
-            if given[k] is None:
-                ptrs.append(None)
-            else:
-                tt = self._as_device(given[k], s)
-                keep.append(tt)
-                ptrs.append(self._ptr(tt))
-        self._inputs_ready()
-        _lib.check(self._lib.qs_set_state(self._h, *ptrs), "qs_set_state")
+        self._call("qs_set_state", *[None if given[k] is None else self._as_device(given[k], s) for k, s in shapes.items()])
         self.sync()
 
     def set_init_state(self, chaser_init, target_init=None):
         """per-env initial states reset() returns to (env.chaser_ini_state / target_ini_state; HoveringEnv.ini_state)"""
         n = self.num_envs
-        self._use_current_stream()
         c = self._as_device(chaser_init, (n, 13))
         t = self._as_device(target_init, (n, 13)) if target_init is not None else None
-        self._inputs_ready()
-        _lib.check(self._lib.qs_set_init_state(self._h, self._ptr(c), self._ptr(t)), "qs_set_init_state")
+        self._call("qs_set_init_state", c, t)
 
     def get_init_state(self):
         torch = _torch()
         n = self.num_envs
-        self._use_current_stream()
         c = torch.empty((n, 13), dtype=torch.float32, device=self.device)
         t = torch.empty((n, 13), dtype=torch.float32, device=self.device)
-        _lib.check(self._lib.qs_get_init_state(self._h, self._ptr(c), self._ptr(t)), "qs_get_init_state")
+        self._call("qs_get_init_state", c, t)
         return c.cpu().numpy(), (None if self.kind == _lib.KIND_HOVER else t.cpu().numpy())
 
     def set_params(self, mass=None, inertia=None):
         n = self.num_envs
-        self._use_current_stream()
         m = self._as_device(mass, (n,)) if mass is not None else None
         i = self._as_device(inertia, (n, 3)) if inertia is not None else None
-        self._inputs_ready()
-        _lib.check(self._lib.qs_set_params(self._h, self._ptr(m), self._ptr(i)), "qs_set_params")
+        self._call("qs_set_params", m, i)
         self.sync()
 
     def get_params(self):
         torch = _torch()
         n = self.num_envs
-        self._use_current_stream()
         m = torch.empty((n,), dtype=torch.float32, device=self.device)
         i = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-        _lib.check(self._lib.qs_get_params(self._h, self._ptr(m), self._ptr(i)), "qs_get_params")
-        self._outputs_ready()
+        self._call("qs_get_params", m, i)
         return m.cpu().numpy(), i.cpu().numpy()
 
     def timer_start(self):
-        _lib.check(self._lib.qs_timer_start(self._h), "qs_timer_start")
+        self._call("qs_timer_start")
 
     def timer_stop(self):
         ms = C.c_float(0)
-        _lib.check(self._lib.qs_timer_stop(self._h, C.byref(ms)), "qs_timer_stop")
+        self._call("qs_timer_stop", C.byref(ms))
         return float(ms.value)
 
 

@@ -75,8 +75,8 @@ class StubLib:
 
 
 def stub_env(torch, lib, num_envs=3):
-    """an env of `num_envs` on the CPU whose library is `lib` and whose stream hooks do nothing"""
+    """an env of `num_envs` on the CPU whose _call goes straight to `lib` (VecDockingEnv._call itself is covered by
+    test_call_path_cpu.py)"""
     import types
-    noop = lambda: None                                       # noqa: E731
-    return types.SimpleNamespace(num_envs=num_envs, device=torch.device("cpu"), _lib=lib, _h=None, _use_current_stream=noop,
-                                 _inputs_ready=noop, _outputs_ready=noop)
+    return types.SimpleNamespace(num_envs=num_envs, device=torch.device("cpu"),
+                                 _call=lambda name, *args: getattr(lib, name)(None, *args))

@@ -160,7 +160,6 @@ def test_truncation_leaves_unfinished_slots_untouched(qa, torch, policies):
     K, n, T = 2, 1000, 250
     env, obs = _make(qa, "docking-v0", 1, n)
     pol = policies["shared"]
-    pol.predict_hip(env, obs)                         # builds the cached transposed weights (pol._wt)
     kw = dict(device=env.device)
     ret = torch.full((K, n), -123.5, dtype=torch.float64, **kw)
     length = torch.full((K, n), -7, dtype=torch.int32, **kw)
@@ -168,7 +167,7 @@ def test_truncation_leaves_unfinished_slots_untouched(qa, torch, policies):
     docked = torch.full((K, n), -9, dtype=torch.int32, **kw)
     fin = torch.full((n,), -1, dtype=torch.int32, **kw)
     p = lambda t: C.c_void_p(t.data_ptr())            # noqa: E731
-    assert env._lib.qs_policy_evaluate(env._h, K, T, *[p(w) for w in pol._wt], p(ret), p(length), p(flags), p(docked), p(fin)) == 0
+    assert env._lib.qs_policy_evaluate(env._h, K, T, *[p(w) for w in pol.transposed_weights()], p(ret), p(length), p(flags), p(docked), p(fin)) == 0
     torch.cuda.synchronize()
     r, le, fl, dk, f = _episodes(*_loop(torch, env, pol, obs, "f32", T), K)
     np.testing.assert_array_equal(fin.cpu().numpy(), f)
