@@ -503,16 +503,30 @@ double res_now()
     return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
-// the resident instantiation matching the packet chain's (chain_resolve_kernel first); res_fits says whether it may be used
+// The resident loop's own choice of the reset-preparation variant where the packet chain takes the third wave (PREP 2) and
+// nothing forces one (QS_RESET_PREP, qs_debug_set_reset_prep).  All tiles of the handle are on the chip at once for the whole
+// roll-out; up to kResPrepMaxTiles of them (2.25 waves per SIMD with three waves per tile) the third wave still runs beside the
+// other two, above that it takes issue slots from the chaser waves and two waves per tile are faster
+// (profiles/step_phases: measured at 256, 512, 768 and 1 024 tiles).
+constexpr int64_t kResPrepMaxTiles = 768;
+int res_prep_for(const QsEnv *e, const QsChain *c)
+{
+    if (c->v_prep != 2 || prep_forced().load(std::memory_order_relaxed) == 2) return c->v_prep;
+    return e->tiles <= kResPrepMaxTiles ? 2 : 0;
+}
+
+// the resident instantiation matching the packet chain's (chain_resolve_kernel first) but for its own PREP (res_prep_for);
+// res_fits says whether it may be used
 int res_resolve_kernel(QsEnv *e)
 {
     QsChain *c = e->chain;
     if (!c->v_split) { c->res_fits = false; return QS_OK; }
-    if (c->res_kernel.object && c->v_integ == c->rv_integ && c->v_params == c->rv_params && c->v_rmode == c->rv_rmode && c->v_prep == c->rv_prep)
+    const int prep = res_prep_for(e, c);
+    if (c->res_kernel.object && c->v_integ == c->rv_integ && c->v_params == c->rv_params && c->v_rmode == c->rv_rmode && prep == c->rv_prep)
         return QS_OK;
     char sym[200];
     snprintf(sym, sizeof sym, "_ZN12_GLOBAL__N_114k_env_residentILi%dELb%dELi%dELi%dEEEvNS_8StepArgsENS_7ResArgsE.kd", c->v_integ,
-             c->v_params, c->v_rmode, c->v_prep);
+             c->v_params, c->v_rmode, prep);
     hsa_executable_symbol_t ks;
     QsKernel k;
     HSA_TRY(hsa_executable_get_symbol_by_name(c->exe, sym, &c->gpu, &ks));
@@ -521,10 +535,10 @@ int res_resolve_kernel(QsEnv *e)
     HSA_TRY(hsa_executable_symbol_get_info(ks, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_GROUP_SEGMENT_SIZE, &k.group_size));
     HSA_TRY(hsa_executable_symbol_get_info(ks, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_PRIVATE_SEGMENT_SIZE, &k.private_size));
     if (k.kernarg_size > kResKernargBytes) return fail(QS_ERR_HIP, "queue mode: kernel argument block of %s is %u B", sym, k.kernarg_size);
-    const int waves = split_waves(c->v_rmode, c->v_prep);
+    const int waves = split_waves(c->v_rmode, prep);
     k.block = (unsigned)(waves * kTile);
     c->res_kernel = k;
-    c->rv_integ = c->v_integ; c->rv_params = c->v_params; c->rv_rmode = c->v_rmode; c->rv_prep = c->v_prep;
+    c->rv_integ = c->v_integ; c->rv_params = c->v_params; c->rv_rmode = c->v_rmode; c->rv_prep = prep;
     // every workgroup of every lane resident at once (the chaser waves of late workgroups would otherwise wait for the first
     // round's idle limit); scratch would be a private segment per wave for the whole roll-out
     c->res_fits = k.private_size == 0 && e->tiles * waves <= c->res_wave_cap;
@@ -819,7 +833,7 @@ int chain_step_variant(QsEnv *e, StepVariant *v)
     if (!resident && (r = chain_resolve_kernel(e))) return r;
     v->family = resident ? kFamResident : c->v_split ? kFamChainSplit : kFamChainSerial;
     v->integ = c->v_integ; v->params = c->v_params; v->rmode = c->v_rmode;
-    v->prep = c->v_split ? c->v_prep : -1;
+    v->prep = resident ? c->rv_prep : c->v_split ? c->v_prep : -1;
     return QS_OK;
 }
 

@@ -675,6 +675,13 @@ __device__ __forceinline__ void res_report_done(const ResArgs &R, unsigned old, 
 // barrier #0 before the first step; the next descriptor is requested at the top of a step and resolved where k_env_split
 // requests the next action; a step's I/O pointers are those of its descriptor D; no placement guard and no slab; the chaser
 // wave keeps its priority for the whole dispatch; the state is stored once, when the tile leaves.
+// Full stamp build: stamp 1 is retaken at the top of every step, so that the stamps a tile flushes when it leaves are the
+// timeline of its LAST step (1 step start, 2 before #1, 3 after #1, 4 before #2, 5 after #2, 6 / 7 as in k_env_split).
+#if defined(QS_STAMP) && QS_STAMP + 0 < 2
+#define QS_STAMP_STEP() QS_STAMP_AT(1)
+#else
+#define QS_STAMP_STEP() ((void)0)
+#endif
 template <int INTEG, bool PARAMS, int RMODE, int PREP>
 __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs R)
 {
@@ -729,6 +736,7 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
         int64_t t = 0;
 #pragma clang loop unroll(disable)
         for (; cmd == RES_STEP; ++t) {
+            QS_STAMP_STEP();
             const int64_t o = io;
             const unsigned long long wn = res_request(R, seq + t + 1, lane);   // the next descriptor, a step ahead of its use
             tt += 1.0f;
@@ -806,6 +814,7 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
         int64_t t = 0;
 #pragma clang loop unroll(disable)
         for (; cmd == RES_STEP; ++t) {
+            QS_STAMP_STEP();
             float pre[13];
 #pragma unroll
             for (int i = 0; i < 13; ++i) pre[i] = st[i];

@@ -2,6 +2,13 @@
 
     QUADSIM_HIP_LIB=quadsim_amd/csrc/libquadsim_hip_stamp.so  python tools/stamp_timeline.py --envs 65536                   (phases)
     QUADSIM_HIP_LIB=quadsim_amd/csrc/libquadsim_hip_stamp2.so python tools/stamp_timeline.py --queue-mode private --queues 2  (light)
+    QUADSIM_HIP_LIB=quadsim_amd/csrc/libquadsim_hip_stamp.so  python tools/stamp_timeline.py --resident 8 --queues 1    (resident loop)
+
+--resident: the resident step loop (k_env_resident) keeps its stamps in registers for the whole dispatch and flushes them when
+the tile leaves, so a drained roll-out yields each tile's LAST step: chaser wave 1 step start, 2 before #1, 3 after #1, 4 before
+#2, 5 after #2, 6 after the reset branch, 7 state stored and drained; target wave 8 + {1 .. 5 likewise, 6 state store issued}.
+A stamp orders memory operations and barriers, not register arithmetic: the compiler may place arithmetic of a later phase in
+front of an earlier stamp, so the waits at the barriers are the trustworthy columns (profiles/step_phases/README.md).
 
 Stamps (100 MHz real-time counter s_memrealtime, kept in registers until the wave ends) per workgroup and step: chaser wave 0
 start, 1 state loads landed, 2 drone step done (before barrier #1), 3 after #1, 4 obs + reward done (before #2), 5 after #2,
@@ -38,11 +45,21 @@ ap.add_argument("--ordering", default="host", choices=["host", "stream"],
                 help="private queues: host = back-to-back packets (pre-staged actions), stream = GPU-side hand-shake per step")
 ap.add_argument("--pool", type=int, default=64, help="distinct action batches cycled")
 ap.add_argument("--json", default=None)
+ap.add_argument("--resident", type=int, default=0, metavar="D",
+                help="the resident step loop (host-ordered private queue, full stamp build): D roll-outs of --resident-steps "
+                     "raw qs_step calls, each drained; a tile flushes its stamps when it leaves, so every roll-out yields the "
+                     "timeline of its LAST step in every tile")
+ap.add_argument("--resident-steps", type=int, default=321, help="steps per roll-out; not a multiple of 64, so that consecutive "
+                                                                "roll-outs flush into different slots of the stamp buffer")
+ap.add_argument("--prep", type=int, default=-1, help="--resident: force the reset-preparation variant (0 two waves, 2 three)")
 args = ap.parse_args()
 n, G = args.envs, args.groups
 lib = qa._lib.load()
 if not hasattr(lib, "qs_debug_set_stamps"):
     raise SystemExit("this library has no stamps: build tools/build_stamp.sh and set QUADSIM_HIP_LIB")
+if args.resident and args.prep in (0, 2):
+    lib.qs_debug_set_reset_prep.argtypes = [C.c_int]
+    lib.qs_debug_set_reset_prep(args.prep)
 env = qa.VecDockingEnv(args.env, num_envs=n, randomise=args.randomise, seed=1234, init_range=qa.C3_INIT_RANGE,
                        mass_scale=(0.8, 1.2), inertia_scale=(0.8, 1.2), copy=False)
 tiles = (n + 63) // 64
@@ -50,6 +67,67 @@ buf = torch.zeros((64, tiles, 16), dtype=torch.int64, device="cuda")
 lib.qs_debug_set_stamps.argtypes = [C.c_void_p, C.c_uint64]
 assert lib.qs_debug_set_stamps(C.c_void_p(buf.data_ptr()), buf.numel()) == 0
 env.reset()
+
+
+def resident_timeline():
+    """per role wave, the phases of the last step of each of args.resident roll-outs (all tiles): median, p10, p90 in us"""
+    import time
+    D, K = args.resident, args.resident_steps
+    assert 0 < D <= 64 and K % 64 != 0, "roll-outs must flush into distinct slots"
+    env.set_queue_mode(True, args.queues, ordering="host")
+    pool = env.random_actions(args.pool, step0=0)
+    p = lambda t: C.c_void_p(t.data_ptr())            # noqa: E731
+    io = (p(env._obs), p(env._rew), p(env._done), p(env._flags), p(env._term))
+    seq = [p(pool[k % args.pool]) for k in range(K)]
+    lib.qs_debug_chain_resident.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    torch.cuda.synchronize()
+    slots, wall = [], []
+    for _ in range(D):
+        slots.append(env.step_counter % 64)            # k0 of the roll-out's dispatch: where its tiles flush
+        t0 = time.perf_counter()
+        for a in seq:
+            lib.qs_step(env._h, a, *io)
+        env.sync()
+        wall.append((time.perf_counter() - t0) * 1e6 / K)
+    d = C.c_uint64(0)
+    lib.qs_debug_chain_resident(env._h, C.byref(d))
+    torch.cuda.synchronize()
+    assert len(set(slots)) == D, slots
+    s = buf.cpu().numpy().astype(np.float64)[slots] * 0.01          # [D][tiles][16] us
+    assert (s[:, :, 1:7] > 0).all() and (s[:, :, 9:15] > 0).all(), "a tile flushed no stamps: more than one dispatch per roll-out?"
+    out = {"envs": n, "env": args.env, "randomise": args.randomise, "queues": args.queues, "prep": args.prep, "rollouts": D,
+           "steps_per_rollout": K, "resident_dispatches": int(d.value), "samples_per_phase": int(D * tiles),
+           "wall_us_per_step_stamped_build": [round(w, 3) for w in wall]}
+    print("envs %d %s randomise %d | resident loop, %d queue(s), prep %d | %d roll-outs x %d steps, %d dispatches | last step of "
+          "each roll-out, %d tiles" % (n, args.env, args.randomise, args.queues, args.prep, D, K, d.value, tiles))
+    print("wall per step of the stamped build: %s us" % " ".join("%.2f" % w for w in wall))
+    phases = {"chaser": (0, [("step start -> before #1", 1, 2), ("wait at #1", 2, 3), ("#1 -> before #2 (obs, reward)", 3, 4),
+                             ("wait at #2", 4, 5), ("after #2: reset branch", 5, 6), ("step start -> after reset branch", 1, 6),
+                             ("output stores, state store, leave (drained)", 6, 7)]),
+              "target": (8, [("step start -> before #1", 1, 2), ("wait at #1", 2, 3), ("#1 -> before #2 (PID)", 3, 4),
+                             ("wait at #2", 4, 5), ("after #2: reset, state store issued, leave", 5, 6),
+                             ("step start -> after #2", 1, 5)])}
+    for role, (off, rows) in phases.items():
+        out[role + "_wave_us"] = {}
+        for nm, a, b in rows:
+            dd = s[:, :, off + b] - s[:, :, off + a]
+            q = [float(np.percentile(dd, x)) for x in (10, 50, 90)]
+            out[role + "_wave_us"][nm] = {"p10": q[0], "median": q[1], "p90": q[2], "mean": float(dd.mean())}
+            print("  %s wave %-46s median %.2f  mean %.3f  p10 %.2f  p90 %.2f us" % (role, nm, q[1], dd.mean(), q[0], q[2]))
+    # who arrives last at each barrier, per workgroup
+    out["chaser_last_at_1"] = float((s[:, :, 2] > s[:, :, 10]).mean())
+    out["chaser_last_at_2"] = float((s[:, :, 4] > s[:, :, 12]).mean())
+    print("  chaser wave arrives after the target wave at #1 in %.0f %%, at #2 in %.0f %% of the workgroups"
+          % (100 * out["chaser_last_at_1"], 100 * out["chaser_last_at_2"]))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+    env.close()
+
+
+if args.resident:
+    resident_timeline()
+    sys.exit(0)
 if G > 1:
     env.set_groups(G, threads=True)
 if args.queue_mode == "private":
