@@ -2,8 +2,11 @@
 """MPC through a LEARNED dynamics net, trained while it controls: the loop of model_train (MPC-based_RL.py:213-259) on N envs.
 
     python examples/mpc_learned.py [--envs 16] [--episodes 5] [--max-steps 600] [--horizon 20] [--paths 200]
+                                   [--planner {shooting,mppi}] [--iterations 2] [--lam L] [--sigma S]
 
-Per step: plan with the learned net (learned_shooting_plan: every candidate of every env in one launch), env.step, append
+Per step: plan with the learned net (--planner shooting: learned_shooting_plan, every candidate of every env in one launch;
+--planner mppi: learned_mppi_plan, `iterations` rounds of `paths` Gaussian candidates around a warm-started nominal, whose
+lam / sigma defaults are mpc.mppi_plan's and were not tuned for a learned model), env.step, append
 (obs, act, delta) to a device-side buffer.  After each episode (the auto-resetting envs each contribute their first episode):
 100 Adam steps of batch 128 at lr 1e-4 on the normalised delta (train_dynamic, :120-128) in plain torch, the normalisers
 refreshed from the buffer, the net re-packed for the planner.  Prints the mean episode return after every episode, as the
@@ -42,6 +45,10 @@ def main():
     ap.add_argument("--horizon", type=int, default=20)
     ap.add_argument("--paths", type=int, default=200)
     ap.add_argument("--capacity", type=int, default=1 << 18)
+    ap.add_argument("--planner", choices=("shooting", "mppi"), default="shooting")
+    ap.add_argument("--iterations", type=int, default=2, help="mppi: refinement rounds per plan")
+    ap.add_argument("--lam", type=float, default=qa.mpc.MPPI_DEFAULT_LAMBDA, help="mppi: temperature of the weights")
+    ap.add_argument("--sigma", type=float, default=qa.mpc.MPPI_DEFAULT_SIGMA, help="mppi: standard deviation of the candidates")
     args = ap.parse_args()
     n = args.envs
     env = qa.VecDockingEnv("docking-v0", num_envs=n, seed=1)
@@ -50,17 +57,24 @@ def main():
     for p in net.parameters():
         p.requires_grad_(True)
     opt = torch.optim.Adam(net.parameters(), lr=1.0e-4)
-    mpc = qa.LearnedShootingMPC(env, net, args.horizon, args.paths)
+    if args.planner == "mppi":
+        mpc = qa.LearnedMPPI(env, net, args.horizon, args.paths, args.iterations, args.lam, args.sigma)
+    else:
+        mpc = qa.LearnedShootingMPC(env, net, args.horizon, args.paths)
     buf_x = torch.zeros(args.capacity, 16, device=dev)
     buf_d = torch.zeros(args.capacity, 12, device=dev)
     size = head = 0
     for episode in range(args.episodes):
         obs = env.reset()
+        if args.planner == "mppi":
+            mpc.reset()                                      # a new episode starts from a cold nominal
         ret = torch.zeros(n, dtype=torch.float64, device=dev)
         running = torch.ones(n, dtype=torch.bool, device=dev)
         for step in range(args.max_steps):
             act = mpc.act()
             nxt, r, d, _ = env.step(act)
+            if args.planner == "mppi":
+                mpc.nominal.masked_fill_(d.view(-1, 1, 1), 0.0)
             # the observation after a done step is the reset one: that transition is not a sample of the dynamics
             rows = torch.nonzero(running & ~d).view(-1)
             m = min(int(rows.numel()), args.capacity - head)

@@ -12,12 +12,19 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("QUADSIM_HIP_LIB") or os.path.join(CSRC, "libquadsim_hip.so")  # override: A/B builds
 SOURCES = [os.path.join(CSRC, "quadsim_hip.hip")]
-# every fragment of the one translation unit is a rebuild dependency (dynplan_*.hpp belong to the second library)
-HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith("dynplan_")) + [os.path.join(HERE, "..", "include", "quadsim.h")]
+# every fragment of the one translation unit is a rebuild dependency (dynplan_*.hpp belong to the second library,
+# dynmppi_*.hpp to the third)
+HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith(("dynplan_", "dynmppi_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
 # the second library, libquadsim_dyn.so (include/quadsim_dyn.h; bound in dynplan.py): its own translation unit and code object
 DYN_LIB_PATH = os.environ.get("QUADSIM_DYN_LIB") or os.path.join(CSRC, "libquadsim_dyn.so")
 DYN_SOURCES = [os.path.join(CSRC, "dynplan.hip")]
 DYN_HEADERS = [os.path.join(CSRC, h) for h in ("dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp")] + [os.path.join(HERE, "..", "include", "quadsim_dyn.h")]
+# the third library, libquadsim_dynmppi.so (include/quadsim_dyn_mppi.h; bound in dynplan.py): MPPI over the learned net.  It shares
+# the second library's device code (the model step and the image layout) and none of its host code
+DYNMPPI_LIB_PATH = os.environ.get("QUADSIM_DYNMPPI_LIB") or os.path.join(CSRC, "libquadsim_dynmppi.so")
+DYNMPPI_SOURCES = [os.path.join(CSRC, "dynmppi.hip")]
+DYNMPPI_HEADERS = [os.path.join(CSRC, h) for h in ("dynmppi_kernels.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp")] + [
+    os.path.join(HERE, "..", "include", "quadsim_dyn_mppi.h")]
 
 QS_OK = 0
 KIND_V0, KIND_V2, KIND_V1, KIND_HOVER = 0, 1, 2, 3
@@ -164,9 +171,23 @@ def build_dyn_library(force=False, verbose=False):
     return DYN_LIB_PATH
 
 
+def build_dynmppi_library(force=False, verbose=False):
+    """libquadsim_dynmppi.so with the flags of the main library -> its path"""
+    if not force and _up_to_date(DYNMPPI_LIB_PATH, DYNMPPI_SOURCES + DYNMPPI_HEADERS):
+        return DYNMPPI_LIB_PATH
+    cmd = [hipcc_path(), "-std=c++20", "-O3", "-fno-slp-vectorize", "-ffp-contract=on", "--offload-arch=gfx950", "-fPIC", "-shared",
+           "-Wno-unused-result", *DYNMPPI_SOURCES, "-o", DYNMPPI_LIB_PATH]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return DYNMPPI_LIB_PATH
+
+
 def build_library(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds both libraries, returns the main one's path."""
+    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all three libraries, returns the main one's
+    path."""
     build_dyn_library(force, verbose)
+    build_dynmppi_library(force, verbose)
     deps = SOURCES + HEADERS
     if not force and _up_to_date(LIB_PATH, deps):
         return LIB_PATH

@@ -52,27 +52,9 @@ inline size_t mppi_lds_bytes(int horizon, int paths)
            + (size_t)paths * sizeof(double);
 }
 
-// Philox4x32-10 with the 128-bit counter given directly: (block, subsequence), key = seed -- rocRAND's generator at
-// rocrand_init(seed, subsequence, 4 * block) for every block that call can express (pinned through tests/mppi_ref.py)
-__device__ __forceinline__ uint4 philox_counter(uint64_t seed, uint64_t subsequence, uint64_t block)
-{
-    unsigned c0 = (unsigned)block, c1 = (unsigned)(block >> 32), c2 = (unsigned)subsequence, c3 = (unsigned)(subsequence >> 32);
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-    // the ten round keys are twenty scalar adds; hidden from the optimiser here, they are not kept in twenty scalar registers
-    // (which the planner's kernel does not have to spare) across the loops around a draw
-    asm volatile("" : "+s"(k0), "+s"(k1));
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return make_uint4(c0, c1, c2, c3);
-}
-
-__device__ __forceinline__ float clamp1(float x) { return fminf(fmaxf(x, -1.0f), 1.0f); }
-
+// philox_counter (the 128-bit counter given directly) and clamp1 are quadsim_device.hpp's, shared with the planner over the
+// learned net (dynmppi_kernels.hpp).
+//
 // actions of candidate c at horizon step h in iteration `it`, around the nominal u (k < 2^33, it < 2^4, c < 2^16, h < 2^10)
 __device__ __forceinline__ void mppi_action(const MppiArgs &X, uint64_t seed, uint64_t gid, uint64_t k, int it, int c, int h,
                                             const float4 &u, float a[4])

@@ -580,6 +580,28 @@ __device__ __forceinline__ void random_normal4(uint64_t seed, uint64_t gid, uint
     normals_from_words(philox_block(seed, STREAM_POLICY, gid, k), n);
 }
 
+// Philox4x32-10 with the 128-bit counter given directly: (block, subsequence), key = seed -- rocRAND's generator at
+// rocrand_init(seed, subsequence, 4 * block) for every block that call can express (pinned through tests/mppi_ref.py).  The
+// MPPI planners' blocks have bit 63 set, which philox_block() cannot express (rocRAND's offset is 4 x block in 64 bits).
+__device__ __forceinline__ uint4 philox_counter(uint64_t seed, uint64_t subsequence, uint64_t block)
+{
+    unsigned c0 = (unsigned)block, c1 = (unsigned)(block >> 32), c2 = (unsigned)subsequence, c3 = (unsigned)(subsequence >> 32);
+    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+    // the ten round keys are twenty scalar adds; hidden from the optimiser here, they are not kept in twenty scalar registers
+    // (which the planner's kernel does not have to spare) across the loops around a draw
+    asm volatile("" : "+s"(k0), "+s"(k1));
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return make_uint4(c0, c1, c2, c3);
+}
+
+__device__ __forceinline__ float clamp1(float x) { return fminf(fmaxf(x, -1.0f), 1.0f); }
+
 // per-env registers
 struct Env {
     float sc[13], st[13], uc[4], ut[4], qd[4], ls, t;

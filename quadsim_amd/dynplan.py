@@ -10,11 +10,15 @@ same (seed, env id, step counter) the two planners score the same action sequenc
 ``DynamicsNet`` holds the weights as torch tensors: ``predict`` is the same formula in plain torch (training and debugging
 need no kernel; the fit of the net is the caller's -- examples/mpc_learned.py), ``pack`` builds the padded device image the
 kernels read.  ``LearnedShootingMPC`` is the closed loop on a VecDockingEnv or a single-env shim.  Nothing here imports oracle/.
+
+``learned_mppi_plan`` / ``LearnedMPPI`` are MPPI (``mpc.mppi_plan``'s candidates, weights and update) over the same net and
+image, through a third library (libquadsim_dynmppi.so, include/quadsim_dyn_mppi.h) bound at the end of this module.
 """
 import ctypes as C
 import os
 
 from . import _lib
+from .mpc import MPPI_DEFAULT_LAMBDA, MPPI_DEFAULT_SIGMA
 
 OBS_DIM, ACT_DIM, IN_DIM = 12, 4, 16
 MAX_PATHS, MAX_HORIZON, MAX_K = 65536, 1024, 1 << 36
@@ -299,5 +303,157 @@ class LearnedShootingMPC:
         R, D = [], []
         for _ in range(int(steps)):
             _, r, d, _ = self.env.step(self.act())
+            R.append([float(r)]); D.append([bool(d)])
+        return torch.tensor(R, dtype=torch.float32), torch.tensor(D, dtype=torch.bool)
+
+
+# ---------------------------------------------------------------------------------------------------- MPPI over the net
+# libquadsim_dynmppi.so (include/quadsim_dyn_mppi.h): a library of its own, bound here beside the shooting planner's.  It takes
+# the image that DynamicsNet.pack builds and the net's widths; nothing of libquadsim_dyn.so's host state.
+MPPI_EXPORTS = ["qsdm_version", "qsdm_last_error", "qsdm_workspace_bytes", "qsdm_mppi_plan"]
+MPPI_MAX_ITERATIONS, MPPI_MAX_K = 16, 1 << 33
+
+_dynmppi = None
+
+
+def load_mppi():
+    """dlopen libquadsim_dynmppi.so; raises QuadsimError if it has not been built (there is no fallback)"""
+    global _dynmppi
+    if _dynmppi is not None:
+        return _dynmppi
+    if not os.path.exists(_lib.DYNMPPI_LIB_PATH):
+        raise _lib.QuadsimError("%s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % _lib.DYNMPPI_LIB_PATH)
+    import torch  # noqa: F401  (its HIP runtime must be the resident one: see _lib.load)
+    lib = C.CDLL(_lib.DYNMPPI_LIB_PATH)
+    vp, i64, u64, i32, f32 = C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_float
+    sig = {
+        "qsdm_version": [],
+        "qsdm_workspace_bytes": [i64, i32, i32, C.POINTER(C.c_size_t)],
+        "qsdm_mppi_plan": [vp, i32, i32, i64, vp, u64, u64, u64, i32, i32, i32, f32, f32, i32] + [vp] * 11,
+    }
+    for name, args in sig.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, C.c_int
+    lib.qsdm_last_error.argtypes, lib.qsdm_last_error.restype = [], C.c_char_p
+    _dynmppi = lib
+    return lib
+
+
+def check_mppi(rc, what):
+    if rc != 0:
+        raise _lib.QuadsimError("%s failed (%d): %s" % (what, rc, load_mppi().qsdm_last_error().decode("utf-8", "replace")))
+
+
+def check_mppi_plan_args(horizon, paths, iterations, lam, sigma, shift=False, k=0, n=1):
+    """-> (horizon, paths, iterations, lam, sigma, shift as 0 / 1, k, n); ValueError for what qsdm_mppi_plan would refuse, before
+    anything touches the library or the GPU"""
+    import math
+    horizon, paths, _, n = check_plan_args(horizon, paths, 0, n)
+    iterations, k = int(iterations), int(k)
+    if not 1 <= iterations <= MPPI_MAX_ITERATIONS:
+        raise ValueError("iterations must be in [1, %d], got %d" % (MPPI_MAX_ITERATIONS, iterations))
+    if not 0 <= k < MPPI_MAX_K:
+        raise ValueError("k must be in [0, 2^33), got %d" % k)
+    lam, sigma = float(lam), float(sigma)
+    if not (lam > 0.0 and math.isfinite(lam)):
+        raise ValueError("lam must be positive and finite, got %r" % lam)
+    if not (sigma >= 0.0 and math.isfinite(sigma)):
+        raise ValueError("sigma must be >= 0 and finite, got %r" % sigma)
+    if isinstance(shift, bool):
+        shift = int(shift)
+    if shift not in (0, 1) or isinstance(shift, float):
+        raise ValueError("shift must be False / True (0 / 1), got %r" % (shift,))
+    return horizon, paths, iterations, lam, sigma, int(shift), k, n
+
+
+def learned_mppi_plan(net, obs, horizon=20, paths=200, iterations=2, lam=MPPI_DEFAULT_LAMBDA, sigma=MPPI_DEFAULT_SIGMA, nominal=None,
+                      shift=False, noise=None, seed=0, k=0, gid0=0, return_scores=False, return_trace=False, return_candidates=False,
+                      return_traj=False):
+    """One MPPI plan per row of `obs` [N,12] (a contiguous float32 tensor on the net's device) through `net`: `iterations`
+    rounds of `paths` Gaussian candidates (standard deviation `sigma`, clamped to [-1, 1]) around the nominal action sequence,
+    rolled through the net and scored by position as ``learned_shooting_plan`` scores them; after each round the nominal becomes
+    the mean of the candidates weighted by exp((score - best) / lam).  `nominal` [N,horizon,4] warm-starts the plan (zeros
+    without it), read one step ahead with `shift`; `noise` [iterations,paths,horizon,4] replaces the keyed draws (shared by the
+    rows).  Returns a dict of device tensors: actions [N,4] (= nominal[:, 0]), nominal [N,horizon,4], best_score [N] float64,
+    plus scores [N,iterations,paths] float64, trace [N,iterations+1,horizon,4], candidates [N,paths,horizon,4] and traj
+    [N,paths,horizon,12] (both of the last round) on request.  The draws are keyed by (seed, gid0 + i, k, round, candidate,
+    step) as ``mpc.mppi_plan``'s: a repeated plan is identical, and a row planned alone equals the same row (same gid) inside a
+    batch, bit for bit.  2 x iterations launches on torch's current stream; nothing synchronises with the host.
+
+    The defaults of `lam` and `sigma` are ``mpc.mppi_plan``'s, tuned on the exact simulator's REWARD objective; they were not
+    tuned on this position score or on a learned model and are untuned here."""
+    import torch
+    if not isinstance(net, DynamicsNet):
+        raise ValueError("net must be a DynamicsNet, got %r" % type(net).__name__)
+    if not (isinstance(obs, torch.Tensor) and obs.dtype == torch.float32 and obs.dim() == 2 and obs.shape[1] == OBS_DIM
+            and obs.device == net.device and obs.is_contiguous()):
+        raise ValueError("obs must be a contiguous float32 tensor of shape [N, %d] on %s" % (OBS_DIM, net.device))
+    horizon, paths, iterations, lam, sigma, shift, k, n = check_mppi_plan_args(horizon, paths, iterations, lam, sigma, shift, k, obs.shape[0])
+    seed, gid0 = int(seed), int(gid0)
+    if not (0 <= seed < 1 << 64 and 0 <= gid0 and gid0 + n <= 1 << 48):
+        raise ValueError("seed must fit 64 bits and gid0 + N 48 bits")
+    for name, t, shape in (("nominal", nominal, (n, horizon, 4)), ("noise", noise, (iterations, paths, horizon, 4))):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == shape
+                                  and t.device == net.device and t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float32 tensor of shape %s on %s" % (name, list(shape), net.device))
+    image = net.pack()
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=net.device)     # noqa: E731
+    out = {"actions": new((n, 4), torch.float32), "nominal": new((n, horizon, 4), torch.float32), "best_score": new((n,), torch.float64)}
+    if return_scores:
+        out["scores"] = new((n, iterations, paths), torch.float64)
+    if return_trace:
+        out["trace"] = new((n, iterations + 1, horizon, 4), torch.float32)
+    if return_candidates:
+        out["candidates"] = new((n, paths, horizon, 4), torch.float32)
+    if return_traj:
+        out["traj"] = new((n, paths, horizon, OBS_DIM), torch.float32)
+    lib = load_mppi()
+    nbytes = C.c_size_t(0)
+    check_mppi(lib.qsdm_workspace_bytes(n, horizon, paths, C.byref(nbytes)), "qsdm_workspace_bytes")
+    work = new((int(nbytes.value),), torch.uint8)         # torch's caching allocator: no device allocation in steady state
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
+    with torch.cuda.device(net.device):
+        check_mppi(lib.qsdm_mppi_plan(p(image), net.h1, net.h2, n, p(obs), seed, gid0, k, horizon, paths, iterations, lam, sigma, shift,
+                                      p(nominal), p(noise), p(work), p(out["actions"]), p(out["nominal"]), p(out["best_score"]),
+                                      p(out.get("scores")), p(out.get("trace")), p(out.get("candidates")), p(out.get("traj")),
+                                      C.c_void_p(torch.cuda.current_stream(net.device).cuda_stream)), "qsdm_mppi_plan")
+    return out
+
+
+class LearnedMPPI(LearnedShootingMPC):
+    """``mpc.MPPI`` with a learned model, with the interface of ``LearnedShootingMPC``: ``act()`` plans from the env's LAST
+    observation (shifting the previous nominal by one step after the first call) and returns the actions; ``run(steps)`` is the
+    closed loop ``a = act(); env.step(a)`` and, after each step, zeroes the nominal of the envs whose episode ended;
+    ``reset()`` forgets the nominal.  The nominal [N,horizon,4] stays on the device between plans.  `env` is a VecDockingEnv or
+    a single-env shim.  `lam` and `sigma` default to ``mpc.mppi_plan``'s values, which were tuned on the exact simulator's reward
+    and are untuned for this planner."""
+
+    def __init__(self, env, net, horizon=20, paths=200, iterations=2, lam=MPPI_DEFAULT_LAMBDA, sigma=MPPI_DEFAULT_SIGMA):
+        super().__init__(env, net, horizon, paths)
+        _, _, self.iterations, self.lam, self.sigma, _, _, _ = check_mppi_plan_args(horizon, paths, iterations, lam, sigma)
+        self.nominal = None
+
+    def reset(self):
+        self.nominal = None
+
+    def act(self):
+        obs, seed, k, gid0 = self._inputs()
+        self.last_plan = learned_mppi_plan(self.net, obs, self.horizon, self.paths, self.iterations, self.lam, self.sigma,
+                                           nominal=self.nominal, shift=self.nominal is not None, seed=seed, k=k, gid0=gid0)
+        self.nominal = self.last_plan["nominal"]
+        a = self.last_plan["actions"]
+        return a[0].cpu().numpy() if self.single else a
+
+    def run(self, steps):
+        """as ``LearnedShootingMPC.run``; a new episode starts from a cold nominal"""
+        from .mpc import _closed_loop
+        if not self.single:
+            return _closed_loop(self.env, self.act, steps, lambda d: self.nominal.masked_fill_(d.bool().view(-1, 1, 1), 0.0))
+        import torch
+        R, D = [], []
+        for _ in range(int(steps)):
+            _, r, d, _ = self.env.step(self.act())
+            if d:
+                self.nominal.zero_()
             R.append([float(r)]); D.append([bool(d)])
         return torch.tensor(R, dtype=torch.float32), torch.tensor(D, dtype=torch.bool)
