@@ -2,7 +2,7 @@
 """MPC through a LEARNED dynamics net, trained while it controls: the loop of model_train (MPC-based_RL.py:213-259) on N envs.
 
     python examples/mpc_learned.py [--envs 16] [--episodes 5] [--max-steps 600] [--horizon 20] [--paths 200]
-                                   [--planner {shooting,mppi}] [--iterations 2] [--lam L] [--sigma S]
+                                   [--planner {shooting,mppi}] [--iterations 2] [--lam L] [--sigma S] [--fit {torch,hip}]
 
 Per step: plan with the learned net (--planner shooting: learned_shooting_plan, every candidate of every env in one launch;
 --planner mppi: learned_mppi_plan, `iterations` rounds of `paths` Gaussian candidates around a warm-started nominal, whose
@@ -10,7 +10,10 @@ lam / sigma defaults are mpc.mppi_plan's and were not tuned for a learned model)
 (obs, act, delta) to a device-side buffer.  After each episode (the auto-resetting envs each contribute their first episode):
 100 Adam steps of batch 128 at lr 1e-4 on the normalised delta (train_dynamic, :120-128) in plain torch, the normalisers
 refreshed from the buffer, the net re-packed for the planner.  Prints the mean episode return after every episode, as the
-script prints episode_reward.  The fit is not part of the library: DynamicsNet.predict_delta is the formula, torch trains it."""
+script prints episode_reward.  The fit is not part of the library: DynamicsNet.predict_delta is the formula, torch trains it.
+--fit hip runs the same 100 steps in one launch instead (DynamicsNet.fit, libquadsim_dynfit.so: tf.train.AdamOptimizer's
+formula, keyed batch draws, a fixed summation order): two runs with the same arguments print the same lines.  The default
+stays torch."""
 import argparse
 import os
 import sys
@@ -49,14 +52,16 @@ def main():
     ap.add_argument("--iterations", type=int, default=2, help="mppi: refinement rounds per plan")
     ap.add_argument("--lam", type=float, default=qa.mpc.MPPI_DEFAULT_LAMBDA, help="mppi: temperature of the weights")
     ap.add_argument("--sigma", type=float, default=qa.mpc.MPPI_DEFAULT_SIGMA, help="mppi: standard deviation of the candidates")
+    ap.add_argument("--fit", choices=("torch", "hip"), default="torch", help="the fit after each episode: the torch loop or DynamicsNet.fit")
     args = ap.parse_args()
     n = args.envs
     env = qa.VecDockingEnv("docking-v0", num_envs=n, seed=1)
     dev = env.device
     net = qa.DynamicsNet(200, 100, device=dev)
-    for p in net.parameters():
-        p.requires_grad_(True)
-    opt = torch.optim.Adam(net.parameters(), lr=1.0e-4)
+    if args.fit == "torch":
+        for p in net.parameters():
+            p.requires_grad_(True)
+        opt = torch.optim.Adam(net.parameters(), lr=1.0e-4)
     if args.planner == "mppi":
         mpc = qa.LearnedMPPI(env, net, args.horizon, args.paths, args.iterations, args.lam, args.sigma)
     else:
@@ -89,7 +94,10 @@ def main():
                 break
         net.set_normalisers(in_mean=buf_x[:size].mean(0), in_std=buf_x[:size].std(0), out_mean=buf_d[:size].mean(0),
                             out_std=buf_d[:size].std(0))
-        loss = train_dynamic(net, opt, buf_x, buf_d, size)
+        if args.fit == "hip":
+            loss = float(net.fit(buf_x, buf_d, size, iters=100, batch=128, lr=1.0e-4, seed=1)["loss"][-1])
+        else:
+            loss = train_dynamic(net, opt, buf_x, buf_d, size)
         net.pack()                                           # the optimiser updated the weights in place: the image follows
         print("episode %d: %d steps, mean episode return %.3f, %d transitions, model loss %.4g"
               % (episode, step + 1, float(ret.mean()), size, loss), flush=True)

@@ -13,8 +13,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("QUADSIM_HIP_LIB") or os.path.join(CSRC, "libquadsim_hip.so")  # override: A/B builds
 SOURCES = [os.path.join(CSRC, "quadsim_hip.hip")]
 # every fragment of the one translation unit is a rebuild dependency (dynplan_*.hpp belong to the second library,
-# dynmppi_*.hpp to the third)
-HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith(("dynplan_", "dynmppi_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
+# dynmppi_*.hpp to the third, dynfit_*.hpp to the fourth)
+HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith(("dynplan_", "dynmppi_", "dynfit_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
 # the second library, libquadsim_dyn.so (include/quadsim_dyn.h; bound in dynplan.py): its own translation unit and code object
 DYN_LIB_PATH = os.environ.get("QUADSIM_DYN_LIB") or os.path.join(CSRC, "libquadsim_dyn.so")
 DYN_SOURCES = [os.path.join(CSRC, "dynplan.hip")]
@@ -25,6 +25,12 @@ DYNMPPI_LIB_PATH = os.environ.get("QUADSIM_DYNMPPI_LIB") or os.path.join(CSRC, "
 DYNMPPI_SOURCES = [os.path.join(CSRC, "dynmppi.hip")]
 DYNMPPI_HEADERS = [os.path.join(CSRC, h) for h in ("dynmppi_kernels.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp")] + [
     os.path.join(HERE, "..", "include", "quadsim_dyn_mppi.h")]
+# the fourth library, libquadsim_dynfit.so (include/quadsim_dyn_fit.h; bound in dynplan.py): the Adam fit of the learned net.  It
+# takes the net's own tensors, not the image, and shares only the Philox generator of quadsim_device.hpp
+DYNFIT_LIB_PATH = os.environ.get("QUADSIM_DYNFIT_LIB") or os.path.join(CSRC, "libquadsim_dynfit.so")
+DYNFIT_SOURCES = [os.path.join(CSRC, "dynfit.hip")]
+DYNFIT_HEADERS = [os.path.join(CSRC, h) for h in ("dynfit_kernels.hpp", "quadsim_device.hpp")] + [
+    os.path.join(HERE, "..", "include", "quadsim_dyn_fit.h")]
 
 QS_OK = 0
 KIND_V0, KIND_V2, KIND_V1, KIND_HOVER = 0, 1, 2, 3
@@ -183,11 +189,24 @@ def build_dynmppi_library(force=False, verbose=False):
     return DYNMPPI_LIB_PATH
 
 
+def build_dynfit_library(force=False, verbose=False):
+    """libquadsim_dynfit.so with the flags of the main library -> its path"""
+    if not force and _up_to_date(DYNFIT_LIB_PATH, DYNFIT_SOURCES + DYNFIT_HEADERS):
+        return DYNFIT_LIB_PATH
+    cmd = [hipcc_path(), "-std=c++20", "-O3", "-fno-slp-vectorize", "-ffp-contract=on", "--offload-arch=gfx950", "-fPIC", "-shared",
+           "-Wno-unused-result", *DYNFIT_SOURCES, "-o", DYNFIT_LIB_PATH]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return DYNFIT_LIB_PATH
+
+
 def build_library(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all three libraries, returns the main one's
+    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all four libraries, returns the main one's
     path."""
     build_dyn_library(force, verbose)
     build_dynmppi_library(force, verbose)
+    build_dynfit_library(force, verbose)
     deps = SOURCES + HEADERS
     if not force and _up_to_date(LIB_PATH, deps):
         return LIB_PATH

@@ -11,6 +11,9 @@ same (seed, env id, step counter) the two planners score the same action sequenc
 need no kernel; the fit of the net is the caller's -- examples/mpc_learned.py), ``pack`` builds the padded device image the
 kernels read.  ``LearnedShootingMPC`` is the closed loop on a VecDockingEnv or a single-env shim.  Nothing here imports oracle/.
 
+``DynamicsNet.fit`` is Dynamic_Net.train_dynamic (:120-128) on the device: every Adam step of a fit in one launch, through a
+fourth library (libquadsim_dynfit.so, include/quadsim_dyn_fit.h) bound above the class.
+
 ``learned_mppi_plan`` / ``LearnedMPPI`` are MPPI (``mpc.mppi_plan``'s candidates, weights and update) over the same net and
 image, through a third library (libquadsim_dynmppi.so, include/quadsim_dyn_mppi.h) bound at the end of this module.
 """
@@ -93,6 +96,76 @@ def check_plan_args(horizon, paths, k=0, n=1):
         raise ValueError("n * ceil(paths / 16) must be below 2^31, got %d x %d" % (n, (paths + 15) // 16))
     return horizon, paths, k, n
 
+# ---------------------------------------------------------------------------------------------------- the fit of the net
+# libquadsim_dynfit.so (include/quadsim_dyn_fit.h): a library of its own.  It takes the net's own tensors (DynamicsNet.fit), not
+# the packed image.
+FIT_EXPORTS = ["qsdf_version", "qsdf_last_error", "qsdf_fit"]
+FIT_MAX_BATCH, FIT_MAX_ITERS, FIT_MAX_K = 256, 4096, 1 << 48
+FIT_BETA1, FIT_BETA2, FIT_EPS = 0.9, 0.999, 1.0e-8          # tf.train.AdamOptimizer's defaults
+
+
+class QsdfNet(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("h1", C.c_int32), ("h2", C.c_int32), ("reserved", C.c_int32),
+                ("w", C.c_void_p * 6), ("m", C.c_void_p * 6), ("v", C.c_void_p * 6)] + [
+        (k, C.c_void_p) for k in ("in_mean", "in_rscale", "out_mean", "out_rscale")]
+
+
+_dynfit = None
+
+
+def load_fit():
+    """dlopen libquadsim_dynfit.so; raises QuadsimError if it has not been built (there is no fallback)"""
+    global _dynfit
+    if _dynfit is not None:
+        return _dynfit
+    if not os.path.exists(_lib.DYNFIT_LIB_PATH):
+        raise _lib.QuadsimError("%s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % _lib.DYNFIT_LIB_PATH)
+    import torch  # noqa: F401  (its HIP runtime must be the resident one: see _lib.load)
+    lib = C.CDLL(_lib.DYNFIT_LIB_PATH)
+    vp, i64, u64, i32, f64 = C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_double
+    lib.qsdf_version.argtypes, lib.qsdf_version.restype = [], C.c_int
+    lib.qsdf_fit.argtypes = [C.POINTER(QsdfNet), vp, vp, i64, i64, i32, i32, f64, f64, f64, f64, i64, u64, u64, vp, vp, vp,
+                             C.POINTER(C.c_void_p * 6), vp]
+    lib.qsdf_fit.restype = C.c_int
+    lib.qsdf_last_error.argtypes, lib.qsdf_last_error.restype = [], C.c_char_p
+    _dynfit = lib
+    return lib
+
+
+def check_fit(rc, what):
+    if rc != 0:
+        raise _lib.QuadsimError("%s failed (%d): %s" % (what, rc, load_fit().qsdf_last_error().decode("utf-8", "replace")))
+
+
+def check_fit_args(h1, h2, capacity, size, iters=100, batch=128, lr=1.0e-4, beta1=FIT_BETA1, beta2=FIT_BETA2, eps=FIT_EPS, t0=0, seed=0, k=0):
+    """-> (size, iters, batch, lr, beta1, beta2, eps, t0, seed, k); ValueError for what qsdf_fit would refuse, before anything
+    touches the library or the GPU"""
+    import math
+    check_widths(h1, h2)
+    capacity, size, iters, batch, t0, seed, k = int(capacity), int(size), int(iters), int(batch), int(t0), int(seed), int(k)
+    lr, beta1, beta2, eps = float(lr), float(beta1), float(beta2), float(eps)
+    if not 1 <= batch <= FIT_MAX_BATCH:
+        raise ValueError("batch must be in [1, %d], got %d" % (FIT_MAX_BATCH, batch))
+    if not 1 <= iters <= FIT_MAX_ITERS:
+        raise ValueError("iters must be in [1, %d], got %d" % (FIT_MAX_ITERS, iters))
+    if not 1 <= capacity < 1 << 31:
+        raise ValueError("capacity must be in [1, 2^31), got %d" % capacity)
+    if not 1 <= size <= capacity:
+        raise ValueError("size must be in [1, capacity = %d], got %d" % (capacity, size))
+    if not (t0 >= 0 and t0 + iters < 1 << 31):
+        raise ValueError("t0 must be >= 0 with t0 + iters below 2^31, got %d" % t0)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must fit 64 bits, got %d" % seed)
+    if not 0 <= k < FIT_MAX_K:
+        raise ValueError("k must be in [0, 2^48), got %d" % k)
+    for name, val in (("lr", lr), ("eps", eps)):
+        if not math.isfinite(val):
+            raise ValueError("%s must be finite, got %r" % (name, val))
+    for name, val in (("beta1", beta1), ("beta2", beta2)):
+        if not 0.0 <= val < 1.0:
+            raise ValueError("%s must be in [0, 1), got %r" % (name, val))
+    return size, iters, batch, lr, beta1, beta2, eps, t0, seed, k
+
 
 class DynamicsNet:
     """Dynamic_Net (MPC-based_RL.py:83-136): 16 -> h1 -> h2 -> 12, ReLU, on normalised inputs and outputs.  The weights are
@@ -116,6 +189,7 @@ class DynamicsNet:
         for k, v in init.items():
             setattr(self, k, v.to(self.device, torch.float32).contiguous())
         self._image, self._image_key = None, None
+        self.adam_m, self.adam_v, self.fit_steps = None, None, 0
         self.set_normalisers()
 
     # ------------------------------------------------------------------ construction
@@ -157,6 +231,7 @@ class DynamicsNet:
             return a
         vals = {"in_mean": arr(in_mean, IN_DIM, 0.0), "in_rscale": 1.0 / (arr(in_std, IN_DIM, 1.0) + STD_EPS),
                 "out_mean": arr(out_mean, OBS_DIM, 0.0), "out_std": arr(out_std, OBS_DIM, 1.0)}
+        vals["out_rscale"] = 1.0 / (vals["out_std"] + STD_EPS)     # the scale of the fit's target, kept as in_rscale is
         for k, v in vals.items():
             setattr(self, k, torch.as_tensor(v.astype(np.float32)).to(self.device).contiguous())
         self._image_key = None
@@ -215,6 +290,63 @@ class DynamicsNet:
                                    C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "qsd_net_pack")
         self._image_key = key
         return self._image
+
+    # ------------------------------------------------------------------ the fit on the device
+    def reset_optimizer(self):
+        """forget Adam's moments and the step count (``fit`` creates them again, zeros, on its next call)"""
+        self.adam_m, self.adam_v, self.fit_steps = None, None, 0
+
+    def fit(self, buf_x, buf_d, size, iters=100, batch=128, lr=1.0e-4, seed=0, indices=None, return_indices=False, return_grads=False,
+            k=None, beta1=FIT_BETA1, beta2=FIT_BETA2, eps=FIT_EPS):
+        """Dynamic_Net.train_dynamic (MPC-based_RL.py:120-128) in ONE launch (qsdf_fit of libquadsim_dynfit.so): `iters` Adam
+        steps (tf.train.AdamOptimizer's formula) on batches of `batch` rows drawn with replacement from the first `size` rows of
+        buf_x [capacity,16] (observation and action) / buf_d [capacity,12] (delta), contiguous float32 tensors on the net's
+        device.  The weights, ``adam_m`` / ``adam_v`` (lists of six tensors, zeros on first use) and ``fit_steps`` are updated
+        in place; the draws are keyed by (seed, k, Adam step, row), k = ``fit_steps`` at the call unless given, or replaced
+        by `indices` [iters,batch] int32.  Returns a dict of device tensors: loss [iters] (the batch loss before each step), plus
+        indices [iters,batch] int32 and grads (the six gradients of the last iteration) on request.  Launched on torch's current
+        stream; nothing synchronises with the host.  A repeated fit from the same state gives the same bits."""
+        import torch
+        if self.device.type != "cuda":
+            raise _lib.QuadsimError("DynamicsNet.fit needs the net on a HIP device, it is on %s; there is no CPU path" % self.device)
+        for name, t, cols in (("buf_x", buf_x, IN_DIM), ("buf_d", buf_d, OBS_DIM)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == cols
+                    and t.device == self.device and t.is_contiguous()):
+                raise ValueError("%s must be a contiguous float32 tensor of shape [capacity, %d] on %s" % (name, cols, self.device))
+        if buf_x.shape[0] != buf_d.shape[0]:
+            raise ValueError("buf_x and buf_d must have the same capacity, got %d and %d" % (buf_x.shape[0], buf_d.shape[0]))
+        k = self.fit_steps if k is None else k
+        size, iters, batch, lr, beta1, beta2, eps, t0, seed, k = check_fit_args(
+            self.h1, self.h2, buf_x.shape[0], size, iters, batch, lr, beta1, beta2, eps, self.fit_steps, seed, k)
+        if indices is not None and not (isinstance(indices, torch.Tensor) and indices.dtype == torch.int32 and tuple(indices.shape) == (iters, batch)
+                                        and indices.device == self.device and indices.is_contiguous()):
+            raise ValueError("indices must be a contiguous int32 tensor of shape [%d, %d] on %s" % (iters, batch, self.device))
+        ws = self.parameters()
+        for name, t in zip(self.WEIGHTS + ("in_mean", "in_rscale", "out_mean", "out_rscale"), self._tensors()[:8] + [self.out_mean, self.out_rscale]):
+            if not (t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()):
+                raise ValueError("%s must be a contiguous float32 tensor on %s" % (name, self.device))
+        if self.adam_m is None:
+            self.adam_m, self.adam_v = [torch.zeros_like(w) for w in ws], [torch.zeros_like(w) for w in ws]
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=self.device)     # noqa: E731
+        out = {"loss": new((iters,), torch.float32)}
+        if return_indices:
+            out["indices"] = new((iters, batch), torch.int32)
+        grads = None
+        if return_grads:
+            out["grads"] = [torch.empty_like(w) for w in ws]
+            grads = (C.c_void_p * 6)(*[g.data_ptr() for g in out["grads"]])
+        six = lambda ts: (C.c_void_p * 6)(*[t.data_ptr() for t in ts])     # noqa: E731
+        net = QsdfNet(C.sizeof(QsdfNet), self.h1, self.h2, 0, six(ws), six(self.adam_m), six(self.adam_v), self.in_mean.data_ptr(),
+                      self.in_rscale.data_ptr(), self.out_mean.data_ptr(), self.out_rscale.data_ptr())
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
+        lib = load_fit()
+        with torch.cuda.device(self.device):
+            check_fit(lib.qsdf_fit(C.byref(net), p(buf_x), p(buf_d), buf_x.shape[0], size, iters, batch, lr, beta1, beta2, eps, t0, seed, k,
+                                   p(indices), p(out["loss"]), p(out.get("indices")), grads,
+                                   C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "qsdf_fit")
+        self.fit_steps += iters
+        self._image_key = None        # the kernel wrote the weights behind torch's back: their _version did not move
+        return out
 
 
 def learned_shooting_plan(net, obs, horizon=20, paths=200, seed=0, k=0, gid0=0, return_scores=False, return_sequence=False,
