@@ -14,7 +14,7 @@ def _row(key, widths, test):
 
 
 ROWS = [
-    _row(("k_dyn_fit", 64, 64), (64, 64), _F + "test_gradients_loss_and_adam_of_one_step[he_20_10]"),
+    _row(("k_dyn_fit", 64, 64), (64, 64), _F + "test_gradients_loss_and_adam_of_one_step[edge_64_64]"),
     _row(("k_dyn_fit", 128, 128), (128, 128), _F + "test_gradients_loss_and_adam_of_one_step[he_128_128]"),
-    _row(("k_dyn_fit", 208, 112), (208, 112), _F + "test_gradients_loss_and_adam_of_one_step[ref_200_100]"),
+    _row(("k_dyn_fit", 208, 112), (208, 112), _F + "test_gradients_loss_and_adam_of_one_step[edge_208_112]"),
 ]

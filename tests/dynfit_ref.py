@@ -196,7 +196,24 @@ def _backward_as(W, x, d, dtype):
 CAPACITY, SIZE = 300, 257
 STEP_SETS = ("he_20_10", "he_128_128", "ref_200_100", "dead")
 STEP_BATCHES = (1, 17, 128, 256)
+# the width edges (dynplan_ref.EDGE_WIDTHS): one row, a ragged second chunk of 16 rows, eight full chunks -- every path the
+# kernel takes along the batch; the sixteen chunks of 256 rows take no other and stay with STEP_SETS.  step_indices seed 71
+# meets the ReLU-edge condition and the mutant conditions of tests/test_dynfit_cpu.py for every (edge set, batch): the sets
+# have no entry in STEP_SEEDS.
+EDGE_SETS = dr.EDGE_SETS
+EDGE_BATCHES = (1, 17, 128)
 _cache = {}
+
+
+def step_batches(name):
+    return EDGE_BATCHES if name in EDGE_SETS else STEP_BATCHES
+
+
+def last_unit_slices(W):
+    """the gradient elements only the last unit of a hidden layer reaches: {label: (key, index)}"""
+    h1, h2 = W["w1"].shape[0], W["w2"].shape[0]
+    return {"row h1-1 of w1": ("w1", np.s_[h1 - 1]), "row h2-1 of w2": ("w2", np.s_[h2 - 1]),
+            "column h1-1 of w2": ("w2", np.s_[:, h1 - 1]), "column h2-1 of w3": ("w3", np.s_[:, h2 - 1])}
 
 
 def buffer(seed=61):

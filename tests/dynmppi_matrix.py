@@ -21,9 +21,9 @@ def _row(key, widths, test, inherited=False):
 
 
 ROWS = [
-    _row(("k_dynm_roll", 4, 4), (64, 64), _F + "test_steps_scores_and_update[he_20_10]"),
+    _row(("k_dynm_roll", 4, 4), (64, 64), _F + "test_steps_scores_and_update[edge_64_64]"),
     _row(("k_dynm_roll", 8, 8), (128, 128), _F + "test_steps_scores_and_update[he_128_128]"),
-    _row(("k_dynm_roll", 13, 7), (208, 112), _F + "test_steps_scores_and_update[ref_200_100]"),
+    _row(("k_dynm_roll", 13, 7), (208, 112), _F + "test_steps_scores_and_update[edge_208_112]"),
     _row(("k_dynm_update",), None, _F + "test_shapes_keyed_draws_every_iteration[257-5-3]"),
     _row(("k_dyn_finish",), None, _D + "test_draws[3]", inherited=True),
     _row(("k_dyn_pack",), None, _D + "test_padding_is_invisible", inherited=True),

@@ -19,7 +19,7 @@ def _row(key, widths, test):
 ROWS = [
     _row(("k_dyn_plan", 4, 4), (64, 64), "test_steps_scores_and_winner[he_64_64]"),
     _row(("k_dyn_plan", 8, 8), (128, 128), "test_steps_scores_and_winner[he_128_128]"),
-    _row(("k_dyn_plan", 13, 7), (208, 112), "test_steps_scores_and_winner[ref_200_100]"),
+    _row(("k_dyn_plan", 13, 7), (208, 112), "test_edge_widths[edge_208_112]"),
     _row(("k_dyn_finish",), None, "test_draws[3]"),
     _row(("k_dyn_pack",), None, "test_padding_is_invisible"),
 ]

@@ -209,6 +209,62 @@ def pad_net(W, h1, h2):
     return P
 
 
+def weights_edge(h1, h2, seed):
+    """weights_he, dense, with the bias of the LAST unit of each hidden layer at +2: that unit is the one a mishandled, partly
+    filled last group of units would drop, so it has to be alive on the rows a test uses"""
+    W = weights_he(h1, h2, seed)
+    W["b1"][h1 - 1] = 2.0
+    W["b2"][h2 - 1] = 2.0
+    return W
+
+
+# the width edges: hidden widths -> the compiled pair they run on.  (1, 1): one unit, three of every four k-lanes padding;
+# (21, 11): h1 % 4 = 1, h2 % 4 = 3, a partly filled second tile; (64, 64): exact fill; (65, 3) / (3, 65): routed up by one width
+# alone, one unit in a new tile; (128, 113): h2 > 112 is legal on (128, 128) only; (129, 1): routed up by h1 alone; (207, 111):
+# one below both maxima, both % 4 = 3; (208, 112): the maxima, a full image.
+EDGE_WIDTHS = {(1, 1): (64, 64), (21, 11): (64, 64), (64, 64): (64, 64), (65, 3): (128, 128), (3, 65): (128, 128),
+               (128, 113): (128, 128), (129, 1): (208, 112), (207, 111): (208, 112), (208, 112): (208, 112)}
+# the weight seed of entry i: the first seed from 400 + i on for which the float64 reference alone finds every condition of
+# tests/test_dynplan_cpu.py::test_edge_fixture_detects_a_dropped_last_unit and of tests/test_dynfit_cpu.py's edge tests to hold
+# (with a dynfit_ref.step_indices seed in 71..199 for each batch of EDGE_BATCHES; 71 does for all).  400 + i does for all but
+# three.  (1, 1): at 400 the last unit of layer 1 is dead on the one row of batch 1, at 401 the last unit of layer 2 is dead on
+# every plan row.  (65, 3): at 403 the last unit of layer 1 is dead on the one row of batch 1.  (3, 65): at 404 the last unit of
+# layer 2 is dead on every plan row.  The bias of +2 makes a dead last unit rare, not impossible.
+EDGE_WEIGHT_SEEDS = {(1, 1): 402, (21, 11): 401, (64, 64): 402, (65, 3): 404, (3, 65): 405, (128, 113): 405, (129, 1): 406,
+                     (207, 111): 407, (208, 112): 408}
+
+
+def edge_name(h1, h2):
+    return "edge_%d_%d" % (h1, h2)
+
+
+EDGE_SETS = tuple(edge_name(*w) for w in EDGE_WIDTHS)
+# the shape of the edge tests of the planners: the smallest that fills one tile of 16 candidates twice and leaves a ragged
+# third, two envs (the second far out: large activations), a few steps along the model's own trajectory
+EDGE_N, EDGE_PATHS, EDGE_HORIZON = 2, 33, 5
+EDGE_SEED, EDGE_GID0, EDGE_K = 0x5EED0123456789AB, (1 << 32) - 2, (1 << 32) + 5       # tests/test_gpu_dynplan.py's SEED, GID0, K0
+
+
+def edge_obs():
+    obs = sample_obs(EDGE_N)
+    obs[1] *= 6.0
+    return obs
+
+
+def edge_plan_rows(W):
+    """-> (obs [2,12], acts [2,33,5,4], before [2,33,5,12]): the inputs of every model step of the planners' edge test, along
+    the float64 trajectory (the device steps from its own float32 trajectory, within step_bound of these)"""
+    import shooting_ref
+    obs = edge_obs()
+    acts = np.stack([shooting_ref.actions_fast(EDGE_SEED, EDGE_GID0 + i, EDGE_K, EDGE_PATHS, EDGE_HORIZON) for i in range(EDGE_N)])
+    s = np.repeat(obs.astype(np.float64)[:, None, :], EDGE_PATHS, axis=1)
+    before = np.zeros((EDGE_N, EDGE_PATHS, EDGE_HORIZON, 12))
+    for h in range(EDGE_HORIZON):                          # the last step too: the planner computes it when traj is asked for
+        before[:, :, h] = s
+        s = step64(W, s, acts[:, :, h])
+    return obs, acts, before
+
+
 WEIGHT_SETS = {
     "ref_200_100": lambda: weights_he(200, 100, 31),
     "he_128_128": lambda: weights_he(128, 128, 32),
@@ -218,6 +274,7 @@ WEIGHT_SETS = {
     "dead": weights_dead_relu,
     "cancel": weights_cancel,
 }
+WEIGHT_SETS.update({edge_name(*w): (lambda w=w: weights_edge(w[0], w[1], EDGE_WEIGHT_SEEDS[w])) for w in EDGE_WIDTHS})
 _cache = {}
 
 

@@ -2,7 +2,8 @@
 plain C99 and every symbol it declares is exported by libquadsim_dynfit.so; every refusal the header promises happens before
 anything is launched; tests/dynfit_matrix.py has exactly one row per kernel instantiation of the new code object, none uses
 scratch and each fits the compute unit's LDS; tests/dynfit_ref.py is checked against finite differences and closed forms; and
-no fixture of tests/test_gpu_dynfit.py holds a pre-activation within its forward bound of zero."""
+no fixture of tests/test_gpu_dynfit.py holds a pre-activation within its forward bound of zero; on the width-edge fixtures a
+gradient slot of the last unit of either hidden layer that was left at zero would be out of bound."""
 import os
 import re
 import shutil
@@ -202,6 +203,13 @@ def test_rows_are_exactly_the_kernels_of_the_code_object_without_scratch(notes):
         print("dynfit notes %s %s" % (sym, f))
 
 
+def test_rows_name_a_net_of_exactly_their_widths():
+    """a row's `widths` are the hidden widths of the net its test id names (the widest the instantiation takes)"""
+    for r in dynfit_matrix.ROWS:
+        W = dr.weight_set(re.search(r"\[(\w+)\]$", r["test"]).group(1))
+        assert (W["w1"].shape[0], W["w2"].shape[0]) == r["widths"] == r["key"][1:], r
+
+
 def test_rows_name_existing_gpu_tests():
     files = sorted({r["test"].split("::")[0] for r in dynfit_matrix.ROWS})
     out = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + files, cwd=ROOT,
@@ -274,16 +282,49 @@ def test_fit64_is_the_loop_of_its_parts_and_learns():
 
 
 # ---------------------------------------------------------------------------------------------------- the ReLU-edge condition
-@pytest.mark.parametrize("name", fr.STEP_SETS)
+@pytest.mark.parametrize("name", fr.STEP_SETS + fr.EDGE_SETS)
 def test_no_gpu_fixture_has_a_preactivation_within_its_bound_of_zero(name):
     """grad_bound assumes the device takes the same side of every ReLU as the float64 reference; that is guaranteed only where
     |z| exceeds the forward bound of z.  The allowed share of such elements is zero: every (weight set, batch) that
-    tests/test_gpu_dynfit.py compares with grad_bound is checked here"""
+    tests/test_gpu_dynfit.py compares with grad_bound is checked here, the width edges with their batches included"""
     W = dr.weight_set(name)
     bx, bd = fr.buffer()
-    for batch in fr.STEP_BATCHES:
+    assert fr.step_batches(name) == (fr.EDGE_BATCHES if name.startswith("edge_") else fr.STEP_BATCHES)
+    for batch in fr.step_batches(name):
         rows = fr.step_rows(name, batch)[0]
         assert rows[0] == 0 and (batch < 4 or (rows[1] == fr.SIZE - 1 and rows[2] == rows[batch - 1]))
         assert rows.max() < fr.SIZE
         n = fr.relu_edge(W, bx[rows], bd[rows])
         assert n == 0, "%s, batch %d: %d pre-activations within their bound of zero" % (name, batch, n)
+
+
+# ---------------------------------------------------------------------------------------------------- the width edges
+def test_check_fit_args_accepts_every_edge_width():
+    from quadsim_amd import dynplan
+    for (h1, h2), compiled in dr.EDGE_WIDTHS.items():
+        assert dynplan.check_fit_args(**dict(GOOD, h1=h1, h2=h2, batch=max(fr.EDGE_BATCHES)))[2] == 128
+        assert dynplan.check_widths(h1, h2)[2] == compiled
+    assert fr.EDGE_BATCHES == (1, 17, 128) and fr.EDGE_SETS == dr.EDGE_SETS and not set(fr.EDGE_SETS) & set(fr.STEP_SETS)
+
+
+@pytest.mark.parametrize("name", fr.EDGE_SETS)
+def test_edge_fixture_detects_an_unowned_gradient_slot(name):
+    """for every batch of the edge sets, the float64 gradient exceeds its grad_bound on at least one element of each slice that
+    only the last unit of a hidden layer reaches: a kernel that left those slots at zero could not pass.  The float32
+    restatement of the whole gradient stays inside the bounds on the same rows."""
+    W = dr.weight_set(name)
+    bx, bd = fr.buffer()
+    for batch in fr.EDGE_BATCHES:
+        rows = fr.step_rows(name, batch)[0]
+        x, d = bx[rows], bd[rows]
+        loss, G, lb, E = fr.backward64(W, x, d, with_bound=True)
+        ratios = []
+        for label, (key, at) in fr.last_unit_slices(W).items():
+            r = np.abs(G[key][at]) / E[key][at]
+            ratios.append(float(r.max()))
+            assert (r > 1.0).any(), "%s, batch %d: %s is within its bound of zero everywhere (worst %.3g)" % (name, batch, label, r.max())
+        loss32, G32 = fr._backward_as(W, x, d, np.float32)
+        worst = max(float((np.abs(G32[key].astype(np.float64) - G[key]) / E[key]).max()) for key in fr.GRAD_KEYS)
+        print("dynfit edge %s batch %d |gradient| / bound of the last unit's slices %s; float32 restatement err/bound %.3g, loss %.3g" % (
+            name, batch, " ".join("%.3g" % r for r in ratios), worst, abs(loss32 - loss) / lb))
+        assert worst < 1.0 and abs(loss32 - loss) <= lb

@@ -213,6 +213,14 @@ def test_rows_are_exactly_the_kernels_of_the_code_object(notes):
     assert not any(r["kernel"].startswith("k_dynm_") for r in dynmppi_matrix.ROWS if r["inherited"])
 
 
+def test_rows_with_widths_name_a_net_of_exactly_those_widths():
+    """a row's `widths` are the hidden widths of the net its test id names (the widest the instantiation takes)"""
+    for r in dynmppi_matrix.ROWS:
+        if r["widths"]:
+            W = dr.weight_set(re.search(r"\[(\w+)\]$", r["test"]).group(1))
+            assert (W["w1"].shape[0], W["w2"].shape[0]) == r["widths"] == (16 * r["key"][1], 16 * r["key"][2]), r
+
+
 def test_rows_name_existing_gpu_tests():
     files = sorted({r["test"].split("::")[0] for r in dynmppi_matrix.ROWS})
     out = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + files, cwd=ROOT,

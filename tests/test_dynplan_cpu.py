@@ -3,7 +3,8 @@ symbol it declares is exported by libquadsim_dyn.so; every refusal the header pr
 (no device is present here, so a launch could not succeed); tests/dynplan_matrix.py has exactly one row per kernel and
 instantiation of the new library's code object, no kernel uses scratch or spills and each fits the compute unit's LDS; the
 float32 k-ordered emulation of the contract stays inside the derived bound of tests/dynplan_ref.py on every weight set of the GPU
-tests, and DynamicsNet.predict in float64 is the float64 restatement."""
+tests, and DynamicsNet.predict in float64 is the float64 restatement; the width-edge fixtures of tests/dynplan_ref.py route
+to the instantiation their table names and can detect a dropped last unit of either hidden layer."""
 import ctypes as C
 import os
 import re
@@ -230,6 +231,68 @@ def test_float32_chain_is_inside_the_bound(name):
     print("dynplan ratio float32-emulation %s worst err/bound %.3g" % (name, worst))
     # on the generic nets the bound is within a small factor of what float32 does (the cancelling net is built so that it is not)
     assert worst < 1.0 and (not name.startswith(("he_", "ref_")) or worst > 1e-3)
+
+
+# ---------------------------------------------------------------------------------------------------- the width edges
+def _image_bytes(p1, p2):
+    """include/quadsim_dyn.h: header, three padded layers with rows 16 T + 4 floats apart, four normalisers"""
+    t1, t2 = p1 // 16, p2 // 16
+    return 4 * (4 + 16 * t1 * 20 + 16 * t1 + 16 * t2 * (16 * t1 + 4) + 16 * t2 + 16 * (16 * t2 + 4) + 16 + 64)
+
+
+def test_edge_widths_route_to_the_table(lib):
+    """check_widths, qsd_net_image_bytes (choose_tiles) and DynamicsNet agree with dynplan_ref.EDGE_WIDTHS on every entry: the
+    first compiled pair that covers both widths"""
+    from quadsim_amd import dynplan
+    assert _image_bytes(208, 112) == 120656
+    assert len(dr.EDGE_WIDTHS) == 9 and set(dr.EDGE_WIDTHS.values()) == set(dynplan.COMPILED_WIDTHS)
+    for (h1, h2), compiled in dr.EDGE_WIDTHS.items():
+        assert dynplan.check_widths(h1, h2) == (h1, h2, compiled)
+        nbytes = C.c_size_t(0)
+        assert lib.qsd_net_image_bytes(h1, h2, C.byref(nbytes)) == 0, lib.qsd_last_error()
+        assert nbytes.value == _image_bytes(*compiled), (h1, h2)
+        W = dr.weight_set(dr.edge_name(h1, h2))
+        net = dr.to_net(W, "cpu")
+        assert (net.h1, net.h2, net.compiled) == (h1, h2, compiled)
+        assert W["w1"].shape == (h1, 16) and W["w2"].shape == (h2, h1) and W["w3"].shape == (12, h2)
+        assert all(np.all(W[k] != 0) for k in dr.WEIGHT_KEYS), "an edge set is dense"
+        assert W["b1"][-1] == 2.0 and W["b2"][-1] == 2.0
+
+
+@pytest.mark.parametrize("name", dr.EDGE_SETS)
+def test_edge_fixture_detects_a_dropped_last_unit(name):
+    """on the model steps of the planners' edge test (dynplan_ref.edge_plan_rows), the float64 step of the net with the last
+    unit of layer 1 cut off (column h1 - 1 of w2 zeroed), and of the net with the last unit of layer 2 cut off (column h2 - 1 of
+    w3 zeroed), is out of step_bound on at least one element: a kernel that dropped the unit could not pass.  The float32 chain
+    of the whole net stays inside the bound on the same rows."""
+    W = dr.weight_set(name)
+    h1, h2 = W["w1"].shape[0], W["w2"].shape[0]
+    obs, acts, before = dr.edge_plan_rows(W)
+    assert before.shape == (2, 33, 5, 12) and np.array_equal(before[:, :, 0], np.repeat(obs[:, None], 33, axis=1))
+    ref, bound = dr.step64(W, before, acts, with_bound=True)
+    ratios = []
+    for key, col in (("w2", h1 - 1), ("w3", h2 - 1)):
+        M = dict(W)
+        M[key] = W[key].copy()
+        M[key][:, col] = 0.0
+        r = np.abs(dr.step64(M, before, acts) - ref) / bound
+        ratios.append(float(r.max()))
+        assert (r > 1.0).any(), "%s: zeroing column %d of %s stays inside the bound everywhere (worst %.3g)" % (name, col, key, r.max())
+    err = np.abs(dr.step32(W, before.astype(np.float32), acts).astype(np.float64) - dr.step64(W, before.astype(np.float32), acts))
+    r32 = float((err / dr.step_bound(W, before.astype(np.float32), acts)).max())
+    print("dynplan edge %s seed %d mutant err/bound: w2 column %.3g, w3 column %.3g; float32 chain %.3g" % (
+        name, dr.EDGE_WEIGHT_SEEDS[(h1, h2)], ratios[0], ratios[1], r32))
+    assert r32 < 1.0
+
+
+def test_rows_with_widths_name_a_net_of_exactly_those_widths():
+    """a row's `widths` are the hidden widths of the net its test id names (the widest the instantiation takes)"""
+    from quadsim_amd import dynplan
+    for r in dynplan_matrix.ROWS:
+        if r["widths"]:
+            W = dr.weight_set(re.search(r"\[(\w+)\]$", r["test"]).group(1))
+            assert (W["w1"].shape[0], W["w2"].shape[0]) == r["widths"], r
+            assert dynplan.check_widths(*r["widths"])[2] == r["widths"] == (16 * r["key"][1], 16 * r["key"][2]), r
 
 
 @pytest.mark.parametrize("name", ["ref_200_100", "he_20_10", "cancel"])

@@ -12,7 +12,9 @@ rows of which 257 are valid, the tail NaN.  What is held:
   draws        indices_out bit for bit dynfit_ref.indices; the NaN tail is never read
   invariants   a second run on another stream at other addresses gives the same bits; zero padding of the net is invisible
   the planner  DynamicsNet.fit invalidates the packed image: the next plan runs the updated net
-Measured worst ratios are in profiles/dynfit/README.md."""
+  widths       the one-step, multi-step and padding tests also run dense nets at the width edges of dynplan_ref.EDGE_WIDTHS
+               (h1 % 4 != 0, widths of 1, every routing edge, both maxima) with dynfit_ref.EDGE_BATCHES
+Measured worst ratios are in profiles/dynfit/README.md and profiles/dyn_edges/README.md."""
 import ctypes as C
 
 import numpy as np
@@ -100,13 +102,15 @@ def state_bits_equal(a, b):
 
 
 # ---------------------------------------------------------------------------------------------------- 1, 2: one step
-@pytest.mark.parametrize("name", fr.STEP_SETS)
+@pytest.mark.parametrize("name", fr.STEP_SETS + fr.EDGE_SETS)
 def test_gradients_loss_and_adam_of_one_step(torch, buf, name):
+    """the width edges (dynfit_ref.EDGE_SETS) run EDGE_BATCHES: tests/test_dynfit_cpu.py holds that on these very rows every
+    gradient slice that only the last unit of a hidden layer reaches is out of bound if left at zero"""
     W = dr.weight_set(name)
     bx, bd = fr.buffer()
     M, V = fr.moments(W)
     worst_g, worst_l, worst_a = 0.0, 0.0, 0.0
-    for batch in fr.STEP_BATCHES:
+    for batch in fr.step_batches(name):
         idx = fr.step_rows(name, batch)
         loss64, G, lb, E = fr.backward64(W, bx[idx[0]], bd[idx[0]], with_bound=True)
         for t0 in (0, 7):
@@ -154,10 +158,46 @@ def test_keyed_draws(torch, buf, seed):
     assert state_bits_equal(a, b) and same_bits(a["loss"], b["loss"])
 
 
+# ---------------------------------------------------------------------------------------------------- 3b: the step counter's edge
+def test_step_counter_at_its_upper_edge(torch, buf):
+    """t0 = 2^31 - 2 is the last step the contract takes (t0 + iters below 2^31): the counter enters the Philox block's upper
+    word and, as t = t0 + 1 = 2^31 - 1, Adam's bias correction, where both powers have long underflowed to 0 and lr_t = lr"""
+    from quadsim_amd import dynplan
+    W = dr.weight_set("he_20_10")
+    M, V = fr.moments(W)
+    batch, lr = 37, 1e-2
+    for t0 in (10 ** 5, 2 ** 31 - 2):
+        assert dynplan.check_fit_args(20, 10, fr.CAPACITY, fr.SIZE, 1, batch, lr, t0=t0, seed=SEED, k=9)[7] == t0
+        out = run(torch, W, M, V, buf, 1, batch, lr=lr, t0=t0, seed=SEED, k=9, want_indices=True, want_grads=True)
+        ref = fr.indices(SEED, 9, t0, batch, fr.SIZE)
+        assert same_bits(out["indices"], ref[None]), t0
+        assert not np.array_equal(ref, fr.indices(SEED, 9, t0 - 1, batch, fr.SIZE)) and not np.array_equal(ref, fr.indices(SEED, 9, t0 & 0xFFFF, batch, fr.SIZE))
+        worst = 0.0
+        for key in KEYS:
+            g = out["grads"][key]
+            x64 = fr.adam64(W[key], M[key], V[key], g, t0 + 1, lr)
+            bounds = fr.adam_bound(W[key], M[key], V[key], g, t0 + 1, lr)
+            for s, x, b in zip("wmv", x64, bounds):
+                e = np.abs(out[s][key].astype(np.float64) - x)
+                worst = max(worst, float((e / b).max()))
+                assert (e <= b).all(), "t0 %d: %s of %s out of the update bound, worst err / bound %.3g" % (t0, s, key, (e / b).max())
+            assert np.median(np.abs(x64[0] - W[key]) / bounds[0]) > 100.0, (t0, key)
+        # the gradient itself does not depend on t0: the rows are the reference's, so it is backward64's within grad_bound
+        bx, bd = fr.buffer()
+        _, G, lb, E = fr.backward64(W, bx[ref], bd[ref], with_bound=True)
+        assert fr.relu_edge(W, bx[ref], bd[ref]) == 0                  # grad_bound's condition, on the reference alone
+        assert all((np.abs(out["grads"][key] - G[key]) <= E[key]).all() for key in KEYS), t0
+        print("dynfit ratio t0 %d adam worst err/bound %.3g" % (t0, worst))
+    assert fr.lr_t64(2 ** 31 - 1, lr) == lr
+
+
 # ---------------------------------------------------------------------------------------------------- 4: one launch = the sequence
-@pytest.mark.parametrize("batch", [17, 128])
-@pytest.mark.parametrize("name", ["he_20_10", "ref_200_100", "he_128_128"])
+@pytest.mark.parametrize("name,batch", [(name, batch) for name in ("he_20_10", "ref_200_100", "he_128_128") for batch in (17, 128)]
+                         + [(name, 17) for name in ("edge_21_11", "edge_207_111", "edge_208_112")],
+                         ids=lambda v: str(v))
 def test_one_launch_equals_the_sequence(torch, buf, name, batch):
+    """(the width edges too: five steps in one launch keep the LDS padding of W2 and W3 for the whole call, five launches
+    load it again -- equal bits show that the padding stayed harmless)"""
     W = dr.weight_set(name)
     M, V = fr.moments(W)
     whole = run(torch, W, M, V, buf, 5, batch, t0=2)
@@ -185,20 +225,32 @@ def test_run_twice_same_bits_on_another_stream(torch, buf):
 
 
 # ---------------------------------------------------------------------------------------------------- 6: padding
-def test_padding_is_invisible(torch, buf):
-    W = dr.weight_set("he_20_10")
-    P = dr.pad_net(W, 64, 64)
+def padding_is_invisible(torch, buf, name, to):
+    """three steps on the net and on the net with zero units appended up to `to`: the same bits on the cut, and every padded
+    entry of w, m, v and the gradients exactly zero"""
+    W = dr.weight_set(name)
+    h1, h2 = W["w1"].shape[0], W["w2"].shape[0]
+    P = dr.pad_net(W, *to)
+    assert (P["w1"].shape[0], P["w2"].shape[0]) == tuple(to) and to[0] >= h1 and to[1] >= h2
     Z, ZP = fr.zero_state(W), fr.zero_state(P)
     a = run(torch, W, Z, Z, buf, 3, 37, want_grads=True)
     b = run(torch, P, ZP, ZP, buf, 3, 37, want_grads=True)
-    assert same_bits(a["loss"], b["loss"])
-    cut = {"w1": np.s_[:20], "b1": np.s_[:20], "w2": np.s_[:10, :20], "b2": np.s_[:10], "w3": np.s_[:, :10], "b3": np.s_[:]}
+    assert same_bits(a["loss"], b["loss"]), (name, to)
+    cut = {"w1": np.s_[:h1], "b1": np.s_[:h1], "w2": np.s_[:h2, :h1], "b2": np.s_[:h2], "w3": np.s_[:, :h2], "b3": np.s_[:]}
     for key in KEYS:
         for s in ("w", "m", "v", "grads"):
-            assert same_bits(a[s][key], b[s][key][cut[key]]), (s, key)
+            assert same_bits(a[s][key], b[s][key][cut[key]]), (name, to, s, key)
             rest = b[s][key].copy()
             rest[cut[key]] = 0.0
-            assert not rest.any(), "%s of %s: a padded entry is not zero" % (s, key)
+            assert not rest.any(), "%s to %s, %s of %s: a padded entry is not zero" % (name, to, s, key)
+
+
+def test_padding_is_invisible(torch, buf):
+    padding_is_invisible(torch, buf, "he_20_10", (64, 64))
+    # the width edges: to the multiple of 4 the kernel rounds to and to the compiled pair; from one unit of layer 2 to the maxima
+    padding_is_invisible(torch, buf, "edge_21_11", (24, 12))
+    padding_is_invisible(torch, buf, "edge_21_11", (64, 64))
+    padding_is_invisible(torch, buf, "edge_129_1", (208, 112))
 
 
 # ---------------------------------------------------------------------------------------------------- 7: the planner sees the fit

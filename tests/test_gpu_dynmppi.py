@@ -13,7 +13,9 @@ checks them afterwards.  What is held, on every element of every output:
   earlier iterations through the prefix property: scores[:, :j] and trace[:, :j + 1] of a 3-iteration call are those of the
               j-iteration call bit for bit, whose candidates and traj are iteration j - 1's
 The mapping has edges at 16 candidates (a wave's tile), 64 (a roll-out workgroup's four tiles), 128 (the update workgroup's
-rows), 1024 (its threads), 8 horizon steps (a row's lanes) and at cus x 4 tiles, where the persistent grid starts to loop.  Measured worst ratios are in profiles/dynmppi/README.md."""
+rows), 1024 (its threads), 8 horizon steps (a row's lanes) and at cus x 4 tiles, where the persistent grid starts to loop.  The
+tests over the nets also run a dense net at every width edge of dynplan_ref.EDGE_WIDTHS.  Measured worst ratios are in
+profiles/dynmppi/README.md and profiles/dyn_edges/README.md."""
 import ctypes as C
 
 import numpy as np
@@ -35,6 +37,7 @@ LAM, SIGMA = 0.5, 0.4
 UPDATE_TOL = 2.0 * 2.0 ** -24
 NORMAL_TOL = 4.0 * 1.7e-6
 NETS = ["he_20_10", "he_128_128", "ref_200_100"]       # one per instantiation: (64, 64), (128, 128), (208, 112)
+EDGES = list(dr.EDGE_SETS)                              # every width edge: tests/dynplan_ref.py's EDGE_WIDTHS
 OUTPUTS = ("actions", "nominal", "best_score", "scores", "trace", "candidates", "traj")
 
 
@@ -200,19 +203,29 @@ def test_persistent_grid_loops(torch):
 
 
 # ---------------------------------------------------------------------------------------------------- every net
-@pytest.mark.parametrize("name", NETS)
+def case_of(name, net, far):
+    """-> (n, paths, horizon, obs, iterations) of a test over NETS + EDGES: the width edges run tests/dynplan_ref.py's small
+    shape (two tiles of 16 candidates and a ragged third, the second env far out) with two iterations"""
+    if name in EDGES:
+        assert net.compiled == dr.EDGE_WIDTHS[(net.h1, net.h2)] and dr.edge_name(net.h1, net.h2) == name
+        return dr.EDGE_N, dr.EDGE_PATHS, dr.EDGE_HORIZON, dr.edge_obs(), 2
+    obs = dr.sample_obs(3)
+    if far:
+        obs[1] *= 6.0                                     # one env far out: large activations
+    return 3, 65, 5, obs, 3
+
+
+@pytest.mark.parametrize("name", NETS + EDGES)
 def test_steps_scores_and_update(torch, name):
     W, net = net_of(name)
-    n, paths, horizon = 3, 65, 5
-    obs = dr.sample_obs(n)
-    obs[1] *= 6.0                                         # one env far out: large activations
+    n, paths, horizon, obs, iterations = case_of(name, net, far=True)
     full = None
     for lam in (0.05, 2.0):                               # a peaked and a flat weighting
-        for j in (3, 1):
+        for j in (iterations, 1):
             out = plan(torch, net, obs, horizon, paths, j, lam=lam)
             r_step, _, _ = check_last_iteration(W, obs, out, lam, "%s lam %g it %d" % (name, lam, j))
-            assert r_step > 1e-3                          # on the generic nets the bound is within a small factor of what float32 does
-            if j == 3:
+            assert r_step > 1e-3 or name in EDGES         # on the generic nets the bound is within a small factor of what float32 does
+            if j == iterations:
                 full = out
             check_prefix(full, out, j, (name, lam))
         assert not same_bits(full["trace"][:, 1], full["trace"][:, 0])
@@ -251,15 +264,14 @@ def test_in_kernel_normals_against_float64(torch):
 
 
 # ---------------------------------------------------------------------------------------------------- one model step
-@pytest.mark.parametrize("name", NETS)
+@pytest.mark.parametrize("name", NETS + EDGES)
 def test_model_step_is_the_shooting_planner_s(torch, name):
     """paths = 1, iterations = 1, shift 0 and the nominal = the winner's sequence of qsd_shooting_plan for the same (net, obs):
     candidate 0 is clamp(U) = U, and its trajectory is that plan's traj[:, best] bit for bit"""
     import quadsim_amd as qa
     W, net = net_of(name)
-    n, horizon = 3, 5
-    obs = dr.sample_obs(n)
-    shot = qa.learned_shooting_plan(net, torch.as_tensor(obs).cuda(), horizon, 65, seed=SEED, k=K0, gid0=GID0, return_sequence=True,
+    n, paths, horizon, obs, _ = case_of(name, net, far=False)
+    shot = qa.learned_shooting_plan(net, torch.as_tensor(obs).cuda(), horizon, paths, seed=SEED, k=K0, gid0=GID0, return_sequence=True,
                                     return_traj=True)
     seq = shot["sequence"].cpu().numpy()
     best = shot["best_index"].cpu().numpy()

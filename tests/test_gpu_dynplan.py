@@ -8,7 +8,9 @@ afterwards.  What is held, on every element of every output:
   scores     against the float64 sum over the kernel's own trajectory, within the bound of the squared terms; best_index = the
              first arg-max of the kernel's own scores; best_score = scores[best_index] bit for bit
 The mapping has edges at 16 candidates (a wave's tile), 64 (a workgroup's four tiles; work items are numbered across envs, so
-with n = 3 an env's tiles start inside a workgroup) and at cus x 4 tiles, where the persistent grid starts to loop.
+with n = 3 an env's tiles start inside a workgroup) and at cus x 4 tiles, where the persistent grid starts to loop.  The net has
+edges of its own, the hidden widths at which the packer masks a partly filled block of 16 units and the router changes the
+instantiation: test_edge_widths runs a dense net at each (dynplan_ref.EDGE_WIDTHS), both maxima included.
 Worst error / bound ratios measured on an MI355X are in profiles/dynplan/README.md.
 """
 import ctypes as C
@@ -176,6 +178,21 @@ def test_steps_scores_and_winner(torch, name):
         assert 0.3 < (z <= 0).mean() < 0.9
 
 
+# ---------------------------------------------------------------------------------------------------- every width edge
+@pytest.mark.parametrize("name", dr.EDGE_SETS)
+def test_edge_widths(torch, name):
+    """dense nets at the widths where the packer masks a partly filled block of 16, where the router changes the instantiation
+    and at both maxima (dynplan_ref.EDGE_WIDTHS); tests/test_dynplan_cpu.py holds that on these very steps a dropped last unit
+    of either hidden layer is out of bound.  Two tiles of 16 candidates and a ragged third, the second env far out."""
+    W, net = net_of(name)
+    assert (SEED, GID0, K0) == (dr.EDGE_SEED, dr.EDGE_GID0, dr.EDGE_K)
+    assert net.compiled == dr.EDGE_WIDTHS[(net.h1, net.h2)] and dr.edge_name(net.h1, net.h2) == name
+    n, paths, horizon = dr.EDGE_N, dr.EDGE_PATHS, dr.EDGE_HORIZON
+    obs = dr.edge_obs()
+    out = plan(torch, net, obs, horizon, paths)
+    check_plan(W, obs, out, draws(n, paths, horizon), name)
+
+
 def test_without_optional_outputs(torch):
     """every nullable output NULL: the scores go through the workspace, the last prediction is not computed, same winner"""
     W, net = net_of("ref_200_100")
@@ -233,7 +250,8 @@ def test_scores_do_not_depend_on_paths_or_n(torch):
 
 
 def test_padding_is_invisible(torch):
-    """a (100, 50) net and the same net hand-padded with zero units to (128, 128): the same bits (k_dyn_pack pads the first)"""
+    """a (100, 50) net and the same net hand-padded with zero units to (128, 128): the same bits (k_dyn_pack pads the first);
+    likewise three of the width edges and their paddings"""
     W, net = net_of("he_100_50")
     P = dr.pad_net(W, 128, 128)
     padded = dr.to_net(P, "cuda")
@@ -244,6 +262,19 @@ def test_padding_is_invisible(torch):
         assert np.array_equal(a[name].view(np.uint8), b[name].view(np.uint8)), name
     assert np.array_equal(net.pack().cpu().numpy(), padded.pack().cpu().numpy())
     check_plan(W, obs, a, draws(3, 65, 20), "he_100_50")
+    # the width edges: padded to the next multiple of 4 (what the fit rounds to) and to the compiled pair, across a tile
+    # boundary by one unit, and from one unit of layer 2 to a full image
+    n, paths, horizon = dr.EDGE_N, dr.EDGE_PATHS, dr.EDGE_HORIZON
+    obs = dr.edge_obs()
+    for name, to in (("edge_21_11", (24, 12)), ("edge_21_11", (64, 64)), ("edge_65_3", (128, 128)), ("edge_129_1", (208, 112))):
+        W, net = net_of(name)
+        padded = dr.to_net(dr.pad_net(W, *to), "cuda")
+        assert (padded.h1, padded.h2) == to and net.compiled == padded.compiled == dr.EDGE_WIDTHS[(net.h1, net.h2)]
+        a, b = plan(torch, net, obs, horizon, paths), plan(torch, padded, obs, horizon, paths)
+        assert set(a) == {"actions", "best_score", "best_index", "sequence", "scores", "traj"}
+        for out in a:
+            assert np.array_equal(a[out].view(np.uint8), b[out].view(np.uint8)), (name, to, out)
+        assert np.array_equal(net.pack().cpu().numpy(), padded.pack().cpu().numpy()), (name, to)
 
 
 # ---------------------------------------------------------------------------------------------------- independent wiring check
