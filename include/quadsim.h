@@ -94,7 +94,9 @@ typedef struct QsConfig {
     int32_t randomise;   /* QS_RANDOMISE_* */
     int32_t io_space;    /* QS_IO_* */
     uint64_t seed;          /* Philox key */
-    uint64_t env_id_offset; /* global id of env 0 of this handle (shard offset; RNG is keyed by global id) */
+    uint64_t env_id_offset; /* global id of env 0 of this handle (shard offset; RNG is keyed by global id).  A global id has
+                               48 bits -- the Philox subsequence of a draw is (stream << 48) | id -- so qs_create refuses
+                               env_id_offset + num_envs > 2^48 with QS_ERR_INVALID */
     float init_range[4];    /* half-ranges: chaser pos [m], vel [m/s], euler [rad], body rates [rad/s] */
     float mass_scale[2];    /* [lo,hi] multiplier of mass    (QS_RANDOMISE_PARAMS) */
     float inertia_scale[2]; /* [lo,hi] multiplier of Ixx,Iyy,Izz */
@@ -488,7 +490,9 @@ int qs_expert_evaluate(QsEnv *env, int32_t episodes, int64_t max_steps, const fl
  *     (k << 26) | (c << 10) | h of subsequence (5 << 48) | gid: stream 5 is the planner's, gid = env_id_offset + i, k the
  *     handle's step counter at the call.  Plans before different steps differ, a plan repeated at the same k is reproducible,
  *     and candidate c does not depend on `paths`: the candidates of a call with fewer paths are a prefix of those of a call
- *     with more.
+ *     with more.  The key is 64-bit arithmetic throughout: k up to 2^36 - 1, gid up to 2^48 - 1 (qs_create refuses more) and
+ *     both words of the seed reach the draw.  tests/test_gpu_plan_edges.py holds the device to this at every k where
+ *     4 x block, the block or k itself crosses 32 bits, with global ids on both sides of 2^32 and at 2^48 - 1.
  *   Score, QS_SHOOT_REWARD.  The float64 sum, in step order, of the float32 step rewards (ep_return of qs_policy_evaluate).
  *   Score, QS_SHOOT_POSITION.  The reference's cost (:200-208): the float64 sum over h of the float32 value
  *     -(o0^2 + o1^2 + o2^2) of the observation BEFORE step h; the h = 0 term is the current observation, common to all
@@ -504,6 +508,8 @@ int qs_expert_evaluate(QsEnv *env, int32_t episodes, int64_t max_steps, const fl
  *   Read-only.  State, parameters, initial states, step counter, q_des and the rollout layout are not modified: the handle
  *     steps on afterwards as if the call had not been made (the contract of qs_policy_evaluate).
  *   1 <= paths <= 65536 (need not be a multiple of 64), 1 <= horizon <= 256, step counter < 2^36, else QS_ERR_INVALID.
+ *     Both maxima are held to the step API and to the float64 oracle (65 536 paths bit for bit; horizon 256 with the
+ *     winner's whole sequence), not only accepted.
  *   docking-v0 / v1 / v2, both integrators, every randomise mode and stored initial states (none is consulted), per-env
  *   params, auto_reset 0 or 1, device buffers; hovering handles and QS_IO_HOST give QS_ERR_INVALID.  In private-queue mode
  *   pending queue work is drained first, as by every entry point that is not a step.  The call reads the step counter back
@@ -558,7 +564,9 @@ int qs_shooting_plan_splits(QsEnv *env, int32_t paths, int32_t *splits);   /* wh
  *     as the policy sampler pairs them, (w.x, w.y) -> z0 = r cos, z1 = r sin and (w.z, w.w) -> z2, z3.  Bit 63 keeps these
  *     blocks apart from every block qs_shooting_plan draws (those are below 2^62).  A plan repeated at the same k is
  *     reproducible; candidate c of iteration it does not depend on `paths`; the first j iterations of a call with more
- *     iterations are the call with iterations = j.
+ *     iterations are the call with iterations = j.  Every field is held on the device at its edge
+ *     (tests/test_gpu_plan_edges.py): k where k << 30 enters the upper counter word, where k crosses 32 bits and at
+ *     2^33 - 1; it = 0, 1, 2 and 15; c up to 65 535 (qs_mppi_plan_split); gid on both sides of 2^32 and at 2^48 - 1.
  *   Score.  That of qs_shooting_plan under the same objective (QS_SHOOT_REWARD / QS_SHOOT_POSITION), a float64 sum.
  *   Weights.  Smax = the largest score that is not NaN; w[c] = exp((S[c] - Smax) / lambda) in float64; a NaN score gives
  *     w[c] = 0.
@@ -573,7 +581,8 @@ int qs_shooting_plan_splits(QsEnv *env, int32_t paths, int32_t *splits);   /* wh
  *     noise, actions, nominal_out, trace, candidates 16-byte aligned, best_score and scores 8-byte.
  *   Read-only.  As qs_shooting_plan: nothing of the handle is modified.
  *   1 <= paths <= 4096, 1 <= horizon <= 128, 1 <= iterations <= 16, lambda > 0 and finite, sigma >= 0 and finite, shift 0 or
- *   1, step counter < 2^33, else QS_ERR_INVALID.  docking-v0 / v1 / v2, both integrators, every randomise mode, per-env params,
+ *   1, step counter < 2^33, else QS_ERR_INVALID.  paths = 4096 with horizon = 128 (the kernel's largest LDS footprint,
+ *   58 432 bytes) is held bit for bit to the step API.  docking-v0 / v1 / v2, both integrators, every randomise mode, per-env params,
  *   auto_reset 0 or 1, device buffers; hovering handles and QS_IO_HOST give QS_ERR_INVALID.  In private-queue mode pending
  *   queue work is drained first.  The call reads the step counter back (one stream synchronisation) before it launches.
  * Added after QS_VERSION 131 without changing it: callers detect this entry point by symbol (dlsym). */

@@ -394,6 +394,10 @@ int qs_create(const QsConfig *cfg, QsEnv **out)
         return fail(QS_ERR_INVALID, "qs_create: QsConfig size mismatch (got %d, want %zu)", cfg->struct_size, sizeof(QsConfig));
     if (cfg->num_envs < 1) return fail(QS_ERR_INVALID, "qs_create: num_envs must be >= 1");
     if (cfg->num_envs > ((int64_t)1 << 31)) return fail(QS_ERR_INVALID, "qs_create: num_envs too large");
+    // a Philox subsequence is (stream << 48) | gid: a global id of 2^48 or above would draw from another stream
+    if (cfg->env_id_offset > ((uint64_t)1 << 48) || cfg->env_id_offset + (uint64_t)cfg->num_envs > ((uint64_t)1 << 48))
+        return fail(QS_ERR_INVALID, "qs_create: env_id_offset + num_envs must fit the 48 bits of a global env id (at most 2^48), got %llu + %lld",
+                    (unsigned long long)cfg->env_id_offset, (long long)cfg->num_envs);
     if (cfg->kind < QS_KIND_DOCKING_V0 || cfg->kind > QS_KIND_HOVERING_V0) return fail(QS_ERR_INVALID, "qs_create: unknown env kind %d", cfg->kind);
     if ((cfg->kind == QS_KIND_DOCKING_V1 || cfg->kind == QS_KIND_HOVERING_V0) && cfg->randomise == QS_RANDOMISE_INIT)
         return fail(QS_ERR_INVALID, "qs_create: docking-v1 / hovering-v0 reset to their stored initial state; randomise must be 0");

@@ -58,6 +58,10 @@ class VecDockingEnv:
             raise ValueError("unknown env id %r (have %s)" % (env_id, sorted(_KINDS)))
         if backend not in ("torch", "numpy"):
             raise ValueError("backend must be 'torch' or 'numpy'")
+        if not (0 <= int(env_id_offset) and int(env_id_offset) + int(num_envs) <= 1 << 48):
+            # the Philox subsequence of a draw is (stream << 48) | global id: qs_create refuses the same
+            raise ValueError("env_id_offset + num_envs must fit the 48 bits of a global env id (at most 2^48), got %d + %d"
+                             % (int(env_id_offset), int(num_envs)))
         self.env_id = env_id
         self.kind = _KINDS[env_id]
         self.num_envs = int(num_envs)

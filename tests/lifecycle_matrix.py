@@ -57,13 +57,8 @@ CENSUS = {
     "k_policy_forward_fast": "tests/test_gpu_actor_numerics.py::test_predict_hip_within_bound",
     # layer 1 and layer 0: tests/layer1_matrix.py
     "k_drone_step": "layer1_matrix", "k_ctrl": "layer1_matrix", "k_rel_obs": "layer1_matrix", "k_transform": "layer1_matrix",
-    # the planners: instantiations and resources on the CPU, values in the GPU files beside them
-    "k_shooting_plan": "tests/test_shooting_cpu.py::test_plan_kernel_instantiations_and_resources",
-    "k_wide_candidates": "tests/test_shooting_split_cpu.py::test_wide_kernel_instantiations_and_resources",
-    "k_wide_finish": "tests/test_shooting_split_cpu.py::test_wide_kernel_instantiations_and_resources",
-    "k_mppi": "tests/test_mppi_cpu.py::test_mppi_kernel_instantiations_and_resources",
-    "k_pathint_part_roll": "tests/test_mppi_split_cpu.py::test_part_kernel_instantiations_and_resources",
-    "k_pathint_part_sums": "tests/test_mppi_split_cpu.py::test_part_kernel_instantiations_and_resources",
-    "k_pathint_part_finish": "tests/test_mppi_split_cpu.py::test_part_kernel_instantiations_and_resources",
+    # the planners on the exact simulator: tests/plan_matrix.py
+    "k_shooting_plan": "plan_matrix", "k_wide_candidates": "plan_matrix", "k_wide_finish": "plan_matrix", "k_mppi": "plan_matrix",
+    "k_pathint_part_roll": "plan_matrix", "k_pathint_part_sums": "plan_matrix", "k_pathint_part_finish": "plan_matrix",
 }
 CENSUS.update({k: "lifecycle_matrix" for k in KERNELS})

@@ -255,3 +255,29 @@ def test_errors(qa, torch):
     obs = np.empty((8, 12), np.float32)
     assert lib.qs_reset(h, None, obs.ctypes.data_as(C.c_void_p)) == 0 and np.isfinite(obs).all()
     lib.qs_destroy(h)
+
+
+def test_global_env_ids_have_48_bits(qa, torch):
+    """the planner's Philox subsequence is (5 << 48) | gid: a handle whose last env has the id 2^48 - 1 is accepted and plans
+    what the reference draws for it; one env more is refused by qs_create and by VecDockingEnv"""
+    lib = qa._lib.load()
+    n, top = 8, 1 << 48
+    env = qa.VecDockingEnv("docking-v0", num_envs=n, seed=SEED, env_id_offset=top - n)
+    env.reset()
+    got = _plan(env, 3, 64)
+    acts = np.stack([shooting_ref.actions_fast(SEED, top - n + g, env.step_counter, 64, 3) for g in range(n)])
+    assert np.array_equal(_bits(got["sequence"]), _bits(acts[np.arange(n), got["best_index"]]))
+    env.close()
+    with pytest.raises(ValueError, match="48 bits"):
+        qa.VecDockingEnv("docking-v0", num_envs=n, env_id_offset=top - n + 1)
+    cfg = qa._lib.default_config()
+    cfg.kind, cfg.num_envs = qa._lib.KIND_V0, n
+    for offset, rc_want in ((top - n + 1, -1), (top, -1), ((1 << 64) - 1, -1), (top - n, 0)):
+        cfg.env_id_offset = offset
+        h = C.c_void_p()
+        assert lib.qs_create(C.byref(cfg), C.byref(h)) == rc_want, offset
+        if rc_want:
+            assert "48 bits" in lib.qs_last_error().decode() and not h.value
+            with pytest.raises(qa.QuadsimError):
+                qa._lib.check(rc_want, "qs_create")
+    lib.qs_destroy(h)
