@@ -13,8 +13,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("QUADSIM_HIP_LIB") or os.path.join(CSRC, "libquadsim_hip.so")  # override: A/B builds
 SOURCES = [os.path.join(CSRC, "quadsim_hip.hip")]
 # every fragment of the one translation unit is a rebuild dependency (dynplan_*.hpp belong to the second library,
-# dynmppi_*.hpp to the third, dynfit_*.hpp to the fourth)
-HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith(("dynplan_", "dynmppi_", "dynfit_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
+# dynmppi_*.hpp to the third, dynfit_*.hpp to the fourth, bcfit_*.hpp to the fifth)
+HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith(("dynplan_", "dynmppi_", "dynfit_", "bcfit_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
 # the second library, libquadsim_dyn.so (include/quadsim_dyn.h; bound in dynplan.py): its own translation unit and code object
 DYN_LIB_PATH = os.environ.get("QUADSIM_DYN_LIB") or os.path.join(CSRC, "libquadsim_dyn.so")
 DYN_SOURCES = [os.path.join(CSRC, "dynplan.hip")]
@@ -31,6 +31,12 @@ DYNFIT_LIB_PATH = os.environ.get("QUADSIM_DYNFIT_LIB") or os.path.join(CSRC, "li
 DYNFIT_SOURCES = [os.path.join(CSRC, "dynfit.hip")]
 DYNFIT_HEADERS = [os.path.join(CSRC, h) for h in ("dynfit_kernels.hpp", "quadsim_device.hpp")] + [
     os.path.join(HERE, "..", "include", "quadsim_dyn_fit.h")]
+# the fifth library, libquadsim_bc.so (include/quadsim_bc.h; bound in bc.py): behaviour cloning of the actor.  It takes the policy's
+# own tensors and shares the forward chain and the Adam step of the fourth library's fragment at the source level
+BC_LIB_PATH = os.environ.get("QUADSIM_BC_LIB") or os.path.join(CSRC, "libquadsim_bc.so")
+BC_SOURCES = [os.path.join(CSRC, "bcfit.hip")]
+BC_HEADERS = [os.path.join(CSRC, h) for h in ("bcfit_kernels.hpp", "dynfit_kernels.hpp", "quadsim_device.hpp")] + [
+    os.path.join(HERE, "..", "include", "quadsim_bc.h")]
 
 QS_OK = 0
 KIND_V0, KIND_V2, KIND_V1, KIND_HOVER = 0, 1, 2, 3
@@ -201,12 +207,25 @@ def build_dynfit_library(force=False, verbose=False):
     return DYNFIT_LIB_PATH
 
 
+def build_bc_library(force=False, verbose=False):
+    """libquadsim_bc.so with the flags of the main library -> its path"""
+    if not force and _up_to_date(BC_LIB_PATH, BC_SOURCES + BC_HEADERS):
+        return BC_LIB_PATH
+    cmd = [hipcc_path(), "-std=c++20", "-O3", "-fno-slp-vectorize", "-ffp-contract=on", "--offload-arch=gfx950", "-fPIC", "-shared",
+           "-Wno-unused-result", *BC_SOURCES, "-o", BC_LIB_PATH]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return BC_LIB_PATH
+
+
 def build_library(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all four libraries, returns the main one's
+    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all five libraries, returns the main one's
     path."""
     build_dyn_library(force, verbose)
     build_dynmppi_library(force, verbose)
     build_dynfit_library(force, verbose)
+    build_bc_library(force, verbose)
     deps = SOURCES + HEADERS
     if not force and _up_to_date(LIB_PATH, deps):
         return LIB_PATH

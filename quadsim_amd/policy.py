@@ -55,6 +55,15 @@ class MlpPolicy:
             self._blob = self.torch.as_tensor(blob.copy()).to(self.w0.device)
         return self._blob
 
+    def pretrain(self, dataset, **kw):
+        """behaviour cloning on the device: quadsim_amd.bc.pretrain(self, dataset, ...)"""
+        from .bc import pretrain
+        return pretrain(self, dataset, **kw)
+
+    def reset_pretrain_optimizer(self):
+        from .bc import reset_pretrain_optimizer
+        reset_pretrain_optimizer(self)
+
     def predict_hip(self, env, obs, precision="f32", out=None):
         """the same actor as ONE hand-written kernel on the matrix cores (qs_policy_forward: exact-f32 MFMA; "bf16x3":
         split-bf16 operands, ~1e-5 on an action), launched on `env`'s stream: obs [n,12] float32 device tensor -> actions

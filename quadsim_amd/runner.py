@@ -76,6 +76,16 @@ class ActorCriticPolicy:
     def value(self, obs, state=None, mask=None):
         return self._heads(obs)[1]
 
+    # -- behaviour cloning of the actor (quadsim_amd.bc) --------------------------------------------------------------
+    def pretrain(self, dataset, **kw):
+        """behaviour cloning on the device: quadsim_amd.bc.pretrain(self, dataset, ...); only w0 .. b2 change"""
+        from .bc import pretrain
+        return pretrain(self, dataset, **kw)
+
+    def reset_pretrain_optimizer(self):
+        from .bc import reset_pretrain_optimizer
+        reset_pretrain_optimizer(self)
+
     # -- device image for the fused kernel --------------------------------------------------------------------------
     def c_struct(self):
         """QsActorCritic (shared trunk) or QsActorCriticNet (towers) over transposed device copies of the weights; the towers'
