@@ -1,5 +1,6 @@
 // kernel_diag.hpp -- macros the kernels are written with: the in-kernel time stamps of the diagnostic builds (QS_STAMP_*,
-// QS_PHASE_*; empty in the product build) and the store flavour of the step kernels (QS_ST, QS_SO)
+// QS_PHASE_*; empty in the product build), the store flavour of the step kernels (QS_ST, QS_SO) and, for the resident step
+// kernel, global-addressed pointers and the vmcnt wait (QS_GLOBAL_PTR, QS_WAIT_VMEM)
 // A fragment of quadsim_hip.hip (ONE translation unit), included there right before step_kernels.hpp, nowhere else.
 #pragma once
 
@@ -80,3 +81,12 @@
 #define QS_ST(p, v) __builtin_nontemporal_store((v), (p))
 #define QS_SO(p, v) QS_ST(p, v)
 #endif
+
+// A pointer the compiler cannot trace to a kernel argument (the resident kernel rebuilds its I/O pointers from descriptor words)
+// is a flat pointer: its stores count in lgkmcnt as well as vmcnt, so every LDS wait also waits for them.  The I/O arrays are
+// device memory: a store through QS_GLOBAL_PTR is a global_store_* that only vmcnt tracks.
+#define QS_GLOBAL __attribute__((address_space(1)))
+#define QS_GLOBAL_PTR(T, p) ((QS_GLOBAL T *)(p))
+// `s_waitcnt vmcnt(0)` as the builtin (gfx9 encoding: expcnt and lgkmcnt left at their maxima), which the compiler's own wait
+// insertion takes into account; the asm waits of the stamp builds are invisible to it
+#define QS_WAIT_VMEM() __builtin_amdgcn_s_waitcnt(0x0f70)

@@ -652,6 +652,25 @@ __device__ __forceinline__ float4 res_action(const float *actions, int64_t io, i
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
 
+// store_obs and store_term_half through descriptor pointers: the same stores, global-addressed (kernel_diag.hpp, QS_GLOBAL_PTR)
+__device__ __forceinline__ void res_store_obs(float *obs, int64_t env, const float o[12])
+{
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    QS_GLOBAL f4 *p = QS_GLOBAL_PTR(f4, obs + env * 12);
+    QS_SO(&p[0], (f4{o[0], o[1], o[2], o[3]}));
+    QS_SO(&p[1], (f4{o[4], o[5], o[6], o[7]}));
+    QS_SO(&p[2], (f4{o[8], o[9], o[10], o[11]}));
+}
+
+__device__ __forceinline__ void res_store_term_half(float *term_state, bool active, int64_t io, int half, const float s[13])
+{
+    if (term_state && active) {
+        QS_GLOBAL float *ts = QS_GLOBAL_PTR(float, term_state + io * 26 + 13 * half);
+#pragma unroll
+        for (int i = 0; i < 13; ++i) ts[i] = s[i];
+    }
+}
+
 // lane 0, after consuming step descriptor s: the tile's report into its progress window, if s closes one (wave-uniform);
 // returns the counter's previous value, checked by res_report_done once the add has long returned
 __device__ __forceinline__ unsigned res_report(const ResArgs &R, unsigned long long s, int64_t tile, int lane)
@@ -675,6 +694,13 @@ __device__ __forceinline__ void res_report_done(const ResArgs &R, unsigned old, 
 // barrier #0 before the first step; the next descriptor is requested at the top of a step and resolved where k_env_split
 // requests the next action; a step's I/O pointers are those of its descriptor D; no placement guard and no slab; the chaser
 // wave keeps its priority for the whole dispatch; the state is stored once, when the tile leaves.
+// Memory waits of the chaser wave: gfx950 counts loads, returning atomics and stores in ONE in-order vmcnt, so a wait for any
+// loaded value behind a step's stores is also a wait for their acknowledge, during which the wave issues nothing.  A step
+// therefore has one such wait, in FRONT of its first store (res_report_done reads the progress add's result, requested
+// before #1 like the next action), and the reset branch only computes: its terminal rows stay in registers until then.  The
+// stores of step t drain under drone_advance of step t + 1, up to the wait for descriptor t + 2.  Nothing reads them before
+// the dispatch has ended (the host waits for its completion signal, a system-scope release); two steps' stores to one buffer
+// come from the same wave in issue order.  The state loads are waited for once, before the loop.
 // Full stamp build: stamp 1 is retaken at the top of every step, so that the stamps a tile flushes when it leaves are the
 // timeline of its LAST step (1 step start, 2 before #1, 3 after #1, 4 before #2, 5 after #2, 6 / 7 as in k_env_split).
 #if defined(QS_STAMP) && QS_STAMP + 0 < 2
@@ -733,6 +759,7 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
         asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
 #endif
         QS_STAMP_AT(1);
+        QS_WAIT_VMEM();                          // the state rows, here and not at the top of every step
         int64_t t = 0;
 #pragma clang loop unroll(disable)
         for (; cmd == RES_STEP; ++t) {
@@ -765,19 +792,27 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
             QS_STAMP_AT(4);
             __syncthreads();                                              // #2: reset flags out, this step's Philox words in
             QS_STAMP_AT(5);
+            // the reset only computes: the terminal observation and state it overwrites wait in registers for the stores below
+            float term_obs[12], term_sc[13];
             if (rs) {
-                if (D.term_obs && active) store_obs(D.term_obs, io, obs);
-                store_term_half(D.term_state, active, io, 0, sc);
+#pragma unroll
+                for (int i = 0; i < 12; ++i) term_obs[i] = obs[i];
+#pragma unroll
+                for (int i = 0; i < 13; ++i) term_sc[i] = sc[i];
                 chaser_reset<PARAMS>(L, A, env, active, lane, t, sc, uc, ls, tt, P, obs);
             }
             QS_STAMP_AT(6);
-            if (active) {
-                store_obs(D.obs, o, obs);
-                QS_SO(&D.reward[o], reward);
-                QS_SO(&D.done[o], (uint8_t)(done ? 1 : 0));
-                if (D.flags) QS_SO(&D.flags[o], (uint8_t)flags);
+            res_report_done(R, rep, seq + t + 1, tile, lane);             // the step's one memory wait (`rep`): before its stores
+            if (rs) {
+                if (D.term_obs && active) res_store_obs(D.term_obs, io, term_obs);
+                res_store_term_half(D.term_state, active, io, 0, term_sc);
             }
-            res_report_done(R, rep, seq + t + 1, tile, lane);
+            if (active) {
+                res_store_obs(D.obs, o, obs);
+                QS_SO(QS_GLOBAL_PTR(float, &D.reward[o]), reward);
+                QS_SO(QS_GLOBAL_PTR(uint8_t, &D.done[o]), (uint8_t)(done ? 1 : 0));
+                if (D.flags) QS_SO(QS_GLOBAL_PTR(uint8_t, &D.flags[o]), (uint8_t)flags);
+            }
             D = Dn;
             cmd = cmdn;
         }
@@ -830,7 +865,7 @@ __global__ __launch_bounds__(3 * kTile) void k_env_resident(StepArgs A, ResArgs 
             __syncthreads();                                              // #2
             QS_STAMP_AT(5);
             if (L.done[lane]) {
-                store_term_half(term_state, active, io, 1, st);
+                res_store_term_half(term_state, active, io, 1, st);
                 target_reset<PARAMS>(L, A, env, active, lane, w0, w1, st, ut, P);
             }
             cmd = s_cmd[(t + 1) & 1];
