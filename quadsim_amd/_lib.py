@@ -1,4 +1,5 @@
-"""ctypes binding of libquadsim_hip.so (the C ABI declared in include/quadsim.h).
+"""ctypes binding of libquadsim_hip.so (the C ABI declared in include/quadsim.h), and the one table (SIDE), build, loader and
+call helper of the four side libraries that dynplan.py and bc.py wrap.
 
 There is deliberately no fallback of any kind: if the HIP library is missing or
 no MI355X is visible, loading / qs_create raise.  Nothing here imports oracle/.
@@ -12,31 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("QUADSIM_HIP_LIB") or os.path.join(CSRC, "libquadsim_hip.so")  # override: A/B builds
 SOURCES = [os.path.join(CSRC, "quadsim_hip.hip")]
-# every fragment of the one translation unit is a rebuild dependency (dynplan_*.hpp belong to the second library,
-# dynmppi_*.hpp to the third, dynfit_*.hpp to the fourth, bcfit_*.hpp to the fifth)
-HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith(("dynplan_", "dynmppi_", "dynfit_", "bcfit_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
-# the second library, libquadsim_dyn.so (include/quadsim_dyn.h; bound in dynplan.py): its own translation unit and code object
-DYN_LIB_PATH = os.environ.get("QUADSIM_DYN_LIB") or os.path.join(CSRC, "libquadsim_dyn.so")
-DYN_SOURCES = [os.path.join(CSRC, "dynplan.hip")]
-DYN_HEADERS = [os.path.join(CSRC, h) for h in ("dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp")] + [os.path.join(HERE, "..", "include", "quadsim_dyn.h")]
-# the third library, libquadsim_dynmppi.so (include/quadsim_dyn_mppi.h; bound in dynplan.py): MPPI over the learned net.  It shares
-# the second library's device code (the model step and the image layout) and none of its host code
-DYNMPPI_LIB_PATH = os.environ.get("QUADSIM_DYNMPPI_LIB") or os.path.join(CSRC, "libquadsim_dynmppi.so")
-DYNMPPI_SOURCES = [os.path.join(CSRC, "dynmppi.hip")]
-DYNMPPI_HEADERS = [os.path.join(CSRC, h) for h in ("dynmppi_kernels.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp")] + [
-    os.path.join(HERE, "..", "include", "quadsim_dyn_mppi.h")]
-# the fourth library, libquadsim_dynfit.so (include/quadsim_dyn_fit.h; bound in dynplan.py): the Adam fit of the learned net.  It
-# takes the net's own tensors, not the image, and shares only the Philox generator of quadsim_device.hpp
-DYNFIT_LIB_PATH = os.environ.get("QUADSIM_DYNFIT_LIB") or os.path.join(CSRC, "libquadsim_dynfit.so")
-DYNFIT_SOURCES = [os.path.join(CSRC, "dynfit.hip")]
-DYNFIT_HEADERS = [os.path.join(CSRC, h) for h in ("dynfit_kernels.hpp", "quadsim_device.hpp")] + [
-    os.path.join(HERE, "..", "include", "quadsim_dyn_fit.h")]
-# the fifth library, libquadsim_bc.so (include/quadsim_bc.h; bound in bc.py): behaviour cloning of the actor.  It takes the policy's
-# own tensors and shares the forward chain and the Adam step of the fourth library's fragment at the source level
-BC_LIB_PATH = os.environ.get("QUADSIM_BC_LIB") or os.path.join(CSRC, "libquadsim_bc.so")
-BC_SOURCES = [os.path.join(CSRC, "bcfit.hip")]
-BC_HEADERS = [os.path.join(CSRC, h) for h in ("bcfit_kernels.hpp", "dynfit_kernels.hpp", "quadsim_device.hpp")] + [
-    os.path.join(HERE, "..", "include", "quadsim_bc.h")]
+# every fragment of the one translation unit is a rebuild dependency, bar those of the side libraries (SIDE below)
+HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith(
+    ("dynplan_", "dynmppi_", "dynfit_", "bcfit_", "side_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
 
 QS_OK = 0
 KIND_V0, KIND_V2, KIND_V1, KIND_HOVER = 0, 1, 2, 3
@@ -156,6 +135,78 @@ SIGNATURES = {
 EXPORTS = sorted(SIGNATURES) + ["qs_last_error"]
 
 
+# ---------------------------------------------------------------------------------------------------- the side libraries
+class QsdNet(C.Structure):                     # include/quadsim_dyn.h
+    _fields_ = [("struct_size", C.c_uint32), ("h1", C.c_int32), ("h2", C.c_int32), ("reserved", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("wt1", "b1", "wt2", "b2", "wt3", "b3", "in_mean", "in_rscale", "out_std", "out_mean")]
+
+
+class QsdfNet(C.Structure):                    # include/quadsim_dyn_fit.h
+    _fields_ = [("struct_size", C.c_uint32), ("h1", C.c_int32), ("h2", C.c_int32), ("reserved", C.c_int32),
+                ("w", C.c_void_p * 6), ("m", C.c_void_p * 6), ("v", C.c_void_p * 6)] + [
+        (k, C.c_void_p) for k in ("in_mean", "in_rscale", "out_mean", "out_rscale")]
+
+
+class QsbcNet(C.Structure):                    # include/quadsim_bc.h
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("w", C.c_void_p * 6), ("m", C.c_void_p * 6), ("v", C.c_void_p * 6)]
+
+
+f64, psize, psix = C.c_double, C.POINTER(C.c_size_t), C.POINTER(vp * 6)
+# The four libraries beside the main one, each its own translation unit, .so and code object, by short name.  They share at the
+# source level only: device fragments (*_kernels.hpp, dynplan_image.hpp, quadsim_device.hpp) and the host fragments side_host.hpp
+# (all four) and dynplan_host.hpp (the two planners).  An entry: the variable that overrides the path (A/B builds) and the file
+# name, the source, the fragments it is rebuilt for, the public header, and the signatures of its entry points in the header's
+# order -- argument types or, where the result is not int, (argument types, result type).  Everything else is derived: the paths,
+# EXPORTS per library, the build, the loader.  tests/test_call_path_cpu.py compares the signatures with the headers.
+SIDE = {
+    # random-shooting MPC over the learned net (bound in dynplan.py)
+    "dyn": dict(env="QUADSIM_DYN_LIB", file="libquadsim_dyn.so", source="dynplan.hip", header="quadsim_dyn.h", prefix="qsd_",
+                fragments=("dynplan_host.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp", "side_host.hpp"),
+                signatures={
+                    "qsd_version": [],
+                    "qsd_last_error": ([], C.c_char_p),
+                    "qsd_net_image_bytes": [i32, i32, psize],
+                    "qsd_net_pack": [C.POINTER(QsdNet), vp, vp],
+                    "qsd_plan_workspace_bytes": [i64, i32, psize],
+                    "qsd_shooting_plan": [vp, i64, vp, u64, u64, u64, i32, i32] + [vp] * 8}),
+    # MPPI over the learned net (dynplan.py): the device code of "dyn" (the model step, the image layout), no host state of it
+    "dynmppi": dict(env="QUADSIM_DYNMPPI_LIB", file="libquadsim_dynmppi.so", source="dynmppi.hip", header="quadsim_dyn_mppi.h", prefix="qsdm_",
+                    fragments=("dynmppi_kernels.hpp", "dynplan_host.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp",
+                               "side_host.hpp"),
+                    signatures={
+                        "qsdm_version": [],
+                        "qsdm_last_error": ([], C.c_char_p),
+                        "qsdm_workspace_bytes": [i64, i32, i32, psize],
+                        "qsdm_mppi_plan": [vp, i32, i32, i64, vp, u64, u64, u64, i32, i32, i32, f32, f32, i32] + [vp] * 11}),
+    # the Adam fit of the learned net (dynplan.py): takes the net's own tensors, not the image; only the Philox generator is shared
+    "dynfit": dict(env="QUADSIM_DYNFIT_LIB", file="libquadsim_dynfit.so", source="dynfit.hip", header="quadsim_dyn_fit.h", prefix="qsdf_",
+                   fragments=("dynfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp"),
+                   signatures={
+                       "qsdf_version": [],
+                       "qsdf_last_error": ([], C.c_char_p),
+                       "qsdf_fit": [C.POINTER(QsdfNet), vp, vp, i64, i64, i32, i32, f64, f64, f64, f64, i64, u64, u64, vp, vp, vp, psix, vp]}),
+    # behaviour cloning of the actor (bc.py): takes the policy's own tensors; the forward chain and the Adam step of "dynfit"
+    "bc": dict(env="QUADSIM_BC_LIB", file="libquadsim_bc.so", source="bcfit.hip", header="quadsim_bc.h", prefix="qsbc_",
+               fragments=("bcfit_kernels.hpp", "dynfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp"),
+               signatures={
+                   "qsbc_version": [],
+                   "qsbc_last_error": ([], C.c_char_p),
+                   "qsbc_fit": [C.POINTER(QsbcNet), vp, vp, i64, vp, vp, i32, i32, f64, f64, f64, f64, i64, vp, psix, vp],
+                   "qsbc_loss_blocks": ([i64], i64),
+                   "qsbc_loss": [psix, vp, vp, i64, vp, i64, vp, vp, i32, vp]}),
+}
+for _e in SIDE.values():
+    _e["path"] = os.environ.get(_e["env"]) or os.path.join(CSRC, _e["file"])
+    _e["sources"] = [os.path.join(CSRC, _e["source"])]
+    _e["headers"] = [os.path.join(CSRC, h) for h in _e["fragments"]] + [os.path.join(HERE, "..", "include", _e["header"])]
+    _e["exports"] = list(_e["signatures"])
+# the positions of every entry point's pointer parameters: side_call sends those through as_arg and leaves the scalars to the
+# argtypes (as_arg on a scalar costs 0.3 us, and a plan has a dozen of them)
+SIDE_POINTERS = {name: tuple(i for i, t in enumerate(sig[0] if isinstance(sig, tuple) else sig) if t is vp or issubclass(t, C._Pointer))
+                 for _e in SIDE.values() for name, sig in _e["signatures"].items()}
+DYN_LIB_PATH, DYNMPPI_LIB_PATH, DYNFIT_LIB_PATH, BC_LIB_PATH = (SIDE[k]["path"] for k in ("dyn", "dynmppi", "dynfit", "bc"))
+
+
 class QuadsimError(RuntimeError):
     pass
 
@@ -171,76 +222,30 @@ def _up_to_date(lib, deps):
     return os.path.exists(lib) and all(os.path.getmtime(lib) >= os.path.getmtime(d) for d in deps)
 
 
-def build_dyn_library(force=False, verbose=False):
-    """libquadsim_dyn.so with the flags of the main library -> its path"""
-    if not force and _up_to_date(DYN_LIB_PATH, DYN_SOURCES + DYN_HEADERS):
-        return DYN_LIB_PATH
-    cmd = [hipcc_path(), "-std=c++20", "-O3", "-fno-slp-vectorize", "-ffp-contract=on", "--offload-arch=gfx950", "-fPIC", "-shared",
-           "-Wno-unused-result", *DYN_SOURCES, "-o", DYN_LIB_PATH]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    return DYN_LIB_PATH
+# -ffp-contract=on: a*b+c fuses only where one expression says so, so every kernel that inlines the same device
+# function computes the same bits (the serial and the role-split step kernel, the policy kernels' env step);
+# hipcc's default (fast) fuses across statements depending on the surrounding code.  Same instruction count.
+# -fno-slp-vectorize: SLP packs the scalar f32 chains into v_pk_* pairs at the price of ~300 extra
+# v_mov and +56 VGPRs; measured 5 % slower on the step kernel (profiles/r01/ab_slp.txt)
+HIPCC_FLAGS = ["-std=c++20", "-O3", "-fno-slp-vectorize", "-ffp-contract=on", "--offload-arch=gfx950", "-fPIC", "-shared", "-Wno-unused-result"]
 
 
-def build_dynmppi_library(force=False, verbose=False):
-    """libquadsim_dynmppi.so with the flags of the main library -> its path"""
-    if not force and _up_to_date(DYNMPPI_LIB_PATH, DYNMPPI_SOURCES + DYNMPPI_HEADERS):
-        return DYNMPPI_LIB_PATH
-    cmd = [hipcc_path(), "-std=c++20", "-O3", "-fno-slp-vectorize", "-ffp-contract=on", "--offload-arch=gfx950", "-fPIC", "-shared",
-           "-Wno-unused-result", *DYNMPPI_SOURCES, "-o", DYNMPPI_LIB_PATH]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    return DYNMPPI_LIB_PATH
-
-
-def build_dynfit_library(force=False, verbose=False):
-    """libquadsim_dynfit.so with the flags of the main library -> its path"""
-    if not force and _up_to_date(DYNFIT_LIB_PATH, DYNFIT_SOURCES + DYNFIT_HEADERS):
-        return DYNFIT_LIB_PATH
-    cmd = [hipcc_path(), "-std=c++20", "-O3", "-fno-slp-vectorize", "-ffp-contract=on", "--offload-arch=gfx950", "-fPIC", "-shared",
-           "-Wno-unused-result", *DYNFIT_SOURCES, "-o", DYNFIT_LIB_PATH]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    return DYNFIT_LIB_PATH
-
-
-def build_bc_library(force=False, verbose=False):
-    """libquadsim_bc.so with the flags of the main library -> its path"""
-    if not force and _up_to_date(BC_LIB_PATH, BC_SOURCES + BC_HEADERS):
-        return BC_LIB_PATH
-    cmd = [hipcc_path(), "-std=c++20", "-O3", "-fno-slp-vectorize", "-ffp-contract=on", "--offload-arch=gfx950", "-fPIC", "-shared",
-           "-Wno-unused-result", *BC_SOURCES, "-o", BC_LIB_PATH]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    return BC_LIB_PATH
+def build_one_library(sources, deps, out, link=(), force=False, verbose=False):
+    """hipcc HIPCC_FLAGS sources link -o out, unless `out` is newer than the sources and `deps` -> out"""
+    if force or not _up_to_date(out, sources + deps):
+        cmd = [hipcc_path(), *HIPCC_FLAGS, *sources, *link, "-o", out]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return out
 
 
 def build_library(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all five libraries, returns the main one's
     path."""
-    build_dyn_library(force, verbose)
-    build_dynmppi_library(force, verbose)
-    build_dynfit_library(force, verbose)
-    build_bc_library(force, verbose)
-    deps = SOURCES + HEADERS
-    if not force and _up_to_date(LIB_PATH, deps):
-        return LIB_PATH
-    # -ffp-contract=on: a*b+c fuses only where one expression says so, so every kernel that inlines the same device
-    # function computes the same bits (the serial and the role-split step kernel, the policy kernels' env step);
-    # hipcc's default (fast) fuses across statements depending on the surrounding code.  Same instruction count.
-    # -fno-slp-vectorize: SLP packs the scalar f32 chains into v_pk_* pairs at the price of ~300 extra
-    # v_mov and +56 VGPRs; measured 5 % slower on the step kernel (profiles/r01/ab_slp.txt)
-    cmd = [hipcc_path(), "-std=c++20", "-O3", "-fno-slp-vectorize", "-ffp-contract=on", "--offload-arch=gfx950", "-fPIC", "-shared",
-           "-Wno-unused-result", *SOURCES, "-lhsa-runtime64", "-o", LIB_PATH]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    return LIB_PATH
-
+    for e in SIDE.values():
+        build_one_library(e["sources"], e["headers"], e["path"], (), force, verbose)
+    return build_one_library(SOURCES, HEADERS, LIB_PATH, ["-lhsa-runtime64"], force, verbose)
 
 _lib = None
 
@@ -310,3 +315,89 @@ def default_config():
     cfg = QsConfig()
     check(load().qs_config_default(C.byref(cfg)), "qs_config_default")
     return cfg
+
+
+# ---------------------------------------------------------------------------------------------------- the side libraries' call path
+_side = {}
+
+
+def side_load(key):
+    """dlopen the side library `key` of SIDE, once; raises QuadsimError if it has not been built (there is no fallback)"""
+    lib = _side.get(key)
+    if lib is None:
+        e = SIDE[key]
+        if not os.path.exists(e["path"]):
+            raise QuadsimError("%s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % e["path"])
+        import torch  # noqa: F401  (its HIP runtime must be the resident one: see load)
+        lib = C.CDLL(e["path"])
+        for name, sig in e["signatures"].items():
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
+        _side[key] = lib
+    return lib
+
+
+def side_check(key, rc, what):
+    if rc != 0:
+        msg = getattr(side_load(key), SIDE[key]["prefix"] + "last_error")().decode("utf-8", "replace")
+        raise QuadsimError("%s failed (%d): %s" % (what, rc, msg))
+
+
+def side_call(key, lib, name, *args, device=None):
+    """the entry point `name` of `lib`, the loaded side library `key` (from the wrapper's own loader, which tests replace),
+    its pointer arguments (tensors, arrays, None) through as_arg, its scalars as they are.  With `device`: that device selected and torch's current stream on it as the last argument.
+    QuadsimError unless it returns 0; an entry point whose result is no status (qsbc_loss_blocks) -> the result"""
+    fn = getattr(lib, name)
+    args, pointers = list(args), SIDE_POINTERS[name]
+    for i in (pointers if device is None else pointers[:-1]):      # the last pointer of a launching entry point is its stream
+        args[i] = as_arg(args[i])
+    if device is None:
+        rc = fn(*args)
+    else:
+        import torch
+        with torch.cuda.device(device):
+            rc = fn(*args, torch.cuda.current_stream(device).cuda_stream)
+    if fn.restype is not C.c_int:
+        return rc
+    side_check(key, rc, name)
+
+
+def six(tensors):
+    """void *[6] of six tensors' device pointers (the w / m / v / grads arrays of both fits)"""
+    return (C.c_void_p * 6)(*map(as_arg, tensors))
+
+
+def new_tensor(device, shape, dtype):
+    """an uninitialised output of the call, from torch's caching allocator: no device allocation in steady state"""
+    import torch
+    return torch.empty(shape, dtype=getattr(torch, dtype), device=device)
+
+
+def check_tensor(name, t, dtype, shape, device):
+    """ValueError unless `t` is a contiguous torch tensor of `dtype` (its torch name) and `shape` on `device`; a str in `shape`
+    names a free dimension, shape None is any shape"""
+    import torch
+    ok = isinstance(t, torch.Tensor) and t.dtype == getattr(torch, dtype) and t.device == device and t.is_contiguous() and (
+        shape is None or t.dim() == len(shape))
+    if ok and shape is not None:
+        for s, d in zip(shape, t.shape):
+            ok = ok and (s == d or isinstance(s, str))
+    if not ok:
+        of = "" if shape is None else " of shape [%s]" % ", ".join(map(str, shape))
+        raise ValueError("%s must be a contiguous %s tensor%s on %s" % (name, dtype, of, device))
+
+
+def check_adam_args(lr, beta1, beta2, eps, t0, steps, word):
+    """-> (lr, beta1, beta2, eps) as floats; ValueError for what both fits refuse of Adam's arguments (`word`: what the fit
+    calls its steps)"""
+    import math
+    lr, beta1, beta2, eps = float(lr), float(beta1), float(beta2), float(eps)
+    if not (t0 >= 0 and t0 + steps < 1 << 31):
+        raise ValueError("t0 must be >= 0 with t0 + %s below 2^31, got %d" % (word, t0))
+    for name, val in (("lr", lr), ("eps", eps)):
+        if not math.isfinite(val):
+            raise ValueError("%s must be finite, got %r" % (name, val))
+    for name, val in (("beta1", beta1), ("beta2", beta2)):
+        if not 0.0 <= val < 1.0:
+            raise ValueError("%s must be in [0, 1), got %r" % (name, val))
+    return lr, beta1, beta2, eps

@@ -12,51 +12,23 @@ Both policies of the package have the same actor (``w0, b0, w1, b1, w2, b2``: 12
 trunk moves under the critic, as it does in SB2).  There is no CPU path.
 """
 import ctypes as C
-import math
+import functools
 import os
 
 import numpy as np
 
 from . import _lib
 
-BC_EXPORTS = ["qsbc_version", "qsbc_last_error", "qsbc_fit", "qsbc_loss_blocks", "qsbc_loss"]
 BC_MAX_BATCH, BC_MAX_STEPS, BC_LOSS_BLOCK = 256, 4096, 256
 BC_BETA1, BC_BETA2 = 0.9, 0.999                     # tf.train.AdamOptimizer's defaults, which SB2's pretrain leaves alone
 ACTOR_KEYS = ("w0", "b0", "w1", "b1", "w2", "b2")
 ACTOR_SHAPES = ((12, 128), (128,), (128, 128), (128,), (128, 4), (4,))
 
 
-class QsbcNet(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("w", C.c_void_p * 6), ("m", C.c_void_p * 6), ("v", C.c_void_p * 6)]
-
-
-_bc = None
-
-
-def load_bc():
-    """dlopen libquadsim_bc.so; raises QuadsimError if it has not been built (there is no fallback)"""
-    global _bc
-    if _bc is not None:
-        return _bc
-    if not os.path.exists(_lib.BC_LIB_PATH):
-        raise _lib.QuadsimError("%s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % _lib.BC_LIB_PATH)
-    import torch  # noqa: F401  (its HIP runtime must be the resident one: see _lib.load)
-    lib = C.CDLL(_lib.BC_LIB_PATH)
-    vp, i64, i32, f64 = C.c_void_p, C.c_int64, C.c_int32, C.c_double
-    lib.qsbc_version.argtypes, lib.qsbc_version.restype = [], C.c_int
-    lib.qsbc_last_error.argtypes, lib.qsbc_last_error.restype = [], C.c_char_p
-    lib.qsbc_fit.argtypes = [C.POINTER(QsbcNet), vp, vp, i64, vp, vp, i32, i32, f64, f64, f64, f64, i64, vp, C.POINTER(C.c_void_p * 6), vp]
-    lib.qsbc_fit.restype = C.c_int
-    lib.qsbc_loss_blocks.argtypes, lib.qsbc_loss_blocks.restype = [i64], i64
-    lib.qsbc_loss.argtypes = [C.POINTER(C.c_void_p * 6), vp, vp, i64, vp, i64, vp, vp, i32, vp]
-    lib.qsbc_loss.restype = C.c_int
-    _bc = lib
-    return lib
-
-
-def check_bc(rc, what):
-    if rc != 0:
-        raise _lib.QuadsimError("%s failed (%d): %s" % (what, rc, load_bc().qsbc_last_error().decode("utf-8", "replace")))
+# libquadsim_bc.so is the entry "bc" of _lib.SIDE: its path, signatures, loader, status check and call helper are _lib's.  The
+# names below stay this module's so that callers and tests can replace the loader
+QsbcNet, BC_EXPORTS = _lib.QsbcNet, _lib.SIDE["bc"]["exports"]
+load_bc, check_bc = functools.partial(_lib.side_load, "bc"), functools.partial(_lib.side_check, "bc")
 
 
 def check_bc_args(n, steps, batch, lr=1.0e-4, beta1=BC_BETA1, beta2=BC_BETA2, eps=1.0e-8, t0=0, counts=None, indices=None):
@@ -64,21 +36,13 @@ def check_bc_args(n, steps, batch, lr=1.0e-4, beta1=BC_BETA1, beta2=BC_BETA2, ep
     `counts` [steps] and `indices` [steps,batch], for what it cannot check (a count outside [1, batch], a row it would read
     outside [0, n)), before anything touches the library or the GPU"""
     n, steps, batch, t0 = int(n), int(steps), int(batch), int(t0)
-    lr, beta1, beta2, eps = float(lr), float(beta1), float(beta2), float(eps)
     if not 1 <= batch <= BC_MAX_BATCH:
         raise ValueError("batch must be in [1, %d], got %d" % (BC_MAX_BATCH, batch))
     if not 1 <= steps <= BC_MAX_STEPS:
         raise ValueError("steps must be in [1, %d], got %d" % (BC_MAX_STEPS, steps))
     if not 1 <= n < 1 << 31:
         raise ValueError("n must be in [1, 2^31), got %d" % n)
-    if not (t0 >= 0 and t0 + steps < 1 << 31):
-        raise ValueError("t0 must be >= 0 with t0 + steps below 2^31, got %d" % t0)
-    for name, val in (("lr", lr), ("eps", eps)):
-        if not math.isfinite(val):
-            raise ValueError("%s must be finite, got %r" % (name, val))
-    for name, val in (("beta1", beta1), ("beta2", beta2)):
-        if not 0.0 <= val < 1.0:
-            raise ValueError("%s must be in [0, 1), got %r" % (name, val))
+    lr, beta1, beta2, eps = _lib.check_adam_args(lr, beta1, beta2, eps, t0, steps, "steps")
     if counts is not None:
         counts = np.asarray(counts)
         if counts.shape != (steps,) or counts.min() < 1 or counts.max() > batch:
@@ -192,19 +156,9 @@ def _state(policy, ws):
     return policy._bc_m, policy._bc_v
 
 
-_ptr = _lib.as_arg          # a tensor as its device pointer, None as NULL
-
-
-def _six(ts):
-    return (C.c_void_p * 6)(*[_lib.as_arg(t) for t in ts])
-
-
 def _dataset_tensors(ws, obs, act):
-    import torch
-    for name, t, cols in (("obs", obs, 12), ("act", act, 4)):
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == cols and t.device == ws[0].device
-                and t.is_contiguous()):
-            raise ValueError("%s must be a contiguous float32 tensor of shape [n, %d] on %s" % (name, cols, ws[0].device))
+    _lib.check_tensor("obs", obs, "float32", ("n", 12), ws[0].device)
+    _lib.check_tensor("act", act, "float32", ("n", 4), ws[0].device)
     if obs.shape[0] != act.shape[0]:
         raise ValueError("obs and act must have the same number of rows, got %d and %d" % (obs.shape[0], act.shape[0]))
 
@@ -232,16 +186,12 @@ def bc_fit(policy, obs, act, indices, counts=None, lr=1.0e-4, beta1=BC_BETA1, be
     dev = ws[0].device
     idx_d = indices.contiguous().to(dev)
     cnt_d = None if counts is None else counts.contiguous().to(dev)
-    out = {"loss": torch.empty((steps,), dtype=torch.float32, device=dev)}
-    grads = None
+    out = {"loss": _lib.new_tensor(dev, (steps,), "float32")}
     if return_grads:
         out["grads"] = [torch.empty_like(w) for w in ws]
-        grads = _six(out["grads"])
-    net = QsbcNet(C.sizeof(QsbcNet), 0, _six(ws), _six(m), _six(v))
-    lib = load_bc()
-    with torch.cuda.device(dev):
-        check_bc(lib.qsbc_fit(C.byref(net), _ptr(obs), _ptr(act), n, _ptr(idx_d), _ptr(cnt_d), steps, batch, lr, beta1, beta2, eps, t0, _ptr(out["loss"]),
-                              grads, torch.cuda.current_stream(dev).cuda_stream), "qsbc_fit")
+    net = QsbcNet(C.sizeof(QsbcNet), 0, _lib.six(ws), _lib.six(m), _lib.six(v))
+    _lib.side_call("bc", load_bc(), "qsbc_fit", C.byref(net), obs, act, n, idx_d, cnt_d, steps, batch, lr, beta1, beta2, eps, t0, out["loss"],
+                   _lib.six(out["grads"]) if return_grads else None, device=dev)
     policy._bc_steps += steps
     drop_cached_images(policy)
     return out
@@ -263,11 +213,9 @@ def bc_loss(policy, obs, act, rows=None, grid=0):
     if not 0 <= int(grid) <= 65535:
         raise ValueError("grid must be in [0, 65535], got %r" % (grid,))
     lib = load_bc()
-    partials = torch.empty((lib.qsbc_loss_blocks(count),), dtype=torch.float64, device=dev)
-    out = torch.empty((1,), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        check_bc(lib.qsbc_loss(_six(ws), _ptr(obs), _ptr(act), obs.shape[0], _ptr(rows), count, _ptr(partials), _ptr(out), int(grid),
-                               torch.cuda.current_stream(dev).cuda_stream), "qsbc_loss")
+    partials = _lib.new_tensor(dev, (_lib.side_call("bc", lib, "qsbc_loss_blocks", count),), "float64")
+    out = _lib.new_tensor(dev, (1,), "float64")
+    _lib.side_call("bc", lib, "qsbc_loss", _lib.six(ws), obs, act, obs.shape[0], rows, count, partials, out, int(grid), device=dev)
     return out
 
 

@@ -1,34 +1,14 @@
 // bcfit.hip -- libquadsim_bc.so: the C ABI of include/quadsim_bc.h over the kernels of bcfit_kernels.hpp.  ONE translation unit
-// of its own: nothing here is part of the other four libraries.  Shared with the fourth at the source level only:
-// dynfit_kernels.hpp (the forward chain and the Adam step), none of whose kernels is instantiated here.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-
+// of its own: nothing here is part of the other four libraries.  Shared at the source level only: dynfit_kernels.hpp with the
+// fourth (the forward chain and the Adam step), none of whose kernels is instantiated here, and side_host.hpp with all the side
+// libraries (error text, the Adam and pointer checks and the fill of the args the two fits have in common).
 #include "../../include/quadsim_bc.h"
+#include "side_host.hpp"
 #include "bcfit_kernels.hpp"
 
+static_assert(QSBC_OK == kOk && QSBC_ERR_INVALID == kErrInvalid && QSBC_ERR_HIP == kErrHip, "side_host.hpp returns the codes of quadsim_bc.h");
+
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define QSBC_HIP_TRY(expr)                                                                             \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(QSBC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-bool misaligned(const void *p, uintptr_t mask = 3) { return ((uintptr_t)p & mask) != 0; }
 
 const size_t kElems[6] = {qsb::kIn * qsb::kH, qsb::kH, qsb::kH * qsb::kH, qsb::kH, qsb::kH * qsb::kOut, qsb::kOut};
 
@@ -54,16 +34,11 @@ int qsbc_fit(const QsbcNet *net, const float *obs, const float *act, int64_t n, 
     if (batch < 1 || batch > QSBC_MAX_BATCH) return fail(QSBC_ERR_INVALID, "batch must be in [1, %d], got %d", QSBC_MAX_BATCH, batch);
     if (steps < 1 || steps > QSBC_MAX_STEPS) return fail(QSBC_ERR_INVALID, "steps must be in [1, %d], got %d", QSBC_MAX_STEPS, steps);
     if (n < 1 || n > 0x7fffffffll) return fail(QSBC_ERR_INVALID, "n must be in [1, 2^31), got %lld", (long long)n);
-    if (t0 < 0 || t0 + steps > 0x7fffffffll) return fail(QSBC_ERR_INVALID, "t0 must be >= 0 with t0 + steps below 2^31, got %lld", (long long)t0);
-    if (!isfinite(lr)) return fail(QSBC_ERR_INVALID, "lr must be finite, got %g", lr);
-    if (!isfinite(eps)) return fail(QSBC_ERR_INVALID, "eps must be finite, got %g", eps);
-    if (!(beta1 >= 0.0 && beta1 < 1.0)) return fail(QSBC_ERR_INVALID, "beta1 must be in [0, 1), got %g", beta1);
-    if (!(beta2 >= 0.0 && beta2 < 1.0)) return fail(QSBC_ERR_INVALID, "beta2 must be in [0, 1), got %g", beta2);
-    bool bad = misaligned(obs) || misaligned(act) || misaligned(indices) || misaligned(counts) || misaligned(loss);
-    for (int i = 0; i < 6; ++i)
-        bad = bad || !net->w[i] || !net->m[i] || !net->v[i] || misaligned(net->w[i]) || misaligned(net->m[i]) || misaligned(net->v[i]) ||
-              (grads && (!grads[i] || misaligned(grads[i])));
-    if (bad) return fail(QSBC_ERR_INVALID, "a tensor of the net or of the call is NULL or not 4-byte aligned");
+    if (int rc = check_adam_t0(t0, steps, "steps")) return rc;
+    if (int rc = check_adam_rates(lr, beta1, beta2, eps)) return rc;
+    if (misaligned(obs) || misaligned(act) || misaligned(indices) || misaligned(counts) || misaligned(loss) ||
+        bad_six(net->w, net->m, net->v, grads))
+        return fail(QSBC_ERR_INVALID, "a tensor of the net or of the call is NULL or not 4-byte aligned");
     // everything the kernel writes, against each other
     Range rs[25];
     int nr = 0;
@@ -78,16 +53,11 @@ int qsbc_fit(const QsbcNet *net, const float *obs, const float *act, int64_t n, 
             if (rs[a].lo < rs[b].hi && rs[b].lo < rs[a].hi) return fail(QSBC_ERR_INVALID, "two tensors the call writes overlap");
 
     qsb::FitArgs F{};
-    for (int i = 0; i < 6; ++i) {
-        F.w[i] = net->w[i]; F.m[i] = net->m[i]; F.v[i] = net->v[i];
-        F.grads[i] = grads ? grads[i] : nullptr;
-    }
+    fill_fit_args(F, net->w, net->m, net->v, grads, lr, beta1, beta2, eps, batch, t0);
     F.obs = obs; F.act = act; F.indices = indices; F.counts = counts; F.loss = loss;
-    F.lr = lr; F.beta1 = beta1; F.beta2 = beta2;
-    F.b1f = (float)beta1; F.b2f = (float)beta2; F.omb1 = (float)(1.0 - beta1); F.omb2 = (float)(1.0 - beta2); F.eps = (float)eps;
-    F.steps = steps; F.batch = batch; F.t0 = (int)t0;
+    F.steps = steps;
     hipLaunchKernelGGL(qsb::k_bc_fit, dim3(1), dim3(qsb::kFitBlock), 0, (hipStream_t)stream, F);   // one workgroup: one CU's worth of work
-    QSBC_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return QSBC_OK;
 }
 
@@ -113,10 +83,10 @@ int qsbc_loss(const float *const *w, const float *obs, const float *act, int64_t
     L.obs = obs; L.act = act; L.rows = rows; L.partials = partials; L.count = (int)count; L.blocks = (int)blocks;
     const int64_t g = grid ? grid : (blocks < 1024 ? blocks : 1024);
     hipLaunchKernelGGL(qsb::k_bc_loss, dim3((unsigned)(g < blocks ? g : blocks)), dim3(qsb::kFitBlock), 0, (hipStream_t)stream, L);
-    QSBC_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(qsb::k_bc_loss_sum, dim3(1), dim3(qsb::kSumBlock), 0, (hipStream_t)stream, (const double *)partials, (int)blocks,
                        (int)count, out);
-    QSBC_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return QSBC_OK;
 }
 

@@ -12,13 +12,15 @@ need no kernel; the fit of the net is the caller's -- examples/mpc_learned.py), 
 kernels read.  ``LearnedShootingMPC`` is the closed loop on a VecDockingEnv or a single-env shim.  Nothing here imports oracle/.
 
 ``DynamicsNet.fit`` is Dynamic_Net.train_dynamic (:120-128) on the device: every Adam step of a fit in one launch, through a
-fourth library (libquadsim_dynfit.so, include/quadsim_dyn_fit.h) bound above the class.
+fourth library (libquadsim_dynfit.so, include/quadsim_dyn_fit.h).
 
 ``learned_mppi_plan`` / ``LearnedMPPI`` are MPPI (``mpc.mppi_plan``'s candidates, weights and update) over the same net and
-image, through a third library (libquadsim_dynmppi.so, include/quadsim_dyn_mppi.h) bound at the end of this module.
+image, through a third library (libquadsim_dynmppi.so, include/quadsim_dyn_mppi.h).
+
+All three libraries are entries of ``_lib.SIDE``, loaded and called through ``_lib``'s one side-library path.
 """
 import ctypes as C
-import os
+import functools
 
 from . import _lib
 from .mpc import MPPI_DEFAULT_LAMBDA, MPPI_DEFAULT_SIGMA
@@ -29,45 +31,12 @@ MAX_PATHS, MAX_HORIZON, MAX_K = 65536, 1024, 1 << 36
 COMPILED_WIDTHS = ((64, 64), (128, 128), (208, 112))
 STD_EPS = 1.0e-6                       # Dynamic_Net.prediction: (s_a - mean) / (std + 1e-6)
 
-EXPORTS = ["qsd_version", "qsd_last_error", "qsd_net_image_bytes", "qsd_net_pack", "qsd_plan_workspace_bytes", "qsd_shooting_plan"]
-
-
-class QsdNet(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("h1", C.c_int32), ("h2", C.c_int32), ("reserved", C.c_int32)] + [
-        (k, C.c_void_p) for k in ("wt1", "b1", "wt2", "b2", "wt3", "b3", "in_mean", "in_rscale", "out_std", "out_mean")]
-
-
-_dyn = None
-
-
-def load():
-    """dlopen libquadsim_dyn.so; raises QuadsimError if it has not been built (there is no fallback)"""
-    global _dyn
-    if _dyn is not None:
-        return _dyn
-    if not os.path.exists(_lib.DYN_LIB_PATH):
-        raise _lib.QuadsimError("%s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % _lib.DYN_LIB_PATH)
-    import torch  # noqa: F401  (its HIP runtime must be the resident one: see _lib.load)
-    lib = C.CDLL(_lib.DYN_LIB_PATH)
-    vp, i64, u64, i32 = C.c_void_p, C.c_int64, C.c_uint64, C.c_int32
-    sig = {
-        "qsd_version": [],
-        "qsd_net_image_bytes": [i32, i32, C.POINTER(C.c_size_t)],
-        "qsd_net_pack": [C.POINTER(QsdNet), vp, vp],
-        "qsd_plan_workspace_bytes": [i64, i32, C.POINTER(C.c_size_t)],
-        "qsd_shooting_plan": [vp, i64, vp, u64, u64, u64, i32, i32] + [vp] * 8,
-    }
-    for name, args in sig.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = args, C.c_int
-    lib.qsd_last_error.argtypes, lib.qsd_last_error.restype = [], C.c_char_p
-    _dyn = lib
-    return lib
-
-
-def check(rc, what):
-    if rc != 0:
-        raise _lib.QuadsimError("%s failed (%d): %s" % (what, rc, load().qsd_last_error().decode("utf-8", "replace")))
+# the three libraries bound here are entries of _lib.SIDE: their paths, signatures, loader, status check and call helper are
+# _lib's.  The names below stay this module's so that callers and tests can replace a loader
+QsdNet, QsdfNet = _lib.QsdNet, _lib.QsdfNet
+EXPORTS, MPPI_EXPORTS, FIT_EXPORTS = (_lib.SIDE[key]["exports"] for key in ("dyn", "dynmppi", "dynfit"))
+load, load_mppi, load_fit = (functools.partial(_lib.side_load, key) for key in ("dyn", "dynmppi", "dynfit"))
+check, check_mppi, check_fit = (functools.partial(_lib.side_check, key) for key in ("dyn", "dynmppi", "dynfit"))
 
 
 def check_widths(h1, h2):
@@ -96,54 +65,26 @@ def check_plan_args(horizon, paths, k=0, n=1):
         raise ValueError("n * ceil(paths / 16) must be below 2^31, got %d x %d" % (n, (paths + 15) // 16))
     return horizon, paths, k, n
 
+
+def check_keys(seed, gid0, n):
+    """-> (seed, gid0) as ints; ValueError unless they key the candidates of n rows"""
+    seed, gid0 = int(seed), int(gid0)
+    if not (0 <= seed < 1 << 64 and 0 <= gid0 and gid0 + n <= 1 << 48):
+        raise ValueError("seed must fit 64 bits and gid0 + N 48 bits")
+    return seed, gid0
+
 # ---------------------------------------------------------------------------------------------------- the fit of the net
 # libquadsim_dynfit.so (include/quadsim_dyn_fit.h): a library of its own.  It takes the net's own tensors (DynamicsNet.fit), not
 # the packed image.
-FIT_EXPORTS = ["qsdf_version", "qsdf_last_error", "qsdf_fit"]
 FIT_MAX_BATCH, FIT_MAX_ITERS, FIT_MAX_K = 256, 4096, 1 << 48
 FIT_BETA1, FIT_BETA2, FIT_EPS = 0.9, 0.999, 1.0e-8          # tf.train.AdamOptimizer's defaults
-
-
-class QsdfNet(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("h1", C.c_int32), ("h2", C.c_int32), ("reserved", C.c_int32),
-                ("w", C.c_void_p * 6), ("m", C.c_void_p * 6), ("v", C.c_void_p * 6)] + [
-        (k, C.c_void_p) for k in ("in_mean", "in_rscale", "out_mean", "out_rscale")]
-
-
-_dynfit = None
-
-
-def load_fit():
-    """dlopen libquadsim_dynfit.so; raises QuadsimError if it has not been built (there is no fallback)"""
-    global _dynfit
-    if _dynfit is not None:
-        return _dynfit
-    if not os.path.exists(_lib.DYNFIT_LIB_PATH):
-        raise _lib.QuadsimError("%s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % _lib.DYNFIT_LIB_PATH)
-    import torch  # noqa: F401  (its HIP runtime must be the resident one: see _lib.load)
-    lib = C.CDLL(_lib.DYNFIT_LIB_PATH)
-    vp, i64, u64, i32, f64 = C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_double
-    lib.qsdf_version.argtypes, lib.qsdf_version.restype = [], C.c_int
-    lib.qsdf_fit.argtypes = [C.POINTER(QsdfNet), vp, vp, i64, i64, i32, i32, f64, f64, f64, f64, i64, u64, u64, vp, vp, vp,
-                             C.POINTER(C.c_void_p * 6), vp]
-    lib.qsdf_fit.restype = C.c_int
-    lib.qsdf_last_error.argtypes, lib.qsdf_last_error.restype = [], C.c_char_p
-    _dynfit = lib
-    return lib
-
-
-def check_fit(rc, what):
-    if rc != 0:
-        raise _lib.QuadsimError("%s failed (%d): %s" % (what, rc, load_fit().qsdf_last_error().decode("utf-8", "replace")))
 
 
 def check_fit_args(h1, h2, capacity, size, iters=100, batch=128, lr=1.0e-4, beta1=FIT_BETA1, beta2=FIT_BETA2, eps=FIT_EPS, t0=0, seed=0, k=0):
     """-> (size, iters, batch, lr, beta1, beta2, eps, t0, seed, k); ValueError for what qsdf_fit would refuse, before anything
     touches the library or the GPU"""
-    import math
     check_widths(h1, h2)
     capacity, size, iters, batch, t0, seed, k = int(capacity), int(size), int(iters), int(batch), int(t0), int(seed), int(k)
-    lr, beta1, beta2, eps = float(lr), float(beta1), float(beta2), float(eps)
     if not 1 <= batch <= FIT_MAX_BATCH:
         raise ValueError("batch must be in [1, %d], got %d" % (FIT_MAX_BATCH, batch))
     if not 1 <= iters <= FIT_MAX_ITERS:
@@ -152,18 +93,11 @@ def check_fit_args(h1, h2, capacity, size, iters=100, batch=128, lr=1.0e-4, beta
         raise ValueError("capacity must be in [1, 2^31), got %d" % capacity)
     if not 1 <= size <= capacity:
         raise ValueError("size must be in [1, capacity = %d], got %d" % (capacity, size))
-    if not (t0 >= 0 and t0 + iters < 1 << 31):
-        raise ValueError("t0 must be >= 0 with t0 + iters below 2^31, got %d" % t0)
+    lr, beta1, beta2, eps = _lib.check_adam_args(lr, beta1, beta2, eps, t0, iters, "iters")
     if not 0 <= seed < 1 << 64:
         raise ValueError("seed must fit 64 bits, got %d" % seed)
     if not 0 <= k < FIT_MAX_K:
         raise ValueError("k must be in [0, 2^48), got %d" % k)
-    for name, val in (("lr", lr), ("eps", eps)):
-        if not math.isfinite(val):
-            raise ValueError("%s must be finite, got %r" % (name, val))
-    for name, val in (("beta1", beta1), ("beta2", beta2)):
-        if not 0.0 <= val < 1.0:
-            raise ValueError("%s must be in [0, 1), got %r" % (name, val))
     return size, iters, batch, lr, beta1, beta2, eps, t0, seed, k
 
 
@@ -273,21 +207,18 @@ class DynamicsNet:
         if self.device.type != "cuda":
             raise _lib.QuadsimError("DynamicsNet.pack needs the net on a HIP device, it is on %s; there is no CPU path" % self.device)
         ts = self._tensors()
-        key = tuple((t.data_ptr(), t._version) for t in ts)
+        key = tuple((_lib.as_arg(t), t._version) for t in ts)
         if self._image is not None and key == self._image_key:
             return self._image
         for k, t in zip(self.WEIGHTS + ("in_mean", "in_rscale", "out_std", "out_mean"), ts):
-            if not (t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()):
-                raise ValueError("%s must be a contiguous float32 tensor on %s" % (k, self.device))
+            _lib.check_tensor(k, t, "float32", None, self.device)
         lib = load()
         if self._image is None:
             nbytes = C.c_size_t(0)
-            check(lib.qsd_net_image_bytes(self.h1, self.h2, C.byref(nbytes)), "qsd_net_image_bytes")
-            self._image = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
-        net = QsdNet(C.sizeof(QsdNet), self.h1, self.h2, 0, *[t.data_ptr() for t in ts])
-        with torch.cuda.device(self.device):
-            check(lib.qsd_net_pack(C.byref(net), C.c_void_p(self._image.data_ptr()),
-                                   C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "qsd_net_pack")
+            _lib.side_call("dyn", lib, "qsd_net_image_bytes", self.h1, self.h2, C.byref(nbytes))
+            self._image = _lib.new_tensor(self.device, (int(nbytes.value),), "uint8")
+        net = QsdNet(C.sizeof(QsdNet), self.h1, self.h2, 0, *map(_lib.as_arg, ts))
+        _lib.side_call("dyn", lib, "qsd_net_pack", C.byref(net), self._image, device=self.device)
         self._image_key = key
         return self._image
 
@@ -309,41 +240,30 @@ class DynamicsNet:
         import torch
         if self.device.type != "cuda":
             raise _lib.QuadsimError("DynamicsNet.fit needs the net on a HIP device, it is on %s; there is no CPU path" % self.device)
-        for name, t, cols in (("buf_x", buf_x, IN_DIM), ("buf_d", buf_d, OBS_DIM)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == cols
-                    and t.device == self.device and t.is_contiguous()):
-                raise ValueError("%s must be a contiguous float32 tensor of shape [capacity, %d] on %s" % (name, cols, self.device))
+        _lib.check_tensor("buf_x", buf_x, "float32", ("capacity", IN_DIM), self.device)
+        _lib.check_tensor("buf_d", buf_d, "float32", ("capacity", OBS_DIM), self.device)
         if buf_x.shape[0] != buf_d.shape[0]:
             raise ValueError("buf_x and buf_d must have the same capacity, got %d and %d" % (buf_x.shape[0], buf_d.shape[0]))
         k = self.fit_steps if k is None else k
         size, iters, batch, lr, beta1, beta2, eps, t0, seed, k = check_fit_args(
             self.h1, self.h2, buf_x.shape[0], size, iters, batch, lr, beta1, beta2, eps, self.fit_steps, seed, k)
-        if indices is not None and not (isinstance(indices, torch.Tensor) and indices.dtype == torch.int32 and tuple(indices.shape) == (iters, batch)
-                                        and indices.device == self.device and indices.is_contiguous()):
-            raise ValueError("indices must be a contiguous int32 tensor of shape [%d, %d] on %s" % (iters, batch, self.device))
+        if indices is not None:
+            _lib.check_tensor("indices", indices, "int32", (iters, batch), self.device)
         ws = self.parameters()
-        for name, t in zip(self.WEIGHTS + ("in_mean", "in_rscale", "out_mean", "out_rscale"), self._tensors()[:8] + [self.out_mean, self.out_rscale]):
-            if not (t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()):
-                raise ValueError("%s must be a contiguous float32 tensor on %s" % (name, self.device))
+        norms = [self.in_mean, self.in_rscale, self.out_mean, self.out_rscale]
+        for name, t in zip(self.WEIGHTS + ("in_mean", "in_rscale", "out_mean", "out_rscale"), ws + norms):
+            _lib.check_tensor(name, t, "float32", None, self.device)
         if self.adam_m is None:
             self.adam_m, self.adam_v = [torch.zeros_like(w) for w in ws], [torch.zeros_like(w) for w in ws]
-        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=self.device)     # noqa: E731
-        out = {"loss": new((iters,), torch.float32)}
+        out = {"loss": _lib.new_tensor(self.device, (iters,), "float32")}
         if return_indices:
-            out["indices"] = new((iters, batch), torch.int32)
-        grads = None
+            out["indices"] = _lib.new_tensor(self.device, (iters, batch), "int32")
         if return_grads:
             out["grads"] = [torch.empty_like(w) for w in ws]
-            grads = (C.c_void_p * 6)(*[g.data_ptr() for g in out["grads"]])
-        six = lambda ts: (C.c_void_p * 6)(*[t.data_ptr() for t in ts])     # noqa: E731
-        net = QsdfNet(C.sizeof(QsdfNet), self.h1, self.h2, 0, six(ws), six(self.adam_m), six(self.adam_v), self.in_mean.data_ptr(),
-                      self.in_rscale.data_ptr(), self.out_mean.data_ptr(), self.out_rscale.data_ptr())
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
-        lib = load_fit()
-        with torch.cuda.device(self.device):
-            check_fit(lib.qsdf_fit(C.byref(net), p(buf_x), p(buf_d), buf_x.shape[0], size, iters, batch, lr, beta1, beta2, eps, t0, seed, k,
-                                   p(indices), p(out["loss"]), p(out.get("indices")), grads,
-                                   C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "qsdf_fit")
+        net = QsdfNet(C.sizeof(QsdfNet), self.h1, self.h2, 0, _lib.six(ws), _lib.six(self.adam_m), _lib.six(self.adam_v), *map(_lib.as_arg, norms))
+        _lib.side_call("dynfit", load_fit(), "qsdf_fit", C.byref(net), buf_x, buf_d, buf_x.shape[0], size, iters, batch, lr, beta1, beta2, eps,
+                       t0, seed, k, indices, out["loss"], out.get("indices"), _lib.six(out["grads"]) if return_grads else None,
+                       device=self.device)
         self.fit_steps += iters
         self._image_key = None        # the kernel wrote the weights behind torch's back: their _version did not move
         return out
@@ -360,31 +280,24 @@ def learned_shooting_plan(net, obs, horizon=20, paths=200, seed=0, k=0, gid0=0, 
     import torch
     if not isinstance(net, DynamicsNet):
         raise ValueError("net must be a DynamicsNet, got %r" % type(net).__name__)
-    if not (isinstance(obs, torch.Tensor) and obs.dtype == torch.float32 and obs.dim() == 2 and obs.shape[1] == OBS_DIM
-            and obs.device == net.device and obs.is_contiguous()):
-        raise ValueError("obs must be a contiguous float32 tensor of shape [N, %d] on %s" % (OBS_DIM, net.device))
+    _lib.check_tensor("obs", obs, "float32", ("N", OBS_DIM), net.device)
     horizon, paths, k, n = check_plan_args(horizon, paths, k, obs.shape[0])
-    seed, gid0 = int(seed), int(gid0)
-    if not (0 <= seed < 1 << 64 and 0 <= gid0 and gid0 + n <= 1 << 48):
-        raise ValueError("seed must fit 64 bits and gid0 + N 48 bits")
+    seed, gid0 = check_keys(seed, gid0, n)
     image = net.pack()
-    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=net.device)     # noqa: E731
-    out = {"actions": new((n, 4), torch.float32), "best_score": new((n,), torch.float64), "best_index": new((n,), torch.int32)}
+    new = functools.partial(_lib.new_tensor, net.device)
+    out = {"actions": new((n, 4), "float32"), "best_score": new((n,), "float64"), "best_index": new((n,), "int32")}
     if return_sequence:
-        out["sequence"] = new((n, horizon, 4), torch.float32)
+        out["sequence"] = new((n, horizon, 4), "float32")
     if return_scores:
-        out["scores"] = new((n, paths), torch.float64)
+        out["scores"] = new((n, paths), "float64")
     if return_traj:
-        out["traj"] = new((n, paths, horizon, OBS_DIM), torch.float32)
+        out["traj"] = new((n, paths, horizon, OBS_DIM), "float32")
     lib = load()
     nbytes = C.c_size_t(0)
-    check(lib.qsd_plan_workspace_bytes(n, paths, C.byref(nbytes)), "qsd_plan_workspace_bytes")
-    work = new((int(nbytes.value),), torch.uint8)         # torch's caching allocator: no device allocation in steady state
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
-    with torch.cuda.device(net.device):
-        check(lib.qsd_shooting_plan(p(image), n, p(obs), seed, gid0, k, horizon, paths, p(work), p(out["actions"]), p(out["best_score"]),
-                                    p(out["best_index"]), p(out.get("sequence")), p(out.get("scores")), p(out.get("traj")),
-                                    C.c_void_p(torch.cuda.current_stream(net.device).cuda_stream)), "qsd_shooting_plan")
+    _lib.side_call("dyn", lib, "qsd_plan_workspace_bytes", n, paths, C.byref(nbytes))
+    _lib.side_call("dyn", lib, "qsd_shooting_plan", image, n, obs, seed, gid0, k, horizon, paths, new((int(nbytes.value),), "uint8"),
+                   out["actions"], out["best_score"], out["best_index"], out.get("sequence"), out.get("scores"), out.get("traj"),
+                   device=net.device)
     return out
 
 
@@ -430,51 +343,23 @@ class LearnedShootingMPC:
         [steps,1] on the host; its step never resets, so stop at the first done yourself)"""
         from .mpc import _closed_loop
         if not self.single:
-            return _closed_loop(self.env, self.act, steps)
+            return _closed_loop(self.env, self.act, steps, self._after_step)
         import torch
         R, D = [], []
         for _ in range(int(steps)):
             _, r, d, _ = self.env.step(self.act())
+            if self._after_step is not None:
+                self._after_step(d)
             R.append([float(r)]); D.append([bool(d)])
         return torch.tensor(R, dtype=torch.float32), torch.tensor(D, dtype=torch.bool)
+
+    _after_step = None      # the per-done hook of mpc._closed_loop: a planner with state between plans defines it
 
 
 # ---------------------------------------------------------------------------------------------------- MPPI over the net
 # libquadsim_dynmppi.so (include/quadsim_dyn_mppi.h): a library of its own, bound here beside the shooting planner's.  It takes
 # the image that DynamicsNet.pack builds and the net's widths; nothing of libquadsim_dyn.so's host state.
-MPPI_EXPORTS = ["qsdm_version", "qsdm_last_error", "qsdm_workspace_bytes", "qsdm_mppi_plan"]
 MPPI_MAX_ITERATIONS, MPPI_MAX_K = 16, 1 << 33
-
-_dynmppi = None
-
-
-def load_mppi():
-    """dlopen libquadsim_dynmppi.so; raises QuadsimError if it has not been built (there is no fallback)"""
-    global _dynmppi
-    if _dynmppi is not None:
-        return _dynmppi
-    if not os.path.exists(_lib.DYNMPPI_LIB_PATH):
-        raise _lib.QuadsimError("%s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % _lib.DYNMPPI_LIB_PATH)
-    import torch  # noqa: F401  (its HIP runtime must be the resident one: see _lib.load)
-    lib = C.CDLL(_lib.DYNMPPI_LIB_PATH)
-    vp, i64, u64, i32, f32 = C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_float
-    sig = {
-        "qsdm_version": [],
-        "qsdm_workspace_bytes": [i64, i32, i32, C.POINTER(C.c_size_t)],
-        "qsdm_mppi_plan": [vp, i32, i32, i64, vp, u64, u64, u64, i32, i32, i32, f32, f32, i32] + [vp] * 11,
-    }
-    for name, args in sig.items():
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = args, C.c_int
-    lib.qsdm_last_error.argtypes, lib.qsdm_last_error.restype = [], C.c_char_p
-    _dynmppi = lib
-    return lib
-
-
-def check_mppi(rc, what):
-    if rc != 0:
-        raise _lib.QuadsimError("%s failed (%d): %s" % (what, rc, load_mppi().qsdm_last_error().decode("utf-8", "replace")))
-
 
 def check_mppi_plan_args(horizon, paths, iterations, lam, sigma, shift=False, k=0, n=1):
     """-> (horizon, paths, iterations, lam, sigma, shift as 0 / 1, k, n); ValueError for what qsdm_mppi_plan would refuse, before
@@ -517,38 +402,29 @@ def learned_mppi_plan(net, obs, horizon=20, paths=200, iterations=2, lam=MPPI_DE
     import torch
     if not isinstance(net, DynamicsNet):
         raise ValueError("net must be a DynamicsNet, got %r" % type(net).__name__)
-    if not (isinstance(obs, torch.Tensor) and obs.dtype == torch.float32 and obs.dim() == 2 and obs.shape[1] == OBS_DIM
-            and obs.device == net.device and obs.is_contiguous()):
-        raise ValueError("obs must be a contiguous float32 tensor of shape [N, %d] on %s" % (OBS_DIM, net.device))
+    _lib.check_tensor("obs", obs, "float32", ("N", OBS_DIM), net.device)
     horizon, paths, iterations, lam, sigma, shift, k, n = check_mppi_plan_args(horizon, paths, iterations, lam, sigma, shift, k, obs.shape[0])
-    seed, gid0 = int(seed), int(gid0)
-    if not (0 <= seed < 1 << 64 and 0 <= gid0 and gid0 + n <= 1 << 48):
-        raise ValueError("seed must fit 64 bits and gid0 + N 48 bits")
+    seed, gid0 = check_keys(seed, gid0, n)
     for name, t, shape in (("nominal", nominal, (n, horizon, 4)), ("noise", noise, (iterations, paths, horizon, 4))):
-        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == shape
-                                  and t.device == net.device and t.is_contiguous()):
-            raise ValueError("%s must be a contiguous float32 tensor of shape %s on %s" % (name, list(shape), net.device))
+        if t is not None:
+            _lib.check_tensor(name, t, "float32", shape, net.device)
     image = net.pack()
-    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=net.device)     # noqa: E731
-    out = {"actions": new((n, 4), torch.float32), "nominal": new((n, horizon, 4), torch.float32), "best_score": new((n,), torch.float64)}
+    new = functools.partial(_lib.new_tensor, net.device)
+    out = {"actions": new((n, 4), "float32"), "nominal": new((n, horizon, 4), "float32"), "best_score": new((n,), "float64")}
     if return_scores:
-        out["scores"] = new((n, iterations, paths), torch.float64)
+        out["scores"] = new((n, iterations, paths), "float64")
     if return_trace:
-        out["trace"] = new((n, iterations + 1, horizon, 4), torch.float32)
+        out["trace"] = new((n, iterations + 1, horizon, 4), "float32")
     if return_candidates:
-        out["candidates"] = new((n, paths, horizon, 4), torch.float32)
+        out["candidates"] = new((n, paths, horizon, 4), "float32")
     if return_traj:
-        out["traj"] = new((n, paths, horizon, OBS_DIM), torch.float32)
+        out["traj"] = new((n, paths, horizon, OBS_DIM), "float32")
     lib = load_mppi()
     nbytes = C.c_size_t(0)
-    check_mppi(lib.qsdm_workspace_bytes(n, horizon, paths, C.byref(nbytes)), "qsdm_workspace_bytes")
-    work = new((int(nbytes.value),), torch.uint8)         # torch's caching allocator: no device allocation in steady state
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
-    with torch.cuda.device(net.device):
-        check_mppi(lib.qsdm_mppi_plan(p(image), net.h1, net.h2, n, p(obs), seed, gid0, k, horizon, paths, iterations, lam, sigma, shift,
-                                      p(nominal), p(noise), p(work), p(out["actions"]), p(out["nominal"]), p(out["best_score"]),
-                                      p(out.get("scores")), p(out.get("trace")), p(out.get("candidates")), p(out.get("traj")),
-                                      C.c_void_p(torch.cuda.current_stream(net.device).cuda_stream)), "qsdm_mppi_plan")
+    _lib.side_call("dynmppi", lib, "qsdm_workspace_bytes", n, horizon, paths, C.byref(nbytes))
+    _lib.side_call("dynmppi", lib, "qsdm_mppi_plan", image, net.h1, net.h2, n, obs, seed, gid0, k, horizon, paths, iterations, lam, sigma, shift,
+                   nominal, noise, new((int(nbytes.value),), "uint8"), out["actions"], out["nominal"], out["best_score"], out.get("scores"),
+                   out.get("trace"), out.get("candidates"), out.get("traj"), device=net.device)
     return out
 
 
@@ -576,16 +452,9 @@ class LearnedMPPI(LearnedShootingMPC):
         a = self.last_plan["actions"]
         return a[0].cpu().numpy() if self.single else a
 
-    def run(self, steps):
-        """as ``LearnedShootingMPC.run``; a new episode starts from a cold nominal"""
-        from .mpc import _closed_loop
+    def _after_step(self, d):
+        """``run`` is ``LearnedShootingMPC.run``; a new episode starts from a cold nominal"""
         if not self.single:
-            return _closed_loop(self.env, self.act, steps, lambda d: self.nominal.masked_fill_(d.bool().view(-1, 1, 1), 0.0))
-        import torch
-        R, D = [], []
-        for _ in range(int(steps)):
-            _, r, d, _ = self.env.step(self.act())
-            if d:
-                self.nominal.zero_()
-            R.append([float(r)]); D.append([bool(d)])
-        return torch.tensor(R, dtype=torch.float32), torch.tensor(D, dtype=torch.bool)
+            self.nominal.masked_fill_(d.bool().view(-1, 1, 1), 0.0)
+        elif d:
+            self.nominal.zero_()

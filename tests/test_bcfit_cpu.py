@@ -53,9 +53,13 @@ def test_every_declared_symbol_is_exported_and_lib_knows_the_fifth_path(lib):
     assert sorted(w for w in out.split() if w.startswith("qsbc_")) == names
     assert not set(bc.BC_EXPORTS) & (set(dynplan.EXPORTS) | set(dynplan.MPPI_EXPORTS) | set(dynplan.FIT_EXPORTS))
     assert os.path.basename(_lib.BC_LIB_PATH) == "libquadsim_bc.so"
-    assert sorted(os.path.basename(h) for h in _lib.BC_HEADERS) == ["bcfit_kernels.hpp", "dynfit_kernels.hpp", "quadsim_bc.h", "quadsim_device.hpp"]
-    assert all(os.path.exists(h) for h in _lib.BC_HEADERS + _lib.BC_SOURCES)
-    assert not [h for h in _lib.HEADERS + _lib.DYN_HEADERS + _lib.DYNMPPI_HEADERS + _lib.DYNFIT_HEADERS if "bc" in os.path.basename(h)]
+    side = _lib.SIDE
+    assert sorted(os.path.basename(h) for h in side["bc"]["headers"]) == ["bcfit_kernels.hpp", "dynfit_kernels.hpp", "quadsim_bc.h",
+                                                                           "quadsim_device.hpp", "side_host.hpp"]
+    assert [os.path.basename(s) for s in side["bc"]["sources"]] == ["bcfit.hip"]
+    assert all(os.path.exists(h) for h in side["bc"]["headers"] + side["bc"]["sources"])
+    assert not [h for h in _lib.HEADERS + side["dyn"]["headers"] + side["dynmppi"]["headers"] + side["dynfit"]["headers"]
+                if "bc" in os.path.basename(h)]
     env = dict(os.environ, QUADSIM_BC_LIB="/somewhere/else.so")
     got = subprocess.run([sys.executable, "-c", "from quadsim_amd import _lib; print(_lib.BC_LIB_PATH)"], cwd=ROOT, env=env,
                          capture_output=True, text=True, check=True).stdout.strip()

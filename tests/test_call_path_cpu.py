@@ -11,39 +11,88 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "policy_best_model_v0.npz")
-SCALARS = {"int32_t": "int32", "int64_t": "int64", "uint64_t": "uint64", "float": "float", "int": "int32"}   # LP64: int is 32 bits
+SCALARS = {"int32_t": "int32", "int64_t": "int64", "uint64_t": "uint64", "float": "float", "double": "double",
+           "int": "int32"}   # LP64: int is 32 bits
 
 
-def _header_prototypes():
-    """{entry point: [kind of every parameter]} from include/quadsim.h, kinds "ptr" / "int32" / "int64" / "uint64" / "float" """
-    text = open(os.path.join(ROOT, "include", "quadsim.h")).read()
+def _header_prototypes(header="quadsim.h", prefix="qs_"):
+    """{entry point: (kind of the result, [kind of every parameter])} of the prototypes `prefix`* in include/`header`, kinds
+    "ptr" / "int32" / "int64" / "uint64" / "float" / "double" """
+    text = open(os.path.join(ROOT, "include", header)).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+    def kind(decl):
+        return "ptr" if "*" in decl else SCALARS[decl.replace("const", "").split()[0]]
     protos = {}
-    for name, params in re.findall(r"\b(qs_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", text):
-        kinds = []
-        for p in (q.strip() for q in params.split(",")):
-            if p == "void":
-                continue
-            kinds.append("ptr" if "*" in p else SCALARS[p.replace("const", "").split()[0]])
-        protos[name] = kinds
+    for result, name, params in re.findall(r"\b((?:const\s+)?\w+[\s*]+)(%s[a-z_0-9]+)\s*\(([^()]*)\)\s*;" % prefix, text):
+        assert name not in protos, name
+        protos[name] = (kind(result), [kind(p) for p in (q.strip() for q in params.split(",")) if p != "void"])
     return protos
 
 
 def _ctype_kind(t):
-    if t is C.c_void_p or issubclass(t, C._Pointer):
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
         return "ptr"
-    return {C.c_int32: "int32", C.c_int64: "int64", C.c_uint64: "uint64", C.c_float: "float"}[t]
+    return {C.c_int32: "int32", C.c_int64: "int64", C.c_uint64: "uint64", C.c_float: "float", C.c_double: "double"}[t]
 
 
 def test_signature_table_matches_the_header():
     """the count and the kind (pointer, int32, int64, uint64, float) of every parameter of every entry point"""
     from quadsim_amd import _lib
     protos = _header_prototypes()
-    assert protos.pop("qs_last_error") == []
+    assert protos.pop("qs_last_error") == ("ptr", [])
     assert sorted(protos) == sorted(_lib.SIGNATURES) and len(protos) == 68
-    for name, kinds in protos.items():
-        assert [_ctype_kind(t) for t in _lib.SIGNATURES[name]] == kinds, name
+    for name, (result, kinds) in protos.items():
+        assert result == "int32" and [_ctype_kind(t) for t in _lib.SIGNATURES[name]] == kinds, name
     assert sorted(_lib.EXPORTS) == sorted(list(_lib.SIGNATURES) + ["qs_last_error"])
+
+
+def test_side_signature_tables_match_their_headers():
+    """the same for the four side libraries: the prototypes of each header are exactly the table's entries, with the count and
+    kind (pointer, int32, int64, uint64, float, double) of every parameter and the kind of the result"""
+    from quadsim_amd import _lib
+    assert list(_lib.SIDE) == ["dyn", "dynmppi", "dynfit", "bc"]
+    counts = {}
+    for key, e in _lib.SIDE.items():
+        protos = _header_prototypes(e["header"], e["prefix"])
+        assert sorted(protos) == sorted(e["signatures"]) == sorted(e["exports"]), key
+        for name, sig in e["signatures"].items():
+            args, result = sig if isinstance(sig, tuple) else (sig, C.c_int)
+            assert (_ctype_kind(result), [_ctype_kind(t) for t in args]) == protos[name], name
+        assert protos[e["prefix"] + "last_error"] == ("ptr", []) and protos[e["prefix"] + "version"] == ("int32", [])
+        counts[key] = len(protos)
+    assert counts == {"dyn": 6, "dynmppi": 4, "dynfit": 3, "bc": 5}
+    assert _header_prototypes("quadsim_bc.h", "qsbc_")["qsbc_loss_blocks"] == ("int64", ["int64"])
+
+
+def test_each_side_library_keeps_its_own_error_text():
+    """a refused call (refused before the device is touched: nothing is launched) writes the error text of its own library and
+    leaves the other three as they were"""
+    from quadsim_amd import _lib
+    _lib.build_library()
+    libs = {key: _lib.side_load(key) for key in _lib.SIDE}
+    nbytes, six = C.c_size_t(0), (C.c_void_p * 6)()
+    x = C.addressof(six)                                       # a non-NULL pointer that no refused call dereferences
+    net = _lib.QsdfNet(12345)                                  # a struct_size no other test uses
+    refusals = {
+        "dyn": (lambda lib: lib.qsd_plan_workspace_bytes(-12345, 200, C.byref(nbytes)), b"n must be >= 1, got -12345"),
+        "dynmppi": (lambda lib: lib.qsdm_workspace_bytes(1, -12345, 200, C.byref(nbytes)), b"horizon must be in [1, 1024], got -12345"),
+        "dynfit": (lambda lib: lib.qsdf_fit(C.byref(net), x, x, 1, 1, 1, 1, 1e-4, 0.9, 0.999, 1e-8, 0, 0, 0, None, x, None, None, None),
+                   b"QsdfNet.struct_size is 12345, expected %d" % C.sizeof(_lib.QsdfNet)),
+        "bc": (lambda lib: lib.qsbc_loss(six, x, x, -12345, None, 1, x, x, 0, None), b"n must be in [1, 2^31), got -12345"),
+    }
+
+    def texts():
+        return {key: getattr(lib, _lib.SIDE[key]["prefix"] + "last_error")() for key, lib in libs.items()}
+    for key, (refuse, text) in refusals.items():
+        before = texts()
+        assert before[key] != text
+        assert refuse(libs[key]) == 1                          # Q??_ERR_INVALID
+        after = texts()
+        assert after.pop(key) == text
+        del before[key]
+        assert after == before, key
+    assert len(set(texts().values())) == 4
 
 
 # ---------------------------------------------------------------- the shipped _call on a fake library
@@ -274,19 +323,23 @@ def test_planner_wrappers_call_through_the_env(stub):
 def test_no_call_site_goes_round_the_call_path():
     """in quadsim_amd/*.py outside _lib.py: no entry point is called on a library object (qs_destroy excepted: a handle that is
     going away follows no stream), raw _lib.call is used only by the host-I/O handles and, in vec_env.py, by the call path
-    itself and the commented group-stream launches, and tensors become pointers in _lib.py alone (dynplan.py binds a library
-    of its own)"""
+    itself and the commented group-stream launches, and tensors become pointers in _lib.py alone.  The side libraries' entry
+    points are attributes of nothing anywhere, _lib.py included: they are named as strings to _lib.side_call, which looks them
+    up, and dynplan.py and bc.py reach their libraries through it alone"""
     raw_ok = {"qs_set_stream", "qs_sync", "name", "qs_step_group", "qs_step_groups"}
     for path in sorted(glob.glob(os.path.join(ROOT, "quadsim_amd", "*.py"))):
         f = os.path.basename(path)
-        if f == "_lib.py":
-            continue
         src = open(path).read()
-        direct = re.findall(r"(?:\blib|\b_lib|load\(\))\.(qs_[a-z_0-9]+)", src)
+        assert not re.findall(r"\.(qs(?:d|dm|df|bc)_[a-z_0-9]+)", src), f
+        if f == "_lib.py":
+            assert len(re.findall(r"getattr\(lib, name\)", src)) == 3          # the two loaders and side_call
+            continue
+        direct = re.findall(r"(?:\blib|\b_lib|load\w*\(\))\.(qs[a-z]*_[a-z_0-9]+)", src)
         assert set(direct) <= {"qs_destroy"}, (f, direct)
-        if f != "dynplan.py":
-            for needle in ("data_ptr()", "data_as", "C.c_void_p("):
-                assert needle not in src, (f, needle)
+        for needle in ("data_ptr()", "data_as", "C.c_void_p(", "CDLL", "argtypes", "cuda_stream"):
+            assert needle not in src or (needle == "cuda_stream" and f == "vec_env.py"), (f, needle)
+        if f in ("dynplan.py", "bc.py"):
+            assert "getattr(lib" not in src and src.count("_lib.side_call(") >= 3, f
         raw = re.findall(r"_lib\.call\(\s*([^,]+),\s*\"?([a-z_0-9]+)\"?", src)
         if f == "vec_env.py":
             assert sorted(n for _, n in raw) == sorted(raw_ok), raw
@@ -295,3 +348,4 @@ def test_no_call_site_goes_round_the_call_path():
                 assert before.lstrip().startswith("# not _call:"), (name, before)
         else:
             assert f in ("envs.py", "drone.py") or not raw, (f, raw)
+

@@ -53,9 +53,13 @@ def test_every_declared_symbol_is_exported_and_lib_knows_the_fourth_path(lib):
     assert sorted(w for w in out.split() if w.startswith("qsdf_")) == names
     assert not set(dynplan.FIT_EXPORTS) & (set(dynplan.EXPORTS) | set(dynplan.MPPI_EXPORTS))
     assert os.path.basename(_lib.DYNFIT_LIB_PATH) == "libquadsim_dynfit.so"
-    assert sorted(os.path.basename(h) for h in _lib.DYNFIT_HEADERS) == ["dynfit_kernels.hpp", "quadsim_device.hpp", "quadsim_dyn_fit.h"]
-    assert all(os.path.exists(h) for h in _lib.DYNFIT_HEADERS + _lib.DYNFIT_SOURCES)
-    assert not [h for h in _lib.HEADERS + _lib.DYN_HEADERS + _lib.DYNMPPI_HEADERS if "dynfit" in os.path.basename(h) or "dyn_fit" in os.path.basename(h)]
+    dynfit = _lib.SIDE["dynfit"]
+    assert sorted(os.path.basename(h) for h in dynfit["headers"]) == ["dynfit_kernels.hpp", "quadsim_device.hpp", "quadsim_dyn_fit.h",
+                                                                       "side_host.hpp"]
+    assert [os.path.basename(s) for s in dynfit["sources"]] == ["dynfit.hip"]
+    assert all(os.path.exists(h) for h in dynfit["headers"] + dynfit["sources"])
+    assert not [h for h in _lib.HEADERS + _lib.SIDE["dyn"]["headers"] + _lib.SIDE["dynmppi"]["headers"]
+                if "dynfit" in os.path.basename(h) or "dyn_fit" in os.path.basename(h)]
     env = dict(os.environ, QUADSIM_DYNFIT_LIB="/somewhere/else.so")
     got = subprocess.run([sys.executable, "-c", "from quadsim_amd import _lib; print(_lib.DYNFIT_LIB_PATH)"], cwd=ROOT, env=env,
                          capture_output=True, text=True, check=True).stdout.strip()

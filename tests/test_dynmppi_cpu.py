@@ -245,12 +245,15 @@ def test_the_other_libraries_are_built_without_the_new_fragment():
     """dynmppi_kernels.hpp is a dependency of the third library alone, whose translation unit is the only file that includes
     it; the lists of the other two are what they were"""
     from quadsim_amd import _lib
-    assert not [h for h in _lib.HEADERS + _lib.DYN_HEADERS if "dynmppi" in os.path.basename(h) or "dyn_mppi" in os.path.basename(h)]
-    assert sorted(os.path.basename(h) for h in _lib.DYN_HEADERS) == ["dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp",
-                                                                      "quadsim_dyn.h"]
-    assert sorted(os.path.basename(h) for h in _lib.DYNMPPI_HEADERS) == ["dynmppi_kernels.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp",
-                                                                          "quadsim_device.hpp", "quadsim_dyn_mppi.h"]
-    assert all(os.path.exists(h) for h in _lib.DYNMPPI_HEADERS + _lib.DYNMPPI_SOURCES)
+    dyn, dynmppi = _lib.SIDE["dyn"], _lib.SIDE["dynmppi"]
+    assert not [h for h in _lib.HEADERS + dyn["headers"] if "dynmppi" in os.path.basename(h) or "dyn_mppi" in os.path.basename(h)]
+    assert sorted(os.path.basename(h) for h in dyn["headers"]) == [
+        "dynplan_host.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp", "quadsim_dyn.h", "side_host.hpp"]
+    assert sorted(os.path.basename(h) for h in dynmppi["headers"]) == [
+        "dynmppi_kernels.hpp", "dynplan_host.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp", "quadsim_dyn_mppi.h",
+        "side_host.hpp"]
+    assert [os.path.basename(s) for s in dynmppi["sources"]] == ["dynmppi.hip"]
+    assert all(os.path.exists(h) for h in dynmppi["headers"] + dynmppi["sources"])
     csrc = os.path.join(ROOT, "quadsim_amd", "csrc")
     users = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f != "dynmppi_kernels.hpp"
                    and "dynmppi_kernels.hpp\"" in open(os.path.join(csrc, f)).read())

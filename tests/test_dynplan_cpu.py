@@ -197,8 +197,9 @@ def test_main_library_is_built_without_the_new_fragments():
     """the second library's fragments are not dependencies of libquadsim_hip.so, and its kernels are not in it"""
     from quadsim_amd import _lib
     assert not [h for h in _lib.HEADERS if "dynplan" in h]
-    assert sorted(os.path.basename(h) for h in _lib.DYN_HEADERS) == ["dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp",
-                                                                      "quadsim_dyn.h"]
+    assert not [h for h in _lib.HEADERS if "side_host" in h]
+    assert sorted(os.path.basename(h) for h in _lib.SIDE["dyn"]["headers"]) == [
+        "dynplan_host.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp", "quadsim_dyn.h", "side_host.hpp"]
     assert _lib.build_library() == _lib.LIB_PATH and os.path.exists(_lib.DYN_LIB_PATH)
 
 
