@@ -1,5 +1,5 @@
-"""ctypes binding of libquadsim_hip.so (the C ABI declared in include/quadsim.h), and the one table (SIDE), build, loader and
-call helper of the four side libraries that dynplan.py and bc.py wrap.
+"""ctypes binding of libquadsim_hip.so (the C ABI declared in include/quadsim.h), and the tables (SIDE, TRAIN), build, loader and
+call helper of the four side libraries that dynplan.py and bc.py wrap and of the training library that ppo2.py wraps.
 
 There is deliberately no fallback of any kind: if the HIP library is missing or
 no MI355X is visible, loading / qs_create raise.  Nothing here imports oracle/.
@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("QUADSIM_HIP_LIB") or os.path.join(CSRC, "libquadsim_h
 SOURCES = [os.path.join(CSRC, "quadsim_hip.hip")]
 # every fragment of the one translation unit is a rebuild dependency, bar those of the side libraries (SIDE below)
 HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith(
-    ("dynplan_", "dynmppi_", "dynfit_", "bcfit_", "side_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
+    ("dynplan_", "dynmppi_", "dynfit_", "bcfit_", "ppo2_", "side_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
 
 QS_OK = 0
 KIND_V0, KIND_V2, KIND_V1, KIND_HOVER = 0, 1, 2, 3
@@ -151,6 +151,20 @@ class QsbcNet(C.Structure):                    # include/quadsim_bc.h
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("w", C.c_void_p * 6), ("m", C.c_void_p * 6), ("v", C.c_void_p * 6)]
 
 
+class QspNet(C.Structure):                     # include/quadsim_ppo.h
+    _fields_ = [("struct_size", C.c_uint32), ("layout", C.c_int32), ("w", C.c_void_p * 13), ("m", C.c_void_p * 13), ("v", C.c_void_p * 13)]
+
+
+class QspBatch(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("n", C.c_int64)] + [
+        (k, C.c_void_p) for k in ("obs", "actions", "returns", "values", "neglogp")]
+
+
+class QspHyper(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32)] + [
+        (k, C.c_double) for k in ("lr", "cliprange", "cliprange_vf", "ent_coef", "vf_coef", "max_grad_norm", "beta1", "beta2", "eps")]
+
+
 f64, psize, psix = C.c_double, C.POINTER(C.c_size_t), C.POINTER(vp * 6)
 # The four libraries beside the main one, each its own translation unit, .so and code object, by short name.  They share at the
 # source level only: device fragments (*_kernels.hpp, dynplan_image.hpp, quadsim_device.hpp) and the host fragments side_host.hpp
@@ -195,7 +209,28 @@ SIDE = {
                    "qsbc_loss_blocks": ([i64], i64),
                    "qsbc_loss": [psix, vp, vp, i64, vp, i64, vp, vp, i32, vp]}),
 }
-for _e in SIDE.values():
+# The libraries that train a policy, entries of the same format in a table of their own: every helper below looks a key up in
+# both tables (_entry).
+TRAIN = {
+    # the PPO2 update (ppo2.py): takes the policy's own tensors; the forward chain and the Adam step of "dynfit"
+    "ppo": dict(env="QUADSIM_PPO_LIB", file="libquadsim_ppo.so", source="ppo2.hip", header="quadsim_ppo.h", prefix="qsp_",
+                fragments=("ppo2_kernels.hpp", "dynfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp"),
+                signatures={
+                    "qsp_version": [],
+                    "qsp_last_error": ([], C.c_char_p),
+                    "qsp_auto_slices": [i64],
+                    "qsp_workspace_bytes": [i64, i32, psize],
+                    "qsp_update": [C.POINTER(QspNet), C.POINTER(QspBatch), vp, i32, i64, i32, C.POINTER(QspHyper), i64, vp, u64, vp,
+                                   C.POINTER(vp * 13), vp]}),
+}
+
+
+def _entry(key):
+    """the entry `key` of SIDE or of TRAIN"""
+    return SIDE[key] if key in SIDE else TRAIN[key]
+
+
+for _e in (*SIDE.values(), *TRAIN.values()):
     _e["path"] = os.environ.get(_e["env"]) or os.path.join(CSRC, _e["file"])
     _e["sources"] = [os.path.join(CSRC, _e["source"])]
     _e["headers"] = [os.path.join(CSRC, h) for h in _e["fragments"]] + [os.path.join(HERE, "..", "include", _e["header"])]
@@ -203,8 +238,9 @@ for _e in SIDE.values():
 # the positions of every entry point's pointer parameters: side_call sends those through as_arg and leaves the scalars to the
 # argtypes (as_arg on a scalar costs 0.3 us, and a plan has a dozen of them)
 SIDE_POINTERS = {name: tuple(i for i, t in enumerate(sig[0] if isinstance(sig, tuple) else sig) if t is vp or issubclass(t, C._Pointer))
-                 for _e in SIDE.values() for name, sig in _e["signatures"].items()}
+                 for _e in (*SIDE.values(), *TRAIN.values()) for name, sig in _e["signatures"].items()}
 DYN_LIB_PATH, DYNMPPI_LIB_PATH, DYNFIT_LIB_PATH, BC_LIB_PATH = (SIDE[k]["path"] for k in ("dyn", "dynmppi", "dynfit", "bc"))
+PPO_LIB_PATH = TRAIN["ppo"]["path"]
 
 
 class QuadsimError(RuntimeError):
@@ -241,9 +277,9 @@ def build_one_library(sources, deps, out, link=(), force=False, verbose=False):
 
 
 def build_library(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all five libraries, returns the main one's
+    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all six libraries, returns the main one's
     path."""
-    for e in SIDE.values():
+    for e in (*SIDE.values(), *TRAIN.values()):
         build_one_library(e["sources"], e["headers"], e["path"], (), force, verbose)
     return build_one_library(SOURCES, HEADERS, LIB_PATH, ["-lhsa-runtime64"], force, verbose)
 
@@ -322,10 +358,10 @@ _side = {}
 
 
 def side_load(key):
-    """dlopen the side library `key` of SIDE, once; raises QuadsimError if it has not been built (there is no fallback)"""
+    """dlopen the side library `key` of SIDE or TRAIN, once; raises QuadsimError if it has not been built (there is no fallback)"""
     lib = _side.get(key)
     if lib is None:
-        e = SIDE[key]
+        e = _entry(key)
         if not os.path.exists(e["path"]):
             raise QuadsimError("%s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % e["path"])
         import torch  # noqa: F401  (its HIP runtime must be the resident one: see load)
@@ -339,7 +375,7 @@ def side_load(key):
 
 def side_check(key, rc, what):
     if rc != 0:
-        msg = getattr(side_load(key), SIDE[key]["prefix"] + "last_error")().decode("utf-8", "replace")
+        msg = getattr(side_load(key), _entry(key)["prefix"] + "last_error")().decode("utf-8", "replace")
         raise QuadsimError("%s failed (%d): %s" % (what, rc, msg))
 
 
@@ -365,6 +401,11 @@ def side_call(key, lib, name, *args, device=None):
 def six(tensors):
     """void *[6] of six tensors' device pointers (the w / m / v / grads arrays of both fits)"""
     return (C.c_void_p * 6)(*map(as_arg, tensors))
+
+
+def pointers(tensors):
+    """void *[len] of the tensors' device pointers, NULL for None (the w / m / v / grads arrays of QspNet)"""
+    return (C.c_void_p * len(tensors))(*map(as_arg, tensors))
 
 
 def new_tensor(device, shape, dtype):

@@ -43,6 +43,16 @@ class ActorCriticPolicy:
         with np.load(path, allow_pickle=False) as z:
             return cls({k: z[k] for k in z.files}, device, squash)
 
+    def save_npz(self, path):
+        """write what from_npz reads: the weights as they are now (the device tensors, logstd included), in the layout's keys"""
+        keys = ("w0", "b0", "w1", "b1", "w2", "b2") + (("wv0", "bv0") if self.towers else ()) + ("wv1", "bv1", "wv2", "bv2", "logstd")
+        np.savez(path, **{k: getattr(self, k).detach().cpu().numpy() for k in keys})
+
+    # -- the PPO2 update (quadsim_amd.ppo2) ---------------------------------------------------------------------------
+    def reset_ppo2_optimizer(self):
+        from .ppo2 import reset_ppo2_optimizer
+        reset_ppo2_optimizer(self)
+
     # -- model.step / model.value (policies.py:592-609) on torch ----------------------------------------------------
     def _heads(self, obs):
         t = self.torch
