@@ -3,7 +3,7 @@ PYTHON ?= python
 
 all: lib oracle
 
-# all five libraries, with the flags, sources and dependencies of quadsim_amd/_lib.py (HIPCC overrides the compiler there too)
+# all the libraries, with the flags, sources and dependencies of quadsim_amd/_lib.py (HIPCC overrides the compiler there too)
 lib:
 	$(PYTHON) -c "from quadsim_amd import _lib; _lib.build_library(verbose=True)"
 

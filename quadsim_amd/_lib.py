@@ -1,5 +1,6 @@
-"""ctypes binding of libquadsim_hip.so (the C ABI declared in include/quadsim.h), and the tables (SIDE, TRAIN), build, loader and
-call helper of the four side libraries that dynplan.py and bc.py wrap and of the training library that ppo2.py wraps.
+"""ctypes binding of libquadsim_hip.so (the C ABI declared in include/quadsim.h), and the tables (SIDE, TRAIN, IMITATE), build,
+loader and call helper of the four side libraries that dynplan.py and bc.py wrap, of the training library that ppo2.py wraps and
+of the imitation library that gail.py wraps.
 
 There is deliberately no fallback of any kind: if the HIP library is missing or
 no MI355X is visible, loading / qs_create raise.  Nothing here imports oracle/.
@@ -15,7 +16,7 @@ LIB_PATH = os.environ.get("QUADSIM_HIP_LIB") or os.path.join(CSRC, "libquadsim_h
 SOURCES = [os.path.join(CSRC, "quadsim_hip.hip")]
 # every fragment of the one translation unit is a rebuild dependency, bar those of the side libraries (SIDE below)
 HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith(
-    ("dynplan_", "dynmppi_", "dynfit_", "bcfit_", "ppo2_", "side_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
+    ("dynplan_", "dynmppi_", "dynfit_", "bcfit_", "ppo2_", "gail_", "side_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
 
 QS_OK = 0
 KIND_V0, KIND_V2, KIND_V1, KIND_HOVER = 0, 1, 2, 3
@@ -155,6 +156,11 @@ class QspNet(C.Structure):                     # include/quadsim_ppo.h
     _fields_ = [("struct_size", C.c_uint32), ("layout", C.c_int32), ("w", C.c_void_p * 13), ("m", C.c_void_p * 13), ("v", C.c_void_p * 13)]
 
 
+class QsgNet(C.Structure):                     # include/quadsim_gail.h
+    _fields_ = [("struct_size", C.c_uint32), ("hidden", C.c_int32), ("w", C.c_void_p * 6), ("m", C.c_void_p * 6), ("v", C.c_void_p * 6),
+                ("mean", C.c_void_p), ("rscale", C.c_void_p)]
+
+
 class QspBatch(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("n", C.c_int64)] + [
         (k, C.c_void_p) for k in ("obs", "actions", "returns", "values", "neglogp")]
@@ -223,14 +229,31 @@ TRAIN = {
                     "qsp_update": [C.POINTER(QspNet), C.POINTER(QspBatch), vp, i32, i64, i32, C.POINTER(QspHyper), i64, vp, u64, vp,
                                    C.POINTER(vp * 13), vp]}),
 }
+# The libraries that imitate an expert adversarially, a third table of the same format.
+IMITATE = {
+    # GAIL's discriminator (gail.py): its own tensors; the Adam step and the chunk geometry of "dynfit", q_tanh of the main library
+    "gail": dict(env="QUADSIM_GAIL_LIB", file="libquadsim_gail.so", source="gail.hip", header="quadsim_gail.h", prefix="qsg_",
+                 fragments=("gail_kernels.hpp", "dynfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp"),
+                 signatures={
+                     "qsg_version": [],
+                     "qsg_last_error": ([], C.c_char_p),
+                     "qsg_fit": [C.POINTER(QsgNet), vp, vp, i64, vp, vp, i64, vp, vp, vp, i32, i32, f64, f64, f64, f64, f64, i64, vp, psix, vp],
+                     "qsg_reward": [C.POINTER(QsgNet), vp, vp, i64, i64, i64, vp, vp, i32, vp],
+                     "qsg_math": [i32, vp, vp, i64, vp]}),
+}
+TABLES = (SIDE, TRAIN, IMITATE)
 
 
 def _entry(key):
-    """the entry `key` of SIDE or of TRAIN"""
-    return SIDE[key] if key in SIDE else TRAIN[key]
+    """the entry `key` of SIDE, of TRAIN or of IMITATE"""
+    return next(t[key] for t in TABLES if key in t)
 
 
-for _e in (*SIDE.values(), *TRAIN.values()):
+def _entries():
+    return [e for t in TABLES for e in t.values()]
+
+
+for _e in _entries():
     _e["path"] = os.environ.get(_e["env"]) or os.path.join(CSRC, _e["file"])
     _e["sources"] = [os.path.join(CSRC, _e["source"])]
     _e["headers"] = [os.path.join(CSRC, h) for h in _e["fragments"]] + [os.path.join(HERE, "..", "include", _e["header"])]
@@ -238,9 +261,10 @@ for _e in (*SIDE.values(), *TRAIN.values()):
 # the positions of every entry point's pointer parameters: side_call sends those through as_arg and leaves the scalars to the
 # argtypes (as_arg on a scalar costs 0.3 us, and a plan has a dozen of them)
 SIDE_POINTERS = {name: tuple(i for i, t in enumerate(sig[0] if isinstance(sig, tuple) else sig) if t is vp or issubclass(t, C._Pointer))
-                 for _e in (*SIDE.values(), *TRAIN.values()) for name, sig in _e["signatures"].items()}
+                 for _e in _entries() for name, sig in _e["signatures"].items()}
 DYN_LIB_PATH, DYNMPPI_LIB_PATH, DYNFIT_LIB_PATH, BC_LIB_PATH = (SIDE[k]["path"] for k in ("dyn", "dynmppi", "dynfit", "bc"))
 PPO_LIB_PATH = TRAIN["ppo"]["path"]
+GAIL_LIB_PATH = IMITATE["gail"]["path"]
 
 
 class QuadsimError(RuntimeError):
@@ -277,9 +301,9 @@ def build_one_library(sources, deps, out, link=(), force=False, verbose=False):
 
 
 def build_library(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all six libraries, returns the main one's
+    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all seven libraries, returns the main one's
     path."""
-    for e in (*SIDE.values(), *TRAIN.values()):
+    for e in _entries():
         build_one_library(e["sources"], e["headers"], e["path"], (), force, verbose)
     return build_one_library(SOURCES, HEADERS, LIB_PATH, ["-lhsa-runtime64"], force, verbose)
 
@@ -358,7 +382,7 @@ _side = {}
 
 
 def side_load(key):
-    """dlopen the side library `key` of SIDE or TRAIN, once; raises QuadsimError if it has not been built (there is no fallback)"""
+    """dlopen the side library `key` of SIDE, TRAIN or IMITATE, once; raises QuadsimError if it has not been built (there is no fallback)"""
     lib = _side.get(key)
     if lib is None:
         e = _entry(key)
