@@ -20,6 +20,7 @@ from .sb2 import load_sb2_model, read_sb2_weights
 from .bc import ExpertData, bc_fit, bc_loss, check_bc_args, epoch_schedule, pretrain
 from .ppo2 import PPO2, check_ppo2_args, minibatch_schedule, ppo2_update, reset_ppo2_optimizer, torch_ppo2_update
 from .gail import GAIL, Discriminator, GailRunner, check_gail_args, discriminator_schedule, torch_discriminator_fit
+from .ddpg import DDPG, DDPGPolicy, OUNoise, ReplayBuffer, check_ddpg_args, ddpg_update, replay_schedule, torch_ddpg_update
 
 __all__ = ["VecDockingEnv", "DockingEnv", "MovingDockingEnv", "ImitatingDockingEnv", "HoveringEnv", "Drone", "controller", "make", "register_gym_ids",
            "shard_range", "build_library", "QuadsimError", "C3_INIT_RANGE", "drone_step_batch", "ctrl_batch",
@@ -28,6 +29,7 @@ __all__ = ["VecDockingEnv", "DockingEnv", "MovingDockingEnv", "ImitatingDockingE
            "DynamicsNet", "LearnedShootingMPC", "learned_shooting_plan", "LearnedMPPI", "learned_mppi_plan", "check_mppi_plan_args", "check_fit_args",
            "ExpertData", "epoch_schedule", "pretrain", "bc_fit", "bc_loss", "check_bc_args",
            "PPO2", "ppo2_update", "torch_ppo2_update", "minibatch_schedule", "check_ppo2_args", "reset_ppo2_optimizer",
-           "GAIL", "Discriminator", "GailRunner", "discriminator_schedule", "torch_discriminator_fit", "check_gail_args"]
+           "GAIL", "Discriminator", "GailRunner", "discriminator_schedule", "torch_discriminator_fit", "check_gail_args",
+           "DDPG", "DDPGPolicy", "ReplayBuffer", "OUNoise", "replay_schedule", "ddpg_update", "torch_ddpg_update", "check_ddpg_args"]
 
 register_gym_ids()

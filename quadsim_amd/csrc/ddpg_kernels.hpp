@@ -1,0 +1,431 @@
+// ddpg_kernels.hpp -- the kernels of libquadsim_ddpg.so (include/quadsim_ddpg.h has the numerical contract).  A fragment of
+// ddpg.hip, nowhere else.  Shared with the fit libraries at the source level: forward_layer, adam_step, ld4 / st4 and the chunk
+// geometry (kFitBlock, kRows, kRP) of dynfit_kernels.hpp, and q_tanh of quadsim_device.hpp; none of their kernels is instantiated.
+//
+// One train step is ONE launch, and the kernel boundary is the only ordering across workgroups:
+//   k_ddpg_step  grid (2).  Workgroup 0 is the critic branch: the online critic 12 -> 128 -> (128 + 4 actions) -> 128 -> 1 in LDS
+//                in k_ppo_grad's transposed image, layer 1 widened to 132 inputs and the head run as four outputs of which three
+//                have zero weights (they add exact zeros).  Per 16-row chunk it computes y with the two TARGET nets, which it
+//                reads forward-only from memory (stream_layer: lanes along the units, so a weight row is one coalesced read and
+//                the activation an LDS broadcast), then runs the critic forward and backward, gradients in registers, rows
+//                ascending.  Workgroup 1 is the actor branch: the online actor in LDS, the online critic read forward-only from
+//                memory, dq/da through the critic's layers 1 and 2 into the actor's backward pass.  Either branch then applies
+//                Adam to its net and the Polyak average to its target, every thread on the elements it accumulated.
+//   k_ddpg_copy  one workgroup per tensor: the caller's 48 tensors into the workspace before the first step, out of it (with the
+//                twelve gradients, where asked for) after the last.
+// A branch reads the other branch's weights from BEFORE the step, so the four nets are double-buffered in the workspace: step s
+// of a call reads buffer s & 1 and writes buffer (s + 1) & 1.  Moments and gradients have one copy: only their branch touches
+// them.  Nothing waits on another workgroup, there is no grid barrier and no float atomic.
+#pragma once
+#include "dynfit_kernels.hpp"
+
+namespace qsdd {
+
+using qsf::Adam;
+using qsf::adam_step;
+using qsf::f32x4;
+using qsf::forward_layer;
+using qsf::kFitBlock;
+using qsf::kRG;
+using qsf::kRows;
+using qsf::kRP;
+using qsf::ld4;
+using qsf::st4;
+
+constexpr int kIn = 12, kInP = 16, kH = 128, kAct = 4, kOut = 4;
+constexpr int kCopyBlock = 256, kCopyTensors = 60;            // 24 weights, 24 moments, 12 gradients
+
+// a net as it lies flat in the workspace, tensors in the ABI's order and the policy's (in, out) layout.  B = 0: the critic (layer
+// 1 has 132 inputs, one output), B = 1: the actor
+template <int B>
+struct Flat {
+    static constexpr int k1 = B ? kH : kH + kAct, outs = B ? kAct : 1;
+    static constexpr int w0 = 0, b0 = w0 + kIn * kH, w1 = b0 + kH, b1 = w1 + k1 * kH, w2 = b1 + kH, b2 = w2 + kH * outs;
+    static constexpr int floats = (b2 + outs + 3) & ~3;
+};
+constexpr int net_at(int b) { return b ? 0 : Flat<1>::floats; }                     // in a buffer: actor | critic | the two targets
+constexpr int kOnline = Flat<0>::floats + Flat<1>::floats, kBuf = 2 * kOnline;     // a target lies kOnline after its online net
+// the workspace, in floats: two buffers, then m, v and the gradients of the two online nets (laid out as the online nets are)
+constexpr int kWsM = 2 * kBuf, kWsV = kWsM + kOnline, kWsG = kWsV + kOnline, kWsFloats = kWsG + kOnline;
+
+struct StepArgs {
+    float *ws;
+    const float *obs0, *act, *rew, *obs1, *done;
+    const int32_t *indices, *counts;             // the step's row [batch]; the step's count, nullable
+    float *stats;                                // the step's four
+    float lr_t[2];                               // critic, actor
+    float b1f, b2f, omb1, omb2, eps, gamma, tau, omt, clip;
+    int batch, cur, want_grads;
+};
+
+struct CopyArgs {
+    float *t[kCopyTensors];
+    int at[kCopyTensors], n[kCopyTensors];
+    float *ws;
+    int to_ws;
+};
+
+template <int B>
+struct Layout {
+    using F = Flat<B>;
+    static constexpr int ld1 = kInP + 4, ld2 = B ? kH + 4 : kH + kAct + 8, ld3 = kH + 4;     // 132 and 140: 4 and 12 mod 32 words
+    static constexpr int w1 = 0, b1 = w1 + kH * ld1, w2 = b1 + kH, b2 = w2 + kH * ld2, w3 = b2 + kH, b3 = w3 + kOut * ld3;
+    static constexpr int x = b3 + 16, a1 = x + kInP * kRP, a2 = a1 + (kH + kAct) * kRP, y = a2 + kH * kRP;
+    static constexpr int d2 = y + kOut * kRP, d1 = d2 + kH * kRP;
+    static constexpr int c1 = d1 + kH * kRP;     // the streamed critic's layer-1 input: h0 | action
+    static constexpr int sc = c1 + (kH + kAct) * kRP;    // per row: reward, done, y, q, q - y | q(pi)
+    static constexpr int floats = sc + 5 * kRP;
+};
+constexpr int kLdsFloats = Layout<0>::floats > Layout<1>::floats ? Layout<0>::floats : Layout<1>::floats;
+constexpr int kStatT = 448;                      // the thread that adds a branch's statistics
+
+// Z[u][r] = B[u] + sum_k W[k][u] A[k][r], k ascending: forward_layer's chain with the weights read from memory in the policy's
+// (in, out) layout.  One item = one unit x four rows, unit along the lanes; K is a multiple of 4
+template <bool RELU>
+__device__ __forceinline__ void stream_layer(const float *W, const float *Bv, const float *A, int K, float *Z)
+{
+    const int u = threadIdx.x & (kH - 1), rg = threadIdx.x >> 7;
+    const float b = Bv[u];
+    f32x4 acc = {b, b, b, b};
+    const float *w = W + u, *a = A + 4 * rg;
+    for (int k = 0; k < K; k += 4) {
+        float wk[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) wk[i] = w[(k + i) * kH];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const f32x4 ak = ld4(a + (k + i) * kRP);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[r] = __fmaf_rn(wk[i], ak[r], acc[r]);
+        }
+    }
+    if (RELU) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = fmaxf(acc[r], 0.0f);
+    }
+    st4(Z + u * kRP + 4 * rg, acc);
+}
+
+// the head of a streamed net for thread t < 16 OUTS: output t >> 4 of row t & 15, the same chain
+template <int OUTS>
+__device__ __forceinline__ float stream_head(const float *W, const float *Bv, const float *A)
+{
+    const int o = threadIdx.x >> 4, r = threadIdx.x & (kRows - 1);
+    float acc = Bv[o];
+#pragma unroll 8
+    for (int k = 0; k < kH; ++k) acc = __fmaf_rn(W[k * OUTS + o], A[k * kRP + r], acc);
+    return acc;
+}
+
+__device__ __forceinline__ float clamp_obs(float v, float clip) { return fminf(fmaxf(v, -clip), clip); }
+
+template <int B>
+__device__ __forceinline__ void branch(float *lds, const StepArgs &S)
+{
+    using L = Layout<B>;
+    using F = Flat<B>;
+    static_assert(L::floats * 4 <= 160 * 1024, "LDS");
+    static_assert(kFitBlock == 512 && kRows == 16 && kH == 128, "the thread maps below");
+    const int t = threadIdx.x;
+    const float *cur = S.ws + S.cur * kBuf;
+    float *nxt = S.ws + (S.cur ^ 1) * kBuf;
+    const float *net = cur + net_at(B);
+
+    // ---- the online net into LDS: zero everything (the padding stays zero), then the weights, transposed
+    for (int i = t; i < L::floats; i += kFitBlock) lds[i] = 0.0f;
+    __syncthreads();
+    for (int i = t; i < kIn * kH; i += kFitBlock) lds[L::w1 + (i & (kH - 1)) * L::ld1 + (i >> 7)] = net[F::w0 + i];
+    for (int i = t; i < F::k1 * kH; i += kFitBlock) lds[L::w2 + (i & (kH - 1)) * L::ld2 + (i >> 7)] = net[F::w1 + i];
+    for (int i = t; i < kH * F::outs; i += kFitBlock) lds[L::w3 + (i % F::outs) * L::ld3 + i / F::outs] = net[F::w2 + i];
+    if (t < kH) { lds[L::b1 + t] = net[F::b0 + t]; lds[L::b2 + t] = net[F::b1 + t]; }
+    if (t < F::outs) lds[L::b3 + t] = net[F::b2 + t];
+
+    int rows = S.counts ? S.counts[0] : S.batch;
+    rows = rows < S.batch ? rows : S.batch;
+    const float dscale = (float)(2.0 / (double)rows), ninv = -(float)(1.0 / (double)rows), frows = (float)rows;
+
+    // ---- the elements of this thread, in the policy's (in, out) layout (k_bc_fit's map; the critic's four action rows of w1
+    // are one element a thread more)
+    const int ti = t & 31, to = t >> 5;                  // w1: inputs 8 to + a, outputs ti + 32 j
+    const int o1 = t & 127, ig1 = t >> 7;                // w0: output o1, inputs 4 ig1 + a (ig1 == 3: the zero padding); w1: input 128 + ig1
+    const int o3 = t & 3, i3 = t >> 2;                   // w2: input i3, output o3
+    const bool own1 = ig1 < 3, own3 = o3 < F::outs;
+    const int bk = t < 128 ? 0 : t < 256 ? 1 : t < 256 + F::outs ? 2 : -1, bu = t & 127;
+    float g2[8][4], g1[4] = {}, g3 = 0.0f, gb = 0.0f, gx = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) g2[a][j] = 0.0f;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;               // thread kStatT: the sums of the rows so far
+
+    for (int r0 = 0; r0 < rows; r0 += kRows) {
+        // (phase C of the chunk before still reads x: the barrier)
+        __syncthreads();
+        const int gr = t & (kRows - 1), gc = t >> 4;
+        int idx = -1;
+        if (t < (kIn + kAct + 1) * kRows && r0 + gr < rows) idx = S.indices[r0 + gr];
+        if (B == 0) {
+            // ---- y = rew + (1 - done) gamma q'(obs1, pi'(obs1)), both target nets streamed
+            const float *at = cur + net_at(1) + kOnline, *ct = cur + net_at(0) + kOnline;
+            float pre = 0.0f;                            // the thread's value of (obs0 | act), fetched under the target pass
+            if (gc < kIn) {
+                lds[L::x + gc * kRP + gr] = idx < 0 ? 0.0f : clamp_obs(S.obs1[(int64_t)idx * kIn + gc], S.clip);
+                pre = idx < 0 ? 0.0f : clamp_obs(S.obs0[(int64_t)idx * kIn + gc], S.clip);
+            } else if (gc < kIn + kAct) {
+                pre = idx < 0 ? 0.0f : S.act[(int64_t)idx * kAct + (gc - kIn)];
+            } else if (gc == kIn + kAct) {
+                lds[L::sc + gr] = idx < 0 ? 0.0f : S.rew[idx];
+                lds[L::sc + kRP + gr] = idx < 0 ? 1.0f : S.done[idx];
+            }
+            __syncthreads();
+            stream_layer<true>(at + Flat<1>::w0, at + Flat<1>::b0, lds + L::x, kIn, lds + L::a1);
+            stream_layer<true>(ct + Flat<0>::w0, ct + Flat<0>::b0, lds + L::x, kIn, lds + L::c1);
+            __syncthreads();
+            stream_layer<true>(at + Flat<1>::w1, at + Flat<1>::b1, lds + L::a1, kH, lds + L::a2);
+            __syncthreads();
+            if (t < kAct * kRows) {
+                float unused;
+                lds[L::c1 + (kH + (t >> 4)) * kRP + gr] = qs::q_tanh(stream_head<kAct>(at + Flat<1>::w2, at + Flat<1>::b2, lds + L::a2), unused);
+            }
+            __syncthreads();
+            stream_layer<true>(ct + Flat<0>::w1, ct + Flat<0>::b1, lds + L::c1, kH + kAct, lds + L::a2);
+            __syncthreads();
+            if (t < kRows) {
+                const float q1 = stream_head<1>(ct + Flat<0>::w2, ct + Flat<0>::b2, lds + L::a2);
+                const float rew = lds[L::sc + t], done = lds[L::sc + kRP + t];
+                lds[L::sc + 2 * kRP + t] = done >= 1.0f ? rew : __fmaf_rn(__fmul_rn(__fsub_rn(1.0f, done), S.gamma), q1, rew);
+            }
+            if (gc < kIn) lds[L::x + gc * kRP + gr] = pre;
+            else if (gc < kIn + kAct) lds[L::a1 + (kH + gc - kIn) * kRP + gr] = pre;
+            __syncthreads();
+            // ---- the critic on (obs0, act), then dq over y's first row
+            forward_layer<true>(lds + L::w1, L::ld1, lds + L::b1, lds + L::x, kInP, kH, lds + L::a1);
+            __syncthreads();
+            forward_layer<true>(lds + L::w2, L::ld2, lds + L::b2, lds + L::a1, kH + kAct, kH, lds + L::a2);
+            __syncthreads();
+            forward_layer<false>(lds + L::w3, L::ld3, lds + L::b3, lds + L::a2, kH, kOut, lds + L::y);
+            __syncthreads();
+            if (t < kRows) {
+                const bool valid = r0 + t < rows;
+                const float q = lds[L::y + t], d = valid ? __fsub_rn(q, lds[L::sc + 2 * kRP + t]) : 0.0f;
+                lds[L::sc + 3 * kRP + t] = q;
+                lds[L::sc + 4 * kRP + t] = d;
+                lds[L::y + t] = __fmul_rn(d, dscale);
+            }
+            __syncthreads();
+            if (t == kStatT) {
+                for (int r = 0; r < kRows && r0 + r < rows; ++r) {
+                    const float d = lds[L::sc + 4 * kRP + r];
+                    s0 = __fmaf_rn(d, d, s0);
+                    s1 = __fadd_rn(s1, lds[L::sc + 3 * kRP + r]);
+                    s2 = __fadd_rn(s2, lds[L::sc + 2 * kRP + r]);
+                }
+            }
+        } else {
+            // ---- pi = actor(obs0), q(obs0, pi) with the online critic streamed, dq/da into y
+            const float *cr = cur + net_at(0);
+            if (gc < kIn) lds[L::x + gc * kRP + gr] = idx < 0 ? 0.0f : clamp_obs(S.obs0[(int64_t)idx * kIn + gc], S.clip);
+            __syncthreads();
+            forward_layer<true>(lds + L::w1, L::ld1, lds + L::b1, lds + L::x, kInP, kH, lds + L::a1);
+            stream_layer<true>(cr + Flat<0>::w0, cr + Flat<0>::b0, lds + L::x, kIn, lds + L::c1);
+            __syncthreads();
+            forward_layer<true>(lds + L::w2, L::ld2, lds + L::b2, lds + L::a1, kH, kH, lds + L::a2);
+            __syncthreads();
+            forward_layer<false>(lds + L::w3, L::ld3, lds + L::b3, lds + L::a2, kH, kOut, lds + L::y);
+            __syncthreads();
+            if (t < kAct * kRows) {
+                float unused;
+                const float a = qs::q_tanh(lds[L::y + (t >> 4) * kRP + gr], unused);
+                lds[L::y + (t >> 4) * kRP + gr] = a;
+                lds[L::c1 + (kH + (t >> 4)) * kRP + gr] = a;
+            }
+            __syncthreads();
+            stream_layer<true>(cr + Flat<0>::w1, cr + Flat<0>::b1, lds + L::c1, kH + kAct, lds + L::d2);
+            __syncthreads();
+            if (t < kRows) lds[L::sc + t] = stream_head<1>(cr + Flat<0>::w2, cr + Flat<0>::b2, lds + L::d2);
+            {
+                // dz1 of the critic: dq/dh1 = w2 under h1's mask, times -1 / rows on the step's rows
+                const int u = t & (kH - 1), rg = t >> 7;
+                const float w2u = cr[Flat<0>::w2 + u];
+                const f32x4 h = ld4(lds + L::d2 + u * kRP + 4 * rg);
+                f32x4 dz;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) dz[r] = (h[r] > 0.0f && r0 + 4 * rg + r < rows) ? __fmul_rn(w2u, ninv) : 0.0f;
+                st4(lds + L::d1 + u * kRP + 4 * rg, dz);
+            }
+            __syncthreads();
+            if (t < kAct * kRows) {
+                const float *w = cr + Flat<0>::w1 + (kH + (t >> 4)) * kH;
+                float da = 0.0f;
+#pragma unroll 8
+                for (int o = 0; o < kH; ++o) da = __fmaf_rn(w[o], lds[L::d1 + o * kRP + gr], da);
+                const float a = lds[L::y + (t >> 4) * kRP + gr];
+                lds[L::y + (t >> 4) * kRP + gr] = __fmul_rn(da, __fmaf_rn(-a, a, 1.0f));
+            }
+            if (t == kStatT)
+                for (int r = 0; r < kRows && r0 + r < rows; ++r) s0 = __fadd_rn(s0, lds[L::sc + r]);
+            __syncthreads();
+        }
+
+        // ---- phase A: the gradient of the head from (dy, a1), dz1 from (w2, dy) under a1's mask
+#pragma clang loop unroll(disable)
+        for (int rg = 0; rg < kRG; ++rg) {
+            const f32x4 a = ld4(lds + L::a2 + i3 * kRP + 4 * rg), d = ld4(lds + L::y + o3 * kRP + 4 * rg);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) g3 = __fmaf_rn(d[r], a[r], g3);
+        }
+        if (bk == 2) {
+#pragma unroll
+            for (int r = 0; r < kRows; ++r) gb = __fadd_rn(gb, lds[L::y + bu * kRP + r]);
+        }
+        if (t < (kH >> 2) * kRG) {
+            const int ig = t >> 2, rg = t & 3;
+            f32x4 acc[4] = {};
+#pragma unroll
+            for (int o = 0; o < kOut; ++o) {
+                const f32x4 wo = ld4(lds + L::w3 + o * L::ld3 + 4 * ig), dz = ld4(lds + L::y + o * kRP + 4 * rg);
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[a][r] = __fmaf_rn(wo[a], dz[r], acc[a][r]);
+            }
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const f32x4 hv = ld4(lds + L::a2 + (4 * ig + a) * kRP + 4 * rg);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[a][r] = hv[r] > 0.0f ? acc[a][r] : 0.0f;
+                st4(lds + L::d2 + (4 * ig + a) * kRP + 4 * rg, acc[a]);
+            }
+        }
+        __syncthreads();
+        // ---- phase B: the gradient of layer 1 from (dz1, a0 | act), dz0 from (w1, dz1) under a0's mask
+#pragma clang loop unroll(disable)
+        for (int rg = 0; rg < kRG; ++rg) {
+            f32x4 dz[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dz[j] = ld4(lds + L::d2 + (ti + 32 * j) * kRP + 4 * rg);
+#pragma unroll
+            for (int a = 0; a < 8; ++a) {
+                const f32x4 av = ld4(lds + L::a1 + (8 * to + a) * kRP + 4 * rg);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) g2[a][j] = __fmaf_rn(dz[j][r], av[r], g2[a][j]);
+            }
+        }
+        if (B == 0) {
+#pragma clang loop unroll(disable)
+            for (int rg = 0; rg < kRG; ++rg) {
+                const f32x4 dz = ld4(lds + L::d2 + o1 * kRP + 4 * rg), av = ld4(lds + L::a1 + (kH + ig1) * kRP + 4 * rg);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) gx = __fmaf_rn(dz[r], av[r], gx);
+            }
+        }
+        if (bk == 1) {
+#pragma unroll
+            for (int r = 0; r < kRows; ++r) gb = __fadd_rn(gb, lds[L::d2 + bu * kRP + r]);
+        }
+        {
+            // four inputs x four rows an item, its 128-term sum over four lanes: chain q takes o = q, q + 4, ...
+            const int lane = t & 63, wv = t >> 6;
+            const int q = lane >> 4, ig = (lane & 15) + 16 * (wv & 1), rg = wv >> 1;
+            f32x4 acc[4] = {};
+            const float *wp = lds + L::w2 + 4 * ig, *d = lds + L::d2 + 4 * rg;
+            for (int o = q; o < kH; o += 4) {
+                const f32x4 wo = ld4(wp + o * L::ld2), dz = ld4(d + o * kRP);
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[a][r] = __fmaf_rn(wo[a], dz[r], acc[a][r]);
+            }
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float s = acc[a][r];
+                    s = __fadd_rn(s, __shfl_xor(s, 16));          // S0 + S1 | S2 + S3
+                    s = __fadd_rn(s, __shfl_xor(s, 32));          // (S0 + S1) + (S2 + S3)
+                    acc[a][r] = s;
+                }
+            if (q == 0) {
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    const f32x4 hv = ld4(lds + L::a1 + (4 * ig + a) * kRP + 4 * rg);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[a][r] = hv[r] > 0.0f ? acc[a][r] : 0.0f;
+                    st4(lds + L::d1 + (4 * ig + a) * kRP + 4 * rg, acc[a]);
+                }
+            }
+        }
+        __syncthreads();
+        // ---- phase C: the gradient of layer 0 from (dz0, obs)
+        if (own1) {
+#pragma clang loop unroll(disable)
+            for (int rg = 0; rg < kRG; ++rg) {
+                const f32x4 dz = ld4(lds + L::d1 + o1 * kRP + 4 * rg);
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    const f32x4 xv = ld4(lds + L::x + (4 * ig1 + a) * kRP + 4 * rg);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) g1[a] = __fmaf_rn(dz[r], xv[r], g1[a]);
+                }
+            }
+        }
+        if (bk == 0) {
+#pragma unroll
+            for (int r = 0; r < kRows; ++r) gb = __fadd_rn(gb, lds[L::d1 + bu * kRP + r]);
+        }
+    }
+
+    // ---- Adam on the thread's own elements (m and v through memory, the weight from LDS into the next buffer), then the
+    // target's average with the new weight.  No thread reads another's element here
+    const Adam A{S.b1f, S.b2f, S.omb1, S.omb2, S.eps, S.lr_t[B]};
+    float *wn = nxt + net_at(B), *m = S.ws + kWsM + net_at(B), *v = S.ws + kWsV + net_at(B);
+    float *gout = S.want_grads ? S.ws + kWsG + net_at(B) : nullptr;
+    const float *tc = cur + net_at(B) + kOnline;
+    float *tn = nxt + net_at(B) + kOnline;
+    auto apply = [&](float g, float *lw, int e) {
+        adam_step(A, g, lw, wn, m, v, gout, e);
+        tn[e] = __fmaf_rn(S.tau, *lw, __fmul_rn(S.omt, tc[e]));
+    };
+#pragma unroll
+    for (int a = 0; a < 8; ++a)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) apply(g2[a][j], lds + L::w2 + (ti + 32 * j) * L::ld2 + 8 * to + a, F::w1 + (8 * to + a) * kH + ti + 32 * j);
+    if (B == 0) apply(gx, lds + L::w2 + o1 * L::ld2 + kH + ig1, F::w1 + (kH + ig1) * kH + o1);
+    if (own1) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) apply(g1[a], lds + L::w1 + o1 * L::ld1 + 4 * ig1 + a, F::w0 + (4 * ig1 + a) * kH + o1);
+    }
+    if (own3) apply(g3, lds + L::w3 + o3 * L::ld3 + i3, F::w2 + i3 * F::outs + o3);
+    if (bk >= 0) apply(gb, lds + (bk == 0 ? L::b1 : bk == 1 ? L::b2 : L::b3) + bu, (bk == 0 ? F::b0 : bk == 1 ? F::b1 : F::b2) + bu);
+    if (t == kStatT) {
+        if (B == 0) {
+            S.stats[0] = __fdiv_rn(s0, frows);
+            S.stats[2] = __fdiv_rn(s1, frows);
+            S.stats[3] = __fdiv_rn(s2, frows);
+        } else {
+            S.stats[1] = -__fdiv_rn(s0, frows);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kFitBlock) void k_ddpg_step(StepArgs S)
+{
+    __shared__ __align__(16) float lds[kLdsFloats];
+    if (blockIdx.x == 0) branch<0>(lds, S);
+    else branch<1>(lds, S);
+}
+
+__global__ __launch_bounds__(kCopyBlock) void k_ddpg_copy(CopyArgs C)
+{
+    const int k = blockIdx.x;
+    float *t = C.t[k], *w = C.ws + C.at[k];
+    if (!t) return;
+    for (int i = threadIdx.x; i < C.n[k]; i += kCopyBlock) {
+        if (C.to_ws) w[i] = t[i];
+        else t[i] = w[i];
+    }
+}
+
+}  // namespace qsdd
