@@ -45,6 +45,18 @@
  * ascending order from 0, written to partials[b] by whichever workgroup reaches the block.  A second launch of one workgroup adds
  * partials[0 .. blocks-1] in ascending order in float64 and writes out[0] = sum / (4 count) (float64).  The result does not
  * depend on `grid` (the number of workgroups of the first launch; 0 = the library's choice).
+ * NON-FINITE VALUES in qsbc_fit (NaN, +inf, -inf in a row, a weight or a moment).  A diverged run looks diverged:
+ * 1. Statistics.  The loss of a step is non-finite exactly when float64 torch autograd over the same rows, weights and moments
+ *    makes it non-finite (torch.relu, the mean squared error, tf.train.AdamOptimizer's formula).  So relu is a select that keeps
+ *    a NaN, relu = z <= 0 ? 0 : z, never a max that drops one.
+ * 2. State.  After a step the net holds a non-finite weight exactly when the arbiter's does: for the net as a whole, not per
+ *    element (the backward masks stay h > 0 ? acc : 0, which turn a NaN activation's term into 0).  Adam is held per element:
+ *    w', m', v' are non-finite in exactly the elements in which the formula above is, applied to the step's own gradient; where
+ *    it is finite the bounds of the finite case apply.
+ * 3. Unread data.  Rows that no index of a step names, index entries at and beyond counts[s] and every step before the first
+ *    one that reads a non-finite value are bit for bit what they are without it.
+ * 4. No faults.  No loaded float becomes an address, an index or a loop bound: no value of any kind makes a call fault or write
+ *    outside its arrays.
  *
  * ---- limits ---------------------------------------------------------------------------------------------------------
  * 1 <= batch <= 256, 1 <= counts[s] <= batch, 1 <= steps <= 4096, 1 <= n < 2^31, t0 >= 0 and t0 + steps < 2^31; lr, beta1,

@@ -59,6 +59,21 @@
  * Invariants: the same inputs give the same bits on any stream; one call with steps = a + b equals the call with steps = a
  * followed by the call with t0 + a, steps = b, bit for bit in all 48 tensors and the stats; a step with counts[s] = c in a call of
  * any batch >= c equals the same step in a call with batch = c.
+ * NON-FINITE VALUES (NaN, +inf, -inf in a row, a weight or a moment).  A diverged run looks diverged:
+ * 1. Statistics.  A statistic of a step is non-finite exactly when float64 torch autograd over the same rows, weights and moments
+ *    makes it non-finite -- torch.relu, torch.clamp, torch.where for the terminal rows, MpiAdam's formula: what update="torch" of
+ *    the package computes.  So relu, the clamp and tanh are selects that keep a NaN (relu = z <= 0 ? 0 : z; the clamp
+ *    v < -c ? -c : v > c ? c : v; tanh(NaN) = NaN, where q_tanh alone would give +-1), never a max / min that drops one.
+ * 2. State.  After a step a net (actor, critic, either target) holds a non-finite weight exactly when the arbiter's does: per
+ *    net, not per element (the backward masks stay h > 0 ? acc : 0, which turn a NaN activation's term into 0).  Adam is held
+ *    per element: w', m', v' are non-finite in exactly the elements in which the formula of 4. is, applied to the step's own
+ *    gradient; where it is finite the bounds of the finite case apply.
+ * 3. No invention.  With a finite obs_clip an infinite observation is its clamped copy, bit for bit; a NaN is never clamped
+ *    away.  A terminal row (done >= 1) never selects q1: non-finite target nets change nothing but themselves there.
+ * 4. Unread data.  Rows that no index of a step names, index entries at and beyond counts[s], and every step before the first
+ *    one that reads a non-finite value are bit for bit what they are without it.
+ * 5. No faults.  No loaded float becomes an address, an index or a loop bound: no value of any kind makes a call fault or write
+ *    outside its arrays.
  *
  * ---- limits ---------------------------------------------------------------------------------------------------------
  * 1 <= batch <= 256, 1 <= counts[s] <= batch, 1 <= steps <= 4096, 1 <= n < 2^31, t0 >= 0 and t0 + steps < 2^31; 0 <= gamma <= 1,

@@ -40,6 +40,18 @@
  * device pointers, which receive the six gradients of the LAST iteration in the weights' own layout.
  * Invariants: one call with iters = a + b equals the call with iters = a followed by the call with t0 + a, iters = b, bit
  * for bit in weights, moments and losses; units padded with zero weights (in and out) have exactly zero gradient and stay zero.
+ * NON-FINITE VALUES (NaN, +inf, -inf in a row, a weight or a moment).  A diverged run looks diverged:
+ * 1. Statistics.  The loss of a step is non-finite exactly when float64 torch autograd over the same rows, weights and moments
+ *    makes it non-finite (torch.relu, the mean squared error, tf.train.AdamOptimizer's formula).  So relu is a select that keeps
+ *    a NaN, relu = z <= 0 ? 0 : z, never a max that drops one.
+ * 2. State.  After a step the net holds a non-finite weight exactly when the arbiter's does: for the net as a whole, not per
+ *    element (the backward masks stay h > 0 ? acc : 0, which turn a NaN activation's term into 0).  Adam is held per element:
+ *    w', m', v' are non-finite in exactly the elements in which the formula above is, applied to the step's own gradient; where
+ *    it is finite the bounds of the finite case apply.
+ * 3. Unread data.  Rows that no index of a step names and every step before the first one that reads a
+ *    non-finite value are bit for bit what they are without it.
+ * 4. No faults.  No loaded float becomes an address, an index or a loop bound: no value of any kind makes a call fault or write
+ *    outside its arrays.
  *
  * ---- limits ---------------------------------------------------------------------------------------------------------
  * Hidden widths as in quadsim_dyn.h: (h1, h2) runs on the first of the compiled pairs (64, 64), (128, 128), (208, 112) that

@@ -69,6 +69,24 @@
  * qsg_math is the tests' window on the four device functions above: y[i] = f(x[i]), kind 0 tanh, 1 its 1 - tanh^2, 2 exp,
  * 3 log, 4 log1p, computed by the same device functions the two kernels inline.
  *
+ * NON-FINITE VALUES (NaN, +inf, -inf in a row, mean or rscale, a weight or a moment).  A diverged run looks diverged:
+ * 1. Statistics.  A statistic of a step of qsg_fit is non-finite exactly when float64 torch autograd over the same rows, weights
+ *    and moments makes it non-finite (torch.clamp on the actions, torch.tanh, the loss above, tf.train.AdamOptimizer's formula:
+ *    what torch_discriminator_fit of the package computes); a reward and a logit of qsg_reward exactly in the rows in which
+ *    torch's are.  So the clamp and tanh keep a NaN: x[12 + k] = act < -1 ? -1 : act > 1 ? 1 : act, and (a, d) = (NaN, NaN) for
+ *    z = NaN, where q_tanh alone would give (+-1, 0).  (The two accuracies count comparisons, which are false for a NaN: they
+ *    stay finite on both sides.)  NOT COVERED: an infinite logit (an infinite weight of the last layer), where torch's
+ *    binary_cross_entropy_with_logits returns NaN for the class whose softplus is 0.
+ * 2. State.  After a step the discriminator holds a non-finite weight exactly when the arbiter's does.  Adam is held per
+ *    element: w', m', v' are non-finite in exactly the elements in which the formula above is, applied to the step's own
+ *    gradient; where it is finite the bounds of the finite case apply.
+ * 3. No invention.  An infinite action is its clamped copy, bit for bit, in qsg_fit and in qsg_reward; a NaN is never clamped
+ *    away.  (An infinite observation saturates tanh: every statistic stays finite, as it does in the arbiter.)
+ * 4. Unread data.  Rows that no index of a step names, index entries at and beyond counts[s], and every step before the first
+ *    one that reads a non-finite value are bit for bit what they are without it; in qsg_reward every row but the poisoned one.
+ * 5. No faults.  No loaded float becomes an address, an index or a loop bound: no value of any kind makes a call fault or write
+ *    outside its arrays.
+ *
  * ---- limits ---------------------------------------------------------------------------------------------------------
  * 1 <= H <= 128; 1 <= batch <= 256 rows per class, 1 <= counts[s] <= batch, 1 <= steps <= 4096, 1 <= n_gen, n_exp < 2^31, t0 >= 0
  * and t0 + steps < 2^31; entcoeff, lr and eps finite, 0 <= beta1, beta2 < 1.  qsg_reward: 1 <= rows < 2^31, n_envs and n_steps both

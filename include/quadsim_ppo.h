@@ -56,6 +56,24 @@
  * Invariants: the bits of a call are a function of (net, data, indices, slices, hyper-parameters, t0) alone -- not of the stream,
  * not of which compute unit ran which workgroup, not of n; one call with steps = a + b equals the call with steps = a followed
  * by the call with t0 + a, steps = b, bit for bit, statistics included.
+ * NON-FINITE VALUES (NaN, +inf, -inf in a row, a weight or a moment).  A diverged run looks diverged:
+ * 1. Statistics.  A statistic of a step is non-finite exactly when float64 torch autograd of the loss of ppo2.py:147-188 over the
+ *    same rows, weights and moments makes it non-finite -- torch.relu, torch.clamp, torch.maximum, tf.clip_by_global_norm: what
+ *    update="torch" of the package computes.  So every max / min / comparison above is a select that keeps a NaN:
+ *    relu = z <= 0 ? 0 : z;  rc = r < lo ? lo : r > hi ? hi : r;  the row is ACTIVE unless p1 < p2, and its term is p1 then (rc
+ *    and p2 are NaN only where r and p1 are);  a row that is not active has dn = 0 * r, which is +0 unless r is infinite (the
+ *    chain rule through exp, as autograd has it);  a NaN step d = v - old_v gives vc = NaN;  the value row is ACTIVE unless
+ *    l1 < l2 and its term is l1 unless l1 < l2 or l2 alone is NaN;  the clip divides by N < max_grad_norm ? max_grad_norm : N,
+ *    so a NaN norm makes every element of the step NaN.
+ * 2. State.  After a step the policy holds a non-finite weight exactly when the arbiter's does: for the net as a whole, not per
+ *    element (the backward masks stay h > 0 ? acc : 0, which turn a NaN activation's term into 0).  The clip and Adam are held
+ *    per element: w', m', v' are non-finite in exactly the elements in which the formula above is, applied to the step's own
+ *    gradient G; where it is finite the bounds of the finite case apply.
+ * 3. Unread data.  Rows that no index of a step names and every step before the first one that reads a non-finite value are
+ *    bit for bit what they are without it.  (The advantage's mean and deviation run over all rows of a step: one non-finite
+ *    return or value spoils every row of that step.)
+ * 4. No faults.  No loaded float becomes an address, an index or a loop bound: no value of any kind makes a call fault or write
+ *    outside its arrays.
  *
  * ---- limits ---------------------------------------------------------------------------------------------------------
  * 1 <= steps <= 4096, 1 <= batch < 2^31, 1 <= n < 2^31, 0 <= slices <= 1024, t0 >= 0 and t0 + steps < 2^31; every

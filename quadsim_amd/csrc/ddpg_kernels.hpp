@@ -101,7 +101,7 @@ __device__ __forceinline__ void stream_layer(const float *W, const float *Bv, co
     }
     if (RELU) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = fmaxf(acc[r], 0.0f);
+        for (int r = 0; r < 4; ++r) acc[r] = acc[r] <= 0.0f ? 0.0f : acc[r];       // forward_layer's select: a NaN stays
     }
     st4(Z + u * kRP + 4 * rg, acc);
 }
@@ -117,7 +117,17 @@ __device__ __forceinline__ float stream_head(const float *W, const float *Bv, co
     return acc;
 }
 
-__device__ __forceinline__ float clamp_obs(float v, float clip) { return fminf(fmaxf(v, -clip), clip); }
+// q_tanh bounds its exponent with fminf, which drops a NaN operand: tanh(NaN) would be +-1 and a diverged actor would go on as a
+// saturated one.  Here a NaN stays; every other value is q_tanh's, bit for bit
+__device__ __forceinline__ float tanh_keep_nan(float x)
+{
+    float unused;
+    const float a = qs::q_tanh(x, unused);
+    return x != x ? x : a;
+}
+
+// (selects, not fminf(fmaxf()): those would turn a NaN observation into -clip; an infinity is clamped as any other value)
+__device__ __forceinline__ float clamp_obs(float v, float clip) { return v < -clip ? -clip : v > clip ? clip : v; }
 
 template <int B>
 __device__ __forceinline__ void branch(float *lds, const StepArgs &S)
@@ -184,8 +194,7 @@ __device__ __forceinline__ void branch(float *lds, const StepArgs &S)
             stream_layer<true>(at + Flat<1>::w1, at + Flat<1>::b1, lds + L::a1, kH, lds + L::a2);
             __syncthreads();
             if (t < kAct * kRows) {
-                float unused;
-                lds[L::c1 + (kH + (t >> 4)) * kRP + gr] = qs::q_tanh(stream_head<kAct>(at + Flat<1>::w2, at + Flat<1>::b2, lds + L::a2), unused);
+                lds[L::c1 + (kH + (t >> 4)) * kRP + gr] = tanh_keep_nan(stream_head<kAct>(at + Flat<1>::w2, at + Flat<1>::b2, lds + L::a2));
             }
             __syncthreads();
             stream_layer<true>(ct + Flat<0>::w1, ct + Flat<0>::b1, lds + L::c1, kH + kAct, lds + L::a2);
@@ -234,8 +243,7 @@ __device__ __forceinline__ void branch(float *lds, const StepArgs &S)
             forward_layer<false>(lds + L::w3, L::ld3, lds + L::b3, lds + L::a2, kH, kOut, lds + L::y);
             __syncthreads();
             if (t < kAct * kRows) {
-                float unused;
-                const float a = qs::q_tanh(lds[L::y + (t >> 4) * kRP + gr], unused);
+                const float a = tanh_keep_nan(lds[L::y + (t >> 4) * kRP + gr]);
                 lds[L::y + (t >> 4) * kRP + gr] = a;
                 lds[L::c1 + (kH + (t >> 4)) * kRP + gr] = a;
             }

@@ -73,8 +73,10 @@ __device__ __forceinline__ void forward_layer(const float *W, int ld, const floa
             }
         }
         if (RELU) {
+            // (a select, not fmaxf: fmaxf drops a NaN operand, and a diverged row would go on as a row of dead units.  -0 <= 0
+            // holds, so a negative zero becomes +0 as it did)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[r] = fmaxf(acc[r], 0.0f);
+            for (int r = 0; r < 4; ++r) acc[r] = acc[r] <= 0.0f ? 0.0f : acc[r];
         }
         st4(Z + u * kRP + 4 * rg, acc);
     }

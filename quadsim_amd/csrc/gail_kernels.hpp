@@ -39,7 +39,16 @@ constexpr int kMathBlock = 256;
 __device__ __forceinline__ float g_exp(float x) { return expf(x); }
 __device__ __forceinline__ float g_log(float x) { return logf(x); }
 __device__ __forceinline__ float g_log1p(float x) { return log1pf(x); }
-__device__ __forceinline__ float g_clamp1(float a) { return fminf(fmaxf(a, -1.0f), 1.0f); }
+// (selects, not fminf(fmaxf()): those would turn a NaN action into -1; an infinity is clamped as any other value)
+__device__ __forceinline__ float g_clamp1(float a) { return a < -1.0f ? -1.0f : a > 1.0f ? 1.0f : a; }
+// q_tanh bounds its exponent with fminf, which drops a NaN operand: tanh(NaN) would be +-1 with a finite derivative.  Here a NaN
+// stays in both; every other value is q_tanh's, bit for bit
+__device__ __forceinline__ float g_tanh(float x, float &sech2)
+{
+    const float a = qs::q_tanh(x, sech2);
+    sech2 = x != x ? x : sech2;
+    return x != x ? x : a;
+}
 
 // input column c of a row: the normalised observation or the clamped action
 __device__ __forceinline__ float input_value(const float *obs, const float *act, const float *mean, const float *rscale, int64_t row, int c)
@@ -100,7 +109,7 @@ __device__ __forceinline__ void tanh_layer(const float *Wt, int ld, const float 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             float s2;
-            acc[r] = qs::q_tanh(acc[r], s2);
+            acc[r] = g_tanh(acc[r], s2);
             d[r] = s2;
         }
         st4(Za + u * kRP + 4 * rg, acc);
@@ -368,7 +377,7 @@ struct RewardLayout {
 __device__ __forceinline__ f32x4 tanh4(f32x4 v)
 {
     float s;
-    return f32x4{qs::q_tanh(v.x, s), qs::q_tanh(v.y, s), qs::q_tanh(v.z, s), qs::q_tanh(v.w, s)};
+    return f32x4{g_tanh(v.x, s), g_tanh(v.y, s), g_tanh(v.z, s), g_tanh(v.w, s)};
 }
 
 template <int W>
@@ -467,8 +476,8 @@ __global__ __launch_bounds__(kMathBlock) void k_gail_math(int kind, const float 
         const float v = x[i];
         float s2 = 0.0f, r;
         switch (kind) {
-        case 0: r = qs::q_tanh(v, s2); break;
-        case 1: qs::q_tanh(v, s2); r = s2; break;
+        case 0: r = g_tanh(v, s2); break;
+        case 1: g_tanh(v, s2); r = s2; break;
         case 2: r = g_exp(v); break;
         case 3: r = g_log(v); break;
         default: r = g_log1p(v); break;

@@ -167,17 +167,22 @@ __global__ __launch_bounds__(kFitBlock) void k_ppo_grad(GradArgs F)
                 }
                 const float nl = __fmaf_rn(0.5f, q, cnl), dnl = __fsub_rn(nl, lds[L::sc + 2 * kRP + r]);
                 const float ratio = expf(-dnl);
-                const float rc = fminf(fmaxf(ratio, F.lo), F.hi);
+                // (selects that keep a NaN, as torch.clamp and torch.maximum do: fminf(fmaxf()) would clip a NaN ratio to lo, and
+                // p1 >= p2 would then report the finite p2 with a zero gradient.  rc is NaN only where ratio is, so p2 is NaN
+                // only where p1 is, and "not p1 < p2" takes p1 exactly where either is NaN)
+                const float rc = ratio < F.lo ? F.lo : ratio > F.hi ? F.hi : ratio;
                 const float p1 = -__fmul_rn(A, ratio), p2 = -__fmul_rn(A, rc);
-                const bool active = valid && p1 >= p2;
-                const float dn = active ? __fmul_rn(__fmul_rn(A, ratio), F.inv_batch) : 0.0f;
+                const bool first = !(p1 < p2);
+                const bool active = valid && first;
+                // (a clipped-off row's zero is 0 * ratio, as the chain rule through exp has it: +0 unless the ratio is infinite)
+                const float dn = active ? __fmul_rn(__fmul_rn(A, ratio), F.inv_batch) : valid ? __fmul_rn(0.0f, ratio) : 0.0f;
 #pragma unroll
                 for (int j = 0; j < kOut; ++j) {
                     lds[L::y + j * kRP + r] = -__fdiv_rn(__fmul_rn(dn, z[j]), sig[j]);
                     lds[L::dl + j * kRP + r] = __fmaf_rn(-__fmul_rn(z[j], z[j]), dn, dn);
                 }
                 if (valid) {
-                    s0 = p1 >= p2 ? p1 : p2;
+                    s0 = first ? p1 : p2;
                     s1 = __fmul_rn(0.5f, __fmul_rn(dnl, dnl));
                     s2 = fabsf(__fsub_rn(ratio, 1.0f)) > F.clip ? 1.0f : 0.0f;
                 }
@@ -185,14 +190,17 @@ __global__ __launch_bounds__(kFitBlock) void k_ppo_grad(GradArgs F)
                 const float v = lds[L::y + r];
                 const float dv = __fsub_rn(v, val);
                 // (a value inside the range is v itself, not val + (v - val): an unclipped row ties exactly and stays active)
-                const float vc = !F.use_crv ? v : dv > F.crv ? __fadd_rn(val, F.crv) : dv < -F.crv ? __fsub_rn(val, F.crv) : v;
+                // (a NaN step v - val is no value inside the range: the clipped value is NaN, as val + clamp(v - val) is)
+                const float vc = !F.use_crv ? v : dv > F.crv ? __fadd_rn(val, F.crv) : dv < -F.crv ? __fsub_rn(val, F.crv) : dv != dv ? dv : v;
                 const float e1 = __fsub_rn(v, ret), e2 = __fsub_rn(vc, ret);
                 const float l1 = __fmul_rn(e1, e1), l2 = __fmul_rn(e2, e2);
-                const bool active = valid && l1 >= l2;
+                // (the larger loss, NaN where either is: l1 unless l1 < l2 or l2 alone is NaN)
+                const bool first = !(l1 < l2), take1 = first && l2 == l2;
+                const bool active = valid && first;
                 lds[L::y + r] = active ? __fmul_rn(e1, F.vf_scale) : 0.0f;
 #pragma unroll
                 for (int j = 1; j < kOut; ++j) lds[L::y + j * kRP + r] = 0.0f;
-                if (valid) s0 = __fmul_rn(0.5f, l1 >= l2 ? l1 : l2);
+                if (valid) s0 = __fmul_rn(0.5f, take1 ? l1 : l2);
             }
             lds[L::sc + 3 * kRP + r] = s0;
             lds[L::sc + 4 * kRP + r] = s1;
@@ -408,7 +416,8 @@ __global__ __launch_bounds__(kElemBlock) void k_ppo_apply(ParamTable T, ApplyArg
         const int k = slot_of(T, e), j = e - T.start[k];
         float g = F.gflat[e];
         if (F.want_grads) T.grads[k][j] = g;
-        if (F.max_grad_norm > 0.0) g = __fmul_rn(g, (float)(F.max_grad_norm / fmax(norm, F.max_grad_norm)));
+        // (a select, not fmax: a NaN norm scales every element to NaN, as tf.clip_by_global_norm does)
+        if (F.max_grad_norm > 0.0) g = __fmul_rn(g, (float)(F.max_grad_norm / (norm < F.max_grad_norm ? F.max_grad_norm : norm)));
         const Adam A{F.b1f, F.b2f, F.omb1, F.omb2, F.eps, F.lr_t};
         float wl = T.w[k][j];
         adam_step(A, g, &wl, T.w[k], T.m[k], T.v[k], nullptr, j);

@@ -130,7 +130,7 @@ def step64(P, rows, gam=GAMMA, clip=OBS_CLIP, with_bound=False):
     T = actor64(P["actor_target"], x1)
     Q1 = critic64(P["critic_target"], x1, T["a"], T["E_a"])
     k = np.where(done >= 1.0, 0.0, (1.0 - done) * gam)
-    y = rew + k * Q1["q"]
+    y = np.where(done >= 1.0, rew, rew + k * Q1["q"])                           # (a select: a terminal row is rew whatever q1 is, NaN included)
     E_y = np.where(k == 0.0, 0.0, k * (Q1["E_q"] + gamma(3) * (np.abs(Q1["q"]) + Q1["E_q"])) + U32 * np.abs(y) + TINY)
     # 2. the critic
     Cr = critic64(P["critic"], x0, act)

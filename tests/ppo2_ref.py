@@ -119,11 +119,11 @@ def head64(W, batch, hp, Fp, Fv):
     lo, hi = f(np.float32(1.0 - cr)), f(np.float32(1.0 + cr))
     rc = np.clip(r, lo, hi)
     p1, p2 = -A * r, -A * rc
-    active = p1 >= p2
+    active = ~(p1 < p2)                                                   # p1 >= p2, and every NaN row: autograd hands it its NaN
     Ar = A * r
     E_Ar = np.abs(A) * E_r + r * E_A + E_A * E_r
     E_Ar = E_Ar + U32 * (np.abs(Ar) + E_Ar) + TINY
-    g = np.where(active, Ar / B, 0.0)                                     # dL / dneglogp
+    g = np.where(active, Ar / B, 0.0 * r)                                 # dL / dneglogp (0 r: a clipped-off infinite ratio is autograd's NaN)
     E_g = np.where(active, (E_Ar + 3 * U32 * np.abs(Ar)) / B * (1 + 8 * U32) + TINY, 0.0)
     gz = g[:, None] * z
     dmean = -gz / sig
@@ -148,7 +148,7 @@ def head64(W, batch, hp, Fp, Fv):
     crv = hp["cliprange_vf"]
     c = f(np.float32(max(crv, 0.0)))
     dv = v - vold
-    vc = v if crv < 0 else np.where(dv > c, vold + c, np.where(dv < -c, vold - c, v))
+    vc = v if crv < 0 else np.where(dv > c, vold + c, np.where(dv < -c, vold - c, np.where(np.isnan(dv), dv, v)))
     e1, e2 = v - ret, vc - ret
     E_e1 = E_v + U32 * (np.abs(e1) + E_v) + TINY
     E_vc = np.where(vc == v, E_v, U32 * (np.abs(vc) + c))
@@ -158,7 +158,7 @@ def head64(W, batch, hp, Fp, Fv):
     E_l1 = E_l1 + U32 * (l1 + E_l1) + TINY
     E_l2 = 2 * np.abs(e2) * E_e2 + E_e2 ** 2
     E_l2 = E_l2 + U32 * (l2 + E_l2) + TINY
-    vact = l1 >= l2
+    vact = ~(l1 < l2)                                                     # l1 >= l2, and every NaN row
     cB = hp["vf_coef"] / B
     dvv = np.where(vact, e1 * cB, 0.0)
     E_dvv = np.where(vact, abs(cB) * (E_e1 + 2 * U32 * (np.abs(e1) + E_e1)) * (1 + 4 * U32) + TINY, 0.0)
