@@ -318,6 +318,29 @@ int qs_episode_stats(QsEnv *env, int64_t T, int64_t n, const float *rewards, con
                      const uint8_t *last_dones, float *ep_ret, int32_t *ep_len, uint64_t *count, int64_t cap,
                      int64_t *out_key, float *out_ret, int32_t *out_len);
 
+/* NON-FINITE VALUES on the acting paths (NaN, +inf, -inf in a weight, a bias, an observation or state, a nominal control or a
+ * caller's noise sample): qs_policy_forward, qs_policy_rollout, qs_policy_evaluate, qs_runner_rollout (each with its _fast /
+ * _net forms), qs_mppi_plan and qs_mppi_plan_split.  A diverged policy looks diverged:
+ * 1. Networks.  An output of a network evaluation (an action mean, a value) is non-finite exactly where the float64 reference
+ *    over the same weights and observations is (np.maximum(z, 0) and plain sums), and on the exact-f32 paths it is the same
+ *    kind: NaN, +inf or -inf.  So ReLU is a select that keeps a NaN of either sign bit and any payload, relu = z <= 0 ? 0 : z,
+ *    never a max that drops one.  On the split-bf16 paths (_fast) it is non-finite wherever the reference is, but an infinity
+ *    may come out as NaN: hi = inf makes lo = inf - inf.  For the same reason an infinite WEIGHT that the packed image stores
+ *    split may give NaN where the reference stays finite (a unit switched off by -inf).
+ * 2. No leak.  Outputs the reference leaves finite and the poison cannot reach have the bits of the same call without the
+ *    poison: other envs and rows, other action components, the other branch of an actor-critic (a poison in the policy branch
+ *    leaves the values alone, one in the value branch leaves means, actions and neglogp alone).
+ * 3. Hand-over.  The clip and the squash of an action keep a NaN: clip(NaN) = NaN, tanh(NaN) = NaN with a NaN neglogp (the
+ *    sampled pre-squash action was NaN already).  An infinity is clipped or squashed like any other value.  The planners'
+ *    clamp of a candidate is the same select: a NaN in nominal_in or in the caller's noise makes exactly the candidates NaN
+ *    that fma and clamp make NaN; their scores are NaN and weigh nothing.  (The weighted sum still adds 0 * NaN: the element
+ *    of U that a NaN candidate of one iteration touched is NaN from then on, every candidate of the env is NaN in the next
+ *    iteration, and U stays.)  Every other env keeps its bits.
+ * 4. Roll-outs.  At the step where a NaN action is taken the reward is NaN (the shaping holds -0.1 |a|).  An evaluation whose
+ *    policy has a NaN weight that reaches the mean returns NaN for every episode.
+ * Not covered: finite inputs whose float32 evaluation overflows; and what env.step itself makes of a NaN action or state AFTER
+ * that first step -- the rotor limits and the Euler-angle clamps of the step still drop a NaN, which the C oracle does not. */
+
 /* Policy-in-the-loop roll-out in one launch: for t < T:  a_t = clip(MLP(obs_t), -1, 1);  obs_{t+1}, r_t, done_t =
  * env.step(a_t) -- the loop of run_trained_docking_ppo2.py:37-60 for N envs, with the deterministic actor of the
  * shipped PPO2 MlpPolicy (shared_fc0 12->128, pi_fc0 128->128, pi 128->4, ReLU).  Weights are passed TRANSPOSED

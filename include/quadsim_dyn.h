@@ -27,6 +27,15 @@
  * candidate runs.  Hidden widths are zero-padded to multiples of 16 (and up to the compiled widths below); the padding units
  * sit at the END of every k-ordered chain and add fmaf(0, 0, acc): acc itself (the one exception IEEE leaves: an accumulator
  * that is exactly -0 becomes +0).
+ * NON-FINITE VALUES (NaN, +inf, -inf in a weight, a bias, a normaliser or an observation).  A diverged net looks diverged:
+ * 1. Network.  A predicted delta is non-finite exactly where the float64 reference over the same net, observation and actions
+ *    is (np.maximum(z, 0) and plain sums), and it is the same kind: NaN, +inf or -inf.  So ReLU is a select that keeps a NaN
+ *    of either sign bit and any payload, relu = z <= 0 ? 0 : z, never a max that drops one: a net poisoned in w1, b1, w2, b2,
+ *    w3, b3 or a normaliser makes every score NaN, for every env and candidate for which the reference does.
+ * 2. Outcome.  A NaN score never wins; the outcome of an env whose scores are all NaN is the one defined above: winner index 0,
+ *    best_score = scores[0], its NaN bits included.
+ * 3. No leak.  An env whose observation is non-finite leaves every other env's outputs bit for bit.
+ * Not covered: finite inputs whose float32 evaluation overflows.
  *
  * ---- limits ---------------------------------------------------------------------------------------------------------
  * 1 <= horizon <= 1024, 1 <= paths <= 65536, k < 2^36 (the keying), 1 <= n, n * ceil(paths / 16) < 2^31.

@@ -38,6 +38,17 @@
  * the last iteration.  best_score, scores, trace, candidates and traj are nullable, as are nominal_in and noise.
  * Invariants: the bits of candidate c depend on (net, obs, seed, gid, k, it, c, the nominal) only -- not on n, on `paths`, or on
  * where the candidate runs; the first j iterations of a call with more iterations are the call with iterations = j.
+ * NON-FINITE VALUES (NaN, +inf, -inf in the net, a normaliser, an observation, nominal_in or the caller's noise):
+ * 1. Network.  As in quadsim_dyn.h (the same device function): a predicted delta is non-finite exactly where, and of the kind
+ *    that, the float64 reference makes it; ReLU keeps a NaN of either sign bit.  A net poisoned in a weight, a bias or a
+ *    normaliser makes every score NaN, for every env and candidate for which the reference does.
+ * 2. Candidates.  clamp keeps a NaN and clamps an infinity like any other value: a NaN in nominal_in[env][h][j] or in
+ *    noise[it][c][h] makes exactly the candidates NaN that fmaf and clamp make NaN.  Their scores are NaN and their weights 0.
+ *    (The weighted sum still adds 0 * NaN: the element of U that a NaN candidate of one iteration touched is NaN from then on,
+ *    every candidate of the env is NaN in the next iteration, and U stays.)
+ * 3. Outcome.  For an env whose scores are all NaN: U stays, best_score = -inf, as defined above.
+ * 4. No leak.  Every env that reads no non-finite value keeps its bits.
+ * Not covered: finite inputs whose float32 evaluation overflows.
  *
  * ---- limits ---------------------------------------------------------------------------------------------------------
  * 1 <= horizon <= 1024, 1 <= paths <= 65536, 1 <= iterations <= 16, k < 2^33 (the keying), lambda > 0 and finite, sigma >= 0

@@ -52,9 +52,12 @@ __device__ __forceinline__ void plan_action(uint64_t seed, uint64_t gid, uint64_
 // the total order of the reduction: higher score first, then lower index (plan_better of shooting.hpp)
 __device__ __forceinline__ bool plan_better(double s, int i, double bs, int bi) { return s > bs || (s == bs && i < bi); }
 
+// (a select, not fmaxf: fmaxf drops a NaN operand, and a net with a NaN weight would plan on as one with a dead unit.  -0 <= 0
+// holds: -0 still becomes +0)
+__device__ __forceinline__ float relu1(float z) { return z <= 0.0f ? 0.0f : z; }
 __device__ __forceinline__ f32x4 relu4(f32x4 v)
 {
-    return f32x4{fmaxf(v.x, 0.0f), fmaxf(v.y, 0.0f), fmaxf(v.z, 0.0f), fmaxf(v.w, 0.0f)};
+    return f32x4{relu1(v.x), relu1(v.y), relu1(v.z), relu1(v.w)};
 }
 
 constexpr int kDynBlock = 256;       // 4 waves: one per SIMD while the 118 KB image leaves room for one workgroup per CU

@@ -40,9 +40,11 @@ constexpr size_t policy_lds_floats()
     return (size_t)kHid * kLdW + 16 * kLdW + kHid * kLdW1 + kHid + kHid + 16 + 4 * (12 * 64) + 4 * (64 * 4);
 }
 
+// (a select, not fmaxf: fmaxf drops a NaN operand, and a NaN weight would act as a dead unit.  -0 <= 0 holds: -0 still becomes +0)
+__device__ __forceinline__ float relu1(float z) { return z <= 0.0f ? 0.0f : z; }
 __device__ __forceinline__ f32x4 relu4(f32x4 v)
 {
-    return f32x4{fmaxf(v.x, 0.0f), fmaxf(v.y, 0.0f), fmaxf(v.z, 0.0f), fmaxf(v.w, 0.0f)};
+    return f32x4{relu1(v.x), relu1(v.y), relu1(v.z), relu1(v.w)};
 }
 
 // ---- the pieces every actor and actor-critic kernel is built from, each written once ------------------------
@@ -101,7 +103,7 @@ __device__ __forceinline__ void init_a3(const float *B3, int lane, f32x4 (&a3)[4
 }
 
 // Hand-over of the actors: rows 0..3 of the action tile live in lanes 0..15 (g == 0); through sAct [64][4] to the lane that
-// owns the env, clipped to [-1, 1]
+// owns the env, clipped to [-1, 1] (clamp1: a NaN mean stays a NaN action)
 __device__ __forceinline__ void actions_to_owner(const f32x4 (&a3)[4], float *sAct, int lane, float act[4])
 {
     const int c = lane & 15, g = lane >> 4;
@@ -113,7 +115,7 @@ __device__ __forceinline__ void actions_to_owner(const f32x4 (&a3)[4], float *sA
     __builtin_amdgcn_wave_barrier();
     const f32x4 av = *reinterpret_cast<const f32x4 *>(sAct + lane * 4);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) act[i] = fminf(fmaxf(av[i], -1.0f), 1.0f);
+    for (int i = 0; i < 4; ++i) act[i] = clamp1(av[i]);
     __builtin_amdgcn_wave_barrier();
 }
 
@@ -240,16 +242,18 @@ __device__ __forceinline__ void split_bf16(float v, __bf16 &hi, __bf16 &lo)
     lo = (__bf16)(v - (float)hi);
 }
 
-// ReLU + hi/lo split of TWO accumulator values into one packed register each: 7 VALU instructions per pair (integer max
-// against 0 = ReLU without a canonicalising v_max; v_cvt_pk_bf16_f32 rounds both at once; the hi halves are widened back with
-// a shift and a mask; one packed subtract; one more v_cvt_pk) where the value-at-a-time form takes 14.  Same roundings.
+// ReLU + hi/lo split of TWO accumulator values into one packed register each: 9 VALU instructions per pair (a compare and a
+// select per value = ReLU without a canonicalising v_max; v_cvt_pk_bf16_f32 rounds both at once; the hi halves are widened
+// back with a shift and a mask; one packed subtract; one more v_cvt_pk) where the value-at-a-time form takes 14.  Same
+// roundings.  The ReLU is relu1's select: a NaN of either sign bit stays (a signed integer max against 0, one instruction less,
+// turns a NaN whose sign bit is set -- what inf - inf and 0 / 0 give -- into +0); -0 .. -inf become +0.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void relu_split_pair(float v0, float v1, uint32_t &hi, uint32_t &lo)
 {
-    v0 = __builtin_bit_cast(float, max(__builtin_bit_cast(int, v0), 0));
-    v1 = __builtin_bit_cast(float, max(__builtin_bit_cast(int, v1), 0));
+    v0 = relu1(v0);
+    v1 = relu1(v1);
     const f32x2 v = {v0, v1};
     hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
     const f32x2 r = {v0 - __builtin_bit_cast(float, hi << 16), v1 - __builtin_bit_cast(float, hi & 0xffff0000u)};
@@ -354,9 +358,8 @@ __device__ __forceinline__ void mlp_layer2_split(const u32x4 (&bh)[4][4], const 
             hn[et] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(term == 0 ? al[p & 1] : ah[p & 1],
                                                              as_bf16x8(term == 1 ? bl[p][E0 + et] : bh[p][E0 + et]), cin, 0, 0, 0);
             const int pair = m / 6, piece = m % 6, se = pair >> 1, pr = pair & 1;
-            // (the element goes through a float temporary: __builtin_bit_cast applied to a vector-element lvalue reads element 0)
-            if (piece == 0) { const float x = hc[se][2 * pr]; v0[pair] = __builtin_bit_cast(float, max(__builtin_bit_cast(int, x), 0)); }
-            if (piece == 1) { const float x = hc[se][2 * pr + 1]; v1[pair] = __builtin_bit_cast(float, max(__builtin_bit_cast(int, x), 0)); }
+            if (piece == 0) v0[pair] = relu1(hc[se][2 * pr]);
+            if (piece == 1) v1[pair] = relu1(hc[se][2 * pr + 1]);
             if (piece == 2) { const f32x2 v = {v0[pair], v1[pair]}; hu[pair] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2)); }
             if (piece == 3) h0[pair] = __builtin_bit_cast(float, hu[pair] << 16);
             if (piece == 4) h1[pair] = __builtin_bit_cast(float, hu[pair] & 0xffff0000u);

@@ -561,6 +561,15 @@ __device__ __forceinline__ float q_tanh(float x, float &sech2)
     sech2 = 4.0f * (e * r) * r;
     return copysignf(1.0f - 2.0f * r, x);
 }
+// q_tanh bounds its exponent with fminf, which drops a NaN operand: tanh(NaN) would be +-1 with sech2 = 0.  Here a NaN stays in
+// both; every other value is q_tanh's, bit for bit
+__device__ __forceinline__ float q_tanh_nan(float x, float &sech2)
+{
+    float s;
+    const float a = q_tanh(x, s);
+    sech2 = x != x ? x : s;
+    return x != x ? x : a;
+}
 
 // four standard normals for (env gid, step k): Philox block k of the POLICY stream, Box-Muller on (0,1] uniforms,
 // (w.x, w.y) -> n0 = r cos, n1 = r sin; (w.z, w.w) -> n2, n3.  Stands in for tf.random_normal in
@@ -600,7 +609,8 @@ __device__ __forceinline__ uint4 philox_counter(uint64_t seed, uint64_t subseque
     return make_uint4(c0, c1, c2, c3);
 }
 
-__device__ __forceinline__ float clamp1(float x) { return fminf(fmaxf(x, -1.0f), 1.0f); }
+// (selects, not fminf(fmaxf()): those would turn a NaN action into -1; an infinity is clamped as any other value)
+__device__ __forceinline__ float clamp1(float x) { return x < -1.0f ? -1.0f : x > 1.0f ? 1.0f : x; }
 
 // per-env registers
 struct Env {

@@ -114,12 +114,12 @@ __device__ __forceinline__ void sample_action(const RunnerArgs &R, const Mean &m
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float sech2;
-            a[i] = q_tanh(u[i], sech2);                           // policies.py:238
+            a[i] = q_tanh_nan(u[i], sech2);                        // policies.py:238
             nl += q_ln(sech2 + 1e-6f);                            // distributions.py:414, 1 - tanh(u)^2 + 1e-6
         }
     } else {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) a[i] = fminf(fmaxf(u[i], -1.0f), 1.0f);   // ppo2.py:483
+        for (int i = 0; i < 4; ++i) a[i] = clamp1(u[i]);   // ppo2.py:483
     }
 }
 
