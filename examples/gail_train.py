@@ -2,14 +2,16 @@
 """GAIL from the PID expert, all on the device: run_docking_gail.py of the reference for N docking-v1 envs.
 
     python examples/gail_train.py [--envs 256] [--episodes 1] [--expert expert.npz] [--timesteps 1000000] [--n-steps 128]
-                                  [--d-steps 3] [--d-batch 256] [--fit hip|torch] [--save out.npz]
+                                  [--d-steps 3] [--d-batch 256] [--fit hip|torch] [--generator ppo2|trpo] [--save out.npz]
 
 The expert is recorded (record_expert_dataset, K complete episodes per env) or loaded from an .npz with its keys; the policy is a
 fresh SB2 actor-critic of the tower layout (pi = vf = [128, 128], ReLU); ``GAIL.learn`` runs roll-out (scored by the current
 discriminator), PPO2 update and discriminator steps per update and prints PPO2's fields, the five discriminator statistics and
 the mean TRUE episode return; evaluate_policy_episodes runs before and after, beside the expert's own PIDExpert.evaluate.
 --fit torch runs the same loop through the two torch autograd paths (torch_ppo2_update, torch_discriminator_fit): the
-comparison.  The generator is this package's PPO2 (SB2's GAIL wraps TRPO).  Whether the result docks is reported, not asserted."""
+comparison.  --generator ppo2 (the default) is this package's PPO2 under ``GAIL``; --generator trpo is SB2's own choice: ``TRPO`` with
+the expert (max_kl 0.01, 10 CG iterations, lam 0.98, 3 value passes of batch 128, g_step 3, d_step 1; --d-steps, --d-batch and --d-lr
+still apply, the PPO2 options do not).  Whether the result docks is reported, not asserted."""
 import argparse
 import os
 import sys
@@ -64,6 +66,8 @@ def main():
     ap.add_argument("--hidden", type=int, default=100, help="SB2's hidden_size_adversary")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fit", default="hip", choices=("hip", "torch"))
+    ap.add_argument("--generator", default="ppo2", choices=("ppo2", "trpo"), help="what trains the policy: GAIL's PPO2, or TRPO as in SB2")
+    ap.add_argument("--g-step", type=int, default=3, help="--generator trpo: roll-outs and policy steps per discriminator fit")
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("--save", default=None, help="write the trained policy as an .npz ActorCriticPolicy.from_npz reads")
     args = ap.parse_args()
@@ -86,9 +90,13 @@ def main():
     eval_env.reset()
     report("policy before", qa.evaluate_policy_episodes(policy, eval_env, 1))
 
-    model = qa.GAIL(policy, env, data, discriminator=disc, d_steps=args.d_steps, d_batch=args.d_batch, d_learning_rate=args.d_lr,
-                    update=args.fit, n_steps=args.n_steps, nminibatches=args.nminibatches, noptepochs=args.noptepochs, ent_coef=args.ent_coef,
-                    learning_rate=args.lr, seed=args.seed)
+    if args.generator == "trpo":
+        model = qa.TRPO(policy, env, n_steps=args.n_steps, expert_data=data, discriminator=disc, g_step=args.g_step, d_step=args.d_steps,
+                        d_batch=args.d_batch, d_stepsize=args.d_lr, update=args.fit, entcoeff=args.ent_coef, seed=args.seed)
+    else:
+        model = qa.GAIL(policy, env, data, discriminator=disc, d_steps=args.d_steps, d_batch=args.d_batch, d_learning_rate=args.d_lr,
+                        update=args.fit, n_steps=args.n_steps, nminibatches=args.nminibatches, noptepochs=args.noptepochs,
+                        ent_coef=args.ent_coef, learning_rate=args.lr, seed=args.seed)
 
     def callback(loc, glob):
         log = loc["logs"][-1] if loc["logs"] and loc["logs"][-1]["n_updates"] == loc["update"] else None
@@ -103,8 +111,12 @@ def main():
     logs = model.learn(args.timesteps, callback=callback)
     torch.cuda.synchronize()
     sec = time.perf_counter() - t0
+    per = args.g_step if args.generator == "trpo" else 1
+    if args.generator == "trpo" and logs:
+        print("--generator trpo: last policy step accepted candidate %d after %d CG iterations, kl %.5f" % (
+            logs[-1]["accepted"], logs[-1]["cg_iters_run"], logs[-1]["kl_after"]))
     print("--fit %s: %d updates of %d x %d steps in %.2f s wall (%.0f env steps / s, host included)"
-          % (args.fit, len(logs), args.envs, args.n_steps, sec, len(logs) * args.envs * args.n_steps / max(sec, 1e-9)))
+          % (args.fit, len(logs), per * args.envs, args.n_steps, sec, len(logs) * per * args.envs * args.n_steps / max(sec, 1e-9)))
     eval_env.reset()
     res = qa.evaluate_policy_episodes(policy, eval_env, 1)
     report("policy after", res)

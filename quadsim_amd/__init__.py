@@ -20,6 +20,8 @@ from .sb2 import load_sb2_model, read_sb2_weights
 from .bc import ExpertData, bc_fit, bc_loss, check_bc_args, epoch_schedule, pretrain
 from .ppo2 import PPO2, check_ppo2_args, minibatch_schedule, ppo2_update, reset_ppo2_optimizer, torch_ppo2_update
 from .gail import GAIL, Discriminator, GailRunner, check_gail_args, discriminator_schedule, torch_discriminator_fit
+from .trpo import (TRPO, check_trpo_args, reset_trpo_optimizer, torch_trpo_policy_step, torch_trpo_vf_fit, trpo_policy_step, trpo_vf_fit,
+                   vf_schedule)
 from .ddpg import DDPG, DDPGPolicy, OUNoise, ReplayBuffer, check_ddpg_args, ddpg_update, replay_schedule, torch_ddpg_update
 
 __all__ = ["VecDockingEnv", "DockingEnv", "MovingDockingEnv", "ImitatingDockingEnv", "HoveringEnv", "Drone", "controller", "make", "register_gym_ids",
@@ -30,6 +32,8 @@ __all__ = ["VecDockingEnv", "DockingEnv", "MovingDockingEnv", "ImitatingDockingE
            "ExpertData", "epoch_schedule", "pretrain", "bc_fit", "bc_loss", "check_bc_args",
            "PPO2", "ppo2_update", "torch_ppo2_update", "minibatch_schedule", "check_ppo2_args", "reset_ppo2_optimizer",
            "GAIL", "Discriminator", "GailRunner", "discriminator_schedule", "torch_discriminator_fit", "check_gail_args",
-           "DDPG", "DDPGPolicy", "ReplayBuffer", "OUNoise", "replay_schedule", "ddpg_update", "torch_ddpg_update", "check_ddpg_args"]
+           "DDPG", "DDPGPolicy", "ReplayBuffer", "OUNoise", "replay_schedule", "ddpg_update", "torch_ddpg_update", "check_ddpg_args",
+           "TRPO", "check_trpo_args", "vf_schedule", "trpo_policy_step", "trpo_vf_fit", "reset_trpo_optimizer", "torch_trpo_policy_step",
+           "torch_trpo_vf_fit"]
 
 register_gym_ids()

@@ -1,6 +1,7 @@
-"""ctypes binding of libquadsim_hip.so (the C ABI declared in include/quadsim.h), and the tables (SIDE, TRAIN, IMITATE, OFFPOLICY),
-build, loader and call helper of the four side libraries that dynplan.py and bc.py wrap, of the training library that ppo2.py wraps,
-of the imitation library that gail.py wraps and of the off-policy library that ddpg.py wraps.
+"""ctypes binding of libquadsim_hip.so (the C ABI declared in include/quadsim.h), and the tables (SIDE, TRAIN, IMITATE, TRUST,
+OFFPOLICY), build, loader and call helper of the four side libraries that dynplan.py and bc.py wrap, of the training library that
+ppo2.py wraps, of the imitation library that gail.py wraps, of the trust-region library that trpo.py wraps and of the off-policy
+library that ddpg.py wraps.
 
 There is deliberately no fallback of any kind: if the HIP library is missing or
 no MI355X is visible, loading / qs_create raise.  Nothing here imports oracle/.
@@ -16,7 +17,7 @@ LIB_PATH = os.environ.get("QUADSIM_HIP_LIB") or os.path.join(CSRC, "libquadsim_h
 SOURCES = [os.path.join(CSRC, "quadsim_hip.hip")]
 # every fragment of the one translation unit is a rebuild dependency, bar those of the side libraries (SIDE below)
 HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith(
-    ("dynplan_", "dynmppi_", "dynfit_", "bcfit_", "ppo2_", "gail_", "ddpg_", "side_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
+    ("dynplan_", "dynmppi_", "dynfit_", "bcfit_", "ppo2_", "gail_", "ddpg_", "trpo_", "side_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
 
 QS_OK = 0
 KIND_V0, KIND_V2, KIND_V1, KIND_HOVER = 0, 1, 2, 3
@@ -171,6 +172,25 @@ class QspHyper(C.Structure):
         (k, C.c_double) for k in ("lr", "cliprange", "cliprange_vf", "ent_coef", "vf_coef", "max_grad_norm", "beta1", "beta2", "eps")]
 
 
+class QstNet(C.Structure):                     # include/quadsim_trpo.h
+    _fields_ = [("struct_size", C.c_uint32), ("layout", C.c_int32), ("w", C.c_void_p * 13), ("m", C.c_void_p * 13), ("v", C.c_void_p * 13)]
+
+
+class QstBatch(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("n", C.c_int64)] + [
+        (k, C.c_void_p) for k in ("obs", "actions", "returns", "values")]
+
+
+class QstHyper(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("cg_iters", C.c_int32), ("backtracks", C.c_int32), ("fvp_stride", C.c_int32)] + [
+        (k, C.c_double) for k in ("max_kl", "cg_damping", "entcoeff", "residual_tol")]
+
+
+class QstTrace(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("fvp_in", "fvp_out", "cg", "x", "fullstep", "ls")]
+
+
 class QsddNets(C.Structure):                   # include/quadsim_ddpg.h
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("w", C.c_void_p * 24), ("m", C.c_void_p * 12), ("v", C.c_void_p * 12)]
 
@@ -255,7 +275,21 @@ IMITATE = {
                      "qsg_reward": [C.POINTER(QsgNet), vp, vp, i64, i64, i64, vp, vp, i32, vp],
                      "qsg_math": [i32, vp, vp, i64, vp]}),
 }
-# The libraries that train off-policy from a replay, a fourth table of the same format.
+# The libraries that take trust-region steps, a table of the same format (the fifth to be added, the fourth in TABLES).
+TRUST = {
+    # the TRPO update (trpo.py): the policy's own tensors; the forward chain and the Adam step of "dynfit"
+    "trpo": dict(env="QUADSIM_TRPO_LIB", file="libquadsim_trpo.so", source="trpo.hip", header="quadsim_trpo.h", prefix="qst_",
+                 fragments=("trpo_kernels.hpp", "dynfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp"),
+                 signatures={
+                     "qst_version": [],
+                     "qst_last_error": ([], C.c_char_p),
+                     "qst_auto_slices": [i64],
+                     "qst_workspace_bytes": [i64, i32, psize],
+                     "qst_policy_step": [C.POINTER(QstNet), C.POINTER(QstBatch), i32, C.POINTER(QstHyper), vp, u64, vp, vp,
+                                         C.POINTER(QstTrace), vp],
+                     "qst_vf_fit": [C.POINTER(QstNet), vp, vp, i64, vp, i32, i32, f64, f64, f64, f64, i64, vp, psix, vp]}),
+}
+# The libraries that train off-policy from a replay, a table of the same format.
 OFFPOLICY = {
     # the DDPG update (ddpg.py): the four nets' own tensors; the forward chain and the Adam step of "dynfit", q_tanh of the main library
     "ddpg": dict(env="QUADSIM_DDPG_LIB", file="libquadsim_ddpg.so", source="ddpg.hip", header="quadsim_ddpg.h", prefix="qsdd_",
@@ -267,11 +301,11 @@ OFFPOLICY = {
                      "qsdd_update": [C.POINTER(QsddNets), C.POINTER(QsddReplay), vp, vp, i32, i32, C.POINTER(QsddHyper), i64, vp, u64, vp,
                                      C.POINTER(vp * 12), vp]}),
 }
-TABLES = (SIDE, TRAIN, IMITATE, OFFPOLICY)
+TABLES = (SIDE, TRAIN, IMITATE, TRUST, OFFPOLICY)
 
 
 def _entry(key):
-    """the entry `key` of SIDE, of TRAIN, of IMITATE or of OFFPOLICY"""
+    """the entry `key` of SIDE, of TRAIN, of IMITATE, of TRUST or of OFFPOLICY"""
     return next(t[key] for t in TABLES if key in t)
 
 
@@ -291,6 +325,7 @@ SIDE_POINTERS = {name: tuple(i for i, t in enumerate(sig[0] if isinstance(sig, t
 DYN_LIB_PATH, DYNMPPI_LIB_PATH, DYNFIT_LIB_PATH, BC_LIB_PATH = (SIDE[k]["path"] for k in ("dyn", "dynmppi", "dynfit", "bc"))
 PPO_LIB_PATH = TRAIN["ppo"]["path"]
 GAIL_LIB_PATH = IMITATE["gail"]["path"]
+TRPO_LIB_PATH = TRUST["trpo"]["path"]
 DDPG_LIB_PATH = OFFPOLICY["ddpg"]["path"]
 
 
@@ -328,7 +363,7 @@ def build_one_library(sources, deps, out, link=(), force=False, verbose=False):
 
 
 def build_library(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all eight libraries, returns the main one's
+    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all nine libraries, returns the main one's
     path."""
     for e in _entries():
         build_one_library(e["sources"], e["headers"], e["path"], (), force, verbose)
@@ -409,7 +444,7 @@ _side = {}
 
 
 def side_load(key):
-    """dlopen the side library `key` of SIDE, TRAIN or IMITATE, once; raises QuadsimError if it has not been built (there is no fallback)"""
+    """dlopen the side library `key` of any table of TABLES, once; raises QuadsimError if it has not been built (there is no fallback)"""
     lib = _side.get(key)
     if lib is None:
         e = _entry(key)

@@ -8,7 +8,8 @@ the exact-float32 matrix pipe (``qsg_reward``), writing the step-major array ``g
 fused Runner with that reward between the roll-out and GAE; ``GAIL`` is the loop.
 
 Decisions, where SB2 leaves a choice or we depart from it:
-  * the generator is this package's PPO2.  SB2's GAIL wraps TRPO, which is not built here.
+  * the generator of ``GAIL`` is this package's PPO2.  SB2's GAIL wraps TRPO: ``quadsim_amd.trpo.TRPO(..., expert_data=...)`` is that
+    loop over the same ``GailRunner`` and ``Discriminator`` (towers layout, one GPU; the shared layout and multi-GPU are not built).
   * generator and expert actions pass the same clamp to [-1, 1]: the Runner stores the unclipped sample u and the env received
     clip(u); on expert rows the clamp is a no-op.
   * the running observation statistics (SB2's RunningMeanStd, float64, kept here in Python) take ONE merge per ``fit`` call, over
