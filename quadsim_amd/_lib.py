@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("QUADSIM_HIP_LIB") or os.path.join(CSRC, "libquadsim_h
 SOURCES = [os.path.join(CSRC, "quadsim_hip.hip")]
 # every fragment of the one translation unit is a rebuild dependency, bar those of the side libraries (SIDE below)
 HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith(
-    ("dynplan_", "dynmppi_", "dynfit_", "bcfit_", "ppo2_", "gail_", "ddpg_", "trpo_", "side_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
+    ("dynplan_", "dynmppi_", "dynfit_", "bcfit_", "ppo2_", "gail_", "ddpg_", "trpo_", "train_", "side_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
 
 QS_OK = 0
 KIND_V0, KIND_V2, KIND_V1, KIND_HOVER = 0, 1, 2, 3
@@ -207,7 +207,7 @@ class QsddHyper(C.Structure):
 
 f64, psize, psix = C.c_double, C.POINTER(C.c_size_t), C.POINTER(vp * 6)
 # The four libraries beside the main one, each its own translation unit, .so and code object, by short name.  They share at the
-# source level only: device fragments (*_kernels.hpp, dynplan_image.hpp, quadsim_device.hpp) and the host fragments side_host.hpp
+# source level only: device fragments (*_kernels.hpp, dynplan_image.hpp, train_pieces.hpp, quadsim_device.hpp) and the host fragments side_host.hpp
 # (all four) and dynplan_host.hpp (the two planners).  An entry: the variable that overrides the path (A/B builds) and the file
 # name, the source, the fragments it is rebuilt for, the public header, and the signatures of its entry points in the header's
 # order -- argument types or, where the result is not int, (argument types, result type).  Everything else is derived: the paths,
@@ -232,16 +232,17 @@ SIDE = {
                         "qsdm_last_error": ([], C.c_char_p),
                         "qsdm_workspace_bytes": [i64, i32, i32, psize],
                         "qsdm_mppi_plan": [vp, i32, i32, i64, vp, u64, u64, u64, i32, i32, i32, f32, f32, i32] + [vp] * 11}),
-    # the Adam fit of the learned net (dynplan.py): takes the net's own tensors, not the image; only the Philox generator is shared
+    # the Adam fit of the learned net (dynplan.py): takes the net's own tensors, not the image; the chunk primitives of
+    # train_pieces.hpp, the Philox generator of the main library
     "dynfit": dict(env="QUADSIM_DYNFIT_LIB", file="libquadsim_dynfit.so", source="dynfit.hip", header="quadsim_dyn_fit.h", prefix="qsdf_",
-                   fragments=("dynfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp"),
+                   fragments=("dynfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
                    signatures={
                        "qsdf_version": [],
                        "qsdf_last_error": ([], C.c_char_p),
                        "qsdf_fit": [C.POINTER(QsdfNet), vp, vp, i64, i64, i32, i32, f64, f64, f64, f64, i64, u64, u64, vp, vp, vp, psix, vp]}),
-    # behaviour cloning of the actor (bc.py): takes the policy's own tensors; the forward chain and the Adam step of "dynfit"
+    # behaviour cloning of the actor (bc.py): takes the policy's own tensors; the tower pieces of train_pieces.hpp
     "bc": dict(env="QUADSIM_BC_LIB", file="libquadsim_bc.so", source="bcfit.hip", header="quadsim_bc.h", prefix="qsbc_",
-               fragments=("bcfit_kernels.hpp", "dynfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp"),
+               fragments=("bcfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
                signatures={
                    "qsbc_version": [],
                    "qsbc_last_error": ([], C.c_char_p),
@@ -252,9 +253,9 @@ SIDE = {
 # The libraries that train a policy, entries of the same format in a table of their own: every helper below looks a key up in
 # both tables (_entry).
 TRAIN = {
-    # the PPO2 update (ppo2.py): takes the policy's own tensors; the forward chain and the Adam step of "dynfit"
+    # the PPO2 update (ppo2.py): takes the policy's own tensors; the tower pieces of train_pieces.hpp
     "ppo": dict(env="QUADSIM_PPO_LIB", file="libquadsim_ppo.so", source="ppo2.hip", header="quadsim_ppo.h", prefix="qsp_",
-                fragments=("ppo2_kernels.hpp", "dynfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp"),
+                fragments=("ppo2_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
                 signatures={
                     "qsp_version": [],
                     "qsp_last_error": ([], C.c_char_p),
@@ -265,9 +266,9 @@ TRAIN = {
 }
 # The libraries that imitate an expert adversarially, a third table of the same format.
 IMITATE = {
-    # GAIL's discriminator (gail.py): its own tensors; the Adam step and the chunk geometry of "dynfit", q_tanh of the main library
+    # GAIL's discriminator (gail.py): its own tensors; the Adam step and the chunk geometry of train_pieces.hpp, q_tanh of the main library
     "gail": dict(env="QUADSIM_GAIL_LIB", file="libquadsim_gail.so", source="gail.hip", header="quadsim_gail.h", prefix="qsg_",
-                 fragments=("gail_kernels.hpp", "dynfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp"),
+                 fragments=("gail_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
                  signatures={
                      "qsg_version": [],
                      "qsg_last_error": ([], C.c_char_p),
@@ -277,9 +278,9 @@ IMITATE = {
 }
 # The libraries that take trust-region steps, a table of the same format (the fifth to be added, the fourth in TABLES).
 TRUST = {
-    # the TRPO update (trpo.py): the policy's own tensors; the forward chain and the Adam step of "dynfit"
+    # the TRPO update (trpo.py): the policy's own tensors; the tower pieces of train_pieces.hpp
     "trpo": dict(env="QUADSIM_TRPO_LIB", file="libquadsim_trpo.so", source="trpo.hip", header="quadsim_trpo.h", prefix="qst_",
-                 fragments=("trpo_kernels.hpp", "dynfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp"),
+                 fragments=("trpo_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
                  signatures={
                      "qst_version": [],
                      "qst_last_error": ([], C.c_char_p),
@@ -291,9 +292,9 @@ TRUST = {
 }
 # The libraries that train off-policy from a replay, a table of the same format.
 OFFPOLICY = {
-    # the DDPG update (ddpg.py): the four nets' own tensors; the forward chain and the Adam step of "dynfit", q_tanh of the main library
+    # the DDPG update (ddpg.py): the four nets' own tensors; the tower pieces of train_pieces.hpp, q_tanh of the main library
     "ddpg": dict(env="QUADSIM_DDPG_LIB", file="libquadsim_ddpg.so", source="ddpg.hip", header="quadsim_ddpg.h", prefix="qsdd_",
-                 fragments=("ddpg_kernels.hpp", "dynfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp"),
+                 fragments=("ddpg_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
                  signatures={
                      "qsdd_version": [],
                      "qsdd_last_error": ([], C.c_char_p),

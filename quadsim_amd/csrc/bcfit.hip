@@ -1,6 +1,6 @@
 // bcfit.hip -- libquadsim_bc.so: the C ABI of include/quadsim_bc.h over the kernels of bcfit_kernels.hpp.  ONE translation unit
-// of its own: nothing here is part of the other four libraries.  Shared at the source level only: dynfit_kernels.hpp with the
-// fourth (the forward chain and the Adam step), none of whose kernels is instantiated here, and side_host.hpp with all the side
+// of its own: nothing here is part of the other four libraries.  Shared at the source level only: train_pieces.hpp with the
+// other trainers (the forward chain, the backward pass and the Adam step) and side_host.hpp with all the side
 // libraries (error text, the Adam and pointer checks and the fill of the args the two fits have in common).
 #include "../../include/quadsim_bc.h"
 #include "side_host.hpp"

@@ -1,6 +1,6 @@
 // ddpg.hip -- libquadsim_ddpg.so: the C ABI of include/quadsim_ddpg.h over the kernels of ddpg_kernels.hpp.  ONE translation unit
-// of its own: nothing here is part of the other seven libraries.  Shared at the source level only: dynfit_kernels.hpp (the forward
-// chain and the Adam step), none of whose kernels is instantiated here, quadsim_device.hpp (q_tanh) and side_host.hpp (error
+// of its own: nothing here is part of the other seven libraries.  Shared at the source level only: train_pieces.hpp (the forward
+// chain, the backward pass and the Adam step), quadsim_device.hpp (q_tanh) and side_host.hpp (error
 // text, the Adam and pointer checks).
 #include "../../include/quadsim_ddpg.h"
 #include "side_host.hpp"

@@ -1,10 +1,10 @@
 // ddpg_kernels.hpp -- the kernels of libquadsim_ddpg.so (include/quadsim_ddpg.h has the numerical contract).  A fragment of
-// ddpg.hip, nowhere else.  Shared with the fit libraries at the source level: forward_layer, adam_step, ld4 / st4 and the chunk
-// geometry (kFitBlock, kRows, kRP) of dynfit_kernels.hpp, and q_tanh of quadsim_device.hpp; none of their kernels is instantiated.
+// ddpg.hip, nowhere else.  Built from train_pieces.hpp: the chunk primitives and the tower pieces (the LDS image and its loader,
+// the element map, backward_chunk); q_tanh is quadsim_device.hpp's.
 //
 // One train step is ONE launch, and the kernel boundary is the only ordering across workgroups:
 //   k_ddpg_step  grid (2).  Workgroup 0 is the critic branch: the online critic 12 -> 128 -> (128 + 4 actions) -> 128 -> 1 in LDS
-//                in k_ppo_grad's transposed image, layer 1 widened to 132 inputs and the head run as four outputs of which three
+//                in the tower's transposed image, layer 1 widened to 132 inputs and the head run as four outputs of which three
 //                have zero weights (they add exact zeros).  Per 16-row chunk it computes y with the two TARGET nets, which it
 //                reads forward-only from memory (stream_layer: lanes along the units, so a weight row is one coalesced read and
 //                the activation an LDS broadcast), then runs the critic forward and backward, gradients in registers, rows
@@ -17,22 +17,13 @@
 // of a call reads buffer s & 1 and writes buffer (s + 1) & 1.  Moments and gradients have one copy: only their branch touches
 // them.  Nothing waits on another workgroup, there is no grid barrier and no float atomic.
 #pragma once
-#include "dynfit_kernels.hpp"
+#include "train_pieces.hpp"
 
 namespace qsdd {
 
-using qsf::Adam;
-using qsf::adam_step;
-using qsf::f32x4;
-using qsf::forward_layer;
-using qsf::kFitBlock;
-using qsf::kRG;
-using qsf::kRows;
-using qsf::kRP;
-using qsf::ld4;
-using qsf::st4;
+using namespace qsf;
 
-constexpr int kIn = 12, kInP = 16, kH = 128, kAct = 4, kOut = 4;
+constexpr int kAct = 4;
 constexpr int kCopyBlock = 256, kCopyTensors = 60;            // 24 weights, 24 moments, 12 gradients
 
 // a net as it lies flat in the workspace, tensors in the ABI's order and the policy's (in, out) layout.  B = 0: the critic (layer
@@ -42,6 +33,7 @@ struct Flat {
     static constexpr int k1 = B ? kH : kH + kAct, outs = B ? kAct : 1;
     static constexpr int w0 = 0, b0 = w0 + kIn * kH, w1 = b0 + kH, b1 = w1 + k1 * kH, w2 = b1 + kH, b2 = w2 + kH * outs;
     static constexpr int floats = (b2 + outs + 3) & ~3;
+    static constexpr int at(int k) { return k == 0 ? w0 : k == 1 ? b0 : k == 2 ? w1 : k == 3 ? b1 : k == 4 ? w2 : b2; }   // slot k's start
 };
 constexpr int net_at(int b) { return b ? 0 : Flat<1>::floats; }                     // in a buffer: actor | critic | the two targets
 constexpr int kOnline = Flat<0>::floats + Flat<1>::floats, kBuf = 2 * kOnline;     // a target lies kOnline after its online net
@@ -65,19 +57,17 @@ struct CopyArgs {
     int to_ws;
 };
 
+// the tower's image with a1 132 units high in either branch; the critic's rows of w2 are 140 apart (132 and 140: 4 and 12 mod 32
+// words)
 template <int B>
-struct Layout {
-    using F = Flat<B>;
-    static constexpr int ld1 = kInP + 4, ld2 = B ? kH + 4 : kH + kAct + 8, ld3 = kH + 4;     // 132 and 140: 4 and 12 mod 32 words
-    static constexpr int w1 = 0, b1 = w1 + kH * ld1, w2 = b1 + kH, b2 = w2 + kH * ld2, w3 = b2 + kH, b3 = w3 + kOut * ld3;
-    static constexpr int x = b3 + 16, a1 = x + kInP * kRP, a2 = a1 + (kH + kAct) * kRP, y = a2 + kH * kRP;
-    static constexpr int d2 = y + kOut * kRP, d1 = d2 + kH * kRP;
+struct Layout : TowerImage<B ? kH + 4 : kH + kAct + 8, kH + kAct> {
+    using T = TowerImage<B ? kH + 4 : kH + kAct + 8, kH + kAct>;
+    static constexpr int d2 = T::planes, d1 = d2 + kH * kRP;
     static constexpr int c1 = d1 + kH * kRP;     // the streamed critic's layer-1 input: h0 | action
     static constexpr int sc = c1 + (kH + kAct) * kRP;    // per row: reward, done, y, q, q - y | q(pi)
     static constexpr int floats = sc + 5 * kRP;
 };
 constexpr int kLdsFloats = Layout<0>::floats > Layout<1>::floats ? Layout<0>::floats : Layout<1>::floats;
-constexpr int kStatT = 448;                      // the thread that adds a branch's statistics
 
 // Z[u][r] = B[u] + sum_k W[k][u] A[k][r], k ascending: forward_layer's chain with the weights read from memory in the policy's
 // (in, out) layout.  One item = one unit x four rows, unit along the lanes; K is a multiple of 4
@@ -135,37 +125,24 @@ __device__ __forceinline__ void branch(float *lds, const StepArgs &S)
     using L = Layout<B>;
     using F = Flat<B>;
     static_assert(L::floats * 4 <= 160 * 1024, "LDS");
-    static_assert(kFitBlock == 512 && kRows == 16 && kH == 128, "the thread maps below");
     const int t = threadIdx.x;
     const float *cur = S.ws + S.cur * kBuf;
     float *nxt = S.ws + (S.cur ^ 1) * kBuf;
     const float *net = cur + net_at(B);
 
-    // ---- the online net into LDS: zero everything (the padding stays zero), then the weights, transposed
-    for (int i = t; i < L::floats; i += kFitBlock) lds[i] = 0.0f;
-    __syncthreads();
-    for (int i = t; i < kIn * kH; i += kFitBlock) lds[L::w1 + (i & (kH - 1)) * L::ld1 + (i >> 7)] = net[F::w0 + i];
-    for (int i = t; i < F::k1 * kH; i += kFitBlock) lds[L::w2 + (i & (kH - 1)) * L::ld2 + (i >> 7)] = net[F::w1 + i];
-    for (int i = t; i < kH * F::outs; i += kFitBlock) lds[L::w3 + (i % F::outs) * L::ld3 + i / F::outs] = net[F::w2 + i];
-    if (t < kH) { lds[L::b1 + t] = net[F::b0 + t]; lds[L::b2 + t] = net[F::b1 + t]; }
-    if (t < F::outs) lds[L::b3 + t] = net[F::b2 + t];
+    // ---- the online net into LDS (the chunk loop opens with the barrier)
+    load_image<L, F::k1>(lds, L::floats, F::outs, [&](int k, int i) { return net[F::at(k) + i]; });
 
     int rows = S.counts ? S.counts[0] : S.batch;
     rows = rows < S.batch ? rows : S.batch;
     const float dscale = (float)(2.0 / (double)rows), ninv = -(float)(1.0 / (double)rows), frows = (float)rows;
 
-    // ---- the elements of this thread, in the policy's (in, out) layout (k_bc_fit's map; the critic's four action rows of w1
-    // are one element a thread more)
-    const int ti = t & 31, to = t >> 5;                  // w1: inputs 8 to + a, outputs ti + 32 j
-    const int o1 = t & 127, ig1 = t >> 7;                // w0: output o1, inputs 4 ig1 + a (ig1 == 3: the zero padding); w1: input 128 + ig1
-    const int o3 = t & 3, i3 = t >> 2;                   // w2: input i3, output o3
-    const bool own1 = ig1 < 3, own3 = o3 < F::outs;
-    const int bk = t < 128 ? 0 : t < 256 ? 1 : t < 256 + F::outs ? 2 : -1, bu = t & 127;
-    float g2[8][4], g1[4] = {}, g3 = 0.0f, gb = 0.0f, gx = 0.0f;
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) g2[a][j] = 0.0f;
+    // ---- the gradient elements of this thread; the critic's four action rows of w1 are one element a thread more: input
+    // 128 + ig1, output o1
+    const int o1 = t & 127, ig1 = t >> 7;
+    Acc G;
+    zero_acc(G);
+    float gx = 0.0f;
     float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;               // thread kStatT: the sums of the rows so far
 
     for (int r0 = 0; r0 < rows; r0 += kRows) {
@@ -275,114 +252,16 @@ __device__ __forceinline__ void branch(float *lds, const StepArgs &S)
             __syncthreads();
         }
 
-        // ---- phase A: the gradient of the head from (dy, a1), dz1 from (w2, dy) under a1's mask
+        backward_chunk<L>(lds, G, [&] {
+            if (B == 0) {
 #pragma clang loop unroll(disable)
-        for (int rg = 0; rg < kRG; ++rg) {
-            const f32x4 a = ld4(lds + L::a2 + i3 * kRP + 4 * rg), d = ld4(lds + L::y + o3 * kRP + 4 * rg);
+                for (int rg = 0; rg < kRG; ++rg) {
+                    const f32x4 dz = ld4(lds + L::d2 + o1 * kRP + 4 * rg), av = ld4(lds + L::a1 + (kH + ig1) * kRP + 4 * rg);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) g3 = __fmaf_rn(d[r], a[r], g3);
-        }
-        if (bk == 2) {
-#pragma unroll
-            for (int r = 0; r < kRows; ++r) gb = __fadd_rn(gb, lds[L::y + bu * kRP + r]);
-        }
-        if (t < (kH >> 2) * kRG) {
-            const int ig = t >> 2, rg = t & 3;
-            f32x4 acc[4] = {};
-#pragma unroll
-            for (int o = 0; o < kOut; ++o) {
-                const f32x4 wo = ld4(lds + L::w3 + o * L::ld3 + 4 * ig), dz = ld4(lds + L::y + o * kRP + 4 * rg);
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[a][r] = __fmaf_rn(wo[a], dz[r], acc[a][r]);
-            }
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const f32x4 hv = ld4(lds + L::a2 + (4 * ig + a) * kRP + 4 * rg);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[a][r] = hv[r] > 0.0f ? acc[a][r] : 0.0f;
-                st4(lds + L::d2 + (4 * ig + a) * kRP + 4 * rg, acc[a]);
-            }
-        }
-        __syncthreads();
-        // ---- phase B: the gradient of layer 1 from (dz1, a0 | act), dz0 from (w1, dz1) under a0's mask
-#pragma clang loop unroll(disable)
-        for (int rg = 0; rg < kRG; ++rg) {
-            f32x4 dz[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dz[j] = ld4(lds + L::d2 + (ti + 32 * j) * kRP + 4 * rg);
-#pragma unroll
-            for (int a = 0; a < 8; ++a) {
-                const f32x4 av = ld4(lds + L::a1 + (8 * to + a) * kRP + 4 * rg);
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) g2[a][j] = __fmaf_rn(dz[j][r], av[r], g2[a][j]);
-            }
-        }
-        if (B == 0) {
-#pragma clang loop unroll(disable)
-            for (int rg = 0; rg < kRG; ++rg) {
-                const f32x4 dz = ld4(lds + L::d2 + o1 * kRP + 4 * rg), av = ld4(lds + L::a1 + (kH + ig1) * kRP + 4 * rg);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) gx = __fmaf_rn(dz[r], av[r], gx);
-            }
-        }
-        if (bk == 1) {
-#pragma unroll
-            for (int r = 0; r < kRows; ++r) gb = __fadd_rn(gb, lds[L::d2 + bu * kRP + r]);
-        }
-        {
-            // four inputs x four rows an item, its 128-term sum over four lanes: chain q takes o = q, q + 4, ...
-            const int lane = t & 63, wv = t >> 6;
-            const int q = lane >> 4, ig = (lane & 15) + 16 * (wv & 1), rg = wv >> 1;
-            f32x4 acc[4] = {};
-            const float *wp = lds + L::w2 + 4 * ig, *d = lds + L::d2 + 4 * rg;
-            for (int o = q; o < kH; o += 4) {
-                const f32x4 wo = ld4(wp + o * L::ld2), dz = ld4(d + o * kRP);
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[a][r] = __fmaf_rn(wo[a], dz[r], acc[a][r]);
-            }
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float s = acc[a][r];
-                    s = __fadd_rn(s, __shfl_xor(s, 16));          // S0 + S1 | S2 + S3
-                    s = __fadd_rn(s, __shfl_xor(s, 32));          // (S0 + S1) + (S2 + S3)
-                    acc[a][r] = s;
-                }
-            if (q == 0) {
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    const f32x4 hv = ld4(lds + L::a1 + (4 * ig + a) * kRP + 4 * rg);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[a][r] = hv[r] > 0.0f ? acc[a][r] : 0.0f;
-                    st4(lds + L::d1 + (4 * ig + a) * kRP + 4 * rg, acc[a]);
+                    for (int r = 0; r < 4; ++r) gx = __fmaf_rn(dz[r], av[r], gx);
                 }
             }
-        }
-        __syncthreads();
-        // ---- phase C: the gradient of layer 0 from (dz0, obs)
-        if (own1) {
-#pragma clang loop unroll(disable)
-            for (int rg = 0; rg < kRG; ++rg) {
-                const f32x4 dz = ld4(lds + L::d1 + o1 * kRP + 4 * rg);
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    const f32x4 xv = ld4(lds + L::x + (4 * ig1 + a) * kRP + 4 * rg);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) g1[a] = __fmaf_rn(dz[r], xv[r], g1[a]);
-                }
-            }
-        }
-        if (bk == 0) {
-#pragma unroll
-            for (int r = 0; r < kRows; ++r) gb = __fadd_rn(gb, lds[L::d1 + bu * kRP + r]);
-        }
+        });
     }
 
     // ---- Adam on the thread's own elements (m and v through memory, the weight from LDS into the next buffer), then the
@@ -396,17 +275,8 @@ __device__ __forceinline__ void branch(float *lds, const StepArgs &S)
         adam_step(A, g, lw, wn, m, v, gout, e);
         tn[e] = __fmaf_rn(S.tau, *lw, __fmul_rn(S.omt, tc[e]));
     };
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) apply(g2[a][j], lds + L::w2 + (ti + 32 * j) * L::ld2 + 8 * to + a, F::w1 + (8 * to + a) * kH + ti + 32 * j);
+    for_own<L, F::outs>(t, [&](int off, int idx, int slot, const float &g) { apply(g, lds + off, F::at(slot) + idx); }, G);
     if (B == 0) apply(gx, lds + L::w2 + o1 * L::ld2 + kH + ig1, F::w1 + (kH + ig1) * kH + o1);
-    if (own1) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) apply(g1[a], lds + L::w1 + o1 * L::ld1 + 4 * ig1 + a, F::w0 + (4 * ig1 + a) * kH + o1);
-    }
-    if (own3) apply(g3, lds + L::w3 + o3 * L::ld3 + i3, F::w2 + i3 * F::outs + o3);
-    if (bk >= 0) apply(gb, lds + (bk == 0 ? L::b1 : bk == 1 ? L::b2 : L::b3) + bu, (bk == 0 ? F::b0 : bk == 1 ? F::b1 : F::b2) + bu);
     if (t == kStatT) {
         if (B == 0) {
             S.stats[0] = __fdiv_rn(s0, frows);

@@ -1,6 +1,6 @@
 // dynfit.hip -- libquadsim_dynfit.so: the C ABI of include/quadsim_dyn_fit.h over the kernel of dynfit_kernels.hpp.  ONE
 // translation unit of its own: nothing here is part of the other libraries.  Shared with them at the source level only:
-// quadsim_device.hpp (the Philox generator of the batch draws) and side_host.hpp (error text, the width rule, the Adam and
+// train_pieces.hpp (the chunk primitives), quadsim_device.hpp (the Philox generator of the batch draws) and side_host.hpp (error text, the width rule, the Adam and
 // pointer checks and the fill of the args the two fits have in common).
 #include "../../include/quadsim_dyn_fit.h"
 #include "side_host.hpp"

@@ -1,29 +1,18 @@
 // dynfit_kernels.hpp -- the one kernel of qsdf_fit (include/quadsim_dyn_fit.h has the numerical contract).  A fragment of
-// dynfit.hip, nowhere else.
+// dynfit.hip, nowhere else.  The chunk primitives it is built from (forward_layer, backward_layer, adam_step, the chunk geometry
+// and the LDS orientation they assume) are train_pieces.hpp's.
 //
 // k_dyn_fit<P1, P2>: ONE workgroup of 512 threads runs every Adam step of the call.  The weights of the net live in LDS for the
-// whole call in torch's (out, in) orientation, rows LD = in + 4 floats apart (a ds_read_b128 per lane fetches four k of one
-// unit; LD = 4 mod 16 words puts 16 units on 16 different bank quads).  The batch is processed in chunks of kRows = 16 rows:
-// the chunk's activations are staged in LDS unit-major, A[unit][row], rows kRP = 20 floats apart, so that one ds_read_b128
-// fetches four ROWS of one unit -- the B operand of a forward tile (1 unit x 4 rows), of a back-propagation tile (4 units x 4
-// rows) and of a gradient tile alike.  Every thread owns a fixed set of gradient elements and keeps them in registers across
-// the chunks of a step (W2: 8 x ceil(P1 / 32), W1: 8, W3: 3, one of each bias), adding rows in ascending order; after the last
-// chunk it applies Adam to exactly those elements, streaming m and v through L2 and writing the weight to LDS and to memory.
-// dz2 overwrites h2 and dz1 overwrites h1 in place once the gradient that needed the activation has been taken.  All ordering
-// is __syncthreads; there is no second workgroup to wait for.
-// Every product here is a plain fmaf chain: the forward must be the planners' k-ascending chain from the bias and the gradient
-// sums row-ascending chains, which plain FMAs give as written.  MFMA gradient tiles (rows as the k dimension) were not built.
+// whole call, the batch is processed in chunks of kRows = 16 rows.  Every thread owns a fixed set of gradient elements and keeps
+// them in registers across the chunks of a step (W2: 8 x ceil(P1 / 32), W1: 8, W3: 3, one of each bias), adding rows in ascending
+// order; after the last chunk it applies Adam to exactly those elements, streaming m and v through L2 and writing the weight to
+// LDS and to memory.  dz2 overwrites h2 and dz1 overwrites h1 in place once the gradient that needed the activation has been
+// taken.  All ordering is __syncthreads; there is no second workgroup to wait for.
 #pragma once
-#include "quadsim_device.hpp"
+#include "train_pieces.hpp"
 
 namespace qsf {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kFitBlock = 512;
-constexpr int kRows = 16;                        // batch rows of a chunk
-constexpr int kRG = kRows / 4;                   // groups of four rows
-constexpr int kRP = 20;                          // floats between two units of a staged activation
 constexpr uint64_t kStreamFit = 6;               // the Philox stream of the batch draws (quadsim_device.hpp uses 0 .. 5)
 
 struct FitArgs {
@@ -49,81 +38,6 @@ struct FitLayout {
     static constexpr int scal = norm + 56;       // lr_t
     static constexpr int floats = scal + 4;
 };
-
-__device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
-__device__ __forceinline__ void st4(float *p, f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
-
-// Z[u][r] = B[u] + sum_k W[u][k] A[k][r], k ascending, for u < U and the chunk's 16 rows; K4 = K rounded up to 4 (the padding
-// is zero on both sides and adds nothing).  One item = one unit x four rows.
-template <bool RELU>
-__device__ __forceinline__ void forward_layer(const float *W, int ld, const float *B, const float *A, int K4, int U, float *Z)
-{
-    for (int item = threadIdx.x; item < U * kRG; item += kFitBlock) {
-        const int u = item >> 2, rg = item & 3;
-        const float b = B[u];
-        f32x4 acc = {b, b, b, b};
-        const float *w = W + u * ld, *a = A + 4 * rg;
-        for (int k = 0; k < K4; k += 4) {
-            const f32x4 wk = ld4(w + k);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const f32x4 ak = ld4(a + (k + i) * kRP);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[r] = __fmaf_rn(wk[i], ak[r], acc[r]);
-            }
-        }
-        if (RELU) {
-            // (a select, not fmaxf: fmaxf drops a NaN operand, and a diverged row would go on as a row of dead units.  -0 <= 0
-            // holds, so a negative zero becomes +0 as it did)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[r] = acc[r] <= 0.0f ? 0.0f : acc[r];
-        }
-        st4(Z + u * kRP + 4 * rg, acc);
-    }
-}
-
-// H[i][r] <- (H[i][r] > 0) ? sum_o W[o][i] D[o][r], o ascending from 0 : 0, for i < I4 (a multiple of 4).  One item = four
-// units x four rows; the item reads and writes its own 16 elements of H only.
-__device__ __forceinline__ void backward_layer(const float *W, int ld, const float *D, int O, int I4, float *H)
-{
-    for (int item = threadIdx.x; item < (I4 >> 2) * kRG; item += kFitBlock) {
-        const int ig = item >> 2, rg = item & 3;
-        f32x4 acc[4] = {};
-        const float *w = W + 4 * ig, *d = D + 4 * rg;
-        for (int o = 0; o < O; ++o) {
-            const f32x4 wo = ld4(w + o * ld), dz = ld4(d + o * kRP);
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[a][r] = __fmaf_rn(wo[a], dz[r], acc[a][r]);
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            float *h = H + (4 * ig + a) * kRP + 4 * rg;
-            const f32x4 hv = ld4(h);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[a][r] = hv[r] > 0.0f ? acc[a][r] : 0.0f;
-            st4(h, acc[a]);
-        }
-    }
-}
-
-struct Adam {
-    float b1, b2, omb1, omb2, eps, lr_t;
-};
-
-// one element: the operation order of the header, every operation rounded once
-__device__ __forceinline__ void adam_step(const Adam &A, float g, float *lds_w, float *w, float *m, float *v, float *grad, int idx)
-{
-    const float mn = __fmaf_rn(A.b1, m[idx], __fmul_rn(A.omb1, g));
-    const float vn = __fmaf_rn(A.b2, v[idx], __fmul_rn(A.omb2, __fmul_rn(g, g)));
-    const float wn = __fsub_rn(*lds_w, __fdiv_rn(__fmul_rn(A.lr_t, mn), __fadd_rn(__fsqrt_rn(vn), A.eps)));
-    m[idx] = mn;
-    v[idx] = vn;
-    w[idx] = wn;
-    *lds_w = wn;
-    if (grad) grad[idx] = g;
-}
 
 template <int P1, int P2>
 __global__ __launch_bounds__(kFitBlock) void k_dyn_fit(FitArgs F)

@@ -1,6 +1,6 @@
 // gail.hip -- libquadsim_gail.so: the C ABI of include/quadsim_gail.h over the kernels of gail_kernels.hpp.  ONE translation unit
-// of its own: nothing here is part of the other six libraries.  Shared at the source level only: dynfit_kernels.hpp (the Adam
-// step and the chunk geometry; none of its kernels is instantiated here), quadsim_device.hpp (q_tanh) and side_host.hpp (error
+// of its own: nothing here is part of the other six libraries.  Shared at the source level only: train_pieces.hpp (the Adam
+// step and the chunk geometry), quadsim_device.hpp (q_tanh) and side_host.hpp (error
 // text, the Adam and pointer checks, the fill of the args the fits have in common, the compute-unit count).
 #include "../../include/quadsim_gail.h"
 #include "side_host.hpp"

@@ -1,6 +1,6 @@
 // gail_kernels.hpp -- the kernels of libquadsim_gail.so (include/quadsim_gail.h has the numerical contract).  A fragment of
 // gail.hip, nowhere else.  Shared at the source level: adam_step, ld4 / st4 and the chunk geometry (kFitBlock, kRows, kRP) of
-// dynfit_kernels.hpp, q_tanh of quadsim_device.hpp.
+// train_pieces.hpp, q_tanh of quadsim_device.hpp.
 //
 // k_gail_fit<W>: ONE workgroup of 512 threads runs every Adam step of the call on the discriminator 16 -> H -> H -> 1, H <= W.
 // It has the shape of k_dyn_fit: the weights in LDS for the whole call in (out, in) orientation, rows LD = in + 4 floats apart,
@@ -16,7 +16,7 @@
 // the B operand of layer-1 k-step i being register i; an accumulator tile holds units 16 t + 4 g + i in register i, which is the
 // B operand of the next layer as it stands against weights in their natural (out, in) order: no permutation anywhere.
 #pragma once
-#include "dynfit_kernels.hpp"
+#include "train_pieces.hpp"
 
 namespace qsg {
 

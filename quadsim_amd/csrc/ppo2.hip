@@ -1,6 +1,6 @@
 // ppo2.hip -- libquadsim_ppo.so: the C ABI of include/quadsim_ppo.h over the kernels of ppo2_kernels.hpp.  ONE translation unit
-// of its own: nothing here is part of the other five libraries.  Shared at the source level only: dynfit_kernels.hpp (the forward
-// chain and the Adam step), none of whose kernels is instantiated here, and side_host.hpp (error text, the Adam and pointer checks).
+// of its own: nothing here is part of the other five libraries.  Shared at the source level only: train_pieces.hpp (the forward
+// chain, the backward pass and the Adam step), and side_host.hpp (error text, the Adam and pointer checks).
 #include "../../include/quadsim_ppo.h"
 #include "side_host.hpp"
 #include "ppo2_kernels.hpp"

@@ -1,6 +1,10 @@
 // ppo2_kernels.hpp -- the kernels of libquadsim_ppo.so (include/quadsim_ppo.h has the numerical contract).  A fragment of
-// ppo2.hip, nowhere else.  Shared with the fit libraries at the source level: forward_layer, adam_step, ld4 / st4 and the chunk
-// geometry (kFitBlock, kRows, kRP) of dynfit_kernels.hpp; none of its kernels is instantiated.
+// ppo2.hip, nowhere else.  From train_pieces.hpp: the chunk primitives, the tower's dimensions and LDS image, the flat tower,
+// block_sum and the advantage statistics.  k_ppo_grad keeps its own text of the loader, the head constants, the element map and
+// the three phases of the backward pass (train_pieces.hpp's load_image, head_consts, for_own and backward_chunk, line for line):
+// written with those pieces it computes the same bits, but the compiler assigns the chunk loop other registers and the kernel
+// measured 1 .. 2 % slower wherever that loop is all there is (profiles/train_pieces/README.md).  A change to a piece has to be
+// made here as well.
 //
 // One Adam step is three launches, and the kernel boundary is the only ordering across workgroups:
 //   k_ppo_grad   grid (slices, 2): workgroup (g, b) holds branch b (0 policy, 1 value) of the net in LDS -- 12 -> 128 -> 128 ->
@@ -14,27 +18,15 @@
 // k_ppo_adv_stats runs once per call: one workgroup per step, the mean and 1 / (std + 1e-8) of returns - values.
 // The value head is run as four outputs of which three have zero weights and a zero dv: they add exact zeros.
 #pragma once
-#include "dynfit_kernels.hpp"
+#include "train_pieces.hpp"
 
 namespace qsp {
 
-using qsf::Adam;
-using qsf::adam_step;
-using qsf::f32x4;
-using qsf::forward_layer;
-using qsf::kFitBlock;
-using qsf::kRG;
-using qsf::kRows;
-using qsf::kRP;
-using qsf::ld4;
-using qsf::st4;
+using namespace qsf;
 
-constexpr int kIn = 12, kInP = 16, kH = 128, kOut = 4;
 constexpr int kTensors = 13, kElemBlock = 256, kAdvBlock = 256;
-// a branch's partial gradient: w_l0 | b_l0 | w_l1 | b_l1 | w_l2 (the value head at stride 4) | b_l2 | logstd
-constexpr int kLW0 = 0, kLB0 = kLW0 + kIn * kH, kLW1 = kLB0 + kH, kLB1 = kLW1 + kH * kH, kLW2 = kLB1 + kH, kLB2 = kLW2 + kH * kOut,
-              kLLS = kLB2 + kOut, kPart = kLLS + kOut;
-constexpr int kStatT = 448, kLsT = 264;          // the threads that add the statistics and the logstd gradient of a chunk
+// a branch's partial gradient is the flat tower of train_pieces.hpp (the value head at stride 4)
+constexpr int kLW0 = kW0, kLB0 = kB0, kLW1 = kW1, kLB1 = kB1, kLW2 = kW2, kLB2 = kB2, kLLS = kLS, kPart = kP;
 
 struct GradArgs {
     const float *w[2][6];                        // the six tensors of either branch
@@ -64,10 +56,8 @@ struct ApplyArgs {
     int total, nblk, slices, want_grads;
 };
 
-struct Layout {
-    static constexpr int ld1 = kInP + 4, ld2 = kH + 4, ld3 = kH + 4;
-    static constexpr int w1 = 0, b1 = w1 + kH * ld1, w2 = b1 + kH, b2 = w2 + kH * ld2, w3 = b2 + kH, b3 = w3 + kOut * ld3;
-    static constexpr int x = b3 + 16, a1 = x + kInP * kRP, a2 = a1 + kH * kRP, y = a2 + kH * kRP, act = y + kOut * kRP;
+struct Layout : TowerImage<> {
+    static constexpr int act = planes;
     static constexpr int sc = act + kOut * kRP;  // per row: returns, values, old neglogp, and the three terms of the statistics
     static constexpr int dl = sc + 6 * kRP;      // per row: the four terms of the logstd gradient
     static constexpr int d2 = dl + kOut * kRP, d1 = d2 + kH * kRP;
@@ -78,7 +68,6 @@ __global__ __launch_bounds__(kFitBlock) void k_ppo_grad(GradArgs F)
 {
     using L = Layout;
     static_assert(L::floats * 4 <= 160 * 1024, "LDS");
-    static_assert(kFitBlock == 512 && kRows == 16 && kH == 128, "the thread maps below");
     __shared__ __align__(16) float lds[L::floats];
     const int t = threadIdx.x, g = blockIdx.x, b = blockIdx.y;
     const int64_t chunks = ((int64_t)F.batch + kRows - 1) / kRows;
@@ -108,8 +97,8 @@ __global__ __launch_bounds__(kFitBlock) void k_ppo_grad(GradArgs F)
         double s = 0.0;
 #pragma unroll
         for (int j = 0; j < kOut; ++j) { const float ls = F.logstd[j]; sig[j] = expf(ls); s += (double)ls; }
-        cnl = (float)(2.0 * 1.8378770664093453 + s);                  // 2 log(2 pi) + sum logstd
-        ent = (float)(s + 2.0 * 2.8378770664093453);                  // sum logstd + 2 log(2 pi e)
+        cnl = (float)(2.0 * kLog2Pi + s);                  // 2 log(2 pi) + sum logstd
+        ent = (float)(s + 2.0 * kLog2PiE);                  // sum logstd + 2 log(2 pi e)
     }
     const float amean = F.adv[0], arstd = F.adv[1];
 
@@ -340,41 +329,14 @@ __global__ __launch_bounds__(kFitBlock) void k_ppo_grad(GradArgs F)
     }
 }
 
-// the sum of the 256 values of a workgroup in a fixed binary tree -> every thread
-__device__ __forceinline__ double block_sum(double *p, double x)
-{
-    const int t = threadIdx.x;
-    __syncthreads();
-    p[t] = x;
-    __syncthreads();
-    for (int h = kElemBlock >> 1; h > 0; h >>= 1) {
-        if (t < h) p[t] += p[t + h];
-        __syncthreads();
-    }
-    return p[0];
-}
-
 // one workgroup per step: float32(mean) and float32(1 / (std + 1e-8)) of d = returns - values over the step's rows
 __global__ __launch_bounds__(kAdvBlock) void k_ppo_adv_stats(const float *ret, const float *val, const int32_t *indices, int batch, float *adv)
 {
-    static_assert(kAdvBlock == kElemBlock, "block_sum");
     __shared__ double p[kAdvBlock];
-    const int t = threadIdx.x;
     const int32_t *row = indices + (int64_t)blockIdx.x * batch;
-    double s = 0.0;
-    for (int64_t i = t; i < batch; i += kAdvBlock) { const int64_t idx = row[i]; s += (double)__fsub_rn(ret[idx], val[idx]); }
-    const double mean = block_sum(p, s) / (double)batch;
-    s = 0.0;
-    for (int64_t i = t; i < batch; i += kAdvBlock) {
-        const int64_t idx = row[i];
-        const double d = (double)__fsub_rn(ret[idx], val[idx]) - mean;
-        s += d * d;
-    }
-    const double var = block_sum(p, s) / (double)batch;
-    if (t == 0) {
-        adv[2 * blockIdx.x] = (float)mean;
-        adv[2 * blockIdx.x + 1] = (float)(1.0 / (sqrt(var) + 1.0e-8));
-    }
+    double mean, var;
+    adv_moments<kAdvBlock>(p, batch, [&](int64_t i) { const int64_t idx = row[i]; return __fsub_rn(ret[idx], val[idx]); }, &mean, &var);
+    if (threadIdx.x == 0) store_adv(adv + 2 * blockIdx.x, mean, var);
 }
 
 __device__ __forceinline__ int slot_of(const ParamTable &T, int e)
@@ -402,7 +364,7 @@ __global__ __launch_bounds__(kElemBlock) void k_ppo_reduce(ParamTable T, const f
         gflat[e] = G;
         sq = (double)G * (double)G;
     }
-    sq = block_sum(p, sq);
+    sq = block_sum<kElemBlock>(p, sq);
     if (threadIdx.x == 0) ssq[blockIdx.x] = sq;
 }
 

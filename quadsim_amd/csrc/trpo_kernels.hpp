@@ -1,10 +1,13 @@
 // trpo_kernels.hpp -- the kernels of libquadsim_trpo.so (include/quadsim_trpo.h has the numerical contract).  A fragment of
-// trpo.hip, nowhere else.  Shared with the fit libraries at the source level: forward_layer, adam_step, ld4 / st4 and the chunk
-// geometry (kFitBlock, kRows, kRP) of dynfit_kernels.hpp; none of its kernels is instantiated.
+// trpo.hip, nowhere else.  Built from train_pieces.hpp: the chunk primitives and the tower pieces (the LDS image and its loader,
+// the flat tower, backward_chunk, block_sum, the advantage statistics, the Gaussian head).  k_trpo_vf_fit keeps its own text of
+// the loader and of the register-resident moments (train_pieces.hpp's load_image, load_moments, step_moments and store_state
+// at a head one unit wide): written with those pieces it computes the same bits but spills 13 scalar registers where this text
+// spills 9 (profiles/train_pieces/README.md).  A change to those pieces has to be made here as well.
 //
 // A policy step is a fixed sequence of launches, and the kernel boundary is the only ordering across workgroups:
 //   k_trpo_prep      one workgroup: the advantage's mean and 1 / (std + 1e-8), theta flattened into the workspace, the flags.
-//   k_trpo_grad      grid slices: the policy tower in LDS, the 16-row chunks of a slice: forward, head, backward (k_ppo_grad's);
+//   k_trpo_grad      grid slices: the policy tower in LDS, the 16-row chunks of a slice: forward, head, backward_chunk;
 //                    keeps the old means and neglogp, writes the slice's partial gradient and its sum of advantages.
 //   k_trpo_reduce    grid over the P elements: the partials of an element in float64, slices ascending, rounded once; for a
 //                    Fisher-vector product plus 2 v on logstd and the damping.
@@ -18,29 +21,16 @@
 //   k_trpo_ls_decide one workgroup: the candidate's statistics, the test, and on acceptance theta_k into the policy's tensors.
 // Flags are written by one-workgroup kernels only and read at the entry of LATER launches: iterations after convergence,
 // candidates after acceptance and everything after a skip return at once.
-// k_trpo_vf_fit: ONE workgroup runs every Adam step of the value fit, k_bc_fit's scheme with a head one unit wide.
+// k_trpo_vf_fit: ONE workgroup runs every Adam step of the value fit, k_bc_fit's scheme with a plain head one unit wide, in its own text.
 #pragma once
-#include "dynfit_kernels.hpp"
+#include "train_pieces.hpp"
 
 namespace qst {
 
-using qsf::Adam;
-using qsf::adam_step;
-using qsf::f32x4;
-using qsf::forward_layer;
-using qsf::kFitBlock;
-using qsf::kRG;
-using qsf::kRows;
-using qsf::kRP;
-using qsf::ld4;
-using qsf::st4;
+using namespace qsf;
 
-constexpr int kIn = 12, kInP = 16, kH = 128, kOut = 4;
-// theta, a partial gradient and every vector of the solver: w0 | b0 | w1 | b1 | w2 | b2 | logstd
-constexpr int kW0 = 0, kB0 = kW0 + kIn * kH, kW1 = kB0 + kH, kB1 = kW1 + kH * kH, kW2 = kB1 + kH, kB2 = kW2 + kH * kOut, kLS = kB2 + kOut,
-              kP = kLS + kOut;
+// theta, a partial gradient and every vector of the solver are flat towers (kW0 .. kLS, kP of train_pieces.hpp)
 constexpr int kVecBlock = 256, kBlocks = (kP + kVecBlock - 1) / kVecBlock, kDotBatch = 8;
-constexpr int kStatT = 448, kLsT = 264;          // the threads that add the statistics and the logstd gradient of a chunk
 constexpr int kPolicySlots = 7;
 constexpr int kFlagSkip = 0, kFlagCgDone = 1, kFlagAccepted = 2, kFlagIters = 3;
 constexpr int kScRdotr = 0, kScSurrBefore = 1;
@@ -64,10 +54,8 @@ struct Rows {
     int n, slices, cps;                          // chunks per slice of the pass
 };
 
-struct Layout {
-    static constexpr int ld1 = kInP + 4, ld2 = kH + 4, ld3 = kH + 4;
-    static constexpr int w1 = 0, b1 = w1 + kH * ld1, w2 = b1 + kH, b2 = w2 + kH * ld2, w3 = b2 + kH, b3 = w3 + kOut * ld3;
-    static constexpr int x = b3 + 16, a1 = x + kInP * kRP, a2 = a1 + kH * kRP, y = a2 + kH * kRP, act = y + kOut * kRP;
+struct Layout : TowerImage<> {
+    static constexpr int act = planes;
     static constexpr int sc = act + kOut * kRP;  // per row: returns, values, old neglogp, and the row's terms of the statistics
     static constexpr int dl = sc + 6 * kRP;      // per row: the four terms of the logstd gradient (the line search: the old means)
     static constexpr int d2 = dl + kOut * kRP, d1 = d2 + kH * kRP;
@@ -75,12 +63,6 @@ struct Layout {
     static constexpr int floats = t1 + kH * kRP;
 };
 static_assert(Layout::floats * 4 <= 160 * 1024, "LDS");
-static_assert(kFitBlock == 512 && kRows == 16 && kH == 128, "the thread maps below");
-
-__device__ __forceinline__ int slot_start(int k)
-{
-    return k == 0 ? kW0 : k == 1 ? kB0 : k == 2 ? kW1 : k == 3 ? kB1 : k == 4 ? kW2 : k == 5 ? kB2 : k == 6 ? kLS : kP;
-}
 
 // element e of theta_old + fullstep 2^-k (fs == nullptr: of theta)
 __device__ __forceinline__ float theta_at(const float *theta, const float *fs, float scale, int e)
@@ -88,18 +70,10 @@ __device__ __forceinline__ float theta_at(const float *theta, const float *fs, f
     return fs ? __fadd_rn(theta[e], __fmul_rn(fs[e], scale)) : theta[e];
 }
 
-// the tower into LDS: zero everything (the padding stays zero), then the weights, transposed
+// the tower into LDS, and a barrier
 __device__ __forceinline__ void load_tower(float *lds, const float *theta, const float *fs, float scale)
 {
-    using L = Layout;
-    const int t = threadIdx.x;
-    for (int i = t; i < L::floats; i += kFitBlock) lds[i] = 0.0f;
-    __syncthreads();
-    for (int i = t; i < kIn * kH; i += kFitBlock) lds[L::w1 + (i & (kH - 1)) * L::ld1 + (i >> 7)] = theta_at(theta, fs, scale, kW0 + i);
-    for (int i = t; i < kH * kH; i += kFitBlock) lds[L::w2 + (i & (kH - 1)) * L::ld2 + (i >> 7)] = theta_at(theta, fs, scale, kW1 + i);
-    for (int i = t; i < kH * kOut; i += kFitBlock) lds[L::w3 + (i & (kOut - 1)) * L::ld3 + (i >> 2)] = theta_at(theta, fs, scale, kW2 + i);
-    if (t < kH) { lds[L::b1 + t] = theta_at(theta, fs, scale, kB0 + t); lds[L::b2 + t] = theta_at(theta, fs, scale, kB1 + t); }
-    if (t < kOut) lds[L::b3 + t] = theta_at(theta, fs, scale, kB2 + t);
+    load_image<Layout>(lds, Layout::floats, kOut, [&](int k, int i) { return theta_at(theta, fs, scale, slot_start(k) + i); });
     __syncthreads();
 }
 
@@ -111,177 +85,6 @@ __device__ __forceinline__ bool slice_rows(int64_t rows, int cps, int g, int64_t
     *begin = c0 * kRows;
     *end = min(c1 * kRows, rows);
     return c0 < c1;
-}
-
-// the gradient elements of a thread, in the policy's (in, out) layout (k_bc_fit's map)
-struct Acc {
-    float g2[8][4], g1[4], g3, gb;
-};
-
-__device__ __forceinline__ void zero_acc(Acc &G)
-{
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) G.g2[a][j] = 0.0f;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) G.g1[a] = 0.0f;
-    G.g3 = 0.0f;
-    G.gb = 0.0f;
-}
-
-// k_ppo_grad's three phases from dy in the plane y: the gradients of the chunk's rows into G, dz1 and dz0 under the masks of a2, a1
-__device__ __forceinline__ void backward_chunk(float *lds, Acc &G)
-{
-    using L = Layout;
-    const int t = threadIdx.x;
-    const int ti = t & 31, to = t >> 5;                  // w1: inputs 8 to + a, outputs ti + 32 j
-    const int o1 = t & 127, ig1 = t >> 7;                // w0: output o1, inputs 4 ig1 + a (ig1 == 3: the zero padding)
-    const int o3 = t & 3, i3 = t >> 2;                   // w2: input i3, output o3
-    const int bk = t < 128 ? 0 : t < 256 ? 1 : t < 260 ? 2 : -1, bu = t & 127;
-    // -- phase A: the gradient of the head from (dy, a1), dz1 from (w2, dy) under a1's mask
-#pragma clang loop unroll(disable)
-    for (int rg = 0; rg < kRG; ++rg) {
-        const f32x4 a = ld4(lds + L::a2 + i3 * kRP + 4 * rg), d = ld4(lds + L::y + o3 * kRP + 4 * rg);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) G.g3 = __fmaf_rn(d[r], a[r], G.g3);
-    }
-    if (bk == 2) {
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) G.gb = __fadd_rn(G.gb, lds[L::y + bu * kRP + r]);
-    }
-    if (t < (kH >> 2) * kRG) {
-        const int ig = t >> 2, rg = t & 3;
-        f32x4 acc[4] = {};
-#pragma unroll
-        for (int o = 0; o < kOut; ++o) {
-            const f32x4 wo = ld4(lds + L::w3 + o * L::ld3 + 4 * ig), dz = ld4(lds + L::y + o * kRP + 4 * rg);
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[a][r] = __fmaf_rn(wo[a], dz[r], acc[a][r]);
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const f32x4 hv = ld4(lds + L::a2 + (4 * ig + a) * kRP + 4 * rg);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[a][r] = hv[r] > 0.0f ? acc[a][r] : 0.0f;
-            st4(lds + L::d2 + (4 * ig + a) * kRP + 4 * rg, acc[a]);
-        }
-    }
-    __syncthreads();
-    // -- phase B: the gradient of layer 1 from (dz1, a0), dz0 from (w1, dz1) under a0's mask
-#pragma clang loop unroll(disable)
-    for (int rg = 0; rg < kRG; ++rg) {
-        f32x4 dz[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dz[j] = ld4(lds + L::d2 + (ti + 32 * j) * kRP + 4 * rg);
-#pragma unroll
-        for (int a = 0; a < 8; ++a) {
-            const f32x4 av = ld4(lds + L::a1 + (8 * to + a) * kRP + 4 * rg);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) G.g2[a][j] = __fmaf_rn(dz[j][r], av[r], G.g2[a][j]);
-        }
-    }
-    if (bk == 1) {
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) G.gb = __fadd_rn(G.gb, lds[L::d2 + bu * kRP + r]);
-    }
-    {
-        // four inputs x four rows an item, its 128-term sum over four lanes: chain q takes o = q, q + 4, ...
-        const int lane = t & 63, wv = t >> 6;
-        const int q = lane >> 4, ig = (lane & 15) + 16 * (wv & 1), rg = wv >> 1;
-        f32x4 acc[4] = {};
-        const float *wp = lds + L::w2 + 4 * ig, *d = lds + L::d2 + 4 * rg;
-        for (int o = q; o < kH; o += 4) {
-            const f32x4 wo = ld4(wp + o * L::ld2), dz = ld4(d + o * kRP);
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[a][r] = __fmaf_rn(wo[a], dz[r], acc[a][r]);
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float s = acc[a][r];
-                s = __fadd_rn(s, __shfl_xor(s, 16));          // S0 + S1 | S2 + S3
-                s = __fadd_rn(s, __shfl_xor(s, 32));          // (S0 + S1) + (S2 + S3)
-                acc[a][r] = s;
-            }
-        if (q == 0) {
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const f32x4 hv = ld4(lds + L::a1 + (4 * ig + a) * kRP + 4 * rg);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[a][r] = hv[r] > 0.0f ? acc[a][r] : 0.0f;
-                st4(lds + L::d1 + (4 * ig + a) * kRP + 4 * rg, acc[a]);
-            }
-        }
-    }
-    __syncthreads();
-    // -- phase C: the gradient of layer 0 from (dz0, obs)
-    if (ig1 < 3) {
-#pragma clang loop unroll(disable)
-        for (int rg = 0; rg < kRG; ++rg) {
-            const f32x4 dz = ld4(lds + L::d1 + o1 * kRP + 4 * rg);
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const f32x4 xv = ld4(lds + L::x + (4 * ig1 + a) * kRP + 4 * rg);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) G.g1[a] = __fmaf_rn(dz[r], xv[r], G.g1[a]);
-            }
-        }
-    }
-    if (bk == 0) {
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) G.gb = __fadd_rn(G.gb, lds[L::d1 + bu * kRP + r]);
-    }
-}
-
-// the slice's partial: every thread its own elements (gls: the logstd element of the threads kLsT .. kLsT + 3)
-__device__ __forceinline__ void store_acc(float *part, const Acc &G, float gls)
-{
-    const int t = threadIdx.x;
-    const int ti = t & 31, to = t >> 5, o1 = t & 127, ig1 = t >> 7;
-    const int bk = t < 128 ? 0 : t < 256 ? 1 : t < 260 ? 2 : -1, bu = t & 127;
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) part[kW1 + (8 * to + a) * kH + ti + 32 * j] = G.g2[a][j];
-    if (ig1 < 3) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) part[kW0 + (4 * ig1 + a) * kH + o1] = G.g1[a];
-    }
-    part[kW2 + t] = G.g3;
-    if (bk >= 0) part[(bk == 0 ? kB0 : bk == 1 ? kB1 : kB2) + bu] = G.gb;
-    if (t >= kLsT && t < kLsT + kOut) part[kLS + t - kLsT] = gls;
-}
-
-// sigma_j and the two constants of neglogp and the entropy from four logstd
-__device__ __forceinline__ void head_consts(const float *ls, float *sig, float *cnl, double *ent)
-{
-    double s = 0.0;
-#pragma unroll
-    for (int j = 0; j < kOut; ++j) { sig[j] = expf(ls[j]); s += (double)ls[j]; }
-    *cnl = (float)(2.0 * 1.8378770664093453 + s);                    // 2 log(2 pi) + sum logstd
-    *ent = s + 2.0 * 2.8378770664093453;                              // sum logstd + 2 log(2 pi e)
-}
-
-// the sum of the 256 values of a workgroup in a fixed binary tree -> every thread
-__device__ __forceinline__ double block_sum(double *p, double x)
-{
-    const int t = threadIdx.x;
-    __syncthreads();
-    p[t] = x;
-    __syncthreads();
-    for (int h = kVecBlock >> 1; h > 0; h >>= 1) {
-        if (t < h) p[t] += p[t + h];
-        __syncthreads();
-    }
-    return p[0];
 }
 
 // DOT of the header, by one workgroup of 256 threads, kDotBatch blocks of 256 elements per pass through LDS -> every thread
@@ -315,18 +118,10 @@ __global__ __launch_bounds__(kVecBlock) void k_trpo_prep(Policy Pol, Rows R, Ws 
 {
     __shared__ double p[kVecBlock];
     const int t = threadIdx.x;
-    double s = 0.0;
-    for (int64_t i = t; i < R.n; i += kVecBlock) s += (double)__fsub_rn(R.ret[i], R.val[i]);
-    const double mean = block_sum(p, s) / (double)R.n;
-    s = 0.0;
-    for (int64_t i = t; i < R.n; i += kVecBlock) {
-        const double d = (double)__fsub_rn(R.ret[i], R.val[i]) - mean;
-        s += d * d;
-    }
-    const double var = block_sum(p, s) / (double)R.n;
+    double mean, var;
+    adv_moments<kVecBlock>(p, R.n, [&](int64_t i) { return __fsub_rn(R.ret[i], R.val[i]); }, &mean, &var);
     if (t == 0) {
-        W.adv[0] = (float)mean;
-        W.adv[1] = (float)(1.0 / (sqrt(var) + 1.0e-8));
+        store_adv(W.adv, mean, var);
         W.flag[kFlagSkip] = 0;
         W.flag[kFlagCgDone] = 0;
         W.flag[kFlagAccepted] = -1;
@@ -409,7 +204,7 @@ __global__ __launch_bounds__(kFitBlock) void k_trpo_grad(Rows R, Ws W, float inv
 #pragma unroll
             for (int r = 0; r < kRows; ++r) gls = __fadd_rn(gls, lds[L::dl + (t - kLsT) * kRP + r]);
         }
-        backward_chunk(lds, G);
+        backward_chunk<L>(lds, G);
     }
     store_acc(part, G, gls);
     if (t == kStatT) {
@@ -461,7 +256,7 @@ __global__ __launch_bounds__(kVecBlock) void k_trpo_cg_init(Ws W, int slices, do
         double s = 0.0, ent = 0.0;
         for (int g = 0; g < slices; ++g) s += W.statp[2 * g];
         for (int j = 0; j < kOut; ++j) ent += (double)W.theta[kLS + j];
-        ent += 2.0 * 2.8378770664093453;
+        ent += 2.0 * kLog2PiE;
         const double sb = s / n + entcoeff * ent;
         const bool skip = rd == 0.0;
         W.sc[kScRdotr] = rd;
@@ -564,7 +359,7 @@ __global__ __launch_bounds__(kFitBlock) void k_trpo_fvp(Rows R, Ws W, const floa
             lds[L::y + o * kRP + r] = r0 + r < end ? __fmul_rn(__fdiv_rn(acc, s2[o]), inv_nf) : 0.0f;
         }
         __syncthreads();
-        backward_chunk(lds, G);
+        backward_chunk<L>(lds, G);
     }
     store_acc(part, G, 0.0f);
 }
@@ -706,8 +501,8 @@ __global__ __launch_bounds__(kVecBlock) void k_trpo_ls_decide(Policy Pol, Ws W, 
         ent += (double)theta_at(W.theta, W.fs, scale, kLS + j);
         ent_old += (double)W.theta[kLS + j];
     }
-    ent += 2.0 * 2.8378770664093453;
-    ent_old += 2.0 * 2.8378770664093453;
+    ent += 2.0 * kLog2PiE;
+    ent_old += 2.0 * kLog2PiE;
     const double sb = W.sc[kScSurrBefore];
     const double surr = s0 / n + entcoeff * ent, kl = s1 / n;
     // (every comparison is false for a NaN; an infinite surrogate would pass the improvement test: isfinite)
@@ -818,7 +613,7 @@ __global__ __launch_bounds__(kFitBlock) void k_trpo_vf_fit(VfArgs F)
             if (t == kStatT) {
                 for (int r = 0; r < kRows && r0 + r < F.batch; ++r) { const float e = lds[L::sc + r]; lsum = __fadd_rn(lsum, __fmul_rn(e, e)); }
             }
-            backward_chunk(lds, G);
+            backward_chunk<L>(lds, G);
         }
         // ---- Adam on the thread's own elements: m and v in registers, the weight in LDS
         __syncthreads();

@@ -1,6 +1,6 @@
 """One row per kernel of libquadsim_bc.so's code object (csrc/bcfit_kernels.hpp): the fit k_bc_fit, the validation pass k_bc_loss
-and its one-workgroup sum k_bc_loss_sum.  None is a template; the library includes dynfit_kernels.hpp for its device functions
-and instantiates none of its kernels.
+and its one-workgroup sum k_bc_loss_sum.  None is a template; the library takes its device functions from train_pieces.hpp,
+which defines no kernel.
 
 Imported by tests/test_bcfit_cpu.py, which checks that the rows are exactly the kernels of the built code object and their
 resources, and names the GPU test that holds each.  Plain Python.

@@ -1,6 +1,6 @@
 """One row per kernel of libquadsim_ddpg.so's code object (csrc/ddpg_kernels.hpp): the train step k_ddpg_step (two workgroups:
 the critic branch and the actor branch) and the copy into and out of the workspace, k_ddpg_copy.  Neither is a template.  The library
-includes dynfit_kernels.hpp for its device functions and instantiates none of its kernels.
+takes its device functions from train_pieces.hpp, which defines no kernel.
 
 Imported by tests/test_ddpg_cpu.py, which checks that the rows are exactly the kernels of the built code object and their
 resources, and names the GPU test that holds each.  Plain Python.

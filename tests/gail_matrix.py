@@ -1,6 +1,6 @@
 """One row per kernel instantiation of libquadsim_gail.so's code object (csrc/gail_kernels.hpp): the fit k_gail_fit<W> and the
-reward pass k_gail_reward<W> at both compiled widths, and the tests' window on the device math, k_gail_math.  The library includes
-dynfit_kernels.hpp for its device functions and instantiates none of its kernels.
+reward pass k_gail_reward<W> at both compiled widths, and the tests' window on the device math, k_gail_math.  The library takes
+its shared device functions from train_pieces.hpp, which defines no kernel.
 
 Imported by tests/test_gail_cpu.py, which checks that the rows are exactly the kernels of the built code object and their
 resources, and names the GPU test that holds each.  Plain Python.

@@ -1,6 +1,6 @@
 """One row per kernel of libquadsim_ppo.so's code object (csrc/ppo2_kernels.hpp): the advantage statistics k_ppo_adv_stats, the
 gradient kernel k_ppo_grad, the reduction k_ppo_reduce and the clip-and-Adam kernel k_ppo_apply.  None is a template; the library
-includes dynfit_kernels.hpp for its device functions and instantiates none of its kernels.
+takes its device functions from train_pieces.hpp, which defines no kernel.
 
 Imported by tests/test_ppo2_cpu.py, which checks that the rows are exactly the kernels of the built code object and their
 resources, and names the GPU test that holds each.  Plain Python.

@@ -54,8 +54,8 @@ def test_every_declared_symbol_is_exported_and_lib_knows_the_fifth_path(lib):
     assert not set(bc.BC_EXPORTS) & (set(dynplan.EXPORTS) | set(dynplan.MPPI_EXPORTS) | set(dynplan.FIT_EXPORTS))
     assert os.path.basename(_lib.BC_LIB_PATH) == "libquadsim_bc.so"
     side = _lib.SIDE
-    assert sorted(os.path.basename(h) for h in side["bc"]["headers"]) == ["bcfit_kernels.hpp", "dynfit_kernels.hpp", "quadsim_bc.h",
-                                                                           "quadsim_device.hpp", "side_host.hpp"]
+    assert sorted(os.path.basename(h) for h in side["bc"]["headers"]) == ["bcfit_kernels.hpp", "quadsim_bc.h", "quadsim_device.hpp",
+                                                                           "side_host.hpp", "train_pieces.hpp"]
     assert [os.path.basename(s) for s in side["bc"]["sources"]] == ["bcfit.hip"]
     assert all(os.path.exists(h) for h in side["bc"]["headers"] + side["bc"]["sources"])
     assert not [h for h in _lib.HEADERS + side["dyn"]["headers"] + side["dynmppi"]["headers"] + side["dynfit"]["headers"]

@@ -59,8 +59,8 @@ def test_every_declared_symbol_is_exported_and_lib_knows_the_eighth_path(lib):
     assert list(_lib.SIDE) == ["dyn", "dynmppi", "dynfit", "bc"] and _lib.TABLES[-1] is _lib.OFFPOLICY
     e = _lib.OFFPOLICY["ddpg"]
     assert _lib._entry("ddpg") is e and os.path.basename(_lib.DDPG_LIB_PATH) == "libquadsim_ddpg.so" == e["file"]
-    assert sorted(os.path.basename(h) for h in e["headers"]) == ["ddpg_kernels.hpp", "dynfit_kernels.hpp", "quadsim_ddpg.h", "quadsim_device.hpp",
-                                                                  "side_host.hpp"]
+    assert sorted(os.path.basename(h) for h in e["headers"]) == ["ddpg_kernels.hpp", "quadsim_ddpg.h", "quadsim_device.hpp", "side_host.hpp",
+                                                                  "train_pieces.hpp"]
     assert [os.path.basename(s) for s in e["sources"]] == ["ddpg.hip"] and all(os.path.exists(h) for h in e["headers"] + e["sources"])
     assert all(name in _lib.SIDE_POINTERS for name in e["signatures"])
     others = [_lib.SIDE[k] for k in _lib.SIDE] + [_lib.TRAIN["ppo"], _lib.IMITATE["gail"]]

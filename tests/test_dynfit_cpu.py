@@ -55,7 +55,7 @@ def test_every_declared_symbol_is_exported_and_lib_knows_the_fourth_path(lib):
     assert os.path.basename(_lib.DYNFIT_LIB_PATH) == "libquadsim_dynfit.so"
     dynfit = _lib.SIDE["dynfit"]
     assert sorted(os.path.basename(h) for h in dynfit["headers"]) == ["dynfit_kernels.hpp", "quadsim_device.hpp", "quadsim_dyn_fit.h",
-                                                                       "side_host.hpp"]
+                                                                       "side_host.hpp", "train_pieces.hpp"]
     assert [os.path.basename(s) for s in dynfit["sources"]] == ["dynfit.hip"]
     assert all(os.path.exists(h) for h in dynfit["headers"] + dynfit["sources"])
     assert not [h for h in _lib.HEADERS + _lib.SIDE["dyn"]["headers"] + _lib.SIDE["dynmppi"]["headers"]

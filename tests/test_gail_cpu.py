@@ -56,8 +56,8 @@ def test_every_declared_symbol_is_exported_and_lib_knows_the_seventh_path(lib):
     assert list(_lib.IMITATE) == ["gail"] and list(_lib.SIDE) == ["dyn", "dynmppi", "dynfit", "bc"] and list(_lib.TRAIN) == ["ppo"]
     e = _lib.IMITATE["gail"]
     assert _lib._entry("gail") is e and os.path.basename(_lib.GAIL_LIB_PATH) == "libquadsim_gail.so" == e["file"]
-    assert sorted(os.path.basename(h) for h in e["headers"]) == ["dynfit_kernels.hpp", "gail_kernels.hpp", "quadsim_device.hpp", "quadsim_gail.h",
-                                                                  "side_host.hpp"]
+    assert sorted(os.path.basename(h) for h in e["headers"]) == ["gail_kernels.hpp", "quadsim_device.hpp", "quadsim_gail.h", "side_host.hpp",
+                                                                  "train_pieces.hpp"]
     assert [os.path.basename(s) for s in e["sources"]] == ["gail.hip"] and all(os.path.exists(h) for h in e["headers"] + e["sources"])
     assert all(name in _lib.SIDE_POINTERS for name in e["signatures"])
     others = [_lib.SIDE[k] for k in _lib.SIDE] + [_lib.TRAIN["ppo"]]

@@ -55,8 +55,8 @@ def test_every_declared_symbol_is_exported_and_lib_knows_the_sixth_path(lib):
     assert sorted(w for w in out.split() if w.startswith("qsp_")) == names
     assert os.path.basename(_lib.PPO_LIB_PATH) == "libquadsim_ppo.so" and list(_lib.TRAIN) == ["ppo"] and "ppo" not in _lib.SIDE
     e = _lib.TRAIN["ppo"]
-    assert sorted(os.path.basename(h) for h in e["headers"]) == ["dynfit_kernels.hpp", "ppo2_kernels.hpp", "quadsim_device.hpp", "quadsim_ppo.h",
-                                                                 "side_host.hpp"]
+    assert sorted(os.path.basename(h) for h in e["headers"]) == ["ppo2_kernels.hpp", "quadsim_device.hpp", "quadsim_ppo.h", "side_host.hpp",
+                                                                 "train_pieces.hpp"]
     assert [os.path.basename(s) for s in e["sources"]] == ["ppo2.hip"] and all(os.path.exists(h) for h in e["headers"] + e["sources"])
     assert not [h for h in _lib.HEADERS + [h for s in _lib.SIDE.values() for h in s["headers"]] if "ppo" in os.path.basename(h)]
     env = dict(os.environ, QUADSIM_PPO_LIB="/somewhere/else.so")

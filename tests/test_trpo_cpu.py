@@ -55,7 +55,7 @@ def test_every_declared_symbol_is_exported_and_lib_knows_the_ninth_path(lib):
     assert list(_lib.OFFPOLICY) == ["ddpg"] and list(_lib.IMITATE) == ["gail"] and list(_lib.TRAIN) == ["ppo"]
     e = _lib.TRUST["trpo"]
     assert _lib._entry("trpo") is e and os.path.basename(_lib.TRPO_LIB_PATH) == "libquadsim_trpo.so" == e["file"]
-    assert sorted(os.path.basename(h) for h in e["headers"]) == ["dynfit_kernels.hpp", "quadsim_device.hpp", "quadsim_trpo.h", "side_host.hpp",
+    assert sorted(os.path.basename(h) for h in e["headers"]) == ["quadsim_device.hpp", "quadsim_trpo.h", "side_host.hpp", "train_pieces.hpp",
                                                                   "trpo_kernels.hpp"]
     assert [os.path.basename(s) for s in e["sources"]] == ["trpo.hip"] and all(os.path.exists(h) for h in e["headers"] + e["sources"])
     assert all(name in _lib.SIDE_POINTERS for name in e["signatures"])

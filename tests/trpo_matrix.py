@@ -1,5 +1,6 @@
 """One row per kernel of libquadsim_trpo.so's code object (csrc/trpo_kernels.hpp): the nine kernels of a policy step and the value
-fit.  None is a template.  The library includes dynfit_kernels.hpp for its device functions and instantiates none of its kernels.
+fit.  None is a template.  The library takes its device functions from train_pieces.hpp, which defines
+no kernel.
 
 Imported by tests/test_trpo_cpu.py, which checks that the rows are exactly the kernels of the built code object and their
 resources, and names the GPU test that holds each.  Plain Python.
