@@ -1,7 +1,5 @@
-"""ctypes binding of libquadsim_hip.so (the C ABI declared in include/quadsim.h), and the tables (SIDE, TRAIN, IMITATE, TRUST,
-OFFPOLICY), build, loader and call helper of the four side libraries that dynplan.py and bc.py wrap, of the training library that
-ppo2.py wraps, of the imitation library that gail.py wraps, of the trust-region library that trpo.py wraps and of the off-policy
-library that ddpg.py wraps.
+"""ctypes binding of libquadsim_hip.so (the C ABI declared in include/quadsim.h), and the table (SIDE), build, loader and call
+helper of the eight side libraries that dynplan.py, bc.py, ppo2.py, gail.py, trpo.py and ddpg.py wrap.
 
 There is deliberately no fallback of any kind: if the HIP library is missing or
 no MI355X is visible, loading / qs_create raise.  Nothing here imports oracle/.
@@ -206,15 +204,19 @@ class QsddHyper(C.Structure):
 
 
 f64, psize, psix = C.c_double, C.POINTER(C.c_size_t), C.POINTER(vp * 6)
-# The four libraries beside the main one, each its own translation unit, .so and code object, by short name.  They share at the
-# source level only: device fragments (*_kernels.hpp, dynplan_image.hpp, train_pieces.hpp, quadsim_device.hpp) and the host fragments side_host.hpp
-# (all four) and dynplan_host.hpp (the two planners).  An entry: the variable that overrides the path (A/B builds) and the file
-# name, the source, the fragments it is rebuilt for, the public header, and the signatures of its entry points in the header's
-# order -- argument types or, where the result is not int, (argument types, result type).  Everything else is derived: the paths,
-# EXPORTS per library, the build, the loader.  tests/test_call_path_cpu.py compares the signatures with the headers.
+# The eight libraries beside the main one, each its own translation unit, .so and code object, by short name, in build order.
+# They share at the source level only: device fragments (*_kernels.hpp, dynplan_image.hpp, train_pieces.hpp, quadsim_device.hpp)
+# and the host fragments side_host.hpp (all eight) and dynplan_host.hpp (the two planners).  An entry: the variable that overrides
+# the path (A/B builds) and the file name, the source, the fragments it is rebuilt for, the public header, the prefix that the
+# kernel names of its code object start with and no kernel name of another library does, and the signatures of its entry points
+# in the header's order -- argument types or, where the result is not int, (argument types, result type).  Everything else is
+# derived: the paths, EXPORTS per library, the build, the loader.  tests/test_call_path_cpu.py compares the signatures with the
+# headers, tests/side_cases.py holds the rest of an entry against the built library.
 SIDE = {
-    # random-shooting MPC over the learned net (bound in dynplan.py)
-    "dyn": dict(env="QUADSIM_DYN_LIB", file="libquadsim_dyn.so", source="dynplan.hip", header="quadsim_dyn.h", prefix="qsd_",
+    # random-shooting MPC over the learned net (bound in dynplan.py).  kernels: the other two kernels of this library, k_dyn_finish
+    # and k_dyn_pack, come in with dynplan_kernels.hpp and so are in "dynmppi" as well, and k_dyn_ begins the kernel of "dynfit" too:
+    # k_dyn_plan is the longest prefix that separates this library from both
+    "dyn": dict(env="QUADSIM_DYN_LIB", file="libquadsim_dyn.so", source="dynplan.hip", header="quadsim_dyn.h", prefix="qsd_", kernels=b"k_dyn_plan",
                 fragments=("dynplan_host.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp", "side_host.hpp"),
                 signatures={
                     "qsd_version": [],
@@ -224,7 +226,7 @@ SIDE = {
                     "qsd_plan_workspace_bytes": [i64, i32, psize],
                     "qsd_shooting_plan": [vp, i64, vp, u64, u64, u64, i32, i32] + [vp] * 8}),
     # MPPI over the learned net (dynplan.py): the device code of "dyn" (the model step, the image layout), no host state of it
-    "dynmppi": dict(env="QUADSIM_DYNMPPI_LIB", file="libquadsim_dynmppi.so", source="dynmppi.hip", header="quadsim_dyn_mppi.h", prefix="qsdm_",
+    "dynmppi": dict(env="QUADSIM_DYNMPPI_LIB", file="libquadsim_dynmppi.so", source="dynmppi.hip", header="quadsim_dyn_mppi.h", prefix="qsdm_", kernels=b"k_dynm_",
                     fragments=("dynmppi_kernels.hpp", "dynplan_host.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp",
                                "side_host.hpp"),
                     signatures={
@@ -234,14 +236,14 @@ SIDE = {
                         "qsdm_mppi_plan": [vp, i32, i32, i64, vp, u64, u64, u64, i32, i32, i32, f32, f32, i32] + [vp] * 11}),
     # the Adam fit of the learned net (dynplan.py): takes the net's own tensors, not the image; the chunk primitives of
     # train_pieces.hpp, the Philox generator of the main library
-    "dynfit": dict(env="QUADSIM_DYNFIT_LIB", file="libquadsim_dynfit.so", source="dynfit.hip", header="quadsim_dyn_fit.h", prefix="qsdf_",
+    "dynfit": dict(env="QUADSIM_DYNFIT_LIB", file="libquadsim_dynfit.so", source="dynfit.hip", header="quadsim_dyn_fit.h", prefix="qsdf_", kernels=b"k_dyn_fit",
                    fragments=("dynfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
                    signatures={
                        "qsdf_version": [],
                        "qsdf_last_error": ([], C.c_char_p),
                        "qsdf_fit": [C.POINTER(QsdfNet), vp, vp, i64, i64, i32, i32, f64, f64, f64, f64, i64, u64, u64, vp, vp, vp, psix, vp]}),
     # behaviour cloning of the actor (bc.py): takes the policy's own tensors; the tower pieces of train_pieces.hpp
-    "bc": dict(env="QUADSIM_BC_LIB", file="libquadsim_bc.so", source="bcfit.hip", header="quadsim_bc.h", prefix="qsbc_",
+    "bc": dict(env="QUADSIM_BC_LIB", file="libquadsim_bc.so", source="bcfit.hip", header="quadsim_bc.h", prefix="qsbc_", kernels=b"k_bc_",
                fragments=("bcfit_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
                signatures={
                    "qsbc_version": [],
@@ -249,12 +251,8 @@ SIDE = {
                    "qsbc_fit": [C.POINTER(QsbcNet), vp, vp, i64, vp, vp, i32, i32, f64, f64, f64, f64, i64, vp, psix, vp],
                    "qsbc_loss_blocks": ([i64], i64),
                    "qsbc_loss": [psix, vp, vp, i64, vp, i64, vp, vp, i32, vp]}),
-}
-# The libraries that train a policy, entries of the same format in a table of their own: every helper below looks a key up in
-# both tables (_entry).
-TRAIN = {
     # the PPO2 update (ppo2.py): takes the policy's own tensors; the tower pieces of train_pieces.hpp
-    "ppo": dict(env="QUADSIM_PPO_LIB", file="libquadsim_ppo.so", source="ppo2.hip", header="quadsim_ppo.h", prefix="qsp_",
+    "ppo": dict(env="QUADSIM_PPO_LIB", file="libquadsim_ppo.so", source="ppo2.hip", header="quadsim_ppo.h", prefix="qsp_", kernels=b"k_ppo_",
                 fragments=("ppo2_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
                 signatures={
                     "qsp_version": [],
@@ -263,11 +261,8 @@ TRAIN = {
                     "qsp_workspace_bytes": [i64, i32, psize],
                     "qsp_update": [C.POINTER(QspNet), C.POINTER(QspBatch), vp, i32, i64, i32, C.POINTER(QspHyper), i64, vp, u64, vp,
                                    C.POINTER(vp * 13), vp]}),
-}
-# The libraries that imitate an expert adversarially, a third table of the same format.
-IMITATE = {
     # GAIL's discriminator (gail.py): its own tensors; the Adam step and the chunk geometry of train_pieces.hpp, q_tanh of the main library
-    "gail": dict(env="QUADSIM_GAIL_LIB", file="libquadsim_gail.so", source="gail.hip", header="quadsim_gail.h", prefix="qsg_",
+    "gail": dict(env="QUADSIM_GAIL_LIB", file="libquadsim_gail.so", source="gail.hip", header="quadsim_gail.h", prefix="qsg_", kernels=b"k_gail_",
                  fragments=("gail_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
                  signatures={
                      "qsg_version": [],
@@ -275,11 +270,8 @@ IMITATE = {
                      "qsg_fit": [C.POINTER(QsgNet), vp, vp, i64, vp, vp, i64, vp, vp, vp, i32, i32, f64, f64, f64, f64, f64, i64, vp, psix, vp],
                      "qsg_reward": [C.POINTER(QsgNet), vp, vp, i64, i64, i64, vp, vp, i32, vp],
                      "qsg_math": [i32, vp, vp, i64, vp]}),
-}
-# The libraries that take trust-region steps, a table of the same format (the fifth to be added, the fourth in TABLES).
-TRUST = {
     # the TRPO update (trpo.py): the policy's own tensors; the tower pieces of train_pieces.hpp
-    "trpo": dict(env="QUADSIM_TRPO_LIB", file="libquadsim_trpo.so", source="trpo.hip", header="quadsim_trpo.h", prefix="qst_",
+    "trpo": dict(env="QUADSIM_TRPO_LIB", file="libquadsim_trpo.so", source="trpo.hip", header="quadsim_trpo.h", prefix="qst_", kernels=b"k_trpo_",
                  fragments=("trpo_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
                  signatures={
                      "qst_version": [],
@@ -289,11 +281,8 @@ TRUST = {
                      "qst_policy_step": [C.POINTER(QstNet), C.POINTER(QstBatch), i32, C.POINTER(QstHyper), vp, u64, vp, vp,
                                          C.POINTER(QstTrace), vp],
                      "qst_vf_fit": [C.POINTER(QstNet), vp, vp, i64, vp, i32, i32, f64, f64, f64, f64, i64, vp, psix, vp]}),
-}
-# The libraries that train off-policy from a replay, a table of the same format.
-OFFPOLICY = {
     # the DDPG update (ddpg.py): the four nets' own tensors; the tower pieces of train_pieces.hpp, q_tanh of the main library
-    "ddpg": dict(env="QUADSIM_DDPG_LIB", file="libquadsim_ddpg.so", source="ddpg.hip", header="quadsim_ddpg.h", prefix="qsdd_",
+    "ddpg": dict(env="QUADSIM_DDPG_LIB", file="libquadsim_ddpg.so", source="ddpg.hip", header="quadsim_ddpg.h", prefix="qsdd_", kernels=b"k_ddpg_",
                  fragments=("ddpg_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
                  signatures={
                      "qsdd_version": [],
@@ -302,19 +291,7 @@ OFFPOLICY = {
                      "qsdd_update": [C.POINTER(QsddNets), C.POINTER(QsddReplay), vp, vp, i32, i32, C.POINTER(QsddHyper), i64, vp, u64, vp,
                                      C.POINTER(vp * 12), vp]}),
 }
-TABLES = (SIDE, TRAIN, IMITATE, TRUST, OFFPOLICY)
-
-
-def _entry(key):
-    """the entry `key` of SIDE, of TRAIN, of IMITATE, of TRUST or of OFFPOLICY"""
-    return next(t[key] for t in TABLES if key in t)
-
-
-def _entries():
-    return [e for t in TABLES for e in t.values()]
-
-
-for _e in _entries():
+for _e in SIDE.values():
     _e["path"] = os.environ.get(_e["env"]) or os.path.join(CSRC, _e["file"])
     _e["sources"] = [os.path.join(CSRC, _e["source"])]
     _e["headers"] = [os.path.join(CSRC, h) for h in _e["fragments"]] + [os.path.join(HERE, "..", "include", _e["header"])]
@@ -322,12 +299,7 @@ for _e in _entries():
 # the positions of every entry point's pointer parameters: side_call sends those through as_arg and leaves the scalars to the
 # argtypes (as_arg on a scalar costs 0.3 us, and a plan has a dozen of them)
 SIDE_POINTERS = {name: tuple(i for i, t in enumerate(sig[0] if isinstance(sig, tuple) else sig) if t is vp or issubclass(t, C._Pointer))
-                 for _e in _entries() for name, sig in _e["signatures"].items()}
-DYN_LIB_PATH, DYNMPPI_LIB_PATH, DYNFIT_LIB_PATH, BC_LIB_PATH = (SIDE[k]["path"] for k in ("dyn", "dynmppi", "dynfit", "bc"))
-PPO_LIB_PATH = TRAIN["ppo"]["path"]
-GAIL_LIB_PATH = IMITATE["gail"]["path"]
-TRPO_LIB_PATH = TRUST["trpo"]["path"]
-DDPG_LIB_PATH = OFFPOLICY["ddpg"]["path"]
+                 for _e in SIDE.values() for name, sig in _e["signatures"].items()}
 
 
 class QuadsimError(RuntimeError):
@@ -366,7 +338,7 @@ def build_one_library(sources, deps, out, link=(), force=False, verbose=False):
 def build_library(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all nine libraries, returns the main one's
     path."""
-    for e in _entries():
+    for e in SIDE.values():
         build_one_library(e["sources"], e["headers"], e["path"], (), force, verbose)
     return build_one_library(SOURCES, HEADERS, LIB_PATH, ["-lhsa-runtime64"], force, verbose)
 
@@ -445,10 +417,10 @@ _side = {}
 
 
 def side_load(key):
-    """dlopen the side library `key` of any table of TABLES, once; raises QuadsimError if it has not been built (there is no fallback)"""
+    """dlopen the side library `key` of SIDE, once; raises QuadsimError if it has not been built (there is no fallback)"""
     lib = _side.get(key)
     if lib is None:
-        e = _entry(key)
+        e = SIDE[key]
         if not os.path.exists(e["path"]):
             raise QuadsimError("%s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % e["path"])
         import torch  # noqa: F401  (its HIP runtime must be the resident one: see load)
@@ -462,7 +434,7 @@ def side_load(key):
 
 def side_check(key, rc, what):
     if rc != 0:
-        msg = getattr(side_load(key), _entry(key)["prefix"] + "last_error")().decode("utf-8", "replace")
+        msg = getattr(side_load(key), SIDE[key]["prefix"] + "last_error")().decode("utf-8", "replace")
         raise QuadsimError("%s failed (%d): %s" % (what, rc, msg))
 
 

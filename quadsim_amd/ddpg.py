@@ -27,9 +27,9 @@ CRITIC_SHAPES = ((12, 128), (128,), (132, 128), (128,), (128, 1), (1,))
 NET_NAMES = ("actor", "critic", "actor_target", "critic_target")
 DDPG_STAT_NAMES = ("critic_loss", "actor_loss", "q_mean", "y_mean")
 
-# libquadsim_ddpg.so is the entry "ddpg" of _lib.OFFPOLICY: its path, signatures, loader, status check and call helper are _lib's.
+# libquadsim_ddpg.so is the entry "ddpg" of _lib.SIDE: its path, signatures, loader, status check and call helper are _lib's.
 # The names below stay this module's so that callers and tests can replace the loader
-QsddNets, QsddReplay, QsddHyper, DDPG_EXPORTS = _lib.QsddNets, _lib.QsddReplay, _lib.QsddHyper, _lib.OFFPOLICY["ddpg"]["exports"]
+QsddNets, QsddReplay, QsddHyper, DDPG_EXPORTS = _lib.QsddNets, _lib.QsddReplay, _lib.QsddHyper, _lib.SIDE["ddpg"]["exports"]
 load_ddpg, check_ddpg = functools.partial(_lib.side_load, "ddpg"), functools.partial(_lib.side_check, "ddpg")
 
 

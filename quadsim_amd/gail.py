@@ -36,9 +36,9 @@ GAIL_WIDTHS = (64, 128)                             # the compiled (padded) hidd
 DISC_KEYS = ("w0", "b0", "w1", "b1", "w2", "b2")
 DISC_STAT_NAMES = ("gen_loss", "exp_loss", "entropy", "gen_acc", "exp_acc")
 
-# libquadsim_gail.so is the entry "gail" of _lib.IMITATE: its path, signatures, loader, status check and call helper are _lib's.
+# libquadsim_gail.so is the entry "gail" of _lib.SIDE: its path, signatures, loader, status check and call helper are _lib's.
 # The names below stay this module's so that callers and tests can replace the loader
-QsgNet, GAIL_EXPORTS = _lib.QsgNet, _lib.IMITATE["gail"]["exports"]
+QsgNet, GAIL_EXPORTS = _lib.QsgNet, _lib.SIDE["gail"]["exports"]
 load_gail, check_gail = functools.partial(_lib.side_load, "gail"), functools.partial(_lib.side_check, "gail")
 
 

@@ -25,8 +25,8 @@ STAT_NAMES = ("policy_loss", "value_loss", "policy_entropy", "approxkl", "clipfr
 SLOT_KEYS = ("w0", "b0", "w1", "b1", "w2", "b2", "wv0", "bv0", "wv1", "bv1", "wv2", "bv2", "logstd")
 SLOT_SHAPES = ((12, 128), (128,), (128, 128), (128,), (128, 4), (4,), (12, 128), (128,), (128, 128), (128,), (128, 1), (1,), (4,))
 
-# libquadsim_ppo.so is the entry "ppo" of _lib.TRAIN: its path, signatures, loader, status check and call helper are _lib's
-QspNet, QspBatch, QspHyper, PPO_EXPORTS = _lib.QspNet, _lib.QspBatch, _lib.QspHyper, _lib.TRAIN["ppo"]["exports"]
+# libquadsim_ppo.so is the entry "ppo" of _lib.SIDE: its path, signatures, loader, status check and call helper are _lib's
+QspNet, QspBatch, QspHyper, PPO_EXPORTS = _lib.QspNet, _lib.QspBatch, _lib.QspHyper, _lib.SIDE["ppo"]["exports"]
 load_ppo, check_ppo = functools.partial(_lib.side_load, "ppo"), functools.partial(_lib.side_check, "ppo")
 
 

@@ -32,8 +32,8 @@ STAT_NAMES = ("surr_before", "surr_after", "kl_after", "entropy", "grad_norm", "
 POLICY_SLOTS, VALUE_SLOTS = (0, 1, 2, 3, 4, 5, 12), (6, 7, 8, 9, 10, 11)
 POLICY_KEYS, VALUE_KEYS = tuple(SLOT_KEYS[i] for i in POLICY_SLOTS), tuple(SLOT_KEYS[i] for i in VALUE_SLOTS)
 
-# libquadsim_trpo.so is the entry "trpo" of _lib.TRUST: its path, signatures, loader, status check and call helper are _lib's
-QstNet, QstBatch, QstHyper, QstTrace, TRPO_EXPORTS = _lib.QstNet, _lib.QstBatch, _lib.QstHyper, _lib.QstTrace, _lib.TRUST["trpo"]["exports"]
+# libquadsim_trpo.so is the entry "trpo" of _lib.SIDE: its path, signatures, loader, status check and call helper are _lib's
+QstNet, QstBatch, QstHyper, QstTrace, TRPO_EXPORTS = _lib.QstNet, _lib.QstBatch, _lib.QstHyper, _lib.QstTrace, _lib.SIDE["trpo"]["exports"]
 load_trpo, check_trpo = functools.partial(_lib.side_load, "trpo"), functools.partial(_lib.side_check, "trpo")
 
 

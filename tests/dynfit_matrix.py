@@ -10,7 +10,7 @@ _F = "tests/test_gpu_dynfit.py::"
 
 
 def _row(key, widths, test):
-    return dict(id="-".join(str(x) for x in key), kernel=key[0], key=key, widths=widths, test=test)
+    return dict(id="-".join(str(x) for x in key), kernel=key[0], key=key, widths=widths, block=512, test=test)
 
 
 ROWS = [

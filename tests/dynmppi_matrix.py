@@ -15,8 +15,8 @@ _F = "tests/test_gpu_dynmppi.py::"
 _D = "tests/test_gpu_dynplan.py::"
 
 
-def _row(key, widths, test, inherited=False):
-    return dict(id="-".join(str(x) for x in key), kernel=key[0], key=key, widths=widths, test=test, inherited=inherited,
+def _row(key, widths, test, inherited=False, block=256):
+    return dict(id="-".join(str(x) for x in key), kernel=key[0], key=key, widths=widths, block=block, test=test, inherited=inherited,
                 note=INHERITED_NOTE if inherited else "")
 
 
@@ -24,7 +24,7 @@ ROWS = [
     _row(("k_dynm_roll", 4, 4), (64, 64), _F + "test_steps_scores_and_update[edge_64_64]"),
     _row(("k_dynm_roll", 8, 8), (128, 128), _F + "test_steps_scores_and_update[he_128_128]"),
     _row(("k_dynm_roll", 13, 7), (208, 112), _F + "test_steps_scores_and_update[edge_208_112]"),
-    _row(("k_dynm_update",), None, _F + "test_shapes_keyed_draws_every_iteration[257-5-3]"),
+    _row(("k_dynm_update",), None, _F + "test_shapes_keyed_draws_every_iteration[257-5-3]", block=1024),
     _row(("k_dyn_finish",), None, _D + "test_draws[3]", inherited=True),
     _row(("k_dyn_pack",), None, _D + "test_padding_is_invisible", inherited=True),
 ]

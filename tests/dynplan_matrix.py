@@ -13,7 +13,7 @@ _F = "tests/test_gpu_dynplan.py::"
 
 
 def _row(key, widths, test):
-    return dict(id="-".join(str(x) for x in key), kernel=key[0], key=key, widths=widths, test=_F + test)
+    return dict(id="-".join(str(x) for x in key), kernel=key[0], key=key, widths=widths, block=256, test=_F + test)
 
 
 ROWS = [

@@ -4,21 +4,13 @@ check_bc_args mirrors it; tests/bcfit_matrix.py has exactly one row per kernel o
 fits the compute unit's LDS; tests/bcfit_ref.py is checked against torch's float64 autograd and central differences; the host
 schedule covers every train row once an epoch; and no fixture of tests/test_gpu_bcfit.py holds a pre-activation within its forward
 bound of zero."""
-import os
-import re
-import shutil
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import bcfit_matrix
 import bcfit_ref as br
 import kernel_notes
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "quadsim_bc.h")
+import side_cases
 
 
 @pytest.fixture(scope="module")
@@ -30,43 +22,25 @@ def lib():
 
 @pytest.fixture(scope="module")
 def notes(tmp_path_factory):
-    from quadsim_amd import _lib
-    _lib.build_library()
-    co = kernel_notes.code_object(tmp_path_factory.mktemp("isa_bcfit"), so=_lib.BC_LIB_PATH)
-    return kernel_notes.kernel_notes(co, kernel_notes.FIELDS + ("sgpr_spill_count",))
+    return side_cases.code_object_notes("bc", tmp_path_factory)
 
 
 # ---------------------------------------------------------------------------------------------------- the header and the ABI
-def _declared():
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(qsbc_\w+)\s*\(", text)))
+def test_every_declared_symbol_is_exported(lib):
+    from quadsim_amd import bc
+    side_cases.check_exports("bc", lib, ["qsbc_fit", "qsbc_last_error", "qsbc_loss", "qsbc_loss_blocks", "qsbc_version"])
+    assert sorted(bc.BC_EXPORTS) == side_cases.declared("bc")
 
 
-def test_every_declared_symbol_is_exported_and_lib_knows_the_fifth_path(lib):
+def test_no_other_library_holds_its_kernels(lib):
+    side_cases.check_no_foreign_kernels("bc")
+
+
+def test_table_entry_names_its_own_files(lib):
     import quadsim_amd as qa
-    from quadsim_amd import _lib, bc, dynplan
-    names = _declared()
-    assert names == sorted(bc.BC_EXPORTS) and len(names) == 5
-    assert not [n for n in names if not hasattr(lib, n)]
-    assert lib.qsbc_version() == 1
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.BC_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert sorted(w for w in out.split() if w.startswith("qsbc_")) == names
+    from quadsim_amd import bc, dynplan
     assert not set(bc.BC_EXPORTS) & (set(dynplan.EXPORTS) | set(dynplan.MPPI_EXPORTS) | set(dynplan.FIT_EXPORTS))
-    assert os.path.basename(_lib.BC_LIB_PATH) == "libquadsim_bc.so"
-    side = _lib.SIDE
-    assert sorted(os.path.basename(h) for h in side["bc"]["headers"]) == ["bcfit_kernels.hpp", "quadsim_bc.h", "quadsim_device.hpp",
-                                                                           "side_host.hpp", "train_pieces.hpp"]
-    assert [os.path.basename(s) for s in side["bc"]["sources"]] == ["bcfit.hip"]
-    assert all(os.path.exists(h) for h in side["bc"]["headers"] + side["bc"]["sources"])
-    assert not [h for h in _lib.HEADERS + side["dyn"]["headers"] + side["dynmppi"]["headers"] + side["dynfit"]["headers"]
-                if "bc" in os.path.basename(h)]
-    env = dict(os.environ, QUADSIM_BC_LIB="/somewhere/else.so")
-    got = subprocess.run([sys.executable, "-c", "from quadsim_amd import _lib; print(_lib.BC_LIB_PATH)"], cwd=ROOT, env=env,
-                         capture_output=True, text=True, check=True).stdout.strip()
-    assert got == "/somewhere/else.so"
-    for so in (_lib.LIB_PATH, _lib.DYN_LIB_PATH, _lib.DYNMPPI_LIB_PATH, _lib.DYNFIT_LIB_PATH):
-        assert b"k_bc_" not in open(so, "rb").read(), so
-    assert b"k_dyn_fit" not in open(_lib.BC_LIB_PATH, "rb").read()
+    side_cases.check_entry("bc", ["bcfit_kernels.hpp", "quadsim_bc.h", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"], "bcfit.hip")
     assert [lib.qsbc_loss_blocks(c) for c in (-1, 0, 1, 256, 257, (1 << 31) - 1)] == [0, 0, 1, 1, 2, 1 << 23]
     for name in ("ExpertData", "epoch_schedule", "pretrain", "check_bc_args", "bc_fit", "bc_loss"):
         assert getattr(qa, name) is getattr(bc, name) and name in qa.__all__
@@ -152,17 +126,7 @@ int main(void)
 def test_header_is_c99_and_every_refusal_launches_nothing(lib, tmp_path):
     """a plain C program, -std=c99 -Wall -Werror, linked against the new library alone.  Every call it makes is one the library
     refuses, with host pointers it would never dereference: each returns before anything is launched"""
-    assert shutil.which("gcc") is not None
-    src = tmp_path / "bcfit_caller.c"
-    src.write_text(C_CALLER)
-    exe = str(tmp_path / "bcfit_caller")
-    libdir = os.path.join(ROOT, "quadsim_amd", "csrc")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + libdir,
-                           "-lquadsim_bc", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.split() == ["ALL-REFUSED", str(len(_declared()))]
+    side_cases.run_c_caller("bc", C_CALLER, tmp_path)
 
 
 GOOD = dict(n=300, steps=100, batch=64, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, t0=0)
@@ -219,28 +183,14 @@ def test_pretrain_refuses_a_host_policy_and_has_no_cpu_path(monkeypatch):
 
 # ---------------------------------------------------------------------------------------------------- the census
 def test_rows_are_exactly_the_kernels_of_the_code_object_without_scratch(notes):
-    keys = [r["kernel"] for r in bcfit_matrix.ROWS]
-    assert len(keys) == len(set(keys)) == len(notes)
-    got = {}
-    for sym, f in notes.items():
-        m = re.match(r"^_ZN3qsb(\d+)(k_\w+?)E", sym)
-        assert m and int(m.group(1)) == len(m.group(2)), "a kernel outside namespace qsb, or a template: %s" % sym
-        got[m.group(2)] = f
-    assert kernel_notes.base_names(notes) == set(bcfit_matrix.KERNELS) == set(keys) == set(got)
-    for r in bcfit_matrix.ROWS:
-        f = got[r["kernel"]]
-        assert f["private_segment_fixed_size"] == 0 and f["vgpr_spill_count"] == 0, (r["kernel"], f)
-        assert f["group_segment_fixed_size"] <= 160 * 1024 and f["max_flat_workgroup_size"] == r["block"], (r["kernel"], f)
-        print("bcfit notes %s %s" % (r["kernel"], f))
+    """no kernel is a template; k_bc_fit, which keeps Adam's state in registers, spills scalar registers"""
+    assert {(r["kernel"],) for r in bcfit_matrix.ROWS} == {r["key"] for r in bcfit_matrix.ROWS}
+    side_cases.check_census(notes, bcfit_matrix, lambda n: kernel_notes.instantiations_with_types(n, bcfit_matrix.KERNELS, namespace="qsb"), "bcfit",
+                            sgpr_spills=("k_bc_fit",))
 
 
 def test_rows_name_existing_gpu_tests():
-    files = sorted({r["test"].split("::")[0] for r in bcfit_matrix.ROWS})
-    out = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + files, cwd=ROOT,
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    ids = set(out.stdout.split())
-    assert not [r["test"] for r in bcfit_matrix.ROWS if r["test"] not in ids]
+    side_cases.check_rows_name_gpu_tests(bcfit_matrix)
 
 
 # ---------------------------------------------------------------------------------------------------- the reference itself

@@ -48,10 +48,11 @@ def test_signature_table_matches_the_header():
 
 
 def test_side_signature_tables_match_their_headers():
-    """the same for the four side libraries: the prototypes of each header are exactly the table's entries, with the count and
-    kind (pointer, int32, int64, uint64, float, double) of every parameter and the kind of the result"""
+    """the same for the eight side libraries: the prototypes of each header are exactly the table's entries, with the count and
+    kind (pointer, int32, int64, uint64, float, double) of every parameter and the kind of the result, and SIDE_POINTERS holds
+    the positions of the pointers"""
     from quadsim_amd import _lib
-    assert list(_lib.SIDE) == ["dyn", "dynmppi", "dynfit", "bc"]
+    assert list(_lib.SIDE) == ["dyn", "dynmppi", "dynfit", "bc", "ppo", "gail", "trpo", "ddpg"]
     counts = {}
     for key, e in _lib.SIDE.items():
         protos = _header_prototypes(e["header"], e["prefix"])
@@ -59,27 +60,34 @@ def test_side_signature_tables_match_their_headers():
         for name, sig in e["signatures"].items():
             args, result = sig if isinstance(sig, tuple) else (sig, C.c_int)
             assert (_ctype_kind(result), [_ctype_kind(t) for t in args]) == protos[name], name
+            assert _lib.SIDE_POINTERS[name] == tuple(i for i, k in enumerate(protos[name][1]) if k == "ptr"), name
         assert protos[e["prefix"] + "last_error"] == ("ptr", []) and protos[e["prefix"] + "version"] == ("int32", [])
         counts[key] = len(protos)
-    assert counts == {"dyn": 6, "dynmppi": 4, "dynfit": 3, "bc": 5}
+    assert counts == {"dyn": 6, "dynmppi": 4, "dynfit": 3, "bc": 5, "ppo": 5, "gail": 5, "trpo": 6, "ddpg": 4}
     assert _header_prototypes("quadsim_bc.h", "qsbc_")["qsbc_loss_blocks"] == ("int64", ["int64"])
 
 
 def test_each_side_library_keeps_its_own_error_text():
     """a refused call (refused before the device is touched: nothing is launched) writes the error text of its own library and
-    leaves the other three as they were"""
+    leaves the other seven as they were"""
     from quadsim_amd import _lib
     _lib.build_library()
     libs = {key: _lib.side_load(key) for key in _lib.SIDE}
     nbytes, six = C.c_size_t(0), (C.c_void_p * 6)()
     x = C.addressof(six)                                       # a non-NULL pointer that no refused call dereferences
     net = _lib.QsdfNet(12345)                                  # a struct_size no other test uses
+    nets, replay, hyper = _lib.QsddNets(12345), _lib.QsddReplay(), _lib.QsddHyper()
     refusals = {
         "dyn": (lambda lib: lib.qsd_plan_workspace_bytes(-12345, 200, C.byref(nbytes)), b"n must be >= 1, got -12345"),
         "dynmppi": (lambda lib: lib.qsdm_workspace_bytes(1, -12345, 200, C.byref(nbytes)), b"horizon must be in [1, 1024], got -12345"),
         "dynfit": (lambda lib: lib.qsdf_fit(C.byref(net), x, x, 1, 1, 1, 1, 1e-4, 0.9, 0.999, 1e-8, 0, 0, 0, None, x, None, None, None),
                    b"QsdfNet.struct_size is 12345, expected %d" % C.sizeof(_lib.QsdfNet)),
         "bc": (lambda lib: lib.qsbc_loss(six, x, x, -12345, None, 1, x, x, 0, None), b"n must be in [1, 2^31), got -12345"),
+        "ppo": (lambda lib: lib.qsp_workspace_bytes(-12345, 1, C.byref(nbytes)), b"batch must be in [1, 2^31), got -12345"),
+        "gail": (lambda lib: lib.qsg_math(-12345, x, x, 10, None), b"kind must be in [0, 4], got -12345"),
+        "trpo": (lambda lib: lib.qst_workspace_bytes(-54321, 7, C.byref(nbytes)), b"n must be in [1, 2^31), got -54321"),
+        "ddpg": (lambda lib: lib.qsdd_update(C.byref(nets), C.byref(replay), x, None, 100, 10, C.byref(hyper), 0, x, 0, x, None, None),
+                 b"QsddNets.struct_size is 12345, expected %d" % C.sizeof(_lib.QsddNets)),
     }
 
     def texts():
@@ -92,7 +100,7 @@ def test_each_side_library_keeps_its_own_error_text():
         assert after.pop(key) == text
         del before[key]
         assert after == before, key
-    assert len(set(texts().values())) == 4
+    assert len(set(texts().values())) == 8
 
 
 # ---------------------------------------------------------------- the shipped _call on a fake library

@@ -1,5 +1,5 @@
 """-m "not gpu": everything of DDPG on the device that needs no device.  include/quadsim_ddpg.h is plain C99 and every symbol it
-declares is exported by libquadsim_ddpg.so; the table entry of _lib.OFFPOLICY matches the header's prototypes; every refusal the
+declares is exported by libquadsim_ddpg.so; the table entry of _lib.SIDE matches the header's prototypes; every refusal the
 header promises happens before anything is launched, and check_ddpg_args mirrors it; tests/ddpg_matrix.py has exactly one row per
 kernel of the new code object, none uses scratch and each fits the compute unit's LDS; tests/ddpg_ref.py is checked against torch's
 float64 autograd, which it shares no code with; the float64 reference meets the learning condition the device is held to; the
@@ -8,9 +8,6 @@ for every kernel."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,9 +15,9 @@ import pytest
 import ddpg_matrix
 import ddpg_ref as dd
 import kernel_notes
+import side_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "quadsim_ddpg.h")
 KEYS = dd.KEYS
 
 
@@ -33,63 +30,33 @@ def lib():
 
 @pytest.fixture(scope="module")
 def notes(tmp_path_factory):
-    from quadsim_amd import _lib
-    _lib.build_library()
-    co = kernel_notes.code_object(tmp_path_factory.mktemp("isa_ddpg"), so=_lib.DDPG_LIB_PATH)
-    return kernel_notes.kernel_notes(co, kernel_notes.FIELDS + ("sgpr_spill_count",))
+    return side_cases.code_object_notes("ddpg", tmp_path_factory)
 
 
 # ---------------------------------------------------------------------------------------------------- the header and the ABI
-def _declared():
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(qsdd_\w+)\s*\(", text)))
+def test_every_declared_symbol_is_exported(lib):
+    side_cases.check_exports("ddpg", lib, ["qsdd_last_error", "qsdd_update", "qsdd_version", "qsdd_workspace_bytes"])
 
 
-def test_every_declared_symbol_is_exported_and_lib_knows_the_eighth_path(lib):
+def test_table_entry_names_its_own_files():
     import quadsim_amd as qa
     from quadsim_amd import _lib, ddpg
-    names = _declared()
-    assert names == sorted(ddpg.DDPG_EXPORTS) == ["qsdd_last_error", "qsdd_update", "qsdd_version", "qsdd_workspace_bytes"]
-    assert not [n for n in names if not hasattr(lib, n)]
-    assert lib.qsdd_version() == 1
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.DDPG_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert sorted(w for w in out.split() if w.startswith("qsdd_")) == names
-    # the fourth table, and the three that existing tests pin
-    assert list(_lib.OFFPOLICY) == ["ddpg"] and list(_lib.IMITATE) == ["gail"] and list(_lib.TRAIN) == ["ppo"]
-    assert list(_lib.SIDE) == ["dyn", "dynmppi", "dynfit", "bc"] and _lib.TABLES[-1] is _lib.OFFPOLICY
-    e = _lib.OFFPOLICY["ddpg"]
-    assert _lib._entry("ddpg") is e and os.path.basename(_lib.DDPG_LIB_PATH) == "libquadsim_ddpg.so" == e["file"]
-    assert sorted(os.path.basename(h) for h in e["headers"]) == ["ddpg_kernels.hpp", "quadsim_ddpg.h", "quadsim_device.hpp", "side_host.hpp",
-                                                                  "train_pieces.hpp"]
-    assert [os.path.basename(s) for s in e["sources"]] == ["ddpg.hip"] and all(os.path.exists(h) for h in e["headers"] + e["sources"])
-    assert all(name in _lib.SIDE_POINTERS for name in e["signatures"])
-    others = [_lib.SIDE[k] for k in _lib.SIDE] + [_lib.TRAIN["ppo"], _lib.IMITATE["gail"]]
-    assert not [h for h in _lib.HEADERS + [h for o in others for h in o["headers"] + o["sources"]] if "ddpg" in os.path.basename(h)]
-    env = dict(os.environ, QUADSIM_DDPG_LIB="/somewhere/else.so")
-    got = subprocess.run([sys.executable, "-c", "from quadsim_amd import _lib; print(_lib.DDPG_LIB_PATH)"], cwd=ROOT, env=env,
-                         capture_output=True, text=True, check=True).stdout.strip()
-    assert got == "/somewhere/else.so"
-    assert len(others) == 6
-    for so in [_lib.LIB_PATH] + [o["path"] for o in others]:
-        assert b"k_ddpg_" not in open(so, "rb").read(), so
-    blob = open(_lib.DDPG_LIB_PATH, "rb").read()
-    assert b"k_ddpg_step" in blob
-    assert b"k_dyn_fit" not in blob and b"k_bc_" not in blob and b"k_ppo_" not in blob and b"k_gail_" not in blob
+    assert ddpg.DDPG_EXPORTS is _lib.SIDE["ddpg"]["exports"]
+    side_cases.check_entry("ddpg", ["ddpg_kernels.hpp", "quadsim_ddpg.h", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"], "ddpg.hip")
     for name in ("DDPG", "DDPGPolicy", "ReplayBuffer", "OUNoise", "replay_schedule", "ddpg_update", "torch_ddpg_update", "check_ddpg_args"):
         assert getattr(qa, name) is getattr(ddpg, name) and name in qa.__all__
     assert ddpg.DDPG_MAX_STEPS == 4096 and ddpg.DDPG_MAX_BATCH == 256
 
 
-def test_table_entry_matches_the_header(lib):
-    import test_call_path_cpu as cp
+def test_no_other_library_holds_its_kernels(lib):
     from quadsim_amd import _lib
-    e = _lib.OFFPOLICY["ddpg"]
-    protos = cp._header_prototypes(e["header"], e["prefix"])
-    assert sorted(protos) == sorted(e["signatures"]) == sorted(e["exports"]) and len(protos) == 4
-    for name, sig in e["signatures"].items():
-        args, result = sig if isinstance(sig, tuple) else (sig, C.c_int)
-        assert (cp._ctype_kind(result), [cp._ctype_kind(t) for t in args]) == protos[name], name
-    assert protos["qsdd_last_error"] == ("ptr", []) and protos["qsdd_version"] == ("int32", [])
+    side_cases.check_no_foreign_kernels("ddpg")
+    assert b"k_ddpg_step" in open(_lib.SIDE["ddpg"]["path"], "rb").read()
+
+
+def test_table_entry_matches_the_header(lib):
+    """the structs and the workspace; the prototypes are held by tests/test_call_path_cpu.py, for every side library"""
+    from quadsim_amd import _lib
     # the structs: two 32-bit fields, then 48 tensors; n and five tensors; eight doubles
     assert C.sizeof(_lib.QsddNets) == 8 + 48 * 8 and _lib.QsddNets.m.offset == 8 + 24 * 8 and _lib.QsddNets.v.offset == 8 + 36 * 8
     assert C.sizeof(_lib.QsddReplay) == 16 + 5 * 8 and C.sizeof(_lib.QsddHyper) == 8 + 8 * 8
@@ -204,17 +171,7 @@ int main(void)
 def test_header_is_c99_and_every_refusal_launches_nothing(lib, tmp_path):
     """a plain C program, -std=c99 -Wall -Werror, linked against the new library alone.  Every call it makes is one the library
     refuses, with host pointers it would never dereference: each returns before anything is launched"""
-    assert shutil.which("gcc") is not None
-    src = tmp_path / "ddpg_caller.c"
-    src.write_text(C_CALLER)
-    exe = str(tmp_path / "ddpg_caller")
-    libdir = os.path.join(ROOT, "quadsim_amd", "csrc")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + libdir,
-                           "-lquadsim_ddpg", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.split() == ["ALL-REFUSED", str(len(_declared()))]
+    side_cases.run_c_caller("ddpg", C_CALLER, tmp_path)
 
 
 GOOD = dict(n=300, steps=100, batch=10, gamma=0.99, tau=1e-3, actor_lr=1e-4, critic_lr=1e-3, obs_clip=5.0, beta1=0.9, beta2=0.999, eps=1e-8,
@@ -271,29 +228,11 @@ def test_host_policies_and_bad_arguments_are_refused(monkeypatch):
 
 # ---------------------------------------------------------------------------------------------------- the census
 def test_rows_are_exactly_the_kernels_of_the_code_object_without_scratch(notes):
-    keys = [r["key"] for r in ddpg_matrix.ROWS]
-    assert len(keys) == len(set(keys)) == len(notes)
-    got = kernel_notes.instantiations_with_types(notes, ddpg_matrix.KERNELS, namespace="qsdd")
-    assert got == set(keys), "a kernel without a row, or a row without a kernel: %s" % sorted(got ^ set(keys))
-    assert kernel_notes.base_names(notes) == set(ddpg_matrix.KERNELS)
-    by_key = {}
-    for sym, fl in notes.items():
-        (k,) = kernel_notes.instantiations_with_types({sym: fl}, ddpg_matrix.KERNELS, namespace="qsdd")
-        by_key[k] = fl
-    for r in ddpg_matrix.ROWS:
-        fl = by_key[r["key"]]
-        assert fl["private_segment_fixed_size"] == 0 and fl["vgpr_spill_count"] == 0 and fl["sgpr_spill_count"] == 0, (r["id"], fl)
-        assert fl["group_segment_fixed_size"] <= 160 * 1024 and fl["max_flat_workgroup_size"] == r["block"], (r["id"], fl)
-        print("ddpg notes %s %s" % (r["id"], fl))
+    side_cases.check_census(notes, ddpg_matrix, lambda n: kernel_notes.instantiations_with_types(n, ddpg_matrix.KERNELS, namespace="qsdd"), "ddpg")
 
 
 def test_rows_name_existing_gpu_tests():
-    files = sorted({r["test"].split("::")[0] for r in ddpg_matrix.ROWS})
-    out = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + files, cwd=ROOT,
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    ids = set(out.stdout.split())
-    assert not [r["test"] for r in ddpg_matrix.ROWS if r["test"] not in ids]
+    side_cases.check_rows_name_gpu_tests(ddpg_matrix)
 
 
 def test_the_other_seven_libraries_are_instruction_identical():

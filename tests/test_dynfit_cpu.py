@@ -4,11 +4,7 @@ anything is launched; tests/dynfit_matrix.py has exactly one row per kernel inst
 scratch and each fits the compute unit's LDS; tests/dynfit_ref.py is checked against finite differences and closed forms; and
 no fixture of tests/test_gpu_dynfit.py holds a pre-activation within its forward bound of zero; on the width-edge fixtures a
 gradient slot of the last unit of either hidden layer that was left at zero would be out of bound."""
-import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,9 +13,7 @@ import dynfit_matrix
 import dynfit_ref as fr
 import dynplan_ref as dr
 import kernel_notes
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "quadsim_dyn_fit.h")
+import side_cases
 
 
 @pytest.fixture(scope="module")
@@ -31,41 +25,23 @@ def lib():
 
 @pytest.fixture(scope="module")
 def notes(tmp_path_factory):
-    from quadsim_amd import _lib
-    _lib.build_library()
-    co = kernel_notes.code_object(tmp_path_factory.mktemp("isa_dynfit"), so=_lib.DYNFIT_LIB_PATH)
-    return kernel_notes.kernel_notes(co, kernel_notes.FIELDS + ("sgpr_spill_count",))
+    return side_cases.code_object_notes("dynfit", tmp_path_factory)
 
 
 # ---------------------------------------------------------------------------------------------------- the header and the ABI
-def _declared():
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(qsdf_\w+)\s*\(", text)))
-
-
-def test_every_declared_symbol_is_exported_and_lib_knows_the_fourth_path(lib):
-    from quadsim_amd import _lib, dynplan
-    names = _declared()
-    assert names == sorted(dynplan.FIT_EXPORTS) and len(names) == 3
-    assert not [n for n in names if not hasattr(lib, n)]
-    assert lib.qsdf_version() == 1
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.DYNFIT_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert sorted(w for w in out.split() if w.startswith("qsdf_")) == names
+def test_every_declared_symbol_is_exported(lib):
+    from quadsim_amd import dynplan
+    side_cases.check_exports("dynfit", lib, ["qsdf_fit", "qsdf_last_error", "qsdf_version"])
+    assert sorted(dynplan.FIT_EXPORTS) == side_cases.declared("dynfit")
     assert not set(dynplan.FIT_EXPORTS) & (set(dynplan.EXPORTS) | set(dynplan.MPPI_EXPORTS))
-    assert os.path.basename(_lib.DYNFIT_LIB_PATH) == "libquadsim_dynfit.so"
-    dynfit = _lib.SIDE["dynfit"]
-    assert sorted(os.path.basename(h) for h in dynfit["headers"]) == ["dynfit_kernels.hpp", "quadsim_device.hpp", "quadsim_dyn_fit.h",
-                                                                       "side_host.hpp", "train_pieces.hpp"]
-    assert [os.path.basename(s) for s in dynfit["sources"]] == ["dynfit.hip"]
-    assert all(os.path.exists(h) for h in dynfit["headers"] + dynfit["sources"])
-    assert not [h for h in _lib.HEADERS + _lib.SIDE["dyn"]["headers"] + _lib.SIDE["dynmppi"]["headers"]
-                if "dynfit" in os.path.basename(h) or "dyn_fit" in os.path.basename(h)]
-    env = dict(os.environ, QUADSIM_DYNFIT_LIB="/somewhere/else.so")
-    got = subprocess.run([sys.executable, "-c", "from quadsim_amd import _lib; print(_lib.DYNFIT_LIB_PATH)"], cwd=ROOT, env=env,
-                         capture_output=True, text=True, check=True).stdout.strip()
-    assert got == "/somewhere/else.so"
-    for so in (_lib.LIB_PATH, _lib.DYN_LIB_PATH, _lib.DYNMPPI_LIB_PATH):
-        assert b"k_dyn_fit" not in open(so, "rb").read(), so
+
+
+def test_table_entry_names_its_own_files():
+    side_cases.check_entry("dynfit", ["dynfit_kernels.hpp", "quadsim_device.hpp", "quadsim_dyn_fit.h", "side_host.hpp", "train_pieces.hpp"], "dynfit.hip")
+
+
+def test_no_other_library_holds_its_kernels(lib):
+    side_cases.check_no_foreign_kernels("dynfit")
 
 
 C_CALLER = r"""
@@ -137,17 +113,7 @@ int main(void)
 def test_header_is_c99_and_every_refusal_launches_nothing(lib, tmp_path):
     """a plain C program, -std=c99 -Wall -Werror, linked against the new library alone.  Every call it makes is one the library
     refuses, with host pointers it would never dereference: each returns before anything is launched"""
-    assert shutil.which("gcc") is not None
-    src = tmp_path / "dynfit_caller.c"
-    src.write_text(C_CALLER)
-    exe = str(tmp_path / "dynfit_caller")
-    libdir = os.path.join(ROOT, "quadsim_amd", "csrc")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + libdir,
-                           "-lquadsim_dynfit", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.split() == ["ALL-REFUSED", str(len(_declared()))]
+    side_cases.run_c_caller("dynfit", C_CALLER, tmp_path)
 
 
 GOOD = dict(h1=200, h2=100, capacity=300, size=257, iters=100, batch=128, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, t0=0, seed=0, k=0)
@@ -190,21 +156,13 @@ def test_fit_refuses_bad_tensors_and_has_no_cpu_path(monkeypatch):
 
 # ---------------------------------------------------------------------------------------------------- the census
 def test_rows_are_exactly_the_kernels_of_the_code_object_without_scratch(notes):
+    """every kernel is the template in namespace qsf; it keeps Adam's state in registers and spills scalar registers"""
     from quadsim_amd import dynplan
     keys = [r["key"] for r in dynfit_matrix.ROWS]
-    assert len(keys) == len(set(keys)) == len(notes)
-    got = set()
-    for sym in notes:
-        m = re.match(r"^_ZN3qsf(\d+)(k_\w+?)I((?:Li\d+E)+)E", sym)
-        assert m and int(m.group(1)) == len(m.group(2)), "a kernel outside namespace qsf: %s" % sym
-        got.add((m.group(2),) + tuple(int(a) for a in re.findall(r"Li(\d+)E", m.group(3))))
-    assert kernel_notes.base_names(notes) == set(dynfit_matrix.KERNELS)
-    assert set(keys) == got, (sorted(set(keys) - got), sorted(got - set(keys)))
+    side_cases.check_census(notes, dynfit_matrix, lambda n: kernel_notes.instantiations_with_types(n, dynfit_matrix.KERNELS, namespace="qsf"), "dynfit",
+                            sgpr_spills=("k_dyn_fit",))
     assert {k[1:] for k in keys} == set(dynplan.COMPILED_WIDTHS) == {r["widths"] for r in dynfit_matrix.ROWS}
-    for sym, f in notes.items():
-        assert f["private_segment_fixed_size"] == 0 and f["vgpr_spill_count"] == 0, (sym, f)
-        assert f["group_segment_fixed_size"] <= 160 * 1024 and f["max_flat_workgroup_size"] == 512, (sym, f)
-        print("dynfit notes %s %s" % (sym, f))
+    assert {len(k) for k in keys} == {3} and {r["block"] for r in dynfit_matrix.ROWS} == {512}
 
 
 def test_rows_name_a_net_of_exactly_their_widths():
@@ -215,12 +173,7 @@ def test_rows_name_a_net_of_exactly_their_widths():
 
 
 def test_rows_name_existing_gpu_tests():
-    files = sorted({r["test"].split("::")[0] for r in dynfit_matrix.ROWS})
-    out = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + files, cwd=ROOT,
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    ids = set(out.stdout.split())
-    assert not [r["test"] for r in dynfit_matrix.ROWS if r["test"] not in ids]
+    side_cases.check_rows_name_gpu_tests(dynfit_matrix)
 
 
 # ---------------------------------------------------------------------------------------------------- the reference itself

@@ -5,9 +5,6 @@ kernel uses scratch or spills and each fits the compute unit's LDS; the other tw
 fragment; tests/dynmppi_ref.py composes the two float64 references consistently."""
 import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,11 +12,10 @@ import pytest
 import dynmppi_matrix
 import dynmppi_ref
 import dynplan_ref as dr
-import kernel_notes
+import side_cases
 import mppi_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "quadsim_dyn_mppi.h")
 
 
 @pytest.fixture(scope="module")
@@ -31,25 +27,14 @@ def lib():
 
 @pytest.fixture(scope="module")
 def notes(tmp_path_factory):
-    from quadsim_amd import _lib
-    _lib.build_library()
-    co = kernel_notes.code_object(tmp_path_factory.mktemp("isa_dynmppi"), so=_lib.DYNMPPI_LIB_PATH)
-    return kernel_notes.kernel_notes(co, kernel_notes.FIELDS + ("sgpr_spill_count",))
+    return side_cases.code_object_notes("dynmppi", tmp_path_factory)
 
 
 # ---------------------------------------------------------------------------------------------------- the header and the ABI
-def _declared():
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(qsdm_\w+)\s*\(", text)))
-
-
 def test_every_declared_symbol_is_exported(lib):
     from quadsim_amd import dynplan
-    names = _declared()
-    assert names == sorted(dynplan.MPPI_EXPORTS) and len(names) == 4
-    missing = [n for n in names if not hasattr(lib, n)]
-    assert not missing, missing
-    assert lib.qsdm_version() == 1
+    side_cases.check_exports("dynmppi", lib, ["qsdm_last_error", "qsdm_mppi_plan", "qsdm_version", "qsdm_workspace_bytes"])
+    assert sorted(dynplan.MPPI_EXPORTS) == side_cases.declared("dynmppi")
     assert dynplan.EXPORTS == ["qsd_version", "qsd_last_error", "qsd_net_image_bytes", "qsd_net_pack", "qsd_plan_workspace_bytes",
                                "qsd_shooting_plan"]
     assert not set(dynplan.EXPORTS) & set(dynplan.MPPI_EXPORTS)
@@ -131,17 +116,7 @@ def test_header_is_c99_and_every_refusal_launches_nothing(lib, tmp_path):
     """a plain C program, -std=c99 -Wall -Werror, linked against the new library alone.  Every call it makes is one the library
     refuses, with host pointers it would never dereference: each returns before the device is queried or anything is launched,
     here without a device and on a machine with one alike"""
-    assert shutil.which("gcc") is not None
-    src = tmp_path / "dynmppi_caller.c"
-    src.write_text(C_CALLER)
-    exe = str(tmp_path / "dynmppi_caller")
-    libdir = os.path.join(ROOT, "quadsim_amd", "csrc")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + libdir,
-                           "-lquadsim_dynmppi", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.split() == ["ALL-REFUSED", str(len(_declared()))]
+    side_cases.run_c_caller("dynmppi", C_CALLER, tmp_path)
 
 
 def test_python_checks_refuse_before_the_library_is_touched(monkeypatch):
@@ -194,14 +169,14 @@ def _instantiations(notes):
     return got
 
 
-def test_rows_are_exactly_the_kernels_of_the_code_object(notes):
+@pytest.fixture(scope="module")
+def census(notes):
+    return side_cases.check_census(notes, dynmppi_matrix, _instantiations, "dynmppi")
+
+
+def test_rows_are_exactly_the_kernels_of_the_code_object(census):
     import dynplan_matrix
     keys = [r["key"] for r in dynmppi_matrix.ROWS]
-    assert len(keys) == len(set(keys)), "duplicate rows"
-    got = _instantiations(notes)
-    assert kernel_notes.base_names(notes) == set(dynmppi_matrix.KERNELS)
-    assert set(keys) == got, "rows without a kernel: %s; kernels without a row: %s" % (
-        sorted(set(keys) - got, key=str), sorted(got - set(keys), key=str))
     from quadsim_amd import dynplan
     assert {(16 * k[1], 16 * k[2]) for k in keys if k[0] == "k_dynm_roll"} == set(dynplan.COMPILED_WIDTHS)
     assert {r["widths"] for r in dynmppi_matrix.ROWS if r["widths"]} == set(dynplan.COMPILED_WIDTHS)
@@ -222,46 +197,26 @@ def test_rows_with_widths_name_a_net_of_exactly_those_widths():
 
 
 def test_rows_name_existing_gpu_tests():
-    files = sorted({r["test"].split("::")[0] for r in dynmppi_matrix.ROWS})
-    out = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + files, cwd=ROOT,
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    ids = set(out.stdout.split())
-    missing = [r["test"] for r in dynmppi_matrix.ROWS if r["test"] not in ids]
-    assert not missing, missing
+    side_cases.check_rows_name_gpu_tests(dynmppi_matrix)
 
 
-def test_no_kernel_uses_scratch_or_spills_and_each_fits_lds(notes):
-    assert len(notes) == len(dynmppi_matrix.ROWS)
-    for sym, f in notes.items():
-        assert f["private_segment_fixed_size"] == 0 and f["vgpr_spill_count"] == 0 and f["sgpr_spill_count"] == 0, (sym, f)
-        assert f["group_segment_fixed_size"] <= 160 * 1024, (sym, f)
-        print("dynmppi notes %s %s" % (sym, f))
-    roll = {k: f for k, f in notes.items() if "k_dynm_roll" in k}
-    assert max(f["group_segment_fixed_size"] for f in roll.values()) == 120656        # the 208 x 112 image, as quadsim_dyn.h says
+def test_no_kernel_uses_scratch_or_spills_and_each_fits_lds(census):
+    assert max(fl["group_segment_fixed_size"] for k, fl in census.items() if k[0] == "k_dynm_roll") == 120656        # the 208 x 112 image, as quadsim_dyn.h says
 
 
 def test_the_other_libraries_are_built_without_the_new_fragment():
     """dynmppi_kernels.hpp is a dependency of the third library alone, whose translation unit is the only file that includes
-    it; the lists of the other two are what they were"""
+    it, and no other library lists it"""
     from quadsim_amd import _lib
-    dyn, dynmppi = _lib.SIDE["dyn"], _lib.SIDE["dynmppi"]
-    assert not [h for h in _lib.HEADERS + dyn["headers"] if "dynmppi" in os.path.basename(h) or "dyn_mppi" in os.path.basename(h)]
-    assert sorted(os.path.basename(h) for h in dyn["headers"]) == [
-        "dynplan_host.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp", "quadsim_dyn.h", "side_host.hpp"]
-    assert sorted(os.path.basename(h) for h in dynmppi["headers"]) == [
-        "dynmppi_kernels.hpp", "dynplan_host.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp", "quadsim_dyn_mppi.h",
-        "side_host.hpp"]
-    assert [os.path.basename(s) for s in dynmppi["sources"]] == ["dynmppi.hip"]
-    assert all(os.path.exists(h) for h in dynmppi["headers"] + dynmppi["sources"])
+    side_cases.check_entry("dynmppi", ["dynmppi_kernels.hpp", "dynplan_host.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp",
+                                       "quadsim_dyn_mppi.h", "side_host.hpp"], "dynmppi.hip")
     csrc = os.path.join(ROOT, "quadsim_amd", "csrc")
     users = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")) and f != "dynmppi_kernels.hpp"
                    and "dynmppi_kernels.hpp\"" in open(os.path.join(csrc, f)).read())
     assert users == ["dynmppi.hip"]
-    assert _lib.build_library() == _lib.LIB_PATH and os.path.exists(_lib.DYN_LIB_PATH) and os.path.exists(_lib.DYNMPPI_LIB_PATH)
-    for so in (_lib.LIB_PATH, _lib.DYN_LIB_PATH):
-        assert b"k_dynm_" not in open(so, "rb").read(), so
-    assert b"k_dynm_roll" in open(_lib.DYNMPPI_LIB_PATH, "rb").read()
+    assert _lib.build_library() == _lib.LIB_PATH and os.path.exists(_lib.SIDE["dyn"]["path"]) and os.path.exists(_lib.SIDE["dynmppi"]["path"])
+    side_cases.check_no_foreign_kernels("dynmppi")
+    assert b"k_dynm_roll" in open(_lib.SIDE["dynmppi"]["path"], "rb").read()
 
 
 # ---------------------------------------------------------------------------------------------------- the reference glue

@@ -8,19 +8,15 @@ to the instantiation their table names and can detect a dropped last unit of eit
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import dynplan_matrix
 import dynplan_ref as dr
-import kernel_notes
+import side_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "quadsim_dyn.h")
 
 
 @pytest.fixture(scope="module")
@@ -32,25 +28,15 @@ def lib():
 
 @pytest.fixture(scope="module")
 def notes(tmp_path_factory):
-    from quadsim_amd import _lib
-    _lib.build_library()
-    co = kernel_notes.code_object(tmp_path_factory.mktemp("isa_dynplan"), so=_lib.DYN_LIB_PATH)
-    return kernel_notes.kernel_notes(co, kernel_notes.FIELDS + ("sgpr_spill_count",))
+    return side_cases.code_object_notes("dyn", tmp_path_factory)
 
 
 # ---------------------------------------------------------------------------------------------------- the header and the ABI
-def _declared():
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(qsd_\w+)\s*\(", text)))
-
-
 def test_every_declared_symbol_is_exported(lib):
     from quadsim_amd import dynplan
-    names = _declared()
-    assert names == sorted(dynplan.EXPORTS)
-    missing = [n for n in names if not hasattr(lib, n)]
-    assert not missing, missing
-    assert lib.qsd_version() == 1
+    side_cases.check_exports("dyn", lib, ["qsd_last_error", "qsd_net_image_bytes", "qsd_net_pack", "qsd_plan_workspace_bytes", "qsd_shooting_plan",
+                                          "qsd_version"])
+    assert sorted(dynplan.EXPORTS) == side_cases.declared("dyn")
 
 
 C_CALLER = r"""
@@ -106,17 +92,7 @@ int main(void)
 def test_header_is_c99_and_every_refusal_launches_nothing(lib, tmp_path):
     """a plain C program, -std=c99 -Wall -Werror, linked against the new library alone; it runs here, without a device, so
     every call it makes returns before a launch"""
-    assert shutil.which("gcc") is not None
-    src = tmp_path / "dyn_caller.c"
-    src.write_text(C_CALLER)
-    exe = str(tmp_path / "dyn_caller")
-    libdir = os.path.join(ROOT, "quadsim_amd", "csrc")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + libdir,
-                           "-lquadsim_dyn", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.split() == ["ALL-REFUSED", str(len(_declared()))]
+    side_cases.run_c_caller("dyn", C_CALLER, tmp_path)
 
 
 def test_python_checks_refuse_before_the_library_is_touched():
@@ -161,46 +137,34 @@ def _instantiations(notes):
     return got
 
 
-def test_rows_are_exactly_the_kernels_of_the_code_object(notes):
+@pytest.fixture(scope="module")
+def census(notes):
+    return side_cases.check_census(notes, dynplan_matrix, _instantiations, "dynplan")
+
+
+def test_rows_are_exactly_the_kernels_of_the_code_object(census):
     keys = [r["key"] for r in dynplan_matrix.ROWS]
-    assert len(keys) == len(set(keys)), "duplicate rows"
-    got = _instantiations(notes)
-    assert kernel_notes.base_names(notes) == set(dynplan_matrix.KERNELS)
-    assert set(keys) == got, "rows without a kernel: %s; kernels without a row: %s" % (
-        sorted(set(keys) - got, key=str), sorted(got - set(keys), key=str))
     from quadsim_amd import dynplan
     assert {(16 * k[1], 16 * k[2]) for k in keys if k[0] == "k_dyn_plan"} == set(dynplan.COMPILED_WIDTHS)
     assert {r["widths"] for r in dynplan_matrix.ROWS if r["widths"]} == set(dynplan.COMPILED_WIDTHS)
 
 
 def test_rows_name_existing_gpu_tests():
-    files = sorted({r["test"].split("::")[0] for r in dynplan_matrix.ROWS})
-    out = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + files, cwd=ROOT,
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    ids = set(out.stdout.split())
-    missing = [r["test"] for r in dynplan_matrix.ROWS if r["test"] not in ids]
-    assert not missing, missing
+    side_cases.check_rows_name_gpu_tests(dynplan_matrix)
 
 
-def test_no_kernel_uses_scratch_or_spills_and_each_fits_lds(notes):
-    assert len(notes) == len(dynplan_matrix.ROWS)
-    for sym, f in notes.items():
-        assert f["private_segment_fixed_size"] == 0 and f["vgpr_spill_count"] == 0 and f["sgpr_spill_count"] == 0, (sym, f)
-        assert f["group_segment_fixed_size"] <= 160 * 1024, (sym, f)
-        print("dynplan notes %s %s" % (sym, f))
-    plan = {k: f for k, f in notes.items() if "k_dyn_plan" in k}
-    assert max(f["group_segment_fixed_size"] for f in plan.values()) == 120656        # the 208 x 112 image, as the header says
+def test_no_kernel_uses_scratch_or_spills_and_each_fits_lds(census):
+    assert max(fl["group_segment_fixed_size"] for k, fl in census.items() if k[0] == "k_dyn_plan") == 120656        # the 208 x 112 image, as the header says
 
 
 def test_main_library_is_built_without_the_new_fragments():
     """the second library's fragments are not dependencies of libquadsim_hip.so, and its kernels are not in it"""
     from quadsim_amd import _lib
-    assert not [h for h in _lib.HEADERS if "dynplan" in h]
     assert not [h for h in _lib.HEADERS if "side_host" in h]
-    assert sorted(os.path.basename(h) for h in _lib.SIDE["dyn"]["headers"]) == [
-        "dynplan_host.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp", "quadsim_dyn.h", "side_host.hpp"]
-    assert _lib.build_library() == _lib.LIB_PATH and os.path.exists(_lib.DYN_LIB_PATH)
+    side_cases.check_entry("dyn", ["dynplan_host.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp", "quadsim_device.hpp", "quadsim_dyn.h",
+                                   "side_host.hpp"], "dynplan.hip")
+    assert _lib.build_library() == _lib.LIB_PATH and os.path.exists(_lib.SIDE["dyn"]["path"])
+    side_cases.check_no_foreign_kernels("dyn")
 
 
 # ---------------------------------------------------------------------------------------------------- the image's permutation

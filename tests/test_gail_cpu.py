@@ -1,5 +1,5 @@
 """-m "not gpu": everything of GAIL on the device that needs no device.  include/quadsim_gail.h is plain C99 and every symbol it
-declares is exported by libquadsim_gail.so; the table entry of _lib.IMITATE matches the header's prototypes; every refusal the
+declares is exported by libquadsim_gail.so; the table entry of _lib.SIDE matches the header's prototypes; every refusal the
 header promises happens before anything is launched, and check_gail_args mirrors it; tests/gail_matrix.py has exactly one row per
 kernel instantiation of the new code object, none uses scratch and each fits the compute unit's LDS; tests/gail_ref.py is checked
 against torch's float64 autograd, which it shares no code with; the schedule and the running statistics hold their properties;
@@ -7,9 +7,6 @@ and the recorded instruction diff of the other six libraries says `same` for eve
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,9 +14,9 @@ import pytest
 import gail_matrix
 import gail_ref as gr
 import kernel_notes
+import side_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "quadsim_gail.h")
 
 
 @pytest.fixture(scope="module")
@@ -31,61 +28,32 @@ def lib():
 
 @pytest.fixture(scope="module")
 def notes(tmp_path_factory):
-    from quadsim_amd import _lib
-    _lib.build_library()
-    co = kernel_notes.code_object(tmp_path_factory.mktemp("isa_gail"), so=_lib.GAIL_LIB_PATH)
-    return kernel_notes.kernel_notes(co, kernel_notes.FIELDS + ("sgpr_spill_count",))
+    return side_cases.code_object_notes("gail", tmp_path_factory)
 
 
 # ---------------------------------------------------------------------------------------------------- the header and the ABI
-def _declared():
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(qsg_\w+)\s*\(", text)))
+def test_every_declared_symbol_is_exported(lib):
+    side_cases.check_exports("gail", lib, ["qsg_fit", "qsg_last_error", "qsg_math", "qsg_reward", "qsg_version"])
 
 
-def test_every_declared_symbol_is_exported_and_lib_knows_the_seventh_path(lib):
+def test_table_entry_names_its_own_files():
     import quadsim_amd as qa
     from quadsim_amd import _lib, gail
-    names = _declared()
-    assert names == sorted(gail.GAIL_EXPORTS) == ["qsg_fit", "qsg_last_error", "qsg_math", "qsg_reward", "qsg_version"]
-    assert not [n for n in names if not hasattr(lib, n)]
-    assert lib.qsg_version() == 1
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.GAIL_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert sorted(w for w in out.split() if w.startswith("qsg_")) == names
-    # the third table, and the two that existing tests pin
-    assert list(_lib.IMITATE) == ["gail"] and list(_lib.SIDE) == ["dyn", "dynmppi", "dynfit", "bc"] and list(_lib.TRAIN) == ["ppo"]
-    e = _lib.IMITATE["gail"]
-    assert _lib._entry("gail") is e and os.path.basename(_lib.GAIL_LIB_PATH) == "libquadsim_gail.so" == e["file"]
-    assert sorted(os.path.basename(h) for h in e["headers"]) == ["gail_kernels.hpp", "quadsim_device.hpp", "quadsim_gail.h", "side_host.hpp",
-                                                                  "train_pieces.hpp"]
-    assert [os.path.basename(s) for s in e["sources"]] == ["gail.hip"] and all(os.path.exists(h) for h in e["headers"] + e["sources"])
-    assert all(name in _lib.SIDE_POINTERS for name in e["signatures"])
-    others = [_lib.SIDE[k] for k in _lib.SIDE] + [_lib.TRAIN["ppo"]]
-    assert not [h for h in _lib.HEADERS + [h for o in others for h in o["headers"] + o["sources"]] if "gail" in os.path.basename(h)]
-    env = dict(os.environ, QUADSIM_GAIL_LIB="/somewhere/else.so")
-    got = subprocess.run([sys.executable, "-c", "from quadsim_amd import _lib; print(_lib.GAIL_LIB_PATH)"], cwd=ROOT, env=env,
-                         capture_output=True, text=True, check=True).stdout.strip()
-    assert got == "/somewhere/else.so"
-    for so in [_lib.LIB_PATH] + [o["path"] for o in others]:
-        assert b"k_gail_" not in open(so, "rb").read(), so
-    blob = open(_lib.GAIL_LIB_PATH, "rb").read()
-    assert b"k_dyn_fit" not in blob and b"k_bc_" not in blob
+    assert gail.GAIL_EXPORTS is _lib.SIDE["gail"]["exports"]
+    side_cases.check_entry("gail", ["gail_kernels.hpp", "quadsim_device.hpp", "quadsim_gail.h", "side_host.hpp", "train_pieces.hpp"], "gail.hip")
     for name in ("GAIL", "Discriminator", "GailRunner", "discriminator_schedule", "torch_discriminator_fit", "check_gail_args"):
         assert getattr(qa, name) is getattr(gail, name) and name in qa.__all__
     assert gail.GAIL_MAX_STEPS == 4096 and gail.GAIL_MAX_BATCH == 256 and gail.GAIL_MAX_HIDDEN == 128
     assert [gail.compiled_width(h) for h in (1, 64, 65, 100, 128)] == [64, 64, 128, 128, 128]
 
 
+def test_no_other_library_holds_its_kernels(lib):
+    side_cases.check_no_foreign_kernels("gail")
+
+
 def test_table_entry_matches_the_header():
-    import test_call_path_cpu as cp
+    """the struct; the prototypes are held by tests/test_call_path_cpu.py, for every side library"""
     from quadsim_amd import _lib
-    e = _lib.IMITATE["gail"]
-    protos = cp._header_prototypes(e["header"], e["prefix"])
-    assert sorted(protos) == sorted(e["signatures"]) == sorted(e["exports"]) and len(protos) == 5
-    for name, sig in e["signatures"].items():
-        args, result = sig if isinstance(sig, tuple) else (sig, C.c_int)
-        assert (cp._ctype_kind(result), [cp._ctype_kind(t) for t in args]) == protos[name], name
-    assert protos["qsg_last_error"] == ("ptr", []) and protos["qsg_version"] == ("int32", [])
     # the struct: two 32-bit fields, eighteen tensors, mean and rscale
     assert C.sizeof(_lib.QsgNet) == 8 + 20 * 8 and _lib.QsgNet.mean.offset == 8 + 18 * 8
 
@@ -205,17 +173,7 @@ int main(void)
 def test_header_is_c99_and_every_refusal_launches_nothing(lib, tmp_path):
     """a plain C program, -std=c99 -Wall -Werror, linked against the new library alone.  Every call it makes is one the library
     refuses, with host pointers it would never dereference: each returns before anything is launched"""
-    assert shutil.which("gcc") is not None
-    src = tmp_path / "gail_caller.c"
-    src.write_text(C_CALLER)
-    exe = str(tmp_path / "gail_caller")
-    libdir = os.path.join(ROOT, "quadsim_amd", "csrc")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + libdir,
-                           "-lquadsim_gail", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.split() == ["ALL-REFUSED", str(len(_declared()))]
+    side_cases.run_c_caller("gail", C_CALLER, tmp_path)
 
 
 GOOD = dict(n_gen=300, n_exp=200, steps=100, batch=64, hidden=100, entcoeff=1e-3, lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-8, t0=0)
@@ -290,29 +248,13 @@ def test_squashed_policies_and_host_discriminators_are_refused(monkeypatch):
 
 # ---------------------------------------------------------------------------------------------------- the census
 def test_rows_are_exactly_the_kernels_of_the_code_object_without_scratch(notes):
-    keys = [r["key"] for r in gail_matrix.ROWS]
-    assert len(keys) == len(set(keys)) == len(notes)
-    got = kernel_notes.instantiations_with_types(notes, gail_matrix.KERNELS, namespace="qsg")
-    assert got == set(keys), "a kernel without a row, or a row without a kernel: %s" % sorted(got ^ set(keys))
-    assert kernel_notes.base_names(notes) == set(gail_matrix.KERNELS)
-    by_key = {}
-    for sym, f in notes.items():
-        (k,) = kernel_notes.instantiations_with_types({sym: f}, gail_matrix.KERNELS, namespace="qsg")
-        by_key[k] = f
-    for r in gail_matrix.ROWS:
-        f = by_key[r["key"]]
-        assert f["private_segment_fixed_size"] == 0 and f["vgpr_spill_count"] == 0, (r["id"], f)
-        assert f["group_segment_fixed_size"] <= 160 * 1024 and f["max_flat_workgroup_size"] == r["block"], (r["id"], f)
-        print("gail notes %s %s" % (r["id"], f))
+    """k_gail_fit, which keeps Adam's state in registers, spills scalar registers"""
+    side_cases.check_census(notes, gail_matrix, lambda n: kernel_notes.instantiations_with_types(n, gail_matrix.KERNELS, namespace="qsg"), "gail",
+                            sgpr_spills=("k_gail_fit",))
 
 
 def test_rows_name_existing_gpu_tests():
-    files = sorted({r["test"].split("::")[0] for r in gail_matrix.ROWS})
-    out = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + files, cwd=ROOT,
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    ids = set(out.stdout.split())
-    assert not [r["test"] for r in gail_matrix.ROWS if r["test"] not in ids]
+    side_cases.check_rows_name_gpu_tests(gail_matrix)
 
 
 def test_the_other_six_libraries_are_instruction_identical():

@@ -21,10 +21,10 @@ import numpy as np
 import pytest
 
 import ddpg_ref as dd
+from side_cases import Guarded, same_bits
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256
 KEYS, NETS, ONLINE = dd.KEYS, dd.NETS, ("actor", "critic")
 HYPER = dict(gamma=dd.GAMMA, tau=dd.TAU, actor_lr=1e-2, critic_lr=1e-2, obs_clip=dd.OBS_CLIP)
 
@@ -34,29 +34,6 @@ def torch():
     import torch
     assert torch.cuda.is_available()
     return torch
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-class Guarded:
-    """a device array between sentinel bytes"""
-
-    def __init__(self, torch, a=None, nbytes=None):
-        if a is None:
-            a = np.zeros(nbytes, np.uint8)
-        a = np.ascontiguousarray(a)
-        self.raw = torch.full((a.nbytes + 2 * GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-        self.n, self.shape, self.dtype = a.nbytes, a.shape, a.dtype
-        self.raw[GUARD:GUARD + self.n].copy_(torch.as_tensor(a.view(np.uint8).reshape(-1)))
-        self.ptr = self.raw.data_ptr() + GUARD
-
-    def get(self, name):
-        h = self.raw.cpu().numpy()
-        assert (h[:GUARD] == 0xA5).all() and (h[GUARD + self.n:] == 0xA5).all(), "sentinel bytes around %s were overwritten" % name
-        return h[GUARD:GUARD + self.n].view(self.dtype).reshape(self.shape).copy()
 
 
 _dev = {}

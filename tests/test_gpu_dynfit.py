@@ -22,10 +22,10 @@ import pytest
 
 import dynfit_ref as fr
 import dynplan_ref as dr
+from side_cases import Guarded, same_bits
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256
 SEED = 0x5EED0123456789AB
 KEYS = fr.GRAD_KEYS
 # "it learns": |mean of the last ten losses, float32 numpy - float64| of fit64 measured on the CPU for this very case is 3.05e-7
@@ -44,27 +44,6 @@ def torch():
 def buf(torch):
     x, d = fr.buffer()
     return torch.as_tensor(x).cuda().contiguous(), torch.as_tensor(d).cuda().contiguous()
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-class Guarded:
-    """a device array between sentinel bytes"""
-
-    def __init__(self, torch, a):
-        a = np.ascontiguousarray(a)
-        self.raw = torch.full((a.nbytes + 2 * GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-        self.n, self.shape, self.dtype = a.nbytes, a.shape, a.dtype
-        self.raw[GUARD:GUARD + self.n].copy_(torch.as_tensor(a.view(np.uint8).reshape(-1)))
-        self.ptr = self.raw.data_ptr() + GUARD
-
-    def get(self, name):
-        h = self.raw.cpu().numpy()
-        assert (h[:GUARD] == 0xA5).all() and (h[GUARD + self.n:] == 0xA5).all(), "sentinel bytes around %s were overwritten" % name
-        return h[GUARD:GUARD + self.n].view(self.dtype).reshape(self.shape).copy()
 
 
 def run(torch, W, M, V, buf, iters, batch, lr=1e-2, t0=0, seed=SEED, k=3, size=fr.SIZE, indices=None, want_indices=False, want_grads=False,

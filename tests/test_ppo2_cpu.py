@@ -1,5 +1,5 @@
 """-m "not gpu": everything of the PPO2 update on the device that needs no device.  include/quadsim_ppo.h is plain C99 and every
-symbol it declares is exported by libquadsim_ppo.so; the TRAIN table of quadsim_amd._lib matches the header; every refusal the
+symbol it declares is exported by libquadsim_ppo.so; the entry of quadsim_amd._lib.SIDE matches the header; every refusal the
 header promises happens before anything is launched, and check_ppo2_args mirrors it; tests/ppo2_matrix.py has exactly one row per
 kernel of the new code object, none uses scratch or spills; tests/ppo2_ref.py is checked against torch's float64 autograd of the
 loss as the reference writes it and against central differences; every fixture of tests/test_gpu_ppo2.py holds the conditions
@@ -7,10 +7,6 @@ under which the derived bounds apply, with no row left out; and the host logic (
 bookkeeping, save_npz) does what it says."""
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,10 +14,9 @@ import pytest
 import kernel_notes
 import ppo2_matrix
 import ppo2_ref as pr
-import test_call_path_cpu as cp
+import side_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "quadsim_ppo.h")
 
 
 @pytest.fixture(scope="module")
@@ -33,40 +28,23 @@ def lib():
 
 @pytest.fixture(scope="module")
 def notes(tmp_path_factory):
-    from quadsim_amd import _lib
-    _lib.build_library()
-    co = kernel_notes.code_object(tmp_path_factory.mktemp("isa_ppo2"), so=_lib.PPO_LIB_PATH)
-    return kernel_notes.kernel_notes(co, kernel_notes.FIELDS + ("sgpr_spill_count",))
+    return side_cases.code_object_notes("ppo", tmp_path_factory)
 
 
 # ---------------------------------------------------------------------------------------------------- the header and the ABI
-def _declared():
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(qsp_\w+)\s*\(", text)))
+def test_every_declared_symbol_is_exported(lib):
+    side_cases.check_exports("ppo", lib, ["qsp_auto_slices", "qsp_last_error", "qsp_update", "qsp_version", "qsp_workspace_bytes"])
 
 
-def test_every_declared_symbol_is_exported_and_lib_knows_the_sixth_path(lib):
+def test_no_other_library_holds_its_kernels(lib):
+    side_cases.check_no_foreign_kernels("ppo")
+
+
+def test_table_entry_names_its_own_files(lib):
     import quadsim_amd as qa
     from quadsim_amd import _lib, ppo2
-    names = _declared()
-    assert names == sorted(ppo2.PPO_EXPORTS) == ["qsp_auto_slices", "qsp_last_error", "qsp_update", "qsp_version", "qsp_workspace_bytes"]
-    assert not [n for n in names if not hasattr(lib, n)] and lib.qsp_version() == 1
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.PPO_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert sorted(w for w in out.split() if w.startswith("qsp_")) == names
-    assert os.path.basename(_lib.PPO_LIB_PATH) == "libquadsim_ppo.so" and list(_lib.TRAIN) == ["ppo"] and "ppo" not in _lib.SIDE
-    e = _lib.TRAIN["ppo"]
-    assert sorted(os.path.basename(h) for h in e["headers"]) == ["ppo2_kernels.hpp", "quadsim_device.hpp", "quadsim_ppo.h", "side_host.hpp",
-                                                                 "train_pieces.hpp"]
-    assert [os.path.basename(s) for s in e["sources"]] == ["ppo2.hip"] and all(os.path.exists(h) for h in e["headers"] + e["sources"])
-    assert not [h for h in _lib.HEADERS + [h for s in _lib.SIDE.values() for h in s["headers"]] if "ppo" in os.path.basename(h)]
-    env = dict(os.environ, QUADSIM_PPO_LIB="/somewhere/else.so")
-    got = subprocess.run([sys.executable, "-c", "from quadsim_amd import _lib; print(_lib.PPO_LIB_PATH)"], cwd=ROOT, env=env,
-                         capture_output=True, text=True, check=True).stdout.strip()
-    assert got == "/somewhere/else.so"
-    for so in [_lib.LIB_PATH] + [s["path"] for s in _lib.SIDE.values()]:
-        assert b"k_ppo_" not in open(so, "rb").read(), so
-    blob = open(_lib.PPO_LIB_PATH, "rb").read()
-    assert b"k_dyn_fit" not in blob and b"k_bc_" not in blob
+    assert ppo2.PPO_EXPORTS is _lib.SIDE["ppo"]["exports"]
+    side_cases.check_entry("ppo", ["ppo2_kernels.hpp", "quadsim_device.hpp", "quadsim_ppo.h", "side_host.hpp", "train_pieces.hpp"], "ppo2.hip")
     assert [lib.qsp_auto_slices(b) for b in (-1, 0, 1, 16, 17, 600, 2048, 2049, (1 << 31) - 1)] == [0, 0, 1, 1, 2, 38, 128, 128, 128]
     assert [ppo2.auto_slices(b) for b in (-1, 0, 1, 16, 17, 600, 2048, 2049, (1 << 31) - 1)] == [0, 0, 1, 1, 2, 38, 128, 128, 128]
     for name in ("PPO2", "ppo2_update", "torch_ppo2_update", "minibatch_schedule", "check_ppo2_args", "reset_ppo2_optimizer"):
@@ -75,17 +53,8 @@ def test_every_declared_symbol_is_exported_and_lib_knows_the_sixth_path(lib):
 
 
 def test_train_signature_table_matches_the_header():
-    """the count and kind of every parameter and the kind of every result, as tests/test_call_path_cpu.py holds for SIDE; the
-    structs have the header's sizes"""
+    """the structs have the header's sizes; the prototypes are held by tests/test_call_path_cpu.py, for every side library"""
     from quadsim_amd import _lib
-    e = _lib.TRAIN["ppo"]
-    protos = cp._header_prototypes(e["header"], e["prefix"])
-    assert sorted(protos) == sorted(e["signatures"]) == sorted(e["exports"]) and len(protos) == 5
-    for name, sig in e["signatures"].items():
-        args, result = sig if isinstance(sig, tuple) else (sig, C.c_int)
-        assert (cp._ctype_kind(result), [cp._ctype_kind(t) for t in args]) == protos[name], name
-        assert _lib.SIDE_POINTERS[name] == tuple(i for i, k in enumerate(protos[name][1]) if k == "ptr"), name
-    assert protos["qsp_last_error"] == ("ptr", []) and protos["qsp_version"] == ("int32", [])
     assert C.sizeof(_lib.QspNet) == 8 + 39 * 8 and C.sizeof(_lib.QspBatch) == 16 + 5 * 8 and C.sizeof(_lib.QspHyper) == 8 + 9 * 8
 
 
@@ -215,17 +184,7 @@ int main(void)
 def test_header_is_c99_and_every_refusal_launches_nothing(lib, tmp_path):
     """a plain C program, -std=c99 -Wall -Werror, linked against the new library alone.  Every call it makes is one the library
     refuses, with host pointers it would never dereference: each returns before anything is launched"""
-    assert shutil.which("gcc") is not None
-    src = tmp_path / "ppo2_caller.c"
-    src.write_text(C_CALLER)
-    exe = str(tmp_path / "ppo2_caller")
-    libdir = os.path.join(ROOT, "quadsim_amd", "csrc")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + libdir,
-                           "-lquadsim_ppo", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.split() == ["ALL-REFUSED", str(len(_declared()))]
+    side_cases.run_c_caller("ppo", C_CALLER, tmp_path)
 
 
 GOOD = dict(n=300, steps=100, batch=60, slices=0)
@@ -274,29 +233,12 @@ def test_update_refuses_squashed_and_host_policies_before_the_library_is_touched
 
 # ---------------------------------------------------------------------------------------------------- the census
 def test_rows_are_exactly_the_kernels_of_the_code_object_without_scratch(notes):
-    keys = [r["kernel"] for r in ppo2_matrix.ROWS]
-    assert len(keys) == len(set(keys)) == len(notes)
-    got = {}
-    for sym, f in notes.items():
-        m = re.match(r"^_ZN3qsp(\d+)(k_ppo_\w+?)E", sym)
-        assert m and int(m.group(1)) == len(m.group(2)), "a kernel outside namespace qsp, or a template: %s" % sym
-        got[m.group(2)] = f
-    assert kernel_notes.base_names(notes) == set(ppo2_matrix.KERNELS) == set(keys) == set(got)
-    for r in ppo2_matrix.ROWS:
-        f = got[r["kernel"]]
-        assert f["private_segment_fixed_size"] == 0 and f["vgpr_spill_count"] == 0 and f["sgpr_spill_count"] == 0, (r["kernel"], f)
-        assert f["group_segment_fixed_size"] <= 160 * 1024 and f["max_flat_workgroup_size"] == r["block"], (r["kernel"], f)
-        print("ppo2 notes %s %s" % (r["kernel"], f))
-    assert got["k_ppo_grad"]["vgpr_count"] < 230                   # Adam's moments do not live in it, unlike k_bc_fit
+    got = side_cases.check_census(notes, ppo2_matrix, lambda n: kernel_notes.instantiations_with_types(n, ppo2_matrix.KERNELS, namespace="qsp"), "ppo2")
+    assert got[("k_ppo_grad",)]["vgpr_count"] < 230                   # Adam's moments do not live in it, unlike k_bc_fit
 
 
 def test_rows_name_existing_gpu_tests():
-    files = sorted({r["test"].split("::")[0] for r in ppo2_matrix.ROWS})
-    out = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + files, cwd=ROOT,
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    ids = set(out.stdout.split())
-    assert not [r["test"] for r in ppo2_matrix.ROWS if r["test"] not in ids]
+    side_cases.check_rows_name_gpu_tests(ppo2_matrix)
 
 
 # ---------------------------------------------------------------------------------------------------- the reference itself

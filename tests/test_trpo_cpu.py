@@ -1,5 +1,5 @@
 """-m "not gpu": everything of TRPO on the device that needs no device.  include/quadsim_trpo.h is plain C99 and every symbol it
-declares is exported by libquadsim_trpo.so; the table entry of _lib.TRUST matches the header's prototypes; every refusal the header
+declares is exported by libquadsim_trpo.so; the table entry of _lib.SIDE matches the header's prototypes; every refusal the header
 promises happens before anything is launched, and check_trpo_args mirrors it; tests/trpo_matrix.py has exactly one row per kernel
 of the new code object, none uses scratch or spills a vector register and each fits the compute unit's LDS; tests/trpo_ref.py is
 checked against torch's float64 autograd, which it shares no code with (the Fisher-vector product against double backprop of the
@@ -8,20 +8,17 @@ every decision of the float64 reference sits more than ten bounds from its thres
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import kernel_notes
 import ppo2_ref as pr
+import side_cases
 import trpo_matrix
 import trpo_ref as tr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "quadsim_trpo.h")
 
 
 @pytest.fixture(scope="module")
@@ -33,60 +30,34 @@ def lib():
 
 @pytest.fixture(scope="module")
 def notes(tmp_path_factory):
-    from quadsim_amd import _lib
-    _lib.build_library()
-    co = kernel_notes.code_object(tmp_path_factory.mktemp("isa_trpo"), so=_lib.TRPO_LIB_PATH)
-    return kernel_notes.kernel_notes(co, kernel_notes.FIELDS)
+    return side_cases.code_object_notes("trpo", tmp_path_factory)
 
 
 # ---------------------------------------------------------------------------------------------------- the header and the ABI
-def test_every_declared_symbol_is_exported_and_lib_knows_the_ninth_path(lib):
+def test_every_declared_symbol_is_exported(lib):
+    side_cases.check_exports("trpo", lib, ["qst_auto_slices", "qst_last_error", "qst_policy_step", "qst_version", "qst_vf_fit", "qst_workspace_bytes"])
+
+
+def test_table_entry_names_its_own_files():
     import quadsim_amd as qa
     from quadsim_amd import _lib, trpo
-    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(qst_\w+)\s*\(", text)))
-    assert names == sorted(trpo.TRPO_EXPORTS) == ["qst_auto_slices", "qst_last_error", "qst_policy_step", "qst_version", "qst_vf_fit",
-                                                  "qst_workspace_bytes"]
-    assert not [n for n in names if not hasattr(lib, n)] and lib.qst_version() == 1
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.TRPO_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert sorted(w for w in out.split() if w.startswith("qst_")) == names
-    # the fifth table, before OFFPOLICY, and the four that existing tests pin
-    assert list(_lib.TRUST) == ["trpo"] and _lib.TABLES == (_lib.SIDE, _lib.TRAIN, _lib.IMITATE, _lib.TRUST, _lib.OFFPOLICY)
-    assert list(_lib.OFFPOLICY) == ["ddpg"] and list(_lib.IMITATE) == ["gail"] and list(_lib.TRAIN) == ["ppo"]
-    e = _lib.TRUST["trpo"]
-    assert _lib._entry("trpo") is e and os.path.basename(_lib.TRPO_LIB_PATH) == "libquadsim_trpo.so" == e["file"]
-    assert sorted(os.path.basename(h) for h in e["headers"]) == ["quadsim_device.hpp", "quadsim_trpo.h", "side_host.hpp", "train_pieces.hpp",
-                                                                  "trpo_kernels.hpp"]
-    assert [os.path.basename(s) for s in e["sources"]] == ["trpo.hip"] and all(os.path.exists(h) for h in e["headers"] + e["sources"])
-    assert all(name in _lib.SIDE_POINTERS for name in e["signatures"])
-    others = [o for t in _lib.TABLES for k, o in t.items() if k != "trpo"]
-    assert len(others) == 7
-    assert not [h for h in _lib.HEADERS + [h for o in others for h in o["headers"] + o["sources"]] if "trpo" in os.path.basename(h)]
-    env = dict(os.environ, QUADSIM_TRPO_LIB="/somewhere/else.so")
-    got = subprocess.run([sys.executable, "-c", "from quadsim_amd import _lib; print(_lib.TRPO_LIB_PATH)"], cwd=ROOT, env=env,
-                         capture_output=True, text=True, check=True).stdout.strip()
-    assert got == "/somewhere/else.so"
-    for so in [_lib.LIB_PATH] + [o["path"] for o in others]:
-        assert b"k_trpo_" not in open(so, "rb").read(), so
-    blob = open(_lib.TRPO_LIB_PATH, "rb").read()
-    assert b"k_trpo_fvp" in blob
-    assert not [w for w in (b"k_dyn_fit", b"k_bc_", b"k_ppo_", b"k_gail_", b"k_ddpg_") if w in blob]
+    assert trpo.TRPO_EXPORTS is _lib.SIDE["trpo"]["exports"]
+    side_cases.check_entry("trpo", ["quadsim_device.hpp", "quadsim_trpo.h", "side_host.hpp", "train_pieces.hpp", "trpo_kernels.hpp"], "trpo.hip")
     for name in ("TRPO", "check_trpo_args", "vf_schedule", "trpo_policy_step", "trpo_vf_fit", "reset_trpo_optimizer", "torch_trpo_policy_step",
                  "torch_trpo_vf_fit"):
         assert getattr(qa, name) is getattr(trpo, name) and name in qa.__all__
     assert trpo.TRPO_PARAMS == tr.P == 18696 and trpo.STAT_NAMES == tr.STAT_NAMES
 
 
-def test_table_entry_matches_the_header(lib):
-    import test_call_path_cpu as cp
+def test_no_other_library_holds_its_kernels(lib):
     from quadsim_amd import _lib
-    e = _lib.TRUST["trpo"]
-    protos = cp._header_prototypes(e["header"], e["prefix"])
-    assert sorted(protos) == sorted(e["signatures"]) == sorted(e["exports"]) and len(protos) == 6
-    for name, sig in e["signatures"].items():
-        args, result = sig if isinstance(sig, tuple) else (sig, C.c_int)
-        assert (cp._ctype_kind(result), [cp._ctype_kind(t) for t in args]) == protos[name], name
-    assert protos["qst_last_error"] == ("ptr", []) and protos["qst_version"] == ("int32", [])
+    side_cases.check_no_foreign_kernels("trpo")
+    assert b"k_trpo_fvp" in open(_lib.SIDE["trpo"]["path"], "rb").read()
+
+
+def test_table_entry_matches_the_header(lib):
+    """the structs, the workspace and the slices; the prototypes are held by tests/test_call_path_cpu.py, for every side library"""
+    from quadsim_amd import _lib
     assert C.sizeof(_lib.QstNet) == 8 + 39 * 8 and C.sizeof(_lib.QstBatch) == 16 + 4 * 8 and C.sizeof(_lib.QstHyper) == 16 + 4 * 8
     assert C.sizeof(_lib.QstTrace) == 8 + 6 * 8
     # the workspace: 4 + 2 slices doubles, 4 ints, 4 floats, seven vectors, the old means and neglogp, the slices' partials
@@ -216,17 +187,7 @@ int main(void)
 def test_header_is_c99_and_every_refusal_launches_nothing(lib, tmp_path):
     """a plain C program, -std=c99 -Wall -Werror, linked against the new library alone.  Every call it makes is one the library
     refuses, with host pointers it would never dereference: each returns before anything is launched"""
-    assert shutil.which("gcc") is not None
-    src = tmp_path / "trpo_caller.c"
-    src.write_text(C_CALLER)
-    exe = str(tmp_path / "trpo_caller")
-    libdir = os.path.join(ROOT, "quadsim_amd", "csrc")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + libdir,
-                           "-lquadsim_trpo", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib",
-                           "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert out.stdout.split() == ["ALL-REFUSED", "6"]
+    side_cases.run_c_caller("trpo", C_CALLER, tmp_path)
 
 
 def test_check_args_mirror_the_library():
@@ -249,27 +210,14 @@ def test_check_args_mirror_the_library():
 
 # ---------------------------------------------------------------------------------------------------- the code object
 def test_matrix_rows_are_the_kernels_of_the_code_object(notes):
-    keys = [r["key"] for r in trpo_matrix.ROWS]
-    assert len(keys) == len(set(keys)) == len(notes) == 10
-    assert kernel_notes.base_names(notes) == set(trpo_matrix.KERNELS)
-    by_name = {}
-    for sym, fl in notes.items():
-        (name,) = [k for k in trpo_matrix.KERNELS if re.search(r"\d%sE" % k, sym)]
-        by_name[name] = fl
-    for r in trpo_matrix.ROWS:
-        fl = by_name[r["kernel"]]
-        assert fl["private_segment_fixed_size"] == 0 and fl["vgpr_spill_count"] == 0, (r["id"], fl)
-        assert fl["group_segment_fixed_size"] <= 160 * 1024 and fl["max_flat_workgroup_size"] == r["block"], (r["id"], fl)
-        print("trpo notes %s %s" % (r["id"], fl))
+    """k_trpo_vf_fit, which keeps Adam's state in registers, spills scalar registers"""
+    assert len(notes) == 10
+    side_cases.check_census(notes, trpo_matrix, lambda n: kernel_notes.instantiations_with_types(n, trpo_matrix.KERNELS, namespace="qst"), "trpo",
+                            sgpr_spills=("k_trpo_vf_fit",))
 
 
 def test_rows_name_existing_gpu_tests():
-    files = sorted({r["test"].split("::")[0] for r in trpo_matrix.ROWS})
-    out = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + files, cwd=ROOT,
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
-    ids = set(out.stdout.split())
-    assert not [r["test"] for r in trpo_matrix.ROWS if r["test"] not in ids]
+    side_cases.check_rows_name_gpu_tests(trpo_matrix)
 
 
 # ---------------------------------------------------------------------------------------------------- the reference against autograd
