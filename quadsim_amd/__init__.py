@@ -23,6 +23,7 @@ from .gail import GAIL, Discriminator, GailRunner, check_gail_args, discriminato
 from .trpo import (TRPO, check_trpo_args, reset_trpo_optimizer, torch_trpo_policy_step, torch_trpo_vf_fit, trpo_policy_step, trpo_vf_fit,
                    vf_schedule)
 from .ddpg import DDPG, DDPGPolicy, OUNoise, ReplayBuffer, check_ddpg_args, ddpg_update, replay_schedule, torch_ddpg_update
+from .td3 import TD3, NormalActionNoise, TD3Policy, check_td3_args, reset_td3_optimizer, td3_update, torch_td3_update
 
 __all__ = ["VecDockingEnv", "DockingEnv", "MovingDockingEnv", "ImitatingDockingEnv", "HoveringEnv", "Drone", "controller", "make", "register_gym_ids",
            "shard_range", "build_library", "QuadsimError", "C3_INIT_RANGE", "drone_step_batch", "ctrl_batch",
@@ -34,6 +35,7 @@ __all__ = ["VecDockingEnv", "DockingEnv", "MovingDockingEnv", "ImitatingDockingE
            "GAIL", "Discriminator", "GailRunner", "discriminator_schedule", "torch_discriminator_fit", "check_gail_args",
            "DDPG", "DDPGPolicy", "ReplayBuffer", "OUNoise", "replay_schedule", "ddpg_update", "torch_ddpg_update", "check_ddpg_args",
            "TRPO", "check_trpo_args", "vf_schedule", "trpo_policy_step", "trpo_vf_fit", "reset_trpo_optimizer", "torch_trpo_policy_step",
-           "torch_trpo_vf_fit"]
+           "torch_trpo_vf_fit",
+           "TD3", "TD3Policy", "NormalActionNoise", "td3_update", "torch_td3_update", "check_td3_args", "reset_td3_optimizer"]
 
 register_gym_ids()

@@ -1,5 +1,6 @@
 """ctypes binding of libquadsim_hip.so (the C ABI declared in include/quadsim.h), and the table (SIDE), build, loader and call
-helper of the eight side libraries that dynplan.py, bc.py, ppo2.py, gail.py, trpo.py and ddpg.py wrap.
+helper of the eight side libraries that dynplan.py, bc.py, ppo2.py, gail.py, trpo.py and ddpg.py wrap, and of the ninth that came
+after them (SIDE_MORE: td3.py's).
 
 There is deliberately no fallback of any kind: if the HIP library is missing or
 no MI355X is visible, loading / qs_create raise.  Nothing here imports oracle/.
@@ -15,7 +16,7 @@ LIB_PATH = os.environ.get("QUADSIM_HIP_LIB") or os.path.join(CSRC, "libquadsim_h
 SOURCES = [os.path.join(CSRC, "quadsim_hip.hip")]
 # every fragment of the one translation unit is a rebuild dependency, bar those of the side libraries (SIDE below)
 HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith(
-    ("dynplan_", "dynmppi_", "dynfit_", "bcfit_", "ppo2_", "gail_", "ddpg_", "trpo_", "train_", "side_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
+    ("dynplan_", "dynmppi_", "dynfit_", "bcfit_", "ppo2_", "gail_", "ddpg_", "trpo_", "td3_", "train_", "side_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
 
 QS_OK = 0
 KIND_V0, KIND_V2, KIND_V1, KIND_HOVER = 0, 1, 2, 3
@@ -203,6 +204,20 @@ class QsddHyper(C.Structure):
         (k, C.c_double) for k in ("gamma", "tau", "actor_lr", "critic_lr", "obs_clip", "beta1", "beta2", "eps")]
 
 
+class QstdNets(C.Structure):                   # include/quadsim_td3.h
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("w", C.c_void_p * 36), ("m", C.c_void_p * 18), ("v", C.c_void_p * 18)]
+
+
+class QstdReplay(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("n", C.c_int64)] + [
+        (k, C.c_void_p) for k in ("obs0", "act", "rew", "obs1", "done")]
+
+
+class QstdHyper(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("policy_delay", C.c_int32)] + [
+        (k, C.c_double) for k in ("gamma", "tau", "actor_lr", "critic_lr", "target_policy_noise", "target_noise_clip", "beta1", "beta2", "eps")]
+
+
 f64, psize, psix = C.c_double, C.POINTER(C.c_size_t), C.POINTER(vp * 6)
 # The eight libraries beside the main one, each its own translation unit, .so and code object, by short name, in build order.
 # They share at the source level only: device fragments (*_kernels.hpp, dynplan_image.hpp, train_pieces.hpp, quadsim_device.hpp)
@@ -291,7 +306,29 @@ SIDE = {
                      "qsdd_update": [C.POINTER(QsddNets), C.POINTER(QsddReplay), vp, vp, i32, i32, C.POINTER(QsddHyper), i64, vp, u64, vp,
                                      C.POINTER(vp * 12), vp]}),
 }
-for _e in SIDE.values():
+# The libraries that came after the eight: a second table of the same shape.  Everything below that takes a key looks it up in
+# either (side_entry); the tests of the eight hold SIDE itself to their list.
+SIDE_MORE = {
+    # the TD3 update (td3.py): the six nets' own tensors; the tower pieces and the streamed nets of train_pieces.hpp, q_tanh, the
+    # Philox counter and the normals of the main library
+    "td3": dict(env="QUADSIM_TD3_LIB", file="libquadsim_td3.so", source="td3.hip", header="quadsim_td3.h", prefix="qstd_", kernels=b"k_td3_",
+                fragments=("td3_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
+                signatures={
+                    "qstd_version": [],
+                    "qstd_last_error": ([], C.c_char_p),
+                    "qstd_workspace_bytes": [psize],
+                    "qstd_update": [C.POINTER(QstdNets), C.POINTER(QstdReplay), vp, vp, i32, i32, C.POINTER(QstdHyper), i64, i64, vp, u64, vp,
+                                    vp, u64, vp, C.POINTER(vp * 18), vp]}),
+}
+ALL_SIDE = dict(SIDE, **SIDE_MORE)               # the same entry objects, in build order
+
+
+def side_entry(key):
+    """the table entry of the side library `key`, whichever table holds it"""
+    return ALL_SIDE[key]
+
+
+for _e in ALL_SIDE.values():
     _e["path"] = os.environ.get(_e["env"]) or os.path.join(CSRC, _e["file"])
     _e["sources"] = [os.path.join(CSRC, _e["source"])]
     _e["headers"] = [os.path.join(CSRC, h) for h in _e["fragments"]] + [os.path.join(HERE, "..", "include", _e["header"])]
@@ -299,7 +336,7 @@ for _e in SIDE.values():
 # the positions of every entry point's pointer parameters: side_call sends those through as_arg and leaves the scalars to the
 # argtypes (as_arg on a scalar costs 0.3 us, and a plan has a dozen of them)
 SIDE_POINTERS = {name: tuple(i for i, t in enumerate(sig[0] if isinstance(sig, tuple) else sig) if t is vp or issubclass(t, C._Pointer))
-                 for _e in SIDE.values() for name, sig in _e["signatures"].items()}
+                 for _e in ALL_SIDE.values() for name, sig in _e["signatures"].items()}
 
 
 class QuadsimError(RuntimeError):
@@ -336,9 +373,9 @@ def build_one_library(sources, deps, out, link=(), force=False, verbose=False):
 
 
 def build_library(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all nine libraries, returns the main one's
+    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all ten libraries, returns the main one's
     path."""
-    for e in SIDE.values():
+    for e in ALL_SIDE.values():
         build_one_library(e["sources"], e["headers"], e["path"], (), force, verbose)
     return build_one_library(SOURCES, HEADERS, LIB_PATH, ["-lhsa-runtime64"], force, verbose)
 
@@ -417,10 +454,10 @@ _side = {}
 
 
 def side_load(key):
-    """dlopen the side library `key` of SIDE, once; raises QuadsimError if it has not been built (there is no fallback)"""
+    """dlopen the side library `key` of SIDE or SIDE_MORE, once; raises QuadsimError if it has not been built (there is no fallback)"""
     lib = _side.get(key)
     if lib is None:
-        e = SIDE[key]
+        e = side_entry(key)
         if not os.path.exists(e["path"]):
             raise QuadsimError("%s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % e["path"])
         import torch  # noqa: F401  (its HIP runtime must be the resident one: see load)
@@ -434,7 +471,7 @@ def side_load(key):
 
 def side_check(key, rc, what):
     if rc != 0:
-        msg = getattr(side_load(key), SIDE[key]["prefix"] + "last_error")().decode("utf-8", "replace")
+        msg = getattr(side_load(key), side_entry(key)["prefix"] + "last_error")().decode("utf-8", "replace")
         raise QuadsimError("%s failed (%d): %s" % (what, rc, msg))
 
 

@@ -69,52 +69,7 @@ struct Layout : TowerImage<B ? kH + 4 : kH + kAct + 8, kH + kAct> {
 };
 constexpr int kLdsFloats = Layout<0>::floats > Layout<1>::floats ? Layout<0>::floats : Layout<1>::floats;
 
-// Z[u][r] = B[u] + sum_k W[k][u] A[k][r], k ascending: forward_layer's chain with the weights read from memory in the policy's
-// (in, out) layout.  One item = one unit x four rows, unit along the lanes; K is a multiple of 4
-template <bool RELU>
-__device__ __forceinline__ void stream_layer(const float *W, const float *Bv, const float *A, int K, float *Z)
-{
-    const int u = threadIdx.x & (kH - 1), rg = threadIdx.x >> 7;
-    const float b = Bv[u];
-    f32x4 acc = {b, b, b, b};
-    const float *w = W + u, *a = A + 4 * rg;
-    for (int k = 0; k < K; k += 4) {
-        float wk[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) wk[i] = w[(k + i) * kH];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const f32x4 ak = ld4(a + (k + i) * kRP);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[r] = __fmaf_rn(wk[i], ak[r], acc[r]);
-        }
-    }
-    if (RELU) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = acc[r] <= 0.0f ? 0.0f : acc[r];       // forward_layer's select: a NaN stays
-    }
-    st4(Z + u * kRP + 4 * rg, acc);
-}
-
-// the head of a streamed net for thread t < 16 OUTS: output t >> 4 of row t & 15, the same chain
-template <int OUTS>
-__device__ __forceinline__ float stream_head(const float *W, const float *Bv, const float *A)
-{
-    const int o = threadIdx.x >> 4, r = threadIdx.x & (kRows - 1);
-    float acc = Bv[o];
-#pragma unroll 8
-    for (int k = 0; k < kH; ++k) acc = __fmaf_rn(W[k * OUTS + o], A[k * kRP + r], acc);
-    return acc;
-}
-
-// q_tanh bounds its exponent with fminf, which drops a NaN operand: tanh(NaN) would be +-1 and a diverged actor would go on as a
-// saturated one.  Here a NaN stays; every other value is q_tanh's, bit for bit
-__device__ __forceinline__ float tanh_keep_nan(float x)
-{
-    float unused;
-    const float a = qs::q_tanh(x, unused);
-    return x != x ? x : a;
-}
+// (stream_layer, stream_head and tanh_keep_nan are train_pieces.hpp's: the TD3 kernels stream their nets the same way)
 
 // (selects, not fminf(fmaxf()): those would turn a NaN observation into -clip; an infinity is clamped as any other value)
 __device__ __forceinline__ float clamp_obs(float v, float clip) { return v < -clip ? -clip : v > clip ? clip : v; }

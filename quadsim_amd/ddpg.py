@@ -375,31 +375,42 @@ class DDPG:
         """-> a list of one dict per logged cycle: the cycle, `total_timesteps` so far, the four statistics (DDPG_STAT_NAMES, the
         mean over the cycle's updates), the mean reward of the cycle's env steps and `fps`"""
         fn = ddpg_update if self.update == "hip" else torch_ddpg_update
-        env, n = self.env, int(self.env.num_envs)
-        if self.obs is None:
-            self.obs = env.reset().clone()
-        logs, cycle, since, rew_sum, rew_n, t_start = [], 0, 0, None, 0, time.time()
-        target = self.num_timesteps + int(total_timesteps)
-        while self.num_timesteps < target:
-            a = self.act(self.obs)
-            obs1, rew, done, _ = env.step(a)
-            self.replay.add(self.obs, a, rew, obs1, done)
-            if self.action_noise is not None:
-                self.action_noise.reset(done)
-            self.obs = obs1.clone()
-            self.num_timesteps += n
-            since += 1
-            rew_sum = rew.double().sum() if rew_sum is None else rew_sum + rew.double().sum()
-            rew_n += n
-            if since >= self.nb_rollout_steps:
-                cycle += 1
-                indices = replay_schedule(self.replay.size, self.nb_train_steps, self.batch_size, self.generator)
-                out = fn(self.policy, self.replay, indices, **self.hyper)
-                if log_interval and (cycle % log_interval == 0 or cycle == 1):
-                    t_now = time.time()
-                    log = {"cycle": cycle, "total_timesteps": self.num_timesteps, "reward_mean": float(rew_sum) / rew_n,
-                           "fps": int(since * n / max(t_now - t_start, 1e-9))}
-                    log.update(zip(DDPG_STAT_NAMES, out["stats"].double().mean(0).tolist()))
-                    logs.append(log)
-                since, rew_sum, rew_n, t_start = 0, None, 0, time.time()
-        return logs
+
+        def train():
+            indices = replay_schedule(self.replay.size, self.nb_train_steps, self.batch_size, self.generator)
+            return fn(self.policy, self.replay, indices, **self.hyper)["stats"]
+        return collect_and_train(self, total_timesteps, log_interval, self.nb_rollout_steps, train, DDPG_STAT_NAMES)
+
+
+def collect_and_train(agent, total_timesteps, log_interval, rollout_steps, train, stat_names):
+    """the per-step collection loop of the off-policy trainers (DDPG here, TD3 in td3.py).  `agent` has env, replay, action_noise,
+    obs, num_timesteps and act(obs).  Per env step: ``agent.act``, ``env.step``, ``replay.add`` of the N transitions, the noise
+    reset where done.  After every `rollout_steps` calls of ``env.step`` one call of `train()` -> the cycle's statistics [updates,
+    len(stat_names)] (None: nothing was trained, the cycle is not logged) -> the list of logged cycles"""
+    env, n = agent.env, int(agent.env.num_envs)
+    if agent.obs is None:
+        agent.obs = env.reset().clone()
+    logs, cycle, since, rew_sum, rew_n, t_start = [], 0, 0, None, 0, time.time()
+    target = agent.num_timesteps + int(total_timesteps)
+    while agent.num_timesteps < target:
+        a = agent.act(agent.obs)
+        obs1, rew, done, _ = env.step(a)
+        agent.replay.add(agent.obs, a, rew, obs1, done)
+        if agent.action_noise is not None:
+            agent.action_noise.reset(done)
+        agent.obs = obs1.clone()
+        agent.num_timesteps += n
+        since += 1
+        rew_sum = rew.double().sum() if rew_sum is None else rew_sum + rew.double().sum()
+        rew_n += n
+        if since >= rollout_steps:
+            cycle += 1
+            stats = train()
+            if stats is not None and log_interval and (cycle % log_interval == 0 or cycle == 1):
+                t_now = time.time()
+                log = {"cycle": cycle, "total_timesteps": agent.num_timesteps, "reward_mean": float(rew_sum) / rew_n,
+                       "fps": int(since * n / max(t_now - t_start, 1e-9))}
+                log.update(zip(stat_names, stats.double().mean(0).tolist()))
+                logs.append(log)
+            since, rew_sum, rew_n, t_start = 0, None, 0, time.time()
+    return logs
