@@ -65,6 +65,30 @@
  * loss of the weights BEFORE step s.  A call of a + b steps equals the call of a steps followed by the call of b steps with
  * t0 + a, bit for bit.  grads (nullable): a HOST array of six device pointers that receive the gradients of the LAST step.
  *
+ * NON-FINITE VALUES (NaN, +inf, -inf in a row, a weight or a moment).  The five rules of quadsim_ddpg.h apply (statistics; state;
+ * no invention; unread data; no faults).  For qst_policy_step the arbiter is float64 torch autograd of steps 1 to 7 (torch.relu,
+ * the surrogate as mean(A_i exp(nlp_old_i - neglogp_i)) + entcoeff entropy, F v as double backprop of the mean KL, SB2's cg and
+ * line search), what update="torch" of the package computes:
+ * 1. Statistics.  A statistic is non-finite exactly when the arbiter's is, with ONE documented deviation: surr_before is the
+ *    formula of step 2, sum A_i / n + entcoeff entropy, which does not read neglogp.  It is finite whenever the advantages, logstd
+ *    and entcoeff entropy are finite, also where a row's neglogp is not (a NaN observation, action or policy weight), where
+ *    autograd's mean(A_i exp(nlp_old_i - neglogp_i)) is NaN.  surr_after of a rejected step is surr_before, and the deviation
+ *    applies to it in the same way.  Non-finite returns or values make every advantage, and with it surr_before, NaN on both.
+ * 2. State.  A step with a non-finite g, x, shs or lm is a REJECTED step.  CG runs all cg_iters products (rdotr < residual_tol is
+ *    false for a NaN), the cg_iters + 1-th product and every candidate are evaluated and, where a trace is given, written to every
+ *    row of it; accepted = -1, kl_after = 0, entropy is the old policy's, cg_iters_run = cg_iters.  Theta, the value tower and all
+ *    moments keep their bits; g is non-finite in at least one element exactly when the arbiter's is.  Which statistics and which
+ *    elements of g are non-finite does not depend on the slices, and no bit of a result on the trace being requested.
+ * 3. No invention.  No clamp stands between the data and the policy: an infinity is never turned into a finite value, and no
+ *    statistic other than surr_before and surr_after is finite where the arbiter's is not.
+ * 4. Unread data.  The policy step does not read slots 6 .. 11, any moment, or rows at and beyond n: a non-finite value there
+ *    changes no bit of any result.  The workspace's contents at entry mean nothing: the flags (skipped, CG converged, accepted)
+ *    and scalars a previous call left, of whatever kind, change no bit of the next call.
+ * 5. No faults.  No loaded float becomes an address, an index or a loop bound.
+ * qst_vf_fit follows the rules of quadsim_bc.h's NON-FINITE VALUES paragraph as they stand (the loss; the value tower as a whole;
+ * Adam per element; unread rows and the steps before the first that reads a non-finite value; no faults).  The policy's slots
+ * 0 .. 5 and 12 and the moments of those slots are not read: a non-finite value there changes no bit, and stays what it was.
+ *
  * ---- limits ---------------------------------------------------------------------------------------------------------
  * 1 <= n < 2^31, 0 <= slices <= 1024, 1 <= cg_iters <= 64, 1 <= backtracks <= 32, fvp_stride >= 1; max_kl > 0 and every
  * hyper-parameter finite, cg_damping, residual_tol >= 0; 1 <= batch <= 256, 1 <= steps <= 4096, t0 >= 0 and t0 + steps < 2^31,

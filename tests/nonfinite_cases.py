@@ -2,8 +2,9 @@
 references' own run of a case.  A helper module, not a test; numpy only.
 
 A case puts ONE non-finite value (NaN, +inf or -inf) into one element of one tensor a training step is given: an input array, a
-weight or a moment.  The contract (the NON-FINITE VALUES paragraph of include/quadsim_ppo.h, include/quadsim_ddpg.h,
-include/quadsim_dyn_fit.h, include/quadsim_bc.h and include/quadsim_gail.h) says what must follow; tests/test_nonfinite_cpu.py
+weight or a moment (for TD3 also the caller's noise).  The contract (the NON-FINITE VALUES paragraph of include/quadsim_ppo.h,
+include/quadsim_ddpg.h, include/quadsim_dyn_fit.h, include/quadsim_bc.h, include/quadsim_gail.h, include/quadsim_td3.h and
+include/quadsim_trpo.h) says what must follow; tests/test_nonfinite_cpu.py
 anchors the references to float64 torch autograd at every case and holds the conditions of the tables,
 tests/test_gpu_nonfinite.py runs every case on the device.
 
@@ -14,6 +15,9 @@ poison, or where a poisoned moment reaches a statistic only through the weight i
 How a row is poisoned: the data set gets one row more, a copy of the fixture row at the poisoned position of the step's index
 row, and the index row points there instead.  The case's TWIN is the same set-up without the poison (for an infinity that the
 header's clamp bounds: with the clamped value), so the twin of a row case is the fixture's own minibatch.
+
+TRPO's policy step takes the rows 0 .. n-1 and no indices: its cases (TRPO_STEP_CASES, outside LIBRARIES like the reward's) poison
+a row of the roll-out itself, and a poisoned case there is a REJECTED step, not a diverged net.
 
   case["clean"] is None   the step reads the poison: at least one statistic of the call is non-finite
   case["clean"] = reason  the contract says the poison changes nothing: bit for bit the twin's result
@@ -26,6 +30,8 @@ import dynfit_ref as fr
 import dynplan_ref as dr
 import gail_ref as gr
 import ppo2_ref as pr
+import td3_ref as td
+import trpo_ref as tr
 
 NAN, PINF, NINF = float("nan"), float("inf"), float("-inf")
 BATCH = 17
@@ -504,6 +510,281 @@ def gail_reward_reference(S):
         return gr.reward64(F["l"]), F["l"], gr.reward_bound(F["l"], F["E_l"]), F["E_l"]
 
 
+# ---------------------------------------------------------------------------------------------------- TD3
+TD3_HYPER = dict(gamma=td.GAMMA, tau=td.TAU, actor_lr=1e-2, critic_lr=1e-2, policy_delay=td.DELAY, target_policy_noise=td.SIGMA,
+                 target_noise_clip=td.CLIP)
+TD3_DATA = ("obs0", "act", "rew", "obs1", "done")
+BIG = 1.0e30                                       # a finite value that every clamp and the twin minimum treat as they treat an infinity
+_NOISE_CLAMPED = "an infinite normal is clamped to +-CL, as the large finite normal of the twin is"
+_MIN_TAKES_Q2 = "qb < qa takes q2's value in every row, as for the twin's large finite q1"
+_NOT_READ = "a critic-only update does not read the actor"
+
+# A call starts at update t0 (0: step 1 is an actor update, step 2 a critic-only one; the actor steps taken before are
+# ceil(t0 / policy_delay)).  ("noise",): the caller's normal, component `elem` of row slot `pos` of step `step`; the slot's row is a
+# copy of its own with done = rowdone.  twin_value: what the twin holds in the poisoned element; hyper: hyper-parameters of the case;
+# nets: the nets that hold a non-finite weight after the last step
+TD3_CASES = (
+    # ---- every input array the step reads
+    _case("obs0-nan-row3", ("row", "obs0"), 5, NAN),
+    _case("obs0-nan-row16", ("row", "obs0"), 0, NAN, pos=16),
+    _case("act-nan", ("row", "act"), 2, NAN),
+    _case("rew-nan", ("row", "rew"), 0, NAN, pos=16),
+    _case("obs1-nan", ("row", "obs1"), 11, NAN, rowdone=0.0),
+    _case("done-nan", ("row", "done"), 0, NAN),
+    _case("rew-pinf", ("row", "rew"), 0, PINF),
+    _case("act-ninf", ("row", "act"), 0, NINF, pos=16),
+    _case("obs0-nan-step2", ("row", "obs0"), 7, NAN, steps=2, step=1),
+    # ---- the caller's noise
+    _case("noise-nan-live", ("noise",), 2, NAN, rowdone=0.0),
+    _case("noise-nan-live-row16", ("noise",), 0, NAN, pos=16, rowdone=0.0),
+    _case("noise-pinf-sigma0", ("noise",), 1, PINF, rowdone=0.0, hyper=dict(target_policy_noise=0.0)),
+    _case("noise-nan-terminal", ("noise",), 2, NAN, rowdone=1.0, clean=_TERMINAL),
+    _case("noise-pinf-clamped", ("noise",), 3, PINF, rowdone=0.0, twin_value=BIG, clean=_NOISE_CLAMPED),
+    _case("noise-ninf-clamped-row16", ("noise",), 0, NINF, pos=16, rowdone=0.0, twin_value=-BIG, clean=_NOISE_CLAMPED),
+    # ---- weights: layer 0, the last layer; a first and a second moment (they reach a statistic through the weight, in step 2: the
+    # critics', since step 2 is a critic-only update)
+    _case("actor-w0-nan", ("w", "actor", "w0"), 5 * 128 + 17, NAN),
+    _case("q1-w2-nan", ("w", "q1", "w2"), 40, NAN),
+    _case("q2-w0-nan", ("w", "q2", "w0"), 13 * 128 + 2, NAN),
+    _case("q1-w0-pinf", ("w", "q1", "w0"), 3 * 128 + 2, PINF),
+    _case("q1-m-w1-nan", ("m", "q1", "w1"), 1000, NAN, steps=2),
+    _case("q2-v-w0-nan", ("v", "q2", "w0"), 300, NAN, steps=2),
+    # ---- a target net's weight, every row live
+    _case("q1-target-w2-nan-live", ("w", "q1_target", "w2"), 3, NAN, done=0.0),
+    _case("q2-target-w1-nan-live", ("w", "q2_target", "w1"), 5 * 128 + 9, NAN, done=0.0),
+    _case("actor-target-w0-nan-live", ("w", "actor_target", "w0"), 9, NAN, done=0.0),
+    _case("q1-target-b2-ninf-live", ("w", "q1_target", "b2"), 0, NINF, done=0.0),
+    # ---- the schedule, policy_delay = 2
+    _case("actor-w0-nan-critic-then-actor", ("w", "actor", "w0"), 2 * 128 + 40, NAN, steps=2, t0=1,
+          nets=("actor", "actor_target")),
+    _case("q1-w1-nan-actor-update", ("w", "q1", "w1"), 7 * 128 + 3, NAN, nets=("actor", "q1", "actor_target", "q1_target")),
+    _case("q2-w1-nan-actor-update", ("w", "q2", "w1"), 7 * 128 + 3, NAN, nets=("q2", "q2_target")),
+    # (a NaN activation of q1 with finite weights behind it: dq/da's masks hand the term on, the actor's gradient is finite and
+    # NOT zero, as autograd's; the actor and its target stay finite)
+    _case("q1-b0-nan-actor-update", ("w", "q1", "b0"), 2, NAN, nets=("q1", "q1_target")),
+    _case("q1-w0-nan-obs-row-actor-update", ("w", "q1", "w0"), 3 * 128 + 77, NAN, nets=("q1", "q1_target")),
+    # ---- clean by contract
+    _case("actor-w0-nan-critic-only", ("w", "actor", "w0"), 2 * 128 + 40, NAN, t0=1, nets=("actor",), clean=_NOT_READ),
+    _case("q1-target-w2-nan-terminal", ("w", "q1_target", "w2"), 3, NAN, done=1.0, clean=_TERMINAL),
+    _case("q2-target-w1-nan-terminal", ("w", "q2_target", "w1"), 5 * 128 + 9, NAN, done=1.0, clean=_TERMINAL),
+    _case("actor-target-w0-nan-terminal", ("w", "actor_target", "w0"), 9, NAN, done=1.0, clean=_TERMINAL),
+    _case("q1-target-b2-pinf-live", ("w", "q1_target", "b2"), 0, PINF, done=0.0, twin_value=BIG, clean=_MIN_TAKES_Q2),
+    _case("obs1-nan-terminal-row", ("row", "obs1"), 11, NAN, rowdone=1.0, clean=_TERMINAL),
+    _case("unread-row-nan", ("row", "obs0"), 5, NAN, step=-1, clean=_UNREAD),
+    _case("beyond-count-nan", ("row", "rew"), 0, NAN, pos=12, counts=(10,), clean=_BEYOND),
+    _case("beyond-count-step2-nan", ("row", "act"), 1, NAN, pos=16, steps=2, step=1, counts=(17, 16), clean=_BEYOND),
+)
+
+
+def td3_setup(case, twin=False):
+    """-> dict(P, M, V: {net: {key: float32 array}}, rp: the five arrays with one row more, idx [steps,17] int32, counts or None,
+    z [steps,17,4] the caller's normals, t0, actor_t0, hp)"""
+    P = {n: {k: np.array(td.nets()[n][k]) for k in td.KEYS} for n in td.NETS}
+    M0, V0 = td.moments()
+    M = {n: {k: np.array(M0[n][k]) for k in td.KEYS} for n in td.ONLINE}
+    V = {n: {k: np.array(V0[n][k]) for k in td.KEYS} for n in td.ONLINE}
+    rp = [np.concatenate([a, a[:1]]) for a in td.replay()]
+    idx = td.step_indices(BATCH, steps=case["steps"]).copy()
+    z = td.noise(case["steps"], BATCH).copy()
+    hp = dict(TD3_HYPER, **case.get("hyper", {}))
+    new = td.N_ROWS
+    kind = case["target"][0]
+    if kind in ("row", "noise"):
+        src = idx[max(case["step"], 0), case["pos"]]
+        for a in rp:
+            a[new] = a[src]
+        if "rowdone" in case:
+            rp[4][new] = case["rowdone"]
+        if case["step"] >= 0:
+            idx[case["step"], case["pos"]] = new
+    if "done" in case:
+        rp[4][:] = case["done"]
+    value = case.get("twin_value") if twin else case["value"]
+    if value is not None:
+        if kind == "row":
+            _poison(rp[TD3_DATA.index(case["target"][1])][new:new + 1], case["elem"], value)
+        elif kind == "noise":
+            _poison(z[case["step"], case["pos"]], case["elem"], value)
+        else:
+            _poison({"w": P, "m": M, "v": V}[kind][case["target"][1]][case["target"][2]], case["elem"], value)
+    counts = None if case.get("counts") is None else np.asarray(case["counts"], np.int32)
+    t0 = case.get("t0", 0)
+    return dict(P=P, M=M, V=V, rp=tuple(rp), idx=idx, counts=counts, z=z, t0=t0, actor_t0=-(-t0 // hp["policy_delay"]), hp=hp)
+
+
+def td3_reference(S, with_bound=False):
+    """td3_ref's loop (fit64's, kept step by step) over a set-up -> dict(stats [steps,6] float64, gflag [steps,3]: a non-finite
+    gradient element per online net (False where the step takes no actor gradient), nets [steps,6]: a non-finite weight per net
+    after the step; with_bound: first = step 1's (stats, G, Es, E) of step64)"""
+    f, hp = np.float64, S["hp"]
+    P = {n: {k: np.asarray(S["P"][n][k], f).copy() for k in td.KEYS} for n in td.NETS}
+    M = {n: {k: np.asarray(S["M"][n][k], f).copy() for k in td.KEYS} for n in td.ONLINE}
+    V = {n: {k: np.asarray(S["V"][n][k], f).copy() for k in td.KEYS} for n in td.ONLINE}
+    out, taken = dict(stats=[], gflag=[], nets=[]), 0
+    with np.errstate(all="ignore"):
+        for s, rows in enumerate(S["idx"]):
+            rows = rows if S["counts"] is None else rows[:S["counts"][s]]
+            mb, z = tuple(a[rows] for a in S["rp"]), S["z"][s, :len(rows)]
+            act = td.actor_step(S["t0"] + s, hp["policy_delay"])
+            args = (P, mb, z, hp["gamma"], hp["target_policy_noise"], hp["target_noise_clip"])
+            if s == 0 and with_bound:
+                st, G, _, Es, E = td.step64(*args, actor=act, with_bound=True)
+                out["first"] = (st, G, Es, E)
+            else:
+                st, G, _ = td.step64(*args, actor=act)
+            out["stats"].append(st)
+            out["gflag"].append([n in G and has_nonfinite(G[n]) for n in td.ONLINE])
+            for n in (td.ONLINE if act else ("q1", "q2")):
+                t, lr = (S["actor_t0"] + taken + 1, hp["actor_lr"]) if n == "actor" else (S["t0"] + s + 1, hp["critic_lr"])
+                for k in td.KEYS:
+                    P[n][k], M[n][k], V[n][k] = td.adam64(P[n][k], M[n][k], V[n][k], G[n][k], t, lr)
+                    if act:
+                        P[n + "_target"][k] = (1.0 - hp["tau"]) * P[n + "_target"][k] + hp["tau"] * P[n][k]
+            taken += int(act)
+            out["nets"].append([has_nonfinite(P[n]) for n in td.NETS])
+    return {k: (v if k == "first" else np.asarray(v)) for k, v in out.items()}
+
+
+# ---------------------------------------------------------------------------------------------------- TRPO's value fit
+TRPO_VF_LR = 1e-2
+TRPO_KEYS = pr.KEYS_TOWERS                          # the thirteen slots; the fit owns tr.VALUE_KEYS and their moments
+_POLICY_SLOT = "the value fit does not read the policy's slots or their moments"
+
+TRPO_VF_CASES = (
+    _case("obs-nan-row3", ("row", "obs"), 5, NAN),
+    _case("obs-nan-row16", ("row", "obs"), 0, NAN, pos=16),
+    _case("returns-nan", ("row", "returns"), 0, NAN),
+    _case("returns-pinf-row16", ("row", "returns"), 0, PINF, pos=16),
+    _case("obs-ninf", ("row", "obs"), 11, NINF),
+    _case("obs-nan-step2", ("row", "obs"), 7, NAN, steps=2, step=1),
+    _case("wv0-nan", ("w", "wv0"), 5 * 128 + 17, NAN),
+    _case("wv2-nan", ("w", "wv2"), 40, NAN),
+    _case("bv1-pinf", ("w", "bv1"), 9, PINF),
+    _case("m-wv1-nan", ("m", "wv1"), 1000, NAN, steps=2),
+    _case("v-wv0-nan", ("v", "wv0"), 300, NAN, steps=2),
+    _case("unread-row-nan", ("row", "obs"), 5, NAN, step=-1, clean=_UNREAD),
+    _case("policy-w0-nan", ("w", "w0"), 5 * 128 + 17, NAN, clean=_POLICY_SLOT),
+    _case("policy-logstd-nan", ("w", "logstd"), 2, NAN, steps=2, clean=_POLICY_SLOT),
+    _case("policy-m-w1-nan", ("m", "w1"), 1000, NAN, steps=2, clean=_POLICY_SLOT),
+)
+
+
+def trpo_vf_indices(steps):
+    """[steps,17] int32 rows of the roll-out's 301, every step a draw of its own"""
+    return np.stack([np.random.default_rng(500 + s).permutation(tr.N_ROWS)[:BATCH] for s in range(steps)]).astype(np.int32)
+
+
+def trpo_vf_setup(case, twin=False):
+    """-> dict(W, M, V: {the thirteen keys: float32 array} (the moments of the policy's slots are zeros), data: the roll-out's four
+    arrays with one row more, idx [steps,17] int32)"""
+    W = {k: np.array(tr.weights()[k]) for k in TRPO_KEYS}
+    M0, V0 = tr.moments()
+    M, V = ({k: np.array(a[k]) if k in a else np.zeros(pr.SHAPES[k], np.float32) for k in TRPO_KEYS} for a in (M0, V0))
+    data = {k: np.concatenate([v, v[:1]]) for k, v in tr.rollout().items()}
+    idx = trpo_vf_indices(case["steps"])
+    new = tr.N_ROWS
+    kind = case["target"][0]
+    if kind == "row":
+        src = idx[max(case["step"], 0), case["pos"]]
+        for a in data.values():
+            a[new] = a[src]
+        if case["step"] >= 0:
+            idx[case["step"], case["pos"]] = new
+    if not twin:
+        if kind == "row":
+            _poison(data[case["target"][1]][new:new + 1], case["elem"], case["value"])
+        else:
+            _poison({"w": W, "m": M, "v": V}[kind][case["target"][1]], case["elem"], case["value"])
+    return dict(W=W, M=M, V=V, data=data, idx=idx)
+
+
+def trpo_vf_reference(S, with_bound=False):
+    """trpo_ref's vf_backward64 and Adam, step by step -> dict(stats [steps,1] float64: the loss, gflag [steps], nets [steps]: a
+    non-finite weight of the VALUE tower after the step; with_bound: first = step 1's (loss, G, loss bound, E) of vf_backward64)"""
+    f = np.float64
+    W = dict(S["W"])
+    for k in tr.VALUE_KEYS:
+        W[k] = np.asarray(W[k], f).copy()
+    M, V = ({k: np.asarray(a[k], f).copy() for k in tr.VALUE_KEYS} for a in (S["M"], S["V"]))
+    out = dict(stats=[], gflag=[], nets=[])
+    with np.errstate(all="ignore"):
+        for s, rows in enumerate(S["idx"]):
+            obs, ret = S["data"]["obs"][rows], S["data"]["returns"][rows]
+            if s == 0 and with_bound:
+                loss, G, lb, E = tr.vf_backward64(W, obs, ret, with_bound=True)
+                out["first"] = (np.array([loss]), G, np.array([lb]), E)
+            else:
+                loss, G = tr.vf_backward64(W, obs, ret)
+            out["stats"].append([loss])
+            out["gflag"].append(has_nonfinite(G))
+            for k in tr.VALUE_KEYS:
+                W[k], M[k], V[k] = pr.adam64(W[k], M[k], V[k], G[k], s + 1, TRPO_VF_LR, tr.VF_BETA1, tr.VF_BETA2, tr.VF_EPS)
+            out["nets"].append(has_nonfinite({k: W[k] for k in tr.VALUE_KEYS}))
+    return {k: (v if k == "first" else np.asarray(v)) for k, v in out.items()}
+
+
+# ---------------------------------------------------------------------------------------------------- TRPO's policy step
+# qst_policy_step takes rows 0 .. n-1, no indices: `row` is the roll-out's own row.  n = 17 (one chunk and a one-row tail);
+# fvp_stride 5 takes the Fisher rows 0, 5, 10, 15 (row 16 outside), 4 the rows 0, 4, .. 16 (row 16 inside); three CG iterations and
+# three candidates; every case runs at 1 and at 3 slices (tests/test_gpu_nonfinite.py).  entcoeff > 0: surr_before carries the entropy
+TRPO_STEP_N, TRPO_STEP_SLICES = 17, (1, 3)
+TRPO_STEP_SEED = 211
+TRPO_STEP_HP = dict(max_kl=0.01, cg_iters=3, cg_damping=1e-2, entcoeff=0.01, backtracks=3, fvp_stride=5)
+TRPO_STEP_DATA = ("obs", "actions", "returns", "values")
+_VALUE_SLOT = "the policy step does not read the value tower"
+_MOMENT = "the policy step reads no moment"
+_BEYOND_N = "the row lies at or beyond n"
+
+
+def _scase(cid, target, row, elem, value, stride=5, rows=TRPO_STEP_N, clean=None):
+    return dict(id=cid, target=target, row=row, elem=elem, value=value, stride=stride, rows=rows, clean=clean)
+
+
+TRPO_STEP_CASES = (
+    _scase("obs-nan-row3", ("row", "obs"), 3, 5, NAN),
+    _scase("obs-nan-row16-stride5", ("row", "obs"), 16, 0, NAN),
+    _scase("obs-nan-row16-stride4", ("row", "obs"), 16, 0, NAN, stride=4),
+    _scase("actions-nan", ("row", "actions"), 3, 2, NAN, stride=4),
+    _scase("actions-pinf-row16", ("row", "actions"), 16, 1, PINF),
+    _scase("returns-nan", ("row", "returns"), 16, 0, NAN),
+    _scase("values-ninf", ("row", "values"), 3, 0, NINF, stride=4),
+    _scase("w0-nan", ("w", "w0"), -1, 5 * 128 + 17, NAN),
+    _scase("w2-nan", ("w", "w2"), -1, 40 * 4 + 1, NAN, stride=4),
+    _scase("logstd-nan", ("w", "logstd"), -1, 2, NAN),
+    _scase("b1-pinf", ("w", "b1"), -1, 9, PINF, stride=4),
+    _scase("wv0-nan", ("w", "wv0"), -1, 5 * 128 + 17, NAN, clean=_VALUE_SLOT),
+    _scase("m-w1-nan", ("m", "w1"), -1, 1000, NAN, stride=4, clean=_MOMENT),
+    _scase("v-logstd-nan", ("v", "logstd"), -1, 1, NAN, clean=_MOMENT),
+    _scase("m-wv2-nan", ("m", "wv2"), -1, 3, NAN, clean=_MOMENT),
+    _scase("row17-of-18-nan", ("row", "obs"), 17, 4, NAN, stride=4, rows=18, clean=_BEYOND_N),
+)
+
+
+def trpo_step_setup(case, twin=False):
+    """-> dict(W, M, V: {the thirteen keys: float32 array}, data: the four arrays of case["rows"] rows, n = 17, hp)"""
+    W = {k: np.array(tr.weights()[k]) for k in TRPO_KEYS}
+    M0, V0 = tr.moments()
+    M, V = ({k: np.array(a[k]) if k in a else np.zeros(pr.SHAPES[k], np.float32) for k in TRPO_KEYS} for a in (M0, V0))
+    data = {k: np.array(v) for k, v in tr.head(tr.rollout(seed=TRPO_STEP_SEED), case["rows"]).items()}
+    if not twin:
+        kind = case["target"][0]
+        if kind == "row":
+            _poison(data[case["target"][1]][case["row"]:case["row"] + 1], case["elem"], case["value"])
+        else:
+            _poison({"w": W, "m": M, "v": V}[kind][case["target"][1]], case["elem"], case["value"])
+    return dict(W=W, M=M, V=V, data=data, n=TRPO_STEP_N, hp=dict(TRPO_STEP_HP, fvp_stride=case["stride"]))
+
+
+def trpo_step_reference(S):
+    """trpo_ref.step64 over the first n rows -> its dict (stats [10], accepted, iters, theta after, G: grad64's dict with bounds) and
+    gflag: a non-finite element of g, nets: a non-finite element of theta after the step"""
+    with np.errstate(all="ignore"):
+        out = tr.step64(S["W"], tr.head(S["data"], S["n"]), **S["hp"])
+    out["gflag"], out["nets"] = bool(nonfinite(out["G"]["g"]).any()), bool(nonfinite(out["theta"]).any())
+    return out
+
+
 LIBRARIES = {"ddpg": (DDPG_CASES, ddpg_setup, ddpg_reference), "ppo2": (PPO2_CASES, ppo2_setup, ppo2_reference),
              "dynfit": (DYNFIT_CASES, dynfit_setup, dynfit_reference), "bc": (BC_CASES, bc_setup, bc_reference),
-             "gail": (GAIL_CASES, gail_setup, gail_reference)}
+             "gail": (GAIL_CASES, gail_setup, gail_reference), "td3": (TD3_CASES, td3_setup, td3_reference),
+             "trpo_vf": (TRPO_VF_CASES, trpo_vf_setup, trpo_vf_reference)}

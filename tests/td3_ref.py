@@ -9,13 +9,14 @@ Adam, the delayed actor and the delayed Polyak average over a schedule with a co
 
 The bounds, beyond those of ddpg_ref (u = 2^-24, gamma_k = k u / (1 - k u); E_x bounds |computed x - x|):
   e          e = clampsel(SIGMA z, -CL, CL): one rounding of the product, the clamp is 1-Lipschitz (and exact where it acts): E_e = u |SIGMA z|
+             (0 for an infinite z: the clamp acts, whatever the rounding)
   a'         a' = clampsel(a1 + e, -1, 1): E_a1 + E_e and one rounding of the sum; the clamp is 1-Lipschitz
-  m          min is 1-Lipschitz in the pair: E_m = max(E_qa, E_qb)
+  m          min is 1-Lipschitz in the pair: E_m = max(E_qa, E_qb) (where one of the pair is infinite, the other's bound)
   y          as ddpg_ref: E_y = k (E_m + gamma_3 (|m| + E_m)) + u |y|, k = (1 - done) gamma; a terminal row is exact
   critic     the action is an exact input of layer 0 (16 terms); dz0 through w1 [128,128] as ddpg_ref's
   dq/da      dc1 = fl(w2 N) under h1's mask; dc0 a chain of 128 under h0's mask (gamma_130); da a chain of 128 on w0's action rows
              (gamma_130); then ddpg_ref's tanh derivative and the actor's own backward pass
-  masks      as ddpg_ref: where a float64 pre-activation lies within its forward bound of zero the bound covers both sides.  The
+  masks      dq/da's two masks hand a NaN activation's term on (_handed_on), the header's h <= 0 ? 0 : acc.  Otherwise as ddpg_ref: where a float64 pre-activation lies within its forward bound of zero the bound covers both sides.  The
              fixtures are chosen so that this happens nowhere (relu_edges == 0, held by tests/test_td3_cpu.py): no element is excluded.
 Nothing is fitted.
 """
@@ -94,7 +95,9 @@ def target64(P, rows, z, gam=GAMMA, sigma=SIGMA, clip=CLIP, E_z=0.0):
     T = actor64(P["actor_target"], x1)
     raw = sg * z
     e = clampsel(raw, -cl, cl)
-    E_e = sg * E_z + U32 * (np.abs(raw) + sg * E_z) + TINY
+    with np.errstate(invalid="ignore"):
+        # (an infinite product is clamped to +-CL exactly: its rounding bound, itself infinite, does not pass the clamp)
+        E_e = np.where(np.isinf(raw), 0.0, sg * E_z + U32 * (np.abs(raw) + sg * E_z) + TINY)
     s = T["a"] + e
     ap = clampsel(s, -1.0, 1.0)
     E_ap = T["E_a"] + E_e
@@ -102,7 +105,8 @@ def target64(P, rows, z, gam=GAMMA, sigma=SIGMA, clip=CLIP, E_z=0.0):
     Qa, Qb = critic64(P["q1_target"], x1, ap, E_ap), critic64(P["q2_target"], x1, ap, E_ap)
     qa, qb = Qa["q"], Qb["q"]
     m = np.where(np.isnan(qa), qa, np.where(np.isnan(qb), qb, np.where(qb < qa, qb, qa)))
-    E_m = np.maximum(Qa["E_q"], Qb["E_q"])
+    # (an infinite target value is exact in float32 as in float64: the minimum is the other critic's value, with that one's bound)
+    E_m = np.where(np.isinf(qa), Qb["E_q"], np.where(np.isinf(qb), Qa["E_q"], np.maximum(Qa["E_q"], Qb["E_q"])))
     k = np.where(done >= 1.0, 0.0, (1.0 - done) * f(np.float32(gam)))
     with np.errstate(invalid="ignore", over="ignore"):
         y = np.where(done >= 1.0, rew, rew + k * m)
@@ -132,6 +136,15 @@ def relu_edges(P, rows):
         for l in (0, 1):
             out |= (np.abs(F["z%d" % l]) <= F["E_z%d" % l]).any(-1)
     return out
+
+
+def _handed_on(acc, E_acc, z, E_z):
+    """dq/da's masks, z <= 0 ? 0 : acc: _masked for every finite z; a NaN pre-activation hands its term on, as float64 autograd's
+    ReLU does (and the header's item 4), where _masked -- the trainers' h > 0 ? acc : 0 -- turns it into 0"""
+    with np.errstate(invalid="ignore"):
+        m = ~(z <= 0.0)
+        edge = np.abs(z) <= E_z
+    return acc * m, np.where(edge, np.abs(acc) + E_acc, E_acc * m)
 
 
 def _critic_step(W, x0, act, y, E_y, B, G, E):
@@ -175,10 +188,10 @@ def step64(P, rows, z, gam=GAMMA, sigma=SIGMA, clip=CLIP, actor=True, with_bound
         wc = {k_: np.asarray(P["q1"][k_], f) for k_ in KEYS}
         n = -1.0 / B
         acc = np.broadcast_to(wc["w2"][:, 0][None, :] * n, (B, 128))
-        dc1, E_dc1 = _masked(acc, gamma(2) * np.abs(acc) + TINY, Cp["z1"], Cp["E_z1"])
+        dc1, E_dc1 = _handed_on(acc, gamma(2) * np.abs(acc) + TINY, Cp["z1"], Cp["E_z1"])
         acc = dc1 @ wc["w1"].T
         E_acc = E_dc1 @ np.abs(wc["w1"]).T + gamma(130) * ((np.abs(dc1) + E_dc1) @ np.abs(wc["w1"]).T) + TINY
-        dc0, E_dc0 = _masked(acc, E_acc, Cp["z0"], Cp["E_z0"])
+        dc0, E_dc0 = _handed_on(acc, E_acc, Cp["z0"], Cp["E_z0"])
         w0a = wc["w0"][12:]                                                      # [4,128]
         da = dc0 @ w0a.T
         E_da = E_dc0 @ np.abs(w0a).T + gamma(130) * ((np.abs(dc0) + E_dc0) @ np.abs(w0a).T) + TINY

@@ -14,8 +14,11 @@ gradients, the noise that was used, the workspace) between 256 sentinel bytes on
   twin minimum swapping the target critics changes nothing; q2_target = q1_target gives the one-critic y restated in numpy float32
   terminal     done = 1 everywhere: target nets of 1e30 change no bit but their own
   ragged       counts inside a call of batch 256 equal one call per step with batch = counts[s], bit for bit
-  non-finite   a NaN observation row, an inf reward, a NaN in q2_target only, a NaN weight in the actor: finiteness of the statistics
-               and of every net as float64 torch_td3_update has it; unread rows and earlier steps bit for bit
+  non-finite   a NaN observation row, an inf reward, a NaN in q2_target only, a NaN weight in the actor over three steps: finiteness
+               of the statistics and of every net as float64 torch_td3_update has it; unread rows and earlier steps bit for bit.
+               The table of single poisons (every input array, the caller's noise, weights, moments, the target nets live and
+               terminal, the actor/critic-only schedule) is tests/nonfinite_cases.py's TD3_CASES, run by tests/test_gpu_nonfinite.py
+               through run_update, which takes the workspace's bytes at entry and returns them after the call for that
   it learns    the regression case td3_ref.learn_case, which test_td3_cpu.py holds the float64 reference to first
   wrapper      td3_update equals the raw call, bit for bit; torch_td3_update within the same bounds
   the loop     TD3.learn on 16 docking-v0 envs, two cycles, both update paths
@@ -55,8 +58,9 @@ def dev(torch, a):
 
 
 def run_update(torch, P, M, V, rp, idx, counts=None, t0=0, actor_t0=0, noise=None, seed=0, want_grads=False, want_noise=False, stream=None,
-               **hyper):
-    """qstd_update on copies of (P, M, V) -> dict(w: {net: {key: array}}, m, v, stats, grads, noise)"""
+               ws_init=None, **hyper):
+    """qstd_update on copies of (P, M, V) -> dict(w: {net: {key: array}}, m, v, stats, grads, noise, ws: the workspace's bytes after
+    the call).  ws_init: the bytes the workspace holds at entry (None: zeros)"""
     from quadsim_amd import td3
     lib = td3.load_td3()
     hp = dict(HYPER, **hyper)
@@ -70,8 +74,8 @@ def run_update(torch, P, M, V, rp, idx, counts=None, t0=0, actor_t0=0, noise=Non
     nout = Guarded(torch, np.full((steps, batch, 4), np.nan, np.float32)) if want_noise else None
     nbytes = C.c_size_t(0)
     td3.check_td3(lib.qstd_workspace_bytes(C.byref(nbytes)), "qstd_workspace_bytes")
-    ws = Guarded(torch, nbytes=nbytes.value)
-    assert ws.ptr % 16 == 0
+    ws = Guarded(torch, nbytes=nbytes.value) if ws_init is None else Guarded(torch, np.asarray(ws_init, np.uint8))
+    assert ws.ptr % 16 == 0 and ws.n == nbytes.value
     it = torch.as_tensor(idx).cuda()
     cnt = None if counts is None else torch.as_tensor(np.ascontiguousarray(counts, np.int32)).cuda()
     nz = None if noise is None else torch.as_tensor(np.ascontiguousarray(noise, np.float32)).cuda()
@@ -89,8 +93,7 @@ def run_update(torch, P, M, V, rp, idx, counts=None, t0=0, actor_t0=0, noise=Non
                                   C.byref(hyp), t0, actor_t0, None if nz is None else nz.data_ptr(), seed, None if nout is None else nout.ptr,
                                   ws.ptr, nbytes.value, stats.ptr, grads, C.c_void_p(s.cuda_stream)), "qstd_update")
     s.synchronize()
-    ws.get("the workspace")
-    out = {"w": {n: {k: g.get("%s %s" % (n, k)) for k, g in zip(KEYS, gw[n])} for n in NETS},
+    out = {"ws": ws.get("the workspace"), "w": {n: {k: g.get("%s %s" % (n, k)) for k, g in zip(KEYS, gw[n])} for n in NETS},
            "m": {n: {k: g.get("m %s %s" % (n, k)) for k, g in zip(KEYS, gm[n])} for n in ONLINE},
            "v": {n: {k: g.get("v %s %s" % (n, k)) for k, g in zip(KEYS, gv[n])} for n in ONLINE}, "stats": stats.get("stats")}
     if want_grads:

@@ -11,7 +11,11 @@ What is held:
   line search  the five fixtures of trpo_ref.LS_FIXTURES: surr_k and kl_k of every evaluated candidate within bounds at the device's
                own theta_k, the accepted k that of the float64 reference, the policy bit for bit float32(theta_old + fullstep 2^-k),
                the value tower and the moments untouched
-  skips        n = 1, equal advantages: accepted = -2, every tensor bit for bit; a NaN observation row: rejected, theta bit for bit
+  skips        n = 1, equal advantages: accepted = -2, every tensor bit for bit; a NaN observation row: rejected, theta bit for bit.
+               The table of single poisons of the policy step and of the value fit is tests/nonfinite_cases.py's TRPO_STEP_CASES and
+               TRPO_VF_CASES, run by tests/test_gpu_nonfinite.py through policy_step and vf_fit; for that policy_step takes moments,
+               a row count below the arrays', the workspace's bytes at entry (and returns them) and a trace of marked NaNs (filled,
+               unwritten: whether an element was written is a question of bits also where a NaN is written)
   invariants   a second stream, with and without the trace, twice from the same state: the same bits
   value fit    one step at batch 1, 15, 16, 17, 128, 256 within bounds; five steps in one launch = five launches; the policy untouched
   Python       trpo_policy_step feeds predict_hip and the Runner; TRPO.learn with and without an expert; the refusals"""
@@ -47,40 +51,59 @@ def _net(torch, W, M=None, V=None):
     return _lib.QstNet(C.sizeof(_lib.QstNet), 1, arr(g), arr(gm), arr(gv)), g, gm, gv
 
 
-def policy_step(torch, W, data, hp, slices=0, trace=True, stream=None, nan_fill=True):
-    """one qst_policy_step -> dict of host arrays (sentinels checked): stats, grad, W (the thirteen tensors after), trace"""
+FILL32, FILL64 = 0x7FC12345, 0x7FF8000012345678      # NaNs with a payload no arithmetic produces: a trace element the call did not write
+
+
+def filled(shape, dtype):
+    """an array of the marked NaN: whether the call wrote an element is a question of bits, also where it writes a NaN"""
+    bits, word = (FILL32, np.uint32) if np.dtype(dtype) == np.float32 else (FILL64, np.uint64)
+    return np.full(shape, bits, word).view(dtype)
+
+
+def unwritten(a):
+    """the elements of a trace array that still hold the marked NaN of `filled`"""
+    bits, word = (FILL32, np.uint32) if a.dtype == np.float32 else (FILL64, np.uint64)
+    return np.ascontiguousarray(a).view(word) == bits
+
+
+def policy_step(torch, W, data, hp, slices=0, trace=True, stream=None, nan_fill=True, M=None, V=None, n=None, ws_init=None, marked=False):
+    """one qst_policy_step -> dict of host arrays (sentinels checked): stats, grad, W (the thirteen tensors after), M, V, trace, ws
+    (the workspace's bytes after the call).  M, V: the moments (None: zeros); n: the rows the call is told of (None: all the arrays
+    hold); ws_init: the bytes the workspace holds at entry (None: zeros); marked: the trace starts as `filled`"""
     from quadsim_amd import _lib, trpo
     lib = trpo.load_trpo()
-    n = data["obs"].shape[0]
+    n = data["obs"].shape[0] if n is None else n
+    assert 1 <= n <= data["obs"].shape[0]
     hp = dict(HP, **hp)
     hp.setdefault("residual_tol", 1e-10)
-    net, g, gm, gv = _net(torch, W)
+    net, g, gm, gv = _net(torch, W, M, V)
     d = {k: Guarded(torch, data[k]) for k in ("obs", "actions", "returns", "values")}
     bat = _lib.QstBatch(C.sizeof(_lib.QstBatch), 0, n, *(d[k].ptr for k in ("obs", "actions", "returns", "values")))
     hyp = _lib.QstHyper(C.sizeof(_lib.QstHyper), hp["cg_iters"], hp["backtracks"], hp["fvp_stride"], hp["max_kl"], hp["cg_damping"],
                         hp["entcoeff"], hp["residual_tol"])
     need = C.c_size_t(0)
     assert lib.qst_workspace_bytes(n, slices, C.byref(need)) == 0
-    ws = Guarded(torch, np.zeros(need.value, np.uint8))
+    ws = Guarded(torch, np.zeros(need.value, np.uint8) if ws_init is None else np.asarray(ws_init, np.uint8))
+    assert ws.n == need.value
     stats, grad = Guarded(torch, np.full(10, np.nan, np.float32)), Guarded(torch, np.full(tr.P, np.nan, np.float32))
     fill = np.nan if nan_fill else 0.0
+    new = filled if marked else (lambda shape, dtype: np.full(shape, fill, dtype))
     T = None
     if trace:
-        T = {"fvp_in": Guarded(torch, np.full((hp["cg_iters"] + 1, tr.P), fill, np.float32)),
-             "fvp_out": Guarded(torch, np.full((hp["cg_iters"] + 1, tr.P), fill, np.float32)),
-             "cg": Guarded(torch, np.full((hp["cg_iters"], 4), fill, np.float64)), "x": Guarded(torch, np.full(tr.P, fill, np.float32)),
-             "fullstep": Guarded(torch, np.full(tr.P, fill, np.float32)), "ls": Guarded(torch, np.full((hp["backtracks"], 2), fill, np.float32))}
+        T = {"fvp_in": Guarded(torch, new((hp["cg_iters"] + 1, tr.P), np.float32)), "fvp_out": Guarded(torch, new((hp["cg_iters"] + 1, tr.P), np.float32)),
+             "cg": Guarded(torch, new((hp["cg_iters"], 4), np.float64)), "x": Guarded(torch, new(tr.P, np.float32)),
+             "fullstep": Guarded(torch, new(tr.P, np.float32)), "ls": Guarded(torch, new((hp["backtracks"], 2), np.float32))}
         trs = _lib.QstTrace(C.sizeof(_lib.QstTrace), 0, *(T[k].ptr for k in ("fvp_in", "fvp_out", "cg", "x", "fullstep", "ls")))
     s = torch.cuda.current_stream() if stream is None else stream
     rc = lib.qst_policy_step(C.byref(net), C.byref(bat), slices, C.byref(hyp), ws.ptr, need.value, stats.ptr, grad.ptr,
                              C.byref(trs) if trace else None, s.cuda_stream)
     assert rc == 0, lib.qst_last_error()
     s.synchronize()
-    ws.get("workspace")
+    wsb = ws.get("workspace")
     for k in d:
         assert same_bits(d[k].get(k), data[k])
     out = {"stats": stats.get("stats"), "grad": grad.get("grad"), "W": {k: g[k].get(k) for k in KEYS},
-           "M": {k: gm[k].get("m " + k) for k in KEYS}, "V": {k: gv[k].get("v " + k) for k in KEYS}}
+           "M": {k: gm[k].get("m " + k) for k in KEYS}, "V": {k: gv[k].get("v " + k) for k in KEYS}, "ws": wsb}
     if trace:
         out["trace"] = {k: T[k].get("trace " + k) for k in T}
     return out

@@ -7,8 +7,11 @@ holds a non-finite element, whether a net holds a non-finite weight after the st
 make of a non-finite gradient, weight or moment.  For DDPG the restatement is tests/test_ddpg_cpu.py's (its actor and critic, with
 the target value selected by torch.where as quadsim_amd.ddpg.torch_ddpg_update selects it), for PPO2 quadsim_amd.ppo2.ppo2_loss,
 which tests/test_ppo2_cpu.py holds the reference to on finite data, for GAIL tests/test_gail_cpu.py's (its loss, with the input
-row built by torch.clamp); the dynamics fit and behaviour cloning have no torch path in
-the package, so their restatements are written here the same way.
+row built by torch.clamp), for TD3 quadsim_amd.torch_td3_update on a float64 CPU TD3Policy, one call per step; the dynamics fit and
+behaviour cloning have no torch path in the package, and TRPO's torch paths take float32 only, so their restatements (for the
+policy step: the header's steps 1 to 7, the Fisher-vector product as double backprop of the mean KL) are written here the same way.
+The one place where the arbiter and the contract part on purpose is held explicitly: surr_before and surr_after of a TRPO policy
+step are the header's formula sum A / n + entcoeff entropy, finite where autograd's mean(A exp(nlp_old - neglogp)) is NaN.
 
 The tables' conditions are held here and not on the device: a poisoned case makes at least one statistic non-finite in the
 arbiter, a clean-by-contract case none, every case is in exactly one of the two lists and no list is empty.  The package's own
@@ -27,6 +30,8 @@ import dynplan_ref as dr
 import gail_ref as gr
 import nonfinite_cases as nc
 import ppo2_ref as pr
+import td3_ref as td
+import trpo_ref as tr
 
 ids = lambda cases: [c["id"] for c in cases]     # noqa: E731
 
@@ -60,6 +65,7 @@ def test_every_case_is_in_exactly_one_list_and_no_list_is_empty(lib):
     assert {3, 16} <= {c["pos"] for c in cases if c["target"][0] == "row" and c["step"] >= 0}
     assert any(c["steps"] == 2 and c["step"] == 1 and c["clean"] is None for c in cases)
     assert {"row", "w", "m", "v"} <= {c["target"][0] for c in cases}
+    assert all(c["steps"] <= 2 for c in cases)
     print("%s: %d poisoned, %d clean by contract" % (lib, len(poisoned), len(clean)))
 
 
@@ -486,3 +492,257 @@ def test_torch_discriminator_fit_on_the_host_gives_the_arbiters_masks(case):
     assert np.array_equal(_mask(out["stats"]), nc.nonfinite(ref["stats"])), (case["id"], out["stats"], ref["stats"])
     assert _any(d.tensors()) == bool(ref["nets"][-1]), case["id"]
     assert nc.nonfinite(ref["stats"]).any() == (case["clean"] is None)
+
+
+# ---------------------------------------------------------------------------------------------------- TD3
+def td3_arbiter(S):
+    """the steps of a set-up in quadsim_amd.torch_td3_update on a float64 CPU TD3Policy, one call per step with the step counts the
+    policy carries -> what nonfinite_cases.td3_reference returns"""
+    import torch
+    import quadsim_amd as qa
+    t64 = lambda a: torch.tensor(np.asarray(a, np.float64))      # noqa: E731
+    pol = qa.TD3Policy(device="cpu", weights={n: {k: np.asarray(S["P"][n][k], np.float64) for k in td.KEYS} for n in td.NETS}, dtype="float64")
+    for n in td.ONLINE:
+        pol.m[n], pol.v[n] = [t64(S["M"][n][k]) for k in td.KEYS], [t64(S["V"][n][k]) for k in td.KEYS]
+    pol.steps, pol.actor_steps = S["t0"], S["actor_t0"]
+    rp = tuple(torch.as_tensor(a) for a in S["rp"])
+    out = dict(stats=[], gflag=[], nets=[])
+    for s in range(S["idx"].shape[0]):
+        counts = None if S["counts"] is None else torch.as_tensor(S["counts"][s:s + 1])
+        o = qa.torch_td3_update(pol, rp, torch.as_tensor(S["idx"][s:s + 1]), counts, noise=torch.as_tensor(S["z"][s:s + 1]), return_grads=True,
+                                **S["hp"])
+        out["stats"].append(o["stats"][0].numpy())
+        if s == 0:
+            first = {n: [g.numpy().copy() for g in o["grads"][n]] for n in td.ONLINE if o["grads"][n] is not None}
+        out["gflag"].append([o["grads"][n] is not None and _any(o["grads"][n]) for n in td.ONLINE])
+        out["nets"].append([_any(getattr(pol, n)) for n in td.NETS])
+    assert pol.steps == S["t0"] + S["idx"].shape[0]
+    return dict({k: np.asarray(v) for k, v in out.items()}, first=first)
+
+
+def _twin_rows_are_off_every_relu_edge(edges):
+    assert not np.asarray(edges).any(), "a twin's row lies on a ReLU edge: the fixtures' census does not hold for it"
+
+
+@pytest.mark.parametrize("case", nc.TD3_CASES, ids=ids(nc.TD3_CASES))
+def test_td3_reference_against_torch_float64_autograd(case):
+    S = nc.td3_setup(case)
+    ref, arb = nc.td3_reference(S, with_bound=True), td3_arbiter(S)
+    _same_masks(ref, arb, case["id"])
+    st, G, Es, _ = ref["first"]
+    _conditions(case, ref, arb, bool(np.isfinite(Es[np.isfinite(st)]).all()))
+    # step 1's gradients: the elements finite in both are the same numbers (a NaN activation of q1 hands dq/da's term on in both)
+    assert set(G) == set(arb["first"])
+    for n in G:
+        for k, g in zip(td.KEYS, arb["first"][n]):
+            both = np.isfinite(G[n][k]) & np.isfinite(g.reshape(G[n][k].shape))
+            assert np.allclose(G[n][k][both], g.reshape(G[n][k].shape)[both], rtol=1e-7, atol=1e-12), (case["id"], n, k)
+    if "nets" in case:
+        assert [n for n, bad in zip(td.NETS, ref["nets"][-1]) if bad] == [n for n in td.NETS if n in case["nets"]], (case["id"], ref["nets"])
+    T = nc.td3_setup(case, twin=True)
+    for s, rows in enumerate(T["idx"]):
+        rows = rows if T["counts"] is None else rows[:T["counts"][s]]
+        _twin_rows_are_off_every_relu_edge(td.relu_edges(T["P"], tuple(a[rows] for a in T["rp"])))
+    if case["clean"]:
+        # the twin differs in nothing that reaches a result: the reference gives the same numbers, every one
+        tw = nc.td3_reference(T)
+        assert np.array_equal(tw["stats"], ref["stats"]) and not tw["nets"].any()
+        own = [case["target"][:2] == ("w", n) for n in td.NETS]          # a poisoned weight stays what it was given, and nothing else
+        assert np.array_equal(ref["nets"][-1], own), (case["id"], ref["nets"])
+        if case["clean"] == nc._NOT_READ:
+            assert ref["stats"][0, 5] == 0.0 and arb["stats"][0, 5] == 0.0 and not np.signbit(ref["stats"][0, 5])
+
+
+@pytest.mark.parametrize("case", nc.TD3_CASES, ids=ids(nc.TD3_CASES))
+def test_td3_adam64_keeps_the_non_finite_elements_torch_keeps(case):
+    """adam64 on step 1's reference gradient and the case's weights and moments, element by element against the formula in torch"""
+    import torch
+    S = nc.td3_setup(case)
+    G = nc.td3_reference(S, with_bound=True)["first"][1]
+    with np.errstate(all="ignore"):
+        for n in G:
+            t = (S["actor_t0"] if n == "actor" else S["t0"]) + 1
+            for k in td.KEYS:
+                w, m, v = S["P"][n][k], S["M"][n][k], S["V"][n][k]
+                want = _adam_t(torch, *(torch.tensor(np.asarray(a, np.float64)) for a in (w, m, v, G[n][k])), t, 1e-2, td.BETA1, td.BETA2, td.EPS)
+                for got, tt in zip(td.adam64(w, m, v, G[n][k], t, 1e-2, td.BETA1, td.BETA2, td.EPS), want):
+                    assert np.array_equal(nc.nonfinite(got), _mask(tt)), (case["id"], n, k)
+                    ok = np.isfinite(got)
+                    assert np.allclose(got[ok], tt.numpy()[ok], rtol=1e-12, atol=0.0)
+
+
+def test_the_td3_table_covers_what_the_issue_names():
+    cases = nc.TD3_CASES
+    by = {c["id"]: c for c in cases}
+    assert {c["target"][1] for c in cases if c["target"][0] == "row" and c["clean"] is None} == set(nc.TD3_DATA)
+    noise = [c for c in cases if c["target"][0] == "noise"]
+    assert {(c["rowdone"], c["clean"] is None) for c in noise if c["value"] != c["value"]} == {(0.0, True), (1.0, False)}
+    assert {c["value"] for c in noise if c["clean"] == nc._NOISE_CLAMPED} == {nc.PINF, nc.NINF}
+    assert by["noise-pinf-sigma0"]["hyper"] == dict(target_policy_noise=0.0) and by["noise-pinf-sigma0"]["clean"] is None
+    tw = [c for c in cases if c["target"][0] == "w" and c["target"][1].endswith("_target") and c["value"] != c["value"]]
+    assert {(c["target"][1], c["done"], c["clean"] is None) for c in tw} == {(n, d, d == 0.0) for n in ("actor_target", "q1_target", "q2_target")
+                                                                             for d in (0.0, 1.0)}
+    assert by["q1-target-b2-pinf-live"]["clean"] and by["q1-target-b2-ninf-live"]["clean"] is None
+    assert by["actor-w0-nan-critic-only"]["t0"] == 1 and by["actor-w0-nan-critic-then-actor"]["t0"] == 1
+    assert {c["target"][:2] for c in cases if c["target"][0] in ("m", "v")} == {("m", "q1"), ("v", "q2")}
+    assert {"unread-row-nan", "beyond-count-nan", "beyond-count-step2-nan"} <= set(by)
+
+
+# ---------------------------------------------------------------------------------------------------- TRPO's value fit
+def trpo_vf_arbiter(S):
+    """the steps of a set-up in float64 torch autograd -> what nonfinite_cases.trpo_vf_reference returns"""
+    import torch
+    t64 = lambda a: torch.tensor(np.asarray(a, np.float64))      # noqa: E731
+    P, M, V = ({k: t64(a[k]) for k in tr.VALUE_KEYS} for a in (S["W"], S["M"], S["V"]))
+    out = dict(stats=[], gflag=[], nets=[])
+    for s, rows in enumerate(S["idx"]):
+        T = {k: w.clone().requires_grad_(True) for k, w in P.items()}
+        h = torch.relu(t64(S["data"]["obs"][rows]) @ T["wv0"] + T["bv0"])
+        h = torch.relu(h @ T["wv1"] + T["bv1"])
+        loss = (((h @ T["wv2"] + T["bv2"])[:, 0] - t64(S["data"]["returns"][rows])) ** 2).mean()
+        G = dict(zip(T, torch.autograd.grad(loss, list(T.values()))))
+        for k in tr.VALUE_KEYS:
+            P[k], M[k], V[k] = _adam_t(torch, P[k], M[k], V[k], G[k], s + 1, nc.TRPO_VF_LR, tr.VF_BETA1, tr.VF_BETA2, tr.VF_EPS)
+        out["stats"].append([float(loss.detach())])
+        out["gflag"].append(_any(G.values()))
+        out["nets"].append(_any(P.values()))
+    return {k: np.asarray(v) for k, v in out.items()}
+
+
+@pytest.mark.parametrize("case", nc.TRPO_VF_CASES, ids=ids(nc.TRPO_VF_CASES))
+def test_trpo_vf_reference_against_torch_float64_autograd(case):
+    import torch
+    S = nc.trpo_vf_setup(case)
+    ref, arb = nc.trpo_vf_reference(S, with_bound=True), trpo_vf_arbiter(S)
+    _same_masks(ref, arb, case["id"])
+    st, G, lb, _ = ref["first"]
+    _conditions(case, ref, arb, bool(np.isfinite(lb[np.isfinite(st)]).all()))
+    T = nc.trpo_vf_setup(case, twin=True)
+    for rows in T["idx"]:
+        _twin_rows_are_off_every_relu_edge(tr.relu_edges(T["W"], T["data"]["obs"][rows]))
+    if case["clean"]:
+        tw = nc.trpo_vf_reference(T)
+        assert np.array_equal(tw["stats"], ref["stats"]) and not ref["nets"].any()
+    t64 = lambda a: torch.tensor(np.asarray(a, np.float64))      # noqa: E731
+    with np.errstate(all="ignore"):
+        for k in tr.VALUE_KEYS:
+            want = _adam_t(torch, *(t64(a) for a in (S["W"][k], S["M"][k], S["V"][k], G[k])), 1, nc.TRPO_VF_LR, tr.VF_BETA1, tr.VF_BETA2, tr.VF_EPS)
+            for got, t in zip(pr.adam64(S["W"][k], S["M"][k], S["V"][k], G[k], 1, nc.TRPO_VF_LR, tr.VF_BETA1, tr.VF_BETA2, tr.VF_EPS), want):
+                assert np.array_equal(nc.nonfinite(got), _mask(t)), (case["id"], k)
+                ok = np.isfinite(got)
+                assert np.allclose(got[ok], t.numpy()[ok], rtol=1e-12, atol=0.0)
+
+
+# ---------------------------------------------------------------------------------------------------- TRPO's policy step
+def trpo_step_arbiter(S):
+    """the header's steps 1 to 7 in float64 torch autograd: the surrogate mean(A exp(nlp_old - neglogp)) + entcoeff entropy and its
+    gradient, the Fisher-vector product as double backprop of the mean KL over every fvp_stride-th row, SB2's cg and line search
+    (quadsim_amd.trpo.torch_trpo_policy_step's loop, whose head, neglogp and KL it takes, in float64 throughout) -> dict(stats [10],
+    gflag, nets: a non-finite element of theta after the step, accepted, iters)"""
+    import torch
+    from quadsim_amd.trpo import _mean_kl, _neglogp, _policy_head
+    hp, n = S["hp"], S["n"]
+    t64 = lambda a: torch.tensor(np.asarray(a, np.float64))      # noqa: E731
+    obs, actions, returns, values = (t64(S["data"][k][:n]) for k in nc.TRPO_STEP_DATA)
+    theta = torch.cat([t64(S["W"][k]).reshape(-1) for k in tr.POLICY_KEYS])
+    unflat = lambda vec: {k: p.view(tr.SHAPES[k]) for k, p in zip(tr.POLICY_KEYS, torch.split(vec, tr.SIZES))}      # noqa: E731
+    adv = returns - values
+    adv = (adv - adv.mean()) / (adv.std(unbiased=False) + 1e-8)
+    with torch.no_grad():
+        P0 = unflat(theta)
+        mean_old, ls_old = _policy_head(torch, P0, obs), P0["logstd"].clone()
+        nlp_old = _neglogp(torch, mean_old, ls_old, actions)
+
+    def losses(vec):
+        P = unflat(vec)
+        mean = _policy_head(torch, P, obs)
+        ent = (P["logstd"] + 0.5 * math.log(2.0 * math.pi * math.e)).sum()
+        surr = (adv * torch.exp(nlp_old - _neglogp(torch, mean, P["logstd"], actions))).mean() + hp["entcoeff"] * ent
+        return surr, _mean_kl(torch, mean_old, ls_old, mean, P["logstd"]), ent
+
+    def fvp(vec):
+        th = theta.clone().requires_grad_(True)
+        P = unflat(th)
+        kl = _mean_kl(torch, mean_old[::hp["fvp_stride"]], ls_old, _policy_head(torch, P, obs[::hp["fvp_stride"]]), P["logstd"])
+        (gk,) = torch.autograd.grad(kl, th, create_graph=True)
+        (hv,) = torch.autograd.grad((gk * vec).sum(), th)
+        return hv + hp["cg_damping"] * vec
+
+    th = theta.clone().requires_grad_(True)
+    surr_before, _, ent0 = losses(th)
+    (g,) = torch.autograd.grad(surr_before, th)
+    surr_before = float(surr_before)
+    stats = [surr_before, surr_before, 0.0, float(ent0), float(g.norm()), 0.0, 0.0, 0.0, -2.0, 0.0]
+    new_theta = theta
+    if float((g ** 2).sum()) != 0.0:
+        x, r, p = torch.zeros_like(g), g.clone(), g.clone()
+        rdotr, iters = float(r.dot(r)), 0
+        for _ in range(hp["cg_iters"]):
+            z = fvp(p)
+            a = rdotr / float(p.dot(z))
+            x, r = x + a * p, r - a * z
+            new = float(r.dot(r))
+            p, rdotr, iters = r + (new / rdotr) * p, new, iters + 1
+            if rdotr < 1e-10:
+                break
+        shs = 0.5 * float(x.dot(fvp(x)))
+        lm = math.sqrt(shs / hp["max_kl"]) if shs >= 0.0 else float("nan")
+        fullstep = x / lm
+        stats[5:10] = [shs, lm, float(g.dot(fullstep)), -1.0, float(iters)]
+        with torch.no_grad():
+            for k in range(hp["backtracks"]):
+                cand = theta + fullstep * 0.5 ** k
+                surr, kl, ent = (float(v) for v in losses(cand))
+                if math.isfinite(surr) and math.isfinite(kl) and kl <= 1.5 * hp["max_kl"] and surr - surr_before >= 0.0:
+                    new_theta = cand
+                    stats[1], stats[2], stats[3], stats[8] = surr, kl, ent, float(k)
+                    break
+    return dict(stats=np.asarray(stats), gflag=_any([g]), nets=_any([new_theta]), accepted=int(stats[8]), iters=int(stats[9]))
+
+
+@pytest.mark.parametrize("case", nc.TRPO_STEP_CASES, ids=ids(nc.TRPO_STEP_CASES))
+def test_trpo_step_reference_against_torch_float64_autograd(case):
+    S = nc.trpo_step_setup(case)
+    ref, arb = nc.trpo_step_reference(S), trpo_step_arbiter(S)
+    rs, as_ = ref["stats"], arb["stats"]
+    # (theta is never written by a poisoned step: it holds a non-finite element exactly when the case put one there)
+    own = case["target"][0] == "w" and case["target"][1] in tr.POLICY_KEYS
+    assert ref["gflag"] == arb["gflag"] and ref["nets"] == arb["nets"] == own, (case["id"], "gradient and theta flags")
+    assert ref["accepted"] == arb["accepted"] and ref["iters"] == arb["iters"], (case["id"], rs, as_)
+    assert np.array_equal(nc.nonfinite(rs[2:]), nc.nonfinite(as_[2:])), (case["id"], rs, as_)
+    both = ~nc.nonfinite(rs) & ~nc.nonfinite(as_)
+    assert np.allclose(rs[both], as_[both], rtol=1e-6, atol=1e-9), (case["id"], rs, as_)
+    _twin_rows_are_off_every_relu_edge(tr.relu_edges(nc.trpo_step_setup(case, twin=True)["W"], S["data"]["obs"][:S["n"]][np.isfinite(S["data"]["obs"][:S["n"]]).all(1)]))
+    if case["clean"]:
+        tw = nc.trpo_step_reference(nc.trpo_step_setup(case, twin=True))
+        assert np.isfinite(rs).all() and np.isfinite(as_).all() and not ref["gflag"], (case["id"], case["clean"], rs, as_)
+        assert np.array_equal(tw["stats"], rs) and np.array_equal(tw["theta"], ref["theta"]) and ref["accepted"] >= 0, (case["id"], rs)
+        return
+    # a poisoned step: g is non-finite, CG runs every product, every candidate is rejected, theta stays
+    assert ref["gflag"] and ref["accepted"] == -1 and ref["iters"] == S["hp"]["cg_iters"] and len(ref["cands"]) == S["hp"]["backtracks"], case["id"]
+    assert nc.nonfinite(rs[4:8]).all() and rs[2] == 0.0 and as_[2] == 0.0, (case["id"], rs)
+    assert np.array_equal(ref["theta"], tr.flatten(S["W"], np.float64), equal_nan=True)
+    # statistics 0 and 1, the documented deviation: the header's sum A / n + entcoeff entropy is finite whenever the advantages and
+    # logstd are, autograd's mean(A exp(nlp_old - neglogp)) is NaN with one row's neglogp
+    A, logstd = ref["G"]["A"], S["W"]["logstd"]
+    header_finite = bool(np.isfinite(A).all() and np.isfinite(logstd).all())
+    assert rs[0] == rs[1] or (rs[0] != rs[0] and rs[1] != rs[1])
+    assert bool(np.isfinite(rs[0])) == header_finite, (case["id"], rs[0])
+    assert as_[0] != as_[0] and as_[1] != as_[1], (case["id"], "autograd's surrogate of a poisoned step is NaN", as_)
+    if header_finite:
+        tw = nc.trpo_step_reference(nc.trpo_step_setup(case, twin=True))
+        if case["target"][0] == "w" or case["target"][1] in ("obs", "actions"):
+            assert rs[0] == tw["stats"][0], "the advantages and logstd are the twin's: so is surr_before"
+
+
+def test_the_trpo_step_table_has_both_lists_and_the_shapes_the_issue_names():
+    cases = nc.TRPO_STEP_CASES
+    assert len({c["id"] for c in cases}) == len(cases) and nc.TRPO_STEP_N == 17 and nc.TRPO_STEP_SLICES == (1, 3)
+    assert nc.TRPO_STEP_HP["cg_iters"] == 3 and nc.TRPO_STEP_HP["backtracks"] == 3
+    poisoned, clean = [c for c in cases if c["clean"] is None], [c for c in cases if c["clean"]]
+    assert poisoned and clean and len(poisoned) + len(clean) == len(cases)
+    assert {(c["row"], c["stride"]) for c in poisoned if c["target"] == ("row", "obs")} == {(3, 5), (16, 5), (16, 4)}
+    assert {c["target"][1] for c in poisoned if c["target"][0] == "row"} == set(nc.TRPO_STEP_DATA)
+    assert {c["target"][1] for c in poisoned if c["target"][0] == "w"} == {"w0", "w2", "logstd", "b1"}
+    assert {c["target"][0] for c in clean} == {"w", "m", "v", "row"} and any(c["rows"] == 18 and c["row"] == 17 for c in clean)
+    assert {c["stride"] for c in poisoned} == {4, 5} == {c["stride"] for c in clean}
