@@ -236,6 +236,17 @@ def nets(seed=211, gain=1.0, bias=0.1):
     return _cache[key]
 
 
+def nets_shifted(shift):
+    """nets() with `shift` added to b2 of the target critic: target values of O(shift), so that gamma shows in y and in the critic's
+    loss (the standard fixtures' target values are small).  The online nets are nets()'s"""
+    key = ("shifted", float(shift))
+    if key not in _cache:
+        P = dict(nets())
+        P["critic_target"] = dict(P["critic_target"], b2=(P["critic_target"]["b2"] + np.float32(shift)).astype(np.float32))
+        _cache[key] = P
+    return _cache[key]
+
+
 def replay(seed=221, n=N_ROWS):
     """(obs0 [n,12]: docking observations with one entry in fifty moved beyond +-5, so that the clamp acts; act [n,4] in [-1, 1];
     rew [n]; obs1 [n,12] likewise; done [n] mixed 0 / 1) float32"""

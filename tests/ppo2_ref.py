@@ -254,16 +254,16 @@ def adam_input_bound(m, v, g, dg, t, lr, beta1=BETA1, beta2=BETA2, eps=EPS):
     return lrt * (dm / lo + np.abs(mn) * ds / (lo * den)), dm, dv
 
 
-def update64(W, M, V, G, hp, t):
+def update64(W, M, V, G, hp, t, beta1=BETA1, beta2=BETA2, eps=EPS):
     """tf.clip_by_global_norm + one tf.train.AdamOptimizer step from the gradients G -> (W', M', V', scale, norm)"""
     scale, norm = clip_scale64(G, hp["max_grad_norm"])
     Wn, Mn, Vn = {}, {}, {}
     for k in G:
-        Wn[k], Mn[k], Vn[k] = adam64(W[k], M[k], V[k], np.asarray(G[k], np.float64) * scale, t, hp["lr"], BETA1, BETA2, EPS)
+        Wn[k], Mn[k], Vn[k] = adam64(W[k], M[k], V[k], np.asarray(G[k], np.float64) * scale, t, hp["lr"], beta1, beta2, eps)
     return Wn, Mn, Vn, scale, norm
 
 
-def update_bound(W, M, V, G, hp, t):
+def update_bound(W, M, V, G, hp, t, beta1=BETA1, beta2=BETA2, eps=EPS):
     """bounds of the device's (w, m, v) against update64 of the SAME float32 gradients G: the scale is rounded to float32 and the
     product rounded (and the norm's float64 sum may be ordered otherwise): dg = 4u |g'|, through adam_input_bound, on top of
     adam_bound at g'"""
@@ -272,8 +272,8 @@ def update_bound(W, M, V, G, hp, t):
     for k in G:
         g = np.asarray(G[k], np.float64) * scale
         dg = 4 * U32 * np.abs(g) + TINY if hp["max_grad_norm"] > 0 else np.zeros_like(g)
-        Ew, Em, Ev = adam_bound(W[k], M[k], V[k], g, t, hp["lr"], BETA1, BETA2, EPS)
-        dw, dm, dv = adam_input_bound(M[k], V[k], g, dg, t, hp["lr"])
+        Ew, Em, Ev = adam_bound(W[k], M[k], V[k], g, t, hp["lr"], beta1, beta2, eps)
+        dw, dm, dv = adam_input_bound(M[k], V[k], g, dg, t, hp["lr"], beta1, beta2, eps)
         out[k] = (Ew + dw * (1 + 4 * U32), Em + dm * (1 + 4 * U32), Ev + dv * (1 + 4 * U32))
     return out
 

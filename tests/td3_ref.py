@@ -259,6 +259,18 @@ def nets(seed=311, gain=1.0, bias=0.1):
     return _cache[key]
 
 
+def nets_shifted(shift):
+    """nets() with `shift` added to b2 of both target critics: target values of O(shift), so that gamma shows in y and in the critics'
+    losses (the standard fixtures' target values are about 0.01).  The online nets, and with them relu_edges, are nets()'s"""
+    key = ("shifted", float(shift))
+    if key not in _cache:
+        P = dict(nets())
+        for n in ("q1_target", "q2_target"):
+            P[n] = dict(P[n], b2=(P[n]["b2"] + np.float32(shift)).astype(np.float32))
+        _cache[key] = P
+    return _cache[key]
+
+
 def replay(seed=321, n=N_ROWS):
     """(obs0 [n,12] docking observations, act [n,4] in [-1, 1], rew [n], obs1 [n,12], done [n] mixed 0 / 1) float32: of 3 n drawn rows
     the first n at which no hidden pre-activation of a differentiated pass of nets() lies within its bound of zero"""

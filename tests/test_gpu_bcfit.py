@@ -42,7 +42,7 @@ def data(torch):
     return torch.as_tensor(x).cuda().contiguous(), torch.as_tensor(a).cuda().contiguous()
 
 
-def run(torch, W, M, V, data, indices, counts=None, lr=1e-2, t0=0, want_grads=False, stream=None):
+def run(torch, W, M, V, data, indices, counts=None, lr=1e-2, t0=0, want_grads=False, stream=None, beta1=br.BETA1, beta2=br.BETA2, eps=br.EPS):
     """qsbc_fit on copies of (W, M, V) -> dict(w, m, v: dicts of numpy arrays, loss, grads)"""
     from quadsim_amd import bc
     lib = bc.load_bc()
@@ -58,7 +58,7 @@ def run(torch, W, M, V, data, indices, counts=None, lr=1e-2, t0=0, want_grads=Fa
     net = bc.QsbcNet(C.sizeof(bc.QsbcNet), 0, six(gw), six(gm), six(gv))
     s = stream if stream is not None else torch.cuda.current_stream()
     bc.check_bc(lib.qsbc_fit(C.byref(net), data[0].data_ptr(), data[1].data_ptr(), data[0].shape[0], idx.data_ptr(),
-                             None if cnt is None else cnt.data_ptr(), steps, batch, lr, br.BETA1, br.BETA2, br.EPS, t0, loss.ptr,
+                             None if cnt is None else cnt.data_ptr(), steps, batch, lr, beta1, beta2, eps, t0, loss.ptr,
                              None if gg is None else six(gg), C.c_void_p(s.cuda_stream)), "qsbc_fit")
     s.synchronize()
     out = {"w": {key: g.get(key) for key, g in zip(KEYS, gw)}, "m": {key: g.get("m " + key) for key, g in zip(KEYS, gm)},

@@ -46,7 +46,7 @@ def dev(torch, a):
     return _dev[id(a)][1]
 
 
-def run_update(torch, P, M, V, rp, idx, counts=None, t0=0, want_grads=False, stream=None, **hyper):
+def run_update(torch, P, M, V, rp, idx, counts=None, t0=0, want_grads=False, stream=None, beta1=dd.BETA1, beta2=dd.BETA2, eps=dd.EPS, **hyper):
     """qsdd_update on copies of (P, M, V) -> dict(w: {net: {key: array}}, m, v, stats, grads)"""
     from quadsim_amd import ddpg
     lib = ddpg.load_ddpg()
@@ -69,8 +69,8 @@ def run_update(torch, P, M, V, rp, idx, counts=None, t0=0, want_grads=False, str
     nets = ddpg.QsddNets(C.sizeof(ddpg.QsddNets), 0, (C.c_void_p * 24)(*[p for n in NETS for p in ptrs(gw[n])]),
                          (C.c_void_p * 12)(*[p for n in ONLINE for p in ptrs(gm[n])]), (C.c_void_p * 12)(*[p for n in ONLINE for p in ptrs(gv[n])]))
     replay = ddpg.QsddReplay(C.sizeof(ddpg.QsddReplay), 0, data[0].shape[0], *[t.data_ptr() for t in data])
-    hyp = ddpg.QsddHyper(C.sizeof(ddpg.QsddHyper), 0, hp["gamma"], hp["tau"], hp["actor_lr"], hp["critic_lr"], hp["obs_clip"], dd.BETA1, dd.BETA2,
-                         dd.EPS)
+    hyp = ddpg.QsddHyper(C.sizeof(ddpg.QsddHyper), 0, hp["gamma"], hp["tau"], hp["actor_lr"], hp["critic_lr"], hp["obs_clip"], beta1, beta2,
+                         eps)
     s = stream if stream is not None else torch.cuda.current_stream()
     grads = None if gg is None else (C.c_void_p * 12)(*[p for n in ONLINE for p in ptrs(gg[n])])
     ddpg.check_ddpg(lib.qsdd_update(C.byref(nets), C.byref(replay), it.data_ptr(), None if cnt is None else cnt.data_ptr(), steps, batch,

@@ -47,7 +47,7 @@ def buf(torch):
 
 
 def run(torch, W, M, V, buf, iters, batch, lr=1e-2, t0=0, seed=SEED, k=3, size=fr.SIZE, indices=None, want_indices=False, want_grads=False,
-        stream=None):
+        stream=None, beta1=fr.BETA1, beta2=fr.BETA2, eps=fr.EPS):
     """qsdf_fit on copies of (W, M, V) -> dict(w, m, v: dicts of numpy arrays, loss, indices, grads)"""
     from quadsim_amd import dynplan
     lib = dynplan.load_fit()
@@ -63,8 +63,8 @@ def run(torch, W, M, V, buf, iters, batch, lr=1e-2, t0=0, seed=SEED, k=3, size=f
     net = dynplan.QsdfNet(C.sizeof(dynplan.QsdfNet), W["w1"].shape[0], W["w2"].shape[0], 0, six(gw), six(gm), six(gv),
                           *[t.data_ptr() for t in norm])
     s = stream if stream is not None else torch.cuda.current_stream()
-    dynplan.check_fit(lib.qsdf_fit(C.byref(net), buf[0].data_ptr(), buf[1].data_ptr(), buf[0].shape[0], size, iters, batch, lr, fr.BETA1,
-                                   fr.BETA2, fr.EPS, t0, seed, k, None if idx is None else idx.data_ptr(), loss.ptr,
+    dynplan.check_fit(lib.qsdf_fit(C.byref(net), buf[0].data_ptr(), buf[1].data_ptr(), buf[0].shape[0], size, iters, batch, lr, beta1,
+                                   beta2, eps, t0, seed, k, None if idx is None else idx.data_ptr(), loss.ptr,
                                    None if iout is None else iout.ptr, None if gg is None else six(gg), C.c_void_p(s.cuda_stream)), "qsdf_fit")
     s.synchronize()
     out = {"w": {key: g.get(key) for key, g in zip(KEYS, gw)}, "m": {key: g.get("m " + key) for key, g in zip(KEYS, gm)},

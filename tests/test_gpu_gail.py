@@ -47,7 +47,7 @@ def dev(torch, a):
 
 
 def run_fit(torch, W, M, V, gen, exp, mean, rscale, gen_idx, exp_idx, counts=None, lr=1e-2, t0=0, entcoeff=gr.ENTCOEFF, want_grads=False,
-            stream=None):
+            stream=None, beta1=gr.BETA1, beta2=gr.BETA2, eps=gr.EPS):
     """qsg_fit on copies of (W, M, V) -> dict(w, m, v: dicts of numpy arrays, stats, grads)"""
     from quadsim_amd import gail
     lib = gail.load_gail()
@@ -66,8 +66,8 @@ def run_fit(torch, W, M, V, gen, exp, mean, rscale, gen_idx, exp_idx, counts=Non
     net = gail.QsgNet(C.sizeof(gail.QsgNet), gr.hidden_of(W), six(gw), six(gm), six(gv), mt.data_ptr(), rt.data_ptr())
     s = stream if stream is not None else torch.cuda.current_stream()
     gail.check_gail(lib.qsg_fit(C.byref(net), go.data_ptr(), ga.data_ptr(), go.shape[0], eo.data_ptr(), ea.data_ptr(), eo.shape[0],
-                                gi.data_ptr(), ei.data_ptr(), None if cnt is None else cnt.data_ptr(), steps, batch, entcoeff, lr, gr.BETA1,
-                                gr.BETA2, gr.EPS, t0, stats.ptr, None if gg is None else six(gg), C.c_void_p(s.cuda_stream)), "qsg_fit")
+                                gi.data_ptr(), ei.data_ptr(), None if cnt is None else cnt.data_ptr(), steps, batch, entcoeff, lr, beta1,
+                                beta2, eps, t0, stats.ptr, None if gg is None else six(gg), C.c_void_p(s.cuda_stream)), "qsg_fit")
     s.synchronize()
     out = {"w": {k: g.get(k) for k, g in zip(KEYS, gw)}, "m": {k: g.get("m " + k) for k, g in zip(KEYS, gm)},
            "v": {k: g.get("v " + k) for k, g in zip(KEYS, gv)}, "stats": stats.get("stats")}

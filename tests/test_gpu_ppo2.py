@@ -49,7 +49,7 @@ def thirteen(W, gs):
     return (C.c_void_p * 13)(*[gs[keys.index(k)].ptr if k in keys else None for k in pr.SLOT_KEYS])
 
 
-def run(torch, W, M, V, data, indices, hp, slices=1, t0=0, want_grads=False, stream=None):
+def run(torch, W, M, V, data, indices, hp, slices=1, t0=0, want_grads=False, stream=None, beta1=pr.BETA1, beta2=pr.BETA2, eps=pr.EPS):
     """qsp_update on copies of (W, M, V) -> dict(w, m, v: dicts of numpy arrays, stats [steps,6], grads)"""
     from quadsim_amd import _lib, ppo2
     lib = ppo2.load_ppo()
@@ -70,7 +70,7 @@ def run(torch, W, M, V, data, indices, hp, slices=1, t0=0, want_grads=False, str
     net = _lib.QspNet(C.sizeof(_lib.QspNet), 1 if "wv0" in W else 0, thirteen(W, gw), thirteen(W, gm), thirteen(W, gv))
     bat = _lib.QspBatch(C.sizeof(_lib.QspBatch), 0, dev[0].shape[0], *[t.data_ptr() for t in dev])
     hyp = _lib.QspHyper(C.sizeof(_lib.QspHyper), 0, hp["lr"], hp["cliprange"], hp["cliprange_vf"], hp["ent_coef"], hp["vf_coef"],
-                        hp["max_grad_norm"], pr.BETA1, pr.BETA2, pr.EPS)
+                        hp["max_grad_norm"], beta1, beta2, eps)
     s = stream if stream is not None else torch.cuda.current_stream()
     ppo2.check_ppo(lib.qsp_update(C.byref(net), C.byref(bat), idx.data_ptr(), steps, batch, slices, C.byref(hyp), t0, ws.ptr, need.value,
                                   stats.ptr, None if gg is None else C.byref(thirteen(W, gg)), C.c_void_p(s.cuda_stream)), "qsp_update")

@@ -58,7 +58,7 @@ def dev(torch, a):
 
 
 def run_update(torch, P, M, V, rp, idx, counts=None, t0=0, actor_t0=0, noise=None, seed=0, want_grads=False, want_noise=False, stream=None,
-               ws_init=None, **hyper):
+               ws_init=None, beta1=td.BETA1, beta2=td.BETA2, eps=td.EPS, **hyper):
     """qstd_update on copies of (P, M, V) -> dict(w: {net: {key: array}}, m, v, stats, grads, noise, ws: the workspace's bytes after
     the call).  ws_init: the bytes the workspace holds at entry (None: zeros)"""
     from quadsim_amd import td3
@@ -86,7 +86,7 @@ def run_update(torch, P, M, V, rp, idx, counts=None, t0=0, actor_t0=0, noise=Non
                         (C.c_void_p * 18)(*[p for n in ONLINE for p in ptrs(gm[n])]), (C.c_void_p * 18)(*[p for n in ONLINE for p in ptrs(gv[n])]))
     replay = td3.QstdReplay(C.sizeof(td3.QstdReplay), 0, data[0].shape[0], *[t.data_ptr() for t in data])
     hyp = td3.QstdHyper(C.sizeof(td3.QstdHyper), hp["policy_delay"], hp["gamma"], hp["tau"], hp["actor_lr"], hp["critic_lr"],
-                        hp["target_policy_noise"], hp["target_noise_clip"], td.BETA1, td.BETA2, td.EPS)
+                        hp["target_policy_noise"], hp["target_noise_clip"], beta1, beta2, eps)
     s = stream if stream is not None else torch.cuda.current_stream()
     grads = None if gg is None else (C.c_void_p * 18)(*[p for n in ONLINE for p in ptrs(gg[n])])
     td3.check_td3(lib.qstd_update(C.byref(nets), C.byref(replay), it.data_ptr(), None if cnt is None else cnt.data_ptr(), steps, batch,

@@ -269,7 +269,7 @@ def test_stream_trace_and_repetition_do_not_change_the_bits(torch):
 
 
 # ---------------------------------------------------------------------------------------------------- the value fit
-def vf_fit(torch, W, M, V, data, idx, t0=0, lr=1e-3, want_grads=True):
+def vf_fit(torch, W, M, V, data, idx, t0=0, lr=1e-3, want_grads=True, beta1=tr.VF_BETA1, beta2=tr.VF_BETA2, eps=tr.VF_EPS):
     from quadsim_amd import trpo
     lib = trpo.load_trpo()
     net, g, gm, gv = _net(torch, W, M, V)
@@ -279,7 +279,7 @@ def vf_fit(torch, W, M, V, data, idx, t0=0, lr=1e-3, want_grads=True):
     stats = Guarded(torch, np.full(steps, np.nan, np.float32))
     grads = [Guarded(torch, np.full(pr.SHAPES[k], np.nan, np.float32)) for k in tr.VALUE_KEYS]
     arr = (C.c_void_p * 6)(*[x.ptr for x in grads])
-    rc = lib.qst_vf_fit(C.byref(net), obs.ptr, ret.ptr, data["obs"].shape[0], gi.ptr, steps, batch, lr, tr.VF_BETA1, tr.VF_BETA2, tr.VF_EPS,
+    rc = lib.qst_vf_fit(C.byref(net), obs.ptr, ret.ptr, data["obs"].shape[0], gi.ptr, steps, batch, lr, beta1, beta2, eps,
                         t0, stats.ptr, C.byref(arr) if want_grads else None, torch.cuda.current_stream().cuda_stream)
     assert rc == 0, lib.qst_last_error()
     torch.cuda.synchronize()

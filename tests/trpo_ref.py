@@ -368,12 +368,12 @@ def vf_backward64(W, obs, ret, with_bound=False):
     return loss, G, sq + gamma(B + 3) * (loss + sq) + TINY, {k: Eb[b] for k, b in zip(VALUE_KEYS, br.KEYS)}
 
 
-def vf_update_bound(W, M, V, G, E_G, t, lr):
+def vf_update_bound(W, M, V, G, E_G, t, lr, beta1=VF_BETA1, beta2=VF_BETA2, eps=VF_EPS):
     """bounds of the device's (w, m, v) after one step against adam64 at the reference's gradient G whose device value lies within E_G"""
     out = {}
     for k in VALUE_KEYS:
-        Ew, Em, Ev = pr.adam_bound(W[k], M[k], V[k], G[k], t, lr, VF_BETA1, VF_BETA2, VF_EPS)
-        dw, dm, dv = pr.adam_input_bound(M[k], V[k], G[k], E_G[k], t, lr, VF_BETA1, VF_BETA2, VF_EPS)
+        Ew, Em, Ev = pr.adam_bound(W[k], M[k], V[k], G[k], t, lr, beta1, beta2, eps)
+        dw, dm, dv = pr.adam_input_bound(M[k], V[k], G[k], E_G[k], t, lr, beta1, beta2, eps)
         out[k] = ((Ew + dw) * (1 + 8 * U32), (Em + dm) * (1 + 8 * U32), (Ev + dv) * (1 + 8 * U32))
     return out
 
