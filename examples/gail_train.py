@@ -103,7 +103,7 @@ def main():
         if log is not None and (log["n_updates"] == 1 or log["n_updates"] % args.log_every == 0):
             print("update %5d  steps %9d  true return %9.3f  paid %7.4f  %s" % (
                 log["n_updates"], log["total_timesteps"], log.get("true_ep_reward_mean", float("nan")), log["disc_reward_mean"],
-                "  ".join("%s %.4f" % (k, log[k]) for k in DISC_STAT_NAMES)))
+                "  ".join("%s %.4f" % (k, log.get("disc_" + k, log[k])) for k in DISC_STAT_NAMES)))      # (TRPO's log: disc_entropy)
         return True
 
     torch.cuda.synchronize()

@@ -437,8 +437,8 @@ class TRPO:
     def learn(self, total_timesteps, callback=None, log_interval=1):
         """-> a list of one dict per logged update: the ten statistics of the (last) policy step (STAT_NAMES), `vf_loss` (the mean
         over the value fit's steps), explained_variance, the timestep counters, the episode statistics where the Runner has them
-        and, with an expert, the five discriminator statistics (DISC_STAT_NAMES, the mean over the d_step fits),
-        `disc_reward_mean` and `true_ep_reward_mean`.  callback(locals_, globals_) returning False stops the loop."""
+        and, with an expert, the five discriminator statistics (DISC_STAT_NAMES, the mean over the d_step fits; its entropy
+        under `disc_entropy`: `entropy` is the policy's), `disc_reward_mean` and `true_ep_reward_mean`.  callback(locals_, globals_) returning False stops the loop."""
         per_update = self.n_batch * (self.g_step if self.expert is not None else 1)
         n_updates = int(total_timesteps) // per_update
         logs, t_first = [], time.time()
@@ -468,7 +468,8 @@ class TRPO:
                     if self.expert is not None:
                         log["true_ep_reward_mean"] = log["ep_reward_mean"]
                 if d_stats is not None:
-                    log.update(zip(DISC_STAT_NAMES, d_stats.double().mean(0).tolist()))
+                    # (both tuples of names have an "entropy": the policy step's keeps the key, the discriminator's is disc_entropy)
+                    log.update(("disc_entropy" if k in STAT_NAMES else k, v) for k, v in zip(DISC_STAT_NAMES, d_stats.double().mean(0).tolist()))
                 paid = getattr(self.runner, "last_reward", None)
                 if self.expert is not None and paid is not None:
                     log["disc_reward_mean"] = float(paid.double().mean())

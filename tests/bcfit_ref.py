@@ -12,7 +12,8 @@ exactly (E = 0: nothing normalises them).
   error        e = fl(y - a): E_e = E_y + u (|e| + E_y)
   dy           fl(e c^), c^ = float32(2 / (4 B)): E_dy = |c| E_e + gamma_2 |c| (|e| + E_e)
   back-prop    dz1: one fma chain of 4 terms, gamma_{4+2}.  dz0: four interleaved chains of 32 fmas and a tree of two additions,
-               34 roundings on the longest path: gamma_{34+2}.  Both GIVEN the same mask (relu_edge)
+               34 roundings on the longest path: gamma_{34+2}.  Both GIVEN the same mask; at a pre-activation within its
+               forward bound of zero (relu_edge) the bound covers either side of the ReLU (_masked)
   gradients    an fma chain over the B rows of the step on two computed factors (the padding rows add exact zeros):
                E_gW = E_a^T |dz| + |a|^T E_dz + E_a^T E_dz + gamma_{B+2} (|a| + E_a)^T (|dz| + E_dz);  gb: a = 1, E_a = 0
   loss         4 fmas a row, B additions, one division by the exact float32 4 B: sum (2 |e| E_e + E_e^2) / (4 B), plus
@@ -58,6 +59,15 @@ def forward64(W, x, a, with_bound=False):
     return F
 
 
+def _masked(acc, E_acc, z, E_z):
+    """dz = acc under the mask z > 0, and its bound.  Where the float64 pre-activation lies within its forward bound of zero
+    (relu_edge counts these) the device may take either side of the ReLU: there the bound is |acc| + E_acc, which covers both.  At
+    every other element this is (acc m, E_acc m), what the one-step fixtures -- chosen so that relu_edge == 0 -- are held to"""
+    m = z > 0.0
+    edge = np.abs(z) <= E_z
+    return acc * m, np.where(edge, np.abs(acc) + E_acc, E_acc * m)
+
+
 def backward64(W, x, a, with_bound=False):
     """-> (loss, {key: gradient}) in float64; with_bound: (loss, grads, loss bound, {key: bound})"""
     f = np.float64
@@ -67,11 +77,10 @@ def backward64(W, x, a, with_bound=False):
     dy = F["e"] * c
     E_dy = c * F["E_e"] + gamma(2) * c * (np.abs(F["e"]) + F["E_e"]) + TINY
     w1, w2 = np.asarray(W["w1"], f), np.asarray(W["w2"], f)
-    m1, m0 = F["z1"] > 0.0, F["z0"] > 0.0
-    dz1 = (dy @ w2.T) * m1
-    E_dz1 = (E_dy @ np.abs(w2).T + gamma(4 + 2) * ((np.abs(dy) + E_dy) @ np.abs(w2).T) + TINY) * m1
-    dz0 = (dz1 @ w1.T) * m0
-    E_dz0 = (E_dz1 @ np.abs(w1).T + gamma(34 + 2) * ((np.abs(dz1) + E_dz1) @ np.abs(w1).T) + TINY) * m0
+    acc = dy @ w2.T
+    dz1, E_dz1 = _masked(acc, E_dy @ np.abs(w2).T + gamma(4 + 2) * ((np.abs(dy) + E_dy) @ np.abs(w2).T) + TINY, F["z1"], F["E_z1"])
+    acc = dz1 @ w1.T
+    dz0, E_dz0 = _masked(acc, E_dz1 @ np.abs(w1).T + gamma(34 + 2) * ((np.abs(dz1) + E_dz1) @ np.abs(w1).T) + TINY, F["z0"], F["E_z0"])
     G, E = {}, {}
     for l, dz, E_dz, h, E_h in ((0, dz0, E_dz0, F["x"], np.zeros_like(F["x"])), (1, dz1, E_dz1, F["a0"], F["E_z0"]),
                                 (2, dy, E_dy, F["a1"], F["E_z1"])):
@@ -101,7 +110,7 @@ def loss_bound(W, x, a):
 
 def relu_edge(W, x, a):
     """the number of hidden pre-activations whose float64 value lies within its forward bound of zero: there a float32
-    evaluation may legitimately take the other side of the ReLU, and grad_bound (which assumes the same mask) does not hold"""
+    evaluation may legitimately take the other side of the ReLU, and grad_bound widens to cover both sides (_masked)"""
     F = forward64(W, x, a)
     return int(sum(np.count_nonzero(np.abs(F["z%d" % l]) <= F["E_z%d" % l]) for l in (0, 1)))
 

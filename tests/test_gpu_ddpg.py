@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import ddpg_ref as dd
+from loop_replay import Recorded
 from side_cases import Guarded, same_bits
 
 pytestmark = pytest.mark.gpu
@@ -291,25 +292,6 @@ def test_torch_update_is_within_the_bounds_of_the_reference(torch):
 
 
 # ---------------------------------------------------------------------------------------------------- the loop
-class Recorded:
-    """an env that keeps a copy of everything its step() was given and returned"""
-
-    def __init__(self, env):
-        self.env, self.log, self.first = env, [], None
-
-    def __getattr__(self, name):
-        return getattr(self.env, name)
-
-    def reset(self):
-        self.first = self.env.reset().clone()
-        return self.first
-
-    def step(self, a):
-        obs, rew, done, info = self.env.step(a)
-        self.log.append((a.clone(), obs.clone(), rew.clone(), done.clone()))
-        return obs, rew, done, info
-
-
 @pytest.mark.parametrize("update", ["hip", "torch"])
 def test_learn_fills_the_ring_and_changes_all_four_nets(torch, update):
     import quadsim_amd as qa

@@ -30,6 +30,7 @@ import pytest
 
 import mppi_ref
 import td3_ref as td
+from loop_replay import NORMAL_ABS
 from side_cases import Guarded, same_bits
 
 pytestmark = pytest.mark.gpu
@@ -37,7 +38,6 @@ pytestmark = pytest.mark.gpu
 KEYS, NETS, ONLINE = td.KEYS, td.NETS, td.ONLINE
 HYPER = dict(gamma=td.GAMMA, tau=td.TAU, actor_lr=1e-2, critic_lr=1e-2, policy_delay=td.DELAY, target_policy_noise=td.SIGMA,
              target_noise_clip=td.CLIP)
-NORMAL_ABS = 6.8e-6          # |device normal - float64 Box-Muller on the same words|: the bound tests/test_gpu_mppi.py asserts for normals_from_words
 
 
 @pytest.fixture(scope="module")
