@@ -24,6 +24,7 @@ from .trpo import (TRPO, check_trpo_args, reset_trpo_optimizer, torch_trpo_polic
                    vf_schedule)
 from .ddpg import DDPG, DDPGPolicy, OUNoise, ReplayBuffer, check_ddpg_args, ddpg_update, replay_schedule, torch_ddpg_update
 from .td3 import TD3, NormalActionNoise, TD3Policy, check_td3_args, reset_td3_optimizer, td3_update, torch_td3_update
+from .sac import SAC, SACPolicy, check_sac_args, reset_sac_optimizer, sac_update, torch_sac_update
 
 __all__ = ["VecDockingEnv", "DockingEnv", "MovingDockingEnv", "ImitatingDockingEnv", "HoveringEnv", "Drone", "controller", "make", "register_gym_ids",
            "shard_range", "build_library", "QuadsimError", "C3_INIT_RANGE", "drone_step_batch", "ctrl_batch",
@@ -36,6 +37,7 @@ __all__ = ["VecDockingEnv", "DockingEnv", "MovingDockingEnv", "ImitatingDockingE
            "DDPG", "DDPGPolicy", "ReplayBuffer", "OUNoise", "replay_schedule", "ddpg_update", "torch_ddpg_update", "check_ddpg_args",
            "TRPO", "check_trpo_args", "vf_schedule", "trpo_policy_step", "trpo_vf_fit", "reset_trpo_optimizer", "torch_trpo_policy_step",
            "torch_trpo_vf_fit",
-           "TD3", "TD3Policy", "NormalActionNoise", "td3_update", "torch_td3_update", "check_td3_args", "reset_td3_optimizer"]
+           "TD3", "TD3Policy", "NormalActionNoise", "td3_update", "torch_td3_update", "check_td3_args", "reset_td3_optimizer",
+           "SAC", "SACPolicy", "sac_update", "torch_sac_update", "check_sac_args", "reset_sac_optimizer"]
 
 register_gym_ids()

@@ -1,6 +1,7 @@
 """ctypes binding of libquadsim_hip.so (the C ABI declared in include/quadsim.h), and the table (SIDE), build, loader and call
-helper of the eight side libraries that dynplan.py, bc.py, ppo2.py, gail.py, trpo.py and ddpg.py wrap, and of the ninth that came
-after them (SIDE_MORE: td3.py's).
+helper of the eight side libraries that dynplan.py, bc.py, ppo2.py, gail.py, trpo.py and ddpg.py wrap, of td3.py's, which came
+after them (SIDE_MORE), and of sac.py's (SIDE_LATER): ten side libraries, eleven libraries with the main one -- which is how the
+headers count (libquadsim_td3.so is the tenth library, libquadsim_sac.so the eleventh).
 
 There is deliberately no fallback of any kind: if the HIP library is missing or
 no MI355X is visible, loading / qs_create raise.  Nothing here imports oracle/.
@@ -16,7 +17,7 @@ LIB_PATH = os.environ.get("QUADSIM_HIP_LIB") or os.path.join(CSRC, "libquadsim_h
 SOURCES = [os.path.join(CSRC, "quadsim_hip.hip")]
 # every fragment of the one translation unit is a rebuild dependency, bar those of the side libraries (SIDE below)
 HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp") and not h.startswith(
-    ("dynplan_", "dynmppi_", "dynfit_", "bcfit_", "ppo2_", "gail_", "ddpg_", "trpo_", "td3_", "train_", "side_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
+    ("dynplan_", "dynmppi_", "dynfit_", "bcfit_", "ppo2_", "gail_", "ddpg_", "trpo_", "td3_", "sac_", "train_", "side_"))) + [os.path.join(HERE, "..", "include", "quadsim.h")]
 
 QS_OK = 0
 KIND_V0, KIND_V2, KIND_V1, KIND_HOVER = 0, 1, 2, 3
@@ -218,6 +219,26 @@ class QstdHyper(C.Structure):
         (k, C.c_double) for k in ("gamma", "tau", "actor_lr", "critic_lr", "target_policy_noise", "target_noise_clip", "beta1", "beta2", "eps")]
 
 
+class QssNets(C.Structure):                    # include/quadsim_sac.h
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("w", C.c_void_p * 30), ("m", C.c_void_p * 24), ("v", C.c_void_p * 24),
+                ("alpha_state", C.c_void_p)]
+
+
+class QssReplay(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("n", C.c_int64)] + [
+        (k, C.c_void_p) for k in ("obs0", "act", "rew", "obs1", "done")]
+
+
+class QssHyper(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("auto_alpha", C.c_int32)] + [
+        (k, C.c_double) for k in ("gamma", "tau", "lr", "target_entropy", "beta1", "beta2", "eps")]
+
+
+class QssTrace(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("logp_out", "vlogp_out", "act_out", "fwd_out")]
+
+
 f64, psize, psix = C.c_double, C.POINTER(C.c_size_t), C.POINTER(vp * 6)
 # The eight libraries beside the main one, each its own translation unit, .so and code object, by short name, in build order.
 # They share at the source level only: device fragments (*_kernels.hpp, dynplan_image.hpp, train_pieces.hpp, quadsim_device.hpp)
@@ -321,14 +342,30 @@ SIDE_MORE = {
                                     vp, u64, vp, C.POINTER(vp * 18), vp]}),
 }
 ALL_SIDE = dict(SIDE, **SIDE_MORE)               # the same entry objects, in build order
+# A third table of the same shape, for what came after TD3.  SIDE, SIDE_MORE and ALL_SIDE stay what the tests of those nine
+# libraries hold them to; EVERY_SIDE is the union that everything below that takes a key looks in.
+SIDE_LATER = {
+    # the SAC update (sac.py): the five nets' own tensors and the temperature; the tower pieces and the streamed nets of
+    # train_pieces.hpp, q_tanh, q_ln, the Philox counter and the normals of the main library
+    "sac": dict(env="QUADSIM_SAC_LIB", file="libquadsim_sac.so", source="sac.hip", header="quadsim_sac.h", prefix="qss_", kernels=b"k_sac_",
+                fragments=("sac_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
+                signatures={
+                    "qss_version": [],
+                    "qss_last_error": ([], C.c_char_p),
+                    "qss_workspace_bytes": [psize],
+                    "qss_update": [C.POINTER(QssNets), C.POINTER(QssReplay), vp, vp, i32, i32, C.POINTER(QssHyper), i64, vp, u64, vp, vp, u64,
+                                   vp, C.POINTER(QssTrace), C.POINTER(vp * 24), vp],
+                    "qss_math": [i32, vp, vp, i64, vp]}),
+}
+EVERY_SIDE = dict(ALL_SIDE, **SIDE_LATER)        # the same entry objects, in build order
 
 
 def side_entry(key):
     """the table entry of the side library `key`, whichever table holds it"""
-    return ALL_SIDE[key]
+    return EVERY_SIDE[key]
 
 
-for _e in ALL_SIDE.values():
+for _e in EVERY_SIDE.values():
     _e["path"] = os.environ.get(_e["env"]) or os.path.join(CSRC, _e["file"])
     _e["sources"] = [os.path.join(CSRC, _e["source"])]
     _e["headers"] = [os.path.join(CSRC, h) for h in _e["fragments"]] + [os.path.join(HERE, "..", "include", _e["header"])]
@@ -336,7 +373,7 @@ for _e in ALL_SIDE.values():
 # the positions of every entry point's pointer parameters: side_call sends those through as_arg and leaves the scalars to the
 # argtypes (as_arg on a scalar costs 0.3 us, and a plan has a dozen of them)
 SIDE_POINTERS = {name: tuple(i for i, t in enumerate(sig[0] if isinstance(sig, tuple) else sig) if t is vp or issubclass(t, C._Pointer))
-                 for _e in ALL_SIDE.values() for name, sig in _e["signatures"].items()}
+                 for _e in EVERY_SIDE.values() for name, sig in _e["signatures"].items()}
 
 
 class QuadsimError(RuntimeError):
@@ -373,9 +410,9 @@ def build_one_library(sources, deps, out, link=(), force=False, verbose=False):
 
 
 def build_library(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all ten libraries, returns the main one's
-    path."""
-    for e in ALL_SIDE.values():
+    """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all eleven libraries (the ten side libraries, then the
+    main one), returns the main one's path."""
+    for e in EVERY_SIDE.values():
         build_one_library(e["sources"], e["headers"], e["path"], (), force, verbose)
     return build_one_library(SOURCES, HEADERS, LIB_PATH, ["-lhsa-runtime64"], force, verbose)
 
@@ -454,7 +491,7 @@ _side = {}
 
 
 def side_load(key):
-    """dlopen the side library `key` of SIDE or SIDE_MORE, once; raises QuadsimError if it has not been built (there is no fallback)"""
+    """dlopen the side library `key` of SIDE, SIDE_MORE or SIDE_LATER, once; raises QuadsimError if it has not been built (there is no fallback)"""
     lib = _side.get(key)
     if lib is None:
         e = side_entry(key)

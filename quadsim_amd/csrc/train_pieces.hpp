@@ -1,5 +1,5 @@
 // train_pieces.hpp -- the device pieces every trainer library is built from.  A fragment of dynfit.hip, gail.hip, bcfit.hip,
-// ppo2.hip, trpo.hip, ddpg.hip and td3.hip; it defines no kernel.  Two sections:
+// ppo2.hip, trpo.hip, ddpg.hip, td3.hip and sac.hip; it defines no kernel.  Two sections:
 //
 // CHUNK PRIMITIVES (k_dyn_fit, k_gail_fit and the tower trainers alike).  A net lives in LDS in torch's (out, in) orientation, rows
 // LD = in + 4 floats apart (a ds_read_b128 per lane fetches four k of one unit; LD = 4 mod 16 words puts 16 units on 16
@@ -182,7 +182,9 @@ struct NoExtra {
 // The backward pass of a chunk from dy in the plane y: the gradients of the chunk's rows into G, rows ascending, dz1 into the
 // plane d2 and dz0 into d1 under the masks of a2 and a1.  Three phases, two barriers between them, none before or after.
 // `extra` runs in phase B between the gradient of layer 1 and the bias sum (DDPG's critic: the four action rows of w1).
-template <class L, class Extra = NoExtra>
+// HEAD: the rows of w3 and of the plane y that dz1 is summed over (SAC's actor: eight, the log-std head behind the mean's; the
+// gradient of rows 4 .. 7 is the caller's).
+template <class L, class Extra = NoExtra, int HEAD = kOut>
 __device__ __forceinline__ void backward_chunk(float *lds, Acc &G, Extra extra = Extra())
 {
     const int t = threadIdx.x;
@@ -203,7 +205,7 @@ __device__ __forceinline__ void backward_chunk(float *lds, Acc &G, Extra extra =
         const int ig = t >> 2, rg = t & 3;
         f32x4 acc[4] = {};
 #pragma unroll
-        for (int o = 0; o < kOut; ++o) {
+        for (int o = 0; o < HEAD; ++o) {
             const f32x4 wo = ld4(lds + L::w3 + o * L::ld3 + 4 * ig), dz = ld4(lds + L::y + o * kRP + 4 * rg);
 #pragma unroll
             for (int a = 0; a < 4; ++a)

@@ -90,13 +90,14 @@ def check_td3_args(n, steps, batch, gamma=0.99, tau=5.0e-3, actor_lr=3.0e-4, cri
             actor_t0)
 
 
-def keyed_noise(seed, t0, steps, batch):
+def keyed_noise(seed, t0, steps, batch, stream=TD3_NOISE_STREAM):
     """-> [steps, batch, 4] float32: the target noise that a call without `noise` draws, restated on the host: Box-Muller in float64 on
     the words of Philox4x32-10 block t0 + s of subsequence (6 << 48) | row slot, key `seed` (the device's own arithmetic is float32:
-    it differs from this in the last digits; ``noise_out`` of td3_update has the device's values)"""
+    it differs from this in the last digits; ``noise_out`` of td3_update has the device's values).  `stream`: the Philox stream in
+    place of 6 (sac.py draws on 7)"""
     m32 = np.uint64(0xFFFFFFFF)
     block = np.broadcast_to(np.arange(int(t0), int(t0) + int(steps), dtype=np.uint64)[:, None], (int(steps), int(batch)))
-    sub = (np.uint64(TD3_NOISE_STREAM) << np.uint64(48)) | np.arange(int(batch), dtype=np.uint64)[None, :]
+    sub = (np.uint64(stream) << np.uint64(48)) | np.arange(int(batch), dtype=np.uint64)[None, :]
     c0, c1, c2, c3 = block & m32, block >> np.uint64(32), np.broadcast_to(sub & m32, block.shape), np.broadcast_to(sub >> np.uint64(32), block.shape)
     k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
     for _ in range(10):
