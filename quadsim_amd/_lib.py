@@ -1,7 +1,7 @@
 """ctypes binding of libquadsim_hip.so (the C ABI declared in include/quadsim.h), and the table (SIDE), build, loader and call
-helper of the eight side libraries that dynplan.py, bc.py, ppo2.py, gail.py, trpo.py and ddpg.py wrap, of td3.py's, which came
-after them (SIDE_MORE), and of sac.py's (SIDE_LATER): ten side libraries, eleven libraries with the main one -- which is how the
-headers count (libquadsim_td3.so is the tenth library, libquadsim_sac.so the eleventh).
+helper of the ten side libraries that dynplan.py, bc.py, ppo2.py, gail.py, trpo.py, ddpg.py, td3.py and sac.py wrap: eleven
+libraries with the main one -- which is how the headers count (libquadsim_td3.so is the tenth library, libquadsim_sac.so the
+eleventh).
 
 There is deliberately no fallback of any kind: if the HIP library is missing or
 no MI355X is visible, loading / qs_create raise.  Nothing here imports oracle/.
@@ -195,9 +195,12 @@ class QsddNets(C.Structure):                   # include/quadsim_ddpg.h
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("w", C.c_void_p * 24), ("m", C.c_void_p * 12), ("v", C.c_void_p * 12)]
 
 
-class QsddReplay(C.Structure):
+class QsddReplay(C.Structure):                 # the one replay struct of the three off-policy headers (QstdReplay, QssReplay below)
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("n", C.c_int64)] + [
         (k, C.c_void_p) for k in ("obs0", "act", "rew", "obs1", "done")]
+
+
+QstdReplay = QssReplay = QsddReplay
 
 
 class QsddHyper(C.Structure):
@@ -209,11 +212,6 @@ class QstdNets(C.Structure):                   # include/quadsim_td3.h
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("w", C.c_void_p * 36), ("m", C.c_void_p * 18), ("v", C.c_void_p * 18)]
 
 
-class QstdReplay(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("n", C.c_int64)] + [
-        (k, C.c_void_p) for k in ("obs0", "act", "rew", "obs1", "done")]
-
-
 class QstdHyper(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("policy_delay", C.c_int32)] + [
         (k, C.c_double) for k in ("gamma", "tau", "actor_lr", "critic_lr", "target_policy_noise", "target_noise_clip", "beta1", "beta2", "eps")]
@@ -222,11 +220,6 @@ class QstdHyper(C.Structure):
 class QssNets(C.Structure):                    # include/quadsim_sac.h
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("w", C.c_void_p * 30), ("m", C.c_void_p * 24), ("v", C.c_void_p * 24),
                 ("alpha_state", C.c_void_p)]
-
-
-class QssReplay(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("n", C.c_int64)] + [
-        (k, C.c_void_p) for k in ("obs0", "act", "rew", "obs1", "done")]
 
 
 class QssHyper(C.Structure):
@@ -240,9 +233,10 @@ class QssTrace(C.Structure):
 
 
 f64, psize, psix = C.c_double, C.POINTER(C.c_size_t), C.POINTER(vp * 6)
-# The eight libraries beside the main one, each its own translation unit, .so and code object, by short name, in build order.
-# They share at the source level only: device fragments (*_kernels.hpp, dynplan_image.hpp, train_pieces.hpp, quadsim_device.hpp)
-# and the host fragments side_host.hpp (all eight) and dynplan_host.hpp (the two planners).  An entry: the variable that overrides
+# The ten libraries beside the main one, each its own translation unit, .so and code object, by short name, in build order.
+# They share at the source level only: device fragments (*_kernels.hpp, dynplan_image.hpp, train_pieces.hpp, train_offpolicy.hpp,
+# quadsim_device.hpp) and the host fragments side_host.hpp (all ten), dynplan_host.hpp (the two planners) and side_offpolicy.hpp
+# (the three off-policy trainers).  An entry: the variable that overrides
 # the path (A/B builds) and the file name, the source, the fragments it is rebuilt for, the public header, the prefix that the
 # kernel names of its code object start with and no kernel name of another library does, and the signatures of its entry points
 # in the header's order -- argument types or, where the result is not int, (argument types, result type).  Everything else is
@@ -317,38 +311,30 @@ SIDE = {
                      "qst_policy_step": [C.POINTER(QstNet), C.POINTER(QstBatch), i32, C.POINTER(QstHyper), vp, u64, vp, vp,
                                          C.POINTER(QstTrace), vp],
                      "qst_vf_fit": [C.POINTER(QstNet), vp, vp, i64, vp, i32, i32, f64, f64, f64, f64, i64, vp, psix, vp]}),
-    # the DDPG update (ddpg.py): the four nets' own tensors; the tower pieces of train_pieces.hpp, q_tanh of the main library
+    # the DDPG update (ddpg.py): the four nets' own tensors; the tower pieces of train_pieces.hpp, the off-policy pieces of
+    # train_offpolicy.hpp and side_offpolicy.hpp, q_tanh of the main library
     "ddpg": dict(env="QUADSIM_DDPG_LIB", file="libquadsim_ddpg.so", source="ddpg.hip", header="quadsim_ddpg.h", prefix="qsdd_", kernels=b"k_ddpg_",
-                 fragments=("ddpg_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
+                 fragments=("ddpg_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "side_offpolicy.hpp", "train_offpolicy.hpp", "train_pieces.hpp"),
                  signatures={
                      "qsdd_version": [],
                      "qsdd_last_error": ([], C.c_char_p),
                      "qsdd_workspace_bytes": [psize],
                      "qsdd_update": [C.POINTER(QsddNets), C.POINTER(QsddReplay), vp, vp, i32, i32, C.POINTER(QsddHyper), i64, vp, u64, vp,
                                      C.POINTER(vp * 12), vp]}),
-}
-# The libraries that came after the eight: a second table of the same shape.  Everything below that takes a key looks it up in
-# either (side_entry); the tests of the eight hold SIDE itself to their list.
-SIDE_MORE = {
-    # the TD3 update (td3.py): the six nets' own tensors; the tower pieces and the streamed nets of train_pieces.hpp, q_tanh, the
-    # Philox counter and the normals of the main library
+    # the TD3 update (td3.py): the six nets' own tensors; the tower pieces and the streamed nets of train_pieces.hpp, the off-policy
+    # pieces, q_tanh, the Philox counter and the normals of the main library
     "td3": dict(env="QUADSIM_TD3_LIB", file="libquadsim_td3.so", source="td3.hip", header="quadsim_td3.h", prefix="qstd_", kernels=b"k_td3_",
-                fragments=("td3_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
+                fragments=("td3_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "side_offpolicy.hpp", "train_offpolicy.hpp", "train_pieces.hpp"),
                 signatures={
                     "qstd_version": [],
                     "qstd_last_error": ([], C.c_char_p),
                     "qstd_workspace_bytes": [psize],
                     "qstd_update": [C.POINTER(QstdNets), C.POINTER(QstdReplay), vp, vp, i32, i32, C.POINTER(QstdHyper), i64, i64, vp, u64, vp,
                                     vp, u64, vp, C.POINTER(vp * 18), vp]}),
-}
-ALL_SIDE = dict(SIDE, **SIDE_MORE)               # the same entry objects, in build order
-# A third table of the same shape, for what came after TD3.  SIDE, SIDE_MORE and ALL_SIDE stay what the tests of those nine
-# libraries hold them to; EVERY_SIDE is the union that everything below that takes a key looks in.
-SIDE_LATER = {
     # the SAC update (sac.py): the five nets' own tensors and the temperature; the tower pieces and the streamed nets of
-    # train_pieces.hpp, q_tanh, q_ln, the Philox counter and the normals of the main library
+    # train_pieces.hpp, the off-policy pieces, q_tanh, q_ln, the Philox counter and the normals of the main library
     "sac": dict(env="QUADSIM_SAC_LIB", file="libquadsim_sac.so", source="sac.hip", header="quadsim_sac.h", prefix="qss_", kernels=b"k_sac_",
-                fragments=("sac_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"),
+                fragments=("sac_kernels.hpp", "quadsim_device.hpp", "side_host.hpp", "side_offpolicy.hpp", "train_offpolicy.hpp", "train_pieces.hpp"),
                 signatures={
                     "qss_version": [],
                     "qss_last_error": ([], C.c_char_p),
@@ -357,15 +343,7 @@ SIDE_LATER = {
                                    vp, C.POINTER(QssTrace), C.POINTER(vp * 24), vp],
                     "qss_math": [i32, vp, vp, i64, vp]}),
 }
-EVERY_SIDE = dict(ALL_SIDE, **SIDE_LATER)        # the same entry objects, in build order
-
-
-def side_entry(key):
-    """the table entry of the side library `key`, whichever table holds it"""
-    return EVERY_SIDE[key]
-
-
-for _e in EVERY_SIDE.values():
+for _e in SIDE.values():
     _e["path"] = os.environ.get(_e["env"]) or os.path.join(CSRC, _e["file"])
     _e["sources"] = [os.path.join(CSRC, _e["source"])]
     _e["headers"] = [os.path.join(CSRC, h) for h in _e["fragments"]] + [os.path.join(HERE, "..", "include", _e["header"])]
@@ -373,7 +351,7 @@ for _e in EVERY_SIDE.values():
 # the positions of every entry point's pointer parameters: side_call sends those through as_arg and leaves the scalars to the
 # argtypes (as_arg on a scalar costs 0.3 us, and a plan has a dozen of them)
 SIDE_POINTERS = {name: tuple(i for i, t in enumerate(sig[0] if isinstance(sig, tuple) else sig) if t is vp or issubclass(t, C._Pointer))
-                 for _e in EVERY_SIDE.values() for name, sig in _e["signatures"].items()}
+                 for _e in SIDE.values() for name, sig in _e["signatures"].items()}
 
 
 class QuadsimError(RuntimeError):
@@ -412,7 +390,7 @@ def build_one_library(sources, deps, out, link=(), force=False, verbose=False):
 def build_library(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU.  Builds all eleven libraries (the ten side libraries, then the
     main one), returns the main one's path."""
-    for e in EVERY_SIDE.values():
+    for e in SIDE.values():
         build_one_library(e["sources"], e["headers"], e["path"], (), force, verbose)
     return build_one_library(SOURCES, HEADERS, LIB_PATH, ["-lhsa-runtime64"], force, verbose)
 
@@ -491,10 +469,10 @@ _side = {}
 
 
 def side_load(key):
-    """dlopen the side library `key` of SIDE, SIDE_MORE or SIDE_LATER, once; raises QuadsimError if it has not been built (there is no fallback)"""
+    """dlopen the side library `key` of SIDE, once; raises QuadsimError if it has not been built (there is no fallback)"""
     lib = _side.get(key)
     if lib is None:
-        e = side_entry(key)
+        e = SIDE[key]
         if not os.path.exists(e["path"]):
             raise QuadsimError("%s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'`." % e["path"])
         import torch  # noqa: F401  (its HIP runtime must be the resident one: see load)
@@ -508,7 +486,7 @@ def side_load(key):
 
 def side_check(key, rc, what):
     if rc != 0:
-        msg = getattr(side_load(key), side_entry(key)["prefix"] + "last_error")().decode("utf-8", "replace")
+        msg = getattr(side_load(key), SIDE[key]["prefix"] + "last_error")().decode("utf-8", "replace")
         raise QuadsimError("%s failed (%d): %s" % (what, rc, msg))
 
 

@@ -1,6 +1,9 @@
 // ddpg_kernels.hpp -- the kernels of libquadsim_ddpg.so (include/quadsim_ddpg.h has the numerical contract).  A fragment of
-// ddpg.hip, nowhere else.  Built from train_pieces.hpp: the chunk primitives and the tower pieces (the LDS image and its loader,
-// the element map, backward_chunk); q_tanh is quadsim_device.hpp's.
+// ddpg.hip, nowhere else.  Built from train_pieces.hpp (the chunk primitives and the tower pieces: the LDS image and its loader,
+// the element map, backward_chunk) and from train_offpolicy.hpp (the flat net, the copy table, clampsel, the TD target and a
+// critic's forward pass with dq); q_tanh is quadsim_device.hpp's.  Three pieces of train_offpolicy.hpp are written out below,
+// because called they compile to another kernel here: the replay gather (gather_critic, here with the clamp), the sums of the statistics (critic_sums)
+// and the Adam-and-Polyak tail (apply_step).  A change to one of them must be made here too.
 //
 // One train step is ONE launch, and the kernel boundary is the only ordering across workgroups:
 //   k_ddpg_step  grid (2).  Workgroup 0 is the critic branch: the online critic 12 -> 128 -> (128 + 4 actions) -> 128 -> 1 in LDS
@@ -17,24 +20,17 @@
 // of a call reads buffer s & 1 and writes buffer (s + 1) & 1.  Moments and gradients have one copy: only their branch touches
 // them.  Nothing waits on another workgroup, there is no grid barrier and no float atomic.
 #pragma once
-#include "train_pieces.hpp"
+#include "train_offpolicy.hpp"
 
 namespace qsdd {
 
 using namespace qsf;
 
-constexpr int kAct = 4;
-constexpr int kCopyBlock = 256, kCopyTensors = 60;            // 24 weights, 24 moments, 12 gradients
+constexpr int kCopyTensors = 60;            // 24 weights, 24 moments, 12 gradients
 
-// a net as it lies flat in the workspace, tensors in the ABI's order and the policy's (in, out) layout.  B = 0: the critic (layer
-// 1 has 132 inputs, one output), B = 1: the actor
+// the flat nets.  B = 0: the critic (layer 1 has 132 inputs, one output), B = 1: the actor
 template <int B>
-struct Flat {
-    static constexpr int k1 = B ? kH : kH + kAct, outs = B ? kAct : 1;
-    static constexpr int w0 = 0, b0 = w0 + kIn * kH, w1 = b0 + kH, b1 = w1 + k1 * kH, w2 = b1 + kH, b2 = w2 + kH * outs;
-    static constexpr int floats = (b2 + outs + 3) & ~3;
-    static constexpr int at(int k) { return k == 0 ? w0 : k == 1 ? b0 : k == 2 ? w1 : k == 3 ? b1 : k == 4 ? w2 : b2; }   // slot k's start
-};
+using Flat = FlatNet<kIn, B ? kH : kH + kAct, B ? kAct : 1>;
 constexpr int net_at(int b) { return b ? 0 : Flat<1>::floats; }                     // in a buffer: actor | critic | the two targets
 constexpr int kOnline = Flat<0>::floats + Flat<1>::floats, kBuf = 2 * kOnline;     // a target lies kOnline after its online net
 // the workspace, in floats: two buffers, then m, v and the gradients of the two online nets (laid out as the online nets are)
@@ -50,12 +46,7 @@ struct StepArgs {
     int batch, cur, want_grads;
 };
 
-struct CopyArgs {
-    float *t[kCopyTensors];
-    int at[kCopyTensors], n[kCopyTensors];
-    float *ws;
-    int to_ws;
-};
+struct CopyArgs : CopyTable<kCopyTensors> {};
 
 // the tower's image with a1 132 units high in either branch; the critic's rows of w2 are 140 apart (132 and 140: 4 and 12 mod 32
 // words)
@@ -71,9 +62,6 @@ constexpr int kLdsFloats = Layout<0>::floats > Layout<1>::floats ? Layout<0>::fl
 
 // (stream_layer, stream_head and tanh_keep_nan are train_pieces.hpp's: the TD3 kernels stream their nets the same way)
 
-// (selects, not fminf(fmaxf()): those would turn a NaN observation into -clip; an infinity is clamped as any other value)
-__device__ __forceinline__ float clamp_obs(float v, float clip) { return v < -clip ? -clip : v > clip ? clip : v; }
-
 template <int B>
 __device__ __forceinline__ void branch(float *lds, const StepArgs &S)
 {
@@ -88,8 +76,7 @@ __device__ __forceinline__ void branch(float *lds, const StepArgs &S)
     // ---- the online net into LDS (the chunk loop opens with the barrier)
     load_image<L, F::k1>(lds, L::floats, F::outs, [&](int k, int i) { return net[F::at(k) + i]; });
 
-    int rows = S.counts ? S.counts[0] : S.batch;
-    rows = rows < S.batch ? rows : S.batch;
+    const int rows = step_rows(S);
     const float dscale = (float)(2.0 / (double)rows), ninv = -(float)(1.0 / (double)rows), frows = (float)rows;
 
     // ---- the gradient elements of this thread; the critic's four action rows of w1 are one element a thread more: input
@@ -111,8 +98,8 @@ __device__ __forceinline__ void branch(float *lds, const StepArgs &S)
             const float *at = cur + net_at(1) + kOnline, *ct = cur + net_at(0) + kOnline;
             float pre = 0.0f;                            // the thread's value of (obs0 | act), fetched under the target pass
             if (gc < kIn) {
-                lds[L::x + gc * kRP + gr] = idx < 0 ? 0.0f : clamp_obs(S.obs1[(int64_t)idx * kIn + gc], S.clip);
-                pre = idx < 0 ? 0.0f : clamp_obs(S.obs0[(int64_t)idx * kIn + gc], S.clip);
+                lds[L::x + gc * kRP + gr] = idx < 0 ? 0.0f : clampsel(S.obs1[(int64_t)idx * kIn + gc], -S.clip, S.clip);
+                pre = idx < 0 ? 0.0f : clampsel(S.obs0[(int64_t)idx * kIn + gc], -S.clip, S.clip);
             } else if (gc < kIn + kAct) {
                 pre = idx < 0 ? 0.0f : S.act[(int64_t)idx * kAct + (gc - kIn)];
             } else if (gc == kIn + kAct) {
@@ -134,26 +121,13 @@ __device__ __forceinline__ void branch(float *lds, const StepArgs &S)
             if (t < kRows) {
                 const float q1 = stream_head<1>(ct + Flat<0>::w2, ct + Flat<0>::b2, lds + L::a2);
                 const float rew = lds[L::sc + t], done = lds[L::sc + kRP + t];
-                lds[L::sc + 2 * kRP + t] = done >= 1.0f ? rew : __fmaf_rn(__fmul_rn(__fsub_rn(1.0f, done), S.gamma), q1, rew);
+                lds[L::sc + 2 * kRP + t] = td_target(rew, done, S.gamma, q1);
             }
             if (gc < kIn) lds[L::x + gc * kRP + gr] = pre;
             else if (gc < kIn + kAct) lds[L::a1 + (kH + gc - kIn) * kRP + gr] = pre;
             __syncthreads();
             // ---- the critic on (obs0, act), then dq over y's first row
-            forward_layer<true>(lds + L::w1, L::ld1, lds + L::b1, lds + L::x, kInP, kH, lds + L::a1);
-            __syncthreads();
-            forward_layer<true>(lds + L::w2, L::ld2, lds + L::b2, lds + L::a1, kH + kAct, kH, lds + L::a2);
-            __syncthreads();
-            forward_layer<false>(lds + L::w3, L::ld3, lds + L::b3, lds + L::a2, kH, kOut, lds + L::y);
-            __syncthreads();
-            if (t < kRows) {
-                const bool valid = r0 + t < rows;
-                const float q = lds[L::y + t], d = valid ? __fsub_rn(q, lds[L::sc + 2 * kRP + t]) : 0.0f;
-                lds[L::sc + 3 * kRP + t] = q;
-                lds[L::sc + 4 * kRP + t] = d;
-                lds[L::y + t] = __fmul_rn(d, dscale);
-            }
-            __syncthreads();
+            critic_forward_dq<L, kH + kAct, true>(lds, r0, rows, dscale);
             if (t == kStatT) {
                 for (int r = 0; r < kRows && r0 + r < rows; ++r) {
                     const float d = lds[L::sc + 4 * kRP + r];
@@ -165,7 +139,7 @@ __device__ __forceinline__ void branch(float *lds, const StepArgs &S)
         } else {
             // ---- pi = actor(obs0), q(obs0, pi) with the online critic streamed, dq/da into y
             const float *cr = cur + net_at(0);
-            if (gc < kIn) lds[L::x + gc * kRP + gr] = idx < 0 ? 0.0f : clamp_obs(S.obs0[(int64_t)idx * kIn + gc], S.clip);
+            if (gc < kIn) lds[L::x + gc * kRP + gr] = idx < 0 ? 0.0f : clampsel(S.obs0[(int64_t)idx * kIn + gc], -S.clip, S.clip);
             __syncthreads();
             forward_layer<true>(lds + L::w1, L::ld1, lds + L::b1, lds + L::x, kInP, kH, lds + L::a1);
             stream_layer<true>(cr + Flat<0>::w0, cr + Flat<0>::b0, lds + L::x, kIn, lds + L::c1);
@@ -252,13 +226,7 @@ __global__ __launch_bounds__(kFitBlock) void k_ddpg_step(StepArgs S)
 
 __global__ __launch_bounds__(kCopyBlock) void k_ddpg_copy(CopyArgs C)
 {
-    const int k = blockIdx.x;
-    float *t = C.t[k], *w = C.ws + C.at[k];
-    if (!t) return;
-    for (int i = threadIdx.x; i < C.n[k]; i += kCopyBlock) {
-        if (C.to_ws) w[i] = t[i];
-        else t[i] = w[i];
-    }
+    copy_tensor(C);
 }
 
 }  // namespace qsdd

@@ -1,7 +1,11 @@
 // sac_kernels.hpp -- the kernels of libquadsim_sac.so (include/quadsim_sac.h has the numerical contract).  A fragment of sac.hip,
-// nowhere else.  Built from train_pieces.hpp: the chunk primitives, the tower pieces (the LDS image and its loader, the element map,
-// backward_chunk), the streamed forward pass of a net that lies in memory and tanh_keep_nan; q_ln, philox_counter and
-// normals_from_words are quadsim_device.hpp's.
+// nowhere else.  Built from train_pieces.hpp (the chunk primitives, the tower pieces -- the LDS image and its loader, the element map,
+// backward_chunk --, the streamed forward pass of a net that lies in memory and tanh_keep_nan) and from train_offpolicy.hpp (the
+// flat net, the copy table, the twin minimum, the noise load, a critic's replay gather and forward pass with dq, the backward pass
+// through the streamed q1 and the Adam-and-Polyak tail); q_ln, philox_counter and normals_from_words are quadsim_device.hpp's.
+// Three pieces of train_offpolicy.hpp are written out below, because called they compile to another kernel here: td_target and
+// critic_sums in the critic branch, and the action rows of w0, which td3_kernels.hpp holds in the same words.  A change to one of
+// them must be made here too.
 //
 // One update is ONE launch, and the kernel boundary is the only ordering across workgroups:
 //   k_sac_step   grid (4).  Workgroups 0 and 1 are the critic branches of q1 and q2: the online critic 16 -> 128 -> 128 -> 1 in LDS in
@@ -20,31 +24,23 @@
 // parity of the step says which one holds them now.  Moments and gradients have one copy: only their branch touches them.  Nothing
 // waits on another workgroup, there is no grid barrier and no float atomic.
 #pragma once
-#include "train_pieces.hpp"
+#include "train_offpolicy.hpp"
 
 namespace qssac {
 
 using namespace qsf;
 
-constexpr int kAct = 4, kHead = 2 * kAct, kCIn = kIn + kAct;
+constexpr int kHead = 2 * kAct;
 constexpr int kNets = 5, kOnlineNets = 4;                     // the ABI's order: actor, q1, q2, v, then v_target
-constexpr int kCopyBlock = 256, kMathBlock = 256;
+constexpr int kMathBlock = 256;
 constexpr int kCopyTensors = 6 * kNets + 12 * kOnlineNets + 6 * kOnlineNets + 2;      // weights, moments, gradients, alpha_state in two parts
 constexpr uint64_t kStreamNoise = 7;                          // the Philox stream of the sample's noise (0 .. 6 are taken)
 constexpr float kL2Pi = 1.8378770664093453f, kE6 = 1.0e-6f, kLsLo = -20.0f, kLsHi = 2.0f;
-static_assert(kCIn == kInP, "a critic's layer 0 fills the tower image's sixteen input rows");
 
-// a net as it lies flat in the workspace, tensors in the ABI's order and the policy's (in, out) layout
-template <int K0, int OUTS>
-struct Flat {
-    static constexpr int k0 = K0, outs = OUTS;
-    static constexpr int w0 = 0, b0 = w0 + k0 * kH, w1 = b0 + kH, b1 = w1 + kH * kH, w2 = b1 + kH, b2 = w2 + kH * outs;
-    static constexpr int floats = (b2 + outs + 3) & ~3;
-    static constexpr int at(int k) { return k == 0 ? w0 : k == 1 ? b0 : k == 2 ? w1 : k == 3 ? b1 : k == 4 ? w2 : b2; }   // slot k's start
-};
-using FA = Flat<kIn, kHead>;                     // the actor
-using FC = Flat<kCIn, 1>;                        // a critic
-using FV = Flat<kIn, 1>;                         // the value net and its target
+// the flat nets
+using FA = FlatNet<kIn, kH, kHead>;                    // the actor
+using FC = FlatNet<kCIn, kH, 1>;                       // a critic
+using FV = FlatNet<kIn, kH, 1>;                        // the value net and its target
 // net k in a buffer: actor | q1 | q2 | v | v_target
 constexpr int net_at(int k) { return k == 0 ? 0 : FA::floats + (k < 3 ? k - 1 : 2) * FC::floats + (k < 4 ? 0 : FV::floats); }
 constexpr int kOnline = net_at(4), kBuf = kOnline + FV::floats;
@@ -66,12 +62,7 @@ struct StepArgs {
     int batch, cur, auto_alpha, want_grads;      // cur: the buffer that holds every net and log_alpha before this step
 };
 
-struct CopyArgs {
-    float *t[kCopyTensors];
-    int at[kCopyTensors], n[kCopyTensors];
-    float *ws;
-    int to_ws;
-};
+struct CopyArgs : CopyTable<kCopyTensors> {};
 
 // where net k lies before the step, and where the step puts it
 __device__ __forceinline__ const float *net_cur(const StepArgs &S, int k) { return S.ws + S.cur * kBuf + net_at(k); }
@@ -105,9 +96,6 @@ constexpr int kLdsFloats = LayoutA::floats > LayoutV::floats ? (LayoutA::floats 
                                                              : (LayoutV::floats > LayoutC::floats ? LayoutV::floats : LayoutC::floats);
 static_assert(kLdsFloats * 4 <= 160 * 1024, "LDS");
 
-// (a select, not fminf(fmaxf()): those would drop a NaN; an infinity is clamped as any other value)
-__device__ __forceinline__ float clampsel(float v, float lo, float hi) { return v < lo ? lo : v > hi ? hi : v; }
-
 // ln(1 - a^2 + 1e-6) from the computed a
 __device__ __forceinline__ float jac_ln(float a) { return qs::q_ln(__fadd_rn(__fmaf_rn(-a, a, 1.0f), kE6)); }
 
@@ -129,56 +117,15 @@ __device__ __forceinline__ Sample sample(float mu, float ls_raw, float z)
     return s;
 }
 
-// the four normals of row slot `slot` into the planes zn: the caller's, or Philox block u of subsequence (7 << 48) | slot
-__device__ __forceinline__ void load_noise(float *zn, const StepArgs &S, int slot, int gr, bool valid, bool write_out)
-{
-    float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (valid) {
-        if (S.noise) {
-#pragma unroll
-            for (int c = 0; c < kAct; ++c) z[c] = S.noise[(int64_t)slot * kAct + c];
-        } else {
-            qs::normals_from_words(qs::philox_counter(S.seed, (kStreamNoise << 48) | (uint64_t)slot, S.u), z);
-        }
-        if (S.noise_out && write_out) {
-#pragma unroll
-            for (int c = 0; c < kAct; ++c) S.noise_out[(int64_t)slot * kAct + c] = z[c];
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < kAct; ++c) zn[c * kRP + gr] = z[c];
-}
-
-// Adam on the thread's own elements (m and v through memory, the weight from LDS into the net's next place), then, for the value
-// net, the target's average with the new weight.  No thread reads another's element here.  ACTION_ROWS: the four action rows of a
-// critic's w0, which the owners of layer 0's padding in the tower's map hold in g1
+// the Adam step of online net k (train_offpolicy.hpp's apply_step); TARGET: the value net's, which takes v_target along
 template <class L, class F, bool ACTION_ROWS, bool TARGET, class More>
 __device__ __forceinline__ void apply_step(float *lds, const StepArgs &S, int k, const Acc &G, More more)
 {
-    const int t = threadIdx.x;
     const Adam A{S.b1f, S.b2f, S.omb1, S.omb2, S.eps, S.lr_t};
-    float *wn = net_nxt(S, k), *m = S.ws + kWsM + net_at(k), *v = S.ws + kWsV + net_at(k);
-    float *gout = S.want_grads ? S.ws + kWsG + net_at(k) : nullptr;
-    const float *tc = net_cur(S, kOnlineNets);
-    float *tn = net_nxt(S, kOnlineNets);
-    auto apply = [&](float g, float *lw, int e) {
-        adam_step(A, g, lw, wn, m, v, gout, e);
-        if (TARGET) tn[e] = __fmaf_rn(S.tau, *lw, __fmul_rn(S.omt, tc[e]));
-    };
-    for_own<L, F::outs>(t, [&](int off, int idx, int slot, const float &g) { apply(g, lds + off, F::at(slot) + idx); }, G);
-    if (ACTION_ROWS) {
-        const int o1 = t & 127;
-        if ((t >> 7) == 3) {
-#pragma unroll
-            for (int a = 0; a < kAct; ++a) apply(G.g1[a], lds + L::w1 + o1 * L::ld1 + kIn + a, F::w0 + (kIn + a) * kH + o1);
-        }
-    }
-    more(apply);
+    const StepPlaces P{net_nxt(S, k), S.ws + kWsM + net_at(k), S.ws + kWsV + net_at(k), S.want_grads ? S.ws + kWsG + net_at(k) : nullptr,
+                       net_cur(S, kOnlineNets), net_nxt(S, kOnlineNets)};
+    qsf::apply_step<L, F, ACTION_ROWS>(lds, A, P, S.tau, S.omt, TARGET, G, more);
 }
-struct NoMore {
-    template <class Fn>
-    __device__ __forceinline__ void operator()(Fn) const {}
-};
 
 // ---- a critic branch: k = 1 (q1) or 2 (q2)
 __device__ __forceinline__ void critic_branch(float *lds, const StepArgs &S, int k)
@@ -192,8 +139,7 @@ __device__ __forceinline__ void critic_branch(float *lds, const StepArgs &S, int
     load_image<L>(lds, L::floats, F::outs, [&](int slot, int i) { return net[F::at(slot) + i]; });
     for (int i = t; i < kAct * kH; i += kFitBlock) lds[L::w1 + (i & (kH - 1)) * L::ld1 + kIn + (i >> 7)] = net[F::w0 + kIn * kH + i];
 
-    int rows = S.counts ? S.counts[0] : S.batch;
-    rows = rows < S.batch ? rows : S.batch;
+    const int rows = step_rows(S);
     const float dscale = (float)(1.0 / (double)rows), frows = (float)rows;
 
     const int o1 = t & 127, ig1 = t >> 7;
@@ -208,16 +154,8 @@ __device__ __forceinline__ void critic_branch(float *lds, const StepArgs &S, int
         int idx = -1;
         if (gc < kCIn + 1 && r0 + gr < rows) idx = S.indices[r0 + gr];
         // ---- y: v_target streamed on obs1
-        float pre = 0.0f;                                // the thread's value of (obs0 | act), fetched under the target pass
-        if (gc < kIn) {
-            lds[L::x + gc * kRP + gr] = idx < 0 ? 0.0f : S.obs1[(int64_t)idx * kIn + gc];
-            pre = idx < 0 ? 0.0f : S.obs0[(int64_t)idx * kIn + gc];
-        } else if (gc < kCIn) {
-            pre = idx < 0 ? 0.0f : S.act[(int64_t)idx * kAct + (gc - kIn)];
-        } else if (gc == kCIn) {
-            lds[L::sc + gr] = idx < 0 ? 0.0f : S.rew[idx];
-            lds[L::sc + kRP + gr] = idx < 0 ? 1.0f : S.done[idx];
-        }
+        // (pre: the thread's value of (obs0 | act), fetched under the target pass)
+        const float pre = gather_critic<L>(lds, S, idx, gr, gc);
         __syncthreads();
         stream_layer<true>(vt + FV::w0, vt + FV::b0, lds + L::x, kIn, lds + L::a1);
         __syncthreads();
@@ -226,7 +164,7 @@ __device__ __forceinline__ void critic_branch(float *lds, const StepArgs &S, int
         if (t < kRows) {
             const float v1 = stream_head<1>(vt + FV::w2, vt + FV::b2, lds + L::a2);
             const float rew = lds[L::sc + t], done = lds[L::sc + kRP + t];
-            const float y = done >= 1.0f ? rew : __fmaf_rn(__fmul_rn(__fsub_rn(1.0f, done), S.gamma), v1, rew);
+            const float y = done >= 1.0f ? rew : __fmaf_rn(__fmul_rn(__fsub_rn(1.0f, done), S.gamma), v1, rew);      // (td_target)
             lds[L::sc + 2 * kRP + t] = y;
             if (S.fwd_out && k == 1 && r0 + t < rows) {
                 S.fwd_out[(int64_t)(r0 + t) * 5 + 0] = done >= 1.0f ? 0.0f : v1;
@@ -236,19 +174,7 @@ __device__ __forceinline__ void critic_branch(float *lds, const StepArgs &S, int
         if (gc < kCIn) lds[L::x + gc * kRP + gr] = pre;
         __syncthreads();
         // ---- the critic on (obs0, act), then dq over y's first row
-        forward_layer<true>(lds + L::w1, L::ld1, lds + L::b1, lds + L::x, kInP, kH, lds + L::a1);
-        __syncthreads();
-        forward_layer<true>(lds + L::w2, L::ld2, lds + L::b2, lds + L::a1, kH, kH, lds + L::a2);
-        __syncthreads();
-        forward_layer<false>(lds + L::w3, L::ld3, lds + L::b3, lds + L::a2, kH, kOut, lds + L::y);
-        __syncthreads();
-        if (t < kRows) {
-            const bool valid = r0 + t < rows;
-            const float q = lds[L::y + t], d = valid ? __fsub_rn(q, lds[L::sc + 2 * kRP + t]) : 0.0f;
-            lds[L::sc + 4 * kRP + t] = d;
-            lds[L::y + t] = __fmul_rn(d, dscale);
-        }
-        __syncthreads();
+        critic_forward_dq<L, kH, false>(lds, r0, rows, dscale);
         if (t == kStatT) {
             for (int r = 0; r < kRows && r0 + r < rows; ++r) {
                 const float d = lds[L::sc + 4 * kRP + r];
@@ -258,7 +184,7 @@ __device__ __forceinline__ void critic_branch(float *lds, const StepArgs &S, int
         }
         backward_chunk<L>(lds, G);
         // the four action rows of w0, by the threads that own layer 0's padding in the tower's map and whose g1 backward_chunk
-        // leaves alone: phase C's chain on inputs 12 .. 15 (dz0 is complete since phase B's barrier)
+        // leaves alone: phase C's chain on inputs 12 .. 15 (dz0 is complete since phase B's barrier).  (As in td3_kernels.hpp)
         if (ig1 == 3) {
 #pragma clang loop unroll(disable)
             for (int rg = 0; rg < kRG; ++rg) {
@@ -290,8 +216,7 @@ __device__ __forceinline__ void value_branch(float *lds, const StepArgs &S)
 
     load_image<L>(lds, L::floats, F::outs, [&](int slot, int i) { return net[F::at(slot) + i]; });
 
-    int rows = S.counts ? S.counts[0] : S.batch;
-    rows = rows < S.batch ? rows : S.batch;
+    const int rows = step_rows(S);
     const float dscale = (float)(1.0 / (double)rows), frows = (float)rows;
     const float alpha = expf(S.ws[kWsAlpha + S.cur]);
 
@@ -308,7 +233,7 @@ __device__ __forceinline__ void value_branch(float *lds, const StepArgs &S)
             lds[L::x + gc * kRP + gr] = v;
             lds[L::cx + gc * kRP + gr] = v;
         } else if (gc == kIn) {
-            load_noise(lds + L::zn, S, r0 + gr, gr, valid, false);
+            load_noise<kStreamNoise>(lds + L::zn, S, r0 + gr, gr, valid, false);
         }
         __syncthreads();
         // ---- the online actor streamed, the sample and the four terms of its logp
@@ -334,7 +259,7 @@ __device__ __forceinline__ void value_branch(float *lds, const StepArgs &S)
         if (t < kRows) {
             const float qa = stream_head<1>(qa_net + FC::w2, qa_net + FC::b2, lds + L::a2);
             const float qb = stream_head<1>(qb_net + FC::w2, qb_net + FC::b2, lds + L::d2);
-            const float mn = qa != qa ? qa : qb != qb ? qb : (qb < qa ? qb : qa);
+            const float mn = twin_min(qa, qb);
             float lp = 0.0f;
 #pragma unroll
             for (int c = 0; c < kAct; ++c) lp = __fadd_rn(lp, lds[L::tm + c * kRP + t]);
@@ -386,8 +311,7 @@ __device__ __forceinline__ void actor_branch(float *lds, const StepArgs &S)
 
     load_image<L>(lds, L::floats, F::outs, [&](int slot, int i) { return net[F::at(slot) + i]; });
 
-    int rows = S.counts ? S.counts[0] : S.batch;
-    rows = rows < S.batch ? rows : S.batch;
+    const int rows = step_rows(S);
     const float rinv = (float)(1.0 / (double)rows), ninv = -rinv, frows = (float)rows;
     const float la = S.ws[kWsAlpha + S.cur], alpha = expf(la), ar = __fmul_rn(alpha, rinv);
 
@@ -406,7 +330,7 @@ __device__ __forceinline__ void actor_branch(float *lds, const StepArgs &S)
             lds[L::x + gc * kRP + gr] = v;
             lds[L::cx + gc * kRP + gr] = v;
         } else if (gc == kIn) {
-            load_noise(lds + L::zn, S, r0 + gr, gr, valid, true);
+            load_noise<kStreamNoise>(lds + L::zn, S, r0 + gr, gr, valid, true);
         }
         __syncthreads();
         // ---- the head of the actor on obs0, the sample, q1(obs0, a) with the online q1 streamed
@@ -438,38 +362,7 @@ __device__ __forceinline__ void actor_branch(float *lds, const StepArgs &S)
             lds[L::sc + kRP + t] = lp;
             if (S.logp_out && r0 + t < rows) S.logp_out[r0 + t] = lp;
         }
-        {
-            // dc1 of q1 into the plane d2: dq/dh1 = w2 under h1's mask, times -1 / rows on the step's rows.  The masks of this
-            // pass are h <= 0 ? 0 : acc, float64 autograd's own: a NaN activation hands its term on
-            const int u = t & (kH - 1), rg = t >> 7;
-            const float w2u = cr[FC::w2 + u];
-            const f32x4 h = ld4(lds + L::c1 + u * kRP + 4 * rg);
-            f32x4 dz;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dz[r] = (h[r] <= 0.0f || r0 + 4 * rg + r >= rows) ? 0.0f : __fmul_rn(w2u, ninv);
-            st4(lds + L::d2 + u * kRP + 4 * rg, dz);
-        }
-        __syncthreads();
-        {
-            // dc0 into the plane d1: unit u's row of w1 is contiguous in memory (the policy's (in, out) layout), o ascending
-            const int u = t & (kH - 1), rg = t >> 7;
-            const float *w = cr + FC::w1 + u * kH, *d = lds + L::d2 + 4 * rg;
-            f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-            for (int o = 0; o < kH; o += 4) {
-                const f32x4 wv = ld4(w + o);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const f32x4 dz = ld4(d + (o + i) * kRP);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[r] = __fmaf_rn(wv[i], dz[r], acc[r]);
-                }
-            }
-            const f32x4 h = ld4(lds + L::c0 + u * kRP + 4 * rg);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[r] = h[r] <= 0.0f ? 0.0f : acc[r];
-            st4(lds + L::d1 + u * kRP + 4 * rg, acc);
-        }
-        __syncthreads();
+        backward_streamed<L, FC>(lds, cr, r0, rows, ninv);
         if (t < kAct * kRows) {
             // da through q1's action rows, then the header's item 5: du into the mean's head, dls into the log-std head
             const float *w = cr + FC::w0 + (kIn + gc) * kH;
@@ -541,13 +434,7 @@ __global__ __launch_bounds__(kFitBlock) void k_sac_step(StepArgs S)
 
 __global__ __launch_bounds__(kCopyBlock) void k_sac_copy(CopyArgs C)
 {
-    const int k = blockIdx.x;
-    float *t = C.t[k], *w = C.ws + C.at[k];
-    if (!t) return;
-    for (int i = threadIdx.x; i < C.n[k]; i += kCopyBlock) {
-        if (C.to_ws) w[i] = t[i];
-        else t[i] = w[i];
-    }
+    copy_tensor(C);
 }
 
 __global__ __launch_bounds__(kMathBlock) void k_sac_math(int which, const float *in, float *out, int64_t n)

@@ -1,7 +1,8 @@
 // td3_kernels.hpp -- the kernels of libquadsim_td3.so (include/quadsim_td3.h has the numerical contract).  A fragment of td3.hip,
-// nowhere else.  Built from train_pieces.hpp: the chunk primitives, the tower pieces (the LDS image and its loader, the element map,
-// backward_chunk), the streamed forward pass of a net that lies in memory and tanh_keep_nan; philox_counter and normals_from_words
-// are quadsim_device.hpp's.
+// nowhere else.  Built from train_pieces.hpp (the chunk primitives, the tower pieces -- the LDS image and its loader, the element map,
+// backward_chunk --, the streamed forward pass of a net that lies in memory and tanh_keep_nan) and from train_offpolicy.hpp (the
+// flat net, the copy table, the selects of the target, a critic's forward pass with dq and its sums, the backward pass through the
+// streamed q1 and the Adam-and-Polyak tail); philox_counter and normals_from_words are quadsim_device.hpp's.
 //
 // One update is ONE launch, and the kernel boundary is the only ordering across workgroups:
 //   k_td3_step   grid (2) on a critic-only update, (3) on an actor update.  Workgroups 0 and 1 are the critic branches of q1 and q2:
@@ -20,27 +21,19 @@
 // a critic-only update) stays where it is and keeps its bits.  Moments and gradients have one copy: only their branch touches
 // them.  Nothing waits on another workgroup, there is no grid barrier and no float atomic.
 #pragma once
-#include "train_pieces.hpp"
+#include "train_offpolicy.hpp"
 
 namespace qstd {
 
 using namespace qsf;
 
-constexpr int kAct = 4, kCIn = kIn + kAct;
 constexpr int kNets = 6, kOnlineNets = 3;                     // the ABI's order: actor, q1, q2, then their targets
-constexpr int kCopyBlock = 256, kCopyTensors = 90;            // 36 weights, 36 moments, 18 gradients
+constexpr int kCopyTensors = 90;                              // 36 weights, 36 moments, 18 gradients
 constexpr uint64_t kStreamNoise = 6;                          // the Philox stream of the target noise (quadsim_device.hpp uses 0 .. 5)
-static_assert(kCIn == kInP, "a critic's layer 0 fills the tower image's sixteen input rows");
 
-// a net as it lies flat in the workspace, tensors in the ABI's order and the policy's (in, out) layout.  B = 0: a critic (sixteen
-// inputs, one output), B = 1: the actor
+// the flat nets.  B = 0: a critic (sixteen inputs, one output), B = 1: the actor
 template <int B>
-struct Flat {
-    static constexpr int k0 = B ? kIn : kCIn, outs = B ? kAct : 1;
-    static constexpr int w0 = 0, b0 = w0 + k0 * kH, w1 = b0 + kH, b1 = w1 + kH * kH, w2 = b1 + kH, b2 = w2 + kH * outs;
-    static constexpr int floats = (b2 + outs + 3) & ~3;
-    static constexpr int at(int k) { return k == 0 ? w0 : k == 1 ? b0 : k == 2 ? w1 : k == 3 ? b1 : k == 4 ? w2 : b2; }   // slot k's start
-};
+using Flat = FlatNet<B ? kIn : kCIn, kH, B ? kAct : 1>;
 // an online net k = 0 .. 2 among the three: actor | q1 | q2.  A buffer: the three online nets, then the three targets
 constexpr int online_at(int k) { return k == 0 ? 0 : Flat<1>::floats + (k - 1) * Flat<0>::floats; }
 constexpr int kOnline = Flat<1>::floats + 2 * Flat<0>::floats, kBuf = 2 * kOnline;
@@ -61,12 +54,7 @@ struct StepArgs {
     int batch, cur, actor_step, want_grads;      // cur: bit k = the buffer that holds net k before this step
 };
 
-struct CopyArgs {
-    float *t[kCopyTensors];
-    int at[kCopyTensors], n[kCopyTensors];
-    float *ws;
-    int to_ws;
-};
+struct CopyArgs : CopyTable<kCopyTensors> {};
 
 // where net k lies before the step, and where the step puts it if it writes it
 __device__ __forceinline__ const float *net_cur(const StepArgs &S, int k) { return S.ws + ((S.cur >> k) & 1) * kBuf + net_at(k); }
@@ -87,33 +75,14 @@ struct LayoutA : TowerImage<> {
 constexpr int kLdsFloats = LayoutC::floats > LayoutA::floats ? LayoutC::floats : LayoutA::floats;
 static_assert(kLdsFloats * 4 <= 160 * 1024, "LDS");
 
-// (a select, not fminf(fmaxf()): those would drop a NaN; an infinity is clamped as any other value)
-__device__ __forceinline__ float clampsel(float v, float lo, float hi) { return v < lo ? lo : v > hi ? hi : v; }
-
-// Adam on the thread's own elements (m and v through memory, the weight from LDS into the net's next place), then, where the
-// targets move, the target's average with the new weight.  No thread reads another's element here.  ACTION_ROWS: the four action
-// rows of a critic's w0, which the owners of layer 0's padding in the tower's map hold in g1
+// the Adam step of online net k (train_offpolicy.hpp's apply_step), with its target's average where the targets move
 template <class L, class F, bool ACTION_ROWS>
 __device__ __forceinline__ void apply_step(float *lds, const StepArgs &S, int k, float lr_t, bool polyak, const Acc &G)
 {
-    const int t = threadIdx.x;
     const Adam A{S.b1f, S.b2f, S.omb1, S.omb2, S.eps, lr_t};
-    float *wn = net_nxt(S, k), *m = S.ws + kWsM + online_at(k), *v = S.ws + kWsV + online_at(k);
-    float *gout = S.want_grads ? S.ws + kWsG + online_at(k) : nullptr;
-    const float *tc = net_cur(S, k + kOnlineNets);
-    float *tn = net_nxt(S, k + kOnlineNets);
-    auto apply = [&](float g, float *lw, int e) {
-        adam_step(A, g, lw, wn, m, v, gout, e);
-        if (polyak) tn[e] = __fmaf_rn(S.tau, *lw, __fmul_rn(S.omt, tc[e]));
-    };
-    for_own<L, F::outs>(t, [&](int off, int idx, int slot, const float &g) { apply(g, lds + off, F::at(slot) + idx); }, G);
-    if (ACTION_ROWS) {
-        const int o1 = t & 127;
-        if ((t >> 7) == 3) {
-#pragma unroll
-            for (int a = 0; a < kAct; ++a) apply(G.g1[a], lds + L::w1 + o1 * L::ld1 + kIn + a, F::w0 + (kIn + a) * kH + o1);
-        }
-    }
+    const StepPlaces P{net_nxt(S, k), S.ws + kWsM + online_at(k), S.ws + kWsV + online_at(k),
+                       S.want_grads ? S.ws + kWsG + online_at(k) : nullptr, net_cur(S, k + kOnlineNets), net_nxt(S, k + kOnlineNets)};
+    qsf::apply_step<L, F, ACTION_ROWS>(lds, A, P, S.tau, S.omt, polyak, G, NoMore());
 }
 
 // ---- a critic branch: k = 1 (q1) or 2 (q2)
@@ -129,8 +98,7 @@ __device__ __forceinline__ void critic_branch(float *lds, const StepArgs &S, int
     load_image<L>(lds, L::floats, F::outs, [&](int slot, int i) { return net[F::at(slot) + i]; });
     for (int i = t; i < kAct * kH; i += kFitBlock) lds[L::w1 + (i & (kH - 1)) * L::ld1 + kIn + (i >> 7)] = net[F::w0 + kIn * kH + i];
 
-    int rows = S.counts ? S.counts[0] : S.batch;
-    rows = rows < S.batch ? rows : S.batch;
+    const int rows = step_rows(S);
     const float dscale = (float)(2.0 / (double)rows), frows = (float)rows;
 
     const int o1 = t & 127, ig1 = t >> 7;
@@ -145,6 +113,8 @@ __device__ __forceinline__ void critic_branch(float *lds, const StepArgs &S, int
         int idx = -1;
         if (gc < kCIn + 2 && r0 + gr < rows) idx = S.indices[r0 + gr];
         // ---- y: the three target nets streamed, the target action smoothed, the smaller of the two target values
+        // (the gather and the noise are train_offpolicy.hpp's gather_critic and load_noise written out: called, they compile to
+        // another kernel here.  A change to those pieces must be made here too)
         float pre = 0.0f;                                // the thread's value of (obs0 | act), fetched under the target pass
         if (gc < kIn) {
             lds[L::x + gc * kRP + gr] = idx < 0 ? 0.0f : S.obs1[(int64_t)idx * kIn + gc];
@@ -193,38 +163,19 @@ __device__ __forceinline__ void critic_branch(float *lds, const StepArgs &S, int
         if (t < kRows) {
             const float qa = stream_head<1>(qa_net + F::w2, qa_net + F::b2, lds + L::a2);
             const float qb = stream_head<1>(qb_net + F::w2, qb_net + F::b2, lds + L::d2);
-            const float m = qa != qa ? qa : qb != qb ? qb : (qb < qa ? qb : qa);
+            const float m = twin_min(qa, qb);
             const float rew = lds[L::sc + t], done = lds[L::sc + kRP + t];
-            lds[L::sc + 2 * kRP + t] = done >= 1.0f ? rew : __fmaf_rn(__fmul_rn(__fsub_rn(1.0f, done), S.gamma), m, rew);
+            lds[L::sc + 2 * kRP + t] = td_target(rew, done, S.gamma, m);
         }
         if (gc < kCIn) lds[L::x + gc * kRP + gr] = pre;
         __syncthreads();
         // ---- the critic on (obs0, act), then dq over y's first row
-        forward_layer<true>(lds + L::w1, L::ld1, lds + L::b1, lds + L::x, kInP, kH, lds + L::a1);
-        __syncthreads();
-        forward_layer<true>(lds + L::w2, L::ld2, lds + L::b2, lds + L::a1, kH, kH, lds + L::a2);
-        __syncthreads();
-        forward_layer<false>(lds + L::w3, L::ld3, lds + L::b3, lds + L::a2, kH, kOut, lds + L::y);
-        __syncthreads();
-        if (t < kRows) {
-            const bool valid = r0 + t < rows;
-            const float q = lds[L::y + t], d = valid ? __fsub_rn(q, lds[L::sc + 2 * kRP + t]) : 0.0f;
-            lds[L::sc + 3 * kRP + t] = q;
-            lds[L::sc + 4 * kRP + t] = d;
-            lds[L::y + t] = __fmul_rn(d, dscale);
-        }
-        __syncthreads();
-        if (t == kStatT) {
-            for (int r = 0; r < kRows && r0 + r < rows; ++r) {
-                const float d = lds[L::sc + 4 * kRP + r];
-                s0 = __fmaf_rn(d, d, s0);
-                s1 = __fadd_rn(s1, lds[L::sc + 3 * kRP + r]);
-                s2 = __fadd_rn(s2, lds[L::sc + 2 * kRP + r]);
-            }
-        }
+        critic_forward_dq<L, kH, true>(lds, r0, rows, dscale);
+        critic_sums<L, true>(lds, r0, rows, s0, s1, s2);
         backward_chunk<L>(lds, G);
         // the four action rows of w0, by the threads that own layer 0's padding in the tower's map and whose g1 backward_chunk
-        // leaves alone: phase C's chain on inputs 12 .. 15 (dz0 is complete since phase B's barrier)
+        // leaves alone: phase C's chain on inputs 12 .. 15 (dz0 is complete since phase B's barrier).  (The same text stands in
+        // sac_kernels.hpp: as a shared piece it compiled to another kernel in either.  A change here must be made there too)
         if (ig1 == 3) {
 #pragma clang loop unroll(disable)
             for (int rg = 0; rg < kRG; ++rg) {
@@ -261,8 +212,7 @@ __device__ __forceinline__ void actor_branch(float *lds, const StepArgs &S)
 
     load_image<L>(lds, L::floats, F::outs, [&](int slot, int i) { return net[F::at(slot) + i]; });
 
-    int rows = S.counts ? S.counts[0] : S.batch;
-    rows = rows < S.batch ? rows : S.batch;
+    const int rows = step_rows(S);
     const float ninv = -(float)(1.0 / (double)rows), frows = (float)rows;
 
     Acc G;
@@ -297,39 +247,7 @@ __device__ __forceinline__ void actor_branch(float *lds, const StepArgs &S)
         stream_layer<true>(cr + FC::w1, cr + FC::b1, lds + L::c0, kH, lds + L::c1);
         __syncthreads();
         if (t < kRows) lds[L::sc + t] = stream_head<1>(cr + FC::w2, cr + FC::b2, lds + L::c1);
-        {
-            // dc1 of q1 into the plane d2: dq/dh1 = w2 under h1's mask, times -1 / rows on the step's rows.  The masks of this
-            // pass are h <= 0 ? 0 : acc, float64 autograd's own: a NaN activation hands its term on, so that an actor behind a
-            // diverged q1 diverges as the arbiter's does (h > 0 ? acc : 0 would feed it zeros)
-            const int u = t & (kH - 1), rg = t >> 7;
-            const float w2u = cr[FC::w2 + u];
-            const f32x4 h = ld4(lds + L::c1 + u * kRP + 4 * rg);
-            f32x4 dz;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dz[r] = (h[r] <= 0.0f || r0 + 4 * rg + r >= rows) ? 0.0f : __fmul_rn(w2u, ninv);
-            st4(lds + L::d2 + u * kRP + 4 * rg, dz);
-        }
-        __syncthreads();
-        {
-            // dc0 into the plane d1: unit u's row of w1 is contiguous in memory (the policy's (in, out) layout), o ascending
-            const int u = t & (kH - 1), rg = t >> 7;
-            const float *w = cr + FC::w1 + u * kH, *d = lds + L::d2 + 4 * rg;
-            f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-            for (int o = 0; o < kH; o += 4) {
-                const f32x4 wv = ld4(w + o);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const f32x4 dz = ld4(d + (o + i) * kRP);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[r] = __fmaf_rn(wv[i], dz[r], acc[r]);
-                }
-            }
-            const f32x4 h = ld4(lds + L::c0 + u * kRP + 4 * rg);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[r] = h[r] <= 0.0f ? 0.0f : acc[r];
-            st4(lds + L::d1 + u * kRP + 4 * rg, acc);
-        }
-        __syncthreads();
+        backward_streamed<L, FC>(lds, cr, r0, rows, ninv);
         if (t < kAct * kRows) {
             const float *w = cr + FC::w0 + (kIn + gc) * kH;
             float da = 0.0f;
@@ -357,13 +275,7 @@ __global__ __launch_bounds__(kFitBlock) void k_td3_step(StepArgs S)
 
 __global__ __launch_bounds__(kCopyBlock) void k_td3_copy(CopyArgs C)
 {
-    const int k = blockIdx.x;
-    float *t = C.t[k], *w = C.ws + C.at[k];
-    if (!t) return;
-    for (int i = threadIdx.x; i < C.n[k]; i += kCopyBlock) {
-        if (C.to_ws) w[i] = t[i];
-        else t[i] = w[i];
-    }
+    copy_tensor(C);
 }
 
 }  // namespace qstd

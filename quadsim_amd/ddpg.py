@@ -15,13 +15,11 @@ import functools
 import math
 import time
 
-import numpy as np
-
-from . import _lib
+from . import _lib, offpolicy
+from .offpolicy import NET_KEYS
 
 DDPG_MAX_BATCH, DDPG_MAX_STEPS = 256, 4096
 DDPG_BETA1, DDPG_BETA2, DDPG_EPS = 0.9, 0.999, 1.0e-8          # MpiAdam's defaults, which SB2's DDPG leaves alone
-NET_KEYS = ("w0", "b0", "w1", "b1", "w2", "b2")
 ACTOR_SHAPES = ((12, 128), (128,), (128, 128), (128,), (128, 4), (4,))
 CRITIC_SHAPES = ((12, 128), (128,), (132, 128), (128,), (128, 1), (1,))
 NET_NAMES = ("actor", "critic", "actor_target", "critic_target")
@@ -39,82 +37,41 @@ def check_ddpg_args(n, steps, batch, gamma=0.99, tau=1.0e-3, actor_lr=1.0e-4, cr
     refuse and, given the host arrays `counts` [steps] and `indices` [steps,batch], for what it cannot check (a count outside
     [1, batch], a row it would read outside [0, n)), before anything touches the library or the GPU"""
     n, steps, batch, t0 = int(n), int(steps), int(batch), int(t0)
-    if not 1 <= batch <= DDPG_MAX_BATCH:
-        raise ValueError("batch must be in [1, %d], got %d" % (DDPG_MAX_BATCH, batch))
-    if not 1 <= steps <= DDPG_MAX_STEPS:
-        raise ValueError("steps must be in [1, %d], got %d" % (DDPG_MAX_STEPS, steps))
-    if not 1 <= n < 1 << 31:
-        raise ValueError("n must be in [1, 2^31), got %d" % n)
+    offpolicy.check_extent(n, steps, batch, DDPG_MAX_BATCH, DDPG_MAX_STEPS)
     gamma, tau, actor_lr, critic_lr, obs_clip = float(gamma), float(tau), float(actor_lr), float(critic_lr), float(obs_clip)
-    if not 0.0 <= gamma <= 1.0:
-        raise ValueError("gamma must be in [0, 1], got %r" % gamma)
-    if not 0.0 < tau <= 1.0:
-        raise ValueError("tau must be in (0, 1], got %r" % tau)
+    offpolicy.check_discount(gamma, tau)
     if not obs_clip > 0.0:
         raise ValueError("obs_clip must be > 0 (inf: no clamp), got %r" % obs_clip)
     for name, val in (("actor_lr", actor_lr), ("critic_lr", critic_lr)):
         if not math.isfinite(val):
             raise ValueError("%s must be finite, got %r" % (name, val))
     _, beta1, beta2, eps = _lib.check_adam_args(0.0, beta1, beta2, eps, t0, steps, "steps")
-    if counts is not None:
-        counts = np.asarray(counts)
-        if counts.shape != (steps,) or counts.min() < 1 or counts.max() > batch:
-            raise ValueError("counts must be [%d] values in [1, batch = %d]" % (steps, batch))
-    if indices is not None:
-        indices = np.asarray(indices)
-        if indices.shape != (steps, batch):
-            raise ValueError("indices must be [%d, %d], got %s" % (steps, batch, indices.shape))
-        used = indices if counts is None else indices[np.arange(batch)[None, :] < counts[:, None]]
-        if used.min() < 0 or used.max() >= n:
-            raise ValueError("indices the update would read must be in [0, n = %d), got [%d, %d]" % (n, used.min(), used.max()))
+    offpolicy.check_schedule(n, steps, batch, counts, indices)
     return n, steps, batch, gamma, tau, actor_lr, critic_lr, obs_clip, beta1, beta2, eps, t0
 
 
+def shapes_of(name):
+    return ACTOR_SHAPES if name.startswith("actor") else CRITIC_SHAPES
+
+
 # ---------------------------------------------------------------------------------------------------- the nets
-class DDPGPolicy:
+class DDPGPolicy(offpolicy.Nets):
     """the four nets of DDPG, float32 in the policy's (in, out) layout, as lists of six tensors: ``actor``, ``critic``,
     ``actor_target``, ``critic_target``; Adam's moments of the two online nets (``m``, ``v``: {"actor": [...], "critic": [...]}) and
     the step count.  SB2's initialisation drawn from `seed`: Glorot-uniform hidden layers, U(-3e-3, 3e-3) output layers, zero
     biases, the targets equal to the online nets.  `weights`: {"actor": {w0 ..}, "critic": {..}, and optionally the two targets}."""
 
+    NET_NAMES, ONLINE_NAMES, OUT_LIM, TAKES_DTYPE, LIB = NET_NAMES, ("actor", "critic"), 3.0e-3, False, ("ddpg", "qsdd_workspace_bytes")
+    shapes_of, load = staticmethod(shapes_of), staticmethod(lambda: load_ddpg())
+
     def __init__(self, seed=0, device="cuda", weights=None):
-        import torch
-        self.device = torch.device(device)
-        if weights is None:
-            rng = np.random.default_rng(int(seed))
-            weights = {}
-            for name, shapes in (("actor", ACTOR_SHAPES), ("critic", CRITIC_SHAPES)):
-                W = {}
-                for k, shape in zip(NET_KEYS, shapes):
-                    if len(shape) == 1:
-                        W[k] = np.zeros(shape, np.float32)
-                    else:
-                        lim = 3.0e-3 if k == "w2" else math.sqrt(6.0 / (shape[0] + shape[1]))
-                        W[k] = rng.uniform(-lim, lim, shape).astype(np.float32)
-                weights[name] = W
-        for name in NET_NAMES:
-            src = weights.get(name, weights[name.split("_")[0]])
-            shapes = ACTOR_SHAPES if name.startswith("actor") else CRITIC_SHAPES
-            ws = []
-            for k, shape in zip(NET_KEYS, shapes):
-                w = np.ascontiguousarray(src[k], np.float32)
-                if w.shape != shape:
-                    raise ValueError("%s %s must be of shape %s, got %s" % (name, k, shape, w.shape))
-                ws.append(torch.as_tensor(w.copy()).to(self.device))
-            setattr(self, name, ws)
-        self.device = self.actor[0].device
+        self.init_nets(seed, device, weights, "float32")
         self.reset_optimizer()
-        self._workspace = None
 
     def reset_optimizer(self):
         """forget Adam's moments and the step count"""
-        import torch
-        self.m = {k: [torch.zeros_like(w) for w in getattr(self, k)] for k in ("actor", "critic")}
-        self.v = {k: [torch.zeros_like(w) for w in getattr(self, k)] for k in ("actor", "critic")}
+        self.zero_moments()
         self.steps = 0
-
-    def nets(self):
-        return [getattr(self, name) for name in NET_NAMES]
 
     def predict(self, obs, obs_clip=5.0):
         """obs [N,12] float32 -> tanh actions [N,4] of the online actor (plain torch)"""
@@ -127,34 +84,6 @@ class DDPGPolicy:
     def actor_weights(self):
         """the online actor in MlpPolicy's key names (numpy): MlpPolicy clips where this actor squashes"""
         return {k: w.detach().cpu().numpy() for k, w in zip(NET_KEYS, self.actor)}
-
-    def save_npz(self, path):
-        arrays = {}
-        for name in NET_NAMES:
-            arrays.update({"%s_%s" % (name, k): w.detach().cpu().numpy() for k, w in zip(NET_KEYS, getattr(self, name))})
-        for name in ("actor", "critic"):
-            arrays.update({"m_%s_%s" % (name, k): t.cpu().numpy() for k, t in zip(NET_KEYS, self.m[name])})
-            arrays.update({"v_%s_%s" % (name, k): t.cpu().numpy() for k, t in zip(NET_KEYS, self.v[name])})
-        np.savez(path, steps=self.steps, **arrays)
-
-    @classmethod
-    def from_npz(cls, path, device="cuda"):
-        import torch
-        with np.load(path, allow_pickle=False) as z:
-            p = cls(device=device, weights={name: {k: z["%s_%s" % (name, k)] for k in NET_KEYS} for name in NET_NAMES})
-            for name in ("actor", "critic"):
-                p.m[name] = [torch.as_tensor(z["m_%s_%s" % (name, k)].copy()).to(p.device) for k in NET_KEYS]
-                p.v[name] = [torch.as_tensor(z["v_%s_%s" % (name, k)].copy()).to(p.device) for k in NET_KEYS]
-            p.steps = int(z["steps"])
-        return p
-
-    def workspace(self):
-        """the device workspace of qsdd_update, allocated once"""
-        if self._workspace is None:
-            nbytes = C.c_size_t(0)
-            _lib.side_call("ddpg", load_ddpg(), "qsdd_workspace_bytes", C.byref(nbytes))
-            self._workspace = _lib.new_tensor(self.device, (int(nbytes.value),), "uint8")
-        return self._workspace
 
 
 class ReplayBuffer:
@@ -225,27 +154,13 @@ class OUNoise:
 
 # ---------------------------------------------------------------------------------------------------- the update
 def _update_args(policy, replay, indices, counts, gamma, tau, actor_lr, critic_lr, obs_clip, need_device):
-    import torch
     dev = policy.device
     if need_device and dev.type != "cuda":
         raise _lib.QuadsimError("ddpg_update needs the policy on a HIP device, it is on %s; torch_ddpg_update is the host path" % (dev,))
-    for name, ws, shapes in ((n, getattr(policy, n), ACTOR_SHAPES if n.startswith("actor") else CRITIC_SHAPES) for n in NET_NAMES):
-        for k, w, shape in zip(NET_KEYS, ws, shapes):
-            _lib.check_tensor("%s %s" % (name, k), w, "float32", shape, dev)
-    obs0, act, rew, obs1, done = replay if isinstance(replay, (tuple, list)) else replay.tensors()
-    n = int(obs0.shape[0])
-    for name, t, shape in (("obs0", obs0, (n, 12)), ("act", act, (n, 4)), ("rew", rew, (n,)), ("obs1", obs1, (n, 12)), ("done", done, (n,))):
-        _lib.check_tensor(name, t, "float32", shape, dev)
-    indices = torch.as_tensor(indices)
-    if indices.dtype != torch.int32 or indices.dim() != 2 or indices.device.type != "cpu":
-        raise ValueError("indices must be a host int32 tensor [steps, batch]")
-    if counts is not None:
-        counts = torch.as_tensor(counts)
-        if counts.dtype != torch.int32 or counts.device.type != "cpu":
-            raise ValueError("counts must be a host int32 tensor [steps]")
+    data, n, indices, counts = offpolicy.update_tensors(policy, replay, indices, counts, "float32")
     args = check_ddpg_args(n, indices.shape[0], indices.shape[1], gamma, tau, actor_lr, critic_lr, obs_clip, t0=policy.steps,
                            counts=None if counts is None else counts.numpy(), indices=indices.numpy())
-    return (obs0, act, rew, obs1, done), indices.contiguous(), counts, args
+    return data, indices.contiguous(), counts, args
 
 
 def ddpg_update(policy, replay, indices, counts=None, gamma=0.99, tau=1.0e-3, actor_lr=1.0e-4, critic_lr=1.0e-3, obs_clip=5.0,

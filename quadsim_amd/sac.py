@@ -17,7 +17,7 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, offpolicy
 from .ddpg import NET_KEYS, ReplayBuffer, collect_and_train, replay_schedule  # noqa: F401  (the pieces SAC shares with DDPG)
 
 SAC_MAX_BATCH, SAC_MAX_STEPS = 256, 4096
@@ -33,9 +33,9 @@ NET_NAMES = ONLINE_NAMES + ("v_target",)
 SAC_STAT_NAMES = ("q1_loss", "q2_loss", "value_loss", "actor_loss", "alpha_loss", "alpha", "logp_mean", "y_mean")
 SAC_FWD_NAMES = ("v_target", "y", "qa", "qb", "vb")
 
-# libquadsim_sac.so is the entry "sac" of _lib.SIDE_LATER: its path, signatures, loader, status check and call helper are _lib's.
+# libquadsim_sac.so is the entry "sac" of _lib.SIDE: its path, signatures, loader, status check and call helper are _lib's.
 # The names below stay this module's so that callers and tests can replace the loader
-QssNets, QssReplay, QssHyper, QssTrace, SAC_EXPORTS = _lib.QssNets, _lib.QssReplay, _lib.QssHyper, _lib.QssTrace, _lib.side_entry("sac")["exports"]
+QssNets, QssReplay, QssHyper, QssTrace, SAC_EXPORTS = _lib.QssNets, _lib.QssReplay, _lib.QssHyper, _lib.QssTrace, _lib.SIDE["sac"]["exports"]
 load_sac, check_sac = functools.partial(_lib.side_load, "sac"), functools.partial(_lib.side_check, "sac")
 
 
@@ -49,45 +49,26 @@ def check_sac_args(n, steps, batch, gamma=0.99, tau=5.0e-3, lr=3.0e-4, target_en
     refuse and, given the host arrays `counts` [steps] and `indices` [steps,batch], for what it cannot check (a count outside
     [1, batch], a row it would read outside [0, n)), before anything touches the library or the GPU"""
     n, steps, batch, t0 = int(n), int(steps), int(batch), int(t0)
-    if not 1 <= batch <= SAC_MAX_BATCH:
-        raise ValueError("batch must be in [1, %d], got %d" % (SAC_MAX_BATCH, batch))
-    if not 1 <= steps <= SAC_MAX_STEPS:
-        raise ValueError("steps must be in [1, %d], got %d" % (SAC_MAX_STEPS, steps))
-    if not 1 <= n < 1 << 31:
-        raise ValueError("n must be in [1, 2^31), got %d" % n)
+    offpolicy.check_extent(n, steps, batch, SAC_MAX_BATCH, SAC_MAX_STEPS)
     gamma, tau, target_entropy = float(gamma), float(tau), float(target_entropy)
-    if not 0.0 <= gamma <= 1.0:
-        raise ValueError("gamma must be in [0, 1], got %r" % gamma)
-    if not 0.0 < tau <= 1.0:
-        raise ValueError("tau must be in (0, 1], got %r" % tau)
+    offpolicy.check_discount(gamma, tau)
     if not math.isfinite(target_entropy):
         raise ValueError("target_entropy must be finite, got %r" % target_entropy)
     if auto_alpha not in (0, 1, False, True):
         raise ValueError("auto_alpha must be 0 or 1, got %r" % (auto_alpha,))
     lr, beta1, beta2, eps = _lib.check_adam_args(lr, beta1, beta2, eps, t0, steps, "steps")
-    if counts is not None:
-        counts = np.asarray(counts)
-        if counts.shape != (steps,) or counts.min() < 1 or counts.max() > batch:
-            raise ValueError("counts must be [%d] values in [1, batch = %d]" % (steps, batch))
-    if indices is not None:
-        indices = np.asarray(indices)
-        if indices.shape != (steps, batch):
-            raise ValueError("indices must be [%d, %d], got %s" % (steps, batch, indices.shape))
-        used = indices if counts is None else indices[np.arange(batch)[None, :] < counts[:, None]]
-        if used.min() < 0 or used.max() >= n:
-            raise ValueError("indices the update would read must be in [0, n = %d), got [%d, %d]" % (n, used.min(), used.max()))
+    offpolicy.check_schedule(n, steps, batch, counts, indices)
     return n, steps, batch, gamma, tau, lr, target_entropy, int(bool(auto_alpha)), beta1, beta2, eps, t0
 
 
 def keyed_noise(seed, t0, steps, batch):
-    """-> [steps, batch, 4] float32: the noise that a call without `noise` draws, restated on the host: td3.keyed_noise's arithmetic on
-    Philox stream 7 (the device's own arithmetic is float32: ``noise_out`` of sac_update has the device's values)"""
-    from . import td3
-    return td3.keyed_noise(seed, t0, steps, batch, stream=SAC_NOISE_STREAM)
+    """-> [steps, batch, 4] float32: the noise that a call without `noise` draws, restated on the host: offpolicy.keyed_noise on Philox
+    stream 7 (the device's own arithmetic is float32: ``noise_out`` of sac_update has the device's values)"""
+    return offpolicy.keyed_noise(seed, t0, steps, batch, SAC_NOISE_STREAM)
 
 
 # ---------------------------------------------------------------------------------------------------- the nets
-class SACPolicy:
+class SACPolicy(offpolicy.Nets):
     """the five nets of SAC in the policy's (in, out) layout, as lists of six tensors: ``actor`` (head eight wide: four means, four raw
     log standard deviations), ``q1``, ``q2``, ``v`` and ``v_target``; Adam's moments of the four online nets (``m``, ``v_``: {"actor":
     [...], ..}), ``alpha_state`` = [log_alpha, m, v] and the update count ``steps``.  SB2's initialisation drawn from `seed`:
@@ -95,50 +76,21 @@ class SACPolicy:
     `weights`: {"actor": {w0 ..}, "q1": {..}, "q2": {..}, "v": {..} and optionally "v_target"}.  `dtype`: "float32" (the device path
     needs it) or "float64" (torch_sac_update alone)."""
 
+    NET_NAMES, ONLINE_NAMES, V, LIB = NET_NAMES, ONLINE_NAMES, "v_", ("sac", "qss_workspace_bytes")
+    shapes_of, load = staticmethod(shapes_of), staticmethod(lambda: load_sac())
+
     def __init__(self, seed=0, device="cuda", weights=None, dtype="float32", ent_coef=1.0):
         import torch
-        self.device, self.dtype = torch.device(device), getattr(torch, dtype)
-        if weights is None:
-            rng = np.random.default_rng(int(seed))
-            weights = {}
-            for name in ONLINE_NAMES:
-                W = {}
-                for k, shape in zip(NET_KEYS, shapes_of(name)):
-                    if len(shape) == 1:
-                        W[k] = np.zeros(shape, np.float32)
-                    else:
-                        lim = math.sqrt(6.0 / (shape[0] + shape[1]))
-                        W[k] = rng.uniform(-lim, lim, shape).astype(np.float32)
-                weights[name] = W
-        for name in NET_NAMES:
-            src = weights.get(name, weights[name.split("_")[0]])
-            ws = []
-            for k, shape in zip(NET_KEYS, shapes_of(name)):
-                w = np.ascontiguousarray(src[k])
-                if w.shape != shape:
-                    raise ValueError("%s %s must be of shape %s, got %s" % (name, k, shape, w.shape))
-                ws.append(torch.as_tensor(w.copy()).to(self.dtype).to(self.device))
-            setattr(self, name, ws)
-        self.device = self.actor[0].device
+        self.init_nets(seed, device, weights, dtype)
         self.alpha_state = torch.zeros(3, dtype=self.dtype, device=self.device)
         self.alpha_state[0] = math.log(float(ent_coef))
         self.reset_optimizer()
-        self._workspace, self._images = None, {}
 
     def reset_optimizer(self):
         """forget Adam's moments (the temperature's too) and the step count; log_alpha stays"""
-        import torch
-        self.m = {k: [torch.zeros_like(w) for w in getattr(self, k)] for k in ONLINE_NAMES}
-        self.v_ = {k: [torch.zeros_like(w) for w in getattr(self, k)] for k in ONLINE_NAMES}
+        self.zero_moments()
         self.alpha_state[1:] = 0.0
         self.steps = 0
-
-    def nets(self):
-        return [getattr(self, name) for name in NET_NAMES]
-
-    def updated(self):
-        """an update wrote the weights in place: every cached image of them is dropped"""
-        self._images = {}
 
     @property
     def alpha(self):
@@ -176,35 +128,13 @@ class SACPolicy:
             self._images["actor"] = W
         return self._images["actor"]
 
-    def save_npz(self, path):
-        arrays = {}
-        for name in NET_NAMES:
-            arrays.update({"%s_%s" % (name, k): w.detach().cpu().numpy() for k, w in zip(NET_KEYS, getattr(self, name))})
-        for name in ONLINE_NAMES:
-            arrays.update({"m_%s_%s" % (name, k): t.cpu().numpy() for k, t in zip(NET_KEYS, self.m[name])})
-            arrays.update({"v_%s_%s" % (name, k): t.cpu().numpy() for k, t in zip(NET_KEYS, self.v_[name])})
-        np.savez(path, steps=self.steps, alpha_state=self.alpha_state.cpu().numpy(), **arrays)
+    def npz_state(self):
+        return {"steps": self.steps, "alpha_state": self.alpha_state.cpu().numpy()}
 
-    @classmethod
-    def from_npz(cls, path, device="cuda"):
+    def set_npz_state(self, z):
         import torch
-        with np.load(path, allow_pickle=False) as z:
-            dtype = str(z["actor_w0"].dtype)
-            p = cls(device=device, weights={name: {k: z["%s_%s" % (name, k)] for k in NET_KEYS} for name in NET_NAMES}, dtype=dtype)
-            for name in ONLINE_NAMES:
-                p.m[name] = [torch.as_tensor(z["m_%s_%s" % (name, k)].copy()).to(p.device) for k in NET_KEYS]
-                p.v_[name] = [torch.as_tensor(z["v_%s_%s" % (name, k)].copy()).to(p.device) for k in NET_KEYS]
-            p.alpha_state = torch.as_tensor(z["alpha_state"].copy()).to(p.device)
-            p.steps = int(z["steps"])
-        return p
-
-    def workspace(self):
-        """the device workspace of qss_update, allocated once"""
-        if self._workspace is None:
-            nbytes = C.c_size_t(0)
-            _lib.side_call("sac", load_sac(), "qss_workspace_bytes", C.byref(nbytes))
-            self._workspace = _lib.new_tensor(self.device, (int(nbytes.value),), "uint8")
-        return self._workspace
+        self.alpha_state = torch.as_tensor(z["alpha_state"].copy()).to(self.device)
+        self.steps = int(z["steps"])
 
 
 def reset_sac_optimizer(policy):
@@ -214,32 +144,18 @@ def reset_sac_optimizer(policy):
 
 # ---------------------------------------------------------------------------------------------------- the update
 def _update_args(policy, replay, indices, counts, hyper, noise, need_device):
-    import torch
     dev = policy.device
     dtype = str(policy.dtype).split(".")[-1]
     if need_device and (dev.type != "cuda" or dtype != "float32"):
         raise _lib.QuadsimError("sac_update needs a float32 policy on a HIP device, it is %s on %s; torch_sac_update is the host path"
                                 % (dtype, dev))
-    for name in NET_NAMES:
-        for k, w, shape in zip(NET_KEYS, getattr(policy, name), shapes_of(name)):
-            _lib.check_tensor("%s %s" % (name, k), w, dtype, shape, dev)
+    data, n, indices, counts = offpolicy.update_tensors(policy, replay, indices, counts, dtype)
     _lib.check_tensor("alpha_state", policy.alpha_state, dtype, (3,), dev)
-    obs0, act, rew, obs1, done = replay if isinstance(replay, (tuple, list)) else replay.tensors()
-    n = int(obs0.shape[0])
-    for name, t, shape in (("obs0", obs0, (n, 12)), ("act", act, (n, 4)), ("rew", rew, (n,)), ("obs1", obs1, (n, 12)), ("done", done, (n,))):
-        _lib.check_tensor(name, t, "float32", shape, dev)
-    indices = torch.as_tensor(indices)
-    if indices.dtype != torch.int32 or indices.dim() != 2 or indices.device.type != "cpu":
-        raise ValueError("indices must be a host int32 tensor [steps, batch]")
-    if counts is not None:
-        counts = torch.as_tensor(counts)
-        if counts.dtype != torch.int32 or counts.device.type != "cpu":
-            raise ValueError("counts must be a host int32 tensor [steps]")
     args = check_sac_args(n, indices.shape[0], indices.shape[1], t0=policy.steps, counts=None if counts is None else counts.numpy(),
                           indices=indices.numpy(), **hyper)
     if noise is not None:
         _lib.check_tensor("noise", noise, "float32", (args[1], args[2], 4), dev)
-    return (obs0, act, rew, obs1, done), indices.contiguous(), counts, args
+    return data, indices.contiguous(), counts, args
 
 
 def sac_update(policy, replay, indices, counts=None, gamma=0.99, tau=5.0e-3, lr=3.0e-4, target_entropy=-4.0, auto_alpha=True, noise=None,

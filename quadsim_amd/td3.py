@@ -16,7 +16,7 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, offpolicy
 from .ddpg import NET_KEYS, OUNoise, ReplayBuffer, collect_and_train, replay_schedule  # noqa: F401  (the pieces TD3 shares with DDPG)
 
 TD3_MAX_BATCH, TD3_MAX_STEPS, TD3_MAX_DELAY = 256, 4096, 1 << 16
@@ -28,9 +28,9 @@ ONLINE_NAMES = ("actor", "q1", "q2")
 NET_NAMES = ONLINE_NAMES + ("actor_target", "q1_target", "q2_target")
 TD3_STAT_NAMES = ("q1_loss", "q2_loss", "q1_mean", "q2_mean", "y_mean", "actor_loss")
 
-# libquadsim_td3.so is the entry "td3" of _lib.SIDE_MORE: its path, signatures, loader, status check and call helper are _lib's.
+# libquadsim_td3.so is the entry "td3" of _lib.SIDE: its path, signatures, loader, status check and call helper are _lib's.
 # The names below stay this module's so that callers and tests can replace the loader
-QstdNets, QstdReplay, QstdHyper, TD3_EXPORTS = _lib.QstdNets, _lib.QstdReplay, _lib.QstdHyper, _lib.side_entry("td3")["exports"]
+QstdNets, QstdReplay, QstdHyper, TD3_EXPORTS = _lib.QstdNets, _lib.QstdReplay, _lib.QstdHyper, _lib.SIDE["td3"]["exports"]
 load_td3, check_td3 = functools.partial(_lib.side_load, "td3"), functools.partial(_lib.side_check, "td3")
 
 
@@ -51,22 +51,14 @@ def check_td3_args(n, steps, batch, gamma=0.99, tau=5.0e-3, actor_lr=3.0e-4, cri
     [steps,batch], for what it cannot check (a count outside [1, batch], a row it would read outside [0, n)), before anything touches
     the library or the GPU"""
     n, steps, batch, t0, actor_t0, policy_delay = int(n), int(steps), int(batch), int(t0), int(actor_t0), int(policy_delay)
-    if not 1 <= batch <= TD3_MAX_BATCH:
-        raise ValueError("batch must be in [1, %d], got %d" % (TD3_MAX_BATCH, batch))
-    if not 1 <= steps <= TD3_MAX_STEPS:
-        raise ValueError("steps must be in [1, %d], got %d" % (TD3_MAX_STEPS, steps))
-    if not 1 <= n < 1 << 31:
-        raise ValueError("n must be in [1, 2^31), got %d" % n)
+    offpolicy.check_extent(n, steps, batch, TD3_MAX_BATCH, TD3_MAX_STEPS)
     if not 1 <= policy_delay <= TD3_MAX_DELAY:
         raise ValueError("policy_delay must be in [1, %d], got %d" % (TD3_MAX_DELAY, policy_delay))
     if not (actor_t0 >= 0 and actor_t0 + steps < 1 << 31):
         raise ValueError("actor_t0 must be >= 0 with actor_t0 + steps below 2^31, got %d" % actor_t0)
     gamma, tau, actor_lr, critic_lr = float(gamma), float(tau), float(actor_lr), float(critic_lr)
     target_policy_noise, target_noise_clip = float(target_policy_noise), float(target_noise_clip)
-    if not 0.0 <= gamma <= 1.0:
-        raise ValueError("gamma must be in [0, 1], got %r" % gamma)
-    if not 0.0 < tau <= 1.0:
-        raise ValueError("tau must be in (0, 1], got %r" % tau)
+    offpolicy.check_discount(gamma, tau)
     if not (target_policy_noise >= 0.0 and math.isfinite(target_policy_noise)):
         raise ValueError("target_policy_noise must be finite and >= 0, got %r" % target_policy_noise)
     if not target_noise_clip >= 0.0:
@@ -75,93 +67,37 @@ def check_td3_args(n, steps, batch, gamma=0.99, tau=5.0e-3, actor_lr=3.0e-4, cri
         if not math.isfinite(val):
             raise ValueError("%s must be finite, got %r" % (name, val))
     _, beta1, beta2, eps = _lib.check_adam_args(0.0, beta1, beta2, eps, t0, steps, "steps")
-    if counts is not None:
-        counts = np.asarray(counts)
-        if counts.shape != (steps,) or counts.min() < 1 or counts.max() > batch:
-            raise ValueError("counts must be [%d] values in [1, batch = %d]" % (steps, batch))
-    if indices is not None:
-        indices = np.asarray(indices)
-        if indices.shape != (steps, batch):
-            raise ValueError("indices must be [%d, %d], got %s" % (steps, batch, indices.shape))
-        used = indices if counts is None else indices[np.arange(batch)[None, :] < counts[:, None]]
-        if used.min() < 0 or used.max() >= n:
-            raise ValueError("indices the update would read must be in [0, n = %d), got [%d, %d]" % (n, used.min(), used.max()))
+    offpolicy.check_schedule(n, steps, batch, counts, indices)
     return (n, steps, batch, gamma, tau, actor_lr, critic_lr, policy_delay, target_policy_noise, target_noise_clip, beta1, beta2, eps, t0,
             actor_t0)
 
 
 def keyed_noise(seed, t0, steps, batch, stream=TD3_NOISE_STREAM):
-    """-> [steps, batch, 4] float32: the target noise that a call without `noise` draws, restated on the host: Box-Muller in float64 on
-    the words of Philox4x32-10 block t0 + s of subsequence (6 << 48) | row slot, key `seed` (the device's own arithmetic is float32:
-    it differs from this in the last digits; ``noise_out`` of td3_update has the device's values).  `stream`: the Philox stream in
-    place of 6 (sac.py draws on 7)"""
-    m32 = np.uint64(0xFFFFFFFF)
-    block = np.broadcast_to(np.arange(int(t0), int(t0) + int(steps), dtype=np.uint64)[:, None], (int(steps), int(batch)))
-    sub = (np.uint64(stream) << np.uint64(48)) | np.arange(int(batch), dtype=np.uint64)[None, :]
-    c0, c1, c2, c3 = block & m32, block >> np.uint64(32), np.broadcast_to(sub & m32, block.shape), np.broadcast_to(sub >> np.uint64(32), block.shape)
-    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & m32, (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & m32
-        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    w = np.stack([c0, c1, c2, c3], axis=-1)
-    u = ((w.astype(np.float32).astype(np.float64) + 1.0) * 2.0 ** -32).astype(np.float32).astype(np.float64)
-    z = np.empty(u.shape, np.float64)
-    for a, b in ((0, 1), (2, 3)):
-        r, th = np.sqrt(-2.0 * np.log(u[..., a])), 2.0 * np.pi * u[..., b]
-        z[..., a], z[..., b] = r * np.cos(th), r * np.sin(th)
-    return z.astype(np.float32)
+    """-> [steps, batch, 4] float32: the target noise that a call without `noise` draws, restated on the host
+    (offpolicy.keyed_noise; ``noise_out`` of td3_update has the device's values).  `stream`: the Philox stream in place of 6 (sac.py
+    draws on 7)"""
+    return offpolicy.keyed_noise(seed, t0, steps, batch, stream)
 
 
 # ---------------------------------------------------------------------------------------------------- the nets
-class TD3Policy:
+class TD3Policy(offpolicy.Nets):
     """the six nets of TD3 in the policy's (in, out) layout, as lists of six tensors: ``actor``, ``q1``, ``q2`` and ``actor_target``,
     ``q1_target``, ``q2_target``; Adam's moments of the three online nets (``m``, ``v``: {"actor": [...], "q1": [...], "q2": [...]}),
     the update count ``steps`` and the actor's own step count ``actor_steps``.  SB2's initialisation drawn from `seed`:
     Glorot-uniform weights, zero biases, the targets equal to the online nets.  `weights`: {"actor": {w0 ..}, "q1": {..}, "q2": {..}
     and optionally the three targets}.  `dtype`: "float32" (the device path needs it) or "float64" (torch_td3_update alone)."""
 
+    NET_NAMES, ONLINE_NAMES, LIB = NET_NAMES, ONLINE_NAMES, ("td3", "qstd_workspace_bytes")
+    shapes_of, load = staticmethod(shapes_of), staticmethod(lambda: load_td3())
+
     def __init__(self, seed=0, device="cuda", weights=None, dtype="float32"):
-        import torch
-        self.device, self.dtype = torch.device(device), getattr(torch, dtype)
-        if weights is None:
-            rng = np.random.default_rng(int(seed))
-            weights = {}
-            for name in ONLINE_NAMES:
-                W = {}
-                for k, shape in zip(NET_KEYS, shapes_of(name)):
-                    if len(shape) == 1:
-                        W[k] = np.zeros(shape, np.float32)
-                    else:
-                        lim = math.sqrt(6.0 / (shape[0] + shape[1]))
-                        W[k] = rng.uniform(-lim, lim, shape).astype(np.float32)
-                weights[name] = W
-        for name in NET_NAMES:
-            src = weights.get(name, weights[name.split("_")[0]])
-            ws = []
-            for k, shape in zip(NET_KEYS, shapes_of(name)):
-                w = np.ascontiguousarray(src[k])
-                if w.shape != shape:
-                    raise ValueError("%s %s must be of shape %s, got %s" % (name, k, shape, w.shape))
-                ws.append(torch.as_tensor(w.copy()).to(self.dtype).to(self.device))
-            setattr(self, name, ws)
-        self.device = self.actor[0].device
+        self.init_nets(seed, device, weights, dtype)
         self.reset_optimizer()
-        self._workspace, self._images = None, {}
 
     def reset_optimizer(self):
         """forget Adam's moments and both step counts"""
-        import torch
-        self.m = {k: [torch.zeros_like(w) for w in getattr(self, k)] for k in ONLINE_NAMES}
-        self.v = {k: [torch.zeros_like(w) for w in getattr(self, k)] for k in ONLINE_NAMES}
+        self.zero_moments()
         self.steps, self.actor_steps = 0, 0
-
-    def nets(self):
-        return [getattr(self, name) for name in NET_NAMES]
-
-    def updated(self):
-        """an update wrote the weights in place: every cached image of them is dropped"""
-        self._images = {}
 
     def predict(self, obs):
         """obs [N,12] -> tanh actions [N,4] of the online actor (plain torch)"""
@@ -178,34 +114,11 @@ class TD3Policy:
             self._images["actor"] = {k: w.detach().cpu().numpy().copy() for k, w in zip(NET_KEYS, self.actor)}   # (a host tensor's numpy() aliases it)
         return self._images["actor"]
 
-    def save_npz(self, path):
-        arrays = {}
-        for name in NET_NAMES:
-            arrays.update({"%s_%s" % (name, k): w.detach().cpu().numpy() for k, w in zip(NET_KEYS, getattr(self, name))})
-        for name in ONLINE_NAMES:
-            arrays.update({"m_%s_%s" % (name, k): t.cpu().numpy() for k, t in zip(NET_KEYS, self.m[name])})
-            arrays.update({"v_%s_%s" % (name, k): t.cpu().numpy() for k, t in zip(NET_KEYS, self.v[name])})
-        np.savez(path, steps=self.steps, actor_steps=self.actor_steps, **arrays)
+    def npz_state(self):
+        return {"steps": self.steps, "actor_steps": self.actor_steps}
 
-    @classmethod
-    def from_npz(cls, path, device="cuda"):
-        import torch
-        with np.load(path, allow_pickle=False) as z:
-            dtype = str(z["actor_w0"].dtype)
-            p = cls(device=device, weights={name: {k: z["%s_%s" % (name, k)] for k in NET_KEYS} for name in NET_NAMES}, dtype=dtype)
-            for name in ONLINE_NAMES:
-                p.m[name] = [torch.as_tensor(z["m_%s_%s" % (name, k)].copy()).to(p.device) for k in NET_KEYS]
-                p.v[name] = [torch.as_tensor(z["v_%s_%s" % (name, k)].copy()).to(p.device) for k in NET_KEYS]
-            p.steps, p.actor_steps = int(z["steps"]), int(z["actor_steps"])
-        return p
-
-    def workspace(self):
-        """the device workspace of qstd_update, allocated once"""
-        if self._workspace is None:
-            nbytes = C.c_size_t(0)
-            _lib.side_call("td3", load_td3(), "qstd_workspace_bytes", C.byref(nbytes))
-            self._workspace = _lib.new_tensor(self.device, (int(nbytes.value),), "uint8")
-        return self._workspace
+    def set_npz_state(self, z):
+        self.steps, self.actor_steps = int(z["steps"]), int(z["actor_steps"])
 
 
 def reset_td3_optimizer(policy):
@@ -233,31 +146,17 @@ class NormalActionNoise:
 
 # ---------------------------------------------------------------------------------------------------- the update
 def _update_args(policy, replay, indices, counts, hyper, noise, need_device):
-    import torch
     dev = policy.device
     dtype = str(policy.dtype).split(".")[-1]
     if need_device and (dev.type != "cuda" or dtype != "float32"):
         raise _lib.QuadsimError("td3_update needs a float32 policy on a HIP device, it is %s on %s; torch_td3_update is the host path"
                                 % (dtype, dev))
-    for name in NET_NAMES:
-        for k, w, shape in zip(NET_KEYS, getattr(policy, name), shapes_of(name)):
-            _lib.check_tensor("%s %s" % (name, k), w, dtype, shape, dev)
-    obs0, act, rew, obs1, done = replay if isinstance(replay, (tuple, list)) else replay.tensors()
-    n = int(obs0.shape[0])
-    for name, t, shape in (("obs0", obs0, (n, 12)), ("act", act, (n, 4)), ("rew", rew, (n,)), ("obs1", obs1, (n, 12)), ("done", done, (n,))):
-        _lib.check_tensor(name, t, "float32", shape, dev)
-    indices = torch.as_tensor(indices)
-    if indices.dtype != torch.int32 or indices.dim() != 2 or indices.device.type != "cpu":
-        raise ValueError("indices must be a host int32 tensor [steps, batch]")
-    if counts is not None:
-        counts = torch.as_tensor(counts)
-        if counts.dtype != torch.int32 or counts.device.type != "cpu":
-            raise ValueError("counts must be a host int32 tensor [steps]")
+    data, n, indices, counts = offpolicy.update_tensors(policy, replay, indices, counts, dtype)
     args = check_td3_args(n, indices.shape[0], indices.shape[1], t0=policy.steps, actor_t0=policy.actor_steps,
                           counts=None if counts is None else counts.numpy(), indices=indices.numpy(), **hyper)
     if noise is not None:
         _lib.check_tensor("noise", noise, "float32", (args[1], args[2], 4), dev)
-    return (obs0, act, rew, obs1, done), indices.contiguous(), counts, args
+    return data, indices.contiguous(), counts, args
 
 
 def td3_update(policy, replay, indices, counts=None, gamma=0.99, tau=5.0e-3, actor_lr=3.0e-4, critic_lr=3.0e-4, policy_delay=2,

@@ -1,6 +1,6 @@
-"""What the tests of the eight side libraries (quadsim_amd._lib.SIDE) have in common.  For the CPU tests, tests/test_*_cpu.py: each
+"""What the tests of the ten side libraries (quadsim_amd._lib.SIDE) have in common.  For the CPU tests, tests/test_*_cpu.py: each
 generic check of a library's ABI as a function of its table key and of the data the caller states -- the header's names against the
-exports, the entry's files against every other entry's, the kernel-name prefixes against the bytes of all nine libraries, the C99
+exports, the entry's files against every other entry's, the kernel-name prefixes against the bytes of all eleven libraries, the C99
 caller, the census of the code object against the rows of a tests/*_matrix.py.  For the trainers' GPU tests: the guard buffer.
 A helper module, not a conftest: imported where it is needed."""
 import ctypes as C
@@ -17,7 +17,7 @@ import kernel_notes
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # what the name of a file says when it belongs to that library alone: the fragments and the source, the public header
 NAMES = {"dyn": ("dynplan", "quadsim_dyn.h"), "dynmppi": ("dynmppi", "dyn_mppi"), "dynfit": ("dynfit", "dyn_fit"), "bc": ("bc",),
-         "ppo": ("ppo",), "gail": ("gail",), "trpo": ("trpo",), "ddpg": ("ddpg",)}
+         "ppo": ("ppo",), "gail": ("gail",), "trpo": ("trpo",), "ddpg": ("ddpg",), "td3": ("td3",), "sac": ("sac",)}
 # the one pair that shares files of such a name on purpose: MPPI over the learned net is built from the shooting planner's fragments
 SHARED = {("dyn", "dynmppi"): ("dynplan_host.hpp", "dynplan_image.hpp", "dynplan_kernels.hpp")}
 
@@ -55,7 +55,7 @@ def check_entry(key, fragments, source):
     assert [os.path.basename(s) for s in e["sources"]] == [source] and all(os.path.exists(h) for h in e["headers"] + e["sources"]), key
     assert all(name in _lib.SIDE_POINTERS for name in e["signatures"])
     others = {k: o for k, o in _lib.SIDE.items() if k != key}
-    assert len(others) == 7
+    assert len(others) == 9
     theirs = [(k, os.path.basename(h)) for k, o in others.items() for h in o["headers"] + o["sources"]]
     theirs = [f for k, f in theirs if f not in SHARED.get((key, k), ())] + [os.path.basename(h) for h in _lib.HEADERS + _lib.SOURCES]
     assert not [f for f in theirs if any(word in f for word in NAMES[key])], key

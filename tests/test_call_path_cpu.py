@@ -48,11 +48,11 @@ def test_signature_table_matches_the_header():
 
 
 def test_side_signature_tables_match_their_headers():
-    """the same for the eight side libraries: the prototypes of each header are exactly the table's entries, with the count and
+    """the same for the ten side libraries: the prototypes of each header are exactly the table's entries, with the count and
     kind (pointer, int32, int64, uint64, float, double) of every parameter and the kind of the result, and SIDE_POINTERS holds
     the positions of the pointers"""
     from quadsim_amd import _lib
-    assert list(_lib.SIDE) == ["dyn", "dynmppi", "dynfit", "bc", "ppo", "gail", "trpo", "ddpg"]
+    assert list(_lib.SIDE) == ["dyn", "dynmppi", "dynfit", "bc", "ppo", "gail", "trpo", "ddpg", "td3", "sac"]
     counts = {}
     for key, e in _lib.SIDE.items():
         protos = _header_prototypes(e["header"], e["prefix"])
@@ -63,13 +63,13 @@ def test_side_signature_tables_match_their_headers():
             assert _lib.SIDE_POINTERS[name] == tuple(i for i, k in enumerate(protos[name][1]) if k == "ptr"), name
         assert protos[e["prefix"] + "last_error"] == ("ptr", []) and protos[e["prefix"] + "version"] == ("int32", [])
         counts[key] = len(protos)
-    assert counts == {"dyn": 6, "dynmppi": 4, "dynfit": 3, "bc": 5, "ppo": 5, "gail": 5, "trpo": 6, "ddpg": 4}
+    assert counts == {"dyn": 6, "dynmppi": 4, "dynfit": 3, "bc": 5, "ppo": 5, "gail": 5, "trpo": 6, "ddpg": 4, "td3": 4, "sac": 5}
     assert _header_prototypes("quadsim_bc.h", "qsbc_")["qsbc_loss_blocks"] == ("int64", ["int64"])
 
 
 def test_each_side_library_keeps_its_own_error_text():
     """a refused call (refused before the device is touched: nothing is launched) writes the error text of its own library and
-    leaves the other seven as they were"""
+    leaves the other nine as they were"""
     from quadsim_amd import _lib
     _lib.build_library()
     libs = {key: _lib.side_load(key) for key in _lib.SIDE}
@@ -77,6 +77,7 @@ def test_each_side_library_keeps_its_own_error_text():
     x = C.addressof(six)                                       # a non-NULL pointer that no refused call dereferences
     net = _lib.QsdfNet(12345)                                  # a struct_size no other test uses
     nets, replay, hyper = _lib.QsddNets(12345), _lib.QsddReplay(), _lib.QsddHyper()
+    tnets, thyper, snets, shyper = _lib.QstdNets(12345), _lib.QstdHyper(), _lib.QssNets(12345), _lib.QssHyper()
     refusals = {
         "dyn": (lambda lib: lib.qsd_plan_workspace_bytes(-12345, 200, C.byref(nbytes)), b"n must be >= 1, got -12345"),
         "dynmppi": (lambda lib: lib.qsdm_workspace_bytes(1, -12345, 200, C.byref(nbytes)), b"horizon must be in [1, 1024], got -12345"),
@@ -88,6 +89,12 @@ def test_each_side_library_keeps_its_own_error_text():
         "trpo": (lambda lib: lib.qst_workspace_bytes(-54321, 7, C.byref(nbytes)), b"n must be in [1, 2^31), got -54321"),
         "ddpg": (lambda lib: lib.qsdd_update(C.byref(nets), C.byref(replay), x, None, 100, 10, C.byref(hyper), 0, x, 0, x, None, None),
                  b"QsddNets.struct_size is 12345, expected %d" % C.sizeof(_lib.QsddNets)),
+        "td3": (lambda lib: lib.qstd_update(C.byref(tnets), C.byref(replay), x, None, 100, 10, C.byref(thyper), 0, 0, None, 0, None, x, 0, x,
+                                            None, None),
+                b"QstdNets.struct_size is 12345, expected %d" % C.sizeof(_lib.QstdNets)),
+        "sac": (lambda lib: lib.qss_update(C.byref(snets), C.byref(replay), x, None, 100, 10, C.byref(shyper), 0, None, 0, None, x, 0, x,
+                                           None, None, None),
+                b"QssNets.struct_size is 12345, expected %d" % C.sizeof(_lib.QssNets)),
     }
 
     def texts():
@@ -100,7 +107,7 @@ def test_each_side_library_keeps_its_own_error_text():
         assert after.pop(key) == text
         del before[key]
         assert after == before, key
-    assert len(set(texts().values())) == 8
+    assert len(set(texts().values())) == 10
 
 
 # ---------------------------------------------------------------- the shipped _call on a fake library

@@ -42,7 +42,8 @@ def test_table_entry_names_its_own_files():
     import quadsim_amd as qa
     from quadsim_amd import _lib, ddpg
     assert ddpg.DDPG_EXPORTS is _lib.SIDE["ddpg"]["exports"]
-    side_cases.check_entry("ddpg", ["ddpg_kernels.hpp", "quadsim_ddpg.h", "quadsim_device.hpp", "side_host.hpp", "train_pieces.hpp"], "ddpg.hip")
+    side_cases.check_entry("ddpg", ["ddpg_kernels.hpp", "quadsim_ddpg.h", "quadsim_device.hpp", "side_host.hpp", "side_offpolicy.hpp",
+                                     "train_offpolicy.hpp", "train_pieces.hpp"], "ddpg.hip")
     for name in ("DDPG", "DDPGPolicy", "ReplayBuffer", "OUNoise", "replay_schedule", "ddpg_update", "torch_ddpg_update", "check_ddpg_args"):
         assert getattr(qa, name) is getattr(ddpg, name) and name in qa.__all__
     assert ddpg.DDPG_MAX_STEPS == 4096 and ddpg.DDPG_MAX_BATCH == 256

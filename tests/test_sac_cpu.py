@@ -1,7 +1,7 @@
 """-m "not gpu": everything of SAC on the device that needs no device.  include/quadsim_sac.h is plain C99 and every symbol it
-declares is exported by libquadsim_sac.so; the entry of _lib.SIDE_LATER matches the header's prototypes and leaves SIDE, SIDE_MORE and
-ALL_SIDE as they were (the checks that tests/side_cases.py keys on _lib.SIDE are restated here for the third table); every refusal
-the header promises happens before anything is launched, and check_sac_args mirrors it; tests/sac_matrix.py has exactly one row per
+declares is exported by libquadsim_sac.so; the entry of _lib.SIDE matches the header's prototypes (tests/side_cases.py has the
+checks every side library shares); every refusal the header promises happens before anything is launched, and check_sac_args
+mirrors it; tests/sac_matrix.py has exactly one row per
 kernel of the code object, none uses scratch and each fits the compute unit's LDS; tests/sac_ref.py is checked against torch's float64
 autograd (quadsim_amd.torch_sac_update, which it shares no code with), its fixtures lie off every ReLU edge and off the clamp's ends
 with |u| <= 3; the float64 reference meets the learning condition the device is held to; and the recorded instruction diff of the
@@ -31,7 +31,7 @@ EXPECTED = ["qss_last_error", "qss_math", "qss_update", "qss_version", "qss_work
 
 def entry():
     from quadsim_amd import _lib
-    return _lib.side_entry("sac")
+    return _lib.SIDE["sac"]
 
 
 @pytest.fixture(scope="module")
@@ -63,51 +63,34 @@ def test_header_table_and_exports_are_the_same_names(lib):
         assert _lib.SIDE_POINTERS[name] == tuple(i for i, k in enumerate(protos[name][1]) if k == "ptr"), name
     assert protos["qss_last_error"] == ("ptr", []) and protos["qss_version"] == ("int32", []) and len(protos["qss_update"][1]) == 17
     assert protos["qss_math"] == ("int32", ["int32", "ptr", "ptr", "int64", "ptr"])
-    out = subprocess.run(["nm", "-D", "--defined-only", e["path"]], capture_output=True, text=True, check=True).stdout
-    assert sorted(w for w in out.split() if w.startswith(e["prefix"])) == EXPECTED
-    assert not [n for n in EXPECTED if not hasattr(lib, n)] and lib.qss_version() == 1
+    side_cases.check_exports("sac", lib, EXPECTED)
 
 
-def test_third_table_leaves_the_other_two_as_they_were():
+def test_table_entry_names_its_own_files():
     import quadsim_amd as qa
     from quadsim_amd import _lib, sac
     e = entry()
-    assert list(_lib.SIDE) == ["dyn", "dynmppi", "dynfit", "bc", "ppo", "gail", "trpo", "ddpg"]
-    assert list(_lib.SIDE_MORE) == ["td3"] and list(_lib.ALL_SIDE) == list(_lib.SIDE) + ["td3"]
-    assert list(_lib.SIDE_LATER) == ["sac"] and "sac" not in _lib.ALL_SIDE and list(_lib.EVERY_SIDE) == list(_lib.ALL_SIDE) + ["sac"]
-    assert all(_lib.EVERY_SIDE[k] is o for t in (_lib.SIDE, _lib.SIDE_MORE, _lib.SIDE_LATER) for k, o in t.items())
-    assert sorted(e) == sorted(_lib.SIDE_MORE["td3"])                           # the same shape of entry, derived fields included
+    assert list(_lib.SIDE) == ["dyn", "dynmppi", "dynfit", "bc", "ppo", "gail", "trpo", "ddpg", "td3", "sac"]         # build order
+    assert sorted(e) == sorted(_lib.SIDE["td3"])                                # the same shape of entry, derived fields included
     assert sac.SAC_EXPORTS is e["exports"]
-    assert os.path.basename(e["path"]) == e["file"] == "libquadsim_sac.so" and e["prefix"] == "qss_" and e["kernels"] == b"k_sac_"
-    assert sorted(os.path.basename(h) for h in e["headers"]) == ["quadsim_device.hpp", "quadsim_sac.h", "sac_kernels.hpp", "side_host.hpp",
-                                                                  "train_pieces.hpp"]
-    assert [os.path.basename(s) for s in e["sources"]] == ["sac.hip"] and all(os.path.exists(h) for h in e["headers"] + e["sources"])
-    # no file of the main library or of another entry carries this library's name, and the main library is not rebuilt for its fragment
-    theirs = [os.path.basename(h) for o in _lib.ALL_SIDE.values() for h in o["headers"] + o["sources"]] + [os.path.basename(h) for h in _lib.HEADERS + _lib.SOURCES]
-    assert not [f for f in theirs if "sac" in f]
-    assert e["env"] == "QUADSIM_SAC_LIB"
-    env = dict(os.environ, QUADSIM_SAC_LIB="/somewhere/else.so")
-    got = subprocess.run([sys.executable, "-c", "from quadsim_amd import _lib; print(_lib.side_entry('sac')['path'])"], cwd=ROOT, env=env,
-                         capture_output=True, text=True, check=True).stdout.strip()
-    assert got == "/somewhere/else.so"
+    assert e["prefix"] == "qss_" and e["kernels"] == b"k_sac_"
+    # (with it: no file of the main library or of another entry carries this library's name, so the main library is not rebuilt for
+    # its fragment)
+    side_cases.check_entry("sac", ["quadsim_device.hpp", "quadsim_sac.h", "sac_kernels.hpp", "side_host.hpp", "side_offpolicy.hpp",
+                                   "train_offpolicy.hpp", "train_pieces.hpp"], "sac.hip")
     for name in ("SAC", "SACPolicy", "sac_update", "torch_sac_update", "check_sac_args", "reset_sac_optimizer"):
         assert getattr(qa, name) is getattr(sac, name) and name in qa.__all__
     assert sac.SAC_MAX_STEPS == 4096 and sac.SAC_MAX_BATCH == 256 and sac.SAC_NOISE_STREAM == sr.NOISE_STREAM == 7
     assert sac.ReplayBuffer is qa.ReplayBuffer and sac.replay_schedule is qa.replay_schedule
     assert sac.collect_and_train is qa.ddpg.collect_and_train                   # one collection loop for the three off-policy trainers
     text = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert "_lib.EVERY_SIDE.items()" in text
+    assert "_lib.SIDE.items()" in text
 
 
 def test_no_other_library_holds_its_kernels(lib):
-    from quadsim_amd import _lib
-    e = entry()
-    blob = open(e["path"], "rb").read()
+    blob = open(entry()["path"], "rb").read()
     assert b"k_sac_step" in blob and b"k_sac_copy" in blob and b"k_sac_math" in blob
-    for k, o in _lib.ALL_SIDE.items():
-        assert e["kernels"] not in open(o["path"], "rb").read(), k
-        assert o["kernels"] not in blob, k
-    assert e["kernels"] not in open(_lib.LIB_PATH, "rb").read()
+    side_cases.check_no_foreign_kernels("sac")
 
 
 def test_structs_and_workspace_match_the_header(lib):

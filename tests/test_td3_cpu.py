@@ -1,6 +1,6 @@
 """-m "not gpu": everything of TD3 on the device that needs no device.  include/quadsim_td3.h is plain C99 and every symbol it
-declares is exported by libquadsim_td3.so; the entry of _lib.SIDE_MORE matches the header's prototypes (the checks that
-tests/side_cases.py keys on _lib.SIDE are restated here for the second table); every refusal the header promises happens before
+declares is exported by libquadsim_td3.so; the entry of _lib.SIDE matches the header's prototypes (tests/side_cases.py has the
+checks every side library shares); every refusal the header promises happens before
 anything is launched, and check_td3_args mirrors it; tests/td3_matrix.py has exactly one row per kernel of the code object, none uses
 scratch and each fits the compute unit's LDS; the schedule of actor steps; tests/td3_ref.py is checked against torch's float64
 autograd (quadsim_amd.torch_td3_update, which it shares no code with), its fixtures lie on every edge of the target value and off
@@ -29,7 +29,7 @@ EXPECTED = ["qstd_last_error", "qstd_update", "qstd_version", "qstd_workspace_by
 
 def entry():
     from quadsim_amd import _lib
-    return _lib.side_entry("td3")
+    return _lib.SIDE["td3"]
 
 
 @pytest.fixture(scope="module")
@@ -60,29 +60,20 @@ def test_header_table_and_exports_are_the_same_names(lib):
         assert (call_path._ctype_kind(result), [call_path._ctype_kind(t) for t in args]) == protos[name], name
         assert _lib.SIDE_POINTERS[name] == tuple(i for i, k in enumerate(protos[name][1]) if k == "ptr"), name
     assert protos["qstd_last_error"] == ("ptr", []) and protos["qstd_version"] == ("int32", []) and len(protos["qstd_update"][1]) == 17
-    out = subprocess.run(["nm", "-D", "--defined-only", e["path"]], capture_output=True, text=True, check=True).stdout
-    assert sorted(w for w in out.split() if w.startswith(e["prefix"])) == EXPECTED
-    assert not [n for n in EXPECTED if not hasattr(lib, n)] and lib.qstd_version() == 1
+    side_cases.check_exports("td3", lib, EXPECTED)
 
 
 def test_table_entry_names_its_own_files():
     import quadsim_amd as qa
     from quadsim_amd import _lib, td3
     e = entry()
-    assert list(_lib.SIDE_MORE) == ["td3"] and "td3" not in _lib.SIDE and list(_lib.ALL_SIDE) == list(_lib.SIDE) + ["td3"]
+    assert list(_lib.SIDE) == ["dyn", "dynmppi", "dynfit", "bc", "ppo", "gail", "trpo", "ddpg", "td3", "sac"]         # build order
     assert td3.TD3_EXPORTS is e["exports"]
-    assert os.path.basename(e["path"]) == e["file"] == "libquadsim_td3.so" and e["prefix"] == "qstd_" and e["kernels"] == b"k_td3_"
-    assert sorted(os.path.basename(h) for h in e["headers"]) == ["quadsim_device.hpp", "quadsim_td3.h", "side_host.hpp", "td3_kernels.hpp",
-                                                                  "train_pieces.hpp"]
-    assert [os.path.basename(s) for s in e["sources"]] == ["td3.hip"] and all(os.path.exists(h) for h in e["headers"] + e["sources"])
-    # no file of the main library or of another entry carries this library's name, and the main library is not rebuilt for its fragment
-    theirs = [os.path.basename(h) for o in _lib.SIDE.values() for h in o["headers"] + o["sources"]] + [os.path.basename(h) for h in _lib.HEADERS + _lib.SOURCES]
-    assert not [f for f in theirs if "td3" in f]
-    assert e["env"] == "QUADSIM_TD3_LIB"
-    env = dict(os.environ, QUADSIM_TD3_LIB="/somewhere/else.so")
-    got = subprocess.run([sys.executable, "-c", "from quadsim_amd import _lib; print(_lib.side_entry('td3')['path'])"], cwd=ROOT, env=env,
-                         capture_output=True, text=True, check=True).stdout.strip()
-    assert got == "/somewhere/else.so"
+    assert e["prefix"] == "qstd_" and e["kernels"] == b"k_td3_"
+    # (with it: no file of the main library or of another entry carries this library's name, so the main library is not rebuilt for
+    # its fragment)
+    side_cases.check_entry("td3", ["quadsim_device.hpp", "quadsim_td3.h", "side_host.hpp", "side_offpolicy.hpp", "td3_kernels.hpp",
+                                   "train_offpolicy.hpp", "train_pieces.hpp"], "td3.hip")
     for name in ("TD3", "TD3Policy", "NormalActionNoise", "td3_update", "torch_td3_update", "check_td3_args", "reset_td3_optimizer"):
         assert getattr(qa, name) is getattr(td3, name) and name in qa.__all__
     assert td3.TD3_MAX_STEPS == 4096 and td3.TD3_MAX_BATCH == 256 and td3.TD3_MAX_DELAY == 65536
@@ -91,14 +82,9 @@ def test_table_entry_names_its_own_files():
 
 
 def test_no_other_library_holds_its_kernels(lib):
-    from quadsim_amd import _lib
-    e = entry()
-    blob = open(e["path"], "rb").read()
+    blob = open(entry()["path"], "rb").read()
     assert b"k_td3_step" in blob and b"k_td3_copy" in blob
-    for k, o in _lib.SIDE.items():
-        assert e["kernels"] not in open(o["path"], "rb").read(), k
-        assert o["kernels"] not in blob, k
-    assert e["kernels"] not in open(_lib.LIB_PATH, "rb").read()
+    side_cases.check_no_foreign_kernels("td3")
 
 
 def test_structs_and_workspace_match_the_header(lib):

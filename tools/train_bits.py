@@ -5,8 +5,9 @@
 
 One line per case: the number of its arrays and one sha256 over their records (name, dtype, shape, sha256 of the bytes); with
 --arrays one line per array, to find which one moved.  One process per build; QUADSIM_BC_LIB, QUADSIM_PPO_LIB, QUADSIM_TRPO_LIB,
-QUADSIM_DDPG_LIB, QUADSIM_GAIL_LIB and QUADSIM_DYNFIT_LIB pick it.  A refactor of csrc/train_pieces.hpp or of a trainer's kernels leaves the two files byte-equal; any difference is a behaviour
-change.  Only public wrapper names are used, so the same file runs from a checkout of an older commit.
+QUADSIM_DDPG_LIB, QUADSIM_TD3_LIB, QUADSIM_SAC_LIB, QUADSIM_GAIL_LIB and QUADSIM_DYNFIT_LIB pick it.  A refactor of
+csrc/train_pieces.hpp, of csrc/train_offpolicy.hpp or of a trainer's kernels leaves the two files byte-equal; any difference is a
+behaviour change.  Only public wrapper names are used, so the same file runs from a checkout of an older commit.
 
 Every tower trainer (bc_fit, ppo2_update, trpo_vf_fit, ddpg_update; trpo_policy_step has no steps): five steps to move Adam's
 moments and step count off zero, then the three hashed steps from t0 = 5 -- the bias correction across steps, k_bc_fit's
@@ -14,7 +15,11 @@ prefetch of the next step's chunk, both of DDPG's buffers.  Shapes: batch 17 (on
 batch 40 (three chunks) with counts 33, 40, 17 where the entry point has counts.  Each with and without the gradients, and with
 one NaN in a row that the schedule touches.  PPO2 and TRPO also at 300 rows in 8 slices of 3 chunks: 19 chunks, so the last slice
 is empty.  TRPO's policy step with the full trace: the clean roll-out's line search accepts a candidate, the NaN one's accepts
-none (asserted here).  One small fit each of GAIL's discriminator and of the learned dynamics net."""
+none (asserted here).  One small fit each of GAIL's discriminator and of the learned dynamics net.
+
+TD3 and SAC under the same recipe, at batch 1, 16 (one full chunk), 17, 40 with counts and 256, each with the caller's noise and with
+keyed noise handed back.  TD3 at policy_delay 1 (every hashed step an actor update) and 2 (from t0 = 5 the steps are critic-only,
+actor, critic-only: the last step is each kind once); SAC with the learned and with the fixed temperature, the full trace on."""
 import hashlib, json, os, sys  # noqa: E401
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
@@ -51,7 +56,7 @@ def put_result(key, res):
 def schedule(seed, steps, batch, n=ROWS):
     """[steps, batch] int32 on the host; row 3 of the data (the one that carries the NaN) is in every step"""
     idx = torch.randint(0, n, (steps, batch), generator=torch.Generator().manual_seed(seed), dtype=torch.int32)
-    idx[:, 1] = 3
+    idx[:, min(1, batch - 1)] = 3
     return idx
 
 
@@ -152,6 +157,56 @@ def ddpg_cases():
             put(key + "/v", pol.v["actor"] + pol.v["critic"])
 
 
+def offpolicy_shapes():
+    return (("b1", 1, None), ("b16", 16, None)) + shapes(True) + (("b256", 256, None),)
+
+
+def replay_of(nan):
+    ro = rollout(ROWS, nan)
+    g = torch.Generator().manual_seed(13)
+    obs1 = ((torch.rand(ROWS, 12, generator=g) - 0.5) * 4.0).to(DEV)
+    done = (torch.rand(ROWS, generator=g) < 0.2).to(torch.float32).to(DEV)
+    return (ro["obs"], torch.tanh(ro["actions"]).contiguous(), ro["returns"], obs1, done)
+
+
+def noise_args(fed, steps, batch, seed):
+    """the caller's normals, or keyed draws that the call hands back"""
+    if fed:
+        return dict(noise=torch.randn(steps, batch, 4, generator=torch.Generator().manual_seed(seed)).to(DEV))
+    return dict(seed=seed, return_noise=True)
+
+
+def td3_cases():
+    for name, batch, counts in offpolicy_shapes():
+        for tag, grads, nan in variants():
+            for delay in (1, 2):
+                for fed in (True, False):
+                    key = "td3_update/%s/%s/delay%d/%s" % (name, tag, delay, "fed" if fed else "keyed")
+                    pol, replay = qa.TD3Policy(seed=8, device=DEV), replay_of(nan)
+                    qa.td3_update(pol, replay, schedule(1, WARM, batch), policy_delay=delay, **noise_args(fed, WARM, batch, 21))
+                    put_result(key, qa.td3_update(pol, replay, schedule(2, STEPS, batch), counts, policy_delay=delay, return_grads=grads,
+                                                  **noise_args(fed, STEPS, batch, 22)))
+                    put(key + "/w", [w for ws in pol.nets() for w in ws])
+                    put(key + "/m", [t for k in ("actor", "q1", "q2") for t in pol.m[k]])
+                    put(key + "/v", [t for k in ("actor", "q1", "q2") for t in pol.v[k]])
+
+
+def sac_cases():
+    for name, batch, counts in offpolicy_shapes():
+        for tag, grads, nan in variants():
+            for auto in (True, False):
+                for fed in (True, False):
+                    key = "sac_update/%s/%s/%s/%s" % (name, tag, "auto" if auto else "fixed", "fed" if fed else "keyed")
+                    pol, replay = qa.SACPolicy(seed=9, device=DEV, ent_coef=0.5), replay_of(nan)
+                    qa.sac_update(pol, replay, schedule(1, WARM, batch), auto_alpha=auto, **noise_args(fed, WARM, batch, 23))
+                    put_result(key, qa.sac_update(pol, replay, schedule(2, STEPS, batch), counts, auto_alpha=auto, return_grads=grads,
+                                                  return_trace=True, **noise_args(fed, STEPS, batch, 24)))
+                    put(key + "/w", [w for ws in pol.nets() for w in ws])
+                    put(key + "/m", [t for k in ("actor", "q1", "q2", "v") for t in pol.m[k]])
+                    put(key + "/v", [t for k in ("actor", "q1", "q2", "v") for t in pol.v_[k]])
+                    put(key + "/alpha_state", pol.alpha_state)
+
+
 class Expert:
     pass
 
@@ -179,6 +234,8 @@ if __name__ == "__main__":
     ppo_cases()
     trpo_cases()
     ddpg_cases()
+    td3_cases()
+    sac_cases()
     other_fits()
     torch.cuda.synchronize()
     if "--arrays" not in sys.argv[1:]:
